@@ -1,14 +1,17 @@
 #!/usr/bin/env python
 """bench.py -- 512x512 summary images/sec for one UNet2DS train step (fwd + BCE + bwd + Adam) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: bench.py starts its own N rank processes)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                               (N > 1: bench.py starts its own N rank processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 Workload = BASELINE.json configs[2] per GPU (batch 16 of 512x512, fp32), i.e. configs[3] (global batch 128) at
 8 GPUs: weak scaling, one process per GPU, gradients all-reduced over RCCL.  Inputs are synthetic
-(x ~ N(0,1), y ~ Bernoulli(0.126)), random-init weights, resident in HBM before the timed region.
-Rank 0 prints ONE JSON line: metric/value (whole-job images/s) + `roofline` for the dominant kernel
-(measured live with HIP events on the launch stream) + `cpu_baseline` (oracle port timed on the host cores).
+(x ~ N(0,1), y ~ Bernoulli(0.126)), seeded random-init weights, resident in HBM before the timed region.
+Rank 0 prints ONE JSON line: metric/value (whole-job images/s) and ms_per_step of the K timed steps.  A plain run does
+nothing else; --full adds what takes runs of its own: `roofline` for the dominant kernel (measured live with HIP events
+on the launch stream, in instrumented steps after the timed region), the gradient all-reduce figures and `cpu_baseline`
+(oracle port timed on the host cores).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -30,6 +33,22 @@ NFB = 32
 
 PEAK_FP16_MFMA_TFLOPS = 2500.0    # same guide: dense fp16/bf16 matrix peak (the 2:1-sparse figure is not used)
 DTYPE_LABEL = {'f16x3': 'f32 (fp16x3 split, fp32 accumulate)', 'f32': 'f32'}
+DUMP_MAX_BYTES = 60 * 1000 * 1000     # --dump-outputs: array data in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 kept, everything else as float32.  Arrays that together exceed
+    DUMP_MAX_BYTES are each replaced by a fixed, seeded sample of their flattened elements (for the same shapes, the same
+    positions on every run), so that two builds of the project can be compared output for output."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_MAX_BYTES:
+            keep = a.size * DUMP_MAX_BYTES // total
+            a = a.ravel()[np.sort(np.random.RandomState(20240).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def synthetic_batch(N, Hh, Ww, seed_x=865, seed_y=866, pos_rate=0.126):
@@ -277,8 +296,9 @@ def bench_infer(args, model, xd, rank, world):
     import torch
     from deep_calcium_amd import parallel
     eng, B = model.engine, xd.shape[0]
-    timer = KernelTimer(eng.L)
-    eng.L = timer
+    if args.full:
+        timer = KernelTimer(eng.L)
+        eng.L = timer
     for _ in range(args.warmup):
         eng.forward_infer(xd)
     torch.cuda.synchronize()
@@ -286,33 +306,35 @@ def bench_infer(args, model, xd, rank, world):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        eng.forward_infer(xd)
+        p = eng.forward_infer(xd)
     torch.cuda.synchronize()
     parallel.barrier()
     dt = time.perf_counter() - t0
-    timer.enabled = True
-    eng.use_tapes = False                 # the instrumented forwards issue every launch from Python, through the timer proxy
-    for _ in range(3):
-        eng.forward_infer(xd)
-    torch.cuda.synchronize()
-    n_launch, k_ms, k_flops = timer.summarize()
-    if rank != 0:
-        return
-    achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
-    _, peak, mpf = KernelTimer.KERNELS[eng.mfma]
-    kname = timer.symbol
-    emit_json(json.dumps({
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'probabilities': p.cpu().numpy()})
+    line = {
         'metric': '512x512 summary images/sec (forward only)', 'value': round(world * B * args.steps / dt, 2),
         'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': DTYPE_LABEL[eng.mfma], 'data': 'synthetic',
         'config': {'workload': 'UNet2DS forward-only, batch=%d 512x512 random fp32, nfb=32 (BASELINE.json configs[1])' % B,
-                   'parallelism': 'replicas x%d' % world},
-        'roofline': {'bound': 'mfma', 'achieved': round(achieved, 3), 'peak': peak, 'unit': 'TFLOP/s',
-                     'frac': round(achieved / peak, 4), 'traffic': None, 'kernel': kname, 'launches': n_launch,
-                     'avg_launch_ms': round(k_ms / max(n_launch, 1), 4),
-                     'algorithmic_flops_per_launch': round(k_flops / max(n_launch, 1)),
-                     'mfma_flops_per_algorithmic_flop': mpf, 'matrix_pipe_frac': round(mpf * achieved / peak, 4)}}))
+                   'parallelism': 'replicas x%d' % world}}
+    if args.full:
+        timer.enabled = True
+        eng.use_tapes = False             # the instrumented forwards issue every launch from Python, through the timer proxy
+        for _ in range(3):
+            eng.forward_infer(xd)
+        torch.cuda.synchronize()
+        n_launch, k_ms, k_flops = timer.summarize()
+        achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
+        _, peak, mpf = KernelTimer.KERNELS[eng.mfma]
+        line['roofline'] = {'bound': 'mfma', 'achieved': round(achieved, 3), 'peak': peak, 'unit': 'TFLOP/s',
+                            'frac': round(achieved / peak, 4), 'traffic': None, 'kernel': timer.symbol, 'launches': n_launch,
+                            'avg_launch_ms': round(k_ms / max(n_launch, 1), 4),
+                            'algorithmic_flops_per_launch': round(k_flops / max(n_launch, 1)),
+                            'mfma_flops_per_algorithmic_flop': mpf, 'matrix_pipe_frac': round(mpf * achieved / peak, 4)}
+    if rank == 0:
+        emit_json(json.dumps(line))
 
 
 def bench_tta(args, model, rank):
@@ -343,22 +365,100 @@ def bench_tta(args, model, rank):
         Mp, _ = api.predict(paths, mpath, augmentation=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    t1 = time.perf_counter()
-    for _ in range(steps):
-        api.predict(paths, mpath, augmentation=False)
-    torch.cuda.synchronize()
-    dt_plain = time.perf_counter() - t1
-    emit_json(json.dumps({
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'masks': np.stack(Mp)})
+    line = {
         'metric': '512x512 forwards/sec through UNet2DSummary.predict with 8x test-time augmentation',
         'value': round(19 * 8 * steps / dt, 2), 'unit': 'forwards/s', 'n_gpus': 1, 'steps': steps, 'warmup': max(1, args.warmup // 3),
         'ms_per_step': round(dt / steps * 1e3, 2), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': DTYPE_LABEL[model.engine.mfma], 'data': 'synthetic',
         'config': {'workload': 'UNet2DSummary.predict(augmentation=True), 19 synthetic 512x512 datasets x 8 TTA variants, '
                                'nfb=32, through the product API; the model file is parsed on the first call and reused while it is unchanged (BASELINE.json configs[4])',
-                   'datasets_per_s': round(19 * steps / dt, 2), 'datasets_per_s_without_tta': round(19 * steps / dt_plain, 2),
-                   'positive_fraction': float(np.mean([m.mean() for m in Mp]))}}))
+                   'datasets_per_s': round(19 * steps / dt, 2),
+                   'positive_fraction': float(np.mean([m.mean() for m in Mp]))}}
+    if args.full:
+        t1 = time.perf_counter()
+        for _ in range(steps):
+            api.predict(paths, mpath, augmentation=False)
+        torch.cuda.synchronize()
+        dt_plain = time.perf_counter() - t1
+        line['config']['datasets_per_s_without_tta'] = round(19 * steps / dt_plain, 2)
+    emit_json(json.dumps(line))
     import shutil
     shutil.rmtree(tmp, ignore_errors=True)
+
+
+def full_train_figures(model, xd, yd, timer, B):
+    """--full, after the timed region: the figures that take train steps of their own.  `roofline` of the dominant kernel
+    from 2 instrumented steps (and 2 more with one stream), the exposed and the stand-alone gradient all-reduce, and the
+    'sync' BatchNorm messages.  Every rank runs it (collectives); returns the fields for rank 0's JSON line."""
+    import torch
+    from deep_calcium_amd import parallel
+    eng = model.engine
+    timer.enabled = True
+    eng.use_tapes = False                 # the instrumented steps issue every launch from Python, through the timer proxy
+    model.ar_events = []                  # also bracket the part of the gradient exchange the step waits for
+    eng.sync_events = [] if eng._sync_bn() else None      # ... and the per-layer 'sync' BatchNorm messages
+    for _ in range(2):
+        model.train_on_device_batch(xd, yd)
+    torch.cuda.synchronize()
+    syncbn = None
+    if eng.sync_events:
+        syncbn = (sum(a.elapsed_time(b) for a, b in eng.sync_events) / 2, len(eng.sync_events) // 2)
+    eng.sync_events = None
+    n_launch, k_ms, k_flops = timer.summarize()
+    k_bytes = timer.last_bytes
+    ar_exposed = [a.elapsed_time(b) for a, b in model.ar_events]
+    model.ar_events = None
+    ar_alone = None
+    if parallel.exchange_active():        # the whole 31 MB flat gradient in ONE blocking all-reduce, nothing else running
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        parallel.all_reduce_sum(eng.gflat)
+        torch.cuda.synchronize()
+        parallel.barrier()
+        e0.record()
+        for _ in range(5):
+            parallel.all_reduce_sum(eng.gflat)
+        e1.record()
+        torch.cuda.synchronize()
+        ar_alone = e0.elapsed_time(e1) / 5
+    # the same kernel without the concurrent weight-gradient stream (production overlaps them: +6.6 % step
+    # throughput, but co-running kernels stretch each other's launch time)
+    streams = eng.streams
+    eng.streams = 1
+    for _ in range(2):
+        model.train_on_device_batch(xd, yd)
+    torch.cuda.synchronize()
+    n_iso, iso_ms, iso_flops = timer.summarize()
+    eng.streams = streams
+    timer.enabled = False
+
+    achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
+    _, peak, mfma_per_flop = KernelTimer.KERNELS[eng.mfma]
+    kname = timer.symbol
+    traffic, traffic_note = pmc_traffic(kname)
+    if (H, B) != (512, 16):
+        traffic, traffic_note = None, 'the committed PMC passes were taken at batch 16 of 512x512'
+    out = {'roofline': {'bound': 'mfma', 'achieved': round(achieved, 3), 'peak': peak,
+                        'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4), 'traffic': traffic,
+                        'kernel': kname, 'launches': n_launch,
+                        'avg_launch_ms': round(k_ms / max(n_launch, 1), 4),
+                        'algorithmic_flops_per_launch': round(k_flops / max(n_launch, 1)),
+                        'algorithmic_bytes_per_launch': round(k_bytes / max(n_launch, 1)),
+                        'traffic_over_algorithmic': round(traffic * max(n_launch, 1) / k_bytes, 3) if traffic and k_bytes else None,
+                        'mfma_flops_per_algorithmic_flop': mfma_per_flop,
+                        'matrix_pipe_frac': round(mfma_per_flop * achieved / peak, 4),
+                        'achieved_without_concurrent_wgrad_stream': round(iso_flops / (iso_ms * 1e-3) / 1e12, 3) if iso_ms > 0 else None,
+                        'streams': streams, 'traffic_note': traffic_note}}
+    if syncbn is not None:
+        # 'sync' BatchNorm: the (forward: sum, sum of squares; backward: dgamma, dbeta) messages of <= 8 KB between two
+        # launches of every BatchNorm layer -- stream time from the launch in front of each all-reduce to its end
+        out['syncbn_allreduce_ms'] = round(syncbn[0], 3)
+        out['syncbn_allreduces_per_step'] = syncbn[1]
+    if parallel.exchange_active():
+        out['allreduce_ms'] = round(ar_alone, 4)
+        out['allreduce_exposed_ms'] = round(sum(ar_exposed) / max(len(ar_exposed), 1), 4)
+    return out
 
 
 _JSON_FD = None
@@ -457,7 +557,13 @@ def main():
                     help='square window size (default 512 = the contract line).  --window 128 --batch 20 is the training '
                          "configuration of the reference's example (examples/neurons/unet2ds_nf.py:36-40), --window 96 --batch 32 "
                          "fit()'s default (unet_2d_summary.py:333-335)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own (off by default): the dominant kernel\'s roofline, the gradient '
+                         'all-reduce figures, the CPU baseline (train); the roofline (infer); predict() without TTA (tta)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB in all): train = metrics, params, moving_stats; infer = probabilities; tta = masks')
     ap.add_argument('--bn', default='local', choices=['local', 'sync'],
                     help="BatchNorm under data parallelism: per-rank statistics (default) or all-reduced ('sync')")
     ap.add_argument('--mode', default='train', choices=['train', 'infer', 'tta'],
@@ -514,8 +620,9 @@ def main():
         wd.phase('infer', 600)
         return bench_infer(args, model, xd, rank, world)
 
-    timer = KernelTimer(eng.L)
-    eng.L = timer
+    if args.full:
+        timer = KernelTimer(eng.L)
+        eng.L = timer
     wd.phase('barrier before warm-up', 120)
     parallel.barrier()
 
@@ -543,54 +650,18 @@ def main():
     parallel.all_reduce_max(tmax)
     dt = float(tmax.item())
     per_rank_s = parallel.all_gather_floats(t_rank, dev)
-    wd.phase('roofline instrumentation steps', 180)
-
-    # ---- roofline of the dominant kernel: 2 instrumented steps outside the timed region --------------------
-    timer.enabled = True
-    eng.use_tapes = False                 # the instrumented steps issue every launch from Python, through the timer proxy
-    model.ar_events = []                  # also bracket the part of the gradient exchange the step waits for
-    eng.sync_events = [] if eng._sync_bn() else None      # ... and the per-layer 'sync' BatchNorm messages
-    for _ in range(2):
-        model.train_on_device_batch(xd, yd)
-    torch.cuda.synchronize()
-    syncbn = None
-    if eng.sync_events:
-        syncbn = (sum(a.elapsed_time(b) for a, b in eng.sync_events) / 2, len(eng.sync_events) // 2)
-    eng.sync_events = None
-    n_launch, k_ms, k_flops = timer.summarize()
-    k_bytes = timer.last_bytes
-    ar_exposed = [a.elapsed_time(b) for a, b in model.ar_events]
-    model.ar_events = None
-    ar_alone = None
-    if parallel.exchange_active():        # the whole 31 MB flat gradient in ONE blocking all-reduce, nothing else running
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        parallel.all_reduce_sum(eng.gflat)
-        torch.cuda.synchronize()
-        parallel.barrier()
-        e0.record()
-        for _ in range(5):
-            parallel.all_reduce_sum(eng.gflat)
-        e1.record()
-        torch.cuda.synchronize()
-        ar_alone = e0.elapsed_time(e1) / 5
-    # the same kernel without the concurrent weight-gradient stream (production overlaps them: +6.6 % step
-    # throughput, but co-running kernels stretch each other's launch time)
-    streams = eng.streams
-    eng.streams = 1
-    for _ in range(2):
-        model.train_on_device_batch(xd, yd)
-    torch.cuda.synchronize()
-    n_iso, iso_ms, iso_flops = timer.summarize()
-    eng.streams = streams
-    timer.enabled = False
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives (the Keras metrics list) and the model state the step leaves behind
+        wd.phase('dump outputs', 120)
+        dump_outputs(args.dump_outputs, {'metrics': np.array(vals, np.float64),      # [loss, F1, prec, reca, dice, dicesq, posyt, posyp]
+                                         'params': eng.pflat[:eng.n_train].cpu().numpy(),
+                                         'moving_stats': eng.sflat.cpu().numpy()})
+    extra = {}
+    if args.full:
+        wd.phase('roofline instrumentation steps', 180)
+        extra = full_train_figures(model, xd, yd, timer, B)
 
     if rank == 0:
-        achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
-        _, peak, mfma_per_flop = KernelTimer.KERNELS[eng.mfma]
-        kname = timer.symbol
-        traffic, traffic_note = pmc_traffic(kname)
-        if (H, B) != (512, 16):
-            traffic, traffic_note = None, 'the committed PMC passes were taken at batch 16 of 512x512'
         out = {
             'metric': ('512x512 summary images/sec (train step)' if H == 512 else '%dx%d training windows/sec (train step)' % (H, W)),
             'value': round(world * B * args.steps / dt, 3),
@@ -606,34 +677,17 @@ def main():
                                       'accumulate' if eng.mfma == 'f16x3' else 'fp32 MFMA',
                        'loss': float(vals[0]), 'shared_gpus': bool(shared_gpus),
                        'dist_backend': (torch.distributed.get_backend() if parallel.is_dist() else None)},
-            'roofline': {'bound': 'mfma', 'achieved': round(achieved, 3), 'peak': peak,
-                         'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4), 'traffic': traffic,
-                         'kernel': kname, 'launches': n_launch,
-                         'avg_launch_ms': round(k_ms / max(n_launch, 1), 4),
-                         'algorithmic_flops_per_launch': round(k_flops / max(n_launch, 1)),
-                         'algorithmic_bytes_per_launch': round(k_bytes / max(n_launch, 1)),
-                         'traffic_over_algorithmic': round(traffic * max(n_launch, 1) / k_bytes, 3) if traffic and k_bytes else None,
-                         'mfma_flops_per_algorithmic_flop': mfma_per_flop,
-                         'matrix_pipe_frac': round(mfma_per_flop * achieved / peak, 4),
-                         'achieved_without_concurrent_wgrad_stream': round(iso_flops / (iso_ms * 1e-3) / 1e12, 3) if iso_ms > 0 else None,
-                         'streams': streams, 'traffic_note': traffic_note},
         }
-        if syncbn is not None:
-            # 'sync' BatchNorm: the (forward: sum, sum of squares; backward: dgamma, dbeta) messages of <= 8 KB between two
-            # launches of every BatchNorm layer -- stream time from the launch in front of each all-reduce to its end
-            out['syncbn_allreduce_ms'] = round(syncbn[0], 3)
-            out['syncbn_allreduces_per_step'] = syncbn[1]
+        out.update(extra)
         if parallel.exchange_active():
             backend = torch.distributed.get_backend()
             out['rccl_ranks'] = world if backend == 'nccl' else 0      # ranks whose gradients travelled over RCCL (0: gloo run)
-            out['allreduce_ms'] = round(ar_alone, 4)
-            out['allreduce_exposed_ms'] = round(sum(ar_exposed) / max(len(ar_exposed), 1), 4)
             out['allreduce_bytes'] = int(eng.n_train * 4)
             out['allreduce_buckets'] = 1 if os.environ.get('DC_AR_BUCKETS', '3') == '1' else 3
             # who issues the collectives: librccl behind the C ABI (dc_comm_*: part of the backward's launch tape) or torch.distributed
             out['comm'] = 'dc_comm (librccl through the C ABI)' if parallel.native_comm(dev) is not None else 'torch.distributed'
             out['per_rank_images_per_s'] = [round(B * args.steps / t, 2) for t in per_rank_s]
-        if world == 1 and not args.no_cpu_baseline and (H, B) == (512, 16):
+        if args.full and world == 1 and not args.no_cpu_baseline and (H, B) == (512, 16):
             wd.phase('cpu_baseline', 300)
             out['cpu_baseline'] = cpu_baseline()
         emit_json(json.dumps(out))

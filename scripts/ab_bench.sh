@@ -4,7 +4,7 @@
 A=$1; B=$2; R=${3:-3}; shift 3
 for r in $(seq $R); do
   for v in $A $B; do
-    echo "== $v"; DC_LIB_PATH=$PWD/$v python bench.py --steps 20 --warmup 5 "$@" 2>&1 | python -c "
+    echo "== $v"; DC_LIB_PATH=$PWD/$v python bench.py --steps 20 --warmup 5 --full "$@" 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

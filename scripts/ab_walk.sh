@@ -10,7 +10,7 @@ tail -3 $OUT/tests.txt
 bash scripts/ab_env.sh DC_TILE_WALK "0 1" > $OUT/ab.txt 2>&1
 cat $OUT/ab.txt
 for w in 0 1; do
-  DC_TILE_WALK=$w DC_STREAMS=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch$w -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/fetch$w.log 2>&1
+  DC_TILE_WALK=$w DC_STREAMS=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch$w -o p -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > $OUT/fetch$w.log 2>&1
   python3 - $OUT/fetch$w <<'PY'
 import csv, sys, collections, glob, re
 f = glob.glob(sys.argv[1] + '/**/p_counter_collection.csv', recursive=True)[0]

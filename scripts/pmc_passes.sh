@@ -13,7 +13,7 @@ cd "$ROOT"
 export DC_STREAMS=1
 for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES"; do
   tag=$(echo $pass | cut -d' ' -f1)
-  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/$tag -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline $EXTRA > $OUT/$tag.log 2>&1
+  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/$tag -o p -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline $EXTRA > $OUT/$tag.log 2>&1
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o p -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline $EXTRA > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o p -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline $EXTRA > $OUT/trace.log 2>&1
 find $OUT -name "*.csv" | head -20

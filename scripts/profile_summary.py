@@ -55,12 +55,12 @@ if os.path.exists(os.path.join(src, 'infer_pmc_per_kernel.json')):      # review
     shutil.copy(os.path.join(src, 'infer_pmc_per_kernel.json'), os.path.join(P, tag.replace('_final', '') + '_infer_pmc_per_kernel.json'))
     shutil.copy(os.path.join(src, 'infer_pmc_table.md'), os.path.join(P, tag.replace('_final', '') + '_infer_pmc_table.md'))
 
-steps = 11   # bench.py --steps 5 --warmup 2 + 4 instrumented steps (2 with, 2 without the side stream)
+steps = 11   # bench.py --steps 5 --warmup 2 --full: + 4 instrumented steps (2 with, 2 without the side stream)
 out = io.StringIO()
-out.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline  (%s)\n\n' % tag)
+out.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline  (%s)\n\n' % tag)
 out.write('%d train steps in the trace (2 warm-up + 5 timed + 2 instrumented with the side stream + 2 without), batch 16 of '
           '512x512, 1x MI355X, two HIP streams (kernels of the two streams overlap, so the column sums exceed wall time).\n\n' % steps)
-out.write('Un-profiled `python bench.py` on the same box: **%.1f images/s, %.2f ms/step**; dominant kernel `%s`: HIP events '
+out.write('Un-profiled `python bench.py --full` on the same box: **%.1f images/s, %.2f ms/step**; dominant kernel `%s`: HIP events '
           '%.1f us/launch = %.1f TF/s algorithmic with the concurrent weight-gradient stream, %.1f TF/s without it.\n\n'
           % (bench['value'], bench['ms_per_step'], bench['roofline']['kernel'], 1e3 * bench['roofline']['avg_launch_ms'],
              bench['roofline']['achieved'], bench['roofline']['achieved_without_concurrent_wgrad_stream']))

@@ -10,5 +10,5 @@ for v in 0 3 1; do
     timeout 600 python scripts/igemm_pp_ablate.py $shape $v >> $O/pp_ablate.txt 2>&1
   done
 done
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench.txt 2>&1
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/bench.txt 2>&1
 tail -3 $O/wgrad_variants.txt; tail -3 $O/pp_ablate.txt; tail -1 $O/bench.txt | cut -c1-300

@@ -3,9 +3,9 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/r06_run3; mkdir -p $O
 timeout 1500 python -m pytest tests/test_comm_gpu.py tests/test_dp_gpu.py tests/test_tape_gpu.py tests/test_sync_bn_gpu.py tests/test_abi.py -m gpu -x -q > $O/pytest_dp.txt 2>&1
 tail -5 $O/pytest_dp.txt
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.txt 2>$O/bench.err
-DC_DIST_FORCE=1 DC_DIST_BACKEND=nccl MASTER_ADDR=127.0.0.1 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_dp_native.txt 2>$O/bench_dp_native.err
-DC_COMM=torch DC_DIST_FORCE=1 DC_DIST_BACKEND=nccl MASTER_ADDR=127.0.0.1 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_dp_torch.txt 2>$O/bench_dp_torch.err
+python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/bench.txt 2>$O/bench.err
+DC_DIST_FORCE=1 DC_DIST_BACKEND=nccl MASTER_ADDR=127.0.0.1 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/bench_dp_native.txt 2>$O/bench_dp_native.err
+DC_COMM=torch DC_DIST_FORCE=1 DC_DIST_BACKEND=nccl MASTER_ADDR=127.0.0.1 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/bench_dp_torch.txt 2>$O/bench_dp_torch.err
 for f in bench bench_dp_native bench_dp_torch; do tail -1 $O/$f.txt | python -c "
 import sys, json
 for l in sys.stdin:

@@ -9,7 +9,7 @@ for v in 0 1; do for shape in "128 128 128" "64 256 256"; do
 done; done
 cat $O/wgrad_presplit.txt $O/pp_presplit.txt
 export DC_DIST_FORCE=1 DC_DIST_BACKEND=nccl MASTER_ADDR=127.0.0.1
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline"
 show() { tail -1 $1 | python -c "
 import sys, json
 for l in sys.stdin:
@@ -21,6 +21,6 @@ DC_COMM_FENCE=0 $B > $O/dp_native_nofence.txt 2>&1; show $O/dp_native_nofence.tx
 DC_AR_BUCKETS=1 $B > $O/dp_native_1bucket.txt 2>&1; show $O/dp_native_1bucket.txt native_1bucket
 DC_TAIL_MAIN=0 $B > $O/dp_native_tail0.txt 2>&1; show $O/dp_native_tail0.txt native_tail0
 DC_TAPES=0 $B > $O/dp_native_notape.txt 2>&1; show $O/dp_native_notape.txt native_notape
-rocprofv3 --kernel-trace --output-format csv -d $O/trace_native -o p -- python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline > $O/trace_native.log 2>&1
-DC_COMM=torch rocprofv3 --kernel-trace --output-format csv -d $O/trace_torch -o p -- python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline > $O/trace_torch.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/trace_native -o p -- python3 bench.py --steps 6 --warmup 3 --full --no-cpu-baseline > $O/trace_native.log 2>&1
+DC_COMM=torch rocprofv3 --kernel-trace --output-format csv -d $O/trace_torch -o p -- python3 bench.py --steps 6 --warmup 3 --full --no-cpu-baseline > $O/trace_torch.log 2>&1
 for t in native torch; do f=$(find $O/trace_$t -name "p_kernel_trace.csv" | head -1); python scripts/queue_timeline.py $f 5 > $O/timeline_$t.txt 2>&1; head -3 $O/timeline_$t.txt; rm -rf $O/trace_$t; done

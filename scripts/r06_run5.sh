@@ -5,7 +5,7 @@ O=gpurun_out/r06_run5; mkdir -p $O
 timeout 1500 python -m pytest tests/test_comm_gpu.py tests/test_dp_gpu.py tests/test_tape_gpu.py tests/test_api_gpu.py -m gpu -x -q > $O/pytest.txt 2>&1
 tail -4 $O/pytest.txt
 export DC_DIST_FORCE=1 DC_DIST_BACKEND=nccl MASTER_ADDR=127.0.0.1
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline"
 show() { grep '^{' $1 | python -c "
 import sys, json
 for l in sys.stdin:

@@ -67,7 +67,7 @@ def test_bench_two_gpus_over_rccl():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'DC_DIST_BACKEND'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
     assert out['n_gpus'] == 2 and out['rccl_ranks'] == 2 and out['config']['shared_gpus'] is False
@@ -80,7 +80,7 @@ def test_bench_self_launches_two_ranks():
     env = dict(os.environ, DC_DIST_BACKEND='gloo')
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -99,7 +99,7 @@ def test_bench_one_rank_over_rccl_bucketed_async_path():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -183,11 +183,11 @@ def test_shard_dropout_seed_reproduces_single_device_masks():
 
 
 def test_bench_default_line_schema():
-    """`python bench.py` (N = 1): ONE JSON line on stdout with every field of the driver's contract, the roofline object of
-    the dominant kernel and the CPU baseline."""
+    """`python bench.py --full` (N = 1): ONE JSON line on stdout with every field of the driver's contract, the roofline object
+    of the dominant kernel and the CPU baseline."""
     env = dict(os.environ)
     env.pop('WORLD_SIZE', None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1'], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--full'], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -218,3 +218,30 @@ def test_bench_default_line_schema():
     for k in ('value', 'unit', 'cores', 'kind', 'sample'):
         assert k in cb, k
     assert cb['kind'] == 'port' and cb['unit'] == 'images/s' and cb['value'] > 0 and cb['cores'] >= 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --dump-outputs DIR` (no --full): the headline line only -- no roofline, no CPU baseline -- for exactly
+    --steps timed steps, and DIR holds what the last timed step computed: the 8 Keras metrics (float64), the trainable
+    parameters and the BatchNorm moving statistics (float32), within 64 MB."""
+    env = dict(os.environ)
+    env.pop('WORLD_SIZE', None)
+    out_dir = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--dump-outputs', str(out_dir)],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in out, k
+    assert 'roofline' not in out and 'cpu_baseline' not in out and 'allreduce_ms' not in out
+    assert out['steps'] == 4 and out['warmup'] == 1 and out['unit'] == 'images/s' and out['higher_is_better'] is True
+    assert out['metric'] == '512x512 summary images/sec (train step)' and out['dtype'] == 'f32 (fp16x3 split, fp32 accumulate)'
+    assert abs(out['value'] - 16 * 1000.0 / out['ms_per_step']) < 0.01 * out['value']
+    assert sorted(os.listdir(out_dir)) == ['metrics.npy', 'moving_stats.npy', 'params.npy']
+    m, p, s = (np.load(str(out_dir / n)) for n in ('metrics.npy', 'params.npy', 'moving_stats.npy'))
+    assert m.dtype == np.float64 and m.shape == (8,) and m[0] == out['config']['loss']
+    assert p.dtype == np.float32 and p.shape == (7766402,) and s.dtype == np.float32 and s.size > 0
+    assert np.isfinite(m).all() and np.isfinite(p).all() and np.isfinite(s).all()
+    assert sum(os.path.getsize(str(out_dir / n)) for n in os.listdir(out_dir)) <= 64 * 1000 * 1000
