@@ -457,3 +457,24 @@ def synthetic_batch(N, H, W, seed_x=865, seed_y=866, pos_rate=0.126):
     x = np.random.RandomState(seed_x).standard_normal((N, H, W)).astype(np.float32)
     y = (np.random.RandomState(seed_y).random_sample((N, H, W)) < pos_rate).astype(np.uint8)
     return x, y
+
+
+def hash_keep_mask(seed, n_elems, keep, start=0):
+    """Keep-bits (uint8, 1 = kept) the device draws for dense elements start .. start + n_elems - 1 under `seed` when a
+    dropout site runs with mask=NULL: a host restatement of the counter hash described in include/dcunet.h /
+    csrc/common.h (dc_hash32, dc_keep_factor), in numpy uint64 wrap-around arithmetic:
+        x = idx * 0x9E3779B97F4A7C15 + seed ;  twice: x ^= x >> 32, x *= 0xD6E8FEB86659FD93 ;  x ^= x >> 32
+        u = float32(uint32(x) >> 8) * 2^-24 ;  kept  <=>  u >= float32(1) - float32(keep)
+    The comparison is made in float32, as the device makes it.  The element index is that of the DENSE tensor
+    (pixel * C + channel), whatever the pixel stride of the buffer it is applied to."""
+    m64 = (1 << 64) - 1
+    idx = np.arange(int(n_elems), dtype=np.uint64) + np.uint64(int(start) & m64)
+    with np.errstate(over='ignore'):
+        x = idx * np.uint64(0x9E3779B97F4A7C15) + np.uint64(int(seed) & m64)
+        for _ in range(2):
+            x ^= x >> np.uint64(32)
+            x *= np.uint64(0xD6E8FEB86659FD93)
+        x ^= x >> np.uint64(32)
+    u = ((x & np.uint64(0xFFFFFFFF)) >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    thr = np.float32(1.0) - np.float32(keep)
+    return (u >= thr).astype(np.uint8)

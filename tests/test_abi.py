@@ -161,3 +161,24 @@ def test_import_raises_the_hardware_queue_count_only_when_unset():
             env['GPU_MAX_HW_QUEUES'] = given
         out = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=120)
         assert out.returncode == 0 and out.stdout.strip() == want, (given, out.stdout, out.stderr[-300:])
+
+
+# Launch entry points that no GPU test names.  Explicit, and empty: an entry point reached only through a whole-network test
+# is held to that test's tolerance at that test's one shape -- add the direct test, not a name here.
+UNTESTED_LAUNCHES_ALLOWED = set()
+
+
+def test_every_tapeable_launch_is_named_by_a_gpu_test():
+    """Census: every launch entry point a tape can replay (_gen_tape.prototypes()) is called by name in at least one
+    tests/test_*.py whose module carries the `gpu` mark."""
+    from deep_calcium_amd import _gen_tape
+    here = os.path.dirname(os.path.abspath(__file__))
+    text = ''
+    for f in sorted(os.listdir(here)):
+        if f.startswith('test_') and f.endswith('.py'):
+            src = open(os.path.join(here, f)).read()
+            if re.search(r'^pytestmark\s*=.*pytest\.mark\.gpu', src, flags=re.M):
+                text += src
+    named = set(re.findall(r'\bdc_\w+', text))
+    missing = sorted(n for n, _ in _gen_tape.prototypes() if n not in named)
+    assert set(missing) == UNTESTED_LAUNCHES_ALLOWED, missing

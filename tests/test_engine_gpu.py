@@ -211,3 +211,61 @@ def test_determinism_same_input_twice(mfma):
         torch.cuda.synchronize()
         outs.append(eng.gflat.cpu().numpy().copy())
     assert np.array_equal(outs[0], outs[1])
+
+
+def production_masks(eng, xd, yd, N):
+    """The keep-bits of the engine's LAST forward_train(..., masks=None), rebuilt on the host: every site's seed is read from the
+    engine's own per-step launch values (what a tape replay patches in) and run through the oracle's restatement of the hash."""
+    vals = eng._step_values(xd, yd, eng._last[2])
+    masks = {}
+    for l in eng.layers:
+        if l.kind != 'head' and l.drop > 0.0:
+            h, w = eng._hw(l.lvl)
+            masks[l.name] = on.hash_keep_mask(vals[('seed', l.name)], N * h * w * l.cout, 1.0 - l.drop).reshape(N, h, w, l.cout)
+    if eng.upsampling:
+        for lvl, rate in eng.up_drop.items():
+            if rate > 0.0:
+                h, w = eng._hw(lvl)
+                c = eng._cup(lvl)
+                masks['u%d' % lvl] = on.hash_keep_mask(vals[('useed', lvl)], N * h * w * c, 1.0 - rate).reshape(N, h, w, c)
+    return masks
+
+
+@pytest.mark.parametrize('upsampling', [False, True])
+@pytest.mark.parametrize('N,H,W,nfb', [(2, 32, 32, 8), (2, 64, 64, 32)])
+def test_production_dropout_step_matches_oracle(N, H, W, nfb, upsampling):
+    """forward_train(x, y, None) + backward(): dropout bits from the counter hash, forward and backward regenerating them
+    independently.  The float64 oracle runs under hash_keep_mask of the same seeds; bounds are those of the explicit-mask tests
+    above.  Three consecutive steps (iterations + 1 each): other masks every step, and the third is a tape REPLAY, the seeds
+    arriving through the patched value slots."""
+    from deep_calcium_amd.net import UNetEngine
+    eng = UNetEngine((H, W), nfb, upsampling=upsampling)
+    Wt = on.init_weights(nfb, randomize_bn=True, upsampling=upsampling)
+    eng.set_weights(Wt)
+    x, y = on.synthetic_batch(N, H, W)
+    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    shapes = {k: v.shape for k, v in on.make_drop_masks(nfb, N, H, W, upsampling=upsampling).items()}
+    seen = []
+    for step in range(3):
+        replays = eng.tape_replays
+        p = eng.forward_train(xd, yd, None, update_moving=False).cpu().numpy()
+        eng.backward()
+        G = eng.grads()
+        masks = production_masks(eng, xd, yd, N)
+        assert {k: v.shape for k, v in masks.items()} == shapes
+        for k, m in masks.items():
+            keep = 1.0 - on.dropout_rates()[k]
+            assert abs(m.mean() - keep) < 4 * np.sqrt(keep * (1 - keep) / m.size) + 1e-12, (k, m.mean())
+            assert all(not np.array_equal(m, old[k]) for old in seen), (step, k)
+        seen.append(masks)
+        loss_ref, p_ref, G_ref, _ = on.UNetOracle(Wt, nfb, upsampling=upsampling, force=device_decisions(eng, N)).loss_and_grads(x, y, masks)
+        tag = 'production dropout, %s nfb%d step %d: ' % ('upsampling' if upsampling else 'transpose', nfb, step)
+        print('%s|dp| = %.3e, |dloss| = %.3e' % (tag, np.abs(p - p_ref).max(), abs(eng.read_sums()[0] / p.size - loss_ref)))
+        assert np.abs(p - p_ref).max() < 1e-4 and abs(eng.read_sums()[0] / p.size - loss_ref) < 1e-4
+        if step == 0:
+            assert_forcing_is_benign(Wt, nfb, x, masks, p_ref, p_dev=p, upsampling=upsampling)
+        worst, rel, _ = grad_report(G, G_ref, tag)
+        assert worst < GRAD_TOL and rel < GRAD_TOL, (step, worst, rel)
+        if step == 2 and eng.use_tapes:
+            assert eng.tape_replays > replays           # this step's launches came from the tapes
+        eng.iterations += 1                              # what adam_step() does: the next step draws other bits

@@ -167,3 +167,32 @@ def test_weight_list_layout():
     up = [l for l in t if l[1] == 'convT']
     assert [(l[2], l[3], l[4]) for l in up] == [(512, 256, 0.5), (256, 128, 0.5), (128, 64, 0.5), (64, 32, 0.5)]
     assert on.dropout_rates(0.25) == {'e1b': 0.25, 'e2b': 0.5, 'e3b': 0.5, 'u3': 0.5, 'u2': 0.5, 'u1': 0.5, 'u0': 0.25}
+
+
+@pytest.mark.parametrize('keep', [0.75, 0.5])
+def test_hash_keep_mask_fraction_and_seed_dependence(keep):
+    """oracle.hash_keep_mask (the host restatement of the device's counter-hash dropout): the kept fraction sits within
+    4 standard deviations of a Bernoulli(keep) sample mean, for the network's two rates; another seed, other bits."""
+    n = 1 << 20
+    m = on.hash_keep_mask(0x1234567, n, keep)
+    assert m.dtype == np.uint8 and m.shape == (n,) and set(np.unique(m)) == {0, 1}
+    assert abs(m.mean() - keep) < 4 * np.sqrt(keep * (1 - keep) / n), m.mean()
+    assert not np.array_equal(m, on.hash_keep_mask(0x1234568, n, keep))
+    assert np.array_equal(m, on.hash_keep_mask(0x1234567, n, keep))
+    assert on.hash_keep_mask(5, 1000, 1.0).all()             # threshold 0: everything is kept
+    # `start` is an index offset
+    assert np.array_equal(on.hash_keep_mask(0x1234567, 1000, keep, start=4321), m[4321:5321])
+
+
+@pytest.mark.parametrize('seed', [1, 0x1234567, (1 << 64) - 3, (1 << 63) + 12345])
+def test_hash_keep_mask_shard_identity(seed):
+    """parallel.shard_drop_seed turns the index offset of rank r's shard into a seed offset (mod 2^64): the shard's mask is
+    the r-th slice of the whole batch's.  The seeds near 2^64 make the offset wrap."""
+    from deep_calcium_amd import parallel
+    G, n, keep = 8, 3 * 7 * 9 * 8, 0.75
+    whole = on.hash_keep_mask(seed, G * n, keep)
+    for r in range(G):
+        s = parallel.shard_drop_seed(seed, n, r)
+        assert 0 <= s < (1 << 64)
+        assert np.array_equal(on.hash_keep_mask(s, n, keep), whole[r * n:(r + 1) * n]), r
+    assert len(set(parallel.shard_drop_seed(seed, n, r) for r in range(G))) == G
