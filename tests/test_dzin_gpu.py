@@ -232,7 +232,8 @@ def test_dgrad_dzin_writes_dz_for_a_plain_weight_gradient(dclib, N, H, W, Cin, C
 
 
 # every weight-gradient tile configuration (wgrad_f16x3.hip CONV_H_DISPATCH) incl. the narrow ones the data gradient
-# leaves to the apply path, ragged tiles, x materialised / BN + ReLU on load
+# leaves to the apply path, ragged tiles, x materialised / BN + ReLU on load.  One tile per workgroup each: the producer pipeline
+# across several tiles (incl. the one-(da, z)-set variant of the 32-wide tiles) is test_multitile_gpu.py's (tests/_tileplan.py)
 WGRAD_SHAPES = [(2, 64, 64, 64, 64), (1, 40, 72, 48, 32), (2, 48, 48, 32, 32), (1, 32, 32, 128, 256), (2, 16, 16, 64, 128),
                 (2, 8, 8, 128, 64), (1, 64, 96, 64, 32), (2, 32, 64, 32, 64), (3, 33, 50, 64, 64)]
 

@@ -51,6 +51,8 @@ def pack(L, K, taps, Kdim, Ncols, s_tap, s_k, s_n, flip):
     return dst
 
 
+# All but three of these give every weight-gradient workgroup ONE tile (and the role-split launches an even item count): the
+# multi-tile loops -- 2 .. 5 tiles per workgroup, short last split, uneven items per workgroup -- are test_multitile_gpu.py's.
 CONV_SHAPES = [
     # N, H, W, Cin, Cout          tile config exercised
     (2, 32, 32, 32, 64),        # A32
