@@ -25,6 +25,7 @@ _EXPORTS = {
               'load_model_with_new_input_shape', 'metrics_from_sums'),
     'unet2ds': ('UNet2DSummary', 'INVERTIBLE_2D_AUGMENTATIONS', '_ValidationMetricsCB'),
     'nf_metrics': ('nf_mask_metrics',),
+    'series': ('SeriesSummarizer', 'summarize_series_device'),
 }
 _WHERE = dict((name, mod) for mod, names in _EXPORTS.items() for name in names)
 __all__ = sorted(_WHERE)

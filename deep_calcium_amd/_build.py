@@ -11,9 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libdcunet.so')
-SOURCES = ['common.cpp', 'comm.cpp', 'nf_score.cpp', 'tape.cpp', 'igemm_conv.hip', 'igemm_f16x3.hip', 'igemm_pp.hip', 'wgrad.hip', 'wgrad_f16x3.hip', 'bwd_joint.hip', 'conv_c1.hip', 'elementwise.hip']
+SOURCES = ['common.cpp', 'comm.cpp', 'nf_score.cpp', 'tape.cpp', 'igemm_conv.hip', 'igemm_f16x3.hip', 'igemm_pp.hip', 'wgrad.hip', 'wgrad_f16x3.hip', 'bwd_joint.hip', 'conv_c1.hip', 'elementwise.hip', 'series.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
-HOST_ONLY = {'nf_score.cpp': ['-ffp-contract=off']}      # host arithmetic that must round like numpy's: no fused multiply-add
+# per-file flags.  Arithmetic that must round like numpy's: no fused multiply-add (nf_score.cpp: host code only; series.hip: its kernels too)
+FILE_FLAGS = {'nf_score.cpp': ['-ffp-contract=off'], 'series.hip': ['-ffp-contract=off']}
 
 
 def _hipcc():
@@ -44,7 +45,7 @@ def build(force=False, verbose=True):
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.splitext(src)[0] + '.o')
-        cmd = [hipcc] + FLAGS + HOST_ONLY.get(src, []) + ['-x', 'hip', '-c', os.path.join(CSRC, src), '-o', obj]
+        cmd = [hipcc] + FLAGS + FILE_FLAGS.get(src, []) + ['-x', 'hip', '-c', os.path.join(CSRC, src), '-o', obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError('hipcc failed for %s:\n%s' % (src, r.stderr[-6000:]))

@@ -206,6 +206,19 @@ class Dataset(_Object):
             raise Hdf5Error('chunked datasets are not supported (Keras weight files are contiguous)')
         return np.frombuffer(raw, dtype=dt.dtype, count=n).reshape(shape).copy()
 
+    def view(self):
+        """A contiguous dataset as a read-only array over the file mapping -- no copy: how a multi-GB series/raw is streamed.
+        The array keeps the mapping in use; drop it before File.close()."""
+        dt, shape, layout = self._meta()
+        if dt.kind not in ('int', 'float') or not shape or layout[0] != 3 or layout[1] != 1:
+            raise Hdf5Error('only contiguous numeric datasets can be viewed in place')
+        n = int(np.prod(shape))
+        addr, size = struct.unpack_from('<QQ', layout, 2)
+        a = self.f.base + addr
+        if addr == UNDEF or a + n * dt.dtype.itemsize > len(self.f.buf):
+            raise Hdf5Error('dataset has no (complete) storage in the file')
+        return np.frombuffer(self.f.buf, dtype=dt.dtype, count=n, offset=a).reshape(shape)
+
     def __array__(self, dtype=None, copy=None):
         a = self.read()
         return a if dtype is None else a.astype(dtype)

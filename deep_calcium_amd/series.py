@@ -1,0 +1,268 @@
+"""Series summaries on the device: a recording (T,H,W) of 16-bit frames -> the (H,W) image the network segments.
+
+The reference computes `series/mean` and `series/max` on the host while it builds a dataset (datasets/nf.py:121-130) and
+leaves every other summary to the user's `series_summary_func` (unet_2d_summary.py:227-241 is the default).  Here the frames
+are streamed once through the dc_series_* kernels (include/dcunet.h):
+
+    kind      dtype     what
+    mean16    float16   the reference's stored mean: accumulated in float16, one rounding per frame   (bit-exact)
+    max16     int16     the reference's stored max: from 0, saturated at 32767                        (exact)
+    mean      float32   sum / T                                        (exact sum, <= 1 ulp)
+    max       float32   the true maximum                               (exact)
+    std       float32   population standard deviation over time        (exact numerator, <= 1 ulp)
+    corr      float32   mean Pearson correlation with the 8 neighbours (exact numerators, abs. error < 1e-14)
+
+    summ = SeriesSummarizer((H, W), T, np.int16, kinds=('mean', 'corr'))
+    for chunk in chunks: summ.feed(chunk)
+    img = summ.result('corr')
+
+    UNet2DSummary(series_summary_func=functools.partial(summarize_series_device, kind='corr'))
+
+Importing this module needs neither torch nor the GPU; constructing a SeriesSummarizer does (there is no CPU fallback).
+"""
+import numpy as np
+
+KINDS = ('mean16', 'max16', 'mean', 'max', 'std', 'corr')
+MAX_FRAMES = 2147483647               # DC_SERIES_MAX_FRAMES: what the int64 state holds
+_CHUNK_BYTES = 32 << 20               # default staging chunk: long enough to hide the launches, short enough to pin twice
+
+
+def _check_kind(kind, kinds=KINDS):
+    if kind not in KINDS:
+        raise ValueError('summary kind %r is not one of %s' % (kind, ', '.join(KINDS)))
+    if kind not in kinds:
+        raise ValueError('summary kind %r was not requested (kinds=%r)' % (kind, tuple(kinds)))
+
+
+def _frame_dtype(dtype):
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise ValueError('frames must be int16 or uint16, not %r' % (dtype,))
+    if dt not in (np.dtype(np.int16), np.dtype(np.uint16)):
+        raise ValueError('frames must be int16 or uint16, not %s' % dt)
+    return dt
+
+
+class SeriesSummarizer(object):
+    """Owns the device state of one recording's summaries; feed() the frames in order, in chunks of any size, then result()."""
+
+    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS):
+        # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
+        try:
+            shape = tuple(int(v) for v in shape)
+        except TypeError:
+            raise ValueError('shape must be (H, W), not %r' % (shape,))
+        if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] > (1 << 30):
+            raise ValueError('shape must be (H, W) with 1 <= H * W <= 2**30, not %r' % (shape,))
+        n_frames = int(n_frames)
+        if not 1 <= n_frames <= MAX_FRAMES:
+            raise ValueError('n_frames must be in [1, %d], not %d' % (MAX_FRAMES, n_frames))
+        self.dtype = _frame_dtype(dtype)
+        kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+        if not kinds:
+            raise ValueError('kinds is empty')
+        for k in kinds:
+            _check_kind(k)
+        H, W = shape
+        if chunk_frames is None:
+            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 1:
+            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
+        self.shape, self.n_frames, self.kinds = shape, n_frames, kinds
+        self.chunk_frames = min(chunk_frames, n_frames)
+        self.fed = 0
+        self._images = None
+
+        import torch
+        from . import net
+        from ._lib import lib
+        self._torch, self._net = torch, net
+        self.L = lib()
+        if not torch.cuda.is_available():
+            from ._lib import DcunetError
+            raise DcunetError('SeriesSummarizer needs a GPU (there is no CPU fallback)')
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        dev, n = self.device, H * W
+        self._chain = 'mean16' in kinds or 'max16' in kinds
+        self._xy = 'corr' in kinds
+        # state: written by the chunk with t0 == 0, so never cleared here
+        self.sum = torch.empty(n, dtype=torch.int64, device=dev)
+        self.sumsq = torch.empty(n, dtype=torch.int64, device=dev)
+        self.vmax = torch.empty(n, dtype=torch.int32, device=dev)
+        self.mean16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None      # float16 BITS
+        self.max16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None
+        self.xy = torch.empty((4, n), dtype=torch.int64, device=dev) if self._xy else None
+        # two staging slots: the H2D copy of chunk k + 1 (copy stream) runs beside the kernels on chunk k (current stream)
+        C = self.chunk_frames
+        self._host = [net._pinned('series_stage%d' % k, (C, H, W), torch.int16, entry=True) for k in range(2)]
+        self._dev = [torch.empty((C, H, W), dtype=torch.int16, device=dev) for _ in range(2)]
+        with torch.cuda.device(dev):
+            self._copy_stream = torch.cuda.Stream(device=dev)
+        self._read = [None, None]         # event behind the last kernel that read device slot k
+        self._slot = 0
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device)
+
+    def feed(self, frames):
+        """The next frames of the recording: (t, H, W) numpy array or memmap of the recording's dtype, any t >= 1."""
+        if not isinstance(frames, np.ndarray):
+            raise ValueError('frames must be a numpy array (or memmap), not %s' % type(frames).__name__)
+        if frames.ndim != 3 or tuple(frames.shape[1:]) != self.shape:
+            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
+        if frames.dtype != self.dtype:
+            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
+        if frames.shape[0] < 1 or self.fed + frames.shape[0] > self.n_frames:
+            raise ValueError('%d frames after %d fed: the recording was declared to have %d' %
+                             (frames.shape[0], self.fed, self.n_frames))
+        torch, L = self._torch, self.L
+        H, W = self.shape
+        uns = int(self.dtype == np.dtype(np.uint16))
+        with torch.cuda.device(self.device):
+            main = self._stream()
+            for a in range(0, frames.shape[0], self.chunk_frames):
+                part = frames[a:a + self.chunk_frames]
+                tc, k = part.shape[0], self._slot
+                self._slot ^= 1
+                host, dev = self._host[k], self._dev[k]
+                if host[1] is not None:
+                    host[1].synchronize()                  # the copy that last read this pinned slot has finished
+                host[0].numpy()[:tc] = part.view(np.int16)         # same bits; the kernels are told the signedness
+                with torch.cuda.stream(self._copy_stream):
+                    if self._read[k] is not None:
+                        self._copy_stream.wait_event(self._read[k])      # the kernels on chunk k - 2 are done with the slot
+                    dev[:tc].copy_(host[0][:tc], non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(self._copy_stream)
+                host[1] = ev
+                main.wait_event(ev)
+                st, fp = main.cuda_stream, dev.data_ptr()
+                L.dc_series_accumulate(fp, uns, tc, self.fed, self.n_frames,
+                                       self.mean16.data_ptr() if self._chain else None,
+                                       self.max16.data_ptr() if self._chain else None,
+                                       self.sum.data_ptr(), self.sumsq.data_ptr(), self.vmax.data_ptr(), H, W, st)
+                if self._xy:
+                    L.dc_series_accumulate_xy(fp, uns, tc, self.fed, self.xy.data_ptr(), H, W, st)
+                done = torch.cuda.Event()
+                done.record(main)
+                self._read[k] = done
+                self.fed += tc
+        self._images = None
+        return self
+
+    def _finalize(self):
+        if self._images is None:
+            torch, L = self._torch, self.L
+            H, W = self.shape
+            with torch.cuda.device(self.device):
+                out = torch.empty((3, H * W), dtype=torch.float32, device=self.device)
+                L.dc_series_finalize(self.sum.data_ptr(), self.sumsq.data_ptr(), self.xy.data_ptr() if self._xy else None,
+                                     out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr() if self._xy else None,
+                                     H, W, self.n_frames, self._stream().cuda_stream)
+            self._images = out
+        return self._images
+
+    def _standardize(self, img):
+        torch, L = self._torch, self.L
+        H, W = self.shape
+        with torch.cuda.device(self.device):
+            ws = torch.empty(int(L.dc_series_standardize_ws_floats(H, W)) // 2, dtype=torch.float64, device=self.device)
+            L.dc_image_standardize(img.data_ptr(), img.data_ptr(), ws.data_ptr(), H, W, self._stream().cuda_stream)
+        return img
+
+    def result(self, kind, standardize=False):
+        """The (H,W) summary: float32 (float16 for 'mean16', int16 for 'max16').  standardize=True: (img - mean) / std of the
+        float32 image, as _summarize_series does with series/mean -- always float32."""
+        _check_kind(kind, self.kinds)
+        if self.fed != self.n_frames:
+            raise ValueError('result() after %d of %d frames' % (self.fed, self.n_frames))
+        torch = self._torch
+        H, W = self.shape
+        if kind == 'mean16':
+            raw = self.mean16.cpu().numpy().view(np.float16).reshape(H, W)
+        elif kind == 'max16':
+            raw = self.max16.cpu().numpy().reshape(H, W)
+        elif kind == 'max':
+            raw = self.vmax.cpu().numpy().astype(np.float32).reshape(H, W)
+        else:
+            img = self._finalize()[('mean', 'std', 'corr').index(kind)]
+            if standardize:
+                return self._standardize(img.clone()).cpu().numpy().reshape(H, W)
+            return img.cpu().numpy().reshape(H, W)
+        if not standardize:
+            return raw
+        with np.errstate(over='ignore'):
+            img = torch.from_numpy(np.ascontiguousarray(raw.astype(np.float32)).reshape(-1)).to(self.device)
+        return self._standardize(img).cpu().numpy().reshape(H, W)
+
+
+def _open_series(dspath, source):
+    """(frames array-like of (T,H,W), close()) without reading the recording: .npz members and contiguous HDF5 datasets are
+    memory-mapped, h5py datasets are sliced chunk by chunk."""
+    key = source.replace('/', '_', 1)
+    if str(dspath).endswith('.npz'):
+        import zipfile
+        with zipfile.ZipFile(dspath) as z:
+            names = z.namelist()
+            if key + '.npy' not in names:
+                raise ValueError('%s has no member %r' % (dspath, key))
+            info = z.getinfo(key + '.npy')
+            stored = info.compress_type == zipfile.ZIP_STORED
+        if stored:                      # np.savez: members are stored, the .npy payload can be mapped in place
+            with open(dspath, 'rb') as fp:
+                fp.seek(info.header_offset)
+                head = fp.read(30)
+                nlen, xlen = int.from_bytes(head[26:28], 'little'), int.from_bytes(head[28:30], 'little')
+                fp.seek(info.header_offset + 30 + nlen + xlen)
+                version = np.lib.format.read_magic(fp)
+                shape, fortran, dt = (np.lib.format.read_array_header_1_0(fp) if version == (1, 0)
+                                      else np.lib.format.read_array_header_2_0(fp))
+                offset = fp.tell()
+            if not fortran and not dt.hasobject:
+                return np.memmap(dspath, dtype=dt, mode='r', offset=offset, shape=shape), (lambda: None)
+        z = np.load(dspath, allow_pickle=False)      # compressed member: has to be inflated
+        return z[key], z.close
+    from .unet2ds import _open_dataset            # the h5py / built-in reader choice of the default summary functions
+    _, fp = _open_dataset(dspath)
+
+    def close():
+        try:
+            fp.close()
+        except BufferError:            # a slice of the mapping is still alive (a traceback holds it): the collector closes the file
+            pass
+    try:
+        node = fp[source]
+    except KeyError:
+        close()
+        raise ValueError('%s has no dataset %r' % (dspath, source))
+    if hasattr(node, 'view'):          # hdf5_min: the dataset in place, no copy
+        from . import hdf5_min
+        try:
+            return node.view(), close
+        except hdf5_min.Hdf5Error:     # compact / unallocated storage: small enough to read
+            return node.read(), close
+    return node, close                 # h5py: sliced chunk by chunk
+
+
+def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None):
+    """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
+    float32 summary (standardised like _summarize_series's by default)."""
+    _check_kind(kind)
+    frames, close = _open_series(dspath, source)
+    try:
+        if len(frames.shape) != 3:
+            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
+        T = int(frames.shape[0])
+        summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
+                                kinds=(kind,))
+        for a in range(0, T, summ.chunk_frames):
+            summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
+        out = summ.result(kind, standardize=standardize)
+    finally:
+        frames = None                        # a view of the file mapping: released before the file is closed
+        close()
+    return np.asarray(out, dtype=np.float32)

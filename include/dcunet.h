@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 107
+#define DC_ABI_VERSION 108
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -458,6 +458,46 @@ long dc_host_nf_ws_bytes(int H, int W);
 int dc_host_nf_pairs(const uint8_t* truth, const uint8_t* pred, int H, int W, double threshold, int* counts,
                      double* inc, double* exc, int cap, void* ws);
 int dc_host_label8(const uint8_t* mask, int H, int W, int* labels, int* n, void* ws);
+
+/* ---- series summaries: a recording (T,H,W) of 16-bit frames -> the (H,W) images the network segments ------------------------
+ * What the reference computes on the host while it builds a dataset (datasets/nf.py:121-130: series/mean accumulated IN its
+ * float16 storage, series/max in int16) and standardises in its default series_summary_func (_summarize_series,
+ * unet_2d_summary.py:227-241), plus the summaries it leaves to the user's own series_summary_func: the true mean, the max
+ * projection, the temporal standard deviation and the local correlation image.
+ * frames: int16 (is_unsigned == 0) or uint16 (is_unsigned != 0), [tc][H][W] contiguous, 2-byte aligned -- W and H*W need no
+ * padding.  A recording arrives in chunks: t0 = index of the chunk's first frame, n_total = frames of the whole recording.
+ * All running state lives in the CALLER's buffers (H*W elements each); the chunk with t0 == 0 initialises it (previous
+ * contents are ignored), every later chunk continues it.  Chunk boundaries never change a bit of any result.
+ * DC_SERIES_MAX_FRAMES: the int64 sums hold T * 65535^2 < 2^63 for every T up to it; beyond: DC_EUNSUP (-3). */
+#define DC_SERIES_MAX_FRAMES 2147483647L
+/* datasets/nf.py:121-130, per pixel over the chunk's frames in order:
+ *   mean16 (bits of a float16): m = float16(double(m) + double(x) / n_total) -- IEEE double divide and add, ONE rounding
+ *     to nearest even per frame (never through float32), inf above 65504: bit-identical to `ds_mean[...] += img * 1. / n`;
+ *   max16 (int16): min(max(m, x), 32767) starting from 0 (`np.maximum(ds_max, img)` through the saturating int16 store);
+ *   sum, sumsq (int64), vmax (int32): exact sum x, sum x*x and the true maximum.
+ * mean16 / max16: both given or both NULL (the float16 chain is the expensive part of the pass). */
+int dc_series_accumulate(const void* frames, int is_unsigned, int tc, long t0, long n_total, uint16_t* mean16,
+                         int16_t* max16, long* sum, long* sumsq, int* vmax, int H, int W, dc_stream_t stream);
+/* the exact cross sums of the local correlation image (no counterpart in datasets/nf.py:121-130 or
+ * unet_2d_summary.py:227-241: a series_summary_func of the user's): xy = int64[4][H*W], xy[j][p] = sum_t x_p * x_q with q the
+ * right (j = 0), down (1), down-right (2), down-left (3) neighbour of p; a neighbour outside the image contributes 0. */
+int dc_series_accumulate_xy(const void* frames, int is_unsigned, int tc, long t0, long* xy, int H, int W,
+                            dc_stream_t stream);
+/* state -> float32 images (each output nullable; the user-side summaries next to datasets/nf.py:121-130 /
+ * unet_2d_summary.py:227-241): mean = sum / T; std = sqrt(T sum x^2 - (sum x)^2) / T (population); corr (needs xy) = the
+ * mean over the pixel's EXISTING 8 neighbours of the Pearson correlation, a pair with a zero-variance pixel counting 0,
+ * a pixel without neighbours giving 0.  The numerators T sum xy - sum x sum y and T sum x^2 - (sum x)^2 are formed
+ * exactly in 128-bit integers, converted to double with one rounding; then one divide (and one sqrt) in double and one
+ * rounding to float32 per value -- mean and std within 1 float32 ulp of the exact value; corr sums up to 8 such quotients
+ * in double (absolute error below 1e-14, i.e. within 1 float32 ulp unless the neighbours' correlations cancel to |corr| < 1e-6). */
+int dc_series_finalize(const long* sum, const long* sumsq, const long* xy, float* mean, float* sdev, float* corr,
+                       int H, int W, long T, dc_stream_t stream);
+/* out = (in - mean(in)) / std(in) over one H x W float32 image: `(summ - np.mean(summ)) / np.std(summ)` of
+ * _summarize_series, unet_2d_summary.py:227-241 (its input: the series/mean of datasets/nf.py:121-130).  Sums in double, fixed
+ * order (two-pass variance); subtraction and division in double, one rounding to float32.
+ * ws: float[dc_series_standardize_ws_floats()], 8-byte aligned.  in == out is allowed. */
+long dc_series_standardize_ws_floats(int H, int W);
+int dc_image_standardize(const float* in, float* out, float* ws, int H, int W, dc_stream_t stream);
 
 /* misc */
 int dc_fill(float* p, long n, float value, dc_stream_t stream);

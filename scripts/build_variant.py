@@ -21,7 +21,7 @@ def build_variant(tag, sources, defines, verbose=False):
         base = os.path.splitext(src)[0] + '.o'
         if src in sources:
             obj = os.path.join(vdir, base)
-            cmd = [_build._hipcc()] + _build.FLAGS + _build.HOST_ONLY.get(src, []) + list(defines) + \
+            cmd = [_build._hipcc()] + _build.FLAGS + _build.FILE_FLAGS.get(src, []) + list(defines) + \
                   ['-x', 'hip', '-c', os.path.join(_build.CSRC, src), '-o', obj]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
