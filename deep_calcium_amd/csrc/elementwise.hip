@@ -43,6 +43,45 @@ static int ew_blocks(long pixels, int C, int cap = kMaxBlocks) {
   return (int)(b > cap ? cap : (b < 1 ? 1 : b));
 }
 static int ew_bwd_blocks(long pixels, int C) { return ew_blocks(pixels, C, kMaxBwdBlocks); }
+__device__ __forceinline__ f32x4 absmax4(const f32x4& m, const f32x4& v) {
+  f32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = fmaxf(m[e], fabsf(v[e]));
+  return r;
+}
+__device__ __forceinline__ f32x4 max4(const f32x4& a, const f32x4& b) {
+  f32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = fmaxf(a[e], b[e]);
+  return r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Block epilogues of the kernels whose 256 threads are PPB = 256 / C4 pixel lanes (pl) x C4 channel quads (q).
+// block_sum_quads / block_max_quads: every thread has stored its value to sm[tid] and the block has synchronised; the pl == 0
+// lane of quad q combines its own v with the other pixel lanes' in the fixed order k = 1 .. PPB-1 (bit-reproducible).
+__device__ __forceinline__ f32x4 block_sum_quads(const f32x4* sm, int C4, int q, f32x4 v) {
+  for (int k = 1; k < 256 / C4; ++k) v += sm[k * C4 + q];
+  return v;
+}
+__device__ __forceinline__ f32x4 block_max_quads(const f32x4* sm, int C4, int q, f32x4 v) {
+  for (int k = 1; k < 256 / C4; ++k) v = max4(v, sm[k * C4 + q]);
+  return v;
+}
+// this block's row of the BatchNorm-backward partials, as dc_bn_bwd_finalize reads them: partial[block][C][2] = (s1, s2)
+__device__ __forceinline__ void store_bn_partial(float* partial, int C, int q, const f32x4& s1, const f32x4& s2) {
+  float* dst = partial + ((long)blockIdx.x * C + 4 * q) * 2;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { dst[2 * e] = s1[e]; dst[2 * e + 1] = s2[e]; }
+}
+// max of v over the block (every thread calls it, every thread gets it): 64-lane xor max, then the four waves through LDS
+__device__ __forceinline__ float block_max_scalar(float v) {
+  __shared__ float smx[4];
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) smx[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
+}
 
 // ------------------------------------------------------------------------------------------------
 // BN statistics finalize: one block per channel, double accumulation over all partials.
@@ -384,17 +423,35 @@ __device__ __forceinline__ void bn_bwd_elem(const BnParams& p, long pix, int q, 
   bn_bwd_math(p, pix, q, z, da, mu, is, sc, sh, drop, inv_keep, dy, xh);
 }
 
-__device__ __forceinline__ f32x4 absmax4(const f32x4& m, const f32x4& v) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = fmaxf(m[e], fabsf(v[e]));
-  return r;
+// grid-stride sweep of (z, da) for the thread's channel quad, two pixels per iteration: four 16-byte loads in flight per lane
+// before the first use.  finish(pix, z, da) takes the pixels in ascending order.
+template <class F>
+__device__ __forceinline__ void bn_bwd_sweep(const BnParams& p, int PPB, int q, int pl, F finish) {
+  const long stride = (long)gridDim.x * PPB;
+  long pix = (long)blockIdx.x * PPB + pl;
+  for (; pix + stride < p.pixels; pix += 2 * stride) {
+    const long pb = pix + stride;
+    const f32x4 z0 = ld4(p.z + pix * p.C + 4 * q), d0 = ld4(p.da + pix * p.da_ld + 4 * q);
+    const f32x4 z1 = ld4(p.z + pb * p.C + 4 * q), d1 = ld4(p.da + pb * p.da_ld + 4 * q);
+    finish(pix, z0, d0);
+    finish(pb, z1, d1);
+  }
+  if (pix < p.pixels) finish(pix, ld4(p.z + pix * p.C + 4 * q), ld4(p.da + pix * p.da_ld + 4 * q));
 }
-__device__ __forceinline__ f32x4 max4(const f32x4& a, const f32x4& b) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = fmaxf(a[e], b[e]);
-  return r;
+// (sum dy, sum dy*xhat) of the block -> p.partial, and with p.amax_c its per-channel max |dy| (am): the epilogue of the kernels
+// that feed dc_bn_bwd_finalize / dc_bn_bwd_finalize_dzin
+__device__ __forceinline__ void bn_bwd_store_partials(const BnParams& p, f32x4* sm1, f32x4* sm2, int C4, int q, int pl,
+                                                      const f32x4& s1, const f32x4& s2, const f32x4& am) {
+  const int tid = threadIdx.x;
+  sm1[tid] = s1; sm2[tid] = s2;
+  __syncthreads();
+  if (pl == 0) store_bn_partial(p.partial, p.C, q, block_sum_quads(sm1, C4, q, s1), block_sum_quads(sm2, C4, q, s2));
+  if (p.amax_c) {
+    __syncthreads();
+    sm1[tid] = am;
+    __syncthreads();
+    if (pl == 0) st4(p.amax_c + (long)blockIdx.x * p.C + 4 * q, block_max_quads(sm1, C4, q, am));
+  }
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BnParams p) {
@@ -407,40 +464,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BnParams p) {
   f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f}, am = {0.f, 0.f, 0.f, 0.f};
   f32x4 sc, sh;
   bn_affine4(mu, is, ga, be, sc, sh);
-  auto finish = [&](long pix, const f32x4& z, const f32x4& da) {
+  bn_bwd_sweep(p, PPB, q, pl, [&](long pix, const f32x4& z, const f32x4& da) {
     f32x4 dy, xh;
     bn_bwd_math(p, pix, q, z, da, mu, is, sc, sh, drop, inv_keep, dy, xh);
     s1 += dy;
     s2 += dy * xh;
     am = absmax4(am, dy);
-  };
-  const long stride = (long)gridDim.x * PPB;
-  long pix = (long)blockIdx.x * PPB + pl;
-  for (; pix + stride < p.pixels; pix += 2 * stride) {
-    const long pb = pix + stride;
-    const f32x4 z0 = ld4(p.z + pix * p.C + 4 * q), d0 = ld4(p.da + pix * p.da_ld + 4 * q);
-    const f32x4 z1 = ld4(p.z + pb * p.C + 4 * q), d1 = ld4(p.da + pb * p.da_ld + 4 * q);
-    finish(pix, z0, d0);
-    finish(pb, z1, d1);
-  }
-  if (pix < p.pixels) finish(pix, ld4(p.z + pix * p.C + 4 * q), ld4(p.da + pix * p.da_ld + 4 * q));
-  sm1[tid] = s1; sm2[tid] = s2;
-  __syncthreads();
-  if (pl == 0) {
-    for (int k = 1; k < PPB; ++k) { s1 += sm1[k * C4 + q]; s2 += sm2[k * C4 + q]; }
-    float* dst = p.partial + ((long)blockIdx.x * p.C + 4 * q) * 2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { dst[2 * e] = s1[e]; dst[2 * e + 1] = s2[e]; }
-  }
-  if (p.amax_c) {
-    __syncthreads();
-    sm1[tid] = am;
-    __syncthreads();
-    if (pl == 0) {
-      for (int k = 1; k < PPB; ++k) am = max4(am, sm1[k * C4 + q]);
-      st4(p.amax_c + (long)blockIdx.x * p.C + 4 * q, am);
-    }
-  }
+  });
+  bn_bwd_store_partials(p, sm1, sm2, C4, q, pl, s1, s2, am);
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnParams p) {
@@ -457,39 +488,22 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnParams p) {
   float amax = 0.f;
   f32x4 sc, sh;
   bn_affine4(mu, is, ga, be, sc, sh);
-  auto finish = [&](long pix, const f32x4& z, const f32x4& da) {
+  bn_bwd_sweep(p, PPB, q, pl, [&](long pix, const f32x4& z, const f32x4& da) {
     f32x4 dy, xh;
     bn_bwd_math(p, pix, q, z, da, mu, is, sc, sh, drop, inv_keep, dy, xh);
     const f32x4 dz = gs * (dy - mdy - xh * mdyx);
     s1 += dz;
     amax = fmaxf(amax, fmaxf(fmaxf(fabsf(dz[0]), fabsf(dz[1])), fmaxf(fabsf(dz[2]), fabsf(dz[3]))));
     st4(p.out + pix * p.out_ld + 4 * q, dz);
-  };
-  // two pixels per iteration: four 16-byte loads in flight per lane before the first use
-  const long stride = (long)gridDim.x * PPB;
-  long pix = (long)blockIdx.x * PPB + pl;
-  for (; pix + stride < p.pixels; pix += 2 * stride) {
-    const long pb = pix + stride;
-    const f32x4 z0 = ld4(p.z + pix * p.C + 4 * q), d0 = ld4(p.da + pix * p.da_ld + 4 * q);
-    const f32x4 z1 = ld4(p.z + pb * p.C + 4 * q), d1 = ld4(p.da + pb * p.da_ld + 4 * q);
-    finish(pix, z0, d0);
-    finish(pb, z1, d1);
-  }
-  if (pix < p.pixels) finish(pix, ld4(p.z + pix * p.C + 4 * q), ld4(p.da + pix * p.da_ld + 4 * q));
+  });
   if (p.partial) {
     sm1[tid] = s1;
     __syncthreads();
-    if (pl == 0) {
-      for (int k = 1; k < PPB; ++k) s1 += sm1[k * C4 + q];
-      st4(p.partial + (long)blockIdx.x * p.C + 4 * q, s1);
-    }
+    if (pl == 0) st4(p.partial + (long)blockIdx.x * p.C + 4 * q, block_sum_quads(sm1, C4, q, s1));
   }
   if (p.absmax) {
-    __shared__ float smax[4];
-    for (int s = 32; s > 0; s >>= 1) amax = fmaxf(amax, __shfl_xor(amax, s));
-    if ((tid & 63) == 0) smax[tid >> 6] = amax;
-    __syncthreads();
-    if (tid == 0) p.absmax[blockIdx.x] = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
+    amax = block_max_scalar(amax);
+    if (tid == 0) p.absmax[blockIdx.x] = amax;
   }
 }
 
@@ -576,7 +590,20 @@ extern "C" int dc_bn_bwd_reduce(const float* da, long da_ld, const float* z, con
 static int bn_bwd_apply_impl(const float* da, long da_ld, const float* z, const float* mean, const float* invstd,
                              const float* gamma, const float* beta, const uint8_t* mask, float keep, uint64_t seed,
                              const float* dgamma, const float* dbeta, float* dz, float* dbias_partial,
-                             float* absmax_partial, long pixels, double count, int C, dc_stream_t stream);
+                             float* absmax_partial, long pixels, double count, int C, dc_stream_t stream) {
+  DC_REQUIRE(da && z && mean && invstd && gamma && beta && dgamma && dbeta && dz, DC_EINVAL,
+             "dc_bn_bwd_apply: null pointer");
+  DC_REQUIRE(pixels > 0 && da_ld >= C && da_ld % 4 == 0 && keep > 0.f, DC_EINVAL, "dc_bn_bwd_apply: bad sizes");
+  int rc = chan_check("dc_bn_bwd_apply", C);
+  if (rc) return rc;
+  BnParams p{};
+  p.da = da; p.da_ld = da_ld; p.z = z; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta;
+  p.mask = mask; p.keep = keep; p.seed = seed; p.dgamma = dgamma; p.dbeta = dbeta; p.out = dz; p.out_ld = C;
+  p.partial = dbias_partial; p.absmax = absmax_partial; p.pixels = pixels; p.C = C; p.count = count;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_bwd_blocks(pixels, C)), dim3(256), 0, (hipStream_t)stream, p);
+  DC_CHECK_LAUNCH("dc_bn_bwd_apply");
+  return DC_OK;
+}
 extern "C" int dc_bn_bwd_apply(const float* da, long da_ld, const float* z, const float* mean, const float* invstd,
                                const float* gamma, const float* beta, const uint8_t* mask, float keep, uint64_t seed,
                                const float* dgamma, const float* dbeta, float* dz, float* dbias_partial,
@@ -591,23 +618,6 @@ extern "C" int dc_bn_bwd_apply_count(const float* da, long da_ld, const float* z
   DC_REQUIRE(count >= (double)pixels, DC_EINVAL, "dc_bn_bwd_apply_count: count < pixels");
   return bn_bwd_apply_impl(da, da_ld, z, mean, invstd, gamma, beta, mask, keep, seed, dgamma, dbeta, dz, dbias_partial,
                            absmax_partial, pixels, count, C, stream);
-}
-static int bn_bwd_apply_impl(const float* da, long da_ld, const float* z, const float* mean, const float* invstd,
-                             const float* gamma, const float* beta, const uint8_t* mask, float keep, uint64_t seed,
-                             const float* dgamma, const float* dbeta, float* dz, float* dbias_partial,
-                             float* absmax_partial, long pixels, double count, int C, dc_stream_t stream) {
-  DC_REQUIRE(da && z && mean && invstd && gamma && beta && dgamma && dbeta && dz, DC_EINVAL,
-             "dc_bn_bwd_apply: null pointer");
-  DC_REQUIRE(pixels > 0 && da_ld >= C && da_ld % 4 == 0 && keep > 0.f, DC_EINVAL, "dc_bn_bwd_apply: bad sizes");
-  int rc = chan_check("dc_bn_bwd_apply", C);
-  if (rc) return rc;
-  BnParams p{};
-  p.da = da; p.da_ld = da_ld; p.z = z; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta;
-  p.mask = mask; p.keep = keep; p.seed = seed; p.dgamma = dgamma; p.dbeta = dbeta; p.out = dz; p.out_ld = C;
-  p.partial = dbias_partial; p.absmax = absmax_partial; p.pixels = pixels; p.C = C; p.count = count;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_bwd_blocks(pixels, C)), dim3(256), 0, (hipStream_t)stream, p);
-  DC_CHECK_LAUNCH("dc_bn_bwd_apply");
-  return DC_OK;
 }
 
 // dbeta[c] = sum_p partial[p][c][0], dgamma[c] = sum_p partial[p][c][1]
@@ -763,7 +773,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bnred_kernel(const float* __r
                                                                const float* __restrict__ skip, long skip_ld,
                                                                float* __restrict__ dx, int N, int H, int W, BnParams p) {
   __shared__ f32x4 sm1[256], sm2[256];
-  const int C = p.C, C4 = C >> 2, h2 = H >> 1, w2 = W >> 1, PPB = 256 / C4;
+  const int C = p.C, C4 = C >> 2, h2 = H >> 1, w2 = W >> 1;
   const int tid = threadIdx.x, q = tid % C4, pl = tid / C4;
   const f32x4 mu = ld4(p.mean + 4 * q), is = ld4(p.invstd + 4 * q), ga = ld4(p.gamma + 4 * q), be = ld4(p.beta + 4 * q);
   f32x4 sc, sh;
@@ -788,36 +798,14 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bnred_kernel(const float* __r
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] += (kk[e] == pos) ? g[e] : 0.f;
       st4(dx + pix * C + 4 * q, v);
-      const long elem = pix * C + 4 * q;
-      const f32x4 z = ld4(p.z + elem);
-      const f32x4 xh = (z - mu) * is;
-      const f32x4 yv = fma4(z, sc, sh);
-      f32x4 d = v;
-      if (drop) d *= drop_factor(p, elem, inv_keep);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) d[e] = (yv[e] > 0.f) ? d[e] : 0.f;
+      f32x4 d, xh;
+      bn_bwd_math(p, pix, q, ld4(p.z + pix * C + 4 * q), v, mu, is, sc, sh, drop, inv_keep, d, xh);
       s1 += d;
       s2 += d * xh;
       am = absmax4(am, d);
     }
   }
-  sm1[tid] = s1; sm2[tid] = s2;
-  __syncthreads();
-  if (pl == 0) {
-    for (int k = 1; k < PPB; ++k) { s1 += sm1[k * C4 + q]; s2 += sm2[k * C4 + q]; }
-    float* dst = p.partial + ((long)blockIdx.x * C + 4 * q) * 2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { dst[2 * e] = s1[e]; dst[2 * e + 1] = s2[e]; }
-  }
-  if (p.amax_c) {
-    __syncthreads();
-    sm1[tid] = am;
-    __syncthreads();
-    if (pl == 0) {
-      for (int k = 1; k < PPB; ++k) am = max4(am, sm1[k * C4 + q]);
-      st4(p.amax_c + (long)blockIdx.x * C + 4 * q, am);
-    }
-  }
+  bn_bwd_store_partials(p, sm1, sm2, C4, q, pl, s1, s2, am);
 }
 
 static int pool_check(const char* fn, int N, int H, int W, int C) {
@@ -975,414 +963,286 @@ extern "C" int dc_upsample2x_drop_bwd(const float* dout, long dout_ld, const uin
 #define DC_HEAD_SUMS 12   // bce, tp, sum round(p), fn, sum y, sum y*p, sum p^2, sum y^2, sum p, weighted-bce, 2 spare
 __device__ __forceinline__ float round_half_even(float x) { return rintf(x); }  // default RN mode = half to even
 
+struct HeadParams {
+  const float* a;                       // [pixels][C] activation; with in_sc the PRE-BatchNorm tensor z
+  const float* kh; const float* bh;     // 1x1 kernel [C][2], bias [2] (bh: forward only)
+  const uint8_t* y;                     // labels (nullable in the forward-only kernel)
+  float* p;                             // class-1 probability: the forward writes it, head_bwd_kernel reads it
+  float* partial;                       // [blocks][DC_HEAD_SUMS] metric sums (nullable in the forward-only kernel)
+  float* da; float* gpartial;           // backward: dL/da and the [blocks][C+4] weight / bias gradient partials
+  int loss_kind; const double* sums;    // sums: the reduced forward sums loss kinds 2 and 3 need
+  // in_sc != NULL: the activation relu(fmaf(z, sc, sh)) is formed on load
+  const float* in_sc; const float* in_sh;
+  // bn_partial != NULL (needs in_sc): also emit this block's (sum dy, sum dy*xhat) of the producing BatchNorm layer,
+  // dy = da * [relu gate] -- the sums dc_bn_bwd_reduce would otherwise re-read da and z for
+  const float* bn_mean; const float* bn_invstd; float* bn_partial;
+  float* amax_partial;                  // [blocks][C] max |da_c| (nullable)
+  long pixels; int C;
+};
+// what a lane holds for the whole sweep: its 4 channels of the head's weights and of the producing BatchNorm layer
+struct HeadLane {
+  float k0[4], k1[4], b0, b1;
+  f32x4 kd;                             // kh[c][1] - kh[c][0]
+  f32x4 isc, ish, bmu, bis;
+  float invM;
+  bool bnin, bnred;
+};
+__device__ __forceinline__ HeadLane head_lane(const HeadParams& hp, int q, bool fwd) {
+  HeadLane L;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    L.k0[e] = hp.kh[(4 * q + e) * 2]; L.k1[e] = hp.kh[(4 * q + e) * 2 + 1]; L.kd[e] = L.k1[e] - L.k0[e];
+  }
+  L.b0 = fwd ? hp.bh[0] : 0.f; L.b1 = fwd ? hp.bh[1] : 0.f;
+  L.invM = 1.f / (float)hp.pixels;
+  L.bnin = hp.in_sc != nullptr; L.bnred = hp.bn_partial != nullptr;
+  L.isc = L.bnin ? ld4(hp.in_sc + 4 * q) : f32x4{1.f, 1.f, 1.f, 1.f};
+  L.ish = L.bnin ? ld4(hp.in_sh + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+  L.bmu = L.bnred ? ld4(hp.bn_mean + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+  L.bis = L.bnred ? ld4(hp.bn_invstd + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+  return L;
+}
 
 // One pixel's contribution of a lane's 4 channels to a logit: an EXPLICIT fma chain, so that every head kernel (inference forward,
 // training forward, fused forward + backward in both instantiations) rounds it identically whatever the compiler would contract.
 __device__ __forceinline__ float head_dot4(const f32x4& v, const float (&k)[4]) {
   return __builtin_fmaf(v[3], k[3], __builtin_fmaf(v[2], k[2], __builtin_fmaf(v[1], k[1], v[0] * k[0])));
 }
-// C4T = 8 (C == 32): the 8 loads of a lane's pixel group are issued together (see head_fwd_bwd_kernel); 0 = generic.
+// pixel j of the group that starts at sweep `it0`, for pixel lane pl
+__device__ __forceinline__ long head_group_pix(long it0, int j, int PPB, int pl) {
+  return ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
+}
+// The C/4 lanes of a pixel share its two logits after the xor-reduce.  Pixels are taken C/4 at a time: lane q keeps the logits
+// of the q-th one (kpix == pixels: none), then EVERY lane runs the softmax / BCE / metric arithmetic (3 exp, 3 log per pixel) for
+// its own pixel -- C/4 times fewer issues of that transcendental-heavy block than one active lane per pixel.
+// C4T = 8 (C == 32, the network's nfb): the 8 loads of a lane's pixel group are issued TOGETHER and held in registers (for the
+// backward half too).  The generic loop issues one load per iteration and waits for it (the shuffle reductions in between keep
+// the compiler from hoisting the next one): 16 groups x 8 dependent loads per lane made the fused kernel latency-bound at
+// 285-300 us for a 200-us sweep.
 template <int C4T>
-__global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ a, const float* __restrict__ kh,
-                                                      const float* __restrict__ bh, const uint8_t* __restrict__ y,
-                                                      float* __restrict__ p, float* __restrict__ partial, long pixels,
-                                                      int C, const float* __restrict__ in_sc,
-                                                      const float* __restrict__ in_sh) {
-  __shared__ float sm[256][DC_HEAD_SUMS];
-  const int C4 = C4T ? C4T : (C >> 2), PPB = 256 / C4;
-  const int tid = threadIdx.x, q = tid % C4, pl = tid / C4;
-  float k0[4], k1[4];
+__device__ __forceinline__ void head_group_logits(const HeadParams& hp, const HeadLane& L, int C4, int PPB, int q, int pl,
+                                                  long it0, f32x4 (&held)[C4T ? C4T : 1], float& kz0, float& kz1, long& kpix) {
+  kz0 = 0.f; kz1 = 0.f;
+  kpix = hp.pixels;
+  auto one = [&](int j, long pix, bool ok, f32x4 v) {
+    if (L.bnin) {
+      v = fma4(v, L.isc, L.ish);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) { k0[e] = kh[(4 * q + e) * 2]; k1[e] = kh[(4 * q + e) * 2 + 1]; }
-  const float b0 = bh[0], b1 = bh[1];
-  // in_sc != NULL: `a` holds the PRE-BatchNorm tensor z and the activation relu(fmaf(z, sc, sh)) is formed here
-  const bool bnin = in_sc != nullptr;
-  const f32x4 isc = bnin ? ld4(in_sc + 4 * q) : f32x4{1.f, 1.f, 1.f, 1.f};
-  const f32x4 ish = bnin ? ld4(in_sh + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-  float acc[DC_HEAD_SUMS];
-#pragma unroll
-  for (int k = 0; k < DC_HEAD_SUMS; ++k) acc[k] = 0.f;
-  // The C/4 lanes of a pixel share its two logits after the xor-reduce.  Pixels are taken C/4 at a time: lane q keeps
-  // the logits of the q-th one, then EVERY lane runs the softmax / BCE / metric arithmetic (3 exp, 3 log per pixel) for
-  // its own pixel -- C/4 times fewer issues of that transcendental-heavy block than one active lane per pixel.
-  const long iters = (pixels + (long)gridDim.x * PPB - 1) / ((long)gridDim.x * PPB);
-  for (long it0 = 0; it0 < iters; it0 += C4) {  // uniform trip counts: the shuffles below need every lane
-    float kz0 = 0.f, kz1 = 0.f;
-    long kpix = pixels;                           // "no pixel"
-    auto one = [&](int j, long pix, bool ok, f32x4 v) {
-      if (bnin) {
-        v = fma4(v, isc, ish);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = ok ? fmaxf(v[e], 0.f) : 0.f;
-      }
-      float z0 = head_dot4(v, k0);
-      float z1 = head_dot4(v, k1);
-      if constexpr (C4T != 0) {
-#pragma unroll
-        for (int s = 1; s < C4T; s <<= 1) { z0 += __shfl_xor(z0, s); z1 += __shfl_xor(z1, s); }
-      } else {
-        for (int s = 1; s < C4; s <<= 1) { z0 += __shfl_xor(z0, s); z1 += __shfl_xor(z1, s); }
-      }
-      if (j == q) { kz0 = z0; kz1 = z1; kpix = pix; }
-    };
+      for (int e = 0; e < 4; ++e) v[e] = ok ? fmaxf(v[e], 0.f) : 0.f;
+    }
+    float z0 = head_dot4(v, L.k0);
+    float z1 = head_dot4(v, L.k1);
     if constexpr (C4T != 0) {
-      f32x4 held[C4T];
 #pragma unroll
-      for (int j = 0; j < C4T; ++j) {
-        const long pix = ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
-        held[j] = pix < pixels ? ld4(a + pix * C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int j = 0; j < C4T; ++j) {
-        const long pix = ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
-        one(j, pix, pix < pixels, held[j]);
-      }
+      for (int s = 1; s < C4T; s <<= 1) { z0 += __shfl_xor(z0, s); z1 += __shfl_xor(z1, s); }
     } else {
-      for (int j = 0; j < C4; ++j) {
-        const long pix = ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
-        const bool ok = pix < pixels;
-        one(j, pix, ok, ok ? ld4(a + pix * C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f});
-      }
+      for (int s = 1; s < C4; s <<= 1) { z0 += __shfl_xor(z0, s); z1 += __shfl_xor(z1, s); }
     }
-    if (kpix < pixels) {
-      const long pix = kpix;
-      const float z0 = kz0 + b0, z1 = kz1 + b1;
-      // 2-way softmax, max-subtracted, class 1
-      const float m = fmaxf(z0, z1);
-      const float e0 = expf(z0 - m), e1 = expf(z1 - m);
-      const float pr = e1 / (e0 + e1);
-      p[pix] = pr;
-      if (y) {
-        const float yt = (float)y[pix];
-        // Keras/TF binary_crossentropy (A.10): clip, logit, stable sigmoid-BCE
-        const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
-        const float x = logf(pc / (1.f - pc));
-        acc[0] += fmaxf(x, 0.f) - x * yt + log1pf(expf(-fabsf(x)));
-        const float rp = round_half_even(pr);
-        acc[1] += rp * yt;
-        acc[2] += rp;
-        acc[3] += fminf(fmaxf(yt - rp, 0.f), 1.f);
-        acc[4] += yt;
-        acc[5] += yt * pr;
-        acc[6] += pr * pr;
-        acc[7] += yt * yt;
-        acc[8] += pr;
-        // weighted_binary_crossentropy (utils/neurons.py:13-29): -(2*y*log(p+1e-7) + (1-y)*log(1-p+1e-7))
-        acc[9] -= 2.f * yt * logf(pr + 1e-7f) + (1.f - yt) * logf(1.f - pr + 1e-7f);
-      }
-    }
-  }
-  if (partial) {
+    if (j == q) { kz0 = z0; kz1 = z1; kpix = pix; }
+  };
+  if constexpr (C4T != 0) {
 #pragma unroll
-    for (int k = 0; k < DC_HEAD_SUMS; ++k) sm[tid][k] = acc[k];
-    __syncthreads();
-    if (tid < DC_HEAD_SUMS) {
-      double s = 0.0;
-      for (int t = 0; t < 256; ++t) s += (double)sm[t][tid];
-      partial[(long)blockIdx.x * DC_HEAD_SUMS + tid] = (float)s;
+    for (int j = 0; j < C4T; ++j) {
+      const long pix = head_group_pix(it0, j, PPB, pl);
+      held[j] = pix < hp.pixels ? ld4(hp.a + pix * hp.C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int j = 0; j < C4T; ++j) {
+      const long pix = head_group_pix(it0, j, PPB, pl);
+      one(j, pix, pix < hp.pixels, held[j]);
+    }
+  } else {
+    for (int j = 0; j < C4; ++j) {
+      const long pix = head_group_pix(it0, j, PPB, pl);
+      const bool ok = pix < hp.pixels;
+      one(j, pix, ok, ok ? ld4(hp.a + pix * hp.C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f});
     }
   }
 }
-
+// 2-way softmax, max-subtracted, class 1
+__device__ __forceinline__ float head_prob(float z0, float z1) {
+  const float m = fmaxf(z0, z1);
+  const float e0 = expf(z0 - m), e1 = expf(z1 - m);
+  return e1 / (e0 + e1);
+}
+__device__ __forceinline__ void head_metric_sums(float (&acc)[DC_HEAD_SUMS], float pr, float yt) {
+  // Keras/TF binary_crossentropy (A.10): clip, logit, stable sigmoid-BCE
+  const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
+  const float x = logf(pc / (1.f - pc));
+  acc[0] += fmaxf(x, 0.f) - x * yt + log1pf(expf(-fabsf(x)));
+  const float rp = round_half_even(pr);
+  acc[1] += rp * yt;
+  acc[2] += rp;
+  acc[3] += fminf(fmaxf(yt - rp, 0.f), 1.f);
+  acc[4] += yt;
+  acc[5] += yt * pr;
+  acc[6] += pr * pr;
+  acc[7] += yt * yt;
+  acc[8] += pr;
+  // weighted_binary_crossentropy (utils/neurons.py:13-29): -(2*y*log(p+1e-7) + (1-y)*log(1-p+1e-7))
+  acc[9] -= 2.f * yt * logf(pr + 1e-7f) + (1.f - yt) * logf(1.f - pr + 1e-7f);
+}
 // s = dL/dlogit1 (dlogit0 = -s).  loss_kind 0: Keras binary_crossentropy, s = (p - y)/M where the clip is inactive.
 // Kinds 1..3 (utils/neurons.py:13-29,78-94) go through dL/dp * p(1-p); the global sums they need come from the
 // forward's reduced sums (device memory, no host round trip):
 //   1 weighted_binary_crossentropy: dL/dp = -(2y/(p+1e-7) - (1-y)/(1-p+1e-7)) / M
 //   2 dice_loss   = 1 - 2I/D,  I = sum y*p, D = sum y + sum p + 1e-7:        dL/dp = -2 (y D - I) / D^2
 //   3 dicesq_loss = -2I/D,     D = sum y^2 + sum p^2 + 1e-7:                 dL/dp = -2 (y D - 2 p I) / D^2
-__global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ a, const float* __restrict__ p,
-                                                      const uint8_t* __restrict__ y, const float* __restrict__ kh,
-                                                      float* __restrict__ da, float* __restrict__ partial, long pixels,
-                                                      int C, int loss_kind, const double* __restrict__ sums,
-                                                      const float* __restrict__ in_sc, const float* __restrict__ in_sh,
-                                                      const float* __restrict__ bn_mean,
-                                                      const float* __restrict__ bn_invstd, float* __restrict__ bn_partial,
-                                                      float* __restrict__ amax_partial) {
-  __shared__ f32x4 sm[256];
-  __shared__ float sms[256];
-  const int C4 = C >> 2, PPB = 256 / C4;
-  const int tid = threadIdx.x, q = tid % C4, pl = tid / C4;
-  f32x4 kd;  // kh[c][1] - kh[c][0]
+// The one fused multiply-add (kind 3) is written out and contraction is off, so that a kind rounds the same in every kernel.
+__device__ __forceinline__ float head_dlogit(int loss_kind, float pr, float yt, float invM, float I, float D, float invD2) {
+#pragma clang fp contract(off)
+  if (loss_kind == 0) {
+    const bool inside = pr > 1e-7f && pr < 1.f - 1e-7f;
+    return inside ? (pr - yt) * invM : 0.f;
+  }
+  float dp;
+  if (loss_kind == 1) dp = -(2.f * yt / (pr + 1e-7f) - (1.f - yt) / (1.f - pr + 1e-7f)) * invM;
+  else if (loss_kind == 2) dp = -2.f * (yt * D - I) * invD2;
+  else dp = -2.f * __builtin_fmaf(-I, 2.f * pr, yt * D) * invD2;
+  return dp * pr * (1.f - pr);
+}
+// this thread's sums of the backward: sa = sum a*s (head weight gradient), ss = sum s (bias gradient, lane q == 0),
+// r1 / r2 = (sum dy, sum dy*xhat) of the producing BatchNorm layer
+struct HeadGrad { f32x4 sa, r1, r2; float ss; };
+// backward of one pixel for a lane's 4 channels: v = a[pix] as loaded, s = the pixel's dL/dlogit1
+__device__ __forceinline__ void head_bwd_pixel(const HeadParams& hp, const HeadLane& L, int q, long pix, f32x4 v, float s,
+                                               HeadGrad& g) {
+  if (L.bnin) {
+    const f32x4 zraw = v;
+    v = fma4(v, L.isc, L.ish);
+    if (L.bnred) {
+      const f32x4 xh = (zraw - L.bmu) * L.bis;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) kd[e] = kh[(4 * q + e) * 2 + 1] - kh[(4 * q + e) * 2];
-  const float invM = 1.f / (float)pixels;
-  const bool bnin = in_sc != nullptr;
-  const f32x4 isc = bnin ? ld4(in_sc + 4 * q) : f32x4{1.f, 1.f, 1.f, 1.f};
-  const f32x4 ish = bnin ? ld4(in_sh + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-  // bn_partial != NULL (needs bnin): also emit this block's (sum dy, sum dy*xhat) of the producing BatchNorm layer,
-  // dy = da * [relu gate] -- the sums dc_bn_bwd_reduce would otherwise re-read da and z for
-  const bool bnred = bn_partial != nullptr;
-  const f32x4 bmu = bnred ? ld4(bn_mean + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-  const f32x4 bis = bnred ? ld4(bn_invstd + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 r1 = {0.f, 0.f, 0.f, 0.f}, r2 = {0.f, 0.f, 0.f, 0.f};
-  float I = 0.f, D = 1.f;
-  if (loss_kind == 2) { I = (float)sums[5]; D = (float)(sums[4] + sums[8] + 1e-7); }
-  if (loss_kind == 3) { I = (float)sums[5]; D = (float)(sums[7] + sums[6] + 1e-7); }
-  const float invD2 = 1.f / (D * D);
-  f32x4 sa = {0.f, 0.f, 0.f, 0.f};
-  float ss = 0.f, smax = 0.f;     // smax: max |dL/dlogit| of this thread's pixels (da = kd * s: max |da_c| = |kd_c| * smax)
-  for (long pix = (long)blockIdx.x * PPB + pl; pix < pixels; pix += (long)gridDim.x * PPB) {
-    const float pr = p[pix], yt = (float)y[pix];
-    float s;
-    if (loss_kind == 0) {
-      const bool inside = pr > 1e-7f && pr < 1.f - 1e-7f;
-      s = inside ? (pr - yt) * invM : 0.f;
-    } else {
-      float dp;
-      if (loss_kind == 1) dp = -(2.f * yt / (pr + 1e-7f) - (1.f - yt) / (1.f - pr + 1e-7f)) * invM;
-      else if (loss_kind == 2) dp = -2.f * (yt * D - I) * invD2;
-      else dp = -2.f * (yt * D - 2.f * pr * I) * invD2;
-      s = dp * pr * (1.f - pr);
-    }
-    f32x4 v = ld4(a + pix * C + 4 * q);
-    if (bnin) {
-      const f32x4 zraw = v;
-      v = fma4(v, isc, ish);
-      if (bnred) {
-        const f32x4 xh = (zraw - bmu) * bis;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float dy = (v[e] > 0.f) ? kd[e] * s : 0.f;
-          r1[e] += dy;
-          r2[e] += dy * xh[e];
-        }
+      for (int e = 0; e < 4; ++e) {
+        const float dy = (v[e] > 0.f) ? L.kd[e] * s : 0.f;
+        g.r1[e] += dy;
+        g.r2[e] += dy * xh[e];
       }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
     }
-    st4(da + pix * C + 4 * q, kd * s);
-    sa += v * s;
-    smax = fmaxf(smax, fabsf(s));
-    if (q == 0) ss += s;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
   }
-  sm[tid] = sa;
-  sms[tid] = (q == 0) ? ss : 0.f;
+  st4(hp.da + pix * hp.C + 4 * q, L.kd * s);
+  g.sa += v * s;
+  if (q == 0) g.ss += s;
+}
+// block epilogue of the backward.  smax: max |dL/dlogit| of this thread's pixels (da = kd * s: max |da_c| = |kd_c| * smax);
+// every pixel's s is seen by a lane of its group, so a block-wide max of the per-thread maxima serves every channel.
+__device__ __forceinline__ void head_bwd_epilogue(const HeadParams& hp, const HeadLane& L, HeadGrad g, float smax, int C4,
+                                                  int q, int pl) {
+  __shared__ f32x4 sm1[256], sm2[256];
+  __shared__ float sms[256];
+  const int tid = threadIdx.x, C = hp.C;
+  sm1[tid] = g.sa;
+  sms[tid] = (q == 0) ? g.ss : 0.f;
   __syncthreads();
-  if (pl == 0) {
-    for (int k = 1; k < PPB; ++k) sa += sm[k * C4 + q];
-    st4(partial + (long)blockIdx.x * (C + 4) + 4 * q, sa);
-  }
+  if (pl == 0) st4(hp.gpartial + (long)blockIdx.x * (C + 4) + 4 * q, block_sum_quads(sm1, C4, q, g.sa));
   if (tid == 0) {
     float s = 0.f;
-    for (int k = 0; k < PPB; ++k) s += sms[k * C4];
-    partial[(long)blockIdx.x * (C + 4) + C] = s;
+    for (int k = 0; k < 256 / C4; ++k) s += sms[k * C4];
+    hp.gpartial[(long)blockIdx.x * (C + 4) + C] = s;
   }
-  if (bnred) {
-    __shared__ f32x4 sm2[256];
+  if (L.bnred) {
     __syncthreads();
-    sm[tid] = r1; sm2[tid] = r2;
+    sm1[tid] = g.r1; sm2[tid] = g.r2;
     __syncthreads();
-    if (pl == 0) {
-      for (int k = 1; k < PPB; ++k) { r1 += sm[k * C4 + q]; r2 += sm2[k * C4 + q]; }
-      float* dst = bn_partial + ((long)blockIdx.x * C + 4 * q) * 2;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { dst[2 * e] = r1[e]; dst[2 * e + 1] = r2[e]; }
-    }
+    if (pl == 0) store_bn_partial(hp.bn_partial, C, q, block_sum_quads(sm1, C4, q, g.r1), block_sum_quads(sm2, C4, q, g.r2));
   }
-  if (amax_partial) {          // every pixel's s is seen by all C/4 lanes of its group: a block-wide max of the per-thread maxima
-    __shared__ float smx[4];
-    __syncthreads();
-    for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o));
-    if ((tid & 63) == 0) smx[tid >> 6] = smax;
-    __syncthreads();
+  if (hp.amax_partial) {
+    const float m = block_max_scalar(smax);
     if (pl == 0) {
-      const float m = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
       f32x4 am;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) am[e] = fabsf(kd[e]) * m;
-      st4(amax_partial + (long)blockIdx.x * C + 4 * q, am);
+      for (int e = 0; e < 4; ++e) am[e] = fabsf(L.kd[e]) * m;
+      st4(hp.amax_partial + (long)blockIdx.x * C + 4 * q, am);
     }
   }
 }
 
-// Training step with a per-pixel loss (loss_kind 0 / 1): the head's backward needs nothing but the pixel's own p and y, so
-// the forward can do it while the C/4 values of the pixel are still in cache -- head_fwd_kernel's pixel-group scheme,
-// then lane q hands the dL/dlogit of ITS pixel back to the group and every lane writes its 4 channels of da, the head's
-// weight-gradient partials and (bn_partial) the producing BatchNorm layer's backward sums, as head_bwd_kernel does.
-// One read of the 512^2 x nfb tensor instead of two, no read of p.  Per-block summation order differs from
-// head_bwd_kernel's (same terms).
-// C4T = 8 (C == 32, the network's nfb): the 8 loads of a lane's pixel group are issued TOGETHER and held in registers for the backward
-// half.  The generic loop issues one load per iteration and waits for it (the shuffle reductions in between keep the compiler from
-// hoisting the next one): 16 groups x 8 dependent loads per lane made the kernel latency-bound at 285-300 us for a 200-us sweep.
-template <int C4T>
-__global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restrict__ a, const float* __restrict__ kh,
-                                                          const float* __restrict__ bh, const uint8_t* __restrict__ y,
-                                                          float* __restrict__ p, float* __restrict__ partial,
-                                                          float* __restrict__ da, float* __restrict__ gpartial, long pixels,
-                                                          int C, int loss_kind, const float* __restrict__ in_sc,
-                                                          const float* __restrict__ in_sh, const float* __restrict__ bn_mean,
-                                                          const float* __restrict__ bn_invstd, float* __restrict__ bn_partial,
-                                                          float* __restrict__ amax_partial) {
+// Forward (BWD = false: p, and with labels the metric sums) and the fused training step of a per-pixel loss (BWD = true,
+// loss_kind 0 / 1): the head's backward needs nothing but the pixel's own p and y, so the forward can do it while the C/4 values
+// of the pixel are still in cache -- lane q hands the dL/dlogit of ITS pixel back to the group and every lane writes its 4
+// channels of da, the head's weight-gradient partials and (bn_partial) the producing BatchNorm layer's backward sums, as
+// head_bwd_kernel does.  One read of the 512^2 x nfb tensor instead of two, no read of p.  Per-block summation order differs
+// from head_bwd_kernel's (same terms).
+template <int C4T, bool BWD>
+__global__ __launch_bounds__(256) void head_fwd_kernel(HeadParams hp) {
   __shared__ float sm[256][DC_HEAD_SUMS];
-  __shared__ f32x4 sm4[256], sm4b[256];
-  __shared__ float sms[256];
-  const int C4 = C4T ? C4T : (C >> 2), PPB = 256 / C4;
+  const int C4 = C4T ? C4T : (hp.C >> 2), PPB = 256 / C4;
   const int tid = threadIdx.x, q = tid % C4, pl = tid / C4, lane = tid & 63;
-  float k0[4], k1[4];
-  f32x4 kd;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { k0[e] = kh[(4 * q + e) * 2]; k1[e] = kh[(4 * q + e) * 2 + 1]; kd[e] = k1[e] - k0[e]; }
-  const float b0 = bh[0], b1 = bh[1];
-  const float invM = 1.f / (float)pixels;
-  const bool bnin = in_sc != nullptr, bnred = bn_partial != nullptr;
-  const f32x4 isc = bnin ? ld4(in_sc + 4 * q) : f32x4{1.f, 1.f, 1.f, 1.f};
-  const f32x4 ish = bnin ? ld4(in_sh + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-  const f32x4 bmu = bnred ? ld4(bn_mean + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-  const f32x4 bis = bnred ? ld4(bn_invstd + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+  const long pixels = hp.pixels;
+  const HeadLane L = head_lane(hp, q, true);
   float acc[DC_HEAD_SUMS];
 #pragma unroll
   for (int k = 0; k < DC_HEAD_SUMS; ++k) acc[k] = 0.f;
-  f32x4 sa = {0.f, 0.f, 0.f, 0.f}, r1 = sa, r2 = sa;
-  float ss = 0.f, smax = 0.f;
+  HeadGrad g{};
+  float smax = 0.f;
   const long iters = (pixels + (long)gridDim.x * PPB - 1) / ((long)gridDim.x * PPB);
-  for (long it0 = 0; it0 < iters; it0 += C4) {
-    float kz0 = 0.f, kz1 = 0.f;
-    long kpix = pixels;
+  for (long it0 = 0; it0 < iters; it0 += C4) {  // uniform trip counts: the shuffles need every lane
+    float kz0, kz1;
+    long kpix;
     f32x4 held[C4T ? C4T : 1];
-    auto fwd_one = [&](int j, long pix, bool ok, f32x4 v) {
-      if (bnin) {
-        v = fma4(v, isc, ish);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = ok ? fmaxf(v[e], 0.f) : 0.f;
-      }
-      float z0 = head_dot4(v, k0);
-      float z1 = head_dot4(v, k1);
-      if constexpr (C4T != 0) {
-#pragma unroll
-        for (int s = 1; s < C4T; s <<= 1) { z0 += __shfl_xor(z0, s); z1 += __shfl_xor(z1, s); }
-      } else {
-        for (int s = 1; s < C4; s <<= 1) { z0 += __shfl_xor(z0, s); z1 += __shfl_xor(z1, s); }
-      }
-      if (j == q) { kz0 = z0; kz1 = z1; kpix = pix; }
-    };
-    if constexpr (C4T != 0) {
-#pragma unroll
-      for (int j = 0; j < C4T; ++j) {
-        const long pix = ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
-        held[j] = pix < pixels ? ld4(a + pix * C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int j = 0; j < C4T; ++j) {
-        const long pix = ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
-        fwd_one(j, pix, pix < pixels, held[j]);
-      }
-    } else {
-      for (int j = 0; j < C4; ++j) {
-        const long pix = ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
-        const bool ok = pix < pixels;
-        fwd_one(j, pix, ok, ok ? ld4(a + pix * C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f});
-      }
-    }
+    head_group_logits<C4T>(hp, L, C4, PPB, q, pl, it0, held, kz0, kz1, kpix);
     float sown = 0.f;                              // dL/dlogit1 of this lane's pixel
     if (kpix < pixels) {
-      const long pix = kpix;
-      const float z0 = kz0 + b0, z1 = kz1 + b1;
-      const float m = fmaxf(z0, z1);
-      const float e0 = expf(z0 - m), e1 = expf(z1 - m);
-      const float pr = e1 / (e0 + e1);
-      p[pix] = pr;
-      const float yt = (float)y[pix];
-      const float pc = fminf(fmaxf(pr, 1e-7f), 1.f - 1e-7f);
-      const float x = logf(pc / (1.f - pc));
-      acc[0] += fmaxf(x, 0.f) - x * yt + log1pf(expf(-fabsf(x)));
-      const float rp = round_half_even(pr);
-      acc[1] += rp * yt;
-      acc[2] += rp;
-      acc[3] += fminf(fmaxf(yt - rp, 0.f), 1.f);
-      acc[4] += yt;
-      acc[5] += yt * pr;
-      acc[6] += pr * pr;
-      acc[7] += yt * yt;
-      acc[8] += pr;
-      acc[9] -= 2.f * yt * logf(pr + 1e-7f) + (1.f - yt) * logf(1.f - pr + 1e-7f);
-      if (loss_kind == 0) {
-        const bool inside = pr > 1e-7f && pr < 1.f - 1e-7f;
-        sown = inside ? (pr - yt) * invM : 0.f;
-      } else {
-        const float dp = -(2.f * yt / (pr + 1e-7f) - (1.f - yt) / (1.f - pr + 1e-7f)) * invM;
-        sown = dp * pr * (1.f - pr);
-      }
-      smax = fmaxf(smax, fabsf(sown));
-    }
-    // backward of the C4 pixels of this group
-    auto bwd_one = [&](int j, f32x4 v, long pix) {
-      const float s = __shfl(sown, lane - q + j);
-      if (pix < pixels) {
-        if (bnin) {
-          const f32x4 zraw = v;
-          v = fma4(v, isc, ish);
-          if (bnred) {
-            const f32x4 xh = (zraw - bmu) * bis;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float dy = (v[e] > 0.f) ? kd[e] * s : 0.f;
-              r1[e] += dy;
-              r2[e] += dy * xh[e];
-            }
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      const float pr = head_prob(kz0 + L.b0, kz1 + L.b1);
+      hp.p[kpix] = pr;
+      if (BWD || hp.y) {
+        const float yt = (float)hp.y[kpix];
+        head_metric_sums(acc, pr, yt);
+        if constexpr (BWD) {
+          sown = head_dlogit(hp.loss_kind == 0 ? 0 : 1, pr, yt, L.invM, 0.f, 1.f, 1.f);
+          smax = fmaxf(smax, fabsf(sown));
         }
-        st4(da + pix * C + 4 * q, kd * s);
-        sa += v * s;
-        if (q == 0) ss += s;
-      }
-    };
-    if constexpr (C4T != 0) {
-#pragma unroll
-      for (int j = 0; j < C4T; ++j) bwd_one(j, held[j], ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl);
-    } else {
-      // (the values are re-read: they were loaded a moment ago)
-      for (int j = 0; j < C4; ++j) {
-        const long pix = ((it0 + j) * gridDim.x + blockIdx.x) * PPB + pl;
-        bwd_one(j, pix < pixels ? ld4(a + pix * C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f}, pix);
       }
     }
-  }
+    if constexpr (BWD) {      // backward of the C4 pixels of this group
+      auto bwd_one = [&](int j, f32x4 v, long pix) {
+        const float s = __shfl(sown, lane - q + j);
+        if (pix < pixels) head_bwd_pixel(hp, L, q, pix, v, s, g);
+      };
+      if constexpr (C4T != 0) {
 #pragma unroll
-  for (int k = 0; k < DC_HEAD_SUMS; ++k) sm[tid][k] = acc[k];
-  sm4[tid] = sa;
-  sms[tid] = (q == 0) ? ss : 0.f;
-  __syncthreads();
-  if (tid < DC_HEAD_SUMS) {
-    double s = 0.0;
-    for (int t = 0; t < 256; ++t) s += (double)sm[t][tid];
-    partial[(long)blockIdx.x * DC_HEAD_SUMS + tid] = (float)s;
-  }
-  if (pl == 0) {
-    for (int k = 1; k < PPB; ++k) sa += sm4[k * C4 + q];
-    st4(gpartial + (long)blockIdx.x * (C + 4) + 4 * q, sa);
-  }
-  if (tid == 0) {
-    float s = 0.f;
-    for (int k = 0; k < PPB; ++k) s += sms[k * C4];
-    gpartial[(long)blockIdx.x * (C + 4) + C] = s;
-  }
-  if (bnred) {
-    __syncthreads();
-    sm4[tid] = r1; sm4b[tid] = r2;
-    __syncthreads();
-    if (pl == 0) {
-      for (int k = 1; k < PPB; ++k) { r1 += sm4[k * C4 + q]; r2 += sm4b[k * C4 + q]; }
-      float* dst = bn_partial + ((long)blockIdx.x * C + 4 * q) * 2;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { dst[2 * e] = r1[e]; dst[2 * e + 1] = r2[e]; }
+        for (int j = 0; j < C4T; ++j) bwd_one(j, held[j], head_group_pix(it0, j, PPB, pl));
+      } else {
+        // (the values are re-read: they were loaded a moment ago)
+        for (int j = 0; j < C4; ++j) {
+          const long pix = head_group_pix(it0, j, PPB, pl);
+          bwd_one(j, pix < pixels ? ld4(hp.a + pix * hp.C + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f}, pix);
+        }
+      }
     }
   }
-  if (amax_partial) {          // every pixel's s is seen by all C/4 lanes of its group: a block-wide max of the per-thread maxima
-    __shared__ float smx[4];
-    __syncthreads();
-    for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o));
-    if ((tid & 63) == 0) smx[tid >> 6] = smax;
-    __syncthreads();
-    if (pl == 0) {
-      const float m = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
-      f32x4 am;
+  if (BWD || hp.partial) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) am[e] = fabsf(kd[e]) * m;
-      st4(amax_partial + (long)blockIdx.x * C + 4 * q, am);
+    for (int k = 0; k < DC_HEAD_SUMS; ++k) sm[tid][k] = acc[k];
+    __syncthreads();
+    if (tid < DC_HEAD_SUMS) {
+      double s = 0.0;
+      for (int t = 0; t < 256; ++t) s += (double)sm[t][tid];
+      hp.partial[(long)blockIdx.x * DC_HEAD_SUMS + tid] = (float)s;
     }
   }
+  if constexpr (BWD) head_bwd_epilogue(hp, L, g, smax, C4, q, pl);
+}
+
+// The backward on its own (any loss kind): reads p, plain grid-stride loop over the pixels.
+__global__ __launch_bounds__(256) void head_bwd_kernel(HeadParams hp) {
+  const int C4 = hp.C >> 2, PPB = 256 / C4;
+  const int tid = threadIdx.x, q = tid % C4, pl = tid / C4;
+  const HeadLane L = head_lane(hp, q, false);
+  float I = 0.f, D = 1.f;
+  if (hp.loss_kind == 2) { I = (float)hp.sums[5]; D = (float)(hp.sums[4] + hp.sums[8] + 1e-7); }
+  if (hp.loss_kind == 3) { I = (float)hp.sums[5]; D = (float)(hp.sums[7] + hp.sums[6] + 1e-7); }
+  const float invD2 = 1.f / (D * D);
+  HeadGrad g{};
+  float smax = 0.f;
+  for (long pix = (long)blockIdx.x * PPB + pl; pix < hp.pixels; pix += (long)gridDim.x * PPB) {
+    const float s = head_dlogit(hp.loss_kind, hp.p[pix], (float)hp.y[pix], L.invM, I, D, invD2);
+    head_bwd_pixel(hp, L, q, pix, ld4(hp.a + pix * hp.C + 4 * q), s, g);
+    smax = fmaxf(smax, fabsf(s));
+  }
+  head_bwd_epilogue(hp, L, g, smax, C4, q, pl);
 }
 
 // partial rows are padded to C+4 floats to keep float4 alignment; one block per output element, fixed order
@@ -1412,7 +1272,20 @@ static int head_blocks(long pixels) {
 extern "C" int dc_head_blocks(long pixels) { return head_blocks(pixels); }
 
 static int head_fwd_impl(const float* a, const float* in_sc, const float* in_sh, const float* kh, const float* bh,
-                         const uint8_t* y, float* p, float* partial, long pixels, int C, dc_stream_t stream);
+                         const uint8_t* y, float* p, float* partial, long pixels, int C, dc_stream_t stream) {
+  DC_REQUIRE(a && kh && bh && p && pixels > 0, DC_EINVAL, "dc_head_fwd: bad arguments");
+  DC_REQUIRE(!y || partial, DC_EINVAL, "dc_head_fwd: y given without a partial buffer");
+  int rc = chan_check("dc_head_fwd", C);
+  if (rc) return rc;
+  DC_REQUIRE(C <= 256, DC_EUNSUP, "dc_head_fwd: C=%d > 256 (the C/4 lanes of a pixel must fit one wave)", C);
+  HeadParams hp{};
+  hp.a = a; hp.in_sc = in_sc; hp.in_sh = in_sh; hp.kh = kh; hp.bh = bh; hp.y = y; hp.p = p;
+  hp.partial = y ? partial : nullptr; hp.pixels = pixels; hp.C = C;
+  hipLaunchKernelGGL((C == 32 ? head_fwd_kernel<8, false> : head_fwd_kernel<0, false>), dim3(head_blocks(pixels)), dim3(256), 0,
+                     (hipStream_t)stream, hp);
+  DC_CHECK_LAUNCH("dc_head_fwd");
+  return DC_OK;
+}
 extern "C" int dc_head_fwd(const float* a, const float* kh, const float* bh, const uint8_t* y, float* p, float* partial,
                            long pixels, int C, dc_stream_t stream) {
   return head_fwd_impl(a, nullptr, nullptr, kh, bh, y, p, partial, pixels, C, stream);
@@ -1423,40 +1296,6 @@ extern "C" int dc_head_fwd_bnin(const float* z, const float* in_scale, const flo
   DC_REQUIRE(in_scale && in_shift, DC_EINVAL, "dc_head_fwd_bnin: null scale/shift");
   return head_fwd_impl(z, in_scale, in_shift, kh, bh, y, p, partial, pixels, C, stream);
 }
-static int head_fwd_impl(const float* a, const float* in_sc, const float* in_sh, const float* kh, const float* bh,
-                         const uint8_t* y, float* p, float* partial, long pixels, int C, dc_stream_t stream) {
-  DC_REQUIRE(a && kh && bh && p && pixels > 0, DC_EINVAL, "dc_head_fwd: bad arguments");
-  DC_REQUIRE(!y || partial, DC_EINVAL, "dc_head_fwd: y given without a partial buffer");
-  int rc = chan_check("dc_head_fwd", C);
-  if (rc) return rc;
-  DC_REQUIRE(C <= 256, DC_EUNSUP, "dc_head_fwd: C=%d > 256 (the C/4 lanes of a pixel must fit one wave)", C);
-  hipLaunchKernelGGL(C == 32 ? head_fwd_kernel<8> : head_fwd_kernel<0>, dim3(head_blocks(pixels)), dim3(256), 0, (hipStream_t)stream, a, kh, bh, y, p,
-                     y ? partial : nullptr, pixels, C, in_sc, in_sh);
-  DC_CHECK_LAUNCH("dc_head_fwd");
-  return DC_OK;
-}
-static int head_bwd_impl(const float* a, const float* in_sc, const float* in_sh, const float* p, const uint8_t* y,
-                         const float* kh, float* da, float* partial, int loss_kind, const double* sums, long pixels,
-                         int C, dc_stream_t stream, const float* bn_mean = nullptr, const float* bn_invstd = nullptr,
-                         float* bn_partial = nullptr, float* amax_partial = nullptr);
-extern "C" int dc_head_bwd(const float* a, const float* p, const uint8_t* y, const float* kh, float* da, float* partial,
-                           int loss_kind, const double* sums, long pixels, int C, dc_stream_t stream) {
-  return head_bwd_impl(a, nullptr, nullptr, p, y, kh, da, partial, loss_kind, sums, pixels, C, stream);
-}
-extern "C" int dc_head_bwd_bnin(const float* z, const float* in_scale, const float* in_shift, const float* p,
-                                const uint8_t* y, const float* kh, float* da, float* partial, int loss_kind,
-                                const double* sums, long pixels, int C, dc_stream_t stream) {
-  DC_REQUIRE(in_scale && in_shift, DC_EINVAL, "dc_head_bwd_bnin: null scale/shift");
-  return head_bwd_impl(z, in_scale, in_shift, p, y, kh, da, partial, loss_kind, sums, pixels, C, stream);
-}
-extern "C" int dc_head_bwd_bnin_bnred(const float* z, const float* in_scale, const float* in_shift, const float* p,
-                                      const uint8_t* y, const float* kh, float* da, float* partial, int loss_kind,
-                                      const double* sums, const float* bn_mean, const float* bn_invstd,
-                                      float* bn_partial, float* amax_partial, long pixels, int C, dc_stream_t stream) {
-  DC_REQUIRE(in_scale && in_shift && bn_mean && bn_invstd && bn_partial, DC_EINVAL, "dc_head_bwd_bnin_bnred: null pointer");
-  return head_bwd_impl(z, in_scale, in_shift, p, y, kh, da, partial, loss_kind, sums, pixels, C, stream, bn_mean,
-                       bn_invstd, bn_partial, amax_partial);
-}
 static int head_bwd_impl(const float* a, const float* in_sc, const float* in_sh, const float* p, const uint8_t* y,
                          const float* kh, float* da, float* partial, int loss_kind, const double* sums, long pixels,
                          int C, dc_stream_t stream, const float* bn_mean, const float* bn_invstd, float* bn_partial,
@@ -1465,10 +1304,33 @@ static int head_bwd_impl(const float* a, const float* in_sc, const float* in_sh,
   DC_REQUIRE(loss_kind >= 0 && loss_kind <= 3 && (loss_kind < 2 || sums), DC_EINVAL, "dc_head_bwd: bad loss_kind / sums");
   int rc = chan_check("dc_head_bwd", C);
   if (rc) return rc;
-  hipLaunchKernelGGL(head_bwd_kernel, dim3(head_blocks(pixels)), dim3(256), 0, (hipStream_t)stream, a, p, y, kh, da,
-                     partial, pixels, C, loss_kind, sums, in_sc, in_sh, bn_mean, bn_invstd, bn_partial, amax_partial);
+  HeadParams hp{};
+  hp.a = a; hp.in_sc = in_sc; hp.in_sh = in_sh; hp.p = const_cast<float*>(p); hp.y = y; hp.kh = kh; hp.da = da;
+  hp.gpartial = partial; hp.loss_kind = loss_kind; hp.sums = sums; hp.bn_mean = bn_mean; hp.bn_invstd = bn_invstd;
+  hp.bn_partial = bn_partial; hp.amax_partial = amax_partial; hp.pixels = pixels; hp.C = C;
+  hipLaunchKernelGGL(head_bwd_kernel, dim3(head_blocks(pixels)), dim3(256), 0, (hipStream_t)stream, hp);
   DC_CHECK_LAUNCH("dc_head_bwd");
   return DC_OK;
+}
+extern "C" int dc_head_bwd(const float* a, const float* p, const uint8_t* y, const float* kh, float* da, float* partial,
+                           int loss_kind, const double* sums, long pixels, int C, dc_stream_t stream) {
+  return head_bwd_impl(a, nullptr, nullptr, p, y, kh, da, partial, loss_kind, sums, pixels, C, stream, nullptr, nullptr,
+                       nullptr, nullptr);
+}
+extern "C" int dc_head_bwd_bnin(const float* z, const float* in_scale, const float* in_shift, const float* p,
+                                const uint8_t* y, const float* kh, float* da, float* partial, int loss_kind,
+                                const double* sums, long pixels, int C, dc_stream_t stream) {
+  DC_REQUIRE(in_scale && in_shift, DC_EINVAL, "dc_head_bwd_bnin: null scale/shift");
+  return head_bwd_impl(z, in_scale, in_shift, p, y, kh, da, partial, loss_kind, sums, pixels, C, stream, nullptr, nullptr,
+                       nullptr, nullptr);
+}
+extern "C" int dc_head_bwd_bnin_bnred(const float* z, const float* in_scale, const float* in_shift, const float* p,
+                                      const uint8_t* y, const float* kh, float* da, float* partial, int loss_kind,
+                                      const double* sums, const float* bn_mean, const float* bn_invstd,
+                                      float* bn_partial, float* amax_partial, long pixels, int C, dc_stream_t stream) {
+  DC_REQUIRE(in_scale && in_shift && bn_mean && bn_invstd && bn_partial, DC_EINVAL, "dc_head_bwd_bnin_bnred: null pointer");
+  return head_bwd_impl(z, in_scale, in_shift, p, y, kh, da, partial, loss_kind, sums, pixels, C, stream, bn_mean,
+                       bn_invstd, bn_partial, amax_partial);
 }
 extern "C" int dc_head_fwd_bwd(const float* a, const float* in_scale, const float* in_shift, const float* kh,
                                const float* bh, const uint8_t* y, float* p, float* partial, float* da, float* grad_partial,
@@ -1482,9 +1344,12 @@ extern "C" int dc_head_fwd_bwd(const float* a, const float* in_scale, const floa
   int rc = chan_check("dc_head_fwd_bwd", C);
   if (rc) return rc;
   DC_REQUIRE(C <= 64, DC_EUNSUP, "dc_head_fwd_bwd: C=%d > 64 (the C/4 lanes of a pixel group must divide a wave)", C);
-  hipLaunchKernelGGL(C == 32 ? head_fwd_bwd_kernel<8> : head_fwd_bwd_kernel<0>, dim3(head_blocks(pixels)), dim3(256), 0, (hipStream_t)stream, a, kh, bh, y, p,
-                     partial, da, grad_partial, pixels, C, loss_kind, in_scale, in_shift, bn_mean, bn_invstd, bn_partial,
-                     amax_partial);
+  HeadParams hp{};
+  hp.a = a; hp.in_sc = in_scale; hp.in_sh = in_shift; hp.kh = kh; hp.bh = bh; hp.y = y; hp.p = p; hp.partial = partial;
+  hp.da = da; hp.gpartial = grad_partial; hp.loss_kind = loss_kind; hp.bn_mean = bn_mean; hp.bn_invstd = bn_invstd;
+  hp.bn_partial = bn_partial; hp.amax_partial = amax_partial; hp.pixels = pixels; hp.C = C;
+  hipLaunchKernelGGL((C == 32 ? head_fwd_kernel<8, true> : head_fwd_kernel<0, true>), dim3(head_blocks(pixels)), dim3(256), 0,
+                     (hipStream_t)stream, hp);
   DC_CHECK_LAUNCH("dc_head_fwd_bwd");
   return DC_OK;
 }

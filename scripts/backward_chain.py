@@ -40,7 +40,7 @@ for r in rows:
 rows.sort(key=lambda r: r['s'])
 # step boundaries: the head kernel (forward's last / backward's first launch) of consecutive steps; a step's backward ends with its
 # last adam_kernel (the deferred tail issues two or three Adam launches per step)
-heads = [i for i, r in enumerate(rows) if r['k'].startswith('head_fwd_bwd') or r['k'].startswith('head_bwd')]
+heads = [i for i, r in enumerate(rows) if re.match(r'head_fwd_kernel<\d+,true>|head_bwd', r['k'])]
 # bench.py's LAST steps run with one stream / launch by launch (roofline instrumentation): take a step of the timed region
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 h0, h1 = heads[k], heads[k + 1]

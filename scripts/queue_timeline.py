@@ -17,7 +17,7 @@ rows = [r for r in csv.DictReader(open(sys.argv[1])) if 'at::native' not in r['K
 for r in rows:
     r['s'], r['e'], r['k'] = int(r['Start_Timestamp']), int(r['End_Timestamp']), short(r['Kernel_Name'])
 rows.sort(key=lambda r: r['s'])
-heads = [i for i, r in enumerate(rows) if r['k'].startswith('head_fwd_bwd') or r['k'].startswith('head_bwd')]
+heads = [i for i, r in enumerate(rows) if re.match(r'head_fwd_kernel<\d+,true>|head_bwd', r['k'])]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 h0 = heads[k]
 prev_adam = max(i for i in range(heads[k - 1], h0) if rows[i]['k'].startswith('adam_kernel'))

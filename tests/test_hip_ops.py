@@ -666,12 +666,10 @@ def test_inference_conv_with_pooled_output_equals_conv_then_pool(dclib, N, H, W,
     assert L.dc_conv3x3_fwd_pool_blocks(2, 16, 16, 64, 64) == 0 and L.dc_conv3x3_fwd_pool_blocks(2, 63, 64, 64, 64) == 0
 
 
-@pytest.mark.parametrize('C,pixels,kind,bnin', [(32, 5000, 0, True), (8, 777, 1, True), (4, 64, 0, False), (64, 4097, 0, True), (16, 300, 1, False)])
-def test_head_fused_forward_backward_equals_separate_calls(dclib, C, pixels, kind, bnin):
+def _head_fused_equals_separate(L, C, pixels, kind, bnin):
     """dc_head_fwd_bwd (training with a per-pixel loss) against dc_head_fwd followed by dc_head_bwd(_bnin_bnred): p, da
     and the metric partial sums bit for bit (same per-pixel arithmetic), the head's weight gradient and the producing
     BatchNorm layer's backward sums to summation-order accuracy (same terms, different order inside a block)."""
-    L = dclib
     rs = np.random.RandomState(C + pixels)
     a = dev((rs.standard_normal((pixels, C)) * 1.5).astype(np.float32))
     kh = dev((rs.standard_normal((C, 2)) * 0.4).astype(np.float32)); bh = dev(rs.standard_normal(2).astype(np.float32) * 0.1)
@@ -716,10 +714,61 @@ def test_head_fused_forward_backward_equals_separate_calls(dclib, C, pixels, kin
             assert np.all(am >= amax_ref * (1 - 1e-6)) and np.all(am <= amax_ref * (1 + 1e-6) + 1e-30), (am, amax_ref)
     for k in ('dk', 'db') + (('dg', 'dbt') if bnin else ()):
         x, z = A[k].cpu().numpy().astype(np.float64), B[k].cpu().numpy().astype(np.float64)
+        print('%s: fused - separate %.3g of the maximum' % (k, np.abs(x - z).max() / max(np.abs(x).max(), 1e-30)))
         assert np.abs(x - z).max() <= 2e-6 * max(np.abs(x).max(), 1e-30), (k, x, z)
     with pytest.raises(Exception):
         L.dc_head_fwd_bwd(a.data_ptr(), scp, shp, kh.data_ptr(), bh.data_ptr(), y.data_ptr(), B['p'].data_ptr(), B['part'].data_ptr(), B['da'].data_ptr(),
                           B['gp'].data_ptr(), 2, None, None, None, None, pixels, C, None)
+
+
+@pytest.mark.parametrize('C,pixels,kind,bnin', [(32, 5000, 0, True), (8, 777, 1, True), (4, 64, 0, False), (64, 4097, 0, True), (16, 300, 1, False)])
+def test_head_fused_forward_backward_equals_separate_calls(dclib, C, pixels, kind, bnin):
+    _head_fused_equals_separate(dclib, C, pixels, kind, bnin)
+
+
+@pytest.mark.parametrize('kind,bnin', [(0, True), (1, False)])
+@pytest.mark.parametrize('C,pixels', [(32, 262144 + 777), (8, 262144 + 777), (4, 1), (32, 1), (64, 1), (4, 255), (32, 255), (64, 255)])
+def test_head_fused_equals_separate_at_the_group_loop_edges(dclib, C, pixels, kind, bnin):
+    """The same comparison where the pixel-group loop leaves its single full pass.  262 921 pixels: dc_head_blocks is at its
+    cap of 1 024 and the loop takes a second, ragged pass (most workgroups idle, some groups partly filled).  1 and 255
+    pixels: one pixel, and one short of a full block of groups, at one lane per pixel without a shuffle (C = 4), on the
+    C == 32 path that issues a group's loads together, and at the widest C the fused kernel takes (64)."""
+    assert dclib.dc_head_blocks(pixels) == (1024 if pixels > 262144 else 1)
+    _head_fused_equals_separate(dclib, C, pixels, kind, bnin)
+
+
+@pytest.mark.parametrize('C', [32, 256])
+@pytest.mark.parametrize('bnin', [False, True])
+def test_head_forward_without_labels(dclib, C, bnin):
+    """dc_head_fwd / dc_head_fwd_bnin with y == NULL and partial == NULL (inference): the p of the same call with labels, bit
+    for bit; at C = 256 (one pixel per wave, past what the fused kernel takes) within 1e-6 of the float64 oracle."""
+    L = dclib
+    pixels = 777
+    rs = np.random.RandomState(C + pixels)
+    a = (rs.standard_normal((pixels, C)) * 1.5).astype(np.float32)
+    kh = (rs.standard_normal((C, 2)) * 0.4).astype(np.float32); bh = (rs.standard_normal(2) * 0.1).astype(np.float32)
+    sc = (rs.random_sample(C) + 0.5).astype(np.float32); sh = (rs.standard_normal(C) * 0.3).astype(np.float32)
+    y = dev((rs.random_sample(pixels) < 0.2).astype(np.uint8))
+    ad, kd, bd, scd, shd = dev(a), dev(kh), dev(bh), dev(sc), dev(sh)
+    hb = L.dc_head_blocks(pixels)
+    ps = []
+    for yp in (y.data_ptr(), None):
+        p = torch.full((pixels,), float('nan'), device='cuda')
+        part = torch.zeros(hb * 12, device='cuda')
+        pp = part.data_ptr() if yp else None
+        if bnin:
+            L.dc_head_fwd_bnin(ad.data_ptr(), scd.data_ptr(), shd.data_ptr(), kd.data_ptr(), bd.data_ptr(), yp, p.data_ptr(), pp, pixels, C, None)
+        else:
+            L.dc_head_fwd(ad.data_ptr(), kd.data_ptr(), bd.data_ptr(), yp, p.data_ptr(), pp, pixels, C, None)
+        torch.cuda.synchronize()
+        ps.append(p.cpu().numpy())
+    assert np.isfinite(ps[0]).all() and np.array_equal(ps[0], ps[1])
+    if C == 256:
+        # the activation as the kernel forms it on load: relu(fmaf(z, sc, sh)) rounded to fp32 (the float64 product is exact)
+        act = np.maximum((a.astype(np.float64) * sc + sh).astype(np.float32), 0) if bnin else a
+        p_ref, _ = on.head_fwd(act.astype(np.float64), kh.astype(np.float64).reshape(1, 1, C, 2), bh.astype(np.float64))
+        print('p - oracle: %.3g' % np.abs(ps[1] - p_ref.reshape(-1)).max())
+        assert np.abs(ps[1] - p_ref.reshape(-1)).max() < 1e-6
 
 
 @pytest.mark.parametrize('N,H,W,C,drop', [(2, 16, 16, 32, 'rng'), (1, 12, 20, 8, 'mask'), (3, 8, 8, 64, 'none'), (1, 64, 64, 256, 'rng')])
