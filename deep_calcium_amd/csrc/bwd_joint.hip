@@ -20,60 +20,13 @@
 // Numerics: those of igemm_f16x3.hip / wgrad_f16x3.hip (split-fp16 operands, power-of-two range-guard scales undone in
 // the epilogues, fp32 accumulation); the summation order differs from the separate kernels (tile shape), same tolerance.
 #include "wgrad_common.h"
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short tr_v4i16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "f16x3_common.h"
 
 // DC_JOINT_ABL (timing experiments only, results are garbage): 1 data-gradient waves skip their MFMA block, 2 weight-gradient
 // waves skip theirs, 4 producers do not split / write LDS, 8 producers do not load
 #ifndef DC_JOINT_ABL
 #define DC_JOINT_ABL 0
 #endif
-namespace bj {
-constexpr int C = 32;
-constexpr int TH = 4, TW = 32, THI = TH + 2, TWI = TW + 2, NPIX = THI * TWI;      // 204 halo'd pixels
-constexpr int PLANE = 13312;                 // NPIX * 64 bytes rounded up to a multiple of 1024 (the swizzle reads address bits 8-9)
-constexpr int IMG = 2 * PLANE;               // hi | lo
-constexpr int RAW = TH * TW * C * 4;          // the tile's interior x values as loaded (fp32): the pre-BN tensor of the layer in front
-constexpr int STAGE = 2 * IMG + RAW;         // dz image | x image | raw interior x
-constexpr int W_SLOTS = 9 * 4 * 2 * C;       // packed data-gradient weights: [tap][k8][hi|lo][col] 16-byte slots
-constexpr int LDS_BYTES = 2 * STAGE + 64;
-constexpr int THREADS = 512;
-constexpr int NL = (NPIX * 8 + 255) / 256;   // float4 loads per producer thread and tensor (7)
-constexpr unsigned OOB = 0x80000000u;
-static_assert(LDS_BYTES <= 160 * 1024 && NPIX * 64 <= PLANE && PLANE % 1024 == 0 && STAGE % 1024 == 0, "LDS plan");
-
-// 16-byte chunk c of pixel p lives at chunk c ^ ((p >> 2) & 3): eight consecutive pixels read the same chunk of
-// their 64-byte rows from eight different bank groups; a 4-aligned pixel group keeps its chunks together (tr reads)
-__device__ __forceinline__ int swz(int rel) { return rel ^ ((rel >> 4) & 0x30); }
-
-__device__ __forceinline__ void split4(const f32x4 v, float s, u32x2& hi, u32x2& lo) {
-  unsigned h01, h23, l01, l23;
-  asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
-      "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
-      "v_fma_mixhi_f16 %0, %5, %8, 0\n\t"
-      "v_fma_mixhi_f16 %1, %7, %8, 0\n\t"
-      "v_fma_mixlo_f16 %2, %4, %8, -%0 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixlo_f16 %3, %6, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %2, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %3, %7, %8, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-      : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23)
-      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(s));
-  hi = u32x2{h01, h23};
-  lo = u32x2{l01, l23};
-}
-
-__device__ __forceinline__ f16x8 tr_frag(const char* base, int off1, int off2) {
-  typedef __attribute__((address_space(3))) tr_v4i16* lds_p;
-  const tr_v4i16 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base + off1));
-  const tr_v4i16 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base + off2));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-  return __builtin_bit_cast(f16x8, v);
-}
-}  // namespace bj
 
 struct JointParams {
   const float* x; const float* xSc; const float* xSh; const float* xAbound;
@@ -85,6 +38,180 @@ struct JointParams {
   float* slabs;
   int N, H, W, tilesX, tilesY;
 };
+
+namespace bj {
+constexpr int C = 32;
+constexpr int TH = 4, TW = 32, THI = TH + 2, TWI = TW + 2, NPIX = THI * TWI;      // 204 halo'd pixels
+// An fp16 image of the halo'd tile: [hi | lo plane][pixel][ROW bytes of channels], 16-byte chunks XOR-swizzled.
+struct Rows64 {          // 32 channels (dz; x of the 32 -> 32 kernel)
+  static constexpr int ROW = 64, PLANE = 13312;     // NPIX * 64 bytes rounded up to a multiple of 1024 (the swizzle reads address bits 8-9)
+  // 16-byte chunk c of pixel p lives at chunk c ^ ((p >> 2) & 3): eight consecutive pixels read the same chunk of
+  // their 64-byte rows from eight different bank groups; a 4-aligned pixel group keeps its chunks together (tr reads)
+  static __device__ __forceinline__ int swz(int rel) { return rel ^ ((rel >> 4) & 0x30); }
+};
+struct Rows128 {         // 64 channels (x of the 64 -> 32 kernel)
+  static constexpr int ROW = 128, PLANE = 26624;    // NPIX * 128 bytes rounded up to a multiple of 1024
+  static __device__ __forceinline__ int swz(int rel) { return rel ^ ((rel >> 2) & 0x40); }     // chunk ^= 4 * bit 1 of the pixel
+};
+constexpr int PLANE = Rows64::PLANE;
+constexpr int IMG = 2 * PLANE;               // hi | lo
+constexpr int RAW = TH * TW * C * 4;          // the tile's interior x values as loaded (fp32): the pre-BN tensor of the layer in front
+constexpr int STAGE = 2 * IMG + RAW;         // dz image | x image | raw interior x
+constexpr int W_SLOTS = 9 * 4 * 2 * C;       // packed data-gradient weights: [tap][k8][hi|lo][col] 16-byte slots
+constexpr int LDS_BYTES = 2 * STAGE + 64;
+constexpr int THREADS = 512;
+constexpr int NL = (NPIX * 8 + 255) / 256;   // float4 loads per producer thread and tensor (7)
+constexpr unsigned OOB = 0x80000000u;
+static_assert(LDS_BYTES <= 160 * 1024 && NPIX * 64 <= PLANE && PLANE % 1024 == 0 && STAGE % 1024 == 0, "LDS plan");
+
+// This workgroup's tiles: each XCD walks a contiguous range of the (image, column, row) list -- consecutive positions
+// are vertically adjacent tiles whose halo rows overlap --, its workgroups striding through it (igemm_pp.hip)
+struct Tile { int img, y0, x0; };
+__device__ __forceinline__ DcXcdRange tile_range(const JointParams& p) {
+  return dc_xcd_range(blockIdx.x, (int)gridDim.x, p.N * p.tilesX * p.tilesY);
+}
+__device__ __forceinline__ Tile decode(const JointParams& p, const DcXcdRange& tiles, int j) {
+  const int work = tiles.work(j);
+  const int ty = work % p.tilesY, t2 = work / p.tilesY;
+  Tile t;
+  t.x0 = (t2 % p.tilesX) * TW; t.img = t2 / p.tilesX; t.y0 = ty * TH;
+  return t;
+}
+// image position of halo'd pixel `pix` of a tile; false outside the image and for the slots behind the tile's last pixel
+__device__ __forceinline__ bool halo_pixel(const JointParams& p, const Tile& tl, int pix, int& y, int& xx) {
+  const int r = __umul24(pix, (65536 + TWI - 1) / TWI) >> 16;          // pix / TWI
+  const int c = pix - __umul24(r, TWI);
+  y = tl.y0 - 1 + r; xx = tl.x0 - 1 + c;
+  return pix < NPIX && (unsigned)y < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;
+}
+
+// The dz producer: thread t of the 256 holds channel quad q = t & 7 of the pixels pb + 32 k, pb = t >> 3 -- its rows of
+// dc_bn_bwd_finalize_dzin's table, the (da, z) request and the dz image of a stage.
+struct DzProducer {
+  int q, pb;
+  f32x4 sc, sh, mu, A, D, E;
+  __device__ __forceinline__ DzProducer(const float* coef, int t) : q(t & 7), pb(t >> 3) {
+    const float* ct = coef + 4 * q;
+    sc = *reinterpret_cast<const f32x4*>(ct); sh = *reinterpret_cast<const f32x4*>(ct + C);
+    mu = *reinterpret_cast<const f32x4*>(ct + 2 * C); A = *reinterpret_cast<const f32x4*>(ct + 3 * C);
+    D = *reinterpret_cast<const f32x4*>(ct + 4 * C); E = *reinterpret_cast<const f32x4*>(ct + 5 * C);
+  }
+  // live: bit k = pixel pb + 32 k lies inside the image (the x request of the same tile asks for the same pixels)
+  __device__ __forceinline__ void request(const JointParams& p, const Tile& tl, f32x4 (&ra)[NL], f32x4 (&rz)[NL], unsigned& live) const {
+    live = 0u;
+    const long img_floats = (long)p.H * p.W * C;
+    const __amdgpu_buffer_rsrc_t rsA = dc_make_rsrc(p.da + tl.img * img_floats, (unsigned)(img_floats * 4));
+    const __amdgpu_buffer_rsrc_t rsZ = dc_make_rsrc(p.z + tl.img * img_floats, (unsigned)(img_floats * 4));
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+      int y, xx;
+      const bool ok = halo_pixel(p, tl, pb + 32 * k, y, xx);
+      const unsigned off = ok ? (unsigned)(((y * p.W + xx) * C + 4 * q) * 4) : OOB;
+      ra[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
+      rz[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsZ, off, 0, 0));
+      if (ok) live |= 1u << k;
+    }
+  }
+  __device__ __forceinline__ void stage(const f32x4 (&ra)[NL], const f32x4 (&rz)[NL], unsigned live, float dz_scale, char* set) const {
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+      const int pix = pb + 32 * k;
+      const bool lv = (live >> k) & 1u;
+      f32x4 dzv;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)         // outside the image dz is zero, not E - D*mu
+        dzv[e] = lv ? dc_dz_on_load(rz[k][e], ra[k][e], sc[e], sh[e], mu[e], A[e], D[e], E[e]) : 0.f;
+      u32x2 dh, dl;
+      dc_split_f16(dzv, dz_scale, dh, dl);
+      if (pix < NPIX) {
+        const int off = Rows64::swz(pix * 64 + q * 8);
+        *reinterpret_cast<u32x2*>(set + off) = dh;
+        *reinterpret_cast<u32x2*>(set + PLANE + off) = dl;
+      }
+    }
+  }
+};
+
+// The producers' schedule over two LDS stages of STAGE_BYTES.  x: two register sets (tile t+2 in flight while t+1 is split);
+// (da, z): one set, requested right after the previous tile's has been split -- one tile of MFMA time ahead (wgrad_f16x3.hip's
+// B1 scheme: 2 x (x + da + z) does not fit).  request_x(j, set) / stage_x(set, stage) / request_dz(j) / stage_dz(stage).
+template <int STAGE_BYTES, class X, class RX, class RD, class SX, class SD>
+__device__ __forceinline__ void produce(char* smem, int nt, X& x0, X& x1, RX request_x, RD request_dz, SX stage_x, SD stage_dz) {
+  constexpr bool LOAD = !(DC_JOINT_ABL & 8), SPLIT = !(DC_JOINT_ABL & 4);
+  if (nt > 0) {
+    request_x(0, x0);
+    request_dz(0);
+    if (nt > 1) request_x(1, x1);
+    stage_x(x0, smem);
+    stage_dz(smem);
+    if (nt > 1) request_dz(1);
+  }
+  __syncthreads();
+  for (int i = 0; i < nt; i += 2) {
+    if (LOAD && i + 2 < nt) request_x(i + 2, x0);
+    if (SPLIT && i + 1 < nt) { stage_x(x1, smem + STAGE_BYTES); stage_dz(smem + STAGE_BYTES); }
+    if (LOAD && i + 2 < nt) request_dz(i + 2);
+    __syncthreads();
+    if (i + 1 < nt) {
+      if (LOAD && i + 3 < nt) request_x(i + 3, x1);
+      if (SPLIT && i + 2 < nt) { stage_x(x0, smem); stage_dz(smem); }
+      if (LOAD && i + 3 < nt) request_dz(i + 3);
+      __syncthreads();
+    }
+  }
+}
+
+// Data gradient, group g = (tap, 16-channel half): the dz fragments of a wave's two pixel rows (lane offsets ar0, ar1) at
+// the tap's shifted window (ds_read_b128, conflict-free through the swizzle)
+__device__ __forceinline__ void fetch_dz_window(const char* cur, int g, int ar0, int ar1, f16x8 (&ah)[2], f16x8 (&al)[2]) {
+  const int tap = g >> 1, ks = g & 1;
+  const int toff = ((tap / 3) * TWI + (tap % 3)) * 64 + ks * 32;
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb) {
+    const int ao = Rows64::swz((mb ? ar1 : ar0) + toff);
+    ah[mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(cur + ao));
+    al[mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(cur + PLANE + ao));
+  }
+}
+
+// Weight gradient of one staged tile: NG (k-step, tap) groups of 3 MFMAs into the 9 tap accumulators, k-step = (row, 16-pixel
+// half); A = the x image (layout XR, behind the dz image) at the tap's shifted window, B = dz, both through the transposing
+// reads.  The x fragments of group g+1 (and the dz fragments of the next k-step) are requested before the MFMAs of group g
+// issue.  lx / lz: the lane's byte offset inside the x / dz image (first row of its slice, its group of 4 contraction
+// pixels, its chunk).
+template <class XR, int NG>
+__device__ __forceinline__ void wgrad_tile(const char* cur, int lx, int lz, f32x16 (&acc)[9]) {
+  f16x8 ah[2], al[2], bh[2], bl[2];
+  auto fetch_a = [&](int g, int buf) __attribute__((always_inline)) {
+    const int ks = g / 9, tap = g % 9;
+    const int r = ks >> 1, xs = ks & 1;
+    const int pbase = lx + ((r + tap / 3) * TWI + 16 * xs + tap % 3) * XR::ROW;
+    const int a0 = XR::swz(pbase), a1 = XR::swz(pbase + 4 * XR::ROW);
+    ah[buf] = dc_tr_frag(cur + IMG, a0, a1);
+    al[buf] = dc_tr_frag(cur + IMG + XR::PLANE, a0, a1);
+  };
+  auto fetch_b = [&](int ks, int buf) __attribute__((always_inline)) {
+    const int r = ks >> 1, xs = ks & 1;
+    const int brel = lz + ((r + 1) * TWI + 16 * xs + 1) * 64;
+    const int b0 = Rows64::swz(brel), b1 = Rows64::swz(brel + 4 * 64);
+    bh[buf] = dc_tr_frag(cur, b0, b1);
+    bl[buf] = dc_tr_frag(cur + PLANE, b0, b1);
+  };
+  fetch_b(0, 0);
+  fetch_a(0, 0);
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int ca = g & 1, ks = g / 9, tap = g % 9, cbuf = ks & 1;
+    if (g + 1 < NG) {
+      fetch_a(g + 1, ca ^ 1);
+      if ((g + 1) % 9 == 0) fetch_b(ks + 1, cbuf ^ 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    dc_mfma3(ah[ca], al[ca], bh[cbuf], bl[cbuf], acc[tap]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+}  // namespace bj
 
 __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams p) {
   using namespace bj;
@@ -99,72 +226,33 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
   // the layer in front's pre-BN values for its fused sums: when that tensor IS the x operand (BN + ReLU on load: x = its z) the
   // producers leave the tile's interior values in LDS as they loaded them -- no second trip to HBM (537 MB per launch less)
   const bool red_lds = p.redZ != nullptr && p.redZ == p.x;
-
-  // this workgroup's tiles: each XCD walks a contiguous range of the (image, column, row) list -- consecutive positions
-  // are vertically adjacent tiles whose halo rows overlap --, its workgroups striding through it (igemm_pp.hip)
-  const int total = p.N * p.tilesX * p.tilesY;
-  const int G = (int)gridDim.x, xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int nx = (G + 7 - xcd) >> 3;
-  const int qq = total >> 3, rr = total & 7;
-  const int xstart = xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq;
-  const int xcount = qq + (xcd < rr ? 1 : 0);
-  const int nt = seq < xcount ? (xcount - seq + nx - 1) / nx : 0;
-  struct Tile { int img, y0, x0; };
-  auto decode = [&](int j) __attribute__((always_inline)) {
-    const int work = xstart + seq + j * nx;
-    const int ty = work % p.tilesY, t2 = work / p.tilesY;
-    Tile t;
-    t.x0 = (t2 % p.tilesX) * TW; t.img = t2 / p.tilesX; t.y0 = ty * TH;
-    return t;
-  };
+  const DcXcdRange tiles = tile_range(p);
+  const int nt = tiles.nt;
   const long img_floats = (long)p.H * p.W * C;
 
   if (wave >= 4) {
     // ============================ producers: HBM -> registers -> the two fp16 hi/lo images =============================
-    const int t = tid & 255, q = t & 7, pb = t >> 3;               // channel quad, first pixel
+    const DzProducer dzp(p.dzCoef, tid & 255);
+    const int q = dzp.q, pb = dzp.pb;                              // x: the same channel quad and pixels as dz
     const bool xbn = p.xSc != nullptr;
     f32x4 x_sc = {1.f, 1.f, 1.f, 1.f}, x_sh = {0.f, 0.f, 0.f, 0.f};
     if (xbn) { x_sc = *reinterpret_cast<const f32x4*>(p.xSc + 4 * q); x_sh = *reinterpret_cast<const f32x4*>(p.xSh + 4 * q); }
-    const float* ct = p.dzCoef + 4 * q;
-    const f32x4 g_sc = *reinterpret_cast<const f32x4*>(ct), g_sh = *reinterpret_cast<const f32x4*>(ct + C),
-                d_mu = *reinterpret_cast<const f32x4*>(ct + 2 * C), d_A = *reinterpret_cast<const f32x4*>(ct + 3 * C),
-                d_D = *reinterpret_cast<const f32x4*>(ct + 4 * C), d_E = *reinterpret_cast<const f32x4*>(ct + 5 * C);
-
-    // lane-constant part of the global offsets / the image positions of this thread's NL pixels are recomputed per request
+    // the image positions of this thread's NL pixels are recomputed per request
     // (registers: the two x sets + one (da, z) set + the per-channel tables are what the producers hold)
-    auto voff = [&](const Tile& tl, int k, bool& ok) {
-      const int pix = pb + 32 * k;
-      const int r = __umul24(pix, (65536 + TWI - 1) / TWI) >> 16;          // pix / TWI
-      const int c = pix - __umul24(r, TWI);
-      const int y = tl.y0 - 1 + r, xx = tl.x0 - 1 + c;
-      ok = pix < NPIX && (unsigned)y < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;
-      return ok ? (unsigned)(((y * p.W + xx) * C + 4 * q) * 4) : OOB;
-    };
-    auto request_x = [&](int j, f32x4 (&rx)[NL], unsigned& live) {
-      live = 0u;
-      const Tile tl = decode(j);
+    f32x4 rx0[NL], rx1[NL], ra[NL], rz[NL];
+    unsigned live = 0u;                                           // of the tile whose (da, z) are in ra, rz: the one staged next
+    auto request_x = [&](int j, f32x4 (&rx)[NL]) __attribute__((always_inline)) {
+      const Tile tl = decode(p, tiles, j);
       const __amdgpu_buffer_rsrc_t rsX = dc_make_rsrc(p.x + tl.img * img_floats, (unsigned)(img_floats * 4));
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
-        bool ok;
-        const unsigned off = voff(tl, k, ok);
+        int y, xx;
+        const bool ok = halo_pixel(p, tl, pb + 32 * k, y, xx);
+        const unsigned off = ok ? (unsigned)(((y * p.W + xx) * C + 4 * q) * 4) : OOB;
         rx[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsX, off, 0, 0));
-        if (ok) live |= 1u << k;
       }
     };
-    auto request_dz = [&](int j, f32x4 (&ra)[NL], f32x4 (&rz)[NL]) {
-      const Tile tl = decode(j);
-      const __amdgpu_buffer_rsrc_t rsA = dc_make_rsrc(p.da + tl.img * img_floats, (unsigned)(img_floats * 4));
-      const __amdgpu_buffer_rsrc_t rsZ = dc_make_rsrc(p.z + tl.img * img_floats, (unsigned)(img_floats * 4));
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        bool ok;
-        const unsigned off = voff(tl, k, ok);
-        ra[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
-        rz[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsZ, off, 0, 0));
-      }
-    };
-    auto stage_x = [&](const f32x4 (&rx)[NL], unsigned live, char* set) {
+    auto stage_x = [&](const f32x4 (&rx)[NL], char* set) __attribute__((always_inline)) {
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
         const int pix = pb + 32 * k;
@@ -176,9 +264,9 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
           xv[e] = xbn ? (lv ? fmaxf(__builtin_fmaf(xr, x_sc[e], x_sh[e]), 0.f) : 0.f) : xr;     // zero padding stays zero
         }
         u32x2 xh, xl;
-        split4(xv, x_scale, xh, xl);
+        dc_split_f16(xv, x_scale, xh, xl);
         if (pix < NPIX) {
-          const int off = swz(pix * 64 + q * 8);
+          const int off = Rows64::swz(pix * 64 + q * 8);
           *reinterpret_cast<u32x2*>(set + IMG + off) = xh;
           *reinterpret_cast<u32x2*>(set + IMG + PLANE + off) = xl;
           if (red_lds) {
@@ -189,54 +277,9 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
         }
       }
     };
-    auto stage_dz = [&](const f32x4 (&ra)[NL], const f32x4 (&rz)[NL], unsigned live, char* set) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int pix = pb + 32 * k;
-        const bool lv = (live >> k) & 1u;
-        f32x4 dzv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float zz = rz[k][e];
-          const float y = __builtin_fmaf(zz, g_sc[e], g_sh[e]);             // the forward's own expression: identical ReLU gate
-          const float dy = y > 0.f ? ra[k][e] : 0.f;
-          const float v = __builtin_fmaf(d_A[e], dy, __builtin_fmaf(d_D[e], zz - d_mu[e], d_E[e]));
-          dzv[e] = lv ? v : 0.f;                                           // outside the image dz is zero, not E - D*mu
-        }
-        u32x2 dh, dl;
-        split4(dzv, dz_scale, dh, dl);
-        if (pix < NPIX) {
-          const int off = swz(pix * 64 + q * 8);
-          *reinterpret_cast<u32x2*>(set + off) = dh;
-          *reinterpret_cast<u32x2*>(set + PLANE + off) = dl;
-        }
-      }
-    };
-    // x: two register sets (tile t+2 in flight while t+1 is split); (da, z): one set, requested right after the previous
-    // tile's has been split -- one tile of MFMA time ahead (wgrad_f16x3.hip's B1 scheme: 2 x (x + da + z) does not fit)
-    f32x4 rx0[NL], rx1[NL], ra[NL], rz[NL];
-    unsigned lv0 = 0u, lv1 = 0u;
-    if (nt > 0) {
-      request_x(0, rx0, lv0);
-      request_dz(0, ra, rz);
-      if (nt > 1) request_x(1, rx1, lv1);
-      stage_x(rx0, lv0, smem);
-      stage_dz(ra, rz, lv0, smem);
-      if (nt > 1) request_dz(1, ra, rz);
-    }
-    __syncthreads();
-    for (int i = 0; i < nt; i += 2) {
-      if (!(DC_JOINT_ABL & 8) && i + 2 < nt) request_x(i + 2, rx0, lv0);
-      if (!(DC_JOINT_ABL & 4) && i + 1 < nt) { stage_x(rx1, lv1, smem + STAGE); stage_dz(ra, rz, lv1, smem + STAGE); }
-      if (!(DC_JOINT_ABL & 8) && i + 2 < nt) request_dz(i + 2, ra, rz);
-      __syncthreads();
-      if (i + 1 < nt) {
-        if (!(DC_JOINT_ABL & 8) && i + 3 < nt) request_x(i + 3, rx1, lv1);
-        if (!(DC_JOINT_ABL & 4) && i + 2 < nt) { stage_x(rx0, lv0, smem); stage_dz(ra, rz, lv0, smem); }
-        if (!(DC_JOINT_ABL & 8) && i + 3 < nt) request_dz(i + 3, ra, rz);
-        __syncthreads();
-      }
-    }
+    produce<STAGE>(smem, nt, rx0, rx1, request_x,
+                   [&](int j) __attribute__((always_inline)) { dzp.request(p, decode(p, tiles, j), ra, rz, live); },
+                   stage_x, [&](char* set) __attribute__((always_inline)) { dzp.stage(ra, rz, live, dz_scale, set); });
 #pragma unroll 1
     for (int k = 0; k < 2 * 9; ++k) __syncthreads();             // the weight-gradient waves' cross-slice reduction
     return;
@@ -278,7 +321,7 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
       for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
-      const Tile tl = decode(i);
+      const Tile tl = decode(p, tiles, i);
       const __amdgpu_buffer_rsrc_t rsO = dc_make_rsrc(p.dx + tl.img * img_floats, (unsigned)(img_floats * 4));
       __builtin_amdgcn_s_setprio(2);
       {
@@ -287,29 +330,15 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
         // latency -- the consumer side alone ran at 45 % of the MFMA issue rate)
         constexpr int NG = (DC_JOINT_ABL & 1) ? 2 : 18;
         f16x8 ah[2][2], al[2][2];
-        auto fetch = [&](int g, int buf) __attribute__((always_inline)) {
-          const int tap = g >> 1, ks = g & 1;
-          const int toff = ((tap / 3) * TWI + (tap % 3)) * 64 + ks * 32;
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb) {
-            const int ao = swz((mb ? ar1 : ar0) + toff);
-            ah[buf][mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(cur + ao));
-            al[buf][mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(cur + PLANE + ao));
-          }
-        };
-        fetch(0, 0);
+        fetch_dz_window(cur, 0, ar0, ar1, ah[0], al[0]);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
           const int b = g & 1;
-          if (g + 1 < NG) fetch(g + 1, b ^ 1);
+          if (g + 1 < NG) fetch_dz_window(cur, g + 1, ar0, ar1, ah[b ^ 1], al[b ^ 1]);
           __builtin_amdgcn_sched_barrier(0);
           const f16x8 bh = __builtin_bit_cast(f16x8, wreg[g][0]), bl = __builtin_bit_cast(f16x8, wreg[g][1]);
 #pragma unroll
-          for (int mb = 0; mb < 2; ++mb) {
-            acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[b][mb], bh, acc[mb], 0, 0, 0);
-            acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[b][mb], bl, acc[mb], 0, 0, 0);
-            acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[b][mb], bh, acc[mb], 0, 0, 0);
-          }
+          for (int mb = 0; mb < 2; ++mb) dc_mfma3(ah[b][mb], al[b][mb], bh, bl, acc[mb]);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -344,14 +373,8 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
         }
         if (red) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float v = acc[mb][r] * out_scale;
-            const float y = __builtin_fmaf(zr[r], gsc, gsh);
-            const float dy = (!(offs[r] >> 31) && y > 0.f) ? v : 0.f;
-            s1 += dy;
-            s2 = __builtin_fmaf(dy, (zr[r] - rmu) * ris, s2);
-            amax = fmaxf(amax, fabsf(dy));
-          }
+          for (int r = 0; r < 16; ++r)
+            dc_bnred_accum(acc[mb][r] * out_scale, zr[r], gsc, gsh, rmu, ris, !(offs[r] >> 31), s1, s2, amax);
         }
       }
       __syncthreads();
@@ -387,42 +410,7 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
     int lrel = lane_rel;
     asm volatile("" : "+v"(lrel));               // opaque per tile: or the 80 swizzled offsets are hoisted and spilled
     __builtin_amdgcn_s_setprio(2);
-    {
-      // 36 (k-step, tap) groups of 3 MFMAs: k-step = (row of this wave's two, 16-pixel half); the x fragments of group g+1
-      // (and the dz fragments of the next k-step) are requested before the MFMAs of group g issue
-      constexpr int NG = (DC_JOINT_ABL & 2) ? 2 : 36;
-      f16x8 ah[2], al[2], bh[2], bl[2];
-      auto fetch_a = [&](int g, int buf) __attribute__((always_inline)) {
-        const int ks = g / 9, tap = g % 9;
-        const int r = ks >> 1, xs = ks & 1;                      // (row relative to the wave's first: in lane_rel)
-        const int pbase = lrel + ((r + tap / 3) * TWI + 16 * xs + tap % 3) * 64;
-        const int a0 = swz(pbase), a1 = swz(pbase + 4 * 64);
-        ah[buf] = tr_frag(cur + IMG, a0, a1);
-        al[buf] = tr_frag(cur + IMG + PLANE, a0, a1);
-      };
-      auto fetch_b = [&](int ks, int buf) __attribute__((always_inline)) {
-        const int r = ks >> 1, xs = ks & 1;
-        const int brel = lrel + ((r + 1) * TWI + 16 * xs + 1) * 64;
-        const int b0 = swz(brel), b1 = swz(brel + 4 * 64);
-        bh[buf] = tr_frag(cur, b0, b1);
-        bl[buf] = tr_frag(cur + PLANE, b0, b1);
-      };
-      fetch_b(0, 0);
-      fetch_a(0, 0);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int ca = g & 1, ks = g / 9, tap = g % 9, cbuf = ks & 1;
-        if (g + 1 < NG) {
-          fetch_a(g + 1, ca ^ 1);
-          if ((g + 1) % 9 == 0) fetch_b(ks + 1, cbuf ^ 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ca], bh[cbuf], acc[tap], 0, 0, 0);
-        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bl[cbuf], acc[tap], 0, 0, 0);
-        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bh[cbuf], acc[tap], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    wgrad_tile<Rows64, (DC_JOINT_ABL & 2) ? 2 : 36>(cur, lrel, lrel, acc);      // 4 k-steps: this wave's two rows x two 16-pixel halves
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
   }
@@ -445,13 +433,12 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
 namespace bj64 {
 using namespace bj;
 constexpr int CX = 64;                         // x / dx channels
-constexpr int XPLANE = 26624;                  // NPIX * 128 bytes rounded up to a multiple of 1024
+constexpr int XPLANE = Rows128::PLANE;
 constexpr int XIMG = 2 * XPLANE;
 constexpr int STAGE64 = IMG + XIMG;            // dz image | x image
 constexpr int LDS64 = 2 * STAGE64 + 64;
 constexpr int NLX = (NPIX * 16 + 255) / 256;   // float4 loads of x per producer thread (13)
 static_assert(LDS64 <= 160 * 1024 && NPIX * 128 <= XPLANE && XPLANE % 1024 == 0 && IMG % 1024 == 0, "LDS plan");
-__device__ __forceinline__ int swzx(int rel) { return rel ^ ((rel >> 2) & 0x40); }     // chunk ^= 4 * bit 1 of the pixel
 }  // namespace bj64
 
 __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint64_kernel(JointParams p) {
@@ -465,123 +452,44 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint64_kernel(JointParams
   constexpr int W_SLOTS64 = 9 * 4 * 2 * CX;     // [tap][k8][hi|lo][64 cols]
   const float w_scale = p.wp[W_SLOTS64 * 4];
 
-  const int total = p.N * p.tilesX * p.tilesY;
-  const int G = (int)gridDim.x, xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int nx = (G + 7 - xcd) >> 3;
-  const int qq = total >> 3, rr = total & 7;
-  const int xstart = xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq;
-  const int xcount = qq + (xcd < rr ? 1 : 0);
-  const int nt = seq < xcount ? (xcount - seq + nx - 1) / nx : 0;
-  struct Tile { int img, y0, x0; };
-  auto decode = [&](int j) __attribute__((always_inline)) {
-    const int work = xstart + seq + j * nx;
-    const int ty = work % p.tilesY, t2 = work / p.tilesY;
-    Tile t;
-    t.x0 = (t2 % p.tilesX) * TW; t.img = t2 / p.tilesX; t.y0 = ty * TH;
-    return t;
-  };
-  const long dz_img = (long)p.H * p.W * C, x_img = (long)p.H * p.W * CX;
+  const DcXcdRange tiles = tile_range(p);
+  const int nt = tiles.nt;
+  const long x_img = (long)p.H * p.W * CX;
 
   if (wave >= 4) {
     // ============================ producers ===========================================================================
     const int t = tid & 255;
-    const int q = t & 7, pb = t >> 3;               // dz: channel quad (8), first pixel (32 pixels per pass)
+    const DzProducer dzp(p.dzCoef, t);              // dz: channel quad (8), first pixel (32 pixels per pass)
     const int qx = t & 15, pbx = t >> 4;            // x: channel quad (16), first pixel (16 pixels per pass)
-    const float* ct = p.dzCoef + 4 * q;
-    const f32x4 g_sc = *reinterpret_cast<const f32x4*>(ct), g_sh = *reinterpret_cast<const f32x4*>(ct + C),
-                d_mu = *reinterpret_cast<const f32x4*>(ct + 2 * C), d_A = *reinterpret_cast<const f32x4*>(ct + 3 * C),
-                d_D = *reinterpret_cast<const f32x4*>(ct + 4 * C), d_E = *reinterpret_cast<const f32x4*>(ct + 5 * C);
-    auto pix_ok = [&](const Tile& tl, int pix, int& y, int& xx) {
-      const int r = __umul24(pix, (65536 + TWI - 1) / TWI) >> 16;
-      const int c = pix - __umul24(r, TWI);
-      y = tl.y0 - 1 + r; xx = tl.x0 - 1 + c;
-      return pix < NPIX && (unsigned)y < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;
-    };
-    auto request_x = [&](int j, f32x4 (&rx)[NLX]) {
-      const Tile tl = decode(j);
+    f32x4 rx0[NLX], rx1[NLX], ra[NL], rz[NL];
+    unsigned live = 0u;
+    auto request_x = [&](int j, f32x4 (&rx)[NLX]) __attribute__((always_inline)) {
+      const Tile tl = decode(p, tiles, j);
       const __amdgpu_buffer_rsrc_t rsX = dc_make_rsrc(p.x + tl.img * x_img, (unsigned)(x_img * 4));
 #pragma unroll
       for (int k = 0; k < NLX; ++k) {
         int y, xx;
-        const bool ok = pix_ok(tl, pbx + 16 * k, y, xx);
+        const bool ok = halo_pixel(p, tl, pbx + 16 * k, y, xx);
         const unsigned off = ok ? (unsigned)(((y * p.W + xx) * CX + 4 * qx) * 4) : OOB;
         rx[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsX, off, 0, 0));      // zeros outside the image
       }
     };
-    auto request_dz = [&](int j, f32x4 (&ra)[NL], f32x4 (&rz)[NL], unsigned& live) {
-      live = 0u;
-      const Tile tl = decode(j);
-      const __amdgpu_buffer_rsrc_t rsA = dc_make_rsrc(p.da + tl.img * dz_img, (unsigned)(dz_img * 4));
-      const __amdgpu_buffer_rsrc_t rsZ = dc_make_rsrc(p.z + tl.img * dz_img, (unsigned)(dz_img * 4));
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        int y, xx;
-        const bool ok = pix_ok(tl, pb + 32 * k, y, xx);
-        const unsigned off = ok ? (unsigned)(((y * p.W + xx) * C + 4 * q) * 4) : OOB;
-        ra[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
-        rz[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsZ, off, 0, 0));
-        if (ok) live |= 1u << k;
-      }
-    };
-    auto stage_x = [&](const f32x4 (&rx)[NLX], char* set) {
+    auto stage_x = [&](const f32x4 (&rx)[NLX], char* set) __attribute__((always_inline)) {
 #pragma unroll
       for (int k = 0; k < NLX; ++k) {
         const int pix = pbx + 16 * k;
         u32x2 xh, xl;
-        split4(rx[k], x_scale, xh, xl);
+        dc_split_f16(rx[k], x_scale, xh, xl);
         if (pix < NPIX) {
-          const int off = swzx(pix * 128 + qx * 8);
+          const int off = Rows128::swz(pix * 128 + qx * 8);
           *reinterpret_cast<u32x2*>(set + IMG + off) = xh;
           *reinterpret_cast<u32x2*>(set + IMG + XPLANE + off) = xl;
         }
       }
     };
-    auto stage_dz = [&](const f32x4 (&ra)[NL], const f32x4 (&rz)[NL], unsigned live, char* set) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int pix = pb + 32 * k;
-        const bool lv = (live >> k) & 1u;
-        f32x4 dzv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float zz = rz[k][e];
-          const float y = __builtin_fmaf(zz, g_sc[e], g_sh[e]);
-          const float dy = y > 0.f ? ra[k][e] : 0.f;
-          const float v = __builtin_fmaf(d_A[e], dy, __builtin_fmaf(d_D[e], zz - d_mu[e], d_E[e]));
-          dzv[e] = lv ? v : 0.f;
-        }
-        u32x2 dh, dl;
-        split4(dzv, dz_scale, dh, dl);
-        if (pix < NPIX) {
-          const int off = swz(pix * 64 + q * 8);
-          *reinterpret_cast<u32x2*>(set + off) = dh;
-          *reinterpret_cast<u32x2*>(set + PLANE + off) = dl;
-        }
-      }
-    };
-    f32x4 rx0[NLX], rx1[NLX], ra[NL], rz[NL];
-    unsigned lv = 0u;
-    if (nt > 0) {
-      request_x(0, rx0);
-      request_dz(0, ra, rz, lv);
-      if (nt > 1) request_x(1, rx1);
-      stage_x(rx0, smem);
-      stage_dz(ra, rz, lv, smem);
-      if (nt > 1) request_dz(1, ra, rz, lv);
-    }
-    __syncthreads();
-    for (int i = 0; i < nt; i += 2) {
-      if (i + 2 < nt) request_x(i + 2, rx0);
-      if (i + 1 < nt) { stage_x(rx1, smem + STAGE64); stage_dz(ra, rz, lv, smem + STAGE64); }
-      if (i + 2 < nt) request_dz(i + 2, ra, rz, lv);
-      __syncthreads();
-      if (i + 1 < nt) {
-        if (i + 3 < nt) request_x(i + 3, rx1);
-        if (i + 2 < nt) { stage_x(rx0, smem); stage_dz(ra, rz, lv, smem); }
-        if (i + 3 < nt) request_dz(i + 3, ra, rz, lv);
-        __syncthreads();
-      }
-    }
+    produce<STAGE64>(smem, nt, rx0, rx1, request_x,
+                     [&](int j) __attribute__((always_inline)) { dzp.request(p, decode(p, tiles, j), ra, rz, live); },
+                     stage_x, [&](char* set) __attribute__((always_inline)) { dzp.stage(ra, rz, live, dz_scale, set); });
     return;
   }
 
@@ -621,39 +529,26 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint64_kernel(JointParams
             wf[slot][nb][1] = __builtin_amdgcn_raw_buffer_load_b128(rsW, w_rel + nb * 512, soff + CX * 16, 0);
           }
         };
-        auto fetch_a = [&](int g, int buf) __attribute__((always_inline)) {
-          const int tap = g >> 1, ks = g & 1;
-          const int toff = ((tap / 3) * TWI + (tap % 3)) * 64 + ks * 32;
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb) {
-            const int ao = swz((mb ? ar1 : ar0) + toff);
-            ah[buf][mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(cur + ao));
-            al[buf][mb] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(cur + PLANE + ao));
-          }
-        };
 #pragma unroll
         for (int g = 0; g < AHEAD; ++g) fetch_w(g, g);
-        fetch_a(0, 0);
+        fetch_dz_window(cur, 0, ar0, ar1, ah[0], al[0]);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
           const int b = g & 1, ws = g % (AHEAD + 1);
           if (g + AHEAD < NG) fetch_w(g + AHEAD, (g + AHEAD) % (AHEAD + 1));
-          if (g + 1 < NG) fetch_a(g + 1, b ^ 1);
+          if (g + 1 < NG) fetch_dz_window(cur, g + 1, ar0, ar1, ah[b ^ 1], al[b ^ 1]);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-              const f16x8 bh = __builtin_bit_cast(f16x8, wf[ws][nb][0]), bl = __builtin_bit_cast(f16x8, wf[ws][nb][1]);
-              acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[b][mb], bh, acc[mb][nb], 0, 0, 0);
-              acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[b][mb], bl, acc[mb][nb], 0, 0, 0);
-              acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[b][mb], bh, acc[mb][nb], 0, 0, 0);
-            }
+            for (int nb = 0; nb < 2; ++nb)
+              dc_mfma3(ah[b][mb], al[b][mb], __builtin_bit_cast(f16x8, wf[ws][nb][0]), __builtin_bit_cast(f16x8, wf[ws][nb][1]),
+                       acc[mb][nb]);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
       __builtin_amdgcn_s_setprio(0);
-      const Tile tl = decode(i);
+      const Tile tl = decode(p, tiles, i);
       const __amdgpu_buffer_rsrc_t rsO = dc_make_rsrc(p.dx + tl.img * x_img, (unsigned)(x_img * 4));
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) {
@@ -691,40 +586,7 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint64_kernel(JointParams
     int lz = lane_z, lx = lane_x;
     asm volatile("" : "+v"(lz), "+v"(lx));
     __builtin_amdgcn_s_setprio(2);
-    {
-      constexpr int NG = 72;                                       // 8 k-steps (row, 16-pixel half) x 9 taps
-      f16x8 ah[2], al[2], bh[2], bl[2];
-      auto fetch_a = [&](int g, int buf) __attribute__((always_inline)) {
-        const int ks = g / 9, tap = g % 9;
-        const int r = ks >> 1, xs = ks & 1;
-        const int pbase = lx + ((r + tap / 3) * TWI + 16 * xs + tap % 3) * 128;
-        const int a0 = swzx(pbase), a1 = swzx(pbase + 4 * 128);
-        ah[buf] = tr_frag(cur + IMG, a0, a1);
-        al[buf] = tr_frag(cur + IMG + XPLANE, a0, a1);
-      };
-      auto fetch_b = [&](int ks, int buf) __attribute__((always_inline)) {
-        const int r = ks >> 1, xs = ks & 1;
-        const int brel = lz + ((r + 1) * TWI + 16 * xs + 1) * 64;
-        const int b0 = swz(brel), b1 = swz(brel + 4 * 64);
-        bh[buf] = tr_frag(cur, b0, b1);
-        bl[buf] = tr_frag(cur + PLANE, b0, b1);
-      };
-      fetch_b(0, 0);
-      fetch_a(0, 0);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int ca = g & 1, ks = g / 9, tap = g % 9, cbuf = ks & 1;
-        if (g + 1 < NG) {
-          fetch_a(g + 1, ca ^ 1);
-          if ((g + 1) % 9 == 0) fetch_b(ks + 1, cbuf ^ 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ca], bh[cbuf], acc[tap], 0, 0, 0);
-        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bl[cbuf], acc[tap], 0, 0, 0);
-        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bh[cbuf], acc[tap], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    wgrad_tile<Rows128, 72>(cur, lx, lz, acc);                     // 8 k-steps: all four rows x two 16-pixel halves
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
   }

@@ -89,6 +89,37 @@ __host__ __device__ __forceinline__ void dc_bn_affine(float mu, float is, float 
   sc = ga * is;
   sh = __builtin_fmaf(-mu, sc, be);
 }
+// "dz on load" (dcunet.h, dc_bn_bwd_finalize_dzin's table: sc | sh | mu | A | D | E per channel): the BatchNorm-backward
+// result of one element, formed by the consumer of dz from da and the block's pre-BN value z.  y is the forward's own
+// expression: identical ReLU gate.  (Outside the image dz is zero, not E - D*mu: that select stays with the caller.)
+__device__ __forceinline__ float dc_dz_on_load(float z, float da, float sc, float sh, float mu, float A, float D, float E) {
+  const float y = __builtin_fmaf(z, sc, sh);
+  const float dy = y > 0.f ? da : 0.f;
+  return __builtin_fmaf(A, dy, __builtin_fmaf(D, z - mu, E));
+}
+
+// ---- XCD-contiguous work split --------------------------------------------------------------------------------------
+// Workgroups are dealt round-robin over the 8 XCDs (ids b and b + 8 share an L2), so each XCD is given a CONTIGUOUS range
+// of the `total` work items: what neighbouring items read in common stays on one L2 (speed only; bijective for every
+// total, any placement computes the same result).  dc_xcd_first: one item per workgroup (total == gridDim.x).
+__device__ __forceinline__ int dc_xcd_first(unsigned block, int total) {
+  const int xcd = block & 7, seq = block >> 3, qq = total >> 3, rr = total & 7;
+  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + seq;
+}
+// Persistent form: the nx workgroups of an XCD stride through its range; this workgroup's item j (of nt) is work(j).
+struct DcXcdRange {
+  int xstart, nx, nt;
+  __device__ __forceinline__ int work(int j) const { return xstart + j * nx; }
+};
+__device__ __forceinline__ DcXcdRange dc_xcd_range(unsigned block, int grid, int total) {
+  const int xcd = block & 7, seq = block >> 3;
+  DcXcdRange r;
+  r.nx = (grid + 7 - xcd) >> 3;                                    // workgroups on this XCD
+  r.xstart = dc_xcd_first(block, total);
+  const int xcount = (total >> 3) + (xcd < (total & 7) ? 1 : 0);   // items of this XCD
+  r.nt = seq < xcount ? (xcount - seq + r.nx - 1) / r.nx : 0;
+  return r;
+}
 
 // ---- per-channel moments that survive |mean| >> sigma ------------------------------------------------------------
 // BatchNorm statistics leave the convolution epilogues as per-(tile, channel) partials.  Summing v and v*v in fp32

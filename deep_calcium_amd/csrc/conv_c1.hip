@@ -136,11 +136,7 @@ struct C1Dz {
   __device__ __forceinline__ f32x4 dz(const f32x4& da, const f32x4& z) const {
     f32x4 v;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float y = __builtin_fmaf(z[e], sc[e], sh[e]);
-      const float dy = y > 0.f ? da[e] : 0.f;
-      v[e] = __builtin_fmaf(A[e], dy, __builtin_fmaf(D[e], z[e] - mu[e], E[e]));
-    }
+    for (int e = 0; e < 4; ++e) v[e] = dc_dz_on_load(z[e], da[e], sc[e], sh[e], mu[e], A[e], D[e], E[e]);
     return v;
   }
 };

@@ -64,9 +64,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmParams p) {
   // each XCD walks a contiguous range of (pixel tile, column block) pairs with the column block fastest: the CTAs
   // that re-read one input patch for different output columns run back to back on ONE L2 (speed only; any
   // placement computes the same result).  Bijective for every grid size.
-  const int nblk = (p.Ncols + BN - 1) / BN, total = (int)gridDim.x;
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3, qq = total >> 3, rr = total & 7;
-  const int work = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + seq;
+  const int nblk = (p.Ncols + BN - 1) / BN;
+  const int work = dc_xcd_first(blockIdx.x, (int)gridDim.x);
   const int tile_id = work / nblk;
   int t = tile_id;
   const int tx = t % p.tilesX; t /= p.tilesX;

@@ -20,6 +20,7 @@
 //   * activations are split while being written to LDS (v_cvt_pk_f16_f32 x2 + 2 sub per pair);
 //   * weights arrive PRE-split from dc_pack_weights_f16x3 ([tap][K/8][hi|lo][col][8]) and are copied verbatim.
 #include "igemm_common.h"
+#include "f16x3_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -39,11 +40,6 @@ extern "C" int dc_debug_set_trace(unsigned long long* p) {
 #define DC_TRACE_INIT() do {} while (0)
 #define DC_TRACE() do {} while (0)
 #endif
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 template <int KH, int KW, int S, int PAD, int TW, int WAVES_M, int MB, int NB, int CK_ = 16>
 struct IgemmH {
@@ -67,27 +63,6 @@ struct IgemmH {
   static_assert(256 % BN == 0, "staging assumes BN divides the block size");
   static_assert(CK % 16 == 0 && 256 % G4 == 0, "CK must be a multiple of the MFMA k (16)");
 };
-
-// hi = fp16(x*s), lo = fp16(x*s - hi) for 4 elements in EIGHT vector instructions: v_fma_mix{lo,hi}_f16 multiplies in
-// fp32, adds an fp16 (or zero) and rounds once to fp16 into one half of the destination.  (s is a power of two and
-// x*s - hi is exactly representable, so the bits equal the two-step form (half)(x*s - (float)hi).)  hipcc's own lowering
-// of the C expression spent 13 instructions per 4 elements, part of them packed-fp32 ops that issue at half rate next to
-// MFMAs -- and this split runs in the matrix waves' own instruction stream, once per staged element.
-__device__ __forceinline__ void split_f16(const f32x4 v, float s, u32x2& hi, u32x2& lo) {
-  unsigned h01, h23, l01, l23;
-  asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
-      "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
-      "v_fma_mixhi_f16 %0, %5, %8, 0\n\t"
-      "v_fma_mixhi_f16 %1, %7, %8, 0\n\t"
-      "v_fma_mixlo_f16 %2, %4, %8, -%0 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixlo_f16 %3, %6, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %2, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %3, %7, %8, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-      : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23)
-      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(s));
-  hi = u32x2{h01, h23};
-  lo = u32x2{l01, l23};
-}
 
 // BNRED (its own instantiations, conv-transpose data gradients only): the output IS `da` of the BatchNorm layer in front (dense,
 // no Dropout); the epilogue also reads that layer's pre-BN tensor bnZ (same layout) and emits its pass-1 partials
@@ -114,9 +89,8 @@ __global__ __launch_bounds__(256, 2) void igemm_f16x3_kernel(IgemmParams p) {
   // each XCD walks a contiguous range of (pixel tile, column block) pairs with the column block fastest: the CTAs
   // that re-read one input patch for different output columns run back to back on ONE L2 (speed only; any
   // placement computes the same result).  Bijective for every grid size.
-  const int nblk = (p.Ncols + BN - 1) / BN, total = (int)gridDim.x;
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3, qq = total >> 3, rr = total & 7;
-  const int work = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + seq;
+  const int nblk = (p.Ncols + BN - 1) / BN;
+  const int work = dc_xcd_first(blockIdx.x, (int)gridDim.x);
   const int wpos = work / nblk;                                // position in the walk over the pixel tiles
   int tx, ty, img;
   if (p.walk) { ty = wpos % p.tilesY; const int t = wpos / p.tilesY; tx = t % p.tilesX; img = t / p.tilesX; }
@@ -251,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void igemm_f16x3_kernel(IgemmParams p) {
             ra[it][e] = live ? y : 0.f;
           }
         }
-        split_f16(ra[it], in_scale, hi, lo);
+        dc_split_f16(ra[it], in_scale, hi, lo);
         char* base = smem + ((a_g >> 1) * PS + pix) * 16 + (a_g & 1) * 8;
         *reinterpret_cast<u32x2*>(base) = hi;
         *reinterpret_cast<u32x2*>(base + G8 * PS * 16) = lo;
@@ -296,11 +270,7 @@ __global__ __launch_bounds__(256, 2) void igemm_f16x3_kernel(IgemmParams p) {
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[cur][mb], bh[cur][nb], acc[mb][nb], 0, 0, 0);
-          acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur][mb], bl[cur][nb], acc[mb][nb], 0, 0, 0);
-          acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[cur][mb], bh[cur][nb], acc[mb][nb], 0, 0, 0);
-        }
+        for (int nb = 0; nb < NB; ++nb) dc_mfma3(ah[cur][mb], al[cur][mb], bh[cur][nb], bl[cur][nb], acc[mb][nb]);
       __builtin_amdgcn_sched_barrier(0);
     }
     DC_TRACE();          // d: MFMA block done
@@ -441,14 +411,8 @@ __global__ __launch_bounds__(256, 2) void igemm_f16x3_kernel(IgemmParams p) {
         for (int r = 0; r < 16; ++r)
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[mb][nb][r] * out_scale), rsrcO, offs[r], 0, 0);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float v = acc[mb][nb][r] * out_scale;
-          const float y = __builtin_fmaf(zr[r], gsc, gsh);        // the forward's own expression: identical ReLU gate
-          const float dy = (!(offs[r] >> 31) && y > 0.f) ? v : 0.f;
-          s1 += dy;
-          s2 = __builtin_fmaf(dy, (zr[r] - mu) * is, s2);
-          amax = fmaxf(amax, fabsf(dy));
-        }
+        for (int r = 0; r < 16; ++r)
+          dc_bnred_accum(acc[mb][nb][r] * out_scale, zr[r], gsc, gsh, mu, is, !(offs[r] >> 31), s1, s2, amax);
       }
       DcMoments m;                                 // container: (max |dy|, sum dy, sum dy*xhat)
       m.n = fmaxf(amax, __shfl_xor(amax, 32));

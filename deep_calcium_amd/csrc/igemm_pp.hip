@@ -13,12 +13,9 @@
 // Served launches: conv3x3 forward (training, BN-on-load, inference) and data gradient with W > 16, > 32 output columns,
 // Cin a multiple of 16 and >= 64 (>= 4 steps per tile for the sliced epilogue); everything else stays on igemm_f16x3.hip.
 #include "igemm_common.h"
+#include "f16x3_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // Step timestamps of sampled workgroups (scripts/igemm_pp_phases.py; compiled out unless -DDC_IGEMM_TRACE): per role the
 // first wave stores s_memtime when its work of a step is done and again when the step's barrier has released it.
@@ -97,23 +94,6 @@ struct Cfg {
   static_assert(256 % BN == 0 && NBLK == 4 && (MB == 2 || MB == 4), "two shapes: 2x2 and 4x1 blocks per wave");
 };
 
-// hi = fp16(x*s), lo = fp16(x*s - hi): two v_fma_mix per element (igemm_f16x3.hip split_f16)
-__device__ __forceinline__ void split(const f32x4 v, float s, u32x2& hi, u32x2& lo) {
-  unsigned h01, h23, l01, l23;
-  asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
-      "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
-      "v_fma_mixhi_f16 %0, %5, %8, 0\n\t"
-      "v_fma_mixhi_f16 %1, %7, %8, 0\n\t"
-      "v_fma_mixlo_f16 %2, %4, %8, -%0 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixlo_f16 %3, %6, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %2, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %3, %7, %8, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-      : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23)
-      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(s));
-  hi = u32x2{h01, h23};
-  lo = u32x2{l01, l23};
-}
-
 struct Item {          // one output tile x column block (wave-uniform)
   int tile_id, img, n0, oy0, ox0;
 };
@@ -155,17 +135,12 @@ __global__ __launch_bounds__(pp::THREADS, 1) void igemm_pp_kernel(IgemmParams p)
   // neighbouring patches, stay on one L2 -- speed only)
   const int nblk = (p.Ncols + BN - 1) / BN;
   const int total = p.N * p.tilesX * p.tilesY * nblk;
-  const int G = (int)gridDim.x, xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int nx = (G + 7 - xcd) >> 3;                               // workgroups on this XCD
-  const int qq = total >> 3, rr = total & 7;
-  const int xstart = xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq;
-  const int xcount = qq + (xcd < rr ? 1 : 0);
-  const int n_items = seq < xcount ? (xcount - seq + nx - 1) / nx : 0;
+  const DcXcdRange items = dc_xcd_range(blockIdx.x, (int)gridDim.x, total);
   const int nch = p.Cin / CK;
-  const int K = n_items * nch;                                     // steps of this workgroup
+  const int K = items.nt * nch;                                    // steps of this workgroup
   auto decode = [&](int j) __attribute__((always_inline)) {
     Item it;
-    const int work = xstart + seq + j * nx;
+    const int work = items.work(j);
     const int wpos = work / nblk;                               // position in the walk over the pixel tiles
     it.n0 = (work - wpos * nblk) * BN;
     int tx, ty;
@@ -327,12 +302,7 @@ __global__ __launch_bounds__(pp::THREADS, 1) void igemm_pp_kernel(IgemmParams p)
             const bool live = !(a_voff[k] >> 31);              // outside the image dz is 0, not E - D*mu
             const f32x4 zz = rz[k];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float y = __builtin_fmaf(zz[e], csc[e], csh[e]);       // the forward's own expression: identical ReLU gate
-              const float dy = y > 0.f ? v[e] : 0.f;
-              const float dzv = __builtin_fmaf(cA[e], dy, __builtin_fmaf(cD[e], zz[e] - cmu[e], cE[e]));
-              v[e] = live ? dzv : 0.f;
-            }
+            for (int e = 0; e < 4; ++e) v[e] = live ? dc_dz_on_load(zz[e], v[e], csc[e], csh[e], cmu[e], cA[e], cD[e], cE[e]) : 0.f;
             // the weight gradient's copy of dz (a store at an out-of-image offset is dropped by the descriptor)
             if constexpr (DZOUT)
               if (store_dz && ((int_mask >> k) & 1u))
@@ -351,7 +321,7 @@ __global__ __launch_bounds__(pp::THREADS, 1) void igemm_pp_kernel(IgemmParams p)
             hi = u32x2{__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1])};
             lo = u32x2{__builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
           } else {
-            split(v, in_scale, hi, lo);
+            dc_split_f16(v, in_scale, hi, lo);
           }
           char* base = st + ((a_g >> 1) * PS + pix) * 16 + (a_g & 1) * 8;
           *reinterpret_cast<u32x2*>(base) = hi;
@@ -618,12 +588,8 @@ __global__ __launch_bounds__(pp::THREADS, 1) void igemm_pp_kernel(IgemmParams p)
         const int mr = (r & 3) + 8 * (r >> 2);
         const int rowc = mr / TW, colc = mr % TW;
         const bool ok = INT || (n_ok && (oyb + rowc) < p.Hout && (oxb + colc) < p.Wout);
-        const float v = __builtin_fmaf(acc[mb][nb][r], out_scale, bv);
-        const float y = __builtin_fmaf(zr[r], sc, sh);          // the forward's own expression: identical ReLU gate
-        const float dy = (ok && y > 0.f) ? v : 0.f;
-        e_s1 += dy;
-        e_s2 = __builtin_fmaf(dy, (zr[r] - mu) * is, e_s2);
-        e_cnt = fmaxf(e_cnt, fabsf(dy));                        // (the count slot is free in this variant: max |dy|)
+        // (the count slot is free in this variant: max |dy|)
+        dc_bnred_accum(__builtin_fmaf(acc[mb][nb][r], out_scale, bv), zr[r], sc, sh, mu, is, ok, e_s1, e_s2, e_cnt);
       }
       if (mb == MB - 1) {
         DcMoments m;                                             // container: (max |dy|, sum dy, sum dy*xhat)

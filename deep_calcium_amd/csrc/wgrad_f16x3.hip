@@ -24,6 +24,7 @@
 //     LDS at the end, one slab per CTA goes to HBM and dc_reduce_partials adds the slabs in a fixed order
 //     (bit-reproducible, no atomics).
 #include "wgrad_common.h"
+#include "f16x3_common.h"
 #include <stdlib.h>
 
 // Experiment switches (scripts/wgrad_variants.py builds copies of the library with them; the shipped build uses the defaults).
@@ -66,11 +67,6 @@ extern "C" int dc_debug_wgrad_timeline(unsigned long long* out4096) {
 #define WG_TL(i) do {} while (0)
 #endif
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short tr_v4i16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 struct WgradHParams {
   WgradParams g;
   const float* aScale;  // nullable device scalars (powers of two)
@@ -108,36 +104,14 @@ struct WgradHCfg {
   static_assert(LDS_BYTES <= 160 * 1024, "two image sets must fit the 160 KiB LDS");
 };
 
-__device__ __forceinline__ f16x8 tr_frag(const char* base, int off1, int off2) {
-  typedef __attribute__((address_space(3))) tr_v4i16* lds_p;
-  const tr_v4i16 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base + off1));
-  const tr_v4i16 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base + off2));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-  return __builtin_bit_cast(f16x8, v);
-}
-
-// hi = fp16(x*s), lo = fp16(x*s - hi): two v_fma_mix per element (see split_f16 in igemm_f16x3.hip)
-template <bool SCALED>
+// dc_split_f16 behind the DC_WG_ABL & 16 switch
 __device__ __forceinline__ void split4_f16(const f32x4 v, float s, u32x2& hi, u32x2& lo) {
   if (DC_WG_ABL & 16) {      // ablation: an operand stored PRE-SPLIT in HBM -- the same LDS writes, none of the split VALU
     hi = u32x2{__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1])};
     lo = u32x2{__builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
     return;
   }
-  unsigned h01, h23, l01, l23;
-  asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
-      "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
-      "v_fma_mixhi_f16 %0, %5, %8, 0\n\t"
-      "v_fma_mixhi_f16 %1, %7, %8, 0\n\t"
-      "v_fma_mixlo_f16 %2, %4, %8, -%0 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixlo_f16 %3, %6, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %2, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mixhi_f16 %3, %7, %8, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-      : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23)
-      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(s));
-  hi = u32x2{h01, h23};
-  lo = u32x2{l01, l23};
+  dc_split_f16(v, s, hi, lo);
 }
 
 template <int KH, int KW, int S, int PAD, int TW, int RW, int WM, int WNW, int NBW, bool A_SCALED, bool DZIN = false>
@@ -170,9 +144,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_f16x3_kernel(WgradHParams hp) {
   // XCD-aware rasterisation (speed only): ids b and b+8 share an L2, so each XCD walks a contiguous range of
   // (pixel split, channel block) pairs with the channel block fastest -- the CTAs that stream the same pixel range
   // for different (m,n) blocks run side by side on one L2.
-  const int nbm = (p.Cm + CM - 1) / CM, nbn = (p.Cn + CN - 1) / CN, total = (int)gridDim.x;
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3, qq = total >> 3, rr8 = total & 7;
-  const int work = (xcd < rr8 ? xcd * (qq + 1) : rr8 * (qq + 1) + (xcd - rr8) * qq) + seq;
+  const int nbm = (p.Cm + CM - 1) / CM, nbn = (p.Cn + CN - 1) / CN;
+  const int work = dc_xcd_first(blockIdx.x, (int)gridDim.x);
   const int split = work / (nbm * nbn), blk = work - split * (nbm * nbn);
   const int m0 = (blk / nbn) * CM, n0 = (blk % nbn) * CN;
   const int tile_beg = split * p.tilesPerSplit;
@@ -263,6 +236,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_f16x3_kernel(WgradHParams hp) {
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+        // common.h dc_dz_on_load, written out: through the helper hipcc allocates the 32-wide DZIN instantiations differently
+        // (the <32, 2, 1, 1, 1> one sits at 256 VGPRs and spilled 8 more bytes)
         const float y = __builtin_fmaf(zz[e], b_sc[e], b_sh[e]);           // the forward's own expression: identical ReLU gate
         const float dy = y > 0.f ? da[e] : 0.f;
         const float dzv = __builtin_fmaf(d_A[e], dy, __builtin_fmaf(d_D[e], zz[e] - d_mu[e], d_E[e]));
@@ -275,7 +250,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_f16x3_kernel(WgradHParams hp) {
       for (int j = 0; j < NA; ++j) {
         const int pix = st / AC4 + j * (256 / AC4);
         u32x2 hi, lo;
-        split4_f16<true>(a_bn ? bn_relu(ra[j], a_sc, a_sh, (ma >> j) & 1u) : ra[j], a_scale, hi, lo);
+        split4_f16(a_bn ? bn_relu(ra[j], a_sc, a_sh, (ma >> j) & 1u) : ra[j], a_scale, hi, lo);
         if (pix < APIX) {
           *reinterpret_cast<u32x2*>(set + a_lbase + pix * 64) = hi;
           *reinterpret_cast<u32x2*>(set + A_IMG + a_lbase + pix * 64) = lo;
@@ -290,7 +265,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_f16x3_kernel(WgradHParams hp) {
         f32x4 bv = rb[k];
         if constexpr (DZIN) bv = dz_on_load(rb[k], rz[k], (mb >> k) & 1u);
         else if (b_bn) bv = bn_relu(rb[k], b_sc, b_sh, (mb >> k) & 1u);
-        split4_f16<true>(bv, b_scale, hi, lo);
+        split4_f16(bv, b_scale, hi, lo);
         if (pix < BPIX) {
           *reinterpret_cast<u32x2*>(set + b_lbase + pix * 64) = hi;
           *reinterpret_cast<u32x2*>(set + B_IMG + b_lbase + pix * 64) = lo;
@@ -413,13 +388,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_f16x3_kernel(WgradHParams hp) {
   if (!(DC_WG_ABL & 4)) {
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
-      ah[d] = tr_frag(smem, offA[0] + a_off(d), offA[1] + a_off(d));
-      al[d] = tr_frag(smem + A_IMG, offA[0] + a_off(d), offA[1] + a_off(d));
+      ah[d] = dc_tr_frag(smem, offA[0] + a_off(d), offA[1] + a_off(d));
+      al[d] = dc_tr_frag(smem + A_IMG, offA[0] + a_off(d), offA[1] + a_off(d));
     }
 #pragma unroll
     for (int w = 0; w < NBW; ++w) {
-      bh[0][w] = tr_frag(smem, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
-      bl[0][w] = tr_frag(smem + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+      bh[0][w] = dc_tr_frag(smem, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+      bl[0][w] = dc_tr_frag(smem + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
     }
   }
   for (int i = 0; i < nt; ++i) {
@@ -433,40 +408,36 @@ __global__ __launch_bounds__(512, 1) void wgrad_f16x3_kernel(WgradHParams hp) {
       if (g == GROUPS - DEPTH) __syncthreads();     // every read of this set has been issued (and is waited for here)
       const int gn = g + DEPTH;
       if (gn < GROUPS) {
-        ah[gn % RING] = tr_frag(cur, offA[0] + a_off(gn), offA[1] + a_off(gn));
-        al[gn % RING] = tr_frag(cur + A_IMG, offA[0] + a_off(gn), offA[1] + a_off(gn));
+        ah[gn % RING] = dc_tr_frag(cur, offA[0] + a_off(gn), offA[1] + a_off(gn));
+        al[gn % RING] = dc_tr_frag(cur + A_IMG, offA[0] + a_off(gn), offA[1] + a_off(gn));
       } else if (more) {                            // the next tile's first groups, from the other image set
-        ah[gn % RING] = tr_frag(nxt, offA[0] + a_off(gn - GROUPS), offA[1] + a_off(gn - GROUPS));
-        al[gn % RING] = tr_frag(nxt + A_IMG, offA[0] + a_off(gn - GROUPS), offA[1] + a_off(gn - GROUPS));
+        ah[gn % RING] = dc_tr_frag(nxt, offA[0] + a_off(gn - GROUPS), offA[1] + a_off(gn - GROUPS));
+        al[gn % RING] = dc_tr_frag(nxt + A_IMG, offA[0] + a_off(gn - GROUPS), offA[1] + a_off(gn - GROUPS));
       }
       if (KSTEPS > 1 && tap == 0 && ks + 1 < KSTEPS) {           // the next k-step's B fragments: the other buffer is free
 #pragma unroll
         for (int w = 0; w < NBW; ++w) {
-          bh[cbuf ^ 1][w] = tr_frag(cur, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
-          bl[cbuf ^ 1][w] = tr_frag(cur + B_IMG, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
+          bh[cbuf ^ 1][w] = dc_tr_frag(cur, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
+          bl[cbuf ^ 1][w] = dc_tr_frag(cur + B_IMG, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
         }
       }
       if (KSTEPS > 1 && g == GROUPS - DEPTH && more) {           // the next tile's k-step 0 (buffer 0: k-step KSTEPS - 2 is long done)
 #pragma unroll
         for (int w = 0; w < NBW; ++w) {
-          bh[0][w] = tr_frag(nxt, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
-          bl[0][w] = tr_frag(nxt + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+          bh[0][w] = dc_tr_frag(nxt, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+          bl[0][w] = dc_tr_frag(nxt + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
         }
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int w = 0; w < NBW; ++w) {
-        acc[w][tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ca], bh[cbuf][w], acc[w][tap], 0, 0, 0);
-        acc[w][tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bl[cbuf][w], acc[w][tap], 0, 0, 0);
-        acc[w][tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bh[cbuf][w], acc[w][tap], 0, 0, 0);
-      }
+      for (int w = 0; w < NBW; ++w) dc_mfma3(ah[ca], al[ca], bh[cbuf][w], bl[cbuf][w], acc[w][tap]);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (KSTEPS == 1 && more) {                      // one k-step per tile: its only B buffer is free only now
 #pragma unroll
       for (int w = 0; w < NBW; ++w) {
-        bh[0][w] = tr_frag(nxt, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
-        bl[0][w] = tr_frag(nxt + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+        bh[0][w] = dc_tr_frag(nxt, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+        bl[0][w] = dc_tr_frag(nxt + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
       }
     }
   }
@@ -479,37 +450,33 @@ __global__ __launch_bounds__(512, 1) void wgrad_f16x3_kernel(WgradHParams hp) {
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       if (d < GROUPS) {
-        ah[d] = tr_frag(cur, offA[0] + a_off(d), offA[1] + a_off(d));
-        al[d] = tr_frag(cur + A_IMG, offA[0] + a_off(d), offA[1] + a_off(d));
+        ah[d] = dc_tr_frag(cur, offA[0] + a_off(d), offA[1] + a_off(d));
+        al[d] = dc_tr_frag(cur + A_IMG, offA[0] + a_off(d), offA[1] + a_off(d));
       }
     }
 #pragma unroll
     for (int w = 0; w < NBW; ++w) {
-      bh[0][w] = tr_frag(cur, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
-      bl[0][w] = tr_frag(cur + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+      bh[0][w] = dc_tr_frag(cur, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
+      bl[0][w] = dc_tr_frag(cur + B_IMG, offB[0] + b_off(0, w), offB[1] + b_off(0, w));
     }
 #pragma unroll
     for (int g = 0; g < GROUPS; ++g) {
       const int ca = g % RING, ks = g / TAPS, tap = g % TAPS, cbuf = ks & 1;
       if (g + DEPTH < GROUPS) {  // fragments of group g + DEPTH are requested before the MFMAs of group g issue
-        ah[(g + DEPTH) % RING] = tr_frag(cur, offA[0] + a_off(g + DEPTH), offA[1] + a_off(g + DEPTH));
-        al[(g + DEPTH) % RING] = tr_frag(cur + A_IMG, offA[0] + a_off(g + DEPTH), offA[1] + a_off(g + DEPTH));
+        ah[(g + DEPTH) % RING] = dc_tr_frag(cur, offA[0] + a_off(g + DEPTH), offA[1] + a_off(g + DEPTH));
+        al[(g + DEPTH) % RING] = dc_tr_frag(cur + A_IMG, offA[0] + a_off(g + DEPTH), offA[1] + a_off(g + DEPTH));
       }
       // the B fragments of the next k-step: one group ahead (DEPTH 1) or at the head of this k-step (the other buffer is free)
       if ((DEPTH == 1 ? (g + 1) % TAPS == 0 : tap == 0) && (ks + 1) * TAPS < GROUPS) {
 #pragma unroll
         for (int w = 0; w < NBW; ++w) {
-          bh[cbuf ^ 1][w] = tr_frag(cur, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
-          bl[cbuf ^ 1][w] = tr_frag(cur + B_IMG, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
+          bh[cbuf ^ 1][w] = dc_tr_frag(cur, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
+          bl[cbuf ^ 1][w] = dc_tr_frag(cur + B_IMG, offB[0] + b_off(ks + 1, w), offB[1] + b_off(ks + 1, w));
         }
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int w = 0; w < NBW; ++w) {
-        acc[w][tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ca], bh[cbuf][w], acc[w][tap], 0, 0, 0);
-        acc[w][tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bl[cbuf][w], acc[w][tap], 0, 0, 0);
-        acc[w][tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ca], bh[cbuf][w], acc[w][tap], 0, 0, 0);
-      }
+      for (int w = 0; w < NBW; ++w) dc_mfma3(ah[ca], al[ca], bh[cbuf][w], bl[cbuf][w], acc[w][tap]);
       __builtin_amdgcn_sched_barrier(0);
     }
     }

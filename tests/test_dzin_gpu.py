@@ -470,3 +470,92 @@ def test_conv3x3_bwd_joint_64_to_32(dclib, N, H, W):
     with pytest.raises(Exception):          # BN-on-load / fused sums are the 32 -> 32 kernel's
         L.dc_conv3x3_bwd_joint_f16x3(xd.data_ptr(), zd.data_ptr(), zd.data_ptr(), None, dad.data_ptr(), zd.data_ptr(), coef.data_ptr(),
                                      wpd.data_ptr(), dx.data_ptr(), *((None,) * 7), dw.data_ptr(), ws.data_ptr(), N, H, W, Cin, Cout, None)
+
+
+def _joint_case(L, N, H, W, Cin, bnin, seed, da_mul=1.0, x_mul=1.0):
+    """Inputs of one dc_conv3x3_bwd_joint_f16x3 launch on the device (Cout = 32) + run(red_z, x_abound, sums) -> (dx, dw, part, amx);
+    part / amx are NaN-filled before the launch."""
+    Cout = 32
+    rows = L.dc_conv3x3_bwd_joint_blocks(N, H, W, Cin, Cout)
+    assert rows > 0
+    rs = np.random.RandomState(seed)
+    x, z, mean, invstd, gamma, beta, da = _block_case(rs, N, H, W, Cin, Cout)
+    x, da = (x * x_mul).astype(np.float32), (da * da_mul).astype(np.float32)
+    K = (rs.standard_normal((3, 3, Cin, Cout)) * 0.05).astype(np.float32)
+    rmu = (rs.standard_normal(Cin) * 0.2).astype(np.float32); ris = (rs.random_sample(Cin) + 0.5).astype(np.float32)
+    rga = (rs.standard_normal(Cin) * 0.5 + 1.0).astype(np.float32); rbe = (rs.standard_normal(Cin) * 0.3).astype(np.float32)
+    xsc = (rga * ris).astype(np.float32)
+    xsh = (rbe.astype(np.float64) - rmu.astype(np.float64) * xsc.astype(np.float64)).astype(np.float32)
+    zd, dad, coef, _, _, _ = _finalize(L, z, mean, invstd, gamma, beta, da)
+    Kd, xd = dev(K), dev(x)
+    wpd = torch.empty(L.dc_pack_weights_f16x3_floats(9, Cout, Cin), device='cuda')
+    L.dc_pack_weights_f16x3(Kd.data_ptr(), wpd.data_ptr(), 9, Cout, Cin, Cin * Cout, 1, Cout, 1, None)
+    ws = torch.empty(L.dc_conv3x3_bwd_joint_ws_floats(N, H, W, Cin, Cout), device='cuda')
+    rmud, risd, rgad, rbed, xscd, xshd = dev(rmu), dev(ris), dev(rga), dev(rbe), dev(xsc), dev(xsh)
+    _KEEP.extend([wpd, ws])
+
+    def run(red_z=None, x_abound=None, sums=True):
+        dx = torch.full((N, H, W, Cin), float('nan'), device='cuda')
+        dw = torch.full((3, 3, Cin, Cout), float('nan'), device='cuda')
+        part = torch.full((rows * Cin * 2,), float('nan'), device='cuda')
+        amx = torch.full((rows * Cin,), float('nan'), device='cuda')
+        red = (None,) * 7
+        if sums:
+            red = ((xd if red_z is None else red_z).data_ptr(), rmud.data_ptr(), risd.data_ptr(), rgad.data_ptr(), rbed.data_ptr(),
+                   part.data_ptr(), amx.data_ptr())
+        L.dc_conv3x3_bwd_joint_f16x3(xd.data_ptr(), xscd.data_ptr() if bnin else None, xshd.data_ptr() if bnin else None,
+                                     x_abound.data_ptr() if x_abound is not None else None, dad.data_ptr(), zd.data_ptr(),
+                                     coef.data_ptr(), wpd.data_ptr(), dx.data_ptr(), *red, dw.data_ptr(), ws.data_ptr(),
+                                     N, H, W, Cin, Cout, None)
+        torch.cuda.synchronize()
+        return dx, dw, part, amx
+
+    return dict(x=x, z=z, mean=mean, invstd=invstd, gamma=gamma, beta=beta, da=da, K=K, xd=xd), run
+
+
+@pytest.mark.parametrize('N,H,W', [(1, 40, 72), (3, 33, 50)])
+@pytest.mark.parametrize('bnin', [True, False])
+def test_conv3x3_bwd_joint_sums_from_hbm(dclib, N, H, W, bnin):
+    """The fused sums of the layer in front read its pre-BN tensor from LDS when red_z IS the x operand (what the producers
+    staged) and with buffer loads in the epilogue when it is another tensor: a copy of x at a different address takes the
+    second path and must give the same bits -- the same arithmetic in the same order."""
+    c, run = _joint_case(dclib, N, H, W, 32, bnin, H * 5 + W)
+    lds = run()
+    clone = c['xd'].clone()
+    assert clone.data_ptr() != c['xd'].data_ptr()
+    hbm = run(red_z=clone)
+    for name, a, b in zip(('dx', 'dw', 'part', 'amx'), lds, hbm):
+        assert not torch.isnan(a).any(), name
+        assert torch.equal(a, b), name
+
+
+def test_conv3x3_bwd_joint_32_without_sums(dclib):
+    """32 -> 32 with no fused sums (all seven red_* / partial arguments NULL): dx and dW are the bits of the run with sums,
+    the partial buffers are not touched."""
+    c, run = _joint_case(dclib, 1, 40, 72, 32, True, 17)
+    dx, dw, _, _ = run()
+    dx0, dw0, part0, amx0 = run(sums=False)
+    assert not torch.isnan(dx).any() and not torch.isnan(dw).any()
+    assert torch.equal(dx, dx0) and torch.equal(dw, dw0)
+    assert torch.isnan(part0).all() and torch.isnan(amx0).all()
+
+
+@pytest.mark.parametrize('Cin', [32, 64])
+@pytest.mark.parametrize('case', ['tiny', 'huge'])
+def test_conv3x3_bwd_joint_range_guard(dclib, Cin, case):
+    """x_abound given: the x operand is split under the guard's power-of-two scale (here 2^4: max |x| in [2^10, 2^11)), dz under
+    the scale of a gradient of 1e-12 / 1e6 (test_dzin_fp16_range's inputs): neither scale is 1, both are undone exactly in the
+    epilogues -- the float64 oracle at the contraction's 2e-5, unchanged."""
+    N, H, W = 1, 40, 72
+    c, run = _joint_case(dclib, N, H, W, Cin, False, Cin + 3, da_mul={'tiny': 1e-9, 'huge': 3e8}[case], x_mul=300.0)
+    amax = np.abs(c['x']).reshape(-1, Cin).max(0)
+    assert 2.0 ** 10 <= amax.max() < 2.0 ** 11
+    dz_ref, _, _, _ = _dz_ref(c['z'], c['mean'], c['invstd'], c['gamma'], c['beta'], c['da'])
+    dx_ref, dK_ref, _ = on.conv3x3_bwd(c['x'].astype(np.float64), c['K'].astype(np.float64), dz_ref)
+    dx, dw, _, _ = run(x_abound=dev(amax.astype(np.float32)), sums=False)
+    gx, gw = dx.cpu().numpy(), dw.cpu().numpy()
+    assert np.isfinite(gx).all() and np.isfinite(gw).all()
+    ex = np.abs(gx - dx_ref).max() / np.abs(dx_ref).max()
+    ew = np.abs(gw - dK_ref).max() / np.abs(dK_ref).max()
+    print('joint %d -> 32, x_abound, da %s: dx error %.2e, dW error %.2e' % (Cin, case, ex, ew))
+    assert ex < 2e-5 and ew < 2e-5, (ex, ew)
