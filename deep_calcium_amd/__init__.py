@@ -26,6 +26,7 @@ _EXPORTS = {
     'unet2ds': ('UNet2DSummary', 'INVERTIBLE_2D_AUGMENTATIONS', '_ValidationMetricsCB'),
     'nf_metrics': ('nf_mask_metrics',),
     'series': ('SeriesSummarizer', 'summarize_series_device'),
+    'traces': ('RoiTraceExtractor', 'rois_to_csr', 'extract_traces_device', 'write_traces_dataset'),
 }
 _WHERE = dict((name, mod) for mod, names in _EXPORTS.items() for name in names)
 __all__ = sorted(_WHERE)

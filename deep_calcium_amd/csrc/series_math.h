@@ -1,4 +1,4 @@
-// Exact scalar helpers of the series-summary kernels (series.hip): binary16 <-> binary64 conversion with ONE rounding, and the
+// Exact scalar helpers of the series-summary and ROI-trace kernels (series.hip, traces.hip): binary16 <-> binary64 conversion with ONE rounding, and the
 // 128-bit integers the correlation / variance numerators are formed in.  Plain C++ on purpose -- no HIP header, no intrinsic beyond
 // __builtin_clzll -- so the same inline functions compile for the device and into a stand-alone host program
 // (tests/native/series_math_check.cpp, run under the address / undefined-behaviour sanitizers).
@@ -84,6 +84,33 @@ DC_HD DcI128 dc_i128_sub(DcI128 a, DcI128 b) {
   r.lo = a.lo - b.lo;
   r.hi = (int64_t)((uint64_t)a.hi - (uint64_t)b.hi - (a.lo < b.lo ? 1ull : 0ull));
   return r;
+}
+// a + b (wraps like the subtraction)
+DC_HD DcI128 dc_i128_add(DcI128 a, DcI128 b) {
+  DcI128 r;
+  r.lo = a.lo + b.lo;
+  r.hi = (int64_t)((uint64_t)a.hi + (uint64_t)b.hi + (r.lo < a.lo ? 1ull : 0ull));
+  return r;
+}
+DC_HD DcI128 dc_i128_from_i64(int64_t a) {
+  DcI128 r;
+  r.lo = (uint64_t)a;
+  r.hi = a < 0 ? -1 : 0;
+  return r;
+}
+// a * b for a 128-bit a and a 64-bit b: the low 128 bits of the product, i.e. exact whenever the product fits (the ROI trace
+// kernels, traces.hip: T * sum(S^2) < 2^124).  Magnitudes are multiplied limb by limb, the sign is put back at the end.
+DC_HD DcI128 dc_i128_mul_i64(DcI128 a, int64_t b) {
+  const bool neg = (a.hi < 0) != (b < 0);
+  if (a.hi < 0) a = dc_i128_neg(a);
+  const uint64_t ub = b < 0 ? 0ull - (uint64_t)b : (uint64_t)b;
+  const uint64_t a0 = a.lo & 0xffffffffull, a1 = a.lo >> 32, b0 = ub & 0xffffffffull, b1 = ub >> 32;
+  const uint64_t p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+  const uint64_t mid = (p00 >> 32) + (p01 & 0xffffffffull) + (p10 & 0xffffffffull);
+  DcI128 r;
+  r.lo = (p00 & 0xffffffffull) | (mid << 32);
+  r.hi = (int64_t)(p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32) + (uint64_t)a.hi * ub);
+  return neg ? dc_i128_neg(r) : r;
 }
 DC_HD bool dc_i128_is_zero(DcI128 a) { return (a.lo | (uint64_t)a.hi) == 0; }
 // nearest binary64 (ties to even), ONE rounding: the top 64 bits of the magnitude with a sticky bit for everything below them are

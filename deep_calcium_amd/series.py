@@ -44,6 +44,46 @@ def _frame_dtype(dtype):
     return dt
 
 
+class _TwoSlotStage(object):
+    """Two pinned host slots and two device slots of `shape` = (C, H, W) int16: the H2D copy of chunk k + 1 (copy stream) runs
+    beside the kernels on chunk k (the caller's stream); events hand the slots back and forth.  The pinned slots are cached by
+    name (net._pinned): every user passes a `tag` of its own, so two users alive at once never share a slot."""
+
+    def __init__(self, torch, net, device, tag, shape):
+        self._torch, self.chunk_frames = torch, int(shape[0])
+        self._host = [net._pinned('%s%d' % (tag, k), shape, torch.int16, entry=True) for k in range(2)]
+        self._dev = [torch.empty(shape, dtype=torch.int16, device=device) for _ in range(2)]
+        with torch.cuda.device(device):
+            self._copy_stream = torch.cuda.Stream(device=device)
+        self._read = [None, None]         # event behind the last kernel that read device slot k
+        self._slot = 0
+
+    def run(self, frames, main, launch):
+        """Cuts `frames` (numpy, 16-bit) into chunks, uploads each and calls launch(device pointer, frames in the chunk), which
+        enqueues the chunk's kernels on `main`.  Called with the device current."""
+        torch = self._torch
+        for a in range(0, frames.shape[0], self.chunk_frames):
+            part = frames[a:a + self.chunk_frames]
+            tc, k = part.shape[0], self._slot
+            self._slot ^= 1
+            host, dev = self._host[k], self._dev[k]
+            if host[1] is not None:
+                host[1].synchronize()                  # the copy that last read this pinned slot has finished
+            host[0].numpy()[:tc] = part.view(np.int16)         # same bits; the kernels are told the signedness
+            with torch.cuda.stream(self._copy_stream):
+                if self._read[k] is not None:
+                    self._copy_stream.wait_event(self._read[k])      # the kernels on chunk k - 2 are done with the slot
+                dev[:tc].copy_(host[0][:tc], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self._copy_stream)
+            host[1] = ev
+            main.wait_event(ev)
+            launch(dev.data_ptr(), tc)
+            done = torch.cuda.Event()
+            done.record(main)
+            self._read[k] = done
+
+
 class SeriesSummarizer(object):
     """Owns the device state of one recording's summaries; feed() the frames in order, in chunks of any size, then result()."""
 
@@ -96,14 +136,7 @@ class SeriesSummarizer(object):
         self.mean16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None      # float16 BITS
         self.max16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None
         self.xy = torch.empty((4, n), dtype=torch.int64, device=dev) if self._xy else None
-        # two staging slots: the H2D copy of chunk k + 1 (copy stream) runs beside the kernels on chunk k (current stream)
-        C = self.chunk_frames
-        self._host = [net._pinned('series_stage%d' % k, (C, H, W), torch.int16, entry=True) for k in range(2)]
-        self._dev = [torch.empty((C, H, W), dtype=torch.int16, device=dev) for _ in range(2)]
-        with torch.cuda.device(dev):
-            self._copy_stream = torch.cuda.Stream(device=dev)
-        self._read = [None, None]         # event behind the last kernel that read device slot k
-        self._slot = 0
+        self._stage = _TwoSlotStage(torch, net, dev, 'series_stage', (self.chunk_frames, H, W))
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
@@ -124,33 +157,17 @@ class SeriesSummarizer(object):
         uns = int(self.dtype == np.dtype(np.uint16))
         with torch.cuda.device(self.device):
             main = self._stream()
-            for a in range(0, frames.shape[0], self.chunk_frames):
-                part = frames[a:a + self.chunk_frames]
-                tc, k = part.shape[0], self._slot
-                self._slot ^= 1
-                host, dev = self._host[k], self._dev[k]
-                if host[1] is not None:
-                    host[1].synchronize()                  # the copy that last read this pinned slot has finished
-                host[0].numpy()[:tc] = part.view(np.int16)         # same bits; the kernels are told the signedness
-                with torch.cuda.stream(self._copy_stream):
-                    if self._read[k] is not None:
-                        self._copy_stream.wait_event(self._read[k])      # the kernels on chunk k - 2 are done with the slot
-                    dev[:tc].copy_(host[0][:tc], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self._copy_stream)
-                host[1] = ev
-                main.wait_event(ev)
-                st, fp = main.cuda_stream, dev.data_ptr()
+            st = main.cuda_stream
+
+            def reduce(fp, tc):
                 L.dc_series_accumulate(fp, uns, tc, self.fed, self.n_frames,
                                        self.mean16.data_ptr() if self._chain else None,
                                        self.max16.data_ptr() if self._chain else None,
                                        self.sum.data_ptr(), self.sumsq.data_ptr(), self.vmax.data_ptr(), H, W, st)
                 if self._xy:
                     L.dc_series_accumulate_xy(fp, uns, tc, self.fed, self.xy.data_ptr(), H, W, st)
-                done = torch.cuda.Event()
-                done.record(main)
-                self._read[k] = done
                 self.fed += tc
+            self._stage.run(frames, main, reduce)
         self._images = None
         return self
 

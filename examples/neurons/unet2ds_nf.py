@@ -1,11 +1,13 @@
 #!/usr/bin/env python
 """Neurofinder training, evaluation and prediction with the HIP UNet2DS path: the reference's example
 (/root/reference/examples/neurons/unet2ds_nf.py) with the same three actions, arguments, seeds and call sequence, on
-`deep_calcium_amd.UNet2DSummary`.
+`deep_calcium_amd.UNet2DSummary`, plus `traces`: predict the neurons' mask, then extract one fluorescence trace per neuron from
+`series/raw` on the GPU and write the file the reference's spikes model reads (models/spikes/unet_1d_segmentation.py:182-187).
 
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -29,7 +31,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 
-from deep_calcium_amd import UNet2DSummary, parallel             # noqa: E402
+from deep_calcium_amd import UNet2DSummary, parallel, extract_traces_device, write_traces_dataset      # noqa: E402
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -100,6 +102,24 @@ def prediction(dataset_name, model_path, checkpoints_dir):
         nf_submit(Mp, names, '%s/submission_latest%s.json' % (model.cpdir, ('_TTA' if aug else '')))
 
 
+def traces(dataset_name, model_path, checkpoints_dir, kind='mean'):
+    """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
+    write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
+    model starts from such a file)."""
+    logger = logging.getLogger('traces')
+    dspaths = nf_find_hdf5(dataset_name)
+    model = UNet2DSummary(cpdir=checkpoints_dir)
+    Mp, names = model.predict(dspaths, model_path=model_path, window_shape=(512, 512), save=False, augmentation=True)
+    for dspath, mp, name in zip(dspaths, Mp, names):
+        mask = np.asarray(mp).round().astype(np.uint8)
+        if not mask.any():
+            logger.info('%s: no neurons predicted, no traces file.' % name)
+            continue
+        tr = extract_traces_device(dspath, mask, kind=kind)
+        out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name)
+        logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser(description='CLI for UNet2DS model.')
     sp = ap.add_subparsers(title='actions', description='Choose an action.')
@@ -120,8 +140,14 @@ if __name__ == '__main__':
     sp_prd.add_argument('dataset_name', help='dataset name', default='all', type=str)
     sp_prd.add_argument('-m', '--model_path', help='path to model', required=True)
     sp_prd.add_argument('-c', '--checkpoints_dir', help='checkpoint directory', default=CHECKPOINTS_DIR)
+    sp_trc = sp.add_parser('traces', help='CLI for ROI traces of predicted neurons.')
+    sp_trc.set_defaults(which='traces')
+    sp_trc.add_argument('dataset_name', help='dataset name', default='all', type=str)
+    sp_trc.add_argument('-m', '--model_path', help='path to model', required=True)
+    sp_trc.add_argument('-c', '--checkpoints_dir', help='checkpoint directory', default=CHECKPOINTS_DIR)
+    sp_trc.add_argument('--kind', help='what a trace holds', default='mean', choices=('sum', 'mean', 'zscore'))
     args = vars(ap.parse_args())
     if 'which' not in args:
-        ap.error('choose an action: train, evaluate or predict')
-    f = {'train': training, 'evaluate': evaluation, 'predict': prediction}[args.pop('which')]
+        ap.error('choose an action: train, evaluate, predict or traces')
+    f = {'train': training, 'evaluate': evaluation, 'predict': prediction, 'traces': traces}[args.pop('which')]
     f(**args)

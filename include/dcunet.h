@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 108
+#define DC_ABI_VERSION 109
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -498,6 +498,37 @@ int dc_series_finalize(const long* sum, const long* sumsq, const long* xy, float
  * ws: float[dc_series_standardize_ws_floats()], 8-byte aligned.  in == out is allowed. */
 long dc_series_standardize_ws_floats(int H, int W);
 int dc_image_standardize(const float* in, float* out, float* ws, int H, int W, dc_stream_t stream);
+
+/* ---- ROI traces: a recording (T,H,W) of 16-bit frames + a set of ROIs -> one fluorescence trace per ROI -------------------
+ * What the reference's spikes model reads from its dataset files: `traces`, a (no. ROIs, no. frames) matrix
+ * (unet_1d_segmentation.py:182-187), normalised per trace as (traces - mean) / std along time (unet_1d_segmentation.py:158-167).
+ * The reference has no code that makes the matrix from a recording and a mask; this is that step.
+ * frames: as for dc_series_accumulate (int16 / uint16 by is_unsigned, [tc][H][W] contiguous, 2-byte aligned), a chunk of the
+ * recording starting at frame t0.
+ * ROIs are CSR rows, all DEVICE memory, never read on the host: row_off int32[S + 1] (non-decreasing, row_off[0] = 0), row_pix
+ * int32[row_off[S]] flat pixel indices y * W + x, row_roi int32[S] (nullable) the ROI (output row) CSR row s adds into; NULL
+ * means CSR row s IS ROI s, and then S == R.  ROIs may overlap, an index listed twice counts twice, a row may be empty, an
+ * index outside [0, H*W) contributes 0 and is never dereferenced, a row whose row_roi is outside [0, R) adds nowhere.  A
+ * caller cuts long ROIs into rows of bounded length (row_roi names the owner), so that one whole-image ROI among hundreds of
+ * small ones does not make the launch as long as one workgroup walking it.
+ *   dc_roi_trace_accumulate: sums = int64[R][ld].  Columns [t0, t0 + tc) of ALL R rows are fully written (never pre-clear),
+ *     no other column is touched: sums[r][t0 + t] = the exact integer sum of ROI r's pixels in frame t of the chunk --
+ *     independent of the chunking of the recording and of how ROIs are cut into rows.
+ *   dc_roi_trace_finalize: areas int32[R] = pixels per ROI; each output float[R][T] dense, nullable.
+ *     mean[r][t] = double(sums) / double(area), ONE rounding to float32 (numpy's (sums / area).astype(float32), bit for bit).
+ *     zscore[r][t] = (trace - mean_t) / std_t with the population standard deviation; the area cancels:
+ *     (T S_t - sum S) / sqrt(T sum S^2 - (sum S)^2), both numerators exact in 128-bit integers, each rounded ONCE to double,
+ *     then sqrt and divide in double and one rounding to float32: within 1 float32 ulp.  A trace that is constant in time
+ *     (T == 1 included) gives exactly 0 where numpy gives NaN (0 / 0) and the reference's asserts (:165-166) fail; an ROI of
+ *     area <= 0 gives 0 in both outputs.
+ * DC_ROI_TRACE_MAX_VOLUME: T * H * W <= 2^46 keeps (T * 65535 * H * W)^2 < 2^124, so every intermediate of the z-score fits
+ * (for ROIs that list at most H * W pixels); beyond: DC_EUNSUP (-3).  dc_roi_trace_accumulate checks (t0 + tc) * H * W,
+ * dc_roi_trace_finalize, which is not told the image size, T alone. */
+#define DC_ROI_TRACE_MAX_VOLUME 70368744177664L
+int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
+                            const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);
+int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,
+                          dc_stream_t stream);
 
 /* misc */
 int dc_fill(float* p, long n, float value, dc_stream_t stream);
