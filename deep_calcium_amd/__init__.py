@@ -27,6 +27,8 @@ _EXPORTS = {
     'nf_metrics': ('nf_mask_metrics',),
     'series': ('SeriesSummarizer', 'summarize_series_device'),
     'traces': ('RoiTraceExtractor', 'rois_to_csr', 'extract_traces_device', 'write_traces_dataset'),
+    'spikes': ('UNet1DSegmentation', 'predict_spikes_device'),
+    'unet1d': ('UNet1DEngine',),
 }
 _WHERE = dict((name, mod) for mod, names in _EXPORTS.items() for name in names)
 __all__ = sorted(_WHERE)

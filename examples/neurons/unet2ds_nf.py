@@ -118,6 +118,7 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean'):
         tr = extract_traces_device(dspath, mask, kind=kind)
         out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
+        logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
 
 
 if __name__ == '__main__':

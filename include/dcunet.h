@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 109
+#define DC_ABI_VERSION 110
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -529,6 +529,39 @@ int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0
                             const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);
 int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,
                           dc_stream_t stream);
+
+/* ---- UNet1D spike inference: traces in, spike probabilities out ------------------------------------------------------------
+ * The reference's second model family, UNet1DSegmentation: the network unet1d (unet_1d_segmentation.py:49-148) as its predict()
+ * runs it (unet_1d_segmentation.py:422-459), inference mode only (Dropout is the identity; BatchNormalization uses its moving
+ * statistics, folded by dc_bn_fold with eps 1e-3).  Input: the (N,T) matrix of z-scored traces dc_roi_trace_finalize writes.
+ * Activations are channels-last fp32 [N][T][C]; a tensor argument `p, ld` addresses channel c of sample t of trace n at
+ * p[(n*T + t)*ld + c] (ld: a multiple of 4), so a producer writes its channel slice of a concat buffer: the skip tensors
+ * are produced straight into channels [2C, 3C) of the buffer the decoder's conv_layer reads (ld = 3C), the pooling reads them from
+ * there, and dc_upsample1d_2x_fwd fills channels [0, 2C).  Every kernel works inside one trace: nothing is read across a trace
+ * boundary and a sample's arithmetic does not depend on N, so a trace's outputs are the same bits however the traces are batched.
+ *   dc_conv1d_k5_fwd: conv_layer, Conv1D(nbf, 5, strides=1, padding='same') + BatchNormalization + relu (:81-84):
+ *     y[n][t][:] = relu?(fmaf(sum_{tap,c} x[n][t+tap-2][c] w[tap][c][:], scale, shift)); samples outside [0,T) of the SAME trace are 0.
+ *     x dense [N][T][Cin]; wp = dc_pack_weights(taps 5, K=Cin, Ncols=Cout, s_tap=Cin*Cout, s_k=Cout, s_n=1, flip 0) of the Keras
+ *     (5,Cin,Cout) kernel; (scale, shift) from dc_bn_fold (the conv bias is folded in).  Cin % 4 == 0, Cout % 4 == 0, any T, N >= 1.
+ *     Implicit GEMM on the fp32 matrix cores, fp32 accumulation in a fixed order (channel chunk of 16, then tap, then channel).
+ *   dc_conv1d_k5_c1_fwd: the first conv_layer (:86-89), Cin == 1: x is the (N,T) trace matrix itself, w the plain (5,1,Cout) kernel
+ *     (16-byte aligned, like scale / shift); the taps are an fmaf chain in tap order.
+ *   dc_maxpool1d_2_fwd: MaxPooling1D(2, strides=2) (:93).  out dense [N][T/2][C], T/2 rounded down (an odd last sample is dropped;
+ *     T == 1: the output is empty, nothing is launched, DC_OK).  Bit-exact.
+ *   dc_upsample1d_2x_fwd: UpSampling1D() (:79).  in dense [N][T][C]; out[n][2t][:] = out[n][2t+1][:] = in[n][t][:].  Bit-exact.
+ *   dc_spike_head_fwd: Conv1D(2, 1) -> MaxPooling1D(margin + 1, strides=1, padding='same') -> softmax -> x[:, :, -1] (:139-145), pool =
+ *     margin + 1 in 1..64.  a dense [N][T][C], kh [C][2], bh [2], p float32 [N][T]:
+ *       l[n][t][j] = bh[j] + sum_c a[n][t][c] kh[c][j];   m[n][t][j] = max l[n][max(0, t-(pool-1)/2) .. min(T-1, t+pool/2)][j]
+ *       p[n][t] = 1 / (1 + exp(m0 - m1))
+ *     (TensorFlow 'SAME': the smaller pad is on the left, and padding never wins the max; T < pool is fine.) */
+int dc_conv1d_k5_fwd(const float* x, const float* wp, const float* scale, const float* shift, int relu, float* y, long y_ld,
+                     int N, int T, int Cin, int Cout, dc_stream_t stream);
+int dc_conv1d_k5_c1_fwd(const float* x, const float* w, const float* scale, const float* shift, int relu, float* y, long y_ld,
+                        int N, int T, int Cout, dc_stream_t stream);
+int dc_maxpool1d_2_fwd(const float* in, long in_ld, float* out, int N, int T, int C, dc_stream_t stream);
+int dc_upsample1d_2x_fwd(const float* in, float* out, long out_ld, int N, int T, int C, dc_stream_t stream);
+int dc_spike_head_fwd(const float* a, const float* kh, const float* bh, int pool, float* p, int N, int T, int C,
+                      dc_stream_t stream);
 
 /* misc */
 int dc_fill(float* p, long n, float value, dc_stream_t stream);
