@@ -29,6 +29,8 @@ _EXPORTS = {
     'traces': ('RoiTraceExtractor', 'rois_to_csr', 'extract_traces_device', 'write_traces_dataset'),
     'spikes': ('UNet1DSegmentation', 'predict_spikes_device'),
     'unet1d': ('UNet1DEngine',),
+    'unet1d_train': ('UNet1DTrainEngine',),
+    'spikes_fit': ('TrainableUNet1DSegmentation', 'get_dataset_spikes', 'fit_spikes_device'),
 }
 _WHERE = dict((name, mod) for mod, names in _EXPORTS.items() for name in names)
 __all__ = sorted(_WHERE)

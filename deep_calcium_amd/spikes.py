@@ -9,8 +9,8 @@ Keras model file of unet1d (:49-148) in, one uint8 (no. ROIs, no. frames) spike 
     p = model.predict_proba(traces, 'unet1d_model.hdf5')                                        # (R,T) normalised -> float32 (R,T)
 
 What differs from the reference, stated:
-  * fit() is not covered: training the 1-D network (backward kernels, the weighted loss, the F2 metrics, the validation
-    splits of :217-420) does not exist here; it raises NotImplementedError.
+  * fit() is not covered by THIS class: it raises NotImplementedError.  Training the 1-D network (:217-420) lives in
+    spikes_fit.TrainableUNet1DSegmentation, a subclass with the reference's fit() signature.
   * Trace length.  The reference graph exists only for T % 16 == 0 (four poolings; Keras fails at the first concatenate
     otherwise).  Here a trace of ANY T >= 1 is extended on the right with zeros -- the mean of a z-scored trace -- to the next
     multiple of 16 and the output is cropped to T.  This has no reference counterpart; for T % 16 == 0 nothing is padded.

@@ -120,6 +120,15 @@ class UNet1DEngine(object):
         return self._buf
 
     def forward(self, x):
+        return self._run(x, True)
+
+    def features(self, x):
+        """Everything but the head: -> the device pointer of the head's input, dense float32 (B, T, nfb), in a buffer the
+        engine owns (valid until its next call; ordered on torch's current stream).  The training engine's evaluate() puts
+        dc_spike_head_train_fwd (the head plus loss and metric sums) on it."""
+        return self._run(x, False)
+
+    def _run(self, x, head):
         torch = self._torch
         if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
             raise ValueError('x must be a float32 (B, T) tensor')
@@ -136,7 +145,7 @@ class UNet1DEngine(object):
             buf = self._buffers(B, T)
             a, b, pool = buf['a'].data_ptr(), buf['b'].data_ptr(), buf['pool'].data_ptr()
             cat = [t.data_ptr() for t in buf['cat']]
-            out = torch.empty((B, T), dtype=torch.float32, device=self.device)
+            out = torch.empty((B, T), dtype=torch.float32, device=self.device) if head else None
 
             def conv(k, src, dst, ld, t):
                 wp, sc, sh, ci, co = self.layers[k]
@@ -161,6 +170,7 @@ class UNet1DEngine(object):
                 L.dc_upsample1d_2x_fwd(b, cat[lvl], 3 * c, B, t >> 1, 2 * c, st)    # channels [0, 2C)
                 conv(10 + 2 * j, cat[lvl], a, c, t)
                 conv(11 + 2 * j, a, b, c, t)
-            L.dc_spike_head_fwd(b, self._kh, self._bh, self.margin + 1, out.data_ptr(), B, T, nfb, st)
+            if head:
+                L.dc_spike_head_fwd(b, self._kh, self._bh, self.margin + 1, out.data_ptr(), B, T, nfb, st)
             x.record_stream(main)
-        return out
+        return out if head else b

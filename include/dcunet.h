@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 110
+#define DC_ABI_VERSION 111
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -562,6 +562,64 @@ int dc_maxpool1d_2_fwd(const float* in, long in_ld, float* out, int N, int T, in
 int dc_upsample1d_2x_fwd(const float* in, float* out, long out_ld, int N, int T, int C, dc_stream_t stream);
 int dc_spike_head_fwd(const float* a, const float* kh, const float* bh, int pool, float* p, int N, int T, int C,
                       dc_stream_t stream);
+
+/* ---- UNet1D training: the 1-D hot path of a train step ---------------------------------------------------------------------
+ * unet1d (unet_1d_segmentation.py:49-148) as fit() trains it (:217-380) with the loss and metrics of utils/spikes.py:11-57.
+ * A 1-D activation [N][T][C] is a [pixels][C] tensor with pixels = N*T, so BatchNorm / ReLU / Dropout (dc_bn_stats_finalize,
+ * dc_bn_relu_drop_fwd, dc_bn_bwd_reduce / _finalize / _apply), dc_adam_step_flat and dc_reduce_partials above serve this network
+ * as they are.  Conventions of the inference section: channels-last fp32, `p, ld` strided tensors, nothing read across a trace
+ * boundary; sums are fp32 (or double) in a FIXED order without atomics, so a repeated call gives the same bits.
+ *   training-mode forward of conv_layer (:81-84): z = conv + bias is dc_conv1d_k5_fwd / _c1_fwd with scale = 1 (a vector of ones),
+ *     shift = bias, relu = 0 (fmaf(acc, 1, b) is exact); then
+ *   dc_conv1d_stats: partial[blocks][C][2] = (sum z, sum z^2) per channel in double, blocks = dc_conv1d_stats_blocks(pixels, C) --
+ *     the layout dc_bn_stats_finalize reads with parts = blocks, groups = 1.  z [pixels][C] with sample stride z_ld; C % 4 == 0,
+ *     C <= 1024.
+ *   data gradient of conv_layer: dx[n][t][ci] = sum_{tap,co} dz[n][t-tap+2][co] w[tap][ci][co] is dc_conv1d_k5_fwd on dz with
+ *     wp = dc_pack_weights(w, taps 5, K=Cout, Ncols=Cin, s_tap=Cin*Cout, s_k=1, s_n=Cout, flip 1), scale = 1, shift = 0, relu = 0
+ *     (y_ld lets it write dx in place).  The first layer (Cin == 1) needs none.
+ *   dc_conv1d_k5_wgrad: dw[tap][ci][co] = sum_{n,t} x[n][t+tap-2][ci] dz[n][t][co], x zero outside [0,T) of the SAME trace.
+ *     x dense [N][T][Cin], dz dense [N][T][Cout], dw the Keras (5,Cin,Cout) kernel gradient; Cin % 4 == 0, Cout % 4 == 0, any T, N >= 1.
+ *     fp32 matrix cores; the contraction over N*T is split over dc_conv1d_k5_wgrad_blocks() workgroups into slabs of
+ *     ws (float[dc_conv1d_k5_wgrad_ws_floats()], caller-owned, contents irrelevant) that dc_reduce_partials adds in a fixed order.
+ *     The bias gradient is the dbias_partial of dc_bn_bwd_apply.
+ *   dc_conv1d_k5_c1_wgrad: the first layer; x is the (N,T) trace matrix, dw the (5,1,Cout) kernel gradient, Cout <= 1024.
+ *   dc_maxpool1d_2_bwd: dx[n][2t+i][c] = (i == argmax ? dy[n][t][c] : 0) + (skip ? skip[n][2t+i][c] : 0).  dy dense [N][T/2][C];
+ *     `in, in_ld` the stored forward INPUT of the pooling, from which the argmax is recomputed (the first of two equal values wins);
+ *     `skip, skip_ld` (nullable) the gradient arriving over the skip connection, i.e. the [2C,3C) slice of the decoder conv's dx;
+ *     dx [N][T][C] with sample stride dx_ld.  An odd last sample gets only its skip gradient.  Values are moved and added once: exact.
+ *   dc_upsample1d_2x_drop_fwd / _bwd: UpSampling1D() + Dropout (:114-115).  out[n][2t+i][c] = in[n][t][c] * f[n][2t+i][c], and
+ *     din[n][t][c] = dout[n][2t][c] f[n][2t][c] + dout[n][2t+1][c] f[n][2t+1][c], with f = mask / keep.  Dropout as in
+ *     dc_bn_relu_drop_fwd: keep >= 1 -> none (the forward is then dc_upsample1d_2x_fwd bit for bit); mask != NULL -> explicit uint8
+ *     {0,1} [N][2T][C] (4-byte aligned); else the counter RNG(seed) on the element index of the dense up-sampled tensor.
+ *   dc_spike_head_train_fwd: dc_spike_head_fwd (the same p, bit for bit) plus, against labels y (uint8 [N][T]),
+ *     partial[blocks][8] = {sum l, sum round(p) y, sum round(p), sum clip(y - round(p), 0, 1), sum y, 0, 0, 0},
+ *     l = -(wpos y log(p + 1e-7) + wneg (1 - y) log(1 - p + 1e-7)), round half to even; blocks = dc_spike_head_train_fwd_blocks(N, T);
+ *     reduce with dc_reduce_partials_f64(partial, blocks, 8, sums).  The reported loss is sums[0] / (N T).  1 - p is formed as
+ *     1 / (1 + exp(m1 - m0)), so it keeps its digits where p rounds to 1.
+ *   dc_spike_head_train_bwd: gradient of that mean loss.  dm1[t] = dl/dp p (1 - p) / (N T), dm0 = -dm1; dm_j[t] goes to the FIRST
+ *     maximal logit of t's 'SAME' window (gathered in ascending t); da[n][s][c] = sum_j dl_j[s] kh[c][j] (dense [N][T][C]);
+ *     grad_partial[blocks][2C+2] = the blocks' shares of (dkh[c][j] ..., dbh[0], dbh[1]), blocks = dc_spike_head_train_bwd_blocks(N, T):
+ *     dc_reduce_partials(grad_partial, blocks, 2C+2, 1, out, tmp) yields the head's kernel and bias gradients back to back. */
+int dc_conv1d_stats_blocks(long pixels, int C);
+int dc_conv1d_stats(const float* z, long z_ld, double* partial, long pixels, int C, dc_stream_t stream);
+long dc_conv1d_k5_wgrad_ws_floats(int N, int T, int Cin, int Cout);
+int dc_conv1d_k5_wgrad_blocks(int N, int T, int Cin, int Cout);
+int dc_conv1d_k5_wgrad(const float* x, const float* dz, float* dw, float* ws, int N, int T, int Cin, int Cout,
+                       dc_stream_t stream);
+long dc_conv1d_k5_c1_wgrad_ws_floats(int N, int T, int Cout);
+int dc_conv1d_k5_c1_wgrad(const float* x, const float* dz, float* dw, float* ws, int N, int T, int Cout, dc_stream_t stream);
+int dc_maxpool1d_2_bwd(const float* dy, const float* in, long in_ld, const float* skip, long skip_ld, float* dx, long dx_ld,
+                       int N, int T, int C, dc_stream_t stream);
+int dc_upsample1d_2x_drop_fwd(const float* in, float* out, long out_ld, const uint8_t* mask, float keep, uint64_t seed,
+                              int N, int T, int C, dc_stream_t stream);
+int dc_upsample1d_2x_drop_bwd(const float* dout, long dout_ld, const uint8_t* mask, float keep, uint64_t seed, float* din,
+                              int N, int T, int C, dc_stream_t stream);
+int dc_spike_head_train_fwd_blocks(int N, int T);
+int dc_spike_head_train_bwd_blocks(int N, int T);
+int dc_spike_head_train_fwd(const float* a, const float* kh, const float* bh, int pool, const uint8_t* y, float wpos, float wneg,
+                            float* p, float* partial, int N, int T, int C, dc_stream_t stream);
+int dc_spike_head_train_bwd(const float* a, const float* kh, const float* bh, int pool, const uint8_t* y, float wpos, float wneg,
+                            float* da, float* grad_partial, int N, int T, int C, dc_stream_t stream);
 
 /* misc */
 int dc_fill(float* p, long n, float value, dc_stream_t stream);
