@@ -4,14 +4,15 @@
 //   dc_conv1d_k5_fwd     Conv1D(nbf, 5, 'same') + BatchNormalization + relu  (:81-84)   implicit GEMM, fp32 matrix cores
 //   dc_conv1d_k5_c1_fwd  the same block on the 1-channel network input       (:86-89)   vector kernel, K = 5
 //   dc_maxpool1d_2_fwd   MaxPooling1D(2, strides=2)                          (:93)
-//   dc_upsample1d_2x_fwd UpSampling1D()                                      (:79)
+//   dc_upsample1d_2x_fwd UpSampling1D()                                      (:79)         and, in training, with Dropout:
+//                        dc_upsample1d_2x_drop_fwd / _bwd                    (:114-115)
 //   dc_spike_head_fwd    Conv1D(2, 1) -> MaxPooling1D(margin + 1, 1, 'same') -> softmax -> [:, :, -1]   (:139-145)
 //
 // Activations are channels-last fp32 [N][T][C]; a trace is one row of N and NOTHING crosses from one trace into the next:
 // every workgroup of every kernel here works inside one trace, the convolution halo outside [0, T) of that trace is zero,
 // and the contraction order of a sample does not depend on N or on where the trace sits in the batch -- a trace's
 // probabilities are the same bits however it is batched.
-#include "igemm_common.h"
+#include "spikes_common.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Conv1D(k = 5, 'same') as an im2col-free implicit GEMM (the 1-D sibling of igemm_conv.hip, same LDS layout):
@@ -191,9 +192,7 @@ static int conv1d_check(const char* fn, const void* x, const void* w, const void
                         long y_ld, int N, int T, int Cin, int Cout) {
   DC_REQUIRE(x && w && scale && shift && y, DC_EINVAL, "%s: null pointer", fn);
   DC_REQUIRE(dc_aligned16(x) && dc_aligned16(w) && dc_aligned16(y), DC_EINVAL, "%s: pointers must be 16-byte aligned", fn);
-  DC_REQUIRE(N >= 1 && T >= 1, DC_EINVAL, "%s: N=%d and T=%d must be >= 1", fn, N, T);
-  DC_REQUIRE(Cin >= 1 && Cout >= 4 && Cout % 4 == 0, DC_EINVAL, "%s: Cout=%d must be a positive multiple of 4", fn, Cout);
-  DC_REQUIRE(y_ld >= Cout && y_ld % 4 == 0, DC_EINVAL, "%s: y_ld=%ld must be a multiple of 4 and >= Cout=%d", fn, y_ld, Cout);
+  if (int rc = spikes_check_shape(fn, N, T, "Cout", Cout, "y_ld", y_ld, Cin >= 1)) return rc;
   DC_REQUIRE((long)T * Cin < (1L << 31) && (long)T * y_ld < (1L << 31), DC_EUNSUP, "%s: one trace exceeds 2^31 elements", fn);
   return DC_OK;
 }
@@ -245,11 +244,6 @@ __global__ __launch_bounds__(256) void conv1d_k5_c1_kernel(const float* __restri
   }
 }
 
-static int spikes_blocks(long total) {
-  const long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
 extern "C" int dc_conv1d_k5_c1_fwd(const float* x, const float* w, const float* scale, const float* shift, int relu, float* y,
                                    long y_ld, int N, int T, int Cout, dc_stream_t stream) {
   if (int rc = conv1d_check("dc_conv1d_k5_c1_fwd", w, w, scale, shift, y, y_ld, N, T, 1, Cout)) return rc;
@@ -284,9 +278,7 @@ __global__ __launch_bounds__(256) void maxpool1d_2_kernel(const float* __restric
 extern "C" int dc_maxpool1d_2_fwd(const float* in, long in_ld, float* out, int N, int T, int C, dc_stream_t stream) {
   DC_REQUIRE(in && out, DC_EINVAL, "dc_maxpool1d_2_fwd: null pointer");
   DC_REQUIRE(dc_aligned16(in) && dc_aligned16(out), DC_EINVAL, "dc_maxpool1d_2_fwd: pointers must be 16-byte aligned");
-  DC_REQUIRE(N >= 1 && T >= 1, DC_EINVAL, "dc_maxpool1d_2_fwd: N=%d and T=%d must be >= 1", N, T);
-  DC_REQUIRE(C >= 4 && C % 4 == 0, DC_EINVAL, "dc_maxpool1d_2_fwd: C=%d must be a positive multiple of 4", C);
-  DC_REQUIRE(in_ld >= C && in_ld % 4 == 0, DC_EINVAL, "dc_maxpool1d_2_fwd: in_ld=%ld must be a multiple of 4 and >= C=%d", in_ld, C);
+  if (int rc = spikes_check_shape("dc_maxpool1d_2_fwd", N, T, "C", C, "in_ld", in_ld)) return rc;
   const int To = T / 2;
   if (To == 0) return DC_OK;          // T == 1: the output is empty, nothing is launched
   const long total = (long)N * To * (C / 4);
@@ -297,90 +289,117 @@ extern "C" int dc_maxpool1d_2_fwd(const float* in, long in_ld, float* out, int N
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// UpSampling1D() (:79): out[n][2t][c] = out[n][2t+1][c] = in[n][t][c], written into the first C channels of the concat
-// buffer the next conv_layer reads (sample stride out_ld; the skip connection already sits behind them).
-__global__ __launch_bounds__(256) void upsample1d_2x_kernel(const float* __restrict__ in, float* __restrict__ out, long out_ld,
-                                                            int C4, long total) {
+// UpSampling1D() (:79), in training followed by Dropout (:114-115 and the three decoder levels after it):
+//   out[n][2t][c] = in[n][t][c] * f[n][2t][c],  out[n][2t+1][c] = in[n][t][c] * f[n][2t+1][c],  f = keep-mask / keep,
+// written into the first C channels of the concat buffer the next conv_layer reads (sample stride out_ld; the skip connection
+// already sits behind them).  The dropout element index is that of the DENSE up-sampled tensor [N][2T][C]
+// (elem = (n * 2T + u) * C + c), mask / seed conventions of dc_bn_relu_drop_fwd.  keep == 1 (inference: dc_upsample1d_2x_fwd
+// launches the same kernel) reads no mask, draws nothing and moves the values bit-exact.
+__device__ __forceinline__ f32x4 up1d_factor(const uint8_t* __restrict__ mask, uint64_t seed, float keep, float inv_keep, long elem) {
+  f32x4 f;
+  if (mask) {
+    const uchar4 m = *reinterpret_cast<const uchar4*>(mask + elem);
+    f[0] = m.x ? inv_keep : 0.f; f[1] = m.y ? inv_keep : 0.f; f[2] = m.z ? inv_keep : 0.f; f[3] = m.w ? inv_keep : 0.f;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f[e] = dc_keep_factor(seed, (uint64_t)(elem + e), keep, inv_keep);
+  }
+  return f;
+}
+
+__global__ __launch_bounds__(256) void upsample1d_2x_drop_fwd_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                     long out_ld, const uint8_t* __restrict__ mask, float keep,
+                                                                     uint64_t seed, int C4, long total) {
+  const bool drop = keep < 1.f;
+  const float inv_keep = drop ? 1.f / keep : 1.f;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int cg = (int)(i % C4);
     const long s = i / C4;            // n * T + t: output samples 2s and 2s + 1 (2 * (n * T + t) = n * 2T + 2t)
     const f32x4 v = reinterpret_cast<const f32x4*>(in)[i];
+    f32x4 v0 = v, v1 = v;
+    if (drop) {
+      const long elem = (2 * s * C4 + cg) * 4;
+      v0 *= up1d_factor(mask, seed, keep, inv_keep, elem);
+      v1 *= up1d_factor(mask, seed, keep, inv_keep, elem + 4L * C4);
+    }
     float* dst = out + 2 * s * out_ld + 4 * cg;
-    *reinterpret_cast<f32x4*>(dst) = v;
-    *reinterpret_cast<f32x4*>(dst + out_ld) = v;
+    *reinterpret_cast<f32x4*>(dst) = v0;
+    *reinterpret_cast<f32x4*>(dst + out_ld) = v1;
+  }
+}
+
+__global__ __launch_bounds__(256) void upsample1d_2x_drop_bwd_kernel(const float* __restrict__ dout, long dout_ld,
+                                                                     const uint8_t* __restrict__ mask, float keep, uint64_t seed,
+                                                                     float* __restrict__ din, int C4, long total) {
+  const bool drop = keep < 1.f;
+  const float inv_keep = drop ? 1.f / keep : 1.f;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int cg = (int)(i % C4);
+    const long s = i / C4;
+    const float* src = dout + 2 * s * dout_ld + 4 * cg;
+    f32x4 g0 = *reinterpret_cast<const f32x4*>(src), g1 = *reinterpret_cast<const f32x4*>(src + dout_ld);
+    if (drop) {
+      const long elem = (2 * s * C4 + cg) * 4;
+      g0 *= up1d_factor(mask, seed, keep, inv_keep, elem);
+      g1 *= up1d_factor(mask, seed, keep, inv_keep, elem + 4L * C4);
+    }
+    reinterpret_cast<f32x4*>(din)[i] = g0 + g1;
   }
 }
 
 extern "C" int dc_upsample1d_2x_fwd(const float* in, float* out, long out_ld, int N, int T, int C, dc_stream_t stream) {
   DC_REQUIRE(in && out, DC_EINVAL, "dc_upsample1d_2x_fwd: null pointer");
   DC_REQUIRE(dc_aligned16(in) && dc_aligned16(out), DC_EINVAL, "dc_upsample1d_2x_fwd: pointers must be 16-byte aligned");
-  DC_REQUIRE(N >= 1 && T >= 1, DC_EINVAL, "dc_upsample1d_2x_fwd: N=%d and T=%d must be >= 1", N, T);
-  DC_REQUIRE(C >= 4 && C % 4 == 0, DC_EINVAL, "dc_upsample1d_2x_fwd: C=%d must be a positive multiple of 4", C);
-  DC_REQUIRE(out_ld >= C && out_ld % 4 == 0, DC_EINVAL, "dc_upsample1d_2x_fwd: out_ld=%ld must be a multiple of 4 and >= C=%d", out_ld, C);
+  if (int rc = spikes_check_shape("dc_upsample1d_2x_fwd", N, T, "C", C, "out_ld", out_ld)) return rc;
   const long total = (long)N * T * (C / 4);
-  hipLaunchKernelGGL(upsample1d_2x_kernel, dim3(spikes_blocks(total)), dim3(256), 0, (hipStream_t)stream, in, out, out_ld, C / 4,
-                     total);
+  hipLaunchKernelGGL(upsample1d_2x_drop_fwd_kernel, dim3(spikes_blocks(total)), dim3(256), 0, (hipStream_t)stream, in, out, out_ld,
+                     (const uint8_t*)nullptr, 1.f, (uint64_t)0, C / 4, total);
   DC_CHECK_LAUNCH("dc_upsample1d_2x_fwd");
   return DC_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The head (:139-145) in one kernel: logits l[t][j] = bh[j] + sum_c a[t][c] kh[c][j] (fmaf chain in channel order), then
-// MaxPooling1D(pool, strides=1, 'same') per logit channel, then softmax over the two pooled logits, channel -1:
-//   m[t][j] = max l[max(0, t - (pool-1)/2) ... min(T-1, t + pool/2)][j]      TF 'SAME': the SMALLER pad is on the left, and
-//   p[t]    = 1 / (1 + exp(m[t][0] - m[t][1]))                               padding never wins the max (the window is clipped)
-// A workgroup owns HEAD_TT output samples of one trace and computes the logits of those plus the window's reach on either
-// side into LDS (at most HEAD_TT + 63 <= 256 samples: one per thread); the window never leaves the trace.
-#define HEAD_TT 192
-#define HEAD_MAX_POOL 64
-
-__global__ __launch_bounds__(256) void spike_head_kernel(const float* __restrict__ a, const float* __restrict__ kh,
-                                                         const float* __restrict__ bh, int pool, float* __restrict__ p, int T,
-                                                         int C, int tilesT) {
-  __shared__ float l0[256], l1[256];
-  const int trace = blockIdx.x / tilesT;
-  const int t0 = (blockIdx.x - trace * tilesT) * HEAD_TT;
-  const int left = (pool - 1) / 2, right = pool / 2;
-  const int tid = threadIdx.x;
-  const int u = t0 - left + tid;                 // the sample whose logits this thread forms
-  if (tid < HEAD_TT + left + right && u >= 0 && u < T) {
-    const f32x4* row = reinterpret_cast<const f32x4*>(a + ((long)trace * T + u) * C);
-    float s0 = bh[0], s1 = bh[1];
-    for (int cg = 0; cg < (C >> 2); ++cg) {
-      const f32x4 v = row[cg];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        s0 = __builtin_fmaf(v[e], kh[(4 * cg + e) * 2 + 0], s0);
-        s1 = __builtin_fmaf(v[e], kh[(4 * cg + e) * 2 + 1], s1);
-      }
-    }
-    l0[tid] = s0;
-    l1[tid] = s1;
-  }
-  __syncthreads();
-  const int t = t0 + tid;
-  if (tid < HEAD_TT && t < T) {
-    const int lo = max(0, t - left), hi = min(T - 1, t + right);
-    float m0 = l0[lo - (t0 - left)], m1 = l1[lo - (t0 - left)];
-    for (int v = lo + 1; v <= hi; ++v) {
-      m0 = fmaxf(m0, l0[v - (t0 - left)]);
-      m1 = fmaxf(m1, l1[v - (t0 - left)]);
-    }
-    p[(long)trace * T + t] = 1.f / (1.f + expf(m0 - m1));
-  }
+static int up1d_check(const char* fn, const void* a, const void* b, const void* mask, long ld, float keep, int N, int T, int C) {
+  DC_REQUIRE(a && b, DC_EINVAL, "%s: null pointer", fn);
+  DC_REQUIRE(dc_aligned16(a) && dc_aligned16(b) && (((uintptr_t)mask) & 3) == 0, DC_EINVAL,
+             "%s: tensors must be 16-byte aligned, the mask 4-byte aligned", fn);
+  if (int rc = spikes_check_shape(fn, N, T, "C", C, "ld", ld)) return rc;
+  DC_REQUIRE(keep > 0.f, DC_EINVAL, "%s: keep=%g must be > 0", fn, (double)keep);
+  return DC_OK;
 }
 
+extern "C" int dc_upsample1d_2x_drop_fwd(const float* in, float* out, long out_ld, const uint8_t* mask, float keep, uint64_t seed,
+                                         int N, int T, int C, dc_stream_t stream) {
+  if (int rc = up1d_check("dc_upsample1d_2x_drop_fwd", in, out, mask, out_ld, keep, N, T, C)) return rc;
+  const long total = (long)N * T * (C / 4);
+  hipLaunchKernelGGL(upsample1d_2x_drop_fwd_kernel, dim3(spikes_blocks(total)), dim3(256), 0, (hipStream_t)stream, in, out, out_ld,
+                     mask, keep, seed, C / 4, total);
+  DC_CHECK_LAUNCH("dc_upsample1d_2x_drop_fwd");
+  return DC_OK;
+}
+
+extern "C" int dc_upsample1d_2x_drop_bwd(const float* dout, long dout_ld, const uint8_t* mask, float keep, uint64_t seed,
+                                         float* din, int N, int T, int C, dc_stream_t stream) {
+  if (int rc = up1d_check("dc_upsample1d_2x_drop_bwd", dout, din, mask, dout_ld, keep, N, T, C)) return rc;
+  const long total = (long)N * T * (C / 4);
+  hipLaunchKernelGGL(upsample1d_2x_drop_bwd_kernel, dim3(spikes_blocks(total)), dim3(256), 0, (hipStream_t)stream, dout, dout_ld,
+                     mask, keep, seed, din, C / 4, total);
+  DC_CHECK_LAUNCH("dc_upsample1d_2x_drop_bwd");
+  return DC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The head (:139-145) in one kernel, spike_head_fwd_kernel<false> of spikes_common.h: logits, 'SAME' window maximum, p.
 extern "C" int dc_spike_head_fwd(const float* a, const float* kh, const float* bh, int pool, float* p, int N, int T, int C,
                                  dc_stream_t stream) {
   DC_REQUIRE(a && kh && bh && p, DC_EINVAL, "dc_spike_head_fwd: null pointer");
   DC_REQUIRE(dc_aligned16(a), DC_EINVAL, "dc_spike_head_fwd: a must be 16-byte aligned");
-  DC_REQUIRE(N >= 1 && T >= 1, DC_EINVAL, "dc_spike_head_fwd: N=%d and T=%d must be >= 1", N, T);
-  DC_REQUIRE(C >= 4 && C % 4 == 0, DC_EINVAL, "dc_spike_head_fwd: C=%d must be a positive multiple of 4", C);
+  if (int rc = spikes_check_shape("dc_spike_head_fwd", N, T, "C", C)) return rc;
   DC_REQUIRE(pool >= 1 && pool <= HEAD_MAX_POOL, DC_EINVAL, "dc_spike_head_fwd: pool=%d must be in 1..%d", pool, HEAD_MAX_POOL);
   const int tilesT = dc_cdiv(T, HEAD_TT);
   const long grid = (long)N * tilesT;
   DC_REQUIRE(grid < (1L << 31), DC_EUNSUP, "dc_spike_head_fwd: %ld workgroups", grid);
-  hipLaunchKernelGGL(spike_head_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, kh, bh, pool, p, T, C, tilesT);
+  hipLaunchKernelGGL(spike_head_fwd_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, kh, bh, pool,
+                     (const uint8_t*)nullptr, 0.f, 0.f, p, (float*)nullptr, T, C, tilesT);
   DC_CHECK_LAUNCH("dc_spike_head_fwd");
   return DC_OK;
 }

@@ -73,7 +73,8 @@ CONV_SHAPES = [(1, 1, 4, 4),           # all halo
                (2, 3, 8, 4),           # T shorter than the kernel
                (3, 37, 12, 36),        # ragged time tile, ragged column block, Cin = 3C
                (2, 130, 32, 32),       # one sample past a tile (and then two: 128 + 2)
-               (2, 70, 768, 256)]      # the widest K of the real network: 48 chunks
+               (2, 70, 768, 256),      # the widest K of the real network: 48 chunks
+               (1, 260, 8, 72)]        # three time tiles (the last ragged), two column blocks (the second ragged), Cin below one chunk
 
 
 @pytest.mark.parametrize('relu', [0, 1])

@@ -124,8 +124,9 @@ def _run_wgrad(dclib, x, dz, fill):
 
 
 # (3,5,4,4): three traces shorter than the halo -- a read across a trace boundary shows; (6,200,4,4): more than one contraction
-# partition; (2,70,96,32): more than one input-channel chunk
-@pytest.mark.parametrize('shape', GRAD_SHAPES + [(3, 5, 4, 4), (6, 200, 4, 4), (2, 70, 96, 32)], ids=lambda s: 'x'.join(map(str, s)))
+# partition; (2,70,96,32): more than one input-channel chunk; (2,70,36,68): both channel counts past 32 (the 2 x 2 wave arrangement),
+# ragged on both channel blocks, two tiles per trace
+@pytest.mark.parametrize('shape', GRAD_SHAPES + [(3, 5, 4, 4), (6, 200, 4, 4), (2, 70, 96, 32), (2, 70, 36, 68)], ids=lambda s: 'x'.join(map(str, s)))
 def test_conv1d_k5_wgrad(dclib, shape):
     N, T, Cin, Cout = shape
     x, k, dz, _, dw_want = _conv_case(shape)
