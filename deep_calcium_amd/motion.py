@@ -1,0 +1,260 @@
+"""Rigid motion correction on the device: the frames of a recording (T,H,W) of 16-bit frames are registered to a template.
+
+Every other stage of the pipeline (series.py, UNet2DSummary.predict, traces.py, spikes.py) assumes registered frames.  Here every
+frame is compared with a template at every whole-pixel shift within +-max_shift (dc_motion_ssd: the exact integer sum of
+squared differences over the template's interior), the best shift is picked (dc_motion_pick) and the frame is moved
+(dc_motion_apply) -- include/dcunet.h:
+
+    what          dtype            exactness
+    scores        int64            exact: (t, 2S+1, 2S+1) sums of squared differences, dy the slow axis, index dy + S
+    shifts        int32 (t, 2)     exact: argmin of (score, dy^2 + dx^2, dy, dx) -- ties go to the smallest displacement
+    corrected     the frames'      exact: out[y, x] = frame[y + dy, x + dx], `fill` outside the frame
+
+Sign convention: a shift (dy, dx) means out[y, x] = frame[y + dy, x + dx]; a frame cut from a scene at offset (+a, +b) relative
+to the template is found as (dy, dx) = (-a, -b).
+
+    mc = MotionCorrector((H, W), T, np.int16, template, max_shift=8)
+    for chunk in chunks: corrected = mc.feed(chunk)        # an int16 CUDA tensor: SeriesSummarizer / RoiTraceExtractor take it
+    shifts, rect = mc.shifts(), mc.valid()
+
+    shifts, template = estimate_shifts_device('dataset.hdf5')                 # one pass over the recording
+    img = summarize_series_device('dataset.hdf5', kind='corr', shifts=shifts)  # corrected on the way in, no second copy
+    traces = extract_traces_device('dataset.hdf5', mask, shifts=shifts)
+
+Scope: rigid, whole-pixel translation found by exhaustive search, max_shift <= 16.  Sub-pixel, piecewise and non-rigid
+registration, FFT methods and larger search radii are not implemented.
+
+Importing this module needs neither torch nor the GPU; constructing a MotionCorrector does (there is no CPU fallback).
+"""
+import numpy as np
+
+from .series import _CHUNK_BYTES, _TwoSlotStage, _check_device_frames, _frame_dtype, _open_series
+from .traces import _check_shape
+
+MAX_SHIFT = 16                        # DC_MOTION_MAX_SHIFT
+
+
+def _check_max_shift(max_shift, shape=None):
+    if isinstance(max_shift, bool) or not isinstance(max_shift, (int, np.integer)):
+        raise ValueError('max_shift must be an integer in [0, %d], not %r' % (MAX_SHIFT, max_shift))
+    S = int(max_shift)
+    if not 0 <= S <= MAX_SHIFT:
+        raise ValueError('max_shift must be in [0, %d], not %d' % (MAX_SHIFT, S))
+    if shape is not None and (shape[0] <= 2 * S or shape[1] <= 2 * S):
+        raise ValueError('max_shift = %d leaves no interior in a %d x %d frame: H > 2 * max_shift and W > 2 * max_shift'
+                         % (S, shape[0], shape[1]))
+    return S
+
+
+def _check_fill(fill):
+    if isinstance(fill, bool) or not isinstance(fill, (int, np.integer)) or not -32768 <= int(fill) <= 65535:
+        raise ValueError('fill must be a 16-bit integer value, not %r' % (fill,))
+    return int(fill)
+
+
+def _check_template(template, shape, dtype):
+    if not isinstance(template, np.ndarray):
+        raise ValueError('template must be a numpy array, not %s' % type(template).__name__)
+    if tuple(template.shape) != tuple(shape):
+        raise ValueError('template is %r, the frames are %r' % (tuple(template.shape), tuple(shape)))
+    if template.dtype != dtype:
+        raise ValueError('template is %s, the recording was declared %s' % (template.dtype, dtype))
+    return np.ascontiguousarray(template)
+
+
+def valid_rectangle(shifts, shape):
+    """((y0, y1), (x0, x1)): the rectangle every frame corrected by `shifts` (n, 2) covers with its own pixels,
+    y in [max(0, -min dy), H - max(0, max dy)), likewise x.  Host only."""
+    H, W = shape
+    s = np.asarray(shifts).reshape(-1, 2).astype(np.int64)
+    if len(s) == 0:
+        return (0, H), (0, W)
+    return ((max(0, -int(s[:, 0].min())), H - max(0, int(s[:, 0].max()))),
+            (max(0, -int(s[:, 1].min())), W - max(0, int(s[:, 1].max()))))
+
+
+class MotionCorrector(object):
+    """Owns the device state of one recording's registration; feed() the frames in order, in chunks of any size."""
+
+    def __init__(self, shape, n_frames, dtype, template, max_shift=8, fill=0, device=None, chunk_frames=None):
+        # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
+        shape = _check_shape(shape)
+        H, W = shape
+        n_frames = int(n_frames)
+        if n_frames < 1:
+            raise ValueError('n_frames must be >= 1, not %d' % n_frames)
+        self.dtype = _frame_dtype(dtype)
+        self.max_shift = _check_max_shift(max_shift, shape)
+        self.fill = _check_fill(fill)
+        template = _check_template(template, shape, self.dtype)
+        if chunk_frames is None:
+            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 1:
+            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
+        self.shape, self.n_frames = shape, n_frames
+        self.chunk_frames = min(chunk_frames, n_frames)
+        self.fed = 0
+        self._stage = None
+        self._last = 0
+
+        import torch
+        from . import net
+        from ._lib import lib
+        self._torch, self._net = torch, net
+        self.L = lib()
+        if not torch.cuda.is_available():
+            from ._lib import DcunetError
+            raise DcunetError('MotionCorrector needs a GPU (there is no CPU fallback)')
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        dev, nd = self.device, 2 * self.max_shift + 1
+        self.template = template
+        self._tmpl = torch.from_numpy(template.view(np.int16)).to(dev)
+        self._shifts = torch.zeros((n_frames, 2), dtype=torch.int32, device=dev)
+        self._scores = torch.empty((self.chunk_frames, nd, nd), dtype=torch.int64, device=dev)      # fully written by every chunk
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device)
+
+    def _register(self, fp, tc, out, st):
+        """The launches of one piece of at most chunk_frames frames at fp; out: where the corrected frames go, or None."""
+        H, W = self.shape
+        L, S = self.L, self.max_shift
+        rows = self._shifts.data_ptr() + 8 * self.fed
+        L.dc_motion_ssd(fp, int(self.dtype == np.dtype(np.uint16)), tc, self._tmpl.data_ptr(), H, W, S, self._scores.data_ptr(), st)
+        L.dc_motion_pick(self._scores.data_ptr(), tc, S, rows, None, st)
+        if out is not None:
+            L.dc_motion_apply(fp, tc, rows, H, W, self.fill, out, st)
+        self.fed += tc
+        self._last = tc
+
+    def feed(self, frames, correct=True):
+        """The next frames of the recording, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype (staged
+        through two pinned slots), or a contiguous (t, H, W) torch.int16 tensor on the corrector's device holding the
+        recording's bits (read in place).  Returns the corrected frames as a (t, H, W) torch.int16 tensor on the device (the
+        frames' bits); their shifts land in rows [fed, fed + t) of shifts_device().  correct=False only estimates the shifts
+        and returns None."""
+        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
+        if not on_device and not isinstance(frames, np.ndarray):
+            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
+        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
+            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
+        if on_device:
+            _check_device_frames(self._torch, frames, self.dtype, self.device, 'corrector')
+        elif frames.dtype != self.dtype:
+            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
+        t = int(frames.shape[0])
+        if t < 1 or self.fed + t > self.n_frames:
+            raise ValueError('%d frames after %d fed: the recording was declared to have %d' % (t, self.fed, self.n_frames))
+        torch = self._torch
+        H, W = self.shape
+        with torch.cuda.device(self.device):
+            main = self._stream()
+            st = main.cuda_stream
+            out = torch.empty((t, H, W), dtype=torch.int16, device=self.device) if correct else None
+            done = [0]
+
+            def piece(fp, tc):
+                self._register(fp, tc, out.data_ptr() + 2 * done[0] * H * W if correct else None, st)
+                done[0] += tc
+            if on_device:
+                for a in range(0, t, self.chunk_frames):
+                    piece(frames.data_ptr() + 2 * a * H * W, min(self.chunk_frames, t - a))
+                frames.record_stream(main)
+            else:
+                if self._stage is None:          # names of its own: a summarizer or extractor alive at the same time keeps its slots
+                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'motion_stage', (self.chunk_frames, H, W))
+                self._stage.run(frames, main, piece)
+        return out
+
+    def shifts_device(self):
+        """The int32 (n_frames, 2) tensor of (dy, dx) rows on the device; rows [0, fed) are set."""
+        return self._shifts
+
+    def shifts(self):
+        """(fed, 2) int32 numpy array of the (dy, dx) found so far."""
+        return self._shifts[:self.fed].cpu().numpy()
+
+    def last_scores(self):
+        """(t, 2S+1, 2S+1) int64 numpy array: the scores of the last piece of at most chunk_frames frames that was registered
+        (dy the slow axis, index dy + S) -- score minus the frame's minimum is a confidence measure."""
+        return self._scores[:self._last].cpu().numpy()
+
+    def valid(self):
+        """((y0, y1), (x0, x1)): the rectangle every frame corrected so far covers with its own pixels."""
+        return valid_rectangle(self.shifts(), self.shape)
+
+
+def _rounded_mean(torch, total, n):
+    """floor((2 * sum + n) / (2 * n)) of an int64 tensor: the mean rounded half up, exact."""
+    return torch.div(2 * total + n, 2 * n, rounding_mode='floor')
+
+
+def _widen(torch, chunk, unsigned):
+    v = chunk.to(torch.int64)
+    return v & 0xffff if unsigned else v
+
+
+def make_template(frames, max_shift=8, iterations=1, device=None):
+    """A template for `frames` (N, H, W) numpy int16 / uint16: the rounded mean floor((2 * sum + N) / (2 N)) of the frames, then
+    `iterations` times: register the frames to the template (fill 0) and take the rounded mean of the corrected frames.
+    Returns (H, W) of the frames' dtype."""
+    if not isinstance(frames, np.ndarray) or frames.ndim != 3 or frames.shape[0] < 1:
+        raise ValueError('frames must be a (N, H, W) numpy array with N >= 1, not %s' %
+                         (type(frames).__name__ if not isinstance(frames, np.ndarray) else repr(tuple(frames.shape))))
+    dtype = _frame_dtype(frames.dtype)
+    shape = _check_shape(frames.shape[1:])
+    S = _check_max_shift(max_shift, shape)
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise ValueError('iterations must be an integer >= 0, not %r' % (iterations,))
+    import torch
+    if not torch.cuda.is_available():
+        from ._lib import DcunetError
+        raise DcunetError('make_template needs a GPU (there is no CPU fallback)')
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    N, (H, W) = int(frames.shape[0]), shape
+    uns = dtype == np.dtype(np.uint16)
+    step = max(1, _CHUNK_BYTES // (2 * H * W))
+    with torch.cuda.device(dev):
+        total = torch.zeros((H, W), dtype=torch.int64, device=dev)
+        for a in range(0, N, step):
+            chunk = torch.from_numpy(np.array(frames[a:a + step]).view(np.int16)).to(dev)      # a copy: a file mapping is read-only
+            total += _widen(torch, chunk, uns).sum(0)
+        tmpl = _rounded_mean(torch, total, N).to(torch.int16).cpu().numpy().view(dtype)
+        for _ in range(int(iterations)):
+            mc = MotionCorrector(shape, N, dtype, tmpl, max_shift=S, fill=0, device=dev, chunk_frames=step)
+            total.zero_()
+            for a in range(0, N, step):
+                total += _widen(torch, mc.feed(np.ascontiguousarray(frames[a:a + step])), uns).sum(0)
+            tmpl = _rounded_mean(torch, total, N).to(torch.int16).cpu().numpy().view(dtype)
+    return tmpl
+
+
+def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=200, source='series/raw', device=None,
+                           chunk_frames=None):
+    """(shifts, template): the (T, 2) int32 (dy, dx) of every frame of `source` of a dataset file against `template` -- built
+    by make_template (one iteration) from the first min(T, template_frames) frames when none is given.  The recording is
+    streamed once, memory-mapped or sliced, never read whole; nothing is corrected here: pass `shifts` to
+    summarize_series_device / extract_traces_device."""
+    _check_max_shift(max_shift)
+    if isinstance(template_frames, bool) or not isinstance(template_frames, (int, np.integer)) or template_frames < 1:
+        raise ValueError('template_frames must be an integer >= 1, not %r' % (template_frames,))
+    frames, close = _open_series(dspath, source)
+    try:
+        if len(frames.shape) != 3:
+            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
+        T = int(frames.shape[0])
+        shape = tuple(int(v) for v in frames.shape[1:])
+        S = _check_max_shift(max_shift, shape)
+        if template is None:
+            template = make_template(np.asarray(frames[:min(T, int(template_frames))]), max_shift=S, iterations=1, device=device)
+        mc = MotionCorrector(shape, T, frames.dtype, template, max_shift=S, device=device, chunk_frames=chunk_frames)
+        for a in range(0, T, mc.chunk_frames):
+            mc.feed(np.asarray(frames[a:a + mc.chunk_frames]), correct=False)
+        out = mc.shifts()
+    finally:
+        frames = None                        # a view of the file mapping: released before the file is closed
+        close()
+    return out, template

@@ -44,6 +44,56 @@ def _frame_dtype(dtype):
     return dt
 
 
+def _check_shifts(shifts, n_frames):
+    """The `shifts=` keyword of SeriesSummarizer / RoiTraceExtractor: None, an (n_frames, 2) integer numpy array of (dy, dx) rows
+    (-> contiguous int32) or an (n_frames, 2) integer tensor (checked, returned as it is).  Host only."""
+    if shifts is None:
+        return None
+    if not isinstance(shifts, np.ndarray) and hasattr(shifts, 'is_cuda') and hasattr(shifts, 'data_ptr'):
+        if tuple(shifts.shape) != (n_frames, 2) or shifts.dtype.is_floating_point or shifts.dtype.is_complex:
+            raise ValueError('shifts must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), not %s %r'
+                             % (n_frames, shifts.dtype, tuple(shifts.shape)))
+        return shifts
+    a = np.asarray(shifts)
+    if a.ndim != 2 or a.shape != (n_frames, 2) or a.dtype.kind not in 'iu':
+        raise ValueError('shifts must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), not %s %r'
+                         % (n_frames, a.dtype, tuple(a.shape)))
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError('shifts must fit int32')
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def _check_device_frames(torch, frames, dtype, device, owner):
+    """A feed() argument that is a tensor: the recording's bits as a contiguous torch.int16 tensor on `device`."""
+    if frames.dtype != torch.int16:
+        raise ValueError('a device tensor must be torch.int16 (the bits of the %s frames), not %s' % (dtype, frames.dtype))
+    if not frames.is_cuda or frames.device != device:
+        raise ValueError('the tensor is on %s, the %s on %s' % (frames.device, owner, device))
+    if not frames.is_contiguous():
+        raise ValueError('a device tensor must be contiguous')
+
+
+class _ShiftedChunks(object):
+    """Known shifts applied on the way in (dc_motion_apply, fill 0): the int32 (n_frames, 2) table on the device and one scratch
+    chunk the accumulate kernels read instead of the staged frames.  Frame `fed + i` of the recording gets row `fed + i`."""
+
+    def __init__(self, torch, L, device, shifts, shape):
+        self._L, self.shape = L, shape
+        if isinstance(shifts, np.ndarray):
+            shifts = torch.from_numpy(shifts)
+        self.shifts = shifts.to(device=device, dtype=torch.int32).contiguous()
+        self.scratch = torch.empty(shape, dtype=torch.int16, device=device)
+
+    def run(self, fp, tc, fed, st, launch):
+        """launch(pointer to corrected frames, count, first frame) for the tc frames at fp, a scratch chunk at a time."""
+        C, H, W = self.shape
+        for a in range(0, tc, C):
+            n = min(C, tc - a)
+            self._L.dc_motion_apply(fp + 2 * a * H * W, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
+                                    self.scratch.data_ptr(), st)
+            launch(self.scratch.data_ptr(), n, fed + a)
+
+
 class _TwoSlotStage(object):
     """Two pinned host slots and two device slots of `shape` = (C, H, W) int16: the H2D copy of chunk k + 1 (copy stream) runs
     beside the kernels on chunk k (the caller's stream); events hand the slots back and forth.  The pinned slots are cached by
@@ -87,7 +137,9 @@ class _TwoSlotStage(object):
 class SeriesSummarizer(object):
     """Owns the device state of one recording's summaries; feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS):
+    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None):
+        """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
+        MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before it is summarised."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         try:
             shape = tuple(int(v) for v in shape)
@@ -110,6 +162,7 @@ class SeriesSummarizer(object):
         chunk_frames = int(chunk_frames)
         if chunk_frames < 1:
             raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
+        shifts = _check_shifts(shifts, n_frames)
         self.shape, self.n_frames, self.kinds = shape, n_frames, kinds
         self.chunk_frames = min(chunk_frames, n_frames)
         self.fed = 0
@@ -137,17 +190,23 @@ class SeriesSummarizer(object):
         self.max16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None
         self.xy = torch.empty((4, n), dtype=torch.int64, device=dev) if self._xy else None
         self._stage = _TwoSlotStage(torch, net, dev, 'series_stage', (self.chunk_frames, H, W))
+        self._shifted = None if shifts is None else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W))
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
 
     def feed(self, frames):
-        """The next frames of the recording: (t, H, W) numpy array or memmap of the recording's dtype, any t >= 1."""
-        if not isinstance(frames, np.ndarray):
-            raise ValueError('frames must be a numpy array (or memmap), not %s' % type(frames).__name__)
-        if frames.ndim != 3 or tuple(frames.shape[1:]) != self.shape:
+        """The next frames of the recording, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype, or a
+        contiguous (t, H, W) torch.int16 tensor on the summarizer's device holding the recording's bits (read in place, no
+        staging; the signedness is the declared dtype's) -- what MotionCorrector.feed() returns."""
+        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
+        if not on_device and not isinstance(frames, np.ndarray):
+            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
+        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
             raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
-        if frames.dtype != self.dtype:
+        if on_device:
+            _check_device_frames(self._torch, frames, self.dtype, self.device, 'summarizer')
+        elif frames.dtype != self.dtype:
             raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
         if frames.shape[0] < 1 or self.fed + frames.shape[0] > self.n_frames:
             raise ValueError('%d frames after %d fed: the recording was declared to have %d' %
@@ -159,15 +218,25 @@ class SeriesSummarizer(object):
             main = self._stream()
             st = main.cuda_stream
 
-            def reduce(fp, tc):
-                L.dc_series_accumulate(fp, uns, tc, self.fed, self.n_frames,
+            def accumulate(fp, tc, t0):
+                L.dc_series_accumulate(fp, uns, tc, t0, self.n_frames,
                                        self.mean16.data_ptr() if self._chain else None,
                                        self.max16.data_ptr() if self._chain else None,
                                        self.sum.data_ptr(), self.sumsq.data_ptr(), self.vmax.data_ptr(), H, W, st)
                 if self._xy:
-                    L.dc_series_accumulate_xy(fp, uns, tc, self.fed, self.xy.data_ptr(), H, W, st)
+                    L.dc_series_accumulate_xy(fp, uns, tc, t0, self.xy.data_ptr(), H, W, st)
+
+            def reduce(fp, tc):
+                if self._shifted is None:
+                    accumulate(fp, tc, self.fed)
+                else:
+                    self._shifted.run(fp, tc, self.fed, st, accumulate)
                 self.fed += tc
-            self._stage.run(frames, main, reduce)
+            if on_device:
+                reduce(frames.data_ptr(), int(frames.shape[0]))
+                frames.record_stream(main)
+            else:
+                self._stage.run(frames, main, reduce)
         self._images = None
         return self
 
@@ -265,9 +334,11 @@ def _open_series(dspath, source):
     return node, close                 # h5py: sliced chunk by chunk
 
 
-def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None):
+def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
+                            shifts=None):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
-    float32 summary (standardised like _summarize_series's by default)."""
+    float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame
+    (motion.estimate_shifts_device), applied on the device on the way in."""
     _check_kind(kind)
     frames, close = _open_series(dspath, source)
     try:
@@ -275,7 +346,7 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
-                                kinds=(kind,))
+                                kinds=(kind,), shifts=shifts)
         for a in range(0, T, summ.chunk_frames):
             summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
         out = summ.result(kind, standardize=standardize)

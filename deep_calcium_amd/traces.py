@@ -24,7 +24,8 @@ Importing this module needs neither torch nor the GPU; constructing a RoiTraceEx
 """
 import numpy as np
 
-from .series import _CHUNK_BYTES, _TwoSlotStage, _frame_dtype, _open_series
+from .series import (_CHUNK_BYTES, _ShiftedChunks, _TwoSlotStage, _check_device_frames, _check_shifts, _frame_dtype,
+                     _open_series)
 
 KINDS = ('sum', 'mean', 'zscore')
 # Longest CSR row handed to the kernel: a longer ROI is cut into rows of this many pixels, so that one whole-image ROI among
@@ -104,7 +105,9 @@ def rois_to_csr(rois, shape):
 class RoiTraceExtractor(object):
     """Owns the device state of one recording's ROI traces; feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None):
+    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None):
+        """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
+        MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before its ROIs are summed."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         H, W = shape
@@ -118,6 +121,7 @@ class RoiTraceExtractor(object):
         chunk_frames = int(chunk_frames)
         if chunk_frames < 1:
             raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
+        shifts = _check_shifts(shifts, n_frames)
         self.shape, self.n_frames, self.areas = shape, n_frames, areas
         self.n_rois = len(areas)
         self.chunk_frames = min(chunk_frames, n_frames)
@@ -143,15 +147,22 @@ class RoiTraceExtractor(object):
         self._rows = len(row_roi)
         # every chunk writes its own columns of every row, so the state is never cleared
         self.sums = torch.empty((self.n_rois, n_frames), dtype=torch.int64, device=dev)
+        self._shifted = None if shifts is None else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W))
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
 
     def _accumulate(self, fp, tc, st):
         H, W = self.shape
-        self.L.dc_roi_trace_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, self.fed, self._row_off.data_ptr(),
-                                       self._row_pix.data_ptr(), self._row_roi.data_ptr(), self._rows, self.n_rois,
-                                       self.sums.data_ptr(), self.n_frames, H, W, st)
+
+        def accumulate(fp, tc, t0):
+            self.L.dc_roi_trace_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, t0, self._row_off.data_ptr(),
+                                           self._row_pix.data_ptr(), self._row_roi.data_ptr(), self._rows, self.n_rois,
+                                           self.sums.data_ptr(), self.n_frames, H, W, st)
+        if self._shifted is None:
+            accumulate(fp, tc, self.fed)
+        else:
+            self._shifted.run(fp, tc, self.fed, st, accumulate)
         self.fed += tc
 
     def feed(self, frames):
@@ -165,13 +176,7 @@ class RoiTraceExtractor(object):
         if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
             raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
         if on_device:
-            torch = self._torch
-            if frames.dtype != torch.int16:
-                raise ValueError('a device tensor must be torch.int16 (the bits of the %s frames), not %s' % (self.dtype, frames.dtype))
-            if not frames.is_cuda or frames.device != self.device:
-                raise ValueError('the tensor is on %s, the extractor on %s' % (frames.device, self.device))
-            if not frames.is_contiguous():
-                raise ValueError('a device tensor must be contiguous')
+            _check_device_frames(self._torch, frames, self.dtype, self.device, 'extractor')
         elif frames.dtype != self.dtype:
             raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
         if frames.shape[0] < 1 or self.fed + frames.shape[0] > self.n_frames:
@@ -207,16 +212,18 @@ class RoiTraceExtractor(object):
         return out.cpu().numpy()
 
 
-def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device=None, chunk_frames=None):
+def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device=None, chunk_frames=None, shifts=None):
     """The (R,T) traces of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
-    recording is memory-mapped or sliced, never read whole."""
+    recording is memory-mapped or sliced, never read whole.  shifts: the (T, 2) (dy, dx) of every frame
+    (motion.estimate_shifts_device), applied on the device on the way in."""
     _check_kind(kind)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
-        ext = RoiTraceExtractor(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames)
+        ext = RoiTraceExtractor(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames,
+                                shifts=shifts)
         for a in range(0, T, ext.chunk_frames):
             ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
         out = ext.result(kind)

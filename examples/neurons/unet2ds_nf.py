@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -31,7 +31,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 
-from deep_calcium_amd import UNet2DSummary, parallel, extract_traces_device, write_traces_dataset      # noqa: E402
+from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
+                              estimate_shifts_device, summarize_series_device, valid_rectangle)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -102,20 +103,32 @@ def prediction(dataset_name, model_path, checkpoints_dir):
         nf_submit(Mp, names, '%s/submission_latest%s.json' % (model.cpdir, ('_TTA' if aug else '')))
 
 
-def traces(dataset_name, model_path, checkpoints_dir, kind='mean'):
+def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
-    model starts from such a file)."""
+    model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
+    within +-S); the summary the network segments is then the mean of the registered raw frames instead of the stored
+    `series/mean`, and the traces are summed over the registered frames."""
     logger = logging.getLogger('traces')
     dspaths = nf_find_hdf5(dataset_name)
-    model = UNet2DSummary(cpdir=checkpoints_dir)
+    shifts = {}
+    if register is not None:
+        for dspath in dspaths:
+            shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register)
+            logger.info('%s: registered within +-%d, largest |dy|, |dx| = %d, %d, valid rectangle %r' % (
+                dspath, register, np.abs(shifts[dspath][:, 0]).max(), np.abs(shifts[dspath][:, 1]).max(),
+                valid_rectangle(shifts[dspath], tmpl.shape)))
+        model = UNet2DSummary(cpdir=checkpoints_dir,
+                              series_summary_func=lambda p: summarize_series_device(p, kind='mean', shifts=shifts[p]))
+    else:
+        model = UNet2DSummary(cpdir=checkpoints_dir)
     Mp, names = model.predict(dspaths, model_path=model_path, window_shape=(512, 512), save=False, augmentation=True)
     for dspath, mp, name in zip(dspaths, Mp, names):
         mask = np.asarray(mp).round().astype(np.uint8)
         if not mask.any():
             logger.info('%s: no neurons predicted, no traces file.' % name)
             continue
-        tr = extract_traces_device(dspath, mask, kind=kind)
+        tr = extract_traces_device(dspath, mask, kind=kind, shifts=shifts.get(dspath))
         out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
         logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
@@ -147,6 +160,8 @@ if __name__ == '__main__':
     sp_trc.add_argument('-m', '--model_path', help='path to model', required=True)
     sp_trc.add_argument('-c', '--checkpoints_dir', help='checkpoint directory', default=CHECKPOINTS_DIR)
     sp_trc.add_argument('--kind', help='what a trace holds', default='mean', choices=('sum', 'mean', 'zscore'))
+    sp_trc.add_argument('--register', help='register the raw frames first, within +-S pixels (default 8)', nargs='?', const=8, default=None,
+                        type=int, metavar='S')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 111
+#define DC_ABI_VERSION 112
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -529,6 +529,33 @@ int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0
                             const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);
 int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,
                           dc_stream_t stream);
+
+/* ---- rigid motion correction: register the frames of a recording to a template ------------------------------------------------
+ * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
+ * examples/neurons/unet2ds_sj.py, were registered by an outside tool: it reads directories named ..._stabilized).  This is that
+ * step: rigid, whole-pixel translation, found by exhaustive search within +-S, S <= DC_MOTION_MAX_SHIFT.  Sub-pixel, piecewise
+ * and non-rigid registration and FFT methods are out of scope.  Integer arithmetic only: every result is exact, so the chunking
+ * of a recording never changes a bit.
+ * frames: as for dc_series_accumulate (int16 / uint16 by is_unsigned, [tc][H][W] contiguous, 2-byte aligned); tmpl: [H][W] of the
+ * same type.  H > 2S and W > 2S (else DC_EINVAL); S > 16 or H * W > 2^30: DC_EUNSUP (-3).
+ * SIGN CONVENTION: a shift (dy, dx) means out[y][x] = frame[y + dy][x + dx].  A frame cut from a scene at offset (+a, +b)
+ * relative to the template is therefore found as (dy, dx) = (-a, -b).
+ *   dc_motion_ssd: scores = int64[tc][2S+1][2S+1], dy the slow axis (index dy + S), fully written (never pre-clear):
+ *     scores[t][dy+S][dx+S] = sum over the template's interior y in [S, H-S), x in [S, W-S) of (tmpl[y][x] - frame[y+dy][x+dx])^2
+ *     -- every shift sums the same (H-2S)(W-2S) pixels and never reads outside the frame.  |d| <= 65535 and H * W <= 2^30, so a
+ *     score is below 2^62.  S = 0 is legal (one score per frame).
+ *   dc_motion_pick: shifts = int32[tc][2] (dy, dx), best = int64[tc] (nullable: the picked score).  The picked shift minimises
+ *     the tuple (score, dy^2 + dx^2, dy, dx) lexicographically: a constant frame, or a pattern periodic within the window, gets the
+ *     smallest displacement, and (0, 0) wins every tie it takes part in.
+ *   dc_motion_apply: out[t][y][x] = frames[t][y + dy][x + dx] where that lies inside the frame, `fill` (a 16-bit value, given
+ *     as an int in [-32768, 65535]) elsewhere; (dy, dx) = shifts[t] is read on the device.  A pure move of 16-bit values (the
+ *     signedness does not matter).  Any int32 shift works (not only those within the search radius); |dy| >= H or |dx| >= W gives
+ *     an all-fill frame.  out must not overlap frames (DC_EINVAL). */
+#define DC_MOTION_MAX_SHIFT 16
+int dc_motion_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, long* scores,
+                  dc_stream_t stream);
+int dc_motion_pick(const long* scores, int tc, int S, int* shifts, long* best, dc_stream_t stream);
+int dc_motion_apply(const void* frames, int tc, const int* shifts, int H, int W, int fill, void* out, dc_stream_t stream);
 
 /* ---- UNet1D spike inference: traces in, spike probabilities out ------------------------------------------------------------
  * The reference's second model family, UNet1DSegmentation: the network unet1d (unet_1d_segmentation.py:49-148) as its predict()

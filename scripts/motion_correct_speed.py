@@ -1,0 +1,151 @@
+"""Times of the motion-correction path on one GPU (the figures of DESIGN.md section 4f).
+
+    python scripts/motion_correct_speed.py [--frames 3000] [--hw 512] [--chunk 64] [--out FILE]
+
+A synthetic int16 recording -- a random scene cut at random offsets within +-5 pixels, plus noise -- is written as an .npz next to
+the output (np.savez: stored, so it is memory-mapped).  Timed, for max_shift S = 4, 8 and 16 and chunks of `--chunk` frames:
+ (a) the H2D copy of one chunk out of pinned memory;
+ (b) kernel time per chunk of dc_motion_ssd, dc_motion_pick and dc_motion_apply: HIP events on the launch stream around 5 launches
+     back to back, median of 5 such samples after a warm-up (min - max), and the ratio of each to the copy;
+ (c) wall time of estimate_shifts_device over the whole recording with a given template (median of 5 after a warm-up, page cache
+     warm), and whether the planted shifts came back;
+ (d) a numpy restatement of the same search on a few frames, scaled to a chunk.
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def median_of(fn, n=5, warm=1):
+    for _ in range(warm):
+        fn()
+    return float(np.median([fn() for _ in range(n)]))
+
+
+def numpy_scores(frames, tmpl, S):
+    T, H, W = frames.shape
+    t = tmpl[S:H - S, S:W - S].astype(np.int64)
+    f = frames.astype(np.int64)
+    out = np.zeros((T, 2 * S + 1, 2 * S + 1), np.int64)
+    for dy in range(-S, S + 1):
+        for dx in range(-S, S + 1):
+            d = t[None] - f[:, S + dy:H - S + dy, S + dx:W - S + dx]
+            out[:, dy + S, dx + S] = (d * d).sum(axis=(1, 2))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, default=3000)
+    ap.add_argument('--hw', type=int, default=512)
+    ap.add_argument('--chunk', type=int, default=64)
+    ap.add_argument('--host-frames', type=int, default=2, help='frames of the numpy search (the time is scaled to a chunk)')
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    import torch
+    from deep_calcium_amd import estimate_shifts_device
+    from deep_calcium_amd._lib import lib
+    L = lib()
+    T, H, W, C = args.frames, args.hw, args.hw, args.chunk
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say('motion correction, %d x %d x %d int16 (%.2f GB), chunks of %d frames, %s'
+        % (T, H, W, T * H * W * 2 / 1e9, C, torch.cuda.get_device_name(0)))
+    rs = np.random.RandomState(0)
+    M = 5
+    scene = rs.randint(100, 1200, size=(H + 2 * M, W + 2 * M)).astype(np.int16)
+    offs = rs.randint(-M, M + 1, size=(T, 2))
+    raw = np.empty((T, H, W), np.int16)
+    for t in range(T):
+        raw[t] = scene[M + offs[t, 0]:M + offs[t, 0] + H, M + offs[t, 1]:M + offs[t, 1] + W]
+    for t0 in range(0, T, 100):
+        raw[t0:t0 + 100] += rs.randint(-30, 30, size=raw[t0:t0 + 100].shape).astype(np.int16)
+    tmpl = scene[M:M + H, M:M + W].copy()
+    tmp = tempfile.mkdtemp()
+    path = os.path.join(tmp, 'rec.npz')
+    np.savez(path, series_raw=raw, name=np.array('synthetic'))
+
+    chunk_bytes = C * H * W * 2
+    host = torch.from_numpy(raw[:C].copy()).pin_memory()
+    dev = torch.empty((C, H, W), dtype=torch.int16, device='cuda')
+    out = torch.empty((C, H, W), dtype=torch.int16, device='cuda')
+    dt = torch.from_numpy(tmpl).cuda()
+    shifts = torch.zeros((C, 2), dtype=torch.int32, device='cuda')
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def timed(fn, reps=1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / reps
+
+    def sample(fn, reps=5):
+        timed(fn, reps)
+        s = [timed(fn, reps) for _ in range(5)]
+        return float(np.median(s)), min(s), max(s)
+
+    dev.copy_(host)
+    h2d, lo, hi = sample(lambda: dev.copy_(host, non_blocking=True))
+    say('(a) H2D copy of one chunk (pinned, %.1f MB)      %8.3f ms  (%.3f - %.3f)  %6.1f GB/s' % (chunk_bytes / 1e6, h2d, lo, hi, chunk_bytes / h2d / 1e6))
+    say('(b) per chunk, 5 back to back per sample, median of 5 samples after a warm-up (min - max), and the ratio to the copy:')
+    for S in (4, 8, 16):
+        nd = 2 * S + 1
+        scores = torch.empty((C, nd, nd), dtype=torch.int64, device='cuda')
+        madds = C * nd * nd * (H - 2 * S) * (W - 2 * S)
+        rows = [('dc_motion_ssd', lambda: L.dc_motion_ssd(dev.data_ptr(), 0, C, dt.data_ptr(), H, W, S, scores.data_ptr(), stream)),
+                ('dc_motion_pick', lambda: L.dc_motion_pick(scores.data_ptr(), C, S, shifts.data_ptr(), None, stream)),
+                ('dc_motion_apply', lambda: L.dc_motion_apply(dev.data_ptr(), C, shifts.data_ptr(), H, W, 0, out.data_ptr(), stream))]
+        total = 0.0
+        for name, fn in rows:
+            ms, lo, hi = sample(fn)
+            total += ms
+            extra = '  %6.2f T multiply-adds/s' % (madds / ms / 1e9) if name == 'dc_motion_ssd' else ''
+            say('  S = %2d  %-16s %8.3f ms  (%.3f - %.3f)  / H2D = %5.2f%s' % (S, name, ms, lo, hi, ms / h2d, extra))
+        say('  S = %2d  all three       %8.3f ms                     / H2D = %5.2f  (%s)'
+            % (S, total, total / h2d, 'hides under the copy' if total < h2d else 'does NOT hide under the copy'))
+        got = shifts.cpu().numpy()
+        say('  S = %2d  planted shifts of the chunk recovered: %s' % (S, bool((got == -offs[:C]).all()) if S >= M else 'n/a (S < 5)'))
+
+    say('(c) estimate_shifts_device(template given), wall, median of 5 after a warm-up:')
+    for S in (4, 8, 16):
+        res = []
+
+        def run():
+            t = time.perf_counter()
+            res[:] = [estimate_shifts_device(path, template=tmpl, max_shift=S, chunk_frames=C)[0]]
+            return time.perf_counter() - t
+        s = median_of(run)
+        say('  S = %2d  %8.3f s  (%.2f GB/s of recording, %.3f ms per chunk)%s'
+            % (S, s, T * H * W * 2 / s / 1e9, s * 1e3 / ((T + C - 1) // C),
+               '  planted shifts recovered: %s' % bool((res[0] == -offs).all()) if S >= M else ''))
+
+    say('(d) numpy, the same search on %d frames, scaled to a chunk of %d:' % (args.host_frames, C))
+    for S in (4, 8, 16):
+        def host():
+            t = time.perf_counter()
+            numpy_scores(raw[:args.host_frames], tmpl, S)
+            return (time.perf_counter() - t) * C / args.host_frames
+        say('  S = %2d  %8.1f ms per chunk' % (S, median_of(host, n=3, warm=0) * 1e3))
+    os.remove(path)
+    os.rmdir(tmp)
+    if args.out:
+        with open(args.out, 'w') as fp:
+            fp.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
