@@ -7,10 +7,14 @@ the multi-tile loops on a machine without a GPU (tests/test_tileplan.py) and cro
   pp_items         csrc/igemm_pp.hip pp_launch: (pixel tile, column block) items of the role-split kernel
   joint_items      csrc/bwd_joint.hip joint_grid: pixel tiles of the joint backward kernels
   c1_plan          csrc/conv_c1.hip c1_blocks + the grid-stride loop of the first-layer weight gradient
+  wgrad1d_plan     csrc/wgrad.hip  CONV1D_WGRAD_DISPATCH + WgradCfg + wgrad_plan (UNet1D; tests/test_spikes_multitile_gpu.py)
+  conv1d_fwd_grid  csrc/spikes.hip dc_conv1d_k5_fwd: one workgroup per (trace, time tile, column block)
+  quad_plan        csrc/spikes_common.h quad_blocks + the grid-stride loops of dc_conv1d_stats / dc_conv1d_k5_c1_wgrad
 """
 
 DC_WGRAD_CTAS = 256         # wgrad_f16x3.hip: one workgroup per CU, one round (a build constant, not the device's CU count)
 DC_WG_RW = 4                # pixel rows per 16-wide tile of the Cin, Cout > 32 instantiation
+DC_WGRAD1D_CTAS = 512       # wgrad.hip wgrad_plan: two workgroups per CU, one resident round (a build constant too)
 
 
 def cdiv(a, b):
@@ -127,6 +131,45 @@ def c1_plan(N, H, W, Cout):
     return blocks, cdiv(units, blocks * PPB)
 
 
+def wgrad1d_plan(N, T, Cin, Cout):
+    """UNet1D weight gradient (dc_conv1d_k5_wgrad) -> (inst, TW, CM, CN, tiles_per_trace, tiles_total, tiles_per_split, splits,
+    last_split_tiles).
+
+    A trace is an image of one row: a tile is TW samples of ONE trace (the last tile of a trace ragged when T % TW != 0), the
+    (m, n) block is (Cin, Cout) in blocks of CM x CN.  Workgroup `split` walks the tiles [split * tiles_per_split,
+    min(.., tiles_total)); tile t lies in trace t // tiles_per_trace and starts at sample (t % tiles_per_trace) * TW."""
+    if Cin > 32 and Cout > 32:
+        inst, TW, CM, CN = '64x64', 64, 64, 64
+    elif Cin > 32:
+        inst, TW, CM, CN = '64x32', 64, 64, 32
+    elif Cout > 32:
+        inst, TW, CM, CN = '32x64', 64, 32, 64
+    else:
+        inst, TW, CM, CN = '32x32', 128, 32, 32
+    per_trace = cdiv(T, TW)
+    tiles_total = N * per_trace
+    blocks_mn = cdiv(Cin, CM) * cdiv(Cout, CN)
+    want = max(1, min(cdiv(DC_WGRAD1D_CTAS, blocks_mn), tiles_total))
+    tiles_per_split = cdiv(tiles_total, want)
+    splits = cdiv(tiles_total, tiles_per_split)
+    last = tiles_total - (splits - 1) * tiles_per_split
+    return inst, TW, CM, CN, per_trace, tiles_total, tiles_per_split, splits, last
+
+
+def conv1d_fwd_grid(N, T, Cout):
+    """Workgroups of dc_conv1d_k5_fwd: one per (trace, 128-sample time tile, 64-column block).  Up to 8 the kernel's
+    XCD-first map of blockIdx.x is the identity; a grid that is no multiple of 8 takes its remainder branch."""
+    return N * cdiv(T, 128) * cdiv(Cout, 64)
+
+
+def quad_plan(samples, C, per_lane, cap):
+    """The two 1-D vector reductions (dc_conv1d_stats: per_lane 16, cap 1024; dc_conv1d_k5_c1_wgrad: 32, 512) -> (blocks,
+    trips): a block holds PPB = 256 / (C / 4) sample lanes, a lane strides by blocks * PPB; past the cap trips > per_lane."""
+    PPB = 256 // (C // 4)
+    blocks = max(1, min(cap, cdiv(samples, PPB * per_lane)))
+    return blocks, cdiv(samples, blocks * PPB)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Case tables of tests/test_multitile_gpu.py.  Weight gradients: DC_WGRAD_CTAS is a build constant, so these are the same
 # on every device.  (kind, instantiation, N, H, W, Cin, Cout, tiles_per_split, last_split_tiles)
@@ -181,6 +224,51 @@ CONVT_WGRAD_CASES = [
 ]
 # first layer (Cin == 1): (N, H, W, Cout, trips of the grid-stride loop); W % 4 == 0 takes the 4-pixel kernel
 C1_WGRAD_CASES = [(2, 130, 132, 256, 2), (3, 61, 63, 256, 2)]
+
+# Case table of tests/test_spikes_multitile_gpu.py: the UNet1D weight gradient at several tiles per workgroup.
+# (instantiation, N, T, Cin, Cout, tiles_per_split, last_split_tiles).  T = 5 rows: one ragged tile per trace, so every tile
+# range spans several traces.  The other rows: several tiles per trace, the last ragged, their count coprime to the tiles per
+# split -- ranges start and end in the middle of a trace.
+WGRAD1D_CASES = [
+    # 32 x 32 (Cin, Cout <= 32): 128 samples, ONE (m, n) block -> up to 512 splits, the four waves a 32-sample segment each
+    ('32x32', 513, 5, 32, 32, 2, 1),
+    ('32x32', 171, 330, 24, 28, 2, 1),
+    ('32x32', 103, 1300, 4, 12, 3, 2),
+    ('32x32', 683, 330, 4, 4, 5, 4),
+    # 64 x 32 (Cin > 32 >= Cout): 64 samples, two waves per channel block, a 32-sample segment each
+    ('64x32', 65, 5, 512, 32, 2, 1),
+    ('64x32', 13, 270, 512, 24, 2, 1),
+    ('64x32', 53, 270, 200, 24, 3, 1),
+    ('64x32', 257, 5, 512, 32, 5, 2),
+    # 32 x 64 (Cin <= 32 < Cout): 64 samples, as above with the roles swapped
+    ('32x64', 65, 5, 32, 512, 2, 1),
+    ('32x64', 13, 270, 24, 512, 2, 1),
+    ('32x64', 53, 270, 24, 200, 3, 1),
+    ('32x64', 257, 5, 32, 512, 5, 2),
+    # 64 x 64 (Cin, Cout > 32): 64 samples, one wave per 32 x 32 block and no cross-wave sum
+    ('64x64', 129, 5, 256, 256, 5, 4),
+    ('64x64', 3, 700, 256, 256, 2, 1),
+    ('64x64', 27, 270, 200, 96, 3, 3),
+    ('64x64', 7, 450, 768, 256, 6, 2),       # the widest contraction of the real network; last tile of a trace: 2 samples
+    ('64x64', 129, 270, 36, 40, 2, 1),       # ONE ragged (m, n) block: 323 splits, this instantiation's two-stage slab reduce
+]
+# the rows test_conv1d_k5_wgrad_multitile_probes runs: one per instantiation, several tiles per trace, a short last split, and
+# enough traces for the probed ones and their neighbours to be distinct
+WGRAD1D_PROBE_CASES = [WGRAD1D_CASES[i] for i in (1, 6, 10, 16)]
+
+# the shapes of tests/test_spikes_train_gpu.py's test_conv1d_k5_wgrad (GRAD_SHAPES plus its four extra ones; the GPU module
+# checks this copy against that file): ONE tile per workgroup at every one of them
+WGRAD1D_DIRECT_SHAPES = [(1, 16, 4, 4), (3, 37, 12, 4), (2, 70, 32, 96), (2, 1, 4, 8), (2, 2, 8, 4),
+                         (3, 5, 4, 4), (6, 200, 4, 4), (2, 70, 96, 32), (2, 70, 36, 68)]
+
+# dc_conv1d_k5_fwd on grids past 8 workgroups: ((N, T, Cin, Cout), grid).  The (7, 5, 12, 36) launch stays below 8, where the
+# XCD-first map is the identity, for contrast.
+CONV1D_FWD_CASES = [((3, 260, 36, 136), 27),        # remainder 3: ragged time tile, ragged column block
+                    ((5, 130, 8, 72), 20),          # remainder 4
+                    ((1, 1100, 4, 200), 36),        # remainder 4: one trace, 9 time tiles
+                    ((7, 5, 12, 36), 7),
+                    ((2, 70, 256, 768), 24),        # remainder 0: the data gradient of the widest layer
+                    ((4, 70, 256, 768), 48)]        # remainder 0, six full rounds of the 8 XCDs
 
 
 def persistent_family(k, cus, H, W, Ncols=None):
