@@ -4,6 +4,8 @@
 // only: a score is the exact int64 sum, so the chunking of a recording never changes a bit and numpy is an exact oracle.
 // Sign convention: out[y][x] = frame[y + dy][x + dx]; a frame cut from a scene at offset (+a, +b) relative to the template is found
 // as (dy, dx) = (-a, -b).
+// Piecewise-rigid on top of it: per block of a By x Bx grid the rigid shift plus a residual within +-D (dc_motion_block_ssd,
+// dc_motion_block_pick), blended into one whole-pixel shift per pixel (dc_motion_warp).
 #include "common.h"
 #include "motion_math.h"
 
@@ -42,7 +44,7 @@ __device__ __forceinline__ void ssd_rows(const uint16_t* __restrict__ ft, int st
   constexpr int NK = 2 * SMAX + 1, FW = kPix + 2 * SMAX;
 #pragma unroll
   for (int j = 0; j < R; ++j) {
-    if (j < nr) {                                        // wave-uniform
+    if (j < nr) {                                        // wave-uniform in motion_ssd_kernel; per 16 lanes in the block kernel
     const uint4* src = reinterpret_cast<const uint4*>(ft + (long)(row0 + j) * stride + kPix * lane);
     unsigned w[FW / 2];
 #pragma unroll
@@ -149,32 +151,62 @@ __global__ __launch_bounds__(kThreads) void motion_ssd_kernel(const uint16_t* __
   }
 }
 
-// One wave per frame: every lane scans the shifts lane, lane + 64, ... and the wave folds its 64 candidates; the order of
-// motion_math.h is total, so the result is the unique minimum whatever the order of the comparisons.
+// One wave per score table: every lane scans the candidates lane, lane + 64, ... and the wave folds its 64 partial minima; the
+// order of motion_math.h is total, so the result is the unique minimum whatever the order of the comparisons.  Every lane returns it.
+__device__ __forceinline__ DcShiftCand pick_wave(const int64_t* __restrict__ sc, int S, int lane) {
+  const int n = (2 * S + 1) * (2 * S + 1);
+  DcShiftCand b = dc_motion_cand(sc, S, lane < n ? lane : 0);
+  for (int i = lane + kWave; i < n; i += kWave) {
+    const DcShiftCand c = dc_motion_cand(sc, S, i);
+    if (dc_motion_before(c, b)) b = c;
+  }
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    DcShiftCand c;
+    c.score = (int64_t)__shfl_xor((unsigned long long)b.score, o, kWave);
+    c.dy = __shfl_xor(b.dy, o, kWave);
+    c.dx = __shfl_xor(b.dx, o, kWave);
+    if (dc_motion_before(c, b)) b = c;
+  }
+  return b;
+}
+
+// One wave per frame.
 __global__ __launch_bounds__(kWave) void motion_pick_kernel(const int64_t* __restrict__ scores, int tc, int S, int* __restrict__ shifts,
                                                            int64_t* __restrict__ best) {
   const int n = (2 * S + 1) * (2 * S + 1), lane = threadIdx.x;
   for (int f = blockIdx.x; f < tc; f += gridDim.x) {
-    const int64_t* sc = scores + (long)f * n;
-    DcShiftCand b = dc_motion_cand(sc, S, lane < n ? lane : 0);
-    for (int i = lane + kWave; i < n; i += kWave) {
-      const DcShiftCand c = dc_motion_cand(sc, S, i);
-      if (dc_motion_before(c, b)) b = c;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      DcShiftCand c;
-      c.score = (int64_t)__shfl_xor((unsigned long long)b.score, o, kWave);
-      c.dy = __shfl_xor(b.dy, o, kWave);
-      c.dx = __shfl_xor(b.dx, o, kWave);
-      if (dc_motion_before(c, b)) b = c;
-    }
+    const DcShiftCand b = pick_wave(scores + (long)f * n, S, lane);
     if (lane == 0) {
       shifts[2 * f] = b.dy;
       shifts[2 * f + 1] = b.dx;
       if (best) best[f] = b.score;
     }
   }
+}
+
+// 8 output values of one row that share a shift, o 16-byte aligned: one store of the 8 source values at (sy, sx .. sx + 7) of the
+// frame f, or of fill where all 8 lie outside it.  The source run starts at any 2-byte address: it is read as the 4 or 5 aligned
+// dwords that hold it and funnel-shifted.  false (nothing stored) where the run straddles the frame's edge.
+__device__ __forceinline__ bool move8(const uint16_t* __restrict__ f, long sy, long sx, int H, int W, unsigned fill2, uint16_t* __restrict__ o) {
+  uint4 v;
+  if (sy < 0 || sy >= H || sx + 8 <= 0 || sx >= W) {
+    v = make_uint4(fill2, fill2, fill2, fill2);
+  } else if (sx >= 0 && sx + 8 <= W) {
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(f + sy * W + sx);
+    const unsigned* p = reinterpret_cast<const unsigned*>(addr & ~(uintptr_t)3);
+    const unsigned w0 = p[0], w1 = p[1], w2 = p[2], w3 = p[3];
+    if (addr & 2) {
+      const unsigned w4 = p[4];
+      v = make_uint4((w0 >> 16) | (w1 << 16), (w1 >> 16) | (w2 << 16), (w2 >> 16) | (w3 << 16), (w3 >> 16) | (w4 << 16));
+    } else {
+      v = make_uint4(w0, w1, w2, w3);
+    }
+  } else {
+    return false;
+  }
+  *reinterpret_cast<uint4*>(o) = v;
+  return true;
 }
 
 // out[t][y][x] = frames[t][y + dy][x + dx] inside the frame, fill outside.  A thread moves 8 consecutive output values; the groups
@@ -198,26 +230,7 @@ __global__ __launch_bounds__(kThreads) void motion_apply_kernel(const uint16_t* 
       const int a = e0 < 0 ? 0 : e0, b = e0 + 8 < HW ? e0 + 8 : HW;
       int y = a / W, x = a - y * W;
       bool done = false;
-      if (wide && b - a == 8 && x + 8 <= W) {
-        const long sy = y + dy, sx = x + dx;
-        uint4 v;
-        if (sy < 0 || sy >= H || sx + 8 <= 0 || sx >= W) {
-          v = make_uint4(fill2, fill2, fill2, fill2);
-          done = true;
-        } else if (sx >= 0 && sx + 8 <= W) {
-          const uintptr_t addr = reinterpret_cast<uintptr_t>(f + sy * W + sx);
-          const unsigned* p = reinterpret_cast<const unsigned*>(addr & ~(uintptr_t)3);
-          const unsigned w0 = p[0], w1 = p[1], w2 = p[2], w3 = p[3];
-          if (addr & 2) {
-            const unsigned w4 = p[4];
-            v = make_uint4((w0 >> 16) | (w1 << 16), (w1 >> 16) | (w2 << 16), (w2 >> 16) | (w3 << 16), (w3 >> 16) | (w4 << 16));
-          } else {
-            v = make_uint4(w0, w1, w2, w3);
-          }
-          done = true;
-        }
-        if (done) *reinterpret_cast<uint4*>(o + a) = v;
-      }
+      if (wide && b - a == 8 && x + 8 <= W) done = move8(f, y + dy, x + dx, H, W, fill2, o + a);
       if (!done) {
         for (int e = a; e < b; ++e) {
           const long sy = y + dy, sx = x + dx;
@@ -227,6 +240,225 @@ __global__ __launch_bounds__(kThreads) void motion_apply_kernel(const uint16_t* 
       }
     }
   }
+}
+
+// ---- piecewise-rigid: block scores, block pick, warp (the definitions are in include/dcunet.h, the arithmetic in motion_math.h) ----
+const int kBlkLanesX = 16;                                     // lanes of a wave along x
+const int kBlkR = 4;                                           // rows a lane owns
+const int kBlkTileW = kBlkLanesX * kPix;                       // 128 columns of a block per sweep
+const int kBlkTileH = kWaves * (kWave / kBlkLanesX) * kBlkR;   // 64 rows of a block per strip
+
+__host__ __device__ inline int bssd_stride(int D) { return kBlkTileW + ((2 * D + 7) & ~7); }
+
+// One workgroup owns a whole (block, frame): it walks the block, clipped to the interior [M, H-M) x [M, W-M), in strips of 64 rows
+// and sweeps of 128 columns -- a wave is 16 lanes x 8 pixels wide and 4 lanes x 4 rows high, so a block 100 pixels wide keeps
+// 13 of 16 lanes busy.  Per tile the frame window around the RIGID shift (dy, dx) of the frame -- read here and clamped to
+// [-S, S], which is what keeps the window inside the frame: its first row is >= M + dy - D >= 0, its last <= H - M - 1 + dy + D
+// <= H - 1 -- is staged in LDS with its D-wide halo and scored by ssd_rows at every residual (ey, ex).  The (2D+1)^2 totals of
+// all tiles meet in LDS and leave with plain stores: every score is written, there is no global atomic and no zero launch.
+template <int DMAX>
+__global__ __launch_bounds__(kThreads) void motion_block_ssd_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
+                                                                   const uint16_t* __restrict__ tmpl, int H, int W, int S, int D, int By,
+                                                                   int Bx, const int* __restrict__ rigid,
+                                                                   unsigned long long* __restrict__ bscores) {
+  constexpr int NK = 2 * DMAX + 1, R = kBlkR;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nd = 2 * D + 1, M = S + D, stride = bssd_stride(D);
+  uint16_t* ft = reinterpret_cast<uint16_t*>(smem);
+  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + (size_t)(kBlkTileH + 2 * D) * stride * sizeof(uint16_t));
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const int cl = lane % kBlkLanesX, rg = wave * (kWave / kBlkLanesX) + lane / kBlkLanesX;
+  const int bi = blockIdx.x / Bx, bj = blockIdx.x % Bx;
+  const int ya = dc_block_edge(bi, H, By), yb = dc_block_edge(bi + 1, H, By);
+  const int xa = dc_block_edge(bj, W, Bx), xb = dc_block_edge(bj + 1, W, Bx);
+  const int y0 = ya > M ? ya : M, y1 = yb < H - M ? yb : H - M;
+  const int x0 = xa > M ? xa : M, x1 = xb < W - M ? xb : W - M;
+  for (int f = blockIdx.y; f < tc; f += gridDim.y) {
+    const int dy = dc_motion_clamp(rigid[2 * f], S), dx = dc_motion_clamp(rigid[2 * f + 1], S);
+    const uint16_t* fr = frames + (long)f * H * W;
+    __syncthreads();                                     // the previous frame's totals have been stored
+    for (int i = threadIdx.x; i < nd * nd; i += kThreads) sc[i] = 0;
+    for (int ty = y0; ty < y1; ty += kBlkTileH) {
+      for (int tx = x0; tx < x1; tx += kBlkTileW) {
+        const int th = y1 - ty < kBlkTileH ? y1 - ty : kBlkTileH, tw = x1 - tx < kBlkTileW ? x1 - tx : kBlkTileW;
+        const int left = tw - kPix * cl, down = th - rg * R;
+        const int np = left < 0 ? 0 : (left < kPix ? left : kPix);      // pixels of this lane
+        const int nr = down < 0 ? 0 : (down < R ? down : R);            // rows of this lane
+        const bool ragged = __ballot(np > 0 && np < kPix) != 0;
+        unsigned mk[kPix];
+#pragma unroll
+        for (int p = 0; p < kPix; ++p) mk[p] = p < np ? 0xffffffffu : 0u;
+        unsigned t2[R][kPix / 2];
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          const uint16_t* trow = tmpl + (long)(ty + rg * R + j) * W + tx + kPix * cl;
+#pragma unroll
+          for (int q = 0; q < kPix / 2; ++q) {
+            const unsigned lo = (j < nr && 2 * q < np) ? (trow[2 * q] ^ flip) : 0u;
+            const unsigned hi = (j < nr && 2 * q + 1 < np) ? (trow[2 * q + 1] ^ flip) : 0u;
+            t2[j][q] = lo | (hi << 16);
+          }
+        }
+        // the window of this tile: th + 2D rows, tw + 2D columns rounded up to the 16-byte pieces the lanes read; LDS (0, 0) is
+        // frame (ty + dy - D, tx + dx - D).  What is not staged is read by lanes without pixels only, or masked.
+        const int srows = th + 2 * D, scols = ((tw + 7) & ~7) + ((2 * D + 7) & ~7);
+        const int oy = ty + dy - D, ox = tx + dx - D;
+        __syncthreads();                                 // the readers of the previous tile are done
+        for (int r = wave; r < srows; r += kWaves) {
+          const int gy = oy + r;
+          for (int c = lane; c < scols; c += kWave) {
+            const int gx = ox + c;
+            ft[r * stride + c] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? (uint16_t)(fr[(long)gy * W + gx] ^ flip) : (uint16_t)0;
+          }
+        }
+        __syncthreads();
+        for (int m = 0; m < nd; ++m) {
+          unsigned long long acc[NK];
+#pragma unroll
+          for (int k = 0; k < NK; ++k) acc[k] = 0;
+          if (np > 0 && nr > 0) {
+            if (ragged) ssd_rows<DMAX, R, true>(ft, stride, D, nd, nr, rg * R + m, cl, t2, mk, acc);
+            else ssd_rows<DMAX, R, false>(ft, stride, D, nd, nr, rg * R + m, cl, t2, mk, acc);
+          }
+          unsigned long long mine = 0;
+#pragma unroll
+          for (int k = 0; k < NK; ++k) {
+            if (k < nd) {
+              const unsigned long long s = wave_sum64(acc[k]);
+              if (lane == k) mine = s;
+            }
+          }
+          if (lane < nd) atomicAdd(&sc[m * nd + lane], mine);
+        }
+      }
+    }
+    __syncthreads();
+    unsigned long long* dst = bscores + ((long)f * gridDim.x + blockIdx.x) * nd * nd;
+    for (int i = threadIdx.x; i < nd * nd; i += kThreads) dst[i] = sc[i];
+  }
+}
+
+// One wave per (frame, block): the residual (ey, ex) under the order of motion_math.h, added to the frame's clamped rigid shift.
+__global__ __launch_bounds__(kWave) void motion_block_pick_kernel(const int64_t* __restrict__ bscores, const int* __restrict__ rigid,
+                                                                 long items, int nblk, int S, int D, int* __restrict__ block_shifts,
+                                                                 int64_t* __restrict__ best) {
+  const int n = (2 * D + 1) * (2 * D + 1), lane = threadIdx.x;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const DcShiftCand b = pick_wave(bscores + it * n, D, lane);
+    if (lane == 0) {
+      const long f = it / nblk;
+      block_shifts[2 * it] = dc_motion_clamp(rigid[2 * f], S) + b.dy;
+      block_shifts[2 * it + 1] = dc_motion_clamp(rigid[2 * f + 1], S) + b.dx;
+      if (best) best[it] = b.score;
+    }
+  }
+}
+
+const int kWarpRows = 16;              // rows of one workgroup's tile
+const int kWarpCols = 1024;            // its columns, at most
+
+// out[t][y][x] = frames[t][y + fy][x + fx], (fy, fx) the shift field at (y, x).  One workgroup per tile of 16 rows x <= 1024
+// columns and frame.  The block edges of both axes, then the taps of the tile's rows and columns (dc_field_tap_edges: a bisection
+// and one division each) are derived once per workgroup into LDS -- from the geometry, so no index read from memory addresses
+// block_shifts --, then per frame the row blends a[r][j] = (256-w) s[i0][j] + w s[i1][j] of both components, which leaves a pixel
+// two multiplications per component, one where a group of 8 lies between the same two centres.
+// A thread moves 8 consecutive outputs of one row, cut at multiples of 8 elements of the WHOLE output as in motion_apply_kernel:
+// where the field is the same at all 8 (compared one by one: along a row it is monotone between two centres only) the group is
+// that kernel's aligned 16-byte store from 4 or 5 aligned source dwords; otherwise it goes value by value.
+__global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* __restrict__ frames, int tc, const int* __restrict__ bs,
+                                                              int By, int Bx, int H, int W, unsigned fill, uint16_t* __restrict__ out,
+                                                              int wide, int tilesX) {
+  __shared__ int ctap[kWarpCols];                        // j0 | v << 8 (j1 = j0 + 1 where v > 0)
+  __shared__ int rtap[kWarpRows];                        // i0 | w << 8
+  __shared__ int64_t a[kWarpRows][DC_MOTION_MAX_BLOCKS][2];
+  __shared__ int edge[2][DC_MOTION_MAX_BLOCKS + 1];      // the block edges of the rows and of the columns
+  const int tx = blockIdx.x % tilesX, ty = blockIdx.x / tilesX;
+  const int xlo = tx * kWarpCols, ylo = ty * kWarpRows;
+  const int xhi = xlo + kWarpCols < W ? xlo + kWarpCols : W, yhi = ylo + kWarpRows < H ? ylo + kWarpRows : H;
+  const int ncol = xhi - xlo, nrow = yhi - ylo;
+  if (threadIdx.x <= By) edge[0][threadIdx.x] = dc_block_edge(threadIdx.x, H, By);
+  if (threadIdx.x >= kWave && threadIdx.x - kWave <= Bx) edge[1][threadIdx.x - kWave] = dc_block_edge(threadIdx.x - kWave, W, Bx);
+  __syncthreads();
+  for (int c = threadIdx.x; c < ncol; c += kThreads) {
+    const DcFieldTap t = dc_field_tap_edges(xlo + c, edge[1], Bx);
+    ctap[c] = t.i0 | (t.w << 8);
+  }
+  if (threadIdx.x < nrow) {
+    const DcFieldTap t = dc_field_tap_edges(ylo + threadIdx.x, edge[0], By);
+    rtap[threadIdx.x] = t.i0 | (t.w << 8);
+  }
+  const int HW = H * W;
+  const unsigned fill2 = fill | (fill << 16);
+  for (int t = blockIdx.y; t < tc; t += gridDim.y) {
+    const int* s = bs + (long)t * By * Bx * 2;
+    __syncthreads();                                     // the taps are there; the readers of the previous frame's blends are done
+    for (int i = threadIdx.x; i < nrow * Bx * 2; i += kThreads) {
+      const int c = i & 1, j = (i >> 1) % Bx, r = (i >> 1) / Bx;
+      const int i0 = rtap[r] & 0xff, w = rtap[r] >> 8, i1 = w ? i0 + 1 : i0;
+      a[r][j][c] = dc_field_blend(s[(i0 * Bx + j) * 2 + c], s[(i1 * Bx + j) * 2 + c], w);
+    }
+    __syncthreads();
+    const long base = (long)t * HW;
+    const uint16_t* f = frames + base;
+    // the groups of row y: [A + 8q, A + 8q + 8) of the whole output, cut to the row's columns [xlo, xhi); A = (e0 & ~7)
+    const int nq = ncol / 8 + 2;
+    for (int g = threadIdx.x; g < nrow * nq; g += kThreads) {
+      const int r = g / nq, q = g - r * nq, y = ylo + r;
+      const long e0 = base + (long)y * W + xlo, e1 = e0 + ncol;
+      const long ga = (e0 & ~7L) + 8L * q;
+      const long lo = ga > e0 ? ga : e0, hi = ga + 8 < e1 ? ga + 8 : e1;
+      if (lo >= hi) continue;
+      const int n = (int)(hi - lo), x = xlo + (int)(lo - e0);
+      long fy[8], fx[8];
+      bool same = true;
+      // j0 never decreases along a row: where the group's ends share it, all 8 pixels blend the same two columns of a[r], and
+      // where those are less than 2^14 pixels apart the blend is one 24-bit multiplication per pixel and component
+      const int jf = ctap[x - xlo] & 0xff, jn = jf + 1 < Bx ? jf + 1 : jf;         // past the last centre v is 0: any jn does
+      const int64_t ay = a[r][jf][0], ax = a[r][jf][1], dy = a[r][jn][0] - ay, dx = a[r][jn][1] - ax;
+      if ((ctap[x - xlo + n - 1] & 0xff) == jf && dc_field_delta_small(dy) && dc_field_delta_small(dx)) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int v = ctap[k < n ? x - xlo + k : x - xlo] >> 8;
+          fy[k] = dc_field_from_delta(ay, (int)dy, v);
+          fx[k] = dc_field_from_delta(ax, (int)dx, v);
+          same = same && fy[k] == fy[0] && fx[k] == fx[0];
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int ct = ctap[k < n ? x - xlo + k : x - xlo];
+          const int j0 = ct & 0xff, v = ct >> 8, j1 = v ? j0 + 1 : j0;
+          fy[k] = dc_field_from_rows(a[r][j0][0], a[r][j1][0], v);
+          fx[k] = dc_field_from_rows(a[r][j0][1], a[r][j1][1], v);
+          same = same && fy[k] == fy[0] && fx[k] == fx[0];
+        }
+      }
+      uint16_t* o = out + lo;
+      bool done = false;
+      if (wide && n == 8 && same) done = move8(f, y + fy[0], x + fx[0], H, W, fill2, o);
+      if (!done) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          if (k < n) {
+            const long sy = y + fy[k], sx = x + k + fx[k];
+            o[k] = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? f[sy * W + sx] : (uint16_t)fill;
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int DMAX>
+int launch_block_ssd(const uint16_t* frames, int is_unsigned, int tc, const uint16_t* tmpl, int H, int W, int S, int D, int By, int Bx,
+                     const int* rigid, unsigned long long* bscores, hipStream_t stream) {
+  const int nd = 2 * D + 1;
+  const int lds = (kBlkTileH + 2 * D) * bssd_stride(D) * (int)sizeof(uint16_t) + nd * nd * (int)sizeof(unsigned long long);
+  const dim3 grid((unsigned)(By * Bx), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
+  hipLaunchKernelGGL(motion_block_ssd_kernel<DMAX>, grid, block, lds, stream, frames, is_unsigned ? 0u : 0x8000u, tc, tmpl, H, W, S, D,
+                     By, Bx, rigid, bscores);
+  DC_CHECK_LAUNCH("dc_motion_block_ssd");
+  return DC_OK;
 }
 
 template <int SMAX, int R>
@@ -296,5 +528,70 @@ extern "C" int dc_motion_apply(const void* frames, int tc, const int* shifts, in
   hipLaunchKernelGGL(motion_apply_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, shifts, H, W,
                      (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0));
   DC_CHECK_LAUNCH("dc_motion_apply");
+  return DC_OK;
+}
+
+// what the three piecewise entry points share: the radii and the block grid
+#define DC_REQUIRE_GRID(name, S, D, By, Bx)                                                                                              \
+  DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, name ": S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);           \
+  DC_REQUIRE(D <= DC_MOTION_MAX_DEV, DC_EUNSUP, name ": D = %d: the block deviation radius is limited to %d", D, DC_MOTION_MAX_DEV);      \
+  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, name ": %d x %d blocks: the grid is limited to %d x %d", \
+             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS)
+
+extern "C" int dc_motion_block_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, int By, int Bx,
+                                   const int* rigid, long* bscores, dc_stream_t stream) {
+  DC_REQUIRE(frames && tmpl && rigid && bscores, DC_EINVAL, "dc_motion_block_ssd: null pointer");
+  DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL,
+             "dc_motion_block_ssd: negative or zero size (tc %d, S %d, D %d, H %d, W %d, blocks %d x %d)", tc, S, D, H, W, By, Bx);
+  DC_REQUIRE_GRID("dc_motion_block_ssd", S, D, By, Bx);
+  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_block_ssd: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE(dc_block_axis_ok(H, By, S + D) && dc_block_axis_ok(W, Bx, S + D), DC_EINVAL,
+             "dc_motion_block_ssd: image %d x %d in %d x %d blocks: a block has no interior at S + D = %d", H, W, By, Bx, S + D);
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)tmpl) & 1) == 0 && (((uintptr_t)rigid) & 3) == 0 && (((uintptr_t)bscores) & 7) == 0, DC_EINVAL,
+             "dc_motion_block_ssd: misaligned buffer");
+  if (tc == 0) return DC_OK;
+  const uint16_t* f = (const uint16_t*)frames;
+  const uint16_t* t = (const uint16_t*)tmpl;
+  unsigned long long* sc = (unsigned long long*)bscores;
+  if (D <= 4) return launch_block_ssd<4>(f, is_unsigned, tc, t, H, W, S, D, By, Bx, rigid, sc, (hipStream_t)stream);
+  return launch_block_ssd<8>(f, is_unsigned, tc, t, H, W, S, D, By, Bx, rigid, sc, (hipStream_t)stream);
+}
+
+extern "C" int dc_motion_block_pick(const long* bscores, const int* rigid, int tc, int By, int Bx, int S, int D, int* block_shifts, long* best,
+                                    dc_stream_t stream) {
+  DC_REQUIRE(bscores && rigid && block_shifts, DC_EINVAL, "dc_motion_block_pick: null pointer");
+  DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && By > 0 && Bx > 0, DC_EINVAL,
+             "dc_motion_block_pick: negative or zero size (tc %d, S %d, D %d, blocks %d x %d)", tc, S, D, By, Bx);
+  DC_REQUIRE_GRID("dc_motion_block_pick", S, D, By, Bx);
+  DC_REQUIRE((((uintptr_t)bscores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)rigid | (uintptr_t)block_shifts) & 3) == 0, DC_EINVAL,
+             "dc_motion_block_pick: misaligned buffer");
+  if (tc == 0) return DC_OK;
+  const long items = (long)tc * By * Bx;
+  hipLaunchKernelGGL(motion_block_pick_kernel, dim3((unsigned)(items < (1L << 20) ? items : (1L << 20))), dim3(kWave), 0, (hipStream_t)stream,
+                     (const int64_t*)bscores, rigid, items, By * Bx, S, D, block_shifts, (int64_t*)best);
+  DC_CHECK_LAUNCH("dc_motion_block_pick");
+  return DC_OK;
+}
+
+extern "C" int dc_motion_warp(const void* frames, int tc, const int* block_shifts, int By, int Bx, int H, int W, int fill, void* out,
+                              dc_stream_t stream) {
+  DC_REQUIRE(frames && block_shifts && out, DC_EINVAL, "dc_motion_warp: null pointer");
+  DC_REQUIRE(tc >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL, "dc_motion_warp: negative or zero size (tc %d, H %d, W %d, blocks %d x %d)",
+             tc, H, W, By, Bx);
+  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, "dc_motion_warp: %d x %d blocks: the grid is limited to %d x %d",
+             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS);
+  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_warp: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE(By <= H && Bx <= W, DC_EINVAL, "dc_motion_warp: image %d x %d in %d x %d blocks: a block is empty", H, W, By, Bx);
+  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, "dc_motion_warp: fill = %d is not a 16-bit value", fill);
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)block_shifts) & 3) == 0, DC_EINVAL, "dc_motion_warp: misaligned buffer");
+  const uintptr_t bytes = (uintptr_t)tc * H * W * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
+  DC_REQUIRE(bytes == 0 || fa + bytes <= oa || oa + bytes <= fa, DC_EINVAL, "dc_motion_warp: out overlaps frames");
+  if (tc == 0) return DC_OK;
+  const int tilesX = dc_cdiv(W, kWarpCols);
+  const long tiles = (long)tilesX * dc_cdiv(H, kWarpRows);              // H * W <= 2^30: at most 2^30 tiles
+  const dim3 grid((unsigned)tiles, (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
+  hipLaunchKernelGGL(motion_warp_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, block_shifts, By, Bx, H, W,
+                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0), tilesX);
+  DC_CHECK_LAUNCH("dc_motion_warp");
   return DC_OK;
 }

@@ -3,7 +3,8 @@
 // smallest displacement, then the smaller dy, then the smaller dx.  Two candidates with different (dy, dx) never compare equal, so
 // the minimum is unique and does not depend on the order in which candidates are compared.  Plain C++ on purpose -- no HIP header,
 // no intrinsic -- so the same inline functions compile for the device and into a stand-alone host program
-// (tests/native/motion_math_check.cpp, run under the address / undefined-behaviour sanitizers).
+// (tests/native/motion_math_check.cpp, run under the address / undefined-behaviour sanitizers).  Below the tie rule: the block
+// geometry and the shift field of the piecewise-rigid mode (tests/native/motion_field_check.cpp), in the same plain C++.
 #pragma once
 #include <stdint.h>
 
@@ -50,3 +51,74 @@ DC_MOTION_HD DcShiftCand dc_motion_pick_serial(const int64_t* scores, int S) {
   }
   return best;
 }
+
+// ---- piecewise-rigid correction (motion.hip, dc_motion_block_ssd / dc_motion_warp): block geometry and the shift field, integers only ---------------------------
+// An axis of n pixels is cut into B blocks; block i covers [e(i), e(i+1)) with e(i) = floor(i * n / B).  n <= 2^30, B <= 32.
+DC_MOTION_HD int dc_block_edge(int i, int n, int B) { return (int)((int64_t)i * n / B); }
+
+// every block clipped to the interior [M, n - M) keeps a pixel: the first and the last one do (the others lie between them)
+DC_MOTION_HD bool dc_block_axis_ok(int n, int B, int M) {
+  if (B < 1 || n < B || M < 0 || n <= 2 * (int64_t)M) return false;
+  const int first = dc_block_edge(1, n, B) < n - M ? dc_block_edge(1, n, B) : n - M;
+  const int last = dc_block_edge(B - 1, n, B) > M ? dc_block_edge(B - 1, n, B) : M;
+  return first > M && last < n - M;
+}
+
+// Where pixel y stands between the block centres, in doubled coordinates p = 2y and C2(i) = e(i) + e(i+1) - 1 (strictly increasing
+// when every block has a pixel, n >= B): at or before the first centre (or B == 1) i0 = i1 = 0, at or after the last i0 = i1 =
+// B - 1, both with w = 0; otherwise i0 is the largest i with C2(i) <= p, i1 = i0 + 1 and
+// w = floor(256 * (p - C2(i0)) / (C2(i1) - C2(i0))) in [0, 256).  The block b that holds y has C2(b - 1) < p < C2(b + 1), so i0 is
+// b or b - 1: no search over the centres.
+struct DcFieldTap {
+  int i0, i1, w;
+};
+
+// The tap from a table of the edges e[0 .. B] (the warp kernel keeps one per axis in LDS): no division but the one for w, and that
+// one in 32 bits where the numerator fits.  The block that holds y is found by bisection (e is strictly increasing).
+DC_MOTION_HD DcFieldTap dc_field_tap_edges(int y, const int* e, int B) {
+  DcFieldTap t;
+  t.i0 = t.i1 = t.w = 0;
+  const int64_t p = 2 * (int64_t)y;
+  if (B == 1 || p <= (int64_t)e[0] + e[1] - 1) return t;
+  if (p >= (int64_t)e[B - 1] + e[B] - 1) {
+    t.i0 = t.i1 = B - 1;
+    return t;
+  }
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (e[mid] <= y) lo = mid; else hi = mid - 1;
+  }
+  t.i0 = p >= (int64_t)e[lo] + e[lo + 1] - 1 ? lo : lo - 1;
+  t.i1 = t.i0 + 1;
+  const int64_t c0 = (int64_t)e[t.i0] + e[t.i0 + 1] - 1, c1 = (int64_t)e[t.i1] + e[t.i1 + 1] - 1;
+  if (c1 - c0 < (1 << 23)) t.w = (int)((uint32_t)(256 * (p - c0)) / (uint32_t)(c1 - c0));      // the numerator is below 2^31
+  else t.w = (int)(256 * (p - c0) / (c1 - c0));
+  return t;
+}
+
+// floor(a / 65536) for any sign
+DC_MOTION_HD int64_t dc_floor_div_65536(int64_t a) {
+  const int64_t q = a / 65536;
+  return (a % 65536 < 0) ? q - 1 : q;
+}
+
+// One axis of the bilinear blend: (256 - w) * s0 + w * s1, exact for any int32 s0, s1 (below 2^40 in magnitude)
+DC_MOTION_HD int64_t dc_field_blend(int64_t s0, int64_t s1, int w) { return (256 - w) * s0 + w * s1; }
+
+// The field from the four block shifts around a pixel:
+//   num = (256-w) * ((256-v) * s00 + v * s01) + w * ((256-v) * s10 + v * s11),  field = floor((num + 32768) / 65536).
+// |num| <= 2^16 * 2^31: 64 bits hold it.  The field lies in [min s, max s]; equal shifts give that shift.
+DC_MOTION_HD int64_t dc_field_value(int64_t s00, int64_t s01, int64_t s10, int64_t s11, int w, int v) {
+  return dc_floor_div_65536(dc_field_blend(dc_field_blend(s00, s01, v), dc_field_blend(s10, s11, v), w) + 32768);
+}
+
+// the same from the two row blends a0 = blend(s00, s10, w), a1 = blend(s01, s11, w): the sum is the same integer in either order
+DC_MOTION_HD int64_t dc_field_from_rows(int64_t a0, int64_t a1, int v) { return dc_floor_div_65536(dc_field_blend(a0, a1, v) + 32768); }
+
+// ... and from a0 and the difference d = a1 - a0 where |d| < 2^22 (block shifts less than 2^14 pixels apart): (256-v) a0 + v a1 =
+// 256 a0 + v d, and v d fits 32 bits -- one 24-bit multiplication per pixel instead of two 64-bit ones
+DC_MOTION_HD bool dc_field_delta_small(int64_t d) { return d > -(1 << 22) && d < (1 << 22); }
+DC_MOTION_HD int64_t dc_field_from_delta(int64_t a0, int d, int v) { return dc_floor_div_65536(256 * a0 + (int64_t)(v * d) + 32768); }
+
+DC_MOTION_HD int dc_motion_clamp(int v, int S) { return v < -S ? -S : (v > S ? S : v); }

@@ -1,4 +1,5 @@
-"""Rigid motion correction on the device: the frames of a recording (T,H,W) of 16-bit frames are registered to a template.
+"""Motion correction on the device, rigid or piecewise-rigid: the frames of a recording (T,H,W) of 16-bit frames are registered
+to a template.
 
 Every other stage of the pipeline (series.py, UNet2DSummary.predict, traces.py, spikes.py) assumes registered frames.  Here every
 frame is compared with a template at every whole-pixel shift within +-max_shift (dc_motion_ssd: the exact integer sum of
@@ -21,8 +22,22 @@ to the template is found as (dy, dx) = (-a, -b).
     img = summarize_series_device('dataset.hdf5', kind='corr', shifts=shifts)  # corrected on the way in, no second copy
     traces = extract_traces_device('dataset.hdf5', mask, shifts=shifts)
 
-Scope: rigid, whole-pixel translation found by exhaustive search, max_shift <= 16.  Sub-pixel, piecewise and non-rigid
-registration, FFT methods and larger search radii are not implemented.
+Piecewise-rigid (blocks=(By, Bx)): a frame is scanned line by line while the tissue moves, so one translation cannot register
+all of it.  The frame is cut into By x Bx blocks (block i covers rows [floor(i H / By), floor((i+1) H / By)), columns likewise);
+every block gets the frame's rigid shift plus a residual within +-max_dev, found the same way over the block's own pixels
+(dc_motion_block_ssd, dc_motion_block_pick: ties go to the smallest residual, so a featureless block follows the rigid shift),
+and the block shifts are blended bilinearly between the block centres into one whole-pixel shift per pixel (dc_motion_warp).
+Where that field changes by one pixel a source pixel is repeated or skipped: the price of whole-pixel exactness.
+
+    mc = MotionCorrector((H, W), T, np.int16, template, max_shift=8, blocks=(4, 4), max_dev=3)
+    for chunk in chunks: corrected = mc.feed(chunk)        # warped by the field
+    bs = mc.block_shifts()                                 # (fed, By, Bx, 2) int32; mc.shifts() stays the rigid table
+
+    bs, template = estimate_shifts_device('dataset.hdf5', blocks=(4, 4))      # (T, By, Bx, 2): shifts= takes it as it is
+
+Scope: whole-pixel shifts found by exhaustive search, max_shift <= 16, max_dev <= 8, at most 32 x 32 blocks.  Sub-pixel shifts
+and interpolation of pixel values, template building with blocks, temporal smoothing of the shifts, FFT methods and larger
+search radii are not implemented.
 
 Importing this module needs neither torch nor the GPU; constructing a MotionCorrector does (there is no CPU fallback).
 """
@@ -32,6 +47,8 @@ from .series import _CHUNK_BYTES, _TwoSlotStage, _check_device_frames, _frame_dt
 from .traces import _check_shape
 
 MAX_SHIFT = 16                        # DC_MOTION_MAX_SHIFT
+MAX_DEV = 8                           # DC_MOTION_MAX_DEV
+MAX_BLOCKS = 32                       # DC_MOTION_MAX_BLOCKS
 
 
 def _check_max_shift(max_shift, shape=None):
@@ -44,6 +61,38 @@ def _check_max_shift(max_shift, shape=None):
         raise ValueError('max_shift = %d leaves no interior in a %d x %d frame: H > 2 * max_shift and W > 2 * max_shift'
                          % (S, shape[0], shape[1]))
     return S
+
+
+def block_edges(n, B):
+    """The B + 1 edges of the blocks of an axis of n pixels: e(i) = floor(i * n / B)."""
+    return [i * n // B for i in range(B + 1)]
+
+
+def _check_blocks(blocks, max_dev, shape=None, max_shift=0):
+    """blocks=(By, Bx) and max_dev of the piecewise-rigid mode -> (By, Bx, D); every block, clipped to the interior that
+    max_shift + max_dev leaves, must keep a pixel."""
+    try:
+        ok = len(blocks) == 2 and all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) for b in blocks)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError('blocks must be (By, Bx), two integers in [1, %d], not %r' % (MAX_BLOCKS, blocks))
+    By, Bx = int(blocks[0]), int(blocks[1])
+    if not (1 <= By <= MAX_BLOCKS and 1 <= Bx <= MAX_BLOCKS):
+        raise ValueError('blocks must be (By, Bx), two integers in [1, %d], not %r' % (MAX_BLOCKS, (By, Bx)))
+    if isinstance(max_dev, bool) or not isinstance(max_dev, (int, np.integer)):
+        raise ValueError('max_dev must be an integer in [0, %d], not %r' % (MAX_DEV, max_dev))
+    D = int(max_dev)
+    if not 0 <= D <= MAX_DEV:
+        raise ValueError('max_dev must be in [0, %d], not %d' % (MAX_DEV, D))
+    if shape is not None:
+        M = int(max_shift) + D
+        for n, B, axis in ((shape[0], By, 'rows'), (shape[1], Bx, 'columns')):
+            e = block_edges(n, B)
+            if n < B or n <= 2 * M or min(e[1], n - M) <= M or max(e[B - 1], M) >= n - M:
+                raise ValueError('blocks = %r: a block of a %d x %d frame has no %s inside the margin max_shift + max_dev = %d'
+                                 % ((By, Bx), shape[0], shape[1], axis, M))
+    return By, Bx, D
 
 
 def _check_fill(fill):
@@ -64,7 +113,8 @@ def _check_template(template, shape, dtype):
 
 def valid_rectangle(shifts, shape):
     """((y0, y1), (x0, x1)): the rectangle every frame corrected by `shifts` (n, 2) covers with its own pixels,
-    y in [max(0, -min dy), H - max(0, max dy)), likewise x.  Host only."""
+    y in [max(0, -min dy), H - max(0, max dy)), likewise x.  Block shifts (n, By, Bx, 2) are taken one by one: the shift field
+    never leaves their range, so the rectangle bounds the warped frames too.  Host only."""
     H, W = shape
     s = np.asarray(shifts).reshape(-1, 2).astype(np.int64)
     if len(s) == 0:
@@ -76,7 +126,8 @@ def valid_rectangle(shifts, shape):
 class MotionCorrector(object):
     """Owns the device state of one recording's registration; feed() the frames in order, in chunks of any size."""
 
-    def __init__(self, shape, n_frames, dtype, template, max_shift=8, fill=0, device=None, chunk_frames=None):
+    def __init__(self, shape, n_frames, dtype, template, max_shift=8, fill=0, device=None, chunk_frames=None, blocks=None,
+                 max_dev=3):
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         H, W = shape
@@ -86,6 +137,10 @@ class MotionCorrector(object):
         self.dtype = _frame_dtype(dtype)
         self.max_shift = _check_max_shift(max_shift, shape)
         self.fill = _check_fill(fill)
+        self.blocks, self.max_dev = None, None
+        if blocks is not None:
+            By, Bx, self.max_dev = _check_blocks(blocks, max_dev, shape, self.max_shift)
+            self.blocks = (By, Bx)
         template = _check_template(template, shape, self.dtype)
         if chunk_frames is None:
             chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
@@ -114,6 +169,10 @@ class MotionCorrector(object):
         self._tmpl = torch.from_numpy(template.view(np.int16)).to(dev)
         self._shifts = torch.zeros((n_frames, 2), dtype=torch.int32, device=dev)
         self._scores = torch.empty((self.chunk_frames, nd, nd), dtype=torch.int64, device=dev)      # fully written by every chunk
+        if self.blocks is not None:
+            (By, Bx), nb = self.blocks, 2 * self.max_dev + 1
+            self._bshifts = torch.zeros((n_frames, By, Bx, 2), dtype=torch.int32, device=dev)
+            self._bscores = torch.empty((self.chunk_frames, By, Bx, nb, nb), dtype=torch.int64, device=dev)
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
@@ -125,7 +184,15 @@ class MotionCorrector(object):
         rows = self._shifts.data_ptr() + 8 * self.fed
         L.dc_motion_ssd(fp, int(self.dtype == np.dtype(np.uint16)), tc, self._tmpl.data_ptr(), H, W, S, self._scores.data_ptr(), st)
         L.dc_motion_pick(self._scores.data_ptr(), tc, S, rows, None, st)
-        if out is not None:
+        if self.blocks is not None:
+            (By, Bx), D = self.blocks, self.max_dev
+            brows = self._bshifts.data_ptr() + 8 * By * Bx * self.fed
+            L.dc_motion_block_ssd(fp, int(self.dtype == np.dtype(np.uint16)), tc, self._tmpl.data_ptr(), H, W, S, D, By, Bx, rows,
+                                  self._bscores.data_ptr(), st)
+            L.dc_motion_block_pick(self._bscores.data_ptr(), rows, tc, By, Bx, S, D, brows, None, st)
+            if out is not None:
+                L.dc_motion_warp(fp, tc, brows, By, Bx, H, W, self.fill, out, st)
+        elif out is not None:
             L.dc_motion_apply(fp, tc, rows, H, W, self.fill, out, st)
         self.fed += tc
         self._last = tc
@@ -135,7 +202,8 @@ class MotionCorrector(object):
         through two pinned slots), or a contiguous (t, H, W) torch.int16 tensor on the corrector's device holding the
         recording's bits (read in place).  Returns the corrected frames as a (t, H, W) torch.int16 tensor on the device (the
         frames' bits); their shifts land in rows [fed, fed + t) of shifts_device().  correct=False only estimates the shifts
-        and returns None."""
+        and returns None.  With blocks: the frames are warped by the shift field, and their block shifts land in rows
+        [fed, fed + t) of block_shifts_device()."""
         on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
         if not on_device and not isinstance(frames, np.ndarray):
             raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
@@ -182,9 +250,29 @@ class MotionCorrector(object):
         (dy the slow axis, index dy + S) -- score minus the frame's minimum is a confidence measure."""
         return self._scores[:self._last].cpu().numpy()
 
+    def _need_blocks(self):
+        if self.blocks is None:
+            raise ValueError('this corrector is rigid: block shifts need blocks=(By, Bx)')
+
+    def block_shifts_device(self):
+        """The int32 (n_frames, By, Bx, 2) tensor of block shifts on the device; rows [0, fed) are set."""
+        self._need_blocks()
+        return self._bshifts
+
+    def block_shifts(self):
+        """(fed, By, Bx, 2) int32 numpy array: the (dy, dx) of every block, the frame's rigid shift included."""
+        self._need_blocks()
+        return self._bshifts[:self.fed].cpu().numpy()
+
+    def last_block_scores(self):
+        """(t, By, Bx, 2D+1, 2D+1) int64 numpy array: the block scores of the last piece that was registered, around the
+        frame's rigid shift (ey the slow axis, index ey + D)."""
+        self._need_blocks()
+        return self._bscores[:self._last].cpu().numpy()
+
     def valid(self):
         """((y0, y1), (x0, x1)): the rectangle every frame corrected so far covers with its own pixels."""
-        return valid_rectangle(self.shifts(), self.shape)
+        return valid_rectangle(self.shifts() if self.blocks is None else self.block_shifts(), self.shape)
 
 
 def _rounded_mean(torch, total, n):
@@ -233,12 +321,15 @@ def make_template(frames, max_shift=8, iterations=1, device=None):
 
 
 def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=200, source='series/raw', device=None,
-                           chunk_frames=None):
+                           chunk_frames=None, blocks=None, max_dev=3):
     """(shifts, template): the (T, 2) int32 (dy, dx) of every frame of `source` of a dataset file against `template` -- built
     by make_template (one iteration) from the first min(T, template_frames) frames when none is given.  The recording is
     streamed once, memory-mapped or sliced, never read whole; nothing is corrected here: pass `shifts` to
-    summarize_series_device / extract_traces_device."""
+    summarize_series_device / extract_traces_device.  blocks=(By, Bx): the (T, By, Bx, 2) int32 block shifts within
+    +-max_dev of each frame's rigid shift instead (the template is still built rigidly); `shifts=` takes them as they are."""
     _check_max_shift(max_shift)
+    if blocks is not None:
+        _check_blocks(blocks, max_dev)
     if isinstance(template_frames, bool) or not isinstance(template_frames, (int, np.integer)) or template_frames < 1:
         raise ValueError('template_frames must be an integer >= 1, not %r' % (template_frames,))
     frames, close = _open_series(dspath, source)
@@ -250,10 +341,13 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
         S = _check_max_shift(max_shift, shape)
         if template is None:
             template = make_template(np.asarray(frames[:min(T, int(template_frames))]), max_shift=S, iterations=1, device=device)
-        mc = MotionCorrector(shape, T, frames.dtype, template, max_shift=S, device=device, chunk_frames=chunk_frames)
+        if blocks is not None:
+            _check_blocks(blocks, max_dev, shape, S)
+        mc = MotionCorrector(shape, T, frames.dtype, template, max_shift=S, device=device, chunk_frames=chunk_frames, blocks=blocks,
+                             max_dev=max_dev)
         for a in range(0, T, mc.chunk_frames):
             mc.feed(np.asarray(frames[a:a + mc.chunk_frames]), correct=False)
-        out = mc.shifts()
+        out = mc.shifts() if blocks is None else mc.block_shifts()
     finally:
         frames = None                        # a view of the file mapping: released before the file is closed
         close()

@@ -44,20 +44,35 @@ def _frame_dtype(dtype):
     return dt
 
 
-def _check_shifts(shifts, n_frames):
+_MAX_BLOCKS = 32                      # DC_MOTION_MAX_BLOCKS
+
+
+def _shifts_shape_ok(shape, n_frames, frame_shape):
+    """(n_frames, 2): one rigid (dy, dx) per frame; (n_frames, By, Bx, 2): one per block of a grid that fits the frame."""
+    shape = tuple(shape)
+    if shape == (n_frames, 2):
+        return True
+    if len(shape) != 4 or shape[0] != n_frames or shape[3] != 2:
+        return False
+    limit = (_MAX_BLOCKS, _MAX_BLOCKS) if frame_shape is None else (min(_MAX_BLOCKS, frame_shape[0]), min(_MAX_BLOCKS, frame_shape[1]))
+    return 1 <= shape[1] <= limit[0] and 1 <= shape[2] <= limit[1]
+
+
+def _check_shifts(shifts, n_frames, frame_shape=None):
     """The `shifts=` keyword of SeriesSummarizer / RoiTraceExtractor: None, an (n_frames, 2) integer numpy array of (dy, dx) rows
-    (-> contiguous int32) or an (n_frames, 2) integer tensor (checked, returned as it is).  Host only."""
+    (-> contiguous int32) or an (n_frames, 2) integer tensor (checked, returned as it is); or the piecewise-rigid
+    (n_frames, By, Bx, 2) block shifts of either kind, By and Bx in [1, 32] and no more blocks than pixels.  Host only."""
     if shifts is None:
         return None
+    what = 'shifts must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), or (%d, By, Bx, 2) block shifts with By, Bx in [1, %d]' \
+        % (n_frames, n_frames, _MAX_BLOCKS)
     if not isinstance(shifts, np.ndarray) and hasattr(shifts, 'is_cuda') and hasattr(shifts, 'data_ptr'):
-        if tuple(shifts.shape) != (n_frames, 2) or shifts.dtype.is_floating_point or shifts.dtype.is_complex:
-            raise ValueError('shifts must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), not %s %r'
-                             % (n_frames, shifts.dtype, tuple(shifts.shape)))
+        if not _shifts_shape_ok(shifts.shape, n_frames, frame_shape) or shifts.dtype.is_floating_point or shifts.dtype.is_complex:
+            raise ValueError('%s, not %s %r' % (what, shifts.dtype, tuple(shifts.shape)))
         return shifts
     a = np.asarray(shifts)
-    if a.ndim != 2 or a.shape != (n_frames, 2) or a.dtype.kind not in 'iu':
-        raise ValueError('shifts must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), not %s %r'
-                         % (n_frames, a.dtype, tuple(a.shape)))
+    if not _shifts_shape_ok(a.shape, n_frames, frame_shape) or a.dtype.kind not in 'iu':
+        raise ValueError('%s, not %s %r' % (what, a.dtype, tuple(a.shape)))
     if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
         raise ValueError('shifts must fit int32')
     return np.ascontiguousarray(a.astype(np.int32))
@@ -74,14 +89,16 @@ def _check_device_frames(torch, frames, dtype, device, owner):
 
 
 class _ShiftedChunks(object):
-    """Known shifts applied on the way in (dc_motion_apply, fill 0): the int32 (n_frames, 2) table on the device and one scratch
-    chunk the accumulate kernels read instead of the staged frames.  Frame `fed + i` of the recording gets row `fed + i`."""
+    """Known shifts applied on the way in (fill 0): the int32 (n_frames, 2) table on the device (dc_motion_apply) or the
+    (n_frames, By, Bx, 2) block shifts (dc_motion_warp) and one scratch chunk the accumulate kernels read instead of the staged
+    frames.  Frame `fed + i` of the recording gets row `fed + i`."""
 
     def __init__(self, torch, L, device, shifts, shape):
         self._L, self.shape = L, shape
         if isinstance(shifts, np.ndarray):
             shifts = torch.from_numpy(shifts)
         self.shifts = shifts.to(device=device, dtype=torch.int32).contiguous()
+        self.blocks = tuple(int(v) for v in self.shifts.shape[1:3]) if self.shifts.dim() == 4 else None
         self.scratch = torch.empty(shape, dtype=torch.int16, device=device)
 
     def run(self, fp, tc, fed, st, launch):
@@ -89,8 +106,13 @@ class _ShiftedChunks(object):
         C, H, W = self.shape
         for a in range(0, tc, C):
             n = min(C, tc - a)
-            self._L.dc_motion_apply(fp + 2 * a * H * W, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
-                                    self.scratch.data_ptr(), st)
+            if self.blocks is None:
+                self._L.dc_motion_apply(fp + 2 * a * H * W, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
+                                        self.scratch.data_ptr(), st)
+            else:
+                By, Bx = self.blocks
+                self._L.dc_motion_warp(fp + 2 * a * H * W, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
+                                       self.scratch.data_ptr(), st)
             launch(self.scratch.data_ptr(), n, fed + a)
 
 
@@ -139,7 +161,8 @@ class SeriesSummarizer(object):
 
     def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None):
         """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
-        MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before it is summarised."""
+        MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before it is summarised.  Piecewise-rigid
+        (n_frames, By, Bx, 2) block shifts (MotionCorrector.block_shifts_device()) are taken too: dc_motion_warp moves the chunk."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         try:
             shape = tuple(int(v) for v in shape)
@@ -162,7 +185,7 @@ class SeriesSummarizer(object):
         chunk_frames = int(chunk_frames)
         if chunk_frames < 1:
             raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        shifts = _check_shifts(shifts, n_frames)
+        shifts = _check_shifts(shifts, n_frames, shape)
         self.shape, self.n_frames, self.kinds = shape, n_frames, kinds
         self.chunk_frames = min(chunk_frames, n_frames)
         self.fed = 0
@@ -337,8 +360,8 @@ def _open_series(dspath, source):
 def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
                             shifts=None):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
-    float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame
-    (motion.estimate_shifts_device), applied on the device on the way in."""
+    float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame, or
+    its (T, By, Bx, 2) block shifts (motion.estimate_shifts_device), applied on the device on the way in."""
     _check_kind(kind)
     frames, close = _open_series(dspath, source)
     try:

@@ -107,7 +107,8 @@ class RoiTraceExtractor(object):
 
     def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None):
         """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
-        MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before its ROIs are summed."""
+        MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before its ROIs are summed.  Piecewise-rigid
+        (n_frames, By, Bx, 2) block shifts (MotionCorrector.block_shifts_device()) are taken too: dc_motion_warp moves the chunk."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         H, W = shape
@@ -121,7 +122,7 @@ class RoiTraceExtractor(object):
         chunk_frames = int(chunk_frames)
         if chunk_frames < 1:
             raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        shifts = _check_shifts(shifts, n_frames)
+        shifts = _check_shifts(shifts, n_frames, shape)
         self.shape, self.n_frames, self.areas = shape, n_frames, areas
         self.n_rois = len(areas)
         self.chunk_frames = min(chunk_frames, n_frames)
@@ -214,8 +215,8 @@ class RoiTraceExtractor(object):
 
 def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device=None, chunk_frames=None, shifts=None):
     """The (R,T) traces of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
-    recording is memory-mapped or sliced, never read whole.  shifts: the (T, 2) (dy, dx) of every frame
-    (motion.estimate_shifts_device), applied on the device on the way in."""
+    recording is memory-mapped or sliced, never read whole.  shifts: the (T, 2) (dy, dx) of every frame, or its (T, By, Bx, 2) block
+    shifts (motion.estimate_shifts_device), applied on the device on the way in."""
     _check_kind(kind)
     frames, close = _open_series(dspath, source)
     try:

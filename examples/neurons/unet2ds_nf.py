@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -103,20 +103,33 @@ def prediction(dataset_name, model_path, checkpoints_dir):
         nf_submit(Mp, names, '%s/submission_latest%s.json' % (model.cpdir, ('_TTA' if aug else '')))
 
 
-def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None):
+def _blocks_arg(text):
+    """'4x4' -> (4, 4)."""
+    try:
+        by, bx = (int(v) for v in text.lower().split('x'))
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected ByxBx, e.g. 4x4, not %r' % text)
+    return by, bx
+
+
+def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
     within +-S); the summary the network segments is then the mean of the registered raw frames instead of the stored
-    `series/mean`, and the traces are summed over the registered frames."""
+    `series/mean`, and the traces are summed over the registered frames.  blocks=(By, Bx) with register: piecewise-rigid -- every
+    block of the frame gets the rigid shift plus a residual within +-max_dev, and the frames are warped by the blended field."""
     logger = logging.getLogger('traces')
+    if blocks is not None and register is None:
+        raise ValueError('--blocks needs --register')
     dspaths = nf_find_hdf5(dataset_name)
     shifts = {}
     if register is not None:
         for dspath in dspaths:
-            shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register)
-            logger.info('%s: registered within +-%d, largest |dy|, |dx| = %d, %d, valid rectangle %r' % (
-                dspath, register, np.abs(shifts[dspath][:, 0]).max(), np.abs(shifts[dspath][:, 1]).max(),
+            shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register, blocks=blocks, max_dev=max_dev)
+            logger.info('%s: registered within +-%d%s, largest |dy|, |dx| = %d, %d, valid rectangle %r' % (
+                dspath, register, '' if blocks is None else ' in %d x %d blocks within +-%d of that' % (blocks + (max_dev,)),
+                np.abs(shifts[dspath][..., 0]).max(), np.abs(shifts[dspath][..., 1]).max(),
                 valid_rectangle(shifts[dspath], tmpl.shape)))
         model = UNet2DSummary(cpdir=checkpoints_dir,
                               series_summary_func=lambda p: summarize_series_device(p, kind='mean', shifts=shifts[p]))
@@ -162,6 +175,10 @@ if __name__ == '__main__':
     sp_trc.add_argument('--kind', help='what a trace holds', default='mean', choices=('sum', 'mean', 'zscore'))
     sp_trc.add_argument('--register', help='register the raw frames first, within +-S pixels (default 8)', nargs='?', const=8, default=None,
                         type=int, metavar='S')
+    sp_trc.add_argument('--blocks', help='with --register: piecewise-rigid, one shift per block of a By x Bx grid (e.g. 4x4)', default=None,
+                        type=_blocks_arg, metavar='ByxBx')
+    sp_trc.add_argument('--max-dev', help='with --blocks: a block may deviate from the rigid shift by +-D pixels (default 3)', default=3,
+                        type=int, metavar='D', dest='max_dev')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

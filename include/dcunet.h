@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 112
+#define DC_ABI_VERSION 113
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -533,8 +533,9 @@ int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, lo
 /* ---- rigid motion correction: register the frames of a recording to a template ------------------------------------------------
  * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
  * examples/neurons/unet2ds_sj.py, were registered by an outside tool: it reads directories named ..._stabilized).  This is that
- * step: rigid, whole-pixel translation, found by exhaustive search within +-S, S <= DC_MOTION_MAX_SHIFT.  Sub-pixel, piecewise
- * and non-rigid registration and FFT methods are out of scope.  Integer arithmetic only: every result is exact, so the chunking
+ * step: rigid, whole-pixel translation, found by exhaustive search within +-S, S <= DC_MOTION_MAX_SHIFT; the piecewise-rigid
+ * mode built on it follows below.  Sub-pixel shifts, interpolation of pixel values and FFT methods are out of scope.  Integer
+ * arithmetic only: every result is exact, so the chunking
  * of a recording never changes a bit.
  * frames: as for dc_series_accumulate (int16 / uint16 by is_unsigned, [tc][H][W] contiguous, 2-byte aligned); tmpl: [H][W] of the
  * same type.  H > 2S and W > 2S (else DC_EINVAL); S > 16 or H * W > 2^30: DC_EUNSUP (-3).
@@ -556,6 +557,43 @@ int dc_motion_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl,
                   dc_stream_t stream);
 int dc_motion_pick(const long* scores, int tc, int S, int* shifts, long* best, dc_stream_t stream);
 int dc_motion_apply(const void* frames, int tc, const int* shifts, int H, int W, int fill, void* out, dc_stream_t stream);
+
+/* ---- piecewise-rigid motion correction: one whole-pixel shift per block of the frame, blended into a shift field ----------------
+ * A two-photon frame is scanned line by line while the tissue moves, so its top is displaced differently from its bottom.  The
+ * frame is cut into By x Bx blocks; every block gets the frame's rigid shift plus a residual within +-D, D <= DC_MOTION_MAX_DEV,
+ * and the block shifts are blended bilinearly into one whole-pixel shift per pixel.  Integers only, the sign convention above.
+ * M = S + D; By, Bx in [1, DC_MOTION_MAX_BLOCKS].
+ * BLOCK GEOMETRY (a function of H, W, By, Bx alone, so an int32[tc][By][Bx][2] array of shifts is self-describing): block i covers
+ *   rows [e(i), e(i+1)), e(i) = floor(i * H / By); columns likewise from W and Bx.  For scoring a block is clipped to the interior
+ *   [M, H-M) x [M, W-M) and every clipped block must keep a pixel on both axes: H > 2M, e(1) > M and e(By-1) < H - M (else DC_EINVAL).
+ *   dc_motion_block_ssd: bscores = int64[tc][By][Bx][2D+1][2D+1], fully written (never pre-clear):
+ *     bscores[t][i][j][ey+D][ex+D] = sum over the clipped block (i, j) of (tmpl[y][x] - frame[y + dy + ey][x + dx + ex])^2,
+ *     (dy, dx) = rigid[t] (int32[tc][2], e.g. what dc_motion_pick wrote) read on the device and CLAMPED there to [-S, S] per
+ *     component: no value in that table makes the kernel read outside the frame.  Every candidate of a block sums the same
+ *     pixels, and summed over the blocks a candidate's scores are the rigid-style score over the margin-M interior at
+ *     (dy + ey, dx + ex).  D = 0 is legal (one score per block).
+ *   dc_motion_block_pick: block_shifts = int32[tc][By][Bx][2], best = int64[tc][By][Bx] (nullable).  The residual minimises
+ *     (bscore, ey^2 + ex^2, ey, ex) lexicographically -- the order of dc_motion_pick, so a featureless block follows the rigid
+ *     shift --; block_shifts[t][i][j] = clamp(rigid[t]) + residual.
+ *   dc_motion_warp: out[t][y][x] = frames[t][y + fy][x + fx] inside the frame, `fill` elsewhere, with the SHIFT FIELD (fy, fx) of
+ *     (y, x) computed per axis in doubled coordinates.  Centres C2(i) = e(i) + e(i+1) - 1 (strictly increasing; By <= H and Bx <= W
+ *     are required, else DC_EINVAL).  For row y, p = 2y: if By == 1 or p <= C2(0): i0 = i1 = 0, w = 0; if p >= C2(By-1): i0 = i1 =
+ *     By-1, w = 0; otherwise i0 is the largest i with C2(i) <= p, i1 = i0 + 1, w = floor(256 (p - C2(i0)) / (C2(i1) - C2(i0))) in
+ *     [0, 256).  Columns give j0, j1, v the same way.  Per component, s the block shifts of the frame, in 64-bit arithmetic:
+ *       num = (256-w) ((256-v) s[i0][j0] + v s[i0][j1]) + w ((256-v) s[i1][j0] + v s[i1][j1]),  field = floor((num + 32768) / 65536).
+ *     Equal block shifts give exactly that shift everywhere (then this is dc_motion_apply), and the field never leaves
+ *     [min s, max s]; any int32 block shift is legal, |fy| >= H gives an all-fill row.  A pure move of 16-bit values: where the
+ *     field changes by one pixel a source pixel is repeated or skipped -- the price of whole-pixel exactness.  The ABI takes the
+ *     geometry, not weight tables: no index read from memory addresses block_shifts.  out must not overlap frames (DC_EINVAL).
+ * D > 8, By or Bx > 32, S > 16 or H * W > 2^30: DC_EUNSUP (-3). */
+#define DC_MOTION_MAX_DEV 8
+#define DC_MOTION_MAX_BLOCKS 32
+int dc_motion_block_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, int By, int Bx,
+                        const int* rigid, long* bscores, dc_stream_t stream);
+int dc_motion_block_pick(const long* bscores, const int* rigid, int tc, int By, int Bx, int S, int D, int* block_shifts, long* best,
+                         dc_stream_t stream);
+int dc_motion_warp(const void* frames, int tc, const int* block_shifts, int By, int Bx, int H, int W, int fill, void* out,
+                   dc_stream_t stream);
 
 /* ---- UNet1D spike inference: traces in, spike probabilities out ------------------------------------------------------------
  * The reference's second model family, UNet1DSegmentation: the network unet1d (unet_1d_segmentation.py:49-148) as its predict()

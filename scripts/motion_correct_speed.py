@@ -1,12 +1,14 @@
 """Times of the motion-correction path on one GPU (the figures of DESIGN.md section 4f).
 
-    python scripts/motion_correct_speed.py [--frames 3000] [--hw 512] [--chunk 64] [--out FILE]
+    python scripts/motion_correct_speed.py [--frames 3000] [--hw 512] [--chunk 64] [--blocks 4x4] [--max-dev 3] [--out FILE]
 
 A synthetic int16 recording -- a random scene cut at random offsets within +-5 pixels, plus noise -- is written as an .npz next to
 the output (np.savez: stored, so it is memory-mapped).  Timed, for max_shift S = 4, 8 and 16 and chunks of `--chunk` frames:
  (a) the H2D copy of one chunk out of pinned memory;
  (b) kernel time per chunk of dc_motion_ssd, dc_motion_pick and dc_motion_apply: HIP events on the launch stream around 5 launches
-     back to back, median of 5 such samples after a warm-up (min - max), and the ratio of each to the copy;
+     back to back, median of 5 such samples after a warm-up (min - max), and the ratio of each to the copy; then the same for the
+     piecewise-rigid entry points dc_motion_block_ssd, dc_motion_block_pick and dc_motion_warp at `--blocks` and `--max-dev`,
+     on the rigid shifts just found;
  (c) wall time of estimate_shifts_device over the whole recording with a given template (median of 5 after a warm-up, page cache
      warm), and whether the planted shifts came back;
  (d) a numpy restatement of the same search on a few frames, scaled to a chunk.
@@ -46,6 +48,8 @@ def main():
     ap.add_argument('--hw', type=int, default=512)
     ap.add_argument('--chunk', type=int, default=64)
     ap.add_argument('--host-frames', type=int, default=2, help='frames of the numpy search (the time is scaled to a chunk)')
+    ap.add_argument('--blocks', default='4x4', help='the block grid ByxBx of the piecewise-rigid rows')
+    ap.add_argument('--max-dev', type=int, default=3, help='their deviation radius D')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
@@ -53,6 +57,8 @@ def main():
     from deep_calcium_amd._lib import lib
     L = lib()
     T, H, W, C = args.frames, args.hw, args.hw, args.chunk
+    By, Bx = (int(v) for v in args.blocks.lower().split('x'))
+    D = args.max_dev
     lines = []
 
     def say(s):
@@ -81,6 +87,8 @@ def main():
     out = torch.empty((C, H, W), dtype=torch.int16, device='cuda')
     dt = torch.from_numpy(tmpl).cuda()
     shifts = torch.zeros((C, 2), dtype=torch.int32, device='cuda')
+    bshifts = torch.zeros((C, By, Bx, 2), dtype=torch.int32, device='cuda')
+    bscores = torch.empty((C, By, Bx, 2 * D + 1, 2 * D + 1), dtype=torch.int64, device='cuda')
     stream = torch.cuda.current_stream().cuda_stream
 
     def timed(fn, reps=1):
@@ -113,10 +121,28 @@ def main():
         for name, fn in rows:
             ms, lo, hi = sample(fn)
             total += ms
+            ms_apply = ms                                # the last row: dc_motion_apply
             extra = '  %6.2f T multiply-adds/s' % (madds / ms / 1e9) if name == 'dc_motion_ssd' else ''
             say('  S = %2d  %-16s %8.3f ms  (%.3f - %.3f)  / H2D = %5.2f%s' % (S, name, ms, lo, hi, ms / h2d, extra))
         say('  S = %2d  all three       %8.3f ms                     / H2D = %5.2f  (%s)'
             % (S, total, total / h2d, 'hides under the copy' if total < h2d else 'does NOT hide under the copy'))
+        bmadds = C * (2 * D + 1) ** 2 * (H - 2 * (S + D)) * (W - 2 * (S + D))
+        brows = [('dc_motion_block_ssd', lambda: L.dc_motion_block_ssd(dev.data_ptr(), 0, C, dt.data_ptr(), H, W, S, D, By, Bx, shifts.data_ptr(),
+                                                                       bscores.data_ptr(), stream)),
+                 ('dc_motion_block_pick', lambda: L.dc_motion_block_pick(bscores.data_ptr(), shifts.data_ptr(), C, By, Bx, S, D,
+                                                                         bshifts.data_ptr(), None, stream)),
+                 ('dc_motion_warp', lambda: L.dc_motion_warp(dev.data_ptr(), C, bshifts.data_ptr(), By, Bx, H, W, 0, out.data_ptr(), stream))]
+        btotal = 0.0
+        for name, fn in brows:
+            ms, lo, hi = sample(fn)
+            btotal += ms
+            extra = '  %6.2f T multiply-adds/s' % (bmadds / ms / 1e9) if name == 'dc_motion_block_ssd' else ''
+            say('  S = %2d  %-20s %8.3f ms  (%.3f - %.3f)  / H2D = %5.2f%s' % (S, name, ms, lo, hi, ms / h2d, extra))
+        say('  S = %2d  piecewise %dx%d, D = %d: these three %8.3f ms, with the rigid ssd and pick %8.3f ms  / H2D = %5.2f'
+            % (S, By, Bx, D, btotal, btotal + total - ms_apply, (btotal + total - ms_apply) / h2d))
+        got_b = bshifts.cpu().numpy()
+        say('  S = %2d  block shifts of the chunk all equal to the planted rigid shift: %s'
+            % (S, bool((got_b == -offs[:C, None, None, :]).all()) if S >= M else 'n/a (S < 5)'))
         got = shifts.cpu().numpy()
         say('  S = %2d  planted shifts of the chunk recovered: %s' % (S, bool((got == -offs[:C]).all()) if S >= M else 'n/a (S < 5)'))
 
@@ -132,6 +158,15 @@ def main():
         say('  S = %2d  %8.3f s  (%.2f GB/s of recording, %.3f ms per chunk)%s'
             % (S, s, T * H * W * 2 / s / 1e9, s * 1e3 / ((T + C - 1) // C),
                '  planted shifts recovered: %s' % bool((res[0] == -offs).all()) if S >= M else ''))
+
+    def run_blocks():
+        t = time.perf_counter()
+        res[:] = [estimate_shifts_device(path, template=tmpl, max_shift=8, chunk_frames=C, blocks=(By, Bx), max_dev=D)[0]]
+        return time.perf_counter() - t
+    res = []
+    s = median_of(run_blocks)
+    say('  S =  8, blocks %dx%d, D = %d  %8.3f s  (%.2f GB/s of recording, %.3f ms per chunk)  block shifts equal the planted rigid ones: %s'
+        % (By, Bx, D, s, T * H * W * 2 / s / 1e9, s * 1e3 / ((T + C - 1) // C), bool((res[0] == -offs[:, None, None, :]).all())))
 
     say('(d) numpy, the same search on %d frames, scaled to a chunk of %d:' % (args.host_frames, C))
     for S in (4, 8, 16):
