@@ -19,6 +19,8 @@
 //              per tile: 108 MFMAs.  The two slices are summed through LDS at the end, one slab per workgroup.
 // Numerics: those of igemm_f16x3.hip / wgrad_f16x3.hip (split-fp16 operands, power-of-two range-guard scales undone in
 // the epilogues, fp32 accumulation); the summation order differs from the separate kernels (tile shape), same tolerance.
+// bwd_joint32_kernel<true> (d0b under the head): da = kd (x) s has rank one -- the producers load s (4 bytes per pixel) and form da.
+#include <type_traits>
 #include "wgrad_common.h"
 #include "f16x3_common.h"
 
@@ -31,6 +33,7 @@
 struct JointParams {
   const float* x; const float* xSc; const float* xSh; const float* xAbound;
   const float* da; const float* z; const float* dzCoef;
+  const float* s; const float* kh;      // rank-one da (bwd_joint32_kernel<true>): da[pix][c] = (kh[c][1] - kh[c][0]) * s[pix], da unused
   const float* wp;
   float* dx;
   const float* redZ; const float* redMean; const float* redInvstd; const float* redGamma; const float* redBeta;
@@ -87,40 +90,67 @@ __device__ __forceinline__ bool halo_pixel(const JointParams& p, const Tile& tl,
 
 // The dz producer: thread t of the 256 holds channel quad q = t & 7 of the pixels pb + 32 k, pb = t >> 3 -- its rows of
 // dc_bn_bwd_finalize_dzin's table, the (da, z) request and the dz image of a stage.
-struct DzProducer {
+// R1 (rank-one da: the block under the head, whose gradient is kd (x) s): the request reads the pixel's s (one dword, the same
+// address in the eight lanes of a pixel) instead of its da row and stage() forms da = kd[c] * s, ONE rounding as the head's store
+// (head_bwd_pixel, elementwise.hip), before dc_dz_on_load: bit for bit the dz of the materialised da.
+template <bool R1>
+struct DzProducerT {
+  using Ra = typename std::conditional<R1, float, f32x4>::type;      // what a pixel's request of da brings
   int q, pb;
   f32x4 sc, sh, mu, A, D, E;
-  __device__ __forceinline__ DzProducer(const float* coef, int t) : q(t & 7), pb(t >> 3) {
+  f32x4 kd;                                                           // R1: kh[c][1] - kh[c][0] of this thread's channel quad (head_lane)
+  __device__ __forceinline__ DzProducerT(const float* coef, int t, const float* kh = nullptr) : q(t & 7), pb(t >> 3) {
     const float* ct = coef + 4 * q;
     sc = *reinterpret_cast<const f32x4*>(ct); sh = *reinterpret_cast<const f32x4*>(ct + C);
     mu = *reinterpret_cast<const f32x4*>(ct + 2 * C); A = *reinterpret_cast<const f32x4*>(ct + 3 * C);
     D = *reinterpret_cast<const f32x4*>(ct + 4 * C); E = *reinterpret_cast<const f32x4*>(ct + 5 * C);
+    kd = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (R1) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) kd[e] = kh[(4 * q + e) * 2 + 1] - kh[(4 * q + e) * 2];
+    }
   }
   // live: bit k = pixel pb + 32 k lies inside the image (the x request of the same tile asks for the same pixels)
-  __device__ __forceinline__ void request(const JointParams& p, const Tile& tl, f32x4 (&ra)[NL], f32x4 (&rz)[NL], unsigned& live) const {
+  __device__ __forceinline__ void request(const JointParams& p, const Tile& tl, Ra (&ra)[NL], f32x4 (&rz)[NL], unsigned& live) const {
     live = 0u;
-    const long img_floats = (long)p.H * p.W * C;
-    const __amdgpu_buffer_rsrc_t rsA = dc_make_rsrc(p.da + tl.img * img_floats, (unsigned)(img_floats * 4));
+    const long img_floats = (long)p.H * p.W * C, img_pixels = (long)p.H * p.W;
+    const __amdgpu_buffer_rsrc_t rsA = R1 ? dc_make_rsrc(p.s + tl.img * img_pixels, (unsigned)(img_pixels * 4))
+                                          : dc_make_rsrc(p.da + tl.img * img_floats, (unsigned)(img_floats * 4));
     const __amdgpu_buffer_rsrc_t rsZ = dc_make_rsrc(p.z + tl.img * img_floats, (unsigned)(img_floats * 4));
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
       int y, xx;
       const bool ok = halo_pixel(p, tl, pb + 32 * k, y, xx);
       const unsigned off = ok ? (unsigned)(((y * p.W + xx) * C + 4 * q) * 4) : OOB;
-      ra[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
+      if constexpr (R1) {
+        // the pixel's byte offset in s from the SAME select as the row offset (pixel * 128 + 16 q -> pixel * 4): plain ALU, so the
+        // request stays the straight-line code of the materialised variant (a second select was compiled into branches around
+        // the loads, with full vmcnt drains).  OOB >> 5 = 2^26 lies behind any image this kernel serves (H * W * 4 < 2^26).
+        const unsigned offs = (off >> 5) & ~3u;
+        ra[k] =__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsA, offs, 0, 0));
+      } else {
+        ra[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
+      }
       rz[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsZ, off, 0, 0));
       if (ok) live |= 1u << k;
     }
   }
-  __device__ __forceinline__ void stage(const f32x4 (&ra)[NL], const f32x4 (&rz)[NL], unsigned live, float dz_scale, char* set) const {
+  __device__ __forceinline__ void stage(const Ra (&ra)[NL], const f32x4 (&rz)[NL], unsigned live, float dz_scale, char* set) const {
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
       const int pix = pb + 32 * k;
       const bool lv = (live >> k) & 1u;
+      f32x4 dav;
+      if constexpr (R1) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dav[e] = __fmul_rn(kd[e], ra[k]);      // rounds on its own: never fused into dz's fma
+      } else {
+        dav = ra[k];
+      }
       f32x4 dzv;
 #pragma unroll
       for (int e = 0; e < 4; ++e)         // outside the image dz is zero, not E - D*mu
-        dzv[e] = lv ? dc_dz_on_load(rz[k][e], ra[k][e], sc[e], sh[e], mu[e], A[e], D[e], E[e]) : 0.f;
+        dzv[e] = lv ? dc_dz_on_load(rz[k][e], dav[e], sc[e], sh[e], mu[e], A[e], D[e], E[e]) : 0.f;
       u32x2 dh, dl;
       dc_split_f16(dzv, dz_scale, dh, dl);
       if (pix < NPIX) {
@@ -131,6 +161,7 @@ struct DzProducer {
     }
   }
 };
+using DzProducer = DzProducerT<false>;
 
 // The producers' schedule over two LDS stages of STAGE_BYTES.  x: two register sets (tile t+2 in flight while t+1 is split);
 // (da, z): one set, requested right after the previous tile's has been split -- one tile of MFMA time ahead (wgrad_f16x3.hip's
@@ -213,6 +244,7 @@ __device__ __forceinline__ void wgrad_tile(const char* cur, int lx, int lz, f32x
 }
 }  // namespace bj
 
+template <bool R1>
 __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams p) {
   using namespace bj;
   extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -232,14 +264,15 @@ __global__ __launch_bounds__(bj::THREADS, 1) void bwd_joint32_kernel(JointParams
 
   if (wave >= 4) {
     // ============================ producers: HBM -> registers -> the two fp16 hi/lo images =============================
-    const DzProducer dzp(p.dzCoef, tid & 255);
+    const DzProducerT<R1> dzp(p.dzCoef, tid & 255, p.kh);
     const int q = dzp.q, pb = dzp.pb;                              // x: the same channel quad and pixels as dz
     const bool xbn = p.xSc != nullptr;
     f32x4 x_sc = {1.f, 1.f, 1.f, 1.f}, x_sh = {0.f, 0.f, 0.f, 0.f};
     if (xbn) { x_sc = *reinterpret_cast<const f32x4*>(p.xSc + 4 * q); x_sh = *reinterpret_cast<const f32x4*>(p.xSh + 4 * q); }
     // the image positions of this thread's NL pixels are recomputed per request
     // (registers: the two x sets + one (da, z) set + the per-channel tables are what the producers hold)
-    f32x4 rx0[NL], rx1[NL], ra[NL], rz[NL];
+    f32x4 rx0[NL], rx1[NL], rz[NL];
+    typename DzProducerT<R1>::Ra ra[NL];
     unsigned live = 0u;                                           // of the tile whose (da, z) are in ra, rz: the one staged next
     auto request_x = [&](int j, f32x4 (&rx)[NL]) __attribute__((always_inline)) {
       const Tile tl = decode(p, tiles, j);
@@ -630,34 +663,37 @@ extern "C" long dc_conv3x3_bwd_joint_ws_floats(int N, int H, int W, int Cin, int
   const long L = 9L * Cin * Cout;
   return (long)joint_grid(N, H, W) * L + 32 * L;
 }
-extern "C" int dc_conv3x3_bwd_joint_f16x3(const float* x, const float* in_sc, const float* in_sh, const float* x_abound,
-                                          const float* da, const float* z, const float* dz_coef, const void* wp16, float* dx,
-                                          const float* red_z, const float* red_mean, const float* red_invstd,
-                                          const float* red_gamma, const float* red_beta, float* bn_partial,
-                                          float* amax_partial, float* dw, float* ws, int N, int H, int W, int Cin, int Cout,
-                                          dc_stream_t stream) {
-  DC_REQUIRE(x && da && z && dz_coef && wp16 && dx && dw && ws, DC_EINVAL, "dc_conv3x3_bwd_joint_f16x3: null pointer");
+// da materialised (s == kh == NULL) or rank one (da == NULL: da[pix][c] = (kh[c][1] - kh[c][0]) * s[pix], 32 -> 32 only)
+static int joint_launch(const char* fn, const float* x, const float* in_sc, const float* in_sh, const float* x_abound,
+                        const float* da, const float* s, const float* kh, const float* z, const float* dz_coef, const void* wp16,
+                        float* dx, const float* red_z, const float* red_mean, const float* red_invstd, const float* red_gamma,
+                        const float* red_beta, float* bn_partial, float* amax_partial, float* dw, float* ws, int N, int H, int W,
+                        int Cin, int Cout, dc_stream_t stream) {
+  const bool r1 = da == nullptr;
+  DC_REQUIRE(x && (r1 ? (s && kh) : true) && z && dz_coef && wp16 && dx && dw && ws, DC_EINVAL, "%s: null pointer", fn);
   DC_REQUIRE(dc_aligned16(x) && dc_aligned16(da) && dc_aligned16(z) && dc_aligned16(dz_coef) && dc_aligned16(wp16) && dc_aligned16(dx),
-             DC_EINVAL, "dc_conv3x3_bwd_joint_f16x3: pointers must be 16-byte aligned");
+             DC_EINVAL, "%s: pointers must be 16-byte aligned", fn);
   DC_REQUIRE((in_sc == nullptr) == (in_sh == nullptr) && (!in_sc || (dc_aligned16(in_sc) && dc_aligned16(in_sh))), DC_EINVAL,
-             "dc_conv3x3_bwd_joint_f16x3: in_scale / in_shift go together, 16-byte aligned");
+             "%s: in_scale / in_shift go together, 16-byte aligned", fn);
   DC_REQUIRE(red_z == nullptr || (red_mean && red_invstd && red_gamma && red_beta && bn_partial), DC_EINVAL,
-             "dc_conv3x3_bwd_joint_f16x3: red_z needs red_mean / red_invstd / red_gamma / red_beta / bn_partial");
-  DC_REQUIRE(joint_serves(N, H, W, Cin, Cout), DC_EUNSUP,
-             "dc_conv3x3_bwd_joint_f16x3: shape not served (dc_conv3x3_bwd_joint_blocks() == 0): use the separate kernels");
+             "%s: red_z needs red_mean / red_invstd / red_gamma / red_beta / bn_partial", fn);
+  DC_REQUIRE(joint_serves(N, H, W, Cin, Cout) && (!r1 || Cin == bj::C), DC_EUNSUP,
+             "%s: shape not served (dc_conv3x3_bwd_joint_blocks() == 0): use the separate kernels", fn);
   const int grid = joint_grid(N, H, W);
-  DC_REQUIRE(grid > 0, DC_EHIP, "dc_conv3x3_bwd_joint_f16x3: no device");
-  static DcLdsAttr lds_attr, lds_attr64;
+  DC_REQUIRE(grid > 0, DC_EHIP, "%s: no device", fn);
+  static DcLdsAttr lds_attr, lds_attr_r1, lds_attr64;
   if (Cin == bj::C) {
-    if (int rc = dc_func_max_lds(lds_attr, reinterpret_cast<const void*>(bwd_joint32_kernel), bj::LDS_BYTES, "conv3x3_bwd_joint_f16x3"))
+    if (int rc = r1 ? dc_func_max_lds(lds_attr_r1, reinterpret_cast<const void*>(bwd_joint32_kernel<true>), bj::LDS_BYTES, fn)
+                    : dc_func_max_lds(lds_attr, reinterpret_cast<const void*>(bwd_joint32_kernel<false>), bj::LDS_BYTES, fn))
       return rc;
   } else {
-    DC_REQUIRE(!in_sc && !red_z, DC_EUNSUP, "dc_conv3x3_bwd_joint_f16x3: the 64 -> 32 kernel takes a materialised x and emits no sums");
-    if (int rc = dc_func_max_lds(lds_attr64, reinterpret_cast<const void*>(bwd_joint64_kernel), bj64::LDS64, "conv3x3_bwd_joint_f16x3"))
+    DC_REQUIRE(!in_sc && !red_z, DC_EUNSUP, "%s: the 64 -> 32 kernel takes a materialised x and emits no sums", fn);
+    if (int rc = dc_func_max_lds(lds_attr64, reinterpret_cast<const void*>(bwd_joint64_kernel), bj64::LDS64, fn))
       return rc;
   }
   JointParams p;
   p.x = x; p.xSc = in_sc; p.xSh = in_sh; p.xAbound = x_abound; p.da = da; p.z = z; p.dzCoef = dz_coef;
+  p.s = s; p.kh = kh;
   p.wp = reinterpret_cast<const float*>(wp16); p.dx = dx;
   p.redZ = red_z; p.redMean = red_mean; p.redInvstd = red_invstd; p.redGamma = red_gamma; p.redBeta = red_beta;
   p.bnPartial = bn_partial; p.bnAmax = amax_partial; p.slabs = ws;
@@ -665,12 +701,36 @@ extern "C" int dc_conv3x3_bwd_joint_f16x3(const float* x, const float* in_sc, co
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   const bool bracket = dc_take_bracket(&ev0, &ev1);          // dc_bracket_next_launch: the matrix kernel without the slab reduction
   if (bracket && ev0) (void)hipEventRecord(ev0, (hipStream_t)stream);
-  if (Cin == bj::C)
-    hipLaunchKernelGGL(bwd_joint32_kernel, dim3((unsigned)grid), dim3(bj::THREADS), bj::LDS_BYTES, (hipStream_t)stream, p);
+  if (Cin == bj::C && r1)
+    hipLaunchKernelGGL(bwd_joint32_kernel<true>, dim3((unsigned)grid), dim3(bj::THREADS), bj::LDS_BYTES, (hipStream_t)stream, p);
+  else if (Cin == bj::C)
+    hipLaunchKernelGGL(bwd_joint32_kernel<false>, dim3((unsigned)grid), dim3(bj::THREADS), bj::LDS_BYTES, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(bwd_joint64_kernel, dim3((unsigned)grid), dim3(bj::THREADS), bj64::LDS64, (hipStream_t)stream, p);
   if (bracket && ev1) (void)hipEventRecord(ev1, (hipStream_t)stream);
-  DC_CHECK_LAUNCH("dc_conv3x3_bwd_joint_f16x3");
+  DC_CHECK_LAUNCH(fn);
   const long L = 9L * Cin * Cout;
   return dc_reduce_partials(ws, grid, L, 1.0f, dw, ws + (long)grid * L, stream);
+}
+extern "C" int dc_conv3x3_bwd_joint_f16x3(const float* x, const float* in_sc, const float* in_sh, const float* x_abound,
+                                          const float* da, const float* z, const float* dz_coef, const void* wp16, float* dx,
+                                          const float* red_z, const float* red_mean, const float* red_invstd,
+                                          const float* red_gamma, const float* red_beta, float* bn_partial,
+                                          float* amax_partial, float* dw, float* ws, int N, int H, int W, int Cin, int Cout,
+                                          dc_stream_t stream) {
+  DC_REQUIRE(da, DC_EINVAL, "dc_conv3x3_bwd_joint_f16x3: null pointer");
+  return joint_launch("dc_conv3x3_bwd_joint_f16x3", x, in_sc, in_sh, x_abound, da, nullptr, nullptr, z, dz_coef, wp16, dx, red_z,
+                      red_mean, red_invstd, red_gamma, red_beta, bn_partial, amax_partial, dw, ws, N, H, W, Cin, Cout, stream);
+}
+// the block under the head (dcunet.h): da given by its rank-one factors (s from dc_head_fwd_bwd_s / dc_head_bwd_bnin_bnred_s, kh)
+extern "C" int dc_conv3x3_bwd_joint_r1_f16x3(const float* x, const float* in_sc, const float* in_sh, const float* x_abound,
+                                             const float* s, const float* kh, const float* z, const float* dz_coef,
+                                             const void* wp16, float* dx, const float* red_z, const float* red_mean,
+                                             const float* red_invstd, const float* red_gamma, const float* red_beta,
+                                             float* bn_partial, float* amax_partial, float* dw, float* ws, int N, int H, int W,
+                                             int Cin, int Cout, dc_stream_t stream) {
+  DC_REQUIRE(s && kh, DC_EINVAL, "dc_conv3x3_bwd_joint_r1_f16x3: null pointer");
+  DC_REQUIRE(Cin == bj::C, DC_EUNSUP, "dc_conv3x3_bwd_joint_r1_f16x3: Cin = Cout = 32 only");
+  return joint_launch("dc_conv3x3_bwd_joint_r1_f16x3", x, in_sc, in_sh, x_abound, nullptr, s, kh, z, dz_coef, wp16, dx, red_z,
+                      red_mean, red_invstd, red_gamma, red_beta, bn_partial, amax_partial, dw, ws, N, H, W, Cin, Cout, stream);
 }

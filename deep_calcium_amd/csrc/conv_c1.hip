@@ -205,6 +205,22 @@ __device__ __forceinline__ void c1_window(const float* __restrict__ xi, int y, i
   }
 }
 
+// The pre-BatchNorm output z of pixel i (0..3) of a thread's window for its channel quad: the bias, then the nine taps in row-major
+// order, every step an EXPLICIT fused multiply-add.  The forward writes this value and the weight gradient's recompute mode
+// rebuilds it from the same window: both must round alike whatever the compiler would contract on its own.
+__device__ __forceinline__ f32x4 c1_pixel_z(const float (&win)[3][6], int i, const f32x4 (&w)[9], const f32x4& b) {
+  f32x4 v = b;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const float xv = win[dy][i + dx];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(xv, w[dy * 3 + dx][e], v[e]);
+    }
+  return v;
+}
+
 __global__ __launch_bounds__(256) void conv_c1_fwd4_kernel(C1Params p) {
   const int C4 = p.Cout >> 2, PPB = 256 / C4;
   const int tid = threadIdx.x, q = tid % C4, pl = tid / C4;
@@ -265,11 +281,7 @@ __global__ __launch_bounds__(256) void conv_c1_fwd4_kernel(C1Params p) {
     const long pix0 = (long)g * 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      f32x4 v = b;
-#pragma unroll
-      for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) v += win[dy][i + dx] * w[dy * 3 + dx];
+      f32x4 v = c1_pixel_z(win, i, w, b);
       a.add_shifted(v);
       if (p.scale) v = v * sc + sh;
       if (p.relu) {
@@ -282,32 +294,66 @@ __global__ __launch_bounds__(256) void conv_c1_fwd4_kernel(C1Params p) {
   c1_finish(p, a, tid, q, pl, C4, PPB);
 }
 
-template <bool DZIN>
-__global__ __launch_bounds__(256) void conv_c1_wgrad4_kernel(const float* __restrict__ x, const float* __restrict__ dz,
-                                                             float* __restrict__ partial, int N, int H, int W, int Cout,
-                                                             long pixels, const float* __restrict__ zt,
-                                                             const float* __restrict__ coef) {
+// ZRE (with DZIN): z is not read -- the thread rebuilds it from the window it holds anyway, as the forward computed it
+// (c1_pixel_z; zw / zb = the forward's kernel and bias): 9 fused multiply-adds per element instead of a tensor pass.
+template <bool DZIN, bool ZRE>
+__device__ __forceinline__ void c1_wgrad4_body(const float* __restrict__ x, const float* __restrict__ dz,
+                                               float* __restrict__ partial, int N, int H, int W, int Cout, long pixels,
+                                               const float* __restrict__ zt, const float* __restrict__ coef,
+                                               const float* __restrict__ zw, const float* __restrict__ zb) {
   __shared__ f32x4 sm[256];
   const int C4 = Cout >> 2, PPB = 256 / C4;
   const int tid = threadIdx.x, q = tid % C4, pl = tid / C4;
   C1Dz cz;
   if constexpr (DZIN) cz.load(coef, Cout, q);
+  f32x4 fw[ZRE ? 9 : 1], fb = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (ZRE) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) fw[t] = ld4(zw + t * Cout + 4 * q);
+    if (zb) fb = ld4(zb + 4 * q);
+  }
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 acc[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = z4;
   const int W4 = W >> 2, HW4 = H * W4;
   const int groups = (int)(pixels >> 2);
-  for (int g = blockIdx.x * PPB + pl; g < groups; g += gridDim.x * PPB) {
+  // a group's image window and its four da (dz) rows
+  auto request = [&](int g, float (&win)[3][6], f32x4 (&gz)[4]) __attribute__((always_inline)) {
     const int img = g / HW4, rem = g - img * HW4;
     const int y = rem / W4, x0 = (rem - y * W4) * 4;
-    float win[3][6];
     c1_window(x + (long)img * H * W, y, x0, H, W, win);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) gz[i] = ld4(dz + ((long)g * 4 + i) * Cout + 4 * q);
+  };
+  // ZRE: the NEXT group's loads are issued before this group's arithmetic (27 fused multiply-adds per element and half the bytes
+  // of the z-reading mode per wave: without the prefetch the sweep waits out every load's latency)
+  float nwin[ZRE ? 3 : 1][6];
+  f32x4 ngz[ZRE ? 4 : 1];
+  if constexpr (ZRE) {
+    const int g0 = blockIdx.x * PPB + pl;
+    if (g0 < groups) request(g0, nwin, ngz);
+  }
+  for (int g = blockIdx.x * PPB + pl; g < groups; g += gridDim.x * PPB) {
+    float win[3][6];
     const long pix0 = (long)g * 4;
     f32x4 gz[4];
+    if constexpr (ZRE) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) gz[i] = ld4(dz + (pix0 + i) * Cout + 4 * q);
-    if constexpr (DZIN) {
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 6; ++dx) win[dy][dx] = nwin[dy][dx];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) gz[i] = ngz[i];
+      const int gn = g + gridDim.x * PPB;
+      if (gn < groups) request(gn, nwin, ngz);
+    } else {
+      request(g, win, gz);
+    }
+    if constexpr (DZIN && ZRE) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) gz[i] = cz.dz(gz[i], c1_pixel_z(win, i, fw, fb));
+    } else if constexpr (DZIN) {
       f32x4 zz[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) zz[i] = ld4(zt + (pix0 + i) * Cout + 4 * q);
@@ -332,6 +378,20 @@ __global__ __launch_bounds__(256) void conv_c1_wgrad4_kernel(const float* __rest
     }
     __syncthreads();
   }
+}
+
+template <bool DZIN>
+__global__ __launch_bounds__(256) void conv_c1_wgrad4_kernel(const float* __restrict__ x, const float* __restrict__ dz,
+                                                             float* __restrict__ partial, int N, int H, int W, int Cout,
+                                                             long pixels, const float* __restrict__ zt,
+                                                             const float* __restrict__ coef) {
+  c1_wgrad4_body<DZIN, false>(x, dz, partial, N, H, W, Cout, pixels, zt, coef, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void conv_c1_wgrad4_zre_kernel(const float* __restrict__ x, const float* __restrict__ da,
+                                                                 float* __restrict__ partial, int N, int H, int W, int Cout,
+                                                                 long pixels, const float* __restrict__ coef,
+                                                                 const float* __restrict__ zw, const float* __restrict__ zb) {
+  c1_wgrad4_body<true, true>(x, da, partial, N, H, W, Cout, pixels, nullptr, coef, zw, zb);
 }
 
 static int c1_blocks(long pixels, int Cout) {
@@ -409,4 +469,29 @@ int dc_conv3x3_c1_wgrad_dzin(const float* x, const float* da, const float* z, co
   DC_CHECK_LAUNCH("dc_conv3x3_wgrad_dzin(Cin=1)");
   const long L = 9L * Cout;
   return dc_reduce_partials(ws, blocks, L, 1.0f, dw, ws + (long)blocks * L, (dc_stream_t)st);
+}
+
+// The same with z REBUILT from the image: z = conv3x3(x, w) + bias exactly as dc_conv3x3_c1_fwd wrote it (no scale / shift / relu,
+// the training forward), so the z tensor is not read.  The 4-pixel kernel only: W % 4 == 0 and a 16-byte aligned image.
+extern "C" int dc_conv3x3_c1_wgrad_dzin_zre(const float* x, const float* w, const float* bias, const float* da,
+                                            const float* dz_coef, float* dw, float* ws, int N, int H, int W, int Cout,
+                                            dc_stream_t stream) {
+  DC_REQUIRE(x && w && da && dz_coef && dw && ws, DC_EINVAL, "dc_conv3x3_c1_wgrad_dzin_zre: null pointer");
+  DC_REQUIRE(dc_aligned16(w) && dc_aligned16(da) && dc_aligned16(dz_coef) && (!bias || dc_aligned16(bias)), DC_EINVAL,
+             "dc_conv3x3_c1_wgrad_dzin_zre: w / bias / da / dz_coef must be 16-byte aligned");
+  int rc = check_c1("dc_conv3x3_c1_wgrad_dzin_zre", N, H, W, Cout);
+  if (rc) return rc;
+  const long pixels = (long)N * H * W;
+  DC_REQUIRE((W % 4 == 0) && dc_aligned16(x) && pixels < (1L << 31), DC_EUNSUP,
+             "dc_conv3x3_c1_wgrad_dzin_zre: needs W %% 4 == 0 and a 16-byte aligned image (use dc_conv3x3_wgrad_dzin_f16x3)");
+  const int blocks = c1_blocks(pixels, Cout);
+  hipStream_t st = (hipStream_t)stream;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  const bool bracket = dc_take_bracket(&ev0, &ev1);          // dc_bracket_next_launch
+  if (bracket && ev0) (void)hipEventRecord(ev0, st);
+  hipLaunchKernelGGL(conv_c1_wgrad4_zre_kernel, dim3(blocks), dim3(256), 0, st, x, da, ws, N, H, W, Cout, pixels, dz_coef, w, bias);
+  if (bracket && ev1) (void)hipEventRecord(ev1, st);
+  DC_CHECK_LAUNCH("dc_conv3x3_c1_wgrad_dzin_zre");
+  const long L = 9L * Cout;
+  return dc_reduce_partials(ws, blocks, L, 1.0f, dw, ws + (long)blocks * L, stream);
 }

@@ -970,6 +970,9 @@ struct HeadParams {
   float* p;                             // class-1 probability: the forward writes it, head_bwd_kernel reads it
   float* partial;                       // [blocks][DC_HEAD_SUMS] metric sums (nullable in the forward-only kernel)
   float* da; float* gpartial;           // backward: dL/da and the [blocks][C+4] weight / bias gradient partials
+  // da == NULL ("s mode"): da = kd (x) s has rank one, so only the per-pixel factor s = dL/dlogit1 is written ([pixels], once per
+  // pixel) and the consumer forms kd[c] * s on load (bwd_joint.hip); the sums below are the same either way
+  float* s;
   int loss_kind; const double* sums;    // sums: the reduced forward sums loss kinds 2 and 3 need
   // in_sc != NULL: the activation relu(fmaf(z, sc, sh)) is formed on load
   const float* in_sc; const float* in_sh;
@@ -1122,7 +1125,7 @@ __device__ __forceinline__ void head_bwd_pixel(const HeadParams& hp, const HeadL
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
   }
-  st4(hp.da + pix * hp.C + 4 * q, L.kd * s);
+  if (hp.da) st4(hp.da + pix * hp.C + 4 * q, L.kd * s);
   g.sa += v * s;
   if (q == 0) g.ss += s;
 }
@@ -1193,6 +1196,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadParams hp) {
         if constexpr (BWD) {
           sown = head_dlogit(hp.loss_kind == 0 ? 0 : 1, pr, yt, L.invM, 0.f, 1.f, 1.f);
           smax = fmaxf(smax, fabsf(sown));
+          if (hp.s) hp.s[kpix] = sown;
         }
       }
     }
@@ -1240,6 +1244,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadParams hp) {
   for (long pix = (long)blockIdx.x * PPB + pl; pix < hp.pixels; pix += (long)gridDim.x * PPB) {
     const float s = head_dlogit(hp.loss_kind, hp.p[pix], (float)hp.y[pix], L.invM, I, D, invD2);
     head_bwd_pixel(hp, L, q, pix, ld4(hp.a + pix * hp.C + 4 * q), s, g);
+    if (hp.s && q == 0) hp.s[pix] = s;
     smax = fmaxf(smax, fabsf(s));
   }
   head_bwd_epilogue(hp, L, g, smax, C4, q, pl);
@@ -1299,13 +1304,13 @@ extern "C" int dc_head_fwd_bnin(const float* z, const float* in_scale, const flo
 static int head_bwd_impl(const float* a, const float* in_sc, const float* in_sh, const float* p, const uint8_t* y,
                          const float* kh, float* da, float* partial, int loss_kind, const double* sums, long pixels,
                          int C, dc_stream_t stream, const float* bn_mean, const float* bn_invstd, float* bn_partial,
-                         float* amax_partial) {
-  DC_REQUIRE(a && p && y && kh && da && partial && pixels > 0, DC_EINVAL, "dc_head_bwd: bad arguments");
+                         float* amax_partial, float* s_out = nullptr) {
+  DC_REQUIRE(a && p && y && kh && (da || s_out) && partial && pixels > 0, DC_EINVAL, "dc_head_bwd: bad arguments");
   DC_REQUIRE(loss_kind >= 0 && loss_kind <= 3 && (loss_kind < 2 || sums), DC_EINVAL, "dc_head_bwd: bad loss_kind / sums");
   int rc = chan_check("dc_head_bwd", C);
   if (rc) return rc;
   HeadParams hp{};
-  hp.a = a; hp.in_sc = in_sc; hp.in_sh = in_sh; hp.p = const_cast<float*>(p); hp.y = y; hp.kh = kh; hp.da = da;
+  hp.a = a; hp.in_sc = in_sc; hp.in_sh = in_sh; hp.p = const_cast<float*>(p); hp.y = y; hp.kh = kh; hp.da = da; hp.s = s_out;
   hp.gpartial = partial; hp.loss_kind = loss_kind; hp.sums = sums; hp.bn_mean = bn_mean; hp.bn_invstd = bn_invstd;
   hp.bn_partial = bn_partial; hp.amax_partial = amax_partial; hp.pixels = pixels; hp.C = C;
   hipLaunchKernelGGL(head_bwd_kernel, dim3(head_blocks(pixels)), dim3(256), 0, (hipStream_t)stream, hp);
@@ -1332,26 +1337,52 @@ extern "C" int dc_head_bwd_bnin_bnred(const float* z, const float* in_scale, con
   return head_bwd_impl(z, in_scale, in_shift, p, y, kh, da, partial, loss_kind, sums, pixels, C, stream, bn_mean,
                        bn_invstd, bn_partial, amax_partial);
 }
+// exactly one of (da, s_out): the materialised gradient or its per-pixel factor
+static int head_fwd_bwd_impl(const char* fn, const float* a, const float* in_scale, const float* in_shift, const float* kh,
+                             const float* bh, const uint8_t* y, float* p, float* partial, float* da, float* s_out,
+                             float* grad_partial, int loss_kind, const float* bn_mean, const float* bn_invstd,
+                             float* bn_partial, float* amax_partial, long pixels, int C, dc_stream_t stream) {
+  DC_REQUIRE(a && kh && bh && y && p && partial && (da || s_out) && grad_partial && pixels > 0, DC_EINVAL, "%s: bad arguments", fn);
+  DC_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), DC_EINVAL, "%s: in_scale and in_shift go together", fn);
+  DC_REQUIRE(loss_kind == 0 || loss_kind == 1, DC_EUNSUP,
+             "%s: loss_kind %d needs the global sums first (use dc_head_fwd + dc_head_bwd)", fn, loss_kind);
+  DC_REQUIRE(!bn_partial || (in_scale && bn_mean && bn_invstd), DC_EINVAL, "%s: bn_partial needs in_scale / bn_mean / bn_invstd", fn);
+  int rc = chan_check(fn, C);
+  if (rc) return rc;
+  DC_REQUIRE(C <= 64, DC_EUNSUP, "%s: C=%d > 64 (the C/4 lanes of a pixel group must divide a wave)", fn, C);
+  HeadParams hp{};
+  hp.a = a; hp.in_sc = in_scale; hp.in_sh = in_shift; hp.kh = kh; hp.bh = bh; hp.y = y; hp.p = p; hp.partial = partial;
+  hp.da = da; hp.s = s_out; hp.gpartial = grad_partial; hp.loss_kind = loss_kind; hp.bn_mean = bn_mean; hp.bn_invstd = bn_invstd;
+  hp.bn_partial = bn_partial; hp.amax_partial = amax_partial; hp.pixels = pixels; hp.C = C;
+  hipLaunchKernelGGL((C == 32 ? head_fwd_kernel<8, true> : head_fwd_kernel<0, true>), dim3(head_blocks(pixels)), dim3(256), 0,
+                     (hipStream_t)stream, hp);
+  DC_CHECK_LAUNCH(fn);
+  return DC_OK;
+}
 extern "C" int dc_head_fwd_bwd(const float* a, const float* in_scale, const float* in_shift, const float* kh,
                                const float* bh, const uint8_t* y, float* p, float* partial, float* da, float* grad_partial,
                                int loss_kind, const float* bn_mean, const float* bn_invstd, float* bn_partial,
                                float* amax_partial, long pixels, int C, dc_stream_t stream) {
-  DC_REQUIRE(a && kh && bh && y && p && partial && da && grad_partial && pixels > 0, DC_EINVAL, "dc_head_fwd_bwd: bad arguments");
-  DC_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), DC_EINVAL, "dc_head_fwd_bwd: in_scale and in_shift go together");
-  DC_REQUIRE(loss_kind == 0 || loss_kind == 1, DC_EUNSUP,
-             "dc_head_fwd_bwd: loss_kind %d needs the global sums first (use dc_head_fwd + dc_head_bwd)", loss_kind);
-  DC_REQUIRE(!bn_partial || (in_scale && bn_mean && bn_invstd), DC_EINVAL, "dc_head_fwd_bwd: bn_partial needs in_scale / bn_mean / bn_invstd");
-  int rc = chan_check("dc_head_fwd_bwd", C);
-  if (rc) return rc;
-  DC_REQUIRE(C <= 64, DC_EUNSUP, "dc_head_fwd_bwd: C=%d > 64 (the C/4 lanes of a pixel group must divide a wave)", C);
-  HeadParams hp{};
-  hp.a = a; hp.in_sc = in_scale; hp.in_sh = in_shift; hp.kh = kh; hp.bh = bh; hp.y = y; hp.p = p; hp.partial = partial;
-  hp.da = da; hp.gpartial = grad_partial; hp.loss_kind = loss_kind; hp.bn_mean = bn_mean; hp.bn_invstd = bn_invstd;
-  hp.bn_partial = bn_partial; hp.amax_partial = amax_partial; hp.pixels = pixels; hp.C = C;
-  hipLaunchKernelGGL((C == 32 ? head_fwd_kernel<8, true> : head_fwd_kernel<0, true>), dim3(head_blocks(pixels)), dim3(256), 0,
-                     (hipStream_t)stream, hp);
-  DC_CHECK_LAUNCH("dc_head_fwd_bwd");
-  return DC_OK;
+  DC_REQUIRE(da, DC_EINVAL, "dc_head_fwd_bwd: bad arguments");
+  return head_fwd_bwd_impl("dc_head_fwd_bwd", a, in_scale, in_shift, kh, bh, y, p, partial, da, nullptr, grad_partial, loss_kind,
+                           bn_mean, bn_invstd, bn_partial, amax_partial, pixels, C, stream);
+}
+// "s mode" (dcunet.h): the per-pixel factor s of da = kd (x) s instead of da
+extern "C" int dc_head_fwd_bwd_s(const float* a, const float* in_scale, const float* in_shift, const float* kh,
+                                 const float* bh, const uint8_t* y, float* p, float* partial, float* s, float* grad_partial,
+                                 int loss_kind, const float* bn_mean, const float* bn_invstd, float* bn_partial,
+                                 float* amax_partial, long pixels, int C, dc_stream_t stream) {
+  DC_REQUIRE(s, DC_EINVAL, "dc_head_fwd_bwd_s: bad arguments");
+  return head_fwd_bwd_impl("dc_head_fwd_bwd_s", a, in_scale, in_shift, kh, bh, y, p, partial, nullptr, s, grad_partial, loss_kind,
+                           bn_mean, bn_invstd, bn_partial, amax_partial, pixels, C, stream);
+}
+extern "C" int dc_head_bwd_bnin_bnred_s(const float* z, const float* in_scale, const float* in_shift, const float* p,
+                                        const uint8_t* y, const float* kh, float* s, float* partial, int loss_kind,
+                                        const double* sums, const float* bn_mean, const float* bn_invstd,
+                                        float* bn_partial, float* amax_partial, long pixels, int C, dc_stream_t stream) {
+  DC_REQUIRE(s && in_scale && in_shift && bn_mean && bn_invstd && bn_partial, DC_EINVAL, "dc_head_bwd_bnin_bnred_s: null pointer");
+  return head_bwd_impl(z, in_scale, in_shift, p, y, kh, nullptr, partial, loss_kind, sums, pixels, C, stream, bn_mean,
+                       bn_invstd, bn_partial, amax_partial, s);
 }
 extern "C" int dc_head_grad_finalize(const float* partial, int blocks, int C, float* dkh, float* dbh, dc_stream_t stream) {
   DC_REQUIRE(partial && dkh && dbh && blocks > 0 && C > 0, DC_EINVAL, "dc_head_grad_finalize: bad arguments");

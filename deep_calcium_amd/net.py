@@ -292,6 +292,13 @@ class UNetEngine(object):
         # measured SLOWER same box (17.651 -> 18.103 ms: the role-split kernel's producers become its longest role, as for DC_DZIN=all)
         self.dz_writeback = False
         self.deep_slots = False           # A/B (set before the first step): one backward buffer set per block instead of a rotation of 3
+        # the first layer's dz-on-load weight gradient rebuilds its pre-BN output z from the image window it holds instead of reading
+        # the 512^2 x nfb tensor back (dc_conv3x3_c1_wgrad_dzin_zre: bit-identical, one tensor pass less; A/B: False)
+        self.c1_z_on_load = True
+        # the head's activation gradient da(d0b) = kd (x) s has rank one: where d0b's backward runs on the 32 -> 32 joint kernel the head
+        # writes only the per-pixel factor s and that kernel forms kd[c] * s on load (dc_head_*_s, dc_conv3x3_bwd_joint_r1_f16x3:
+        # bit-identical, the 512^2 x nfb tensor is neither written nor read; A/B: False)
+        self.head_rank1 = True
         self.tail_main = os.environ.get('DC_TAIL_MAIN', '1') == '1'      # the step's last weight gradient on the main stream (A/B: 0)
         self.stats_per_wg = True          # BatchNorm partials: one row per (workgroup, consumer set) of the role-split kernel (A/B: False)
         self.use_tapes = os.environ.get('DC_TAPES', '1') != '0'
@@ -491,7 +498,7 @@ class UNetEngine(object):
     # these drops every tape (they bake in the control flow AND raw device pointers), and so does any allocation path that
     # can move a buffer a tape points into (buf() regrow, set_crop_sources, a new side stream).
     _TAPE_STATE = frozenset(('range_guard', 'bnin', 'dzin', 'dzin_lvls', 'dzin_all', 'joint', 'stats_per_wg', 'tail_main',
-                             'dz_writeback', 'deep_slots', 'FOLD_MIN', 'bn_mode', 'streams', 'mfma', 'upsampling', 'up_drop',
+                             'dz_writeback', 'deep_slots', 'c1_z_on_load', 'head_rank1', 'FOLD_MIN', 'bn_mode', 'streams', 'mfma', 'upsampling', 'up_drop',
                              'infer_measured', 'SLOTS', 'SLOTS_DEEP', 'SLOTS_DEEP_MAX_BYTES', '_side_stream', 'nm', 'use_tapes',
                              'ar_buckets'))
 
@@ -973,6 +980,7 @@ class UNetEngine(object):
         T['amax_ws'] = torch.empty(part_floats // 2 + 4, dtype=torch.float32, device=dev)
         T['amax_ws2'] = torch.empty(part_floats // 2 + 4, dtype=torch.float32, device=dev)
         T['head_gpart'] = torch.empty(hb * (nfb + 4), dtype=torch.float32, device=dev)
+        T['head_s'] = torch.empty(N * self.H * self.W, dtype=torch.float32, device=dev)      # per-pixel dL/dlogit1 (head_rank1)
         # per dz buffer: the apply pass' per-block max |dz| and conv-bias-gradient partials (read by the finalize launch on the
         # weight-gradient stream and by the data gradient: they rotate with the dz buffer they describe)
         big = N * self.H * self.W * nfb
@@ -1222,11 +1230,13 @@ class UNetEngine(object):
             a_in, sc_in, sh_in = (hsrc[0], hsrc[1][0], hsrc[1][1]) if hsrc is not None else (_ptr(A['d0b']), None, None)
             ld0 = self.by_name['d0b']
             red = hsrc is not None
-            L.dc_head_fwd_bwd(a_in, sc_in, sh_in, self.pview(self.pflat, lo, 'k'), self.pview(self.pflat, lo, 'b'),
-                              yp, _ptr(A['p']), _ptr(T['part_ws']), _ptr(T['g'][0]), _ptr(T['head_gpart']),
-                              self.loss_kind, self.stat_ptr(ld0, 0) if red else None, self.stat_ptr(ld0, 1) if red else None,
-                              _ptr(T['part_ws2']) if red else None, _ptr(T['amax_ws2']) if red else None, pixels, self.nfb, st)
-            self._head_bwd_done = True
+            s_mode = self._head_s_ok(N)       # d0b's joint backward forms da = kd * s on load: write s, not g[0]
+            head = L.dc_head_fwd_bwd_s if s_mode else L.dc_head_fwd_bwd
+            head(a_in, sc_in, sh_in, self.pview(self.pflat, lo, 'k'), self.pview(self.pflat, lo, 'b'),
+                 yp, _ptr(A['p']), _ptr(T['part_ws']), _ptr(T['head_s'] if s_mode else T['g'][0]), _ptr(T['head_gpart']),
+                 self.loss_kind, self.stat_ptr(ld0, 0) if red else None, self.stat_ptr(ld0, 1) if red else None,
+                 _ptr(T['part_ws2']) if red else None, _ptr(T['amax_ws2']) if red else None, pixels, self.nfb, st)
+            self._head_bwd_done = 's' if s_mode else True      # (part of the backward's tape key)
         elif hsrc is not None:
             L.dc_head_fwd_bnin(hsrc[0], hsrc[1][0], hsrc[1][1], self.pview(self.pflat, lo, 'k'),
                                self.pview(self.pflat, lo, 'b'), yp, _ptr(A['p']), _ptr(T['part_ws']),
@@ -1242,6 +1252,20 @@ class UNetEngine(object):
         encoder (flat layout = Keras get_weights order: encoder, bottleneck, decoder, head)."""
         o_ba, o_dec = self.by_name['ba'].off['k'][0], self.layers[10].off['k'][0]
         return [(o_dec, self.n_train), (o_ba, o_dec), (0, o_ba)]
+
+    def _head_s_ok(self, N):
+        """Will block d0b's backward of an N-image step go through the 32 -> 32 joint kernel?  Then its `da` -- the head's rank-one
+        kd (x) s -- is formed there on load (dc_conv3x3_bwd_joint_r1_f16x3) and the head kernels write s instead of g[0].  The
+        conditions are block_bwd's own for that block; everywhere else g[0] is written as ever."""
+        l = self.by_name['d0b']
+        if not (self.head_rank1 and self.joint and self.mfma == 'f16x3' and l.cin == 32 and l.cout == 32):
+            return False
+        if l.name not in self.nm:             # a materialised d0b: its pass-1 sums come from dc_bn_bwd_reduce, which reads da
+            return False
+        if self._dzin_ok(l, N) != 1:
+            return False
+        h, w = self._hw(l.lvl)
+        return self.L.dc_conv3x3_bwd_joint_blocks(N, h, w, l.cin, l.cout) > 0
 
     def _dzin_ok(self, l, N):
         """Does block l run without the BatchNorm-backward apply pass?  0: no (finalize -> apply -> gradients);
@@ -1324,17 +1348,23 @@ class UNetEngine(object):
         gb = T['g']
         fused_d0b = None          # (partial ptr, amax ptr, rows): pass-1 sums of d0b already produced by the head kernel
         gpart = T['part_ws']
-        if self._head_bwd_done:   # forward_train's fused head kernel has written g[0], the gradient partials and the sums
+        head_s = None             # (s, kh): the head wrote the per-pixel factor of its rank-one gradient instead of g[0] (head_rank1)
+        if self._head_bwd_done:   # forward_train's fused head kernel has written g[0] (or s), the gradient partials and the sums
+            if self._head_bwd_done == 's':
+                head_s = (_ptr(T['head_s']), self.pview(self.pflat, lo, 'k'))
             self._head_bwd_done = False
             gpart = T['head_gpart']
             if hsrc is not None:
                 fused_d0b = (_ptr(T['part_ws2']), _ptr(T['amax_ws2']), hb)
         elif hsrc is not None:
             ld0 = self.by_name['d0b']
-            L.dc_head_bwd_bnin_bnred(hsrc[0], hsrc[1][0], hsrc[1][1], _ptr(A['p']), yp,
-                                     self.pview(self.pflat, lo, 'k'), _ptr(gb[0]), _ptr(T['part_ws']), self.loss_kind,
-                                     T['sums'].data_ptr(), self.stat_ptr(ld0, 0), self.stat_ptr(ld0, 1),
-                                     _ptr(T['part_ws2']), _ptr(T['amax_ws2']), pixels0, nfb, st)
+            if self._head_s_ok(N):
+                head_s = (_ptr(T['head_s']), self.pview(self.pflat, lo, 'k'))
+            head = L.dc_head_bwd_bnin_bnred_s if head_s else L.dc_head_bwd_bnin_bnred
+            head(hsrc[0], hsrc[1][0], hsrc[1][1], _ptr(A['p']), yp,
+                 self.pview(self.pflat, lo, 'k'), head_s[0] if head_s else _ptr(gb[0]), _ptr(T['part_ws']), self.loss_kind,
+                 T['sums'].data_ptr(), self.stat_ptr(ld0, 0), self.stat_ptr(ld0, 1),
+                 _ptr(T['part_ws2']), _ptr(T['amax_ws2']), pixels0, nfb, st)
             fused_d0b = (_ptr(T['part_ws2']), _ptr(T['amax_ws2']), hb)
         else:
             L.dc_head_bwd(_ptr(A['d0b']), _ptr(A['p']), yp, self.pview(self.pflat, lo, 'k'),
@@ -1370,13 +1400,14 @@ class UNetEngine(object):
         def red_of(la):          # pass-1 sums out of the data gradient's epilogue: dense da of a dropout-free layer only
             return la if la.drop <= 0.0 else None
 
-        def block_bwd(l, x_in, da_ptr, da_ld, dx_ptr, prod=None, fused=None, red=None, da_g=None, on_main=False):
+        def block_bwd(l, x_in, da_ptr, da_ld, dx_ptr, prod=None, fused=None, red=None, da_g=None, on_main=False, r1=None):
             """da (da_ld-strided) -> gradients of block l; dx (dense [.., cin]) written to dx_ptr unless None.  prod: the
             layer that produced x_in (its activation may be non-materialised: BN + ReLU on load).  fused: (partial, amax,
             rows) when the producer of da emitted the pass-1 sums.  red: the layer whose `da` dx is -- when the data
             gradient runs on the role-split kernel it emits that layer's sums; returned for that layer's `fused`.
             da_g: index of the g buffer da lives in (None: a dcat buffer, written once per step).  on_main: the weight gradient
-            stays on the main stream (the step's last block: nothing is left to run beside it)."""
+            stays on the main stream (the step's last block: nothing is left to run beside it).  r1: (s, kh) when da is the
+            head's rank-one gradient and was NOT written to da_ptr: only the 32 -> 32 joint kernel can take it (_head_s_ok)."""
             two = two_streams and not on_main
             bsrc = self._bnin_src(prod, T)
             h, w = self._hw(l.lvl)
@@ -1435,10 +1466,18 @@ class UNetEngine(object):
                                  self.pview(self.pflat, red, 'gamma'), self.pview(self.pflat, red, 'beta'),
                                  _ptr(T['part_ws']), _ptr(T['amax_ws']))
                         fused_next = (_ptr(T['part_ws']), _ptr(T['amax_ws']), jrows)
-                    L.dc_conv3x3_bwd_joint_f16x3(xa[0], xa[1], xa[2], self._ab_in(l), da_ptr, _ptr(z), coef,
-                                                 _ptr(self.wp_dgrad[l.name]), dx_ptr, *rargs, dk, _ptr(T['joint_ws']),
-                                                 N, h, w, l.cin, l.cout, st)
+                    if r1 is not None:
+                        L.dc_conv3x3_bwd_joint_r1_f16x3(xa[0], xa[1], xa[2], self._ab_in(l), r1[0], r1[1], _ptr(z), coef,
+                                                        _ptr(self.wp_dgrad[l.name]), dx_ptr, *rargs, dk, _ptr(T['joint_ws']),
+                                                        N, h, w, l.cin, l.cout, st)
+                    else:
+                        L.dc_conv3x3_bwd_joint_f16x3(xa[0], xa[1], xa[2], self._ab_in(l), da_ptr, _ptr(z), coef,
+                                                     _ptr(self.wp_dgrad[l.name]), dx_ptr, *rargs, dk, _ptr(T['joint_ws']),
+                                                     N, h, w, l.cin, l.cout, st)
                     return fused_next
+                if r1 is not None:
+                    raise DcunetError('block %s: the head wrote its rank-one gradient factors but the joint kernel does not serve '
+                                      'the block (_head_s_ok and block_bwd disagree)' % l.name)
                 if dx_ptr is not None:
                     rargs = (None,) * 7
                     if red is not None:
@@ -1461,6 +1500,11 @@ class UNetEngine(object):
                                                       l.cin, l.cout, sw)
                     else:
                         L.dc_conv3x3_wgrad_f16x3(x_in, dzp, dk, ws, scale, self._ab_in(l), N, h, w, l.cin, l.cout, sw)
+                elif l.cin == 1 and self.c1_z_on_load and w % 4 == 0 and x_dev.data_ptr() % 16 == 0:
+                    # first layer: z is rebuilt from the image window the kernel holds anyway, not read back (batches are whole
+                    # images of a row length that is a multiple of 4: every batch pointer of a run is aligned alike)
+                    L.dc_conv3x3_c1_wgrad_dzin_zre(xa[0], self.pview(self.pflat, l, 'k'), self.pview(self.pflat, l, 'b'), da_ptr,
+                                                   coef, dk, ws, N, h, w, l.cout, sw)
                 else:
                     L.dc_conv3x3_wgrad_dzin_f16x3(xa[0], xa[1], xa[2], self._ab_in(l), da_ptr, _ptr(z), coef, dk, ws,
                                                   N, h, w, l.cin, l.cout, sw)
@@ -1472,6 +1516,9 @@ class UNetEngine(object):
                 return fused_next
 
             # ---- apply pass: dz is materialised (Dropout blocks, conv-transposes, shapes the dz-on-load kernels skip) ----
+            if r1 is not None:
+                raise DcunetError('block %s: the head wrote its rank-one gradient factors but the block takes the apply pass '
+                                  '(_head_s_ok and block_bwd disagree)' % l.name)
             dz, scale = _ptr(T['dz'][k]), _ptr(T['dz_scale'], 4 * k)
             dpart, amaxp = _ptr(T['dbias_part'][k]), _ptr(T['absmax'][k])
             blocks = L.dc_bn_bwd_blocks(pixels, l.cout)
@@ -1564,7 +1611,8 @@ class UNetEngine(object):
             la = self.by_name['d%da' % lvl]
             ki, ko = state['g'], g_next()
             fa = block_bwd(self.by_name['d%db' % lvl], _ptr(A['d%da' % lvl]), _ptr(gb[ki]), c, _ptr(gb[ko]),
-                           prod=la, fused=fused_d0b if lvl == 0 else fused_up, red=red_of(la), da_g=ki)
+                           prod=la, fused=fused_d0b if lvl == 0 else fused_up, red=red_of(la), da_g=ki,
+                           r1=head_s if lvl == 0 else None)
             state['g'] = ko
             block_bwd(la, _ptr(cat), _ptr(gb[ko]), c, _ptr(dcat), fused=fa, da_g=ko)
             x_up = A['bb'] if lvl == 3 else A['d%db' % (lvl + 1)]

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 113
+#define DC_ABI_VERSION 114
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -320,6 +320,14 @@ int dc_conv3x3_dgrad_dzin_f16x3(const float* da, const float* z, const float* dz
 int dc_conv3x3_wgrad_dzin_f16x3(const float* x, const float* in_scale, const float* in_shift, const float* x_abound,
                                 const float* da, const float* z, const float* dz_coef, float* dw, float* ws,
                                 int N, int H, int W, int Cin, int Cout, dc_stream_t stream);
+/* The first layer's (unet_2d_summary.py:170-172, Cin == 1) dz-on-load weight gradient WITHOUT the read of z: the thread that
+ * holds the 3 x 6 image window of its four pixels rebuilds z = conv3x3(x, w) + bias from it, bit for bit what
+ * dc_conv3x3_c1_fwd(x, w, bias, z, ..., scale = shift = NULL, relu = 0) wrote (one definition of that arithmetic, explicit
+ * fused multiply-adds), and forms dz from (da, that z, dz_coef): dw equals dc_conv3x3_wgrad_dzin_f16x3(Cin = 1)'s exactly,
+ * one full-resolution tensor pass less.  w: the layer's (3,3,1,Cout) kernel, bias nullable; ws as
+ * dc_conv3x3_wgrad_ws_floats(Cin = 1).  Serves the 4-pixel kernel only: W % 4 != 0 or an unaligned x -> DC_EUNSUP. */
+int dc_conv3x3_c1_wgrad_dzin_zre(const float* x, const float* w, const float* bias, const float* da, const float* dz_coef,
+                                 float* dw, float* ws, int N, int H, int W, int Cout, dc_stream_t stream);
 
 /* Joint backward of a conv block with 32 output channels at a 512^2-class resolution (the HBM-bound blocks of the network:
  * e0b / d0b, 32 -> 32, and d0a, 64 -> 32): ONE kernel stages dz (formed on load, as above) and the block input x once per
@@ -337,6 +345,17 @@ int dc_conv3x3_bwd_joint_f16x3(const float* x, const float* in_scale, const floa
                                const float* red_z, const float* red_mean, const float* red_invstd, const float* red_gamma,
                                const float* red_beta, float* bn_partial, float* amax_partial, float* dw, float* ws,
                                int N, int H, int W, int Cin, int Cout, dc_stream_t stream);
+/* The 32 -> 32 block right under the head (d0b, unet_2d_summary.py:219-222): its `da` is the head's dlogits.Kh^T, a rank-one
+ * tensor da[pix][c] = kd[c] * s[pix], kd[c] = kh[c][1] - kh[c][0], s = dL/dlogit1.  The head's "s mode" entry points
+ * (dc_head_fwd_bwd_s, dc_head_bwd_bnin_bnred_s) write s[pixels] instead of da[pixels][C]; this entry point takes (s, kh) in
+ * place of da and its producers form kd[c] * s (one rounding, as the head's store) on load: every output equals
+ * dc_conv3x3_bwd_joint_f16x3's on the materialised da bit for bit, and the tensor is neither written nor read.
+ * Cin = Cout = 32 only (DC_EUNSUP otherwise); the remaining arguments as dc_conv3x3_bwd_joint_f16x3. */
+int dc_conv3x3_bwd_joint_r1_f16x3(const float* x, const float* in_scale, const float* in_shift, const float* x_abound,
+                                  const float* s, const float* kh, const float* z, const float* dz_coef, const void* wp16,
+                                  float* dx, const float* red_z, const float* red_mean, const float* red_invstd,
+                                  const float* red_gamma, const float* red_beta, float* bn_partial, float* amax_partial,
+                                  float* dw, float* ws, int N, int H, int W, int Cin, int Cout, dc_stream_t stream);
 
 /* ---- synchronised BatchNorm for batch-sharded data parallelism ('sync' mode) ---------------------
  * The per-channel sums leave the device between two launches so the host can all-reduce them over the ranks:
@@ -403,6 +422,18 @@ int dc_head_fwd_bwd(const float* a, const float* in_scale, const float* in_shift
                     const uint8_t* y, float* p, float* partial, float* da, float* grad_partial, int loss_kind,
                     const float* bn_mean, const float* bn_invstd, float* bn_partial, float* amax_partial, long pixels,
                     int C, dc_stream_t stream);
+/* "s mode" of the two head backward kernels that feed a dz-on-load block (:221-222): da = dlogits.Kh^T has rank one, so only
+ * its per-pixel factor s[pixels] = dL/dlogit1 is written (da[pix][c] = (kh[c][1] - kh[c][0]) * s[pix], formed on load by
+ * dc_conv3x3_bwd_joint_r1_f16x3); p, the metric partials, the weight-gradient partials, bn_partial and amax_partial are those
+ * of dc_head_fwd_bwd / dc_head_bwd_bnin_bnred bit for bit.  No da argument: nothing of that size is touched. */
+int dc_head_fwd_bwd_s(const float* a, const float* in_scale, const float* in_shift, const float* kh, const float* bh,
+                      const uint8_t* y, float* p, float* partial, float* s, float* grad_partial, int loss_kind,
+                      const float* bn_mean, const float* bn_invstd, float* bn_partial, float* amax_partial, long pixels,
+                      int C, dc_stream_t stream);
+int dc_head_bwd_bnin_bnred_s(const float* z_in, const float* in_scale, const float* in_shift, const float* p,
+                             const uint8_t* y, const float* kh, float* s, float* partial, int loss_kind,
+                             const double* sums, const float* bn_mean, const float* bn_invstd, float* bn_partial,
+                             float* amax_partial, long pixels, int C, dc_stream_t stream);
 int dc_head_grad_finalize(const float* partial, int blocks, int C, float* dkh, float* dbh, dc_stream_t stream);
 
 /* ---- generic deterministic reductions ------------------------------------------

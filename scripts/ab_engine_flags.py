@@ -1,6 +1,8 @@
 """Same-box, same-process, interleaved A/B of an engine flag on the train step (two models of the same seed, alternating rounds):
     python scripts/ab_engine_flags.py stats_per_wg [window=512] [batch=16] [rounds=4] [steps=20]
-Prints ms/step per round for flag = False / True (the default)."""
+Prints ms/step per round for flag = False / True (the default).  Flags: any boolean engine attribute of UNetEngine._TAPE_STATE, e.g.
+stats_per_wg, tail_main, head_rank1 (the head writes s, d0b's joint backward forms da = kd * s on load), c1_z_on_load (the first
+layer's weight gradient rebuilds z from the image window)."""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
