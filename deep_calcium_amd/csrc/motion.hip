@@ -6,6 +6,8 @@
 // as (dy, dx) = (-a, -b).
 // Piecewise-rigid on top of it: per block of a By x Bx grid the rigid shift plus a residual within +-D (dc_motion_block_ssd,
 // dc_motion_block_pick), blended into one whole-pixel shift per pixel (dc_motion_warp).
+// Sub-pixel on top of both: every pick refined to a sixteenth of a pixel from the scores next to it (dc_motion_refine,
+// dc_motion_block_refine) and the frames interpolated bilinearly with integer weights (dc_motion_apply_sub, dc_motion_warp_sub).
 #include "common.h"
 #include "motion_math.h"
 
@@ -242,6 +244,134 @@ __global__ __launch_bounds__(kThreads) void motion_apply_kernel(const uint16_t* 
   }
 }
 
+// ---- sub-pixel: refine, interpolate (the definitions are in include/dcunet.h, the arithmetic in motion_math.h) ---------------------
+// One thread per frame: the pick's neighbours on both axes, five scores of a table the pick kernel has just read.
+__global__ __launch_bounds__(kThreads) void motion_refine_kernel(const int64_t* __restrict__ scores, const int* __restrict__ shifts, int tc,
+                                                                int S, int* __restrict__ fine) {
+  const long n = (2 * S + 1) * (2 * S + 1);
+  for (int f = blockIdx.x * kThreads + threadIdx.x; f < tc; f += gridDim.x * kThreads) {
+    const int dy = shifts[2 * f], dx = shifts[2 * f + 1];
+    const DcSubShift q = dc_motion_refine_entry(scores + f * n, S, dy, dx);
+    fine[2 * f] = dc_motion_fine(dy, q.qy);
+    fine[2 * f + 1] = dc_motion_fine(dx, q.qx);
+  }
+}
+
+// One thread per (frame, block): the residual the block pick added to the frame's clamped rigid shift, refined in the block's table.
+__global__ __launch_bounds__(kThreads) void motion_block_refine_kernel(const int64_t* __restrict__ bscores, const int* __restrict__ rigid,
+                                                                      const int* __restrict__ block_shifts, long items, int nblk, int S,
+                                                                      int D, int* __restrict__ fine) {
+  const long n = (2 * D + 1) * (2 * D + 1);
+  for (long it = (long)blockIdx.x * kThreads + threadIdx.x; it < items; it += (long)gridDim.x * kThreads) {
+    const long f = it / nblk;
+    const int by = block_shifts[2 * it], bx = block_shifts[2 * it + 1];
+    const int64_t ey = (int64_t)by - dc_motion_clamp(rigid[2 * f], S), ex = (int64_t)bx - dc_motion_clamp(rigid[2 * f + 1], S);
+    DcSubShift q;
+    q.qy = q.qx = 0;
+    if (ey >= -D && ey <= D && ex >= -D && ex <= D) q = dc_motion_refine_entry(bscores + it * n, D, (int)ey, (int)ex);
+    fine[2 * it] = dc_motion_fine(by, q.qy);
+    fine[2 * it + 1] = dc_motion_fine(bx, q.qx);
+  }
+}
+
+// One output value at the split fine shift: source (sy, sx) = (y + iy, x + ix), weights (fy, fx).  flip: 0x8000 for int16 (the
+// interpolation commutes with adding 32768 to every tap).
+__device__ __forceinline__ uint16_t sub1(const uint16_t* __restrict__ f, long sy, long sx, int fy, int fx, int H, int W, unsigned flip,
+                                         unsigned fill) {
+  if (sy < 0 || sx < 0 || sy + (fy > 0) >= H || sx + (fx > 0) >= W) return (uint16_t)fill;
+  const uint16_t* p = f + sy * W + sx;
+  const int a00 = (int)(p[0] ^ flip), a01 = fx ? (int)(p[1] ^ flip) : 0;
+  const int a10 = fy ? (int)(p[W] ^ flip) : 0, a11 = (fy && fx) ? (int)(p[W + 1] ^ flip) : 0;
+  return (uint16_t)((unsigned)dc_motion_interp(a00, a01, a10, a11, fy, fx) ^ flip);
+}
+
+// 8 (nine: 9) consecutive values from any 2-byte address p, out of the 4 or 5 aligned dwords that hold them: n[0 .. 3] = values
+// 0 .. 7 in pairs, the low half of n[4] = value 8.  The fifth dword is read only where it holds one of the values asked for (as in
+// move8: an aligned dword that holds one value of the buffer lies inside the buffer's pages).
+__device__ __forceinline__ void run9(const uint16_t* __restrict__ p, bool nine, unsigned (&n)[5]) {
+  const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
+  const unsigned* q = reinterpret_cast<const unsigned*>(addr & ~(uintptr_t)3);
+  const unsigned w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];
+  if (addr & 2) {
+    const unsigned w4 = q[4];
+    n[0] = (w0 >> 16) | (w1 << 16); n[1] = (w1 >> 16) | (w2 << 16); n[2] = (w2 >> 16) | (w3 << 16); n[3] = (w3 >> 16) | (w4 << 16);
+    n[4] = w4 >> 16;
+  } else {
+    n[0] = w0; n[1] = w1; n[2] = w2; n[3] = w3;
+    n[4] = nine ? q[4] : 0u;
+  }
+}
+
+// 8 output values of one row that share a split fine shift, o 16-byte aligned: one store of the 8 interpolations between the source
+// rows sy and (fy > 0) sy + 1, columns sx .. sx + 7 and (fx > 0) sx + 8 -- or of fill where all 8 use a tap outside the frame.  The
+// rows' runs start at any 2-byte address each (run9).  false (nothing stored) where the runs straddle the frame's left or right edge.
+__device__ __forceinline__ bool sub8(const uint16_t* __restrict__ f, long sy, long sx, int fy, int fx, int H, int W, unsigned flip,
+                                     unsigned fill2, uint16_t* __restrict__ o) {
+  const int ny = fy > 0, nx = fx > 0;
+  uint4 v;
+  if (sy < 0 || sy + ny >= H || sx + 8 <= 0 || sx + nx >= W) {
+    v = make_uint4(fill2, fill2, fill2, fill2);
+  } else if (sx >= 0 && sx + 8 + nx <= W) {
+    const unsigned flip2 = flip | (flip << 16);
+    unsigned r0[5], r1[5] = {0u, 0u, 0u, 0u, 0u};
+    run9(f + sy * W + sx, nx, r0);
+    if (ny) run9(f + (sy + 1) * W + sx, nx, r1);           // uniform over the frame
+    int a[9], b[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      a[i] = (int)(((r0[i / 2] ^ flip2) >> (16 * (i & 1))) & 0xffffu);
+      b[i] = (int)(((r1[i / 2] ^ flip2) >> (16 * (i & 1))) & 0xffffu);
+    }
+    unsigned r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned lo = (unsigned)dc_motion_interp(a[2 * i], a[2 * i + 1], b[2 * i], b[2 * i + 1], fy, fx);
+      const unsigned hi = (unsigned)dc_motion_interp(a[2 * i + 1], a[2 * i + 2], b[2 * i + 1], b[2 * i + 2], fy, fx);
+      r[i] = (lo | (hi << 16)) ^ flip2;
+    }
+    v = make_uint4(r[0], r[1], r[2], r[3]);
+  } else {
+    return false;
+  }
+  *reinterpret_cast<uint4*>(o) = v;
+  return true;
+}
+
+// out[t][y][x] = the bilinear interpolation of frames[t] at the fine shift fine[t] (include/dcunet.h), fill where a used tap lies
+// outside the frame.  The shape of motion_apply_kernel: a thread produces 8 consecutive outputs, the groups cut at multiples of 8
+// elements of the WHOLE output, so a group that lies in one row is one aligned 16-byte store; its source is two runs of 9 values,
+// one per source row, each out of its own aligned dwords.  The split and the weights are uniform over the frame.  Groups that
+// cross a row, a frame or the source's edge go value by value.
+__global__ __launch_bounds__(kThreads) void motion_apply_sub_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
+                                                                   const int* __restrict__ fine, int H, int W, unsigned fill,
+                                                                   uint16_t* __restrict__ out, int wide) {
+  const int HW = H * W;
+  const unsigned fill2 = fill | (fill << 16);
+  for (int t = blockIdx.y; t < tc; t += gridDim.y) {
+    const int s0 = fine[2 * t], s1 = fine[2 * t + 1];
+    const long iy = dc_motion_floor16(s0), ix = dc_motion_floor16(s1);
+    const int fy = dc_motion_frac16(s0), fx = dc_motion_frac16(s1);
+    const long base = (long)t * HW;
+    const int off = (int)(base & 7);
+    const int groups = (HW + off + 7) / 8;
+    const uint16_t* f = frames + base;
+    uint16_t* o = out + base;
+    for (int g = blockIdx.x * kThreads + threadIdx.x; g < groups; g += gridDim.x * kThreads) {
+      const int e0 = g * 8 - off;
+      const int a = e0 < 0 ? 0 : e0, b = e0 + 8 < HW ? e0 + 8 : HW;
+      int y = a / W, x = a - y * W;
+      bool done = false;
+      if (wide && b - a == 8 && x + 8 <= W) done = sub8(f, y + iy, x + ix, fy, fx, H, W, flip, fill2, o + a);
+      if (!done) {
+        for (int e = a; e < b; ++e) {
+          o[e] = sub1(f, y + iy, x + ix, fy, fx, H, W, flip, fill);
+          if (++x == W) { x = 0; ++y; }
+        }
+      }
+    }
+  }
+}
+
 // ---- piecewise-rigid: block scores, block pick, warp (the definitions are in include/dcunet.h, the arithmetic in motion_math.h) ----
 const int kBlkLanesX = 16;                                     // lanes of a wave along x
 const int kBlkR = 4;                                           // rows a lane owns
@@ -365,9 +495,12 @@ const int kWarpCols = 1024;            // its columns, at most
 // A thread moves 8 consecutive outputs of one row, cut at multiples of 8 elements of the WHOLE output as in motion_apply_kernel:
 // where the field is the same at all 8 (compared one by one: along a row it is monotone between two centres only) the group is
 // that kernel's aligned 16-byte store from 4 or 5 aligned source dwords; otherwise it goes value by value.
+// SUB (dc_motion_warp_sub): bs holds FINE block shifts, so the field is a fine shift per pixel; it is split, and the group is sub8's
+// aligned store where all 8 share it, sub1 value by value otherwise (flip: as for motion_apply_sub_kernel; unused without SUB).
+template <bool SUB>
 __global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* __restrict__ frames, int tc, const int* __restrict__ bs,
                                                               int By, int Bx, int H, int W, unsigned fill, uint16_t* __restrict__ out,
-                                                              int wide, int tilesX) {
+                                                              int wide, int tilesX, unsigned flip) {
   __shared__ int ctap[kWarpCols];                        // j0 | v << 8 (j1 = j0 + 1 where v > 0)
   __shared__ int rtap[kWarpRows];                        // i0 | w << 8
   __shared__ int64_t a[kWarpRows][DC_MOTION_MAX_BLOCKS][2];
@@ -435,6 +568,20 @@ __global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* _
       }
       uint16_t* o = out + lo;
       bool done = false;
+      if constexpr (SUB) {
+        // the field never leaves the int32 range of the block shifts
+        if (wide && n == 8 && same)
+          done = sub8(f, (long)y + dc_motion_floor16((int)fy[0]), (long)x + dc_motion_floor16((int)fx[0]), dc_motion_frac16((int)fy[0]),
+                      dc_motion_frac16((int)fx[0]), H, W, flip, fill2, o);
+        if (!done) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            if (k < n)
+              o[k] = sub1(f, (long)y + dc_motion_floor16((int)fy[k]), (long)x + k + dc_motion_floor16((int)fx[k]), dc_motion_frac16((int)fy[k]),
+                          dc_motion_frac16((int)fx[k]), H, W, flip, fill);
+          }
+        }
+      } else {
       if (wide && n == 8 && same) done = move8(f, y + fy[0], x + fx[0], H, W, fill2, o);
       if (!done) {
 #pragma unroll
@@ -444,6 +591,7 @@ __global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* _
             o[k] = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? f[sy * W + sx] : (uint16_t)fill;
           }
         }
+      }
       }
     }
   }
@@ -590,8 +738,79 @@ extern "C" int dc_motion_warp(const void* frames, int tc, const int* block_shift
   const int tilesX = dc_cdiv(W, kWarpCols);
   const long tiles = (long)tilesX * dc_cdiv(H, kWarpRows);              // H * W <= 2^30: at most 2^30 tiles
   const dim3 grid((unsigned)tiles, (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(motion_warp_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, block_shifts, By, Bx, H, W,
-                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0), tilesX);
+  hipLaunchKernelGGL(motion_warp_kernel<false>, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, block_shifts, By, Bx, H, W,
+                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0), tilesX, 0u);
   DC_CHECK_LAUNCH("dc_motion_warp");
+  return DC_OK;
+}
+
+extern "C" int dc_motion_refine(const long* scores, const int* shifts, int tc, int S, int* fine, dc_stream_t stream) {
+  DC_REQUIRE(scores && shifts && fine, DC_EINVAL, "dc_motion_refine: null pointer");
+  DC_REQUIRE(tc >= 0 && S >= 0, DC_EINVAL, "dc_motion_refine: negative size (tc %d, S %d)", tc, S);
+  DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, "dc_motion_refine: S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);
+  DC_REQUIRE((((uintptr_t)scores) & 7) == 0 && (((uintptr_t)shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL, "dc_motion_refine: misaligned buffer");
+  if (tc == 0) return DC_OK;
+  hipLaunchKernelGGL(motion_refine_kernel, dim3((unsigned)dc_cdiv(tc, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const int64_t*)scores, shifts, tc, S, fine);
+  DC_CHECK_LAUNCH("dc_motion_refine");
+  return DC_OK;
+}
+
+extern "C" int dc_motion_block_refine(const long* bscores, const int* rigid, const int* block_shifts, int tc, int By, int Bx, int S, int D,
+                                      int* fine, dc_stream_t stream) {
+  DC_REQUIRE(bscores && rigid && block_shifts && fine, DC_EINVAL, "dc_motion_block_refine: null pointer");
+  DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && By > 0 && Bx > 0, DC_EINVAL,
+             "dc_motion_block_refine: negative or zero size (tc %d, S %d, D %d, blocks %d x %d)", tc, S, D, By, Bx);
+  DC_REQUIRE_GRID("dc_motion_block_refine", S, D, By, Bx);
+  DC_REQUIRE((((uintptr_t)bscores) & 7) == 0 && (((uintptr_t)rigid | (uintptr_t)block_shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL,
+             "dc_motion_block_refine: misaligned buffer");
+  if (tc == 0) return DC_OK;
+  const long items = (long)tc * By * Bx, blocks = dc_cdiv(items, kThreads);
+  hipLaunchKernelGGL(motion_block_refine_kernel, dim3((unsigned)(blocks < (1L << 20) ? blocks : (1L << 20))), dim3(kThreads), 0,
+                     (hipStream_t)stream, (const int64_t*)bscores, rigid, block_shifts, items, By * Bx, S, D, fine);
+  DC_CHECK_LAUNCH("dc_motion_block_refine");
+  return DC_OK;
+}
+
+extern "C" int dc_motion_apply_sub(const void* frames, int is_unsigned, int tc, const int* fine, int H, int W, int fill, void* out,
+                                   dc_stream_t stream) {
+  DC_REQUIRE(frames && fine && out, DC_EINVAL, "dc_motion_apply_sub: null pointer");
+  DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_apply_sub: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_apply_sub: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, "dc_motion_apply_sub: fill = %d is not a 16-bit value", fill);
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)fine) & 3) == 0, DC_EINVAL, "dc_motion_apply_sub: misaligned buffer");
+  const uintptr_t bytes = (uintptr_t)tc * H * W * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
+  DC_REQUIRE(bytes == 0 || fa + bytes <= oa || oa + bytes <= fa, DC_EINVAL, "dc_motion_apply_sub: out overlaps frames");
+  if (tc == 0) return DC_OK;
+  const int groups = dc_cdiv((long)H * W + 7, 8);
+  const int bx = dc_cdiv(groups, kThreads);
+  const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
+  hipLaunchKernelGGL(motion_apply_sub_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, is_unsigned ? 0u : 0x8000u, tc, fine,
+                     H, W, (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0));
+  DC_CHECK_LAUNCH("dc_motion_apply_sub");
+  return DC_OK;
+}
+
+extern "C" int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, const int* fine_block_shifts, int By, int Bx, int H, int W,
+                                  int fill, void* out, dc_stream_t stream) {
+  DC_REQUIRE(frames && fine_block_shifts && out, DC_EINVAL, "dc_motion_warp_sub: null pointer");
+  DC_REQUIRE(tc >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL,
+             "dc_motion_warp_sub: negative or zero size (tc %d, H %d, W %d, blocks %d x %d)", tc, H, W, By, Bx);
+  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, "dc_motion_warp_sub: %d x %d blocks: the grid is limited to %d x %d",
+             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS);
+  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_warp_sub: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE(By <= H && Bx <= W, DC_EINVAL, "dc_motion_warp_sub: image %d x %d in %d x %d blocks: a block is empty", H, W, By, Bx);
+  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, "dc_motion_warp_sub: fill = %d is not a 16-bit value", fill);
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)fine_block_shifts) & 3) == 0, DC_EINVAL,
+             "dc_motion_warp_sub: misaligned buffer");
+  const uintptr_t bytes = (uintptr_t)tc * H * W * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
+  DC_REQUIRE(bytes == 0 || fa + bytes <= oa || oa + bytes <= fa, DC_EINVAL, "dc_motion_warp_sub: out overlaps frames");
+  if (tc == 0) return DC_OK;
+  const int tilesX = dc_cdiv(W, kWarpCols);
+  const long tiles = (long)tilesX * dc_cdiv(H, kWarpRows);
+  const dim3 grid((unsigned)tiles, (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
+  hipLaunchKernelGGL(motion_warp_kernel<true>, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, fine_block_shifts, By, Bx, H, W,
+                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0), tilesX, is_unsigned ? 0u : 0x8000u);
+  DC_CHECK_LAUNCH("dc_motion_warp_sub");
   return DC_OK;
 }

@@ -122,3 +122,79 @@ DC_MOTION_HD bool dc_field_delta_small(int64_t d) { return d > -(1 << 22) && d <
 DC_MOTION_HD int64_t dc_field_from_delta(int64_t a0, int d, int v) { return dc_floor_div_65536(256 * a0 + (int64_t)(v * d) + 32768); }
 
 DC_MOTION_HD int dc_motion_clamp(int v, int S) { return v < -S ? -S : (v > S ? S : v); }
+
+// ---- sub-pixel correction (motion.hip, dc_motion_refine / dc_motion_apply_sub / dc_motion_warp_sub): FINE shifts, int32 in units of
+// 1 / DC_MOTION_SUB of a pixel, same sign convention; 16 dy is exactly the whole-pixel shift dy.  Integers only.
+// (tests/native/motion_sub_check.cpp)
+#ifndef DC_MOTION_SUB
+#define DC_MOTION_SUB 16                 // include/dcunet.h defines the same value
+#endif
+
+// One axis of the refinement of a pick: s0 the picked score, sm and sp its neighbours at -1 and +1 on that axis.  The vertex of the
+// parabola through the three lies at N / (2 D) pixels from the pick, N = sm - sp, D = sm - 2 s0 + sp; in sixteenths, rounded to
+// the nearest with a tie at a half going to the pick:
+//   D == 0: q = 0;  otherwise m = floor((16 |N| + D - 1) / (2 D)),  q = sign(N) * m.
+// s0 is the minimum of the three, so D >= 0 and |N| <= D: q lies in [-8, 8].  A symmetric neighbourhood (sm == sp) gives 0,
+// sm == s0 < sp gives exactly -8, swapping sm and sp negates q (the mirror image of a table gives the mirrored q), and N = 1,
+// D = 16 -- half a sixteenth -- gives 0.
+// Scores go up to 2^62 - 1, so 16 |N| does not fit 64 bits and is never formed: 16 |N| = t D + r with 0 <= r < D comes from four
+// doubling steps of a long division (every intermediate is below 2 D <= 2^64 - 4), and then
+//   m = floor(((t + 1) D + r - 1) / (2 D)) = floor((t + 1) / 2) where r > 0, floor(t / 2) where r == 0.
+// Scores that are not those of a pick (s0 not the minimum; only a caller's own table can hold them) stay defined: D <= 0 gives 0,
+// |N| >= D gives +-8, and the differences wrap like unsigned arithmetic.
+DC_MOTION_HD int dc_motion_subpixel(int64_t sm, int64_t s0, int64_t sp) {
+  const int64_t N = (int64_t)((uint64_t)sm - (uint64_t)sp);
+  const int64_t D = (int64_t)(((uint64_t)sm - (uint64_t)s0) + ((uint64_t)sp - (uint64_t)s0));
+  if (D <= 0 || N == 0) return 0;
+  const uint64_t a = N < 0 ? 0ull - (uint64_t)N : (uint64_t)N, d = (uint64_t)D;
+  int m = DC_MOTION_SUB / 2;
+  if (a < d) {
+    uint64_t r = a;
+    int t = 0;
+    for (int i = 0; i < 4; ++i) {                        // 16 = 2^4
+      r <<= 1;
+      t <<= 1;
+      if (r >= d) { r -= d; t += 1; }
+    }
+    m = r ? (t + 1) / 2 : t / 2;
+  }
+  return N < 0 ? -m : m;
+}
+
+// (qy, qx) of the entry (py, px) of one [2R+1][2R+1] score table (py the slow axis, index py + R): per axis dc_motion_subpixel of
+// the entry and its two neighbours on that axis, the other axis held; 0 on an axis where the entry lies on the table's border.  An
+// entry outside [-R, R]^2 gives (0, 0) and reads nothing.
+struct DcSubShift {
+  int qy, qx;
+};
+DC_MOTION_HD DcSubShift dc_motion_refine_entry(const int64_t* table, int R, int py, int px) {
+  DcSubShift q;
+  q.qy = q.qx = 0;
+  if (py < -R || py > R || px < -R || px > R) return q;
+  const int nd = 2 * R + 1;
+  const int64_t* c = table + (py + R) * nd + (px + R);
+  if (py > -R && py < R) q.qy = dc_motion_subpixel(c[-nd], c[0], c[nd]);
+  if (px > -R && px < R) q.qx = dc_motion_subpixel(c[-1], c[0], c[1]);
+  return q;
+}
+
+// 16 * whole + q in wrapping 32-bit arithmetic (exact for |whole| < 2^27, which every searched shift is)
+DC_MOTION_HD int dc_motion_fine(int whole, int q) { return (int)((uint32_t)whole * (uint32_t)DC_MOTION_SUB + (uint32_t)q); }
+
+// The split of a fine shift s: i = floor(s / 16), f = s - 16 i in [0, 16), for either sign
+DC_MOTION_HD int dc_motion_floor16(int s) {
+  const int q = s / DC_MOTION_SUB;
+  return (s % DC_MOTION_SUB < 0) ? q - 1 : q;
+}
+DC_MOTION_HD int dc_motion_frac16(int s) { return (int)((int64_t)s - (int64_t)DC_MOTION_SUB * dc_motion_floor16(s)); }
+
+// Bilinear interpolation between four taps a_ij = frame[y + iy + i][x + ix + j], any values in [-32768, 65535]:
+//   out = floor(((16-fy) ((16-fx) a00 + fx a01) + fy ((16-fx) a10 + fx a11) + 128) / 256).
+// The weights are non-negative and add up to 256, so out lies between the smallest and the largest tap (it fits their dtype), equal
+// taps give that value, and adding a constant to all four adds it to out -- the kernels interpolate int16 values with the sign bit
+// flipped.  |numerator| < 2^25; the floor for either sign comes from shifting a numerator made positive by 2^15 * 256.
+DC_MOTION_HD int dc_motion_interp(int a00, int a01, int a10, int a11, int fy, int fx) {
+  const int gx = DC_MOTION_SUB - fx, gy = DC_MOTION_SUB - fy;
+  const int num = gy * (gx * a00 + fx * a01) + fy * (gx * a10 + fx * a11) + 128;
+  return ((num + (1 << 23)) >> 8) - (1 << 15);
+}

@@ -35,9 +35,30 @@ Where that field changes by one pixel a source pixel is repeated or skipped: the
 
     bs, template = estimate_shifts_device('dataset.hdf5', blocks=(4, 4))      # (T, By, Bx, 2): shifts= takes it as it is
 
-Scope: whole-pixel shifts found by exhaustive search, max_shift <= 16, max_dev <= 8, at most 32 x 32 blocks.  Sub-pixel shifts
-and interpolation of pixel values, template building with blocks, temporal smoothing of the shifts, FFT methods and larger
-search radii are not implemented.
+Sub-pixel (subpixel=True): every pick -- the frame's, and with blocks every block's -- is refined to a sixteenth of a pixel from
+the scores next to it (dc_motion_refine, dc_motion_block_refine: the vertex of the parabola through the picked score and its two
+neighbours, per axis), and the frames are interpolated bilinearly at the fine shift or the fine shift field (dc_motion_apply_sub,
+dc_motion_warp_sub).  Still integers only -- fine shifts are int32 in sixteenths, the interpolation weights are sixteenths:
+
+    what          dtype            exactness
+    fine shifts   int32 (t, 2)     exact: 16 * pick + q, q = sign(N) floor((16 |N| + D - 1) / (2 D)) in [-8, 8] per axis,
+                  (t, By, Bx, 2)   N = s(-1) - s(+1), D = s(-1) - 2 s(0) + s(+1); 0 at the table's border and where D = 0
+    corrected     the frames'      exact: floor(((16-fy) ((16-fx) a00 + fx a01) + fy ((16-fx) a10 + fx a11) + 128) / 256) with
+                                   (iy, fy) = divmod(sy, 16), a_ij = frame[y + iy + i, x + ix + j]; `fill` where a tap that
+                                   is used (weight > 0) lies outside the frame
+
+    mc = MotionCorrector((H, W), T, np.int16, template, max_shift=8, subpixel=True)
+    for chunk in chunks: corrected = mc.feed(chunk)        # interpolated
+    fine = mc.fine_shifts()                                # (fed, 2) int32 sixteenths; fine_to_pixels(fine) = fine / 16
+    fine, template = estimate_shifts_device('dataset.hdf5', subpixel=True)
+    img = summarize_series_device('dataset.hdf5', kind='corr', fine_shifts=fine)
+
+Interpolation averages up to four values, so at fractional shifts it lowers the pixel noise: `std` and `corr` of a
+sub-pixel-corrected recording are not comparable bit for bit with those of a whole-pixel-corrected one.
+
+Scope: shifts found by exhaustive whole-pixel search, max_shift <= 16, max_dev <= 8, at most 32 x 32 blocks, refined to 1/16
+pixel by a parabola fit, bilinear interpolation.  Template building with sub-pixel or block shifts, temporal smoothing of the
+shifts, FFT methods, other interpolation kernels and larger search radii are not implemented.
 
 Importing this module needs neither torch nor the GPU; constructing a MotionCorrector does (there is no CPU fallback).
 """
@@ -49,6 +70,7 @@ from .traces import _check_shape
 MAX_SHIFT = 16                        # DC_MOTION_MAX_SHIFT
 MAX_DEV = 8                           # DC_MOTION_MAX_DEV
 MAX_BLOCKS = 32                       # DC_MOTION_MAX_BLOCKS
+SUBPIXEL = 16                         # DC_MOTION_SUB: fine shifts are int32 in units of 1 / SUBPIXEL of a pixel
 
 
 def _check_max_shift(max_shift, shape=None):
@@ -95,6 +117,12 @@ def _check_blocks(blocks, max_dev, shape=None, max_shift=0):
     return By, Bx, D
 
 
+def _check_subpixel(subpixel):
+    if not isinstance(subpixel, (bool, np.bool_)):
+        raise ValueError('subpixel must be True or False, not %r' % (subpixel,))
+    return bool(subpixel)
+
+
 def _check_fill(fill):
     if isinstance(fill, bool) or not isinstance(fill, (int, np.integer)) or not -32768 <= int(fill) <= 65535:
         raise ValueError('fill must be a 16-bit integer value, not %r' % (fill,))
@@ -111,23 +139,37 @@ def _check_template(template, shape, dtype):
     return np.ascontiguousarray(template)
 
 
-def valid_rectangle(shifts, shape):
+def valid_rectangle(shifts, shape, fine=False):
     """((y0, y1), (x0, x1)): the rectangle every frame corrected by `shifts` (n, 2) covers with its own pixels,
     y in [max(0, -min dy), H - max(0, max dy)), likewise x.  Block shifts (n, By, Bx, 2) are taken one by one: the shift field
-    never leaves their range, so the rectangle bounds the warped frames too.  Host only."""
+    never leaves their range, so the rectangle bounds the warped frames too.  fine=True: `shifts` are fine shifts (sixteenths of a
+    pixel) and an interpolated pixel needs every tap it uses: y0 = max(0, -floor(min sy / 16)), y1 = H - max(0, ceil(max sy / 16)),
+    likewise x.  Host only."""
     H, W = shape
+    if not isinstance(fine, (bool, np.bool_)):
+        raise ValueError('fine must be True or False, not %r' % (fine,))
     s = np.asarray(shifts).reshape(-1, 2).astype(np.int64)
     if len(s) == 0:
         return (0, H), (0, W)
-    return ((max(0, -int(s[:, 0].min())), H - max(0, int(s[:, 0].max()))),
-            (max(0, -int(s[:, 1].min())), W - max(0, int(s[:, 1].max()))))
+    lo, hi = s.min(axis=0), s.max(axis=0)
+    if fine:
+        lo, hi = lo // SUBPIXEL, -((-hi) // SUBPIXEL)        # floor and ceiling for either sign
+    return ((max(0, -int(lo[0])), H - max(0, int(hi[0]))), (max(0, -int(lo[1])), W - max(0, int(hi[1]))))
+
+
+def fine_to_pixels(fine):
+    """Fine shifts (integers in sixteenths of a pixel, any shape) as float64 pixels: fine / 16, exact.  Host only."""
+    a = np.asarray(fine)
+    if a.dtype.kind not in 'iu':
+        raise ValueError('fine shifts are integers (sixteenths of a pixel), not %s' % a.dtype)
+    return a.astype(np.float64) / SUBPIXEL
 
 
 class MotionCorrector(object):
     """Owns the device state of one recording's registration; feed() the frames in order, in chunks of any size."""
 
     def __init__(self, shape, n_frames, dtype, template, max_shift=8, fill=0, device=None, chunk_frames=None, blocks=None,
-                 max_dev=3):
+                 max_dev=3, subpixel=False):
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         H, W = shape
@@ -137,6 +179,7 @@ class MotionCorrector(object):
         self.dtype = _frame_dtype(dtype)
         self.max_shift = _check_max_shift(max_shift, shape)
         self.fill = _check_fill(fill)
+        self.subpixel = _check_subpixel(subpixel)
         self.blocks, self.max_dev = None, None
         if blocks is not None:
             By, Bx, self.max_dev = _check_blocks(blocks, max_dev, shape, self.max_shift)
@@ -173,6 +216,8 @@ class MotionCorrector(object):
             (By, Bx), nb = self.blocks, 2 * self.max_dev + 1
             self._bshifts = torch.zeros((n_frames, By, Bx, 2), dtype=torch.int32, device=dev)
             self._bscores = torch.empty((self.chunk_frames, By, Bx, nb, nb), dtype=torch.int64, device=dev)
+        if self.subpixel:                  # the fine shifts (sixteenths) beside the whole-pixel picks they refine
+            self._fine = torch.zeros((n_frames, 2) if self.blocks is None else (n_frames,) + self.blocks + (2,), dtype=torch.int32, device=dev)
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
@@ -181,17 +226,27 @@ class MotionCorrector(object):
         """The launches of one piece of at most chunk_frames frames at fp; out: where the corrected frames go, or None."""
         H, W = self.shape
         L, S = self.L, self.max_shift
+        uns = int(self.dtype == np.dtype(np.uint16))
         rows = self._shifts.data_ptr() + 8 * self.fed
-        L.dc_motion_ssd(fp, int(self.dtype == np.dtype(np.uint16)), tc, self._tmpl.data_ptr(), H, W, S, self._scores.data_ptr(), st)
+        L.dc_motion_ssd(fp, uns, tc, self._tmpl.data_ptr(), H, W, S, self._scores.data_ptr(), st)
         L.dc_motion_pick(self._scores.data_ptr(), tc, S, rows, None, st)
         if self.blocks is not None:
             (By, Bx), D = self.blocks, self.max_dev
             brows = self._bshifts.data_ptr() + 8 * By * Bx * self.fed
-            L.dc_motion_block_ssd(fp, int(self.dtype == np.dtype(np.uint16)), tc, self._tmpl.data_ptr(), H, W, S, D, By, Bx, rows,
-                                  self._bscores.data_ptr(), st)
+            L.dc_motion_block_ssd(fp, uns, tc, self._tmpl.data_ptr(), H, W, S, D, By, Bx, rows, self._bscores.data_ptr(), st)
             L.dc_motion_block_pick(self._bscores.data_ptr(), rows, tc, By, Bx, S, D, brows, None, st)
-            if out is not None:
+            if self.subpixel:
+                frows = self._fine.data_ptr() + 8 * By * Bx * self.fed
+                L.dc_motion_block_refine(self._bscores.data_ptr(), rows, brows, tc, By, Bx, S, D, frows, st)
+                if out is not None:
+                    L.dc_motion_warp_sub(fp, uns, tc, frows, By, Bx, H, W, self.fill, out, st)
+            elif out is not None:
                 L.dc_motion_warp(fp, tc, brows, By, Bx, H, W, self.fill, out, st)
+        elif self.subpixel:
+            frows = self._fine.data_ptr() + 8 * self.fed
+            L.dc_motion_refine(self._scores.data_ptr(), rows, tc, S, frows, st)
+            if out is not None:
+                L.dc_motion_apply_sub(fp, uns, tc, frows, H, W, self.fill, out, st)
         elif out is not None:
             L.dc_motion_apply(fp, tc, rows, H, W, self.fill, out, st)
         self.fed += tc
@@ -203,7 +258,9 @@ class MotionCorrector(object):
         recording's bits (read in place).  Returns the corrected frames as a (t, H, W) torch.int16 tensor on the device (the
         frames' bits); their shifts land in rows [fed, fed + t) of shifts_device().  correct=False only estimates the shifts
         and returns None.  With blocks: the frames are warped by the shift field, and their block shifts land in rows
-        [fed, fed + t) of block_shifts_device()."""
+        [fed, fed + t) of block_shifts_device().  With subpixel=True every pick is refined to a sixteenth of a pixel (rows
+        [fed, fed + t) of fine_shifts_device()) and the frames are interpolated bilinearly at the fine shifts (or the fine
+        shift field), `fill` where a tap that is used lies outside the frame."""
         on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
         if not on_device and not isinstance(frames, np.ndarray):
             raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
@@ -270,8 +327,27 @@ class MotionCorrector(object):
         self._need_blocks()
         return self._bscores[:self._last].cpu().numpy()
 
+    def _need_subpixel(self):
+        if not self.subpixel:
+            raise ValueError('this corrector stops at whole pixels: fine shifts need subpixel=True')
+
+    def fine_shifts_device(self):
+        """The int32 (n_frames, 2) tensor of fine shifts (sy, sx) in sixteenths of a pixel on the device -- with blocks the
+        (n_frames, By, Bx, 2) fine block shifts --; rows [0, fed) are set.  `fine_shifts=` of SeriesSummarizer /
+        RoiTraceExtractor takes it."""
+        self._need_subpixel()
+        return self._fine
+
+    def fine_shifts(self):
+        """(fed, 2) int32 numpy array of the fine shifts found so far, or with blocks (fed, By, Bx, 2): 16 * the whole-pixel
+        pick (shifts(), block_shifts()) plus its refinement in [-8, 8]."""
+        self._need_subpixel()
+        return self._fine[:self.fed].cpu().numpy()
+
     def valid(self):
         """((y0, y1), (x0, x1)): the rectangle every frame corrected so far covers with its own pixels."""
+        if self.subpixel:
+            return valid_rectangle(self.fine_shifts(), self.shape, fine=True)
         return valid_rectangle(self.shifts() if self.blocks is None else self.block_shifts(), self.shape)
 
 
@@ -321,13 +397,16 @@ def make_template(frames, max_shift=8, iterations=1, device=None):
 
 
 def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=200, source='series/raw', device=None,
-                           chunk_frames=None, blocks=None, max_dev=3):
+                           chunk_frames=None, blocks=None, max_dev=3, subpixel=False):
     """(shifts, template): the (T, 2) int32 (dy, dx) of every frame of `source` of a dataset file against `template` -- built
     by make_template (one iteration) from the first min(T, template_frames) frames when none is given.  The recording is
     streamed once, memory-mapped or sliced, never read whole; nothing is corrected here: pass `shifts` to
     summarize_series_device / extract_traces_device.  blocks=(By, Bx): the (T, By, Bx, 2) int32 block shifts within
-    +-max_dev of each frame's rigid shift instead (the template is still built rigidly); `shifts=` takes them as they are."""
+    +-max_dev of each frame's rigid shift instead (the template is still built rigidly); `shifts=` takes them as they are.
+    subpixel=True: the fine shifts in sixteenths of a pixel instead, in the same shapes (the template is still built from
+    whole-pixel corrections); `fine_shifts=` takes them as they are."""
     _check_max_shift(max_shift)
+    subpixel = _check_subpixel(subpixel)
     if blocks is not None:
         _check_blocks(blocks, max_dev)
     if isinstance(template_frames, bool) or not isinstance(template_frames, (int, np.integer)) or template_frames < 1:
@@ -344,10 +423,10 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
         if blocks is not None:
             _check_blocks(blocks, max_dev, shape, S)
         mc = MotionCorrector(shape, T, frames.dtype, template, max_shift=S, device=device, chunk_frames=chunk_frames, blocks=blocks,
-                             max_dev=max_dev)
+                             max_dev=max_dev, subpixel=subpixel)
         for a in range(0, T, mc.chunk_frames):
             mc.feed(np.asarray(frames[a:a + mc.chunk_frames]), correct=False)
-        out = mc.shifts() if blocks is None else mc.block_shifts()
+        out = mc.fine_shifts() if subpixel else (mc.shifts() if blocks is None else mc.block_shifts())
     finally:
         frames = None                        # a view of the file mapping: released before the file is closed
         close()

@@ -58,14 +58,15 @@ def _shifts_shape_ok(shape, n_frames, frame_shape):
     return 1 <= shape[1] <= limit[0] and 1 <= shape[2] <= limit[1]
 
 
-def _check_shifts(shifts, n_frames, frame_shape=None):
+def _check_shifts(shifts, n_frames, frame_shape=None, name='shifts'):
     """The `shifts=` keyword of SeriesSummarizer / RoiTraceExtractor: None, an (n_frames, 2) integer numpy array of (dy, dx) rows
     (-> contiguous int32) or an (n_frames, 2) integer tensor (checked, returned as it is); or the piecewise-rigid
-    (n_frames, By, Bx, 2) block shifts of either kind, By and Bx in [1, 32] and no more blocks than pixels.  Host only."""
+    (n_frames, By, Bx, 2) block shifts of either kind, By and Bx in [1, 32] and no more blocks than pixels.  `fine_shifts=`
+    (name='fine_shifts': sixteenths of a pixel) is held to the same checks.  Host only."""
     if shifts is None:
         return None
-    what = 'shifts must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), or (%d, By, Bx, 2) block shifts with By, Bx in [1, %d]' \
-        % (n_frames, n_frames, _MAX_BLOCKS)
+    what = '%s must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), or (%d, By, Bx, 2) block shifts with By, Bx in [1, %d]' \
+        % (name, n_frames, n_frames, _MAX_BLOCKS)
     if not isinstance(shifts, np.ndarray) and hasattr(shifts, 'is_cuda') and hasattr(shifts, 'data_ptr'):
         if not _shifts_shape_ok(shifts.shape, n_frames, frame_shape) or shifts.dtype.is_floating_point or shifts.dtype.is_complex:
             raise ValueError('%s, not %s %r' % (what, shifts.dtype, tuple(shifts.shape)))
@@ -74,8 +75,18 @@ def _check_shifts(shifts, n_frames, frame_shape=None):
     if not _shifts_shape_ok(a.shape, n_frames, frame_shape) or a.dtype.kind not in 'iu':
         raise ValueError('%s, not %s %r' % (what, a.dtype, tuple(a.shape)))
     if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError('shifts must fit int32')
+        raise ValueError('%s must fit int32' % name)
     return np.ascontiguousarray(a.astype(np.int32))
+
+
+def _check_known_shifts(shifts, fine_shifts, n_frames, frame_shape):
+    """`shifts=` and `fine_shifts=` of a consumer of known shifts -> (the checked table or None, whether it is fine).  Giving both
+    is a ValueError.  Host only."""
+    if shifts is not None and fine_shifts is not None:
+        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
+    if fine_shifts is not None:
+        return _check_shifts(fine_shifts, n_frames, frame_shape, name='fine_shifts'), True
+    return _check_shifts(shifts, n_frames, frame_shape), False
 
 
 def _check_device_frames(torch, frames, dtype, device, owner):
@@ -91,10 +102,11 @@ def _check_device_frames(torch, frames, dtype, device, owner):
 class _ShiftedChunks(object):
     """Known shifts applied on the way in (fill 0): the int32 (n_frames, 2) table on the device (dc_motion_apply) or the
     (n_frames, By, Bx, 2) block shifts (dc_motion_warp) and one scratch chunk the accumulate kernels read instead of the staged
-    frames.  Frame `fed + i` of the recording gets row `fed + i`."""
+    frames.  Frame `fed + i` of the recording gets row `fed + i`.  fine: the table holds fine shifts (sixteenths of a pixel), the
+    frames are interpolated (dc_motion_apply_sub, dc_motion_warp_sub: they are told the signedness)."""
 
-    def __init__(self, torch, L, device, shifts, shape):
-        self._L, self.shape = L, shape
+    def __init__(self, torch, L, device, shifts, shape, fine=False, unsigned=0):
+        self._L, self.shape, self.fine, self._uns = L, shape, fine, int(unsigned)
         if isinstance(shifts, np.ndarray):
             shifts = torch.from_numpy(shifts)
         self.shifts = shifts.to(device=device, dtype=torch.int32).contiguous()
@@ -106,7 +118,14 @@ class _ShiftedChunks(object):
         C, H, W = self.shape
         for a in range(0, tc, C):
             n = min(C, tc - a)
-            if self.blocks is None:
+            if self.fine and self.blocks is None:
+                self._L.dc_motion_apply_sub(fp + 2 * a * H * W, self._uns, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
+                                            self.scratch.data_ptr(), st)
+            elif self.fine:
+                By, Bx = self.blocks
+                self._L.dc_motion_warp_sub(fp + 2 * a * H * W, self._uns, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
+                                           self.scratch.data_ptr(), st)
+            elif self.blocks is None:
                 self._L.dc_motion_apply(fp + 2 * a * H * W, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
                                         self.scratch.data_ptr(), st)
             else:
@@ -159,10 +178,12 @@ class _TwoSlotStage(object):
 class SeriesSummarizer(object):
     """Owns the device state of one recording's summaries; feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None):
+    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None, fine_shifts=None):
         """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
         MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before it is summarised.  Piecewise-rigid
-        (n_frames, By, Bx, 2) block shifts (MotionCorrector.block_shifts_device()) are taken too: dc_motion_warp moves the chunk."""
+        (n_frames, By, Bx, 2) block shifts (MotionCorrector.block_shifts_device()) are taken too: dc_motion_warp moves the chunk.
+        fine_shifts: instead of shifts, the same shapes in sixteenths of a pixel (MotionCorrector.fine_shifts_device()): each
+        chunk is interpolated by dc_motion_apply_sub / dc_motion_warp_sub (fill 0)."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         try:
             shape = tuple(int(v) for v in shape)
@@ -185,7 +206,7 @@ class SeriesSummarizer(object):
         chunk_frames = int(chunk_frames)
         if chunk_frames < 1:
             raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        shifts = _check_shifts(shifts, n_frames, shape)
+        shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
         self.shape, self.n_frames, self.kinds = shape, n_frames, kinds
         self.chunk_frames = min(chunk_frames, n_frames)
         self.fed = 0
@@ -213,7 +234,8 @@ class SeriesSummarizer(object):
         self.max16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None
         self.xy = torch.empty((4, n), dtype=torch.int64, device=dev) if self._xy else None
         self._stage = _TwoSlotStage(torch, net, dev, 'series_stage', (self.chunk_frames, H, W))
-        self._shifted = None if shifts is None else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W))
+        self._shifted = None if shifts is None else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
+                                                                   self.dtype == np.dtype(np.uint16))
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
@@ -358,18 +380,21 @@ def _open_series(dspath, source):
 
 
 def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
-                            shifts=None):
+                            shifts=None, fine_shifts=None):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
     float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame, or
-    its (T, By, Bx, 2) block shifts (motion.estimate_shifts_device), applied on the device on the way in."""
+    its (T, By, Bx, 2) block shifts (motion.estimate_shifts_device), applied on the device on the way in.  fine_shifts: instead,
+    either shape in sixteenths of a pixel (estimate_shifts_device(subpixel=True)): the frames are interpolated on the way in."""
     _check_kind(kind)
+    if shifts is not None and fine_shifts is not None:
+        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
-                                kinds=(kind,), shifts=shifts)
+                                kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts)
         for a in range(0, T, summ.chunk_frames):
             summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
         out = summ.result(kind, standardize=standardize)

@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--subpixel]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -112,27 +112,33 @@ def _blocks_arg(text):
     return by, bx
 
 
-def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3):
+def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
     within +-S); the summary the network segments is then the mean of the registered raw frames instead of the stored
     `series/mean`, and the traces are summed over the registered frames.  blocks=(By, Bx) with register: piecewise-rigid -- every
-    block of the frame gets the rigid shift plus a residual within +-max_dev, and the frames are warped by the blended field."""
+    block of the frame gets the rigid shift plus a residual within +-max_dev, and the frames are warped by the blended field.
+    subpixel with register: every shift is refined to a sixteenth of a pixel and the frames are interpolated bilinearly."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
+    if subpixel and register is None:
+        raise ValueError('--subpixel needs --register')
+    known = 'fine_shifts' if subpixel else 'shifts'
+    unit = 16 if subpixel else 1
     dspaths = nf_find_hdf5(dataset_name)
     shifts = {}
     if register is not None:
         for dspath in dspaths:
-            shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register, blocks=blocks, max_dev=max_dev)
-            logger.info('%s: registered within +-%d%s, largest |dy|, |dx| = %d, %d, valid rectangle %r' % (
+            shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register, blocks=blocks, max_dev=max_dev, subpixel=subpixel)
+            logger.info('%s: registered within +-%d%s%s, largest |dy|, |dx| = %g, %g, valid rectangle %r' % (
                 dspath, register, '' if blocks is None else ' in %d x %d blocks within +-%d of that' % (blocks + (max_dev,)),
-                np.abs(shifts[dspath][..., 0]).max(), np.abs(shifts[dspath][..., 1]).max(),
-                valid_rectangle(shifts[dspath], tmpl.shape)))
+                ', refined to 1/16 pixel' if subpixel else '',
+                np.abs(shifts[dspath][..., 0]).max() / unit, np.abs(shifts[dspath][..., 1]).max() / unit,
+                valid_rectangle(shifts[dspath], tmpl.shape, fine=subpixel)))
         model = UNet2DSummary(cpdir=checkpoints_dir,
-                              series_summary_func=lambda p: summarize_series_device(p, kind='mean', shifts=shifts[p]))
+                              series_summary_func=lambda p: summarize_series_device(p, kind='mean', **{known: shifts[p]}))
     else:
         model = UNet2DSummary(cpdir=checkpoints_dir)
     Mp, names = model.predict(dspaths, model_path=model_path, window_shape=(512, 512), save=False, augmentation=True)
@@ -141,7 +147,7 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         if not mask.any():
             logger.info('%s: no neurons predicted, no traces file.' % name)
             continue
-        tr = extract_traces_device(dspath, mask, kind=kind, shifts=shifts.get(dspath))
+        tr = extract_traces_device(dspath, mask, kind=kind, **{known: shifts.get(dspath)})
         out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
         logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
@@ -179,6 +185,7 @@ if __name__ == '__main__':
                         type=_blocks_arg, metavar='ByxBx')
     sp_trc.add_argument('--max-dev', help='with --blocks: a block may deviate from the rigid shift by +-D pixels (default 3)', default=3,
                         type=int, metavar='D', dest='max_dev')
+    sp_trc.add_argument('--subpixel', help='with --register: refine every shift to 1/16 pixel and interpolate the frames', action='store_true')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 114
+#define DC_ABI_VERSION 115
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -565,7 +565,7 @@ int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, lo
  * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
  * examples/neurons/unet2ds_sj.py, were registered by an outside tool: it reads directories named ..._stabilized).  This is that
  * step: rigid, whole-pixel translation, found by exhaustive search within +-S, S <= DC_MOTION_MAX_SHIFT; the piecewise-rigid
- * mode built on it follows below.  Sub-pixel shifts, interpolation of pixel values and FFT methods are out of scope.  Integer
+ * mode built on it and the sub-pixel refinement of both follow below.  FFT methods are out of scope.  Integer
  * arithmetic only: every result is exact, so the chunking
  * of a recording never changes a bit.
  * frames: as for dc_series_accumulate (int16 / uint16 by is_unsigned, [tc][H][W] contiguous, 2-byte aligned); tmpl: [H][W] of the
@@ -625,6 +625,44 @@ int dc_motion_block_pick(const long* bscores, const int* rigid, int tc, int By, 
                          dc_stream_t stream);
 int dc_motion_warp(const void* frames, int tc, const int* block_shifts, int By, int Bx, int H, int W, int fill, void* out,
                    dc_stream_t stream);
+
+/* ---- sub-pixel motion correction: the picks refined to 1/16 pixel, the frames interpolated bilinearly ---------------------------
+ * FINE SHIFTS are int32 in units of 1 / DC_MOTION_SUB of a pixel, with the sign convention above: a fine shift (sy, sx) =
+ * (16 dy, 16 dx) means exactly the whole-pixel shift (dy, dx).  Integers only (csrc/motion_math.h): every result is exact and the
+ * chunking of a recording never changes a bit.
+ * REFINEMENT of a picked entry of a score table, per axis: s0 the picked score, sm and sp its neighbours at -1 and +1 on that axis
+ *   with the other axis held at the pick.  A pick on the table's border on that axis: q = 0.  Otherwise N = sm - sp,
+ *   D = sm - 2 s0 + sp (>= 0, and |N| <= D, because s0 is the minimum); D == 0: q = 0; otherwise
+ *   m = floor((16 |N| + D - 1) / (2 D)), q = sign(N) m -- the vertex of the parabola through the three scores in sixteenths, a tie
+ *   at a half going to the pick.  q lies in [-8, 8]; a symmetric neighbourhood gives 0; sm == s0 < sp gives exactly -8; the mirror
+ *   image of a table gives the mirrored q.  Exact for scores up to 2^62 - 1 (16 |N| is never formed).  fine = 16 * picked + q.
+ *   dc_motion_refine: fine = int32[tc][2] from the dc_motion_ssd tables `scores` and the dc_motion_pick rows `shifts`.  A row
+ *     outside [-S, S] (no pick writes one) gives q = 0 and reads nothing outside the table.
+ *   dc_motion_block_refine: fine = int32[tc][By][Bx][2] from the dc_motion_block_ssd tables, the rigid rows and the
+ *     dc_motion_block_pick rows `block_shifts`: the picked residual is block_shifts - clamp(rigid, S), refined within its own
+ *     [2D+1][2D+1] table; fine = 16 * block_shifts + q.  A residual outside [-D, D] gives q = 0 and reads nothing outside the table.
+ * SPLIT of a fine shift: iy = floor(sy / 16), fy = sy - 16 iy in [0, 16) for either sign; ix, fx likewise.
+ * INTERPOLATION: the values are read as int16 or uint16 numbers (is_unsigned as for dc_motion_ssd); a_ij = frame[y + iy + i][x + ix + j]:
+ *     out = floor(((16-fy) ((16-fx) a00 + fx a01) + fy ((16-fx) a10 + fx a11) + 128) / 256).
+ *   The result lies between the smallest and the largest tap, so it fits the dtype.  A tap whose weight is zero is not used: row
+ *   i = 1 only when fy > 0, column j = 1 only when fx > 0.  If any USED tap lies outside the frame the output is `fill`.
+ *   dc_motion_apply_sub: out[t][y][x] = the interpolation at (sy, sx) = fine[t] (int32[tc][2], read on the device; any int32 is
+ *     legal).  With fine shifts that are multiples of 16 this is dc_motion_apply bit for bit.
+ *   dc_motion_warp_sub: the same with a fine shift per pixel: the SHIFT FIELD of dc_motion_warp computed from the fine block shifts
+ *     (int32[tc][By][Bx][2]; that arithmetic is exact for any int32), split and interpolated per pixel.  Equal fine block shifts
+ *     make it dc_motion_apply_sub.  With fine block shifts that are multiples of 16, the output equals that of
+ *     dc_motion_warp on the block shifts / 16 at every pixel where the fine field is itself a multiple of 16 -- everywhere when
+ *     the frame's block shifts are equal; between block centres whose shifts differ the fine field passes through the fractions
+ *     that the whole-pixel field rounds away, which is the point of it.
+ * Sizes, limits, alignment and the overlap rule are those of the whole-pixel counterparts (DC_EINVAL / DC_EUNSUP alike). */
+#define DC_MOTION_SUB 16
+int dc_motion_refine(const long* scores, const int* shifts, int tc, int S, int* fine, dc_stream_t stream);
+int dc_motion_block_refine(const long* bscores, const int* rigid, const int* block_shifts, int tc, int By, int Bx, int S, int D, int* fine,
+                           dc_stream_t stream);
+int dc_motion_apply_sub(const void* frames, int is_unsigned, int tc, const int* fine, int H, int W, int fill, void* out,
+                        dc_stream_t stream);
+int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, const int* fine_block_shifts, int By, int Bx, int H, int W, int fill,
+                       void* out, dc_stream_t stream);
 
 /* ---- UNet1D spike inference: traces in, spike probabilities out ------------------------------------------------------------
  * The reference's second model family, UNet1DSegmentation: the network unet1d (unet_1d_segmentation.py:49-148) as its predict()

@@ -8,7 +8,10 @@ the output (np.savez: stored, so it is memory-mapped).  Timed, for max_shift S =
  (b) kernel time per chunk of dc_motion_ssd, dc_motion_pick and dc_motion_apply: HIP events on the launch stream around 5 launches
      back to back, median of 5 such samples after a warm-up (min - max), and the ratio of each to the copy; then the same for the
      piecewise-rigid entry points dc_motion_block_ssd, dc_motion_block_pick and dc_motion_warp at `--blocks` and `--max-dev`,
-     on the rigid shifts just found;
+     on the rigid shifts just found; then the sub-pixel entry points: dc_motion_refine and dc_motion_block_refine on those tables,
+     dc_motion_apply_sub at fine shifts with both fractions non-zero (two source rows, nine values each) and dc_motion_warp_sub
+     at equal fine block shifts (every group of 8 shares its split) and at block shifts a few sixteenths apart (the field changes
+     within most groups: value by value);
  (c) wall time of estimate_shifts_device over the whole recording with a given template (median of 5 after a warm-up, page cache
      warm), and whether the planted shifts came back;
  (d) a numpy restatement of the same search on a few frames, scaled to a chunk.
@@ -40,6 +43,11 @@ def numpy_scores(frames, tmpl, S):
             d = t[None] - f[:, S + dy:H - S + dy, S + dx:W - S + dx]
             out[:, dy + S, dx + S] = (d * d).sum(axis=(1, 2))
     return out
+
+
+def rs_blocks(C, By, Bx):
+    """Per-block offsets within +-6 sixteenths: block shifts as far apart as a refinement leaves them."""
+    return np.random.RandomState(1).randint(-6, 7, size=(C, By, Bx, 2)).astype(np.int32)
 
 
 def main():
@@ -89,6 +97,10 @@ def main():
     shifts = torch.zeros((C, 2), dtype=torch.int32, device='cuda')
     bshifts = torch.zeros((C, By, Bx, 2), dtype=torch.int32, device='cuda')
     bscores = torch.empty((C, By, Bx, 2 * D + 1, 2 * D + 1), dtype=torch.int64, device='cuda')
+    fine = torch.zeros((C, 2), dtype=torch.int32, device='cuda')
+    bfine = torch.zeros((C, By, Bx, 2), dtype=torch.int32, device='cuda')
+    frac = torch.tensor([5, 9], dtype=torch.int32, device='cuda')                       # both fractions non-zero
+    apart = torch.from_numpy(rs_blocks(C, By, Bx)).cuda()
     stream = torch.cuda.current_stream().cuda_stream
 
     def timed(fn, reps=1):
@@ -140,6 +152,32 @@ def main():
             say('  S = %2d  %-20s %8.3f ms  (%.3f - %.3f)  / H2D = %5.2f%s' % (S, name, ms, lo, hi, ms / h2d, extra))
         say('  S = %2d  piecewise %dx%d, D = %d: these three %8.3f ms, with the rigid ssd and pick %8.3f ms  / H2D = %5.2f'
             % (S, By, Bx, D, btotal, btotal + total - ms_apply, (btotal + total - ms_apply) / h2d))
+        ms_warp = ms                                     # the last row: dc_motion_warp
+        fine_f, bfine_u, bfine_v = fine.clone(), bfine.clone(), bfine.clone()
+        srows = [('dc_motion_refine', lambda: L.dc_motion_refine(scores.data_ptr(), shifts.data_ptr(), C, S, fine.data_ptr(), stream)),
+                 ('dc_motion_block_refine', lambda: L.dc_motion_block_refine(bscores.data_ptr(), shifts.data_ptr(), bshifts.data_ptr(), C, By, Bx,
+                                                                             S, D, bfine.data_ptr(), stream)),
+                 ('dc_motion_apply_sub', lambda: L.dc_motion_apply_sub(dev.data_ptr(), 0, C, fine_f.data_ptr(), H, W, 0, out.data_ptr(), stream)),
+                 ('dc_motion_warp_sub, equal', lambda: L.dc_motion_warp_sub(dev.data_ptr(), 0, C, bfine_u.data_ptr(), By, Bx, H, W, 0,
+                                                                            out.data_ptr(), stream)),
+                 ('dc_motion_warp_sub, apart', lambda: L.dc_motion_warp_sub(dev.data_ptr(), 0, C, bfine_v.data_ptr(), By, Bx, H, W, 0,
+                                                                            out.data_ptr(), stream))]
+        sub = {}
+        for name, fn in srows:
+            if name == 'dc_motion_apply_sub':            # the refined shifts are there: move them off the whole pixels
+                fine_f.copy_(16 * shifts + frac)
+                bfine_u.copy_((16 * shifts + frac)[:, None, None, :].expand(C, By, Bx, 2))
+                bfine_v.copy_(bfine_u + apart)
+            ms, lo, hi = sample(fn)
+            sub[name] = ms
+            say('  S = %2d  %-26s %8.3f ms  (%.3f - %.3f)  / H2D = %5.2f' % (S, name, ms, lo, hi, ms / h2d))
+        rigid_sub = total - ms_apply + sub['dc_motion_refine'] + sub['dc_motion_apply_sub']
+        say('  S = %2d  sub-pixel rigid: ssd, pick, refine, apply_sub %8.3f ms  / H2D = %5.2f  (%s);  apply_sub / apply = %.2f, '
+            'warp_sub / warp = %.2f (equal), %.2f (apart)'
+            % (S, rigid_sub, rigid_sub / h2d, 'hides under the copy' if rigid_sub < h2d else 'does NOT hide under the copy',
+               sub['dc_motion_apply_sub'] / ms_apply, sub['dc_motion_warp_sub, equal'] / ms_warp, sub['dc_motion_warp_sub, apart'] / ms_warp))
+        q = (fine.cpu().numpy() - 16 * shifts.cpu().numpy())
+        say('  S = %2d  refinements q of the chunk within [-8, 8]: %s (largest |q| %d)' % (S, bool((np.abs(q) <= 8).all()), int(np.abs(q).max())))
         got_b = bshifts.cpu().numpy()
         say('  S = %2d  block shifts of the chunk all equal to the planted rigid shift: %s'
             % (S, bool((got_b == -offs[:C, None, None, :]).all()) if S >= M else 'n/a (S < 5)'))
