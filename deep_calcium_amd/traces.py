@@ -200,6 +200,17 @@ class RoiTraceExtractor(object):
                 self._stage.run(frames, main, lambda fp, tc: self._accumulate(fp, tc, st))
         return self
 
+    def sums_device(self):
+        """The (R, T) int64 sums where they lie, on the device, once every frame has been fed: what dff.TraceBaseline reads in
+        place.  The extractor's own state: do not write to it."""
+        if self.fed != self.n_frames:
+            raise ValueError('sums_device() after %d of %d frames' % (self.fed, self.n_frames))
+        return self.sums
+
+    def areas_host(self):
+        """The pixel count of every ROI, int32[R], on the host."""
+        return self.areas.copy()
+
     def result(self, kind='mean'):
         """(R, T): int64 for 'sum', float32 for 'mean' and 'zscore'."""
         _check_kind(kind)

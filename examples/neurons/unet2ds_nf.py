@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--subpixel]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -32,7 +32,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
-                              estimate_shifts_device, summarize_series_device, valid_rectangle)
+                              estimate_shifts_device, summarize_series_device, valid_rectangle, dff_traces_device)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -112,19 +112,32 @@ def _blocks_arg(text):
     return by, bx
 
 
-def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False):
+def _neuropil_arg(text):
+    try:
+        inner, outer, weight = text.split(',')
+        return int(inner), int(outer), float(weight)
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected INNER,OUTER,WEIGHT such as 2,12,0.7, not %r' % text)
+
+
+def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
+           percentile=8, neuropil=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
     within +-S); the summary the network segments is then the mean of the registered raw frames instead of the stored
     `series/mean`, and the traces are summed over the registered frames.  blocks=(By, Bx) with register: piecewise-rigid -- every
     block of the frame gets the rigid shift plus a residual within +-max_dev, and the frames are warped by the blended field.
-    subpixel with register: every shift is refined to a sixteenth of a pixel and the frames are interpolated bilinearly."""
+    subpixel with register: every shift is refined to a sixteenth of a pixel and the frames are interpolated bilinearly.
+    dff=WINDOW: instead of `kind`, the traces are dF/F against a rolling-percentile baseline over WINDOW frames (odd; `percentile`,
+    default 8), after subtracting neuropil=(inner, outer, weight) times the trace of a ring around every ROI when given."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
     if subpixel and register is None:
         raise ValueError('--subpixel needs --register')
+    if dff is None and neuropil is not None:
+        raise ValueError('--neuropil needs --dff')
     known = 'fine_shifts' if subpixel else 'shifts'
     unit = 16 if subpixel else 1
     dspaths = nf_find_hdf5(dataset_name)
@@ -147,7 +160,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         if not mask.any():
             logger.info('%s: no neurons predicted, no traces file.' % name)
             continue
-        tr = extract_traces_device(dspath, mask, kind=kind, **{known: shifts.get(dspath)})
+        if dff is not None:
+            tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **{known: shifts.get(dspath)})
+        else:
+            tr = extract_traces_device(dspath, mask, kind=kind, **{known: shifts.get(dspath)})
         out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
         logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
@@ -186,6 +202,11 @@ if __name__ == '__main__':
     sp_trc.add_argument('--max-dev', help='with --blocks: a block may deviate from the rigid shift by +-D pixels (default 3)', default=3,
                         type=int, metavar='D', dest='max_dev')
     sp_trc.add_argument('--subpixel', help='with --register: refine every shift to 1/16 pixel and interpolate the frames', action='store_true')
+    sp_trc.add_argument('--dff', help='write dF/F against a rolling-percentile baseline over WINDOW frames (odd) instead of --kind', default=None,
+                        type=int, metavar='WINDOW')
+    sp_trc.add_argument('--percentile', help='with --dff: the integer percentile of the baseline (default 8)', default=8, type=int, metavar='Q')
+    sp_trc.add_argument('--neuropil', help='with --dff: subtract WEIGHT times the trace of the ring INNER < distance <= OUTER (e.g. 2,12,0.7)',
+                        default=None, type=_neuropil_arg, metavar='INNER,OUTER,WEIGHT')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

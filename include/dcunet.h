@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 115
+#define DC_ABI_VERSION 116
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -560,6 +560,43 @@ int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0
                             const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);
 int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,
                           dc_stream_t stream);
+
+/* ---- dF/F traces: neuropil correction, rolling-percentile baseline, (F - F0) / F0 -----------------------------------------------
+ * The step between ROI traces and spikes that the z-score above cannot replace: a recording bleaches and drifts, and every ROI
+ * collects out-of-focus neuropil light.  The reference has no counterpart; THESE DEFINITIONS ARE THE SPECIFICATION.  Integers end
+ * to end, one rounding at the end, no dependence on how the recording was chunked.
+ * Inputs: S[r][t], the int64 ROI sums dc_roi_trace_accumulate writes, and A[r], the ROI areas.
+ *   offset   o: an integer dark level added to every pixel, |o| <= 65535 (default 0).
+ *   weight   w in [0, 1], taken in 256ths: a = floor(256 w + 0.5).
+ *   numerator N[r][t] and denominator D[r] (int64; the corrected per-pixel fluorescence is N / D):
+ *     without neuropil, or for an ROI whose ring is empty:   N = S + o A,                               D = A;
+ *     with a ring of An > 0 pixels and sums Sn:              N = 256 An (S + o A) - a A (Sn + o An),    D = 256 An A.
+ *     The HOST checks An * A < 2^36 before anything is launched: |S + o A| < 2^17 A for 16-bit pixels, so |N| < 2^62.
+ *   window   half-width h in [0, DC_TRACE_BASELINE_MAX_HALF]: the window of frame t is [max(0, t - h), min(T - 1, t + h)], n frames
+ *            -- clipped at the ends of the trace, never padded.
+ *   rank     integer percentile q in [0, 100]: k = (q * (n - 1)) / 100 in INTEGER division.  Not numpy's float rule
+ *            (floor(0.29 * 100) is 28, this gives 29; the two differ in 198 (q, n) pairs for n < 4096): the oracle is
+ *            np.sort(window)[k], never np.percentile.
+ *   baseline B[r][t] = the k-th smallest (0-based) of N[r] over the window, int64.  Ties are values: which of two equal samples is
+ *            picked cannot matter.
+ *   dF/F     dff[r][t] = (float)((double)(N - B) / (double)B) where B > 0, exactly 0.f where B <= 0.  N - B is formed in int64 (no
+ *            overflow below 2^62); each int64 -> double conversion is one round-to-nearest, like numpy's: bit-equal to
+ *            ((N - B).astype(float64) / B.astype(float64)).astype(float32).  D cancels.
+ *   scaled   f = (float)((double)N / (double)D), baseline = (float)((double)B / (double)D).
+ * All pointers are DEVICE memory, there are no out-parameters and nothing is read on the host.
+ *   dc_trace_combine: num[r][t] = ca[r] * sums[r][t] - cb[r] * sums[np_row[r]][t] + cc[r] in int64, r < R.  sums = int64 rows of
+ *     stride ld; np_row int32[R]: np_row[r] < 0 means no second term, otherwise ANY row of sums, rows >= R included (the rings
+ *     of a streaming pass follow the ROIs); ca, cb, cc int64[R] come from the host (the formulas above); num int64[R][T] dense.
+ *   dc_trace_baseline: num = int64 rows of stride ld; base int64[R][T] and dff float[R][T], each nullable and dense.  THE CALLER
+ *     PROMISES |num| < 2^62 (not checked).  half > DC_TRACE_BASELINE_MAX_HALF: DC_EUNSUP (-3); q outside [0, 100], a negative
+ *     count, ld < T or a misaligned buffer: -1.  R == 0 or T == 0: 0, nothing launched.
+ *   dc_trace_scale: out[r][t] = (float)((double)x[r][t] / (double)den[r]), exactly 0 where den[r] <= 0; x = int64 rows of stride
+ *     ld, den int64[R], out float[R][T] dense. */
+#define DC_TRACE_BASELINE_MAX_HALF 2047
+int dc_trace_combine(const long* sums, long ld, const int* np_row, const long* ca, const long* cb, const long* cc, int R, long T,
+                     long* num, dc_stream_t stream);
+int dc_trace_baseline(const long* num, long ld, int R, long T, int half, int q, long* base, float* dff, dc_stream_t stream);
+int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float* out, dc_stream_t stream);
 
 /* ---- rigid motion correction: register the frames of a recording to a template ------------------------------------------------
  * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
