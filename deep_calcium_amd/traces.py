@@ -130,6 +130,8 @@ class RoiTraceExtractor(object):
         self.chunk_frames = min(chunk_frames, n_frames)
         self.fed = 0
         self._stage = None
+        self._stage_tag = 'traces_stage'
+        self._after_chunk = None
 
         import torch
         from . import net
@@ -163,6 +165,8 @@ class RoiTraceExtractor(object):
             self.L.dc_roi_trace_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, t0, self._row_off.data_ptr(),
                                            self._row_pix.data_ptr(), self._row_roi.data_ptr(), self._rows, self.n_rois,
                                            self.sums.data_ptr(), self.n_frames, H, W, st)
+            if self._after_chunk is not None:     # a second reader of the same frames, behind the sums (footprints.RoiFootprints)
+                self._after_chunk(fp, tc, t0, st)
         if self._shifted is None:
             accumulate(fp, tc, self.fed)
         else:
@@ -196,7 +200,7 @@ class RoiTraceExtractor(object):
             else:
                 if self._stage is None:          # names of its own: a SeriesSummarizer alive at the same time keeps its slots
                     H, W = self.shape
-                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'traces_stage', (self.chunk_frames, H, W))
+                    self._stage = _TwoSlotStage(torch, self._net, self.device, self._stage_tag, (self.chunk_frames, H, W))
                 self._stage.run(frames, main, lambda fp, tc: self._accumulate(fp, tc, st))
         return self
 

@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -32,7 +32,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
-                              estimate_shifts_device, summarize_series_device, valid_rectangle, dff_traces_device)
+                              estimate_shifts_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -121,7 +121,7 @@ def _neuropil_arg(text):
 
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
-           percentile=8, neuropil=None):
+           percentile=8, neuropil=None, refine=None, halo=2):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -130,7 +130,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     block of the frame gets the rigid shift plus a residual within +-max_dev, and the frames are warped by the blended field.
     subpixel with register: every shift is refined to a sixteenth of a pixel and the frames are interpolated bilinearly.
     dff=WINDOW: instead of `kind`, the traces are dF/F against a rolling-percentile baseline over WINDOW frames (odd; `percentile`,
-    default 8), after subtracting neuropil=(inner, outer, weight) times the trace of a ring around every ROI when given."""
+    default 8), after subtracting neuropil=(inner, outer, weight) times the trace of a ring around every ROI when given.
+    refine=THR: a first pass over the recording computes every ROI's footprint map (the correlation of each pixel of the ROI and of
+    a `halo` around it with the ROI's trace); every ROI is cut down (or grown) to the largest connected set of pixels with
+    correlation >= THR, ROIs with none are dropped, and the traces are those of the refined ROIs (a second pass)."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -160,6 +163,19 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         if not mask.any():
             logger.info('%s: no neurons predicted, no traces file.' % name)
             continue
+        if refine is not None:
+            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, **{known: shifts.get(dspath)})
+            rois, kept = refine_rois(coords, corr, mask.shape, threshold=refine)
+            before = [set(map(tuple, c[i].tolist())) for c, i in zip(coords, inside)]
+            after = dict((r, set(map(tuple, c.tolist()))) for r, c in zip(kept, rois))
+            logger.info('%s: refined at corr >= %g (halo %d): %d of %d ROIs dropped, %d pixels removed, %d added' % (
+                name, refine, halo, len(coords) - len(kept), len(coords),
+                sum(len(b - after.get(r, set())) for r, b in enumerate(before)),
+                sum(len(after[r] - before[r]) for r in kept)))
+            if not rois:
+                logger.info('%s: no ROI survives the refinement, no traces file.' % name)
+                continue
+            mask = rois
         if dff is not None:
             tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **{known: shifts.get(dspath)})
         else:
@@ -207,6 +223,10 @@ if __name__ == '__main__':
     sp_trc.add_argument('--percentile', help='with --dff: the integer percentile of the baseline (default 8)', default=8, type=int, metavar='Q')
     sp_trc.add_argument('--neuropil', help='with --dff: subtract WEIGHT times the trace of the ring INNER < distance <= OUTER (e.g. 2,12,0.7)',
                         default=None, type=_neuropil_arg, metavar='INNER,OUTER,WEIGHT')
+    sp_trc.add_argument('--refine', help='refine every ROI by its footprint map first: keep the pixels whose correlation with the trace is >= THR',
+                        default=None, type=float, metavar='THR')
+    sp_trc.add_argument('--halo', help='with --refine: how far beyond an ROI, in pixels, its footprint map reaches (0..16, default 2)', default=2,
+                        type=int, metavar='N')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 116
+#define DC_ABI_VERSION 117
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -560,6 +560,45 @@ int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0
                             const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);
 int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,
                           dc_stream_t stream);
+
+/* ---- ROI footprint maps: the correlation of every pixel of an ROI's support with the ROI's own trace ---------------------------
+ * The one decision of the chain that never looks at the recording is which pixels belong to a neuron (the ROIs are the regions
+ * of a mask predicted from ONE summary image).  This is the check of an ROI against the movie it came from, the quantity
+ * CaImAn's spatial r_values and suite2p's footprint weights are built on.  The reference has no counterpart; THESE DEFINITIONS
+ * ARE THE SPECIFICATION.  Integers until the last step, independent of how the recording was chunked.
+ * x_p(t): pixel p in frame t.  ROI r: pixels P_r, area A_r, trace S_r(t) = sum over P_r of x_p(t) (what
+ * dc_roi_trace_accumulate writes).  The SUPPORT of ROI r is chosen by the caller (P_r plus a halo, sorted by flat index); each
+ * of its ENTRIES (r, p) is `inside` (p in P_r) or not.  A pixel in the supports of two ROIs is two independent entries.
+ *   per entry, over all T frames:   a = sum x,  b = sum x^2,  c = sum x S_r      (c: 128 bits, c_hi * 2^64 + c_lo)
+ *   per ROI:                        u = sum S_r,  w = sum S_r^2                   (w: 128 bits)
+ *   Cxx = T b - a^2,  Cxs = T c - a u,  Css = T w - u^2, exact in 128-bit integers;
+ *   halo entry:    Cxl = Cxs,        Cll = Css;
+ *   inside entry:  Cxl = Cxs - Cxx,  Cll = Css - 2 Cxs + Cxx: the pixel is taken out of the trace it is compared with
+ *                  (L = S - x), otherwise every pixel of a small ROI correlates with itself;
+ *   corr = (float)(f64(Cxl) / (sqrt(f64(Cxx)) * sqrt(f64(Cll)))), each numerator rounded ONCE to double, no fused multiply-add;
+ *   exactly 0 where Cxx <= 0 or Cll <= 0 (a pixel or trace constant in time, T == 1, the pixel of a one-pixel ROI; numpy: NaN).
+ * Limits: T * H * W <= DC_ROI_TRACE_MAX_VOLUME as above, and T <= DC_ROI_PIXEL_MAX_FRAMES = 2^31 - 1 so that b < 2^63; under
+ * both every intermediate stays below 2^127 (csrc/footprint_math.h derives it).  Beyond: DC_EUNSUP (-3).
+ * All pointers are DEVICE memory, there are no out-parameters and nothing is read on the host.
+ *   dc_roi_pixel_accumulate: row_off / row_pix / row_roi: a CSR over the support ENTRIES, in the form of
+ *     dc_roi_trace_accumulate (row_roi nullable, then S == R); entry e = position in row_pix, N = row_off[S] entries (an
+ *     entry at or beyond N is never touched).  sums = int64[R][ld] whose columns [t0, t0 + tc) dc_roi_trace_accumulate has
+ *     filled on the same stream.  mom = int64[4 * N], CALLER-OWNED AND CALLER-ZEROED before the first chunk: planes a, b, c_lo,
+ *     c_hi of N entries each; the call ADDS the chunk's contribution.  Every entry is owned by one thread of one workgroup:
+ *     no atomics, the same bits for every chunking and every run.  Exact for any 16-bit x and ANY int64 sums (|S| <= 2^46 is
+ *     what the limits allow).  An index outside [0, H*W) contributes nothing and is never dereferenced; a row whose row_roi is
+ *     outside [0, R) adds nothing.
+ *   dc_roi_trace_moments: rmom = int64[3 * R]: u, w_lo, w_hi of every row of sums = int64[R][ld] over its first T columns.
+ *   dc_roi_pixel_corr: inside int32[N] (non-zero: inside); corr float[N], one value per entry in entry order; the entries of a
+ *     row whose row_roi is outside [0, R) get 0.
+ * N == 0, S == 0, R == 0 (and tc == 0 for the accumulation): 0, nothing launched. */
+#define DC_ROI_PIXEL_MAX_FRAMES 2147483647L
+int dc_roi_pixel_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
+                            const int* row_roi, int S, int R, const long* sums, long ld, long* mom, int N, int H, int W,
+                            dc_stream_t stream);
+int dc_roi_trace_moments(const long* sums, long ld, int R, long T, long* rmom, dc_stream_t stream);
+int dc_roi_pixel_corr(const long* mom, int N, const int* row_off, const int* row_roi, int S, int R, const int* inside,
+                      const long* rmom, long T, float* corr, dc_stream_t stream);
 
 /* ---- dF/F traces: neuropil correction, rolling-percentile baseline, (F - F0) / F0 -----------------------------------------------
  * The step between ROI traces and spikes that the z-score above cannot replace: a recording bleaches and drifts, and every ROI
