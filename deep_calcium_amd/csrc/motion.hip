@@ -8,6 +8,9 @@
 // dc_motion_block_pick), blended into one whole-pixel shift per pixel (dc_motion_warp).
 // Sub-pixel on top of both: every pick refined to a sixteenth of a pixel from the scores next to it (dc_motion_refine,
 // dc_motion_block_refine) and the frames interpolated bilinearly with integer weights (dc_motion_apply_sub, dc_motion_warp_sub).
+// Wide search beside the exhaustive one, for shifts up to 128: frames and template binned c x c (dc_motion_bin), the coarse pick by
+// dc_motion_ssd + dc_motion_pick on the binned pair, then the full-resolution scores within +-c of c times that pick
+// (dc_motion_ssd_around) and the pick over total shifts (dc_motion_pick_around).
 #include "common.h"
 #include "motion_math.h"
 
@@ -155,11 +158,12 @@ __global__ __launch_bounds__(kThreads) void motion_ssd_kernel(const uint16_t* __
 
 // One wave per score table: every lane scans the candidates lane, lane + 64, ... and the wave folds its 64 partial minima; the
 // order of motion_math.h is total, so the result is the unique minimum whatever the order of the comparisons.  Every lane returns it.
-__device__ __forceinline__ DcShiftCand pick_wave(const int64_t* __restrict__ sc, int S, int lane) {
+// (cy, cx): the centre of a window table (dc_motion_pick_around: the candidates are ordered as total shifts), (0, 0) otherwise.
+__device__ __forceinline__ DcShiftCand pick_wave(const int64_t* __restrict__ sc, int S, int lane, int cy = 0, int cx = 0) {
   const int n = (2 * S + 1) * (2 * S + 1);
-  DcShiftCand b = dc_motion_cand(sc, S, lane < n ? lane : 0);
+  DcShiftCand b = dc_motion_cand_around(sc, S, lane < n ? lane : 0, cy, cx);
   for (int i = lane + kWave; i < n; i += kWave) {
-    const DcShiftCand c = dc_motion_cand(sc, S, i);
+    const DcShiftCand c = dc_motion_cand_around(sc, S, i, cy, cx);
     if (dc_motion_before(c, b)) b = c;
   }
 #pragma unroll
@@ -597,6 +601,191 @@ __global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* _
   }
 }
 
+// ---- wide search: bin, window scores, window pick (the definitions are in include/dcunet.h, the arithmetic in motion_math.h) -------
+// out[t][Y][X] = the rounded mean of the c x c cell (cY.., cX..) of frame t, c = 2^LG.  One memory-bound pass: a thread owns 8
+// consecutive input columns of the c rows of one binned row -- c 16-byte loads where the rows are 16-byte aligned (wide: W % 8 == 0
+// and an aligned base), value by value otherwise -- and stores the 8 / c bins they hold.  Neighbouring threads read neighbouring
+// 16-byte pieces of a row.  The trailing H % c rows and W % c columns are never read for a bin.
+template <int LG>
+__global__ __launch_bounds__(kThreads) void motion_bin_kernel(const uint16_t* __restrict__ frames, int is_unsigned, int tc, int H, int W,
+                                                             uint16_t* __restrict__ out, int wide) {
+  constexpr int C = 1 << LG, PER = kPix / C;
+  const int Hc = H >> LG, Wc = W >> LG;
+  const int G = (Wc * C + kPix - 1) / kPix;              // groups of 8 input columns that hold a binned column
+  const long items = (long)tc * Hc * G;
+  for (long it = (long)blockIdx.x * kThreads + threadIdx.x; it < items; it += (long)gridDim.x * kThreads) {
+    const int g = (int)(it % G);
+    const long row = it / G;                             // t * Hc + Y
+    const int Y = (int)(row % Hc);
+    const long t = row / Hc;
+    const int x0 = kPix * g;
+    const uint16_t* src = frames + (t * H + (long)Y * C) * W + x0;
+    int s[kPix];
+#pragma unroll
+    for (int k = 0; k < kPix; ++k) s[k] = 0;
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+      const uint16_t* p = src + (long)i * W;
+      unsigned w[kPix / 2];
+      if (wide) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+      } else {
+#pragma unroll
+        for (int q = 0; q < kPix / 2; ++q) {
+          const unsigned lo = x0 + 2 * q < W ? p[2 * q] : 0u, hi = x0 + 2 * q + 1 < W ? p[2 * q + 1] : 0u;
+          w[q] = lo | (hi << 16);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kPix; ++k) {
+        const unsigned v = (w[k / 2] >> (16 * (k & 1))) & 0xffffu;
+        s[k] += is_unsigned ? (int)v : (int)(int16_t)v;
+      }
+    }
+    uint16_t* dst = out + row * Wc + (long)PER * g;
+#pragma unroll
+    for (int o = 0; o < PER; ++o) {
+      int sum = 0;
+#pragma unroll
+      for (int j = 0; j < C; ++j) sum += s[o * C + j];
+      if (PER * g + o < Wc) dst[o] = (uint16_t)dc_motion_bin_round(sum, LG);
+    }
+  }
+}
+
+// dc_motion_ssd at the (2D+1)^2 shifts around a centre per frame: the tiling of motion_ssd_kernel -- one workgroup per tile of the
+// radius-S interior (kWaves * R rows x 512 columns) and frame, template values in registers, the frame tile with its D-wide halo in
+// LDS, ssd_rows over the residuals --, with the LDS window's origin moved by the frame's centre (cy, cx) = clamp(mult * rows[f],
+// S - D), formed HERE: LDS (0, 0) is frame (S + j0 + cy - D, S + i0 + cx - D), and because |cy| <= S - D the window's first row
+// is >= 0 and its last, S + (H - 2S - 1) + cy + D, is <= H - 1, likewise the columns -- whatever the table holds, nothing outside
+// the frame is read (what the staging loop does not find inside the frame is read by lanes without pixels only, or masked).
+template <int DMAX, int R>
+__global__ __launch_bounds__(kThreads) void motion_ssd_around_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
+                                                                    const uint16_t* __restrict__ tmpl, int H, int W, int S, int D,
+                                                                    const int* __restrict__ centres, int mult,
+                                                                    unsigned long long* __restrict__ wscores, int tilesX) {
+  constexpr int NK = 2 * DMAX + 1, TH = kWaves * R;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nd = 2 * D + 1, stride = ssd_stride(D), rows = TH + 2 * D;
+  uint16_t* ft = reinterpret_cast<uint16_t*>(smem);
+  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + (size_t)rows * stride * sizeof(uint16_t));
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const int tx = blockIdx.x % tilesX, ty = blockIdx.x / tilesX;
+  const int i0 = tx * kTileW, j0 = ty * TH;              // the tile's first pixel, counted from the interior's corner (S, S)
+  const int IW = W - 2 * S, IH = H - 2 * S;
+  const int left = IW - i0 - kPix * lane, down = IH - j0 - wave * R;
+  const int np = left < 0 ? 0 : (left < kPix ? left : kPix);      // interior pixels of this lane
+  const int nr = down < 0 ? 0 : (down < R ? down : R);            // interior rows of this wave
+  const bool ragged = __ballot(np > 0 && np < kPix) != 0;
+  unsigned mk[kPix];
+#pragma unroll
+  for (int p = 0; p < kPix; ++p) mk[p] = p < np ? 0xffffffffu : 0u;
+  unsigned t2[R][kPix / 2];
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const uint16_t* trow = tmpl + (long)(S + j0 + wave * R + j) * W + S + i0 + kPix * lane;
+#pragma unroll
+    for (int q = 0; q < kPix / 2; ++q) {
+      const unsigned lo = (j < nr && 2 * q < np) ? (trow[2 * q] ^ flip) : 0u;
+      const unsigned hi = (j < nr && 2 * q + 1 < np) ? (trow[2 * q + 1] ^ flip) : 0u;
+      t2[j][q] = lo | (hi << 16);
+    }
+  }
+  for (int f = blockIdx.y; f < tc; f += gridDim.y) {
+    const uint16_t* fr = frames + (long)f * H * W;
+    const int oy = S + j0 + dc_motion_centre(mult, centres[2 * f], S - D) - D;
+    const int ox = S + i0 + dc_motion_centre(mult, centres[2 * f + 1], S - D) - D;
+    __syncthreads();                                     // the readers of the previous frame's tile and totals are done
+    for (int r = wave; r < rows; r += kWaves) {
+      const int gy = oy + r;
+      for (int c = lane; c < stride; c += kWave) {
+        const int gx = ox + c;
+        ft[r * stride + c] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? (uint16_t)(fr[(long)gy * W + gx] ^ flip) : (uint16_t)0;
+      }
+    }
+    for (int i = threadIdx.x; i < nd * nd; i += kThreads) sc[i] = 0;
+    __syncthreads();
+    if (nr > 0) {                                        // wave-uniform
+      for (int m = 0; m < nd; ++m) {
+        unsigned long long acc[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) acc[k] = 0;
+        if (np > 0) {
+          if (ragged) ssd_rows<DMAX, R, true>(ft, stride, D, nd, nr, wave * R + m, lane, t2, mk, acc);
+          else ssd_rows<DMAX, R, false>(ft, stride, D, nd, nr, wave * R + m, lane, t2, mk, acc);
+        }
+        unsigned long long mine = 0;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+          if (k < nd) {
+            const unsigned long long s = wave_sum64(acc[k]);
+            if (lane == k) mine = s;
+          }
+        }
+        if (lane < nd) atomicAdd(&sc[m * nd + lane], mine);
+      }
+    }
+    __syncthreads();
+    unsigned long long* dst = wscores + (long)f * nd * nd;
+    for (int i = threadIdx.x; i < nd * nd; i += kThreads) {
+      const unsigned long long v = sc[i];
+      if (v) atomicAdd(dst + i, v);
+    }
+  }
+}
+
+// One wave per frame: the total shift centre + (ey, ex) under the order of motion_math.h over TOTAL shifts, and (fine non-null) its
+// refinement within the window table at the picked residual -- 0 on an axis where the residual lies on the window's border.
+__global__ __launch_bounds__(kWave) void motion_pick_around_kernel(const int64_t* __restrict__ wscores, const int* __restrict__ centres,
+                                                                  int mult, int tc, int S, int D, int* __restrict__ shifts,
+                                                                  int64_t* __restrict__ best, int* __restrict__ fine) {
+  const int n = (2 * D + 1) * (2 * D + 1), lane = threadIdx.x;
+  for (int f = blockIdx.x; f < tc; f += gridDim.x) {
+    const int cy = dc_motion_centre(mult, centres[2 * f], S - D), cx = dc_motion_centre(mult, centres[2 * f + 1], S - D);
+    const int64_t* sc = wscores + (long)f * n;
+    const DcShiftCand b = pick_wave(sc, D, lane, cy, cx);
+    if (lane == 0) {
+      shifts[2 * f] = b.dy;
+      shifts[2 * f + 1] = b.dx;
+      if (best) best[f] = b.score;
+      if (fine) {
+        const DcSubShift q = dc_motion_refine_entry(sc, D, b.dy - cy, b.dx - cx);
+        fine[2 * f] = dc_motion_fine(b.dy, q.qy);
+        fine[2 * f + 1] = dc_motion_fine(b.dx, q.qx);
+      }
+    }
+  }
+}
+
+template <int LG>
+int launch_bin(const uint16_t* frames, int is_unsigned, int tc, int H, int W, uint16_t* out, hipStream_t stream) {
+  const int Hc = H >> LG, Wc = W >> LG;
+  const long items = (long)tc * Hc * dc_cdiv((long)Wc << LG, kPix), blocks = (items + kThreads - 1) / kThreads;
+  const int wide = (int)(W % kPix == 0 && dc_aligned16(frames));
+  hipLaunchKernelGGL(motion_bin_kernel<LG>, dim3((unsigned)(blocks < (1L << 20) ? blocks : (1L << 20))), dim3(kThreads), 0, stream, frames,
+                     is_unsigned, tc, H, W, out, wide);
+  DC_CHECK_LAUNCH("dc_motion_bin");
+  return DC_OK;
+}
+
+template <int DMAX, int R>
+int launch_ssd_around(const uint16_t* frames, int is_unsigned, int tc, const uint16_t* tmpl, int H, int W, int S, int D, const int* rows,
+                      int mult, unsigned long long* wscores, hipStream_t stream) {
+  static DcLdsAttr lds_attr;
+  const int TH = kWaves * R;
+  const int nd = 2 * D + 1;
+  const int lds = (TH + 2 * D) * ssd_stride(D) * (int)sizeof(uint16_t) + nd * nd * (int)sizeof(unsigned long long);
+  const int lds_max = (TH + 2 * DMAX) * ssd_stride(DMAX) * (int)sizeof(uint16_t) + (2 * DMAX + 1) * (2 * DMAX + 1) * (int)sizeof(unsigned long long);
+  auto kern = motion_ssd_around_kernel<DMAX, R>;
+  if (int rc = dc_func_max_lds(lds_attr, reinterpret_cast<const void*>(kern), lds_max, "dc_motion_ssd_around")) return rc;
+  const int tilesX = dc_cdiv(W - 2 * S, kTileW), tilesY = dc_cdiv(H - 2 * S, TH);
+  const dim3 grid((unsigned)(tilesX * tilesY), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
+  hipLaunchKernelGGL(kern, grid, block, lds, stream, frames, is_unsigned ? 0u : 0x8000u, tc, tmpl, H, W, S, D, rows, mult, wscores, tilesX);
+  DC_CHECK_LAUNCH("dc_motion_ssd_around");
+  return DC_OK;
+}
+
 template <int DMAX>
 int launch_block_ssd(const uint16_t* frames, int is_unsigned, int tc, const uint16_t* tmpl, int H, int W, int S, int D, int By, int Bx,
                      const int* rigid, unsigned long long* bscores, hipStream_t stream) {
@@ -812,5 +1001,64 @@ extern "C" int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, c
   hipLaunchKernelGGL(motion_warp_kernel<true>, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, fine_block_shifts, By, Bx, H, W,
                      (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0), tilesX, is_unsigned ? 0u : 0x8000u);
   DC_CHECK_LAUNCH("dc_motion_warp_sub");
+  return DC_OK;
+}
+
+extern "C" int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H, int W, int c, void* out, dc_stream_t stream) {
+  DC_REQUIRE(frames && out, DC_EINVAL, "dc_motion_bin: null pointer");
+  DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_bin: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  const int lg = dc_motion_bin_log2(c);
+  DC_REQUIRE(lg > 0, DC_EUNSUP, "dc_motion_bin: c = %d: the binning factor is limited to 2, 4 and 8", c);
+  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_bin: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE((H >> lg) > 0 && (W >> lg) > 0, DC_EINVAL, "dc_motion_bin: image %d x %d holds no %d x %d bin", H, W, c, c);
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0, DC_EINVAL, "dc_motion_bin: misaligned buffer");
+  const uintptr_t fb = (uintptr_t)tc * H * W * 2, ob = (uintptr_t)tc * (H >> lg) * (W >> lg) * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
+  DC_REQUIRE(tc == 0 || fa + fb <= oa || oa + ob <= fa, DC_EINVAL, "dc_motion_bin: out overlaps frames");
+  if (tc == 0) return DC_OK;
+  const uint16_t* f = (const uint16_t*)frames;
+  if (lg == 1) return launch_bin<1>(f, is_unsigned, tc, H, W, (uint16_t*)out, (hipStream_t)stream);
+  if (lg == 2) return launch_bin<2>(f, is_unsigned, tc, H, W, (uint16_t*)out, (hipStream_t)stream);
+  return launch_bin<3>(f, is_unsigned, tc, H, W, (uint16_t*)out, (hipStream_t)stream);
+}
+
+// what the two window entry points share: the radii
+#define DC_REQUIRE_WINDOW(name, S, D)                                                                                                        \
+  DC_REQUIRE(S <= DC_MOTION_MAX_WIDE_SHIFT, DC_EUNSUP, name ": S = %d: the wide search radius is limited to %d", S, DC_MOTION_MAX_WIDE_SHIFT); \
+  DC_REQUIRE(D <= DC_MOTION_MAX_DEV, DC_EUNSUP, name ": D = %d: the window half-width is limited to %d", D, DC_MOTION_MAX_DEV);               \
+  DC_REQUIRE(S >= D, DC_EINVAL, name ": S = %d is smaller than the window half-width D = %d", S, D)
+
+extern "C" int dc_motion_ssd_around(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, const int* rows,
+                                    int mult, long* wscores, dc_stream_t stream) {
+  DC_REQUIRE(frames && tmpl && rows && wscores, DC_EINVAL, "dc_motion_ssd_around: null pointer");
+  DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_ssd_around: negative or zero size (tc %d, S %d, D %d, H %d, W %d)",
+             tc, S, D, H, W);
+  DC_REQUIRE_WINDOW("dc_motion_ssd_around", S, D);
+  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_ssd_around: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE(H > 2 * S && W > 2 * S, DC_EINVAL, "dc_motion_ssd_around: image %d x %d has no interior at S = %d (H > 2S and W > 2S)", H, W, S);
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)tmpl) & 1) == 0 && (((uintptr_t)rows) & 3) == 0 && (((uintptr_t)wscores) & 7) == 0, DC_EINVAL,
+             "dc_motion_ssd_around: misaligned buffer");
+  if (tc == 0) return DC_OK;
+  const long n = (long)tc * (2 * D + 1) * (2 * D + 1);
+  unsigned long long* sc = (unsigned long long*)wscores;
+  const int blocks = (int)(dc_cdiv(n, kThreads) < kZeroBlocks ? dc_cdiv(n, kThreads) : kZeroBlocks);
+  hipLaunchKernelGGL(motion_zero_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, sc, n);
+  DC_CHECK_LAUNCH("dc_motion_ssd_around(zero)");
+  const uint16_t* f = (const uint16_t*)frames;
+  const uint16_t* t = (const uint16_t*)tmpl;
+  if (D <= 4) return launch_ssd_around<4, 8>(f, is_unsigned, tc, t, H, W, S, D, rows, mult, sc, (hipStream_t)stream);
+  return launch_ssd_around<8, 8>(f, is_unsigned, tc, t, H, W, S, D, rows, mult, sc, (hipStream_t)stream);
+}
+
+extern "C" int dc_motion_pick_around(const long* wscores, const int* rows, int mult, int tc, int S, int D, int* shifts, long* best, int* fine,
+                                     dc_stream_t stream) {
+  DC_REQUIRE(wscores && rows && shifts, DC_EINVAL, "dc_motion_pick_around: null pointer");
+  DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0, DC_EINVAL, "dc_motion_pick_around: negative size (tc %d, S %d, D %d)", tc, S, D);
+  DC_REQUIRE_WINDOW("dc_motion_pick_around", S, D);
+  DC_REQUIRE((((uintptr_t)wscores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL,
+             "dc_motion_pick_around: misaligned buffer");
+  if (tc == 0) return DC_OK;
+  hipLaunchKernelGGL(motion_pick_around_kernel, dim3((unsigned)(tc < 65535 ? tc : 65535)), dim3(kWave), 0, (hipStream_t)stream,
+                     (const int64_t*)wscores, rows, mult, tc, S, D, shifts, (int64_t*)best, fine);
+  DC_CHECK_LAUNCH("dc_motion_pick_around");
   return DC_OK;
 }

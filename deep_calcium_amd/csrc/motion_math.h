@@ -198,3 +198,49 @@ DC_MOTION_HD int dc_motion_interp(int a00, int a01, int a10, int a11, int fy, in
   const int num = gy * (gx * a00 + fx * a01) + fy * (gx * a10 + fx * a11) + 128;
   return ((num + (1 << 23)) >> 8) - (1 << 15);
 }
+
+// ---- wide search (motion.hip, dc_motion_bin / dc_motion_ssd_around / dc_motion_pick_around): a coarse pick on frames binned c x c,
+// then the scores of the full-resolution shifts within +-D of c times that pick.  Integers only.  (tests/native/motion_wide_check.cpp)
+#ifndef DC_MOTION_MAX_WIDE_SHIFT
+#define DC_MOTION_MAX_WIDE_SHIFT 128     // include/dcunet.h defines the same value
+#endif
+
+// log2 of the binning factor c, -1 where c is not one of 2, 4, 8
+DC_MOTION_HD int dc_motion_bin_log2(int c) { return c == 2 ? 1 : (c == 4 ? 2 : (c == 8 ? 3 : -1)); }
+
+// The value of one bin from the sum of its c x c = 4^lg cells (16-bit values, signed or unsigned: |sum| <= 64 * 65535):
+// floor((sum + c^2 / 2) / c^2), the mean rounded half up -- the rule of the rounded-mean template.  The floor for a negative sum is
+// spelled out (a right shift of a negative value is the compiler's choice before C++20).  The result lies between the smallest
+// and the largest cell, so it fits their dtype.
+DC_MOTION_HD int dc_motion_bin_round(int sum, int lg) {
+  const int k = 2 * lg, a = sum + (1 << (k - 1));
+  return a >= 0 ? a >> k : -((-a + (1 << k) - 1) >> k);
+}
+
+// The centre of a frame's fine window on one axis: clamp(mult * row, -M, M), M = S - D >= 0.  The product is formed in 64 bits, so
+// any int32 row (and any int32 mult) is legal; centre + [-D, D] lies inside [-S, S].
+DC_MOTION_HD int dc_motion_centre(int mult, int row, int M) {
+  const int64_t v = (int64_t)mult * row;
+  return v < -(int64_t)M ? -M : (v > (int64_t)M ? M : (int)v);
+}
+
+// candidate i of the [2D+1][2D+1] window table of one frame (ey the slow axis, index ey + D) as the TOTAL shift centre + (ey, ex):
+// the order of dc_motion_before is then over total shifts, so the pick equals the exhaustive pick of radius S whenever that
+// pick lies inside the window -- an order over the residuals would prefer the candidate nearest the centre instead.
+DC_MOTION_HD DcShiftCand dc_motion_cand_around(const int64_t* wscores, int D, int i, int cy, int cx) {
+  DcShiftCand c = dc_motion_cand(wscores, D, i);
+  c.dy += cy;
+  c.dx += cx;
+  return c;
+}
+
+// the picked total shift of one frame: a serial scan (what the kernel's strided scan + wave reduction must equal)
+DC_MOTION_HD DcShiftCand dc_motion_pick_around_serial(const int64_t* wscores, int D, int cy, int cx) {
+  const int nd = 2 * D + 1;
+  DcShiftCand best = dc_motion_cand_around(wscores, D, 0, cy, cx);
+  for (int i = 1; i < nd * nd; ++i) {
+    const DcShiftCand c = dc_motion_cand_around(wscores, D, i, cy, cx);
+    if (dc_motion_before(c, best)) best = c;
+  }
+  return best;
+}

@@ -56,9 +56,31 @@ dc_motion_warp_sub).  Still integers only -- fine shifts are int32 in sixteenths
 Interpolation averages up to four values, so at fractional shifts it lowers the pixel noise: `std` and `corr` of a
 sub-pixel-corrected recording are not comparable bit for bit with those of a whole-pixel-corrected one.
 
-Scope: shifts found by exhaustive whole-pixel search, max_shift <= 16, max_dev <= 8, at most 32 x 32 blocks, refined to 1/16
-pixel by a parabola fit, bilinear interpolation.  Template building with sub-pixel or block shifts, temporal smoothing of the
-shifts, FFT methods, other interpolation kernels and larger search radii are not implemented.
+Wide search (coarse=c, c in 2, 4, 8; max_shift in [c, 16 c], so up to 128): the exhaustive search costs (2S+1)^2 passes and is
+capped at 16 pixels, less than a behaving animal moves the field of view.  With coarse=c frames and template are binned c x c
+(dc_motion_bin: the mean rounded half up, trailing rows and columns dropped), the unchanged exhaustive search finds a coarse
+shift on the binned frames within +-ceil(max_shift / c), and the full-resolution scores are computed only within +-c of c times
+that shift, clamped so that the window stays inside +-max_shift (dc_motion_ssd_around, dc_motion_pick_around):
+
+    what            dtype            exactness
+    coarse shifts   int32 (t, 2)     exact: the pick of the binned frames against the binned template, unscaled
+    scores          int64            exact: (t, 2c+1, 2c+1), the entries centre + (ey, ex) of the exhaustive table of radius S,
+                                     centre = clamp(c * coarse, -(S - c), S - c) per component
+    shifts          int32 (t, 2)     exact: the argmin of (score, dy^2 + dx^2, dy, dx) over the TOTAL shifts of the window
+
+This is NOT the exhaustive argmin of radius max_shift: it is that argmin whenever it lies within +-c of the clamped c * coarse
+pick (a scene whose coarse structure is ambiguous can send the window to the wrong place).  With subpixel=True the pick is
+refined within the window table; a pick on the window's border is not refined (q = 0 on that axis).
+
+    mc = MotionCorrector((H, W), T, np.int16, template, max_shift=48, coarse=4)
+    for chunk in chunks: corrected = mc.feed(chunk)
+    shifts, coarse = mc.shifts(), mc.coarse_shifts()
+    shifts, template = estimate_shifts_device('dataset.hdf5', max_shift=48, coarse=4)
+
+Scope: shifts found by exhaustive whole-pixel search, max_shift <= 16 -- or by the two-level wide search, max_shift <= 128,
+rigid only --, max_dev <= 8, at most 32 x 32 blocks, refined to 1/16 pixel by a parabola fit, bilinear interpolation.  Template
+building with sub-pixel or block shifts, temporal smoothing of the shifts, FFT methods, other interpolation kernels,
+piecewise-rigid blocks on top of a wide search and more than two levels are not implemented.
 
 Importing this module needs neither torch nor the GPU; constructing a MotionCorrector does (there is no CPU fallback).
 """
@@ -71,6 +93,8 @@ MAX_SHIFT = 16                        # DC_MOTION_MAX_SHIFT
 MAX_DEV = 8                           # DC_MOTION_MAX_DEV
 MAX_BLOCKS = 32                       # DC_MOTION_MAX_BLOCKS
 SUBPIXEL = 16                         # DC_MOTION_SUB: fine shifts are int32 in units of 1 / SUBPIXEL of a pixel
+MAX_WIDE_SHIFT = 128                  # DC_MOTION_MAX_WIDE_SHIFT: the largest max_shift of the wide search (coarse=8)
+COARSE = (2, 4, 8)                    # the binning factors of the wide search
 
 
 def _check_max_shift(max_shift, shape=None):
@@ -83,6 +107,31 @@ def _check_max_shift(max_shift, shape=None):
         raise ValueError('max_shift = %d leaves no interior in a %d x %d frame: H > 2 * max_shift and W > 2 * max_shift'
                          % (S, shape[0], shape[1]))
     return S
+
+
+def _check_coarse(coarse, max_shift, shape=None, blocks=None):
+    """coarse=c and max_shift of the wide search -> (c, S): c in 2, 4, 8, S in [c, 16 c], and the frame keeps an interior at both
+    levels: H > 2S, W > 2S, and floor(H / c) > 2 ceil(S / c), floor(W / c) > 2 ceil(S / c) for the binned frame."""
+    if isinstance(coarse, bool) or not isinstance(coarse, (int, np.integer)) or int(coarse) not in COARSE:
+        raise ValueError('coarse must be None or one of 2, 4, 8, not %r' % (coarse,))
+    c = int(coarse)
+    if blocks is not None:
+        raise ValueError('blocks together with coarse = %d is not built: the piecewise-rigid mode needs max_shift <= %d' % (c, MAX_SHIFT))
+    if isinstance(max_shift, bool) or not isinstance(max_shift, (int, np.integer)):
+        raise ValueError('max_shift must be an integer in [%d, %d] with coarse = %d, not %r' % (c, MAX_SHIFT * c, c, max_shift))
+    S = int(max_shift)
+    if not c <= S <= MAX_SHIFT * c:
+        raise ValueError('max_shift must be in [%d, %d] with coarse = %d, not %d' % (c, MAX_SHIFT * c, c, S))
+    if shape is not None:
+        H, W = shape
+        Sc = -(-S // c)
+        if H <= 2 * S or W <= 2 * S:
+            raise ValueError('max_shift = %d with coarse = %d leaves no interior in a %d x %d frame: H > 2 * max_shift and '
+                             'W > 2 * max_shift' % (S, c, H, W))
+        if H // c <= 2 * Sc or W // c <= 2 * Sc:
+            raise ValueError('coarse = %d leaves no interior in the binned %d x %d frame at the coarse radius %d'
+                             % (c, H // c, W // c, Sc))
+    return c, S
 
 
 def block_edges(n, B):
@@ -169,7 +218,7 @@ class MotionCorrector(object):
     """Owns the device state of one recording's registration; feed() the frames in order, in chunks of any size."""
 
     def __init__(self, shape, n_frames, dtype, template, max_shift=8, fill=0, device=None, chunk_frames=None, blocks=None,
-                 max_dev=3, subpixel=False):
+                 max_dev=3, subpixel=False, coarse=None):
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         H, W = shape
@@ -177,7 +226,11 @@ class MotionCorrector(object):
         if n_frames < 1:
             raise ValueError('n_frames must be >= 1, not %d' % n_frames)
         self.dtype = _frame_dtype(dtype)
-        self.max_shift = _check_max_shift(max_shift, shape)
+        self.coarse = None
+        if coarse is None:
+            self.max_shift = _check_max_shift(max_shift, shape)
+        else:                              # the wide search: max_shift in [c, 16 c], rigid only
+            self.coarse, self.max_shift = _check_coarse(coarse, max_shift, shape, blocks)
         self.fill = _check_fill(fill)
         self.subpixel = _check_subpixel(subpixel)
         self.blocks, self.max_dev = None, None
@@ -207,11 +260,23 @@ class MotionCorrector(object):
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
-        dev, nd = self.device, 2 * self.max_shift + 1
+        dev, nd = self.device, 2 * (self.max_shift if self.coarse is None else self.coarse) + 1
         self.template = template
         self._tmpl = torch.from_numpy(template.view(np.int16)).to(dev)
         self._shifts = torch.zeros((n_frames, 2), dtype=torch.int32, device=dev)
         self._scores = torch.empty((self.chunk_frames, nd, nd), dtype=torch.int64, device=dev)      # fully written by every chunk
+        if self.coarse is not None:        # the binned template, made once; the chunk's binned frames and their coarse tables
+            c = self.coarse
+            Hc, Wc, Sc = H // c, W // c, -(-self.max_shift // c)
+            self._cshape, self._cradius = (Hc, Wc), Sc
+            self._tmpl_c = torch.empty((Hc, Wc), dtype=torch.int16, device=dev)
+            self._binned = torch.empty((self.chunk_frames, Hc, Wc), dtype=torch.int16, device=dev)
+            self._cscores = torch.empty((self.chunk_frames, 2 * Sc + 1, 2 * Sc + 1), dtype=torch.int64, device=dev)
+            self._coarse = torch.zeros((n_frames, 2), dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                self.L.dc_motion_bin(self._tmpl.data_ptr(), int(self.dtype == np.dtype(np.uint16)), 1, H, W, c, self._tmpl_c.data_ptr(),
+                                     self._stream().cuda_stream)
+                self._stream().synchronize()         # feed() may run on another stream
         if self.blocks is not None:
             (By, Bx), nb = self.blocks, 2 * self.max_dev + 1
             self._bshifts = torch.zeros((n_frames, By, Bx, 2), dtype=torch.int32, device=dev)
@@ -228,8 +293,19 @@ class MotionCorrector(object):
         L, S = self.L, self.max_shift
         uns = int(self.dtype == np.dtype(np.uint16))
         rows = self._shifts.data_ptr() + 8 * self.fed
-        L.dc_motion_ssd(fp, uns, tc, self._tmpl.data_ptr(), H, W, S, self._scores.data_ptr(), st)
-        L.dc_motion_pick(self._scores.data_ptr(), tc, S, rows, None, st)
+        if self.coarse is not None:
+            # the wide search: the exhaustive pick on the binned frames, then the full-resolution window around c times it
+            c, (Hc, Wc), Sc = self.coarse, self._cshape, self._cradius
+            crows = self._coarse.data_ptr() + 8 * self.fed
+            frows = self._fine.data_ptr() + 8 * self.fed if self.subpixel else None
+            L.dc_motion_bin(fp, uns, tc, H, W, c, self._binned.data_ptr(), st)
+            L.dc_motion_ssd(self._binned.data_ptr(), uns, tc, self._tmpl_c.data_ptr(), Hc, Wc, Sc, self._cscores.data_ptr(), st)
+            L.dc_motion_pick(self._cscores.data_ptr(), tc, Sc, crows, None, st)
+            L.dc_motion_ssd_around(fp, uns, tc, self._tmpl.data_ptr(), H, W, S, c, crows, c, self._scores.data_ptr(), st)
+            L.dc_motion_pick_around(self._scores.data_ptr(), crows, c, tc, S, c, rows, None, frows, st)
+        else:
+            L.dc_motion_ssd(fp, uns, tc, self._tmpl.data_ptr(), H, W, S, self._scores.data_ptr(), st)
+            L.dc_motion_pick(self._scores.data_ptr(), tc, S, rows, None, st)
         if self.blocks is not None:
             (By, Bx), D = self.blocks, self.max_dev
             brows = self._bshifts.data_ptr() + 8 * By * Bx * self.fed
@@ -244,7 +320,8 @@ class MotionCorrector(object):
                 L.dc_motion_warp(fp, tc, brows, By, Bx, H, W, self.fill, out, st)
         elif self.subpixel:
             frows = self._fine.data_ptr() + 8 * self.fed
-            L.dc_motion_refine(self._scores.data_ptr(), rows, tc, S, frows, st)
+            if self.coarse is None:        # the wide search has refined its pick within the window table already
+                L.dc_motion_refine(self._scores.data_ptr(), rows, tc, S, frows, st)
             if out is not None:
                 L.dc_motion_apply_sub(fp, uns, tc, frows, H, W, self.fill, out, st)
         elif out is not None:
@@ -304,8 +381,29 @@ class MotionCorrector(object):
 
     def last_scores(self):
         """(t, 2S+1, 2S+1) int64 numpy array: the scores of the last piece of at most chunk_frames frames that was registered
-        (dy the slow axis, index dy + S) -- score minus the frame's minimum is a confidence measure."""
+        (dy the slow axis, index dy + S) -- score minus the frame's minimum is a confidence measure.  With coarse=c: the window
+        table (t, 2c+1, 2c+1) around each frame's centre clamp(c * coarse shift, max_shift - c) (ey the slow axis, index ey + c)."""
         return self._scores[:self._last].cpu().numpy()
+
+    def _need_coarse(self):
+        if self.coarse is None:
+            raise ValueError('this corrector searches exhaustively: coarse shifts need coarse=2, 4 or 8')
+
+    def coarse_shifts_device(self):
+        """The int32 (n_frames, 2) tensor of the coarse picks on the device, in binned pixels (unscaled); rows [0, fed) are set."""
+        self._need_coarse()
+        return self._coarse
+
+    def coarse_shifts(self):
+        """(fed, 2) int32 numpy array: the pick of every binned frame against the binned template, in binned pixels."""
+        self._need_coarse()
+        return self._coarse[:self.fed].cpu().numpy()
+
+    def last_coarse_scores(self):
+        """(t, 2Sc+1, 2Sc+1) int64 numpy array, Sc = ceil(max_shift / coarse): the scores of the binned frames of the last piece
+        that was registered."""
+        self._need_coarse()
+        return self._cscores[:self._last].cpu().numpy()
 
     def _need_blocks(self):
         if self.blocks is None:
@@ -361,16 +459,16 @@ def _widen(torch, chunk, unsigned):
     return v & 0xffff if unsigned else v
 
 
-def make_template(frames, max_shift=8, iterations=1, device=None):
+def make_template(frames, max_shift=8, iterations=1, device=None, coarse=None):
     """A template for `frames` (N, H, W) numpy int16 / uint16: the rounded mean floor((2 * sum + N) / (2 N)) of the frames, then
     `iterations` times: register the frames to the template (fill 0) and take the rounded mean of the corrected frames.
-    Returns (H, W) of the frames' dtype."""
+    coarse=c: the registration is the wide search (max_shift in [c, 16 c]).  Returns (H, W) of the frames' dtype."""
     if not isinstance(frames, np.ndarray) or frames.ndim != 3 or frames.shape[0] < 1:
         raise ValueError('frames must be a (N, H, W) numpy array with N >= 1, not %s' %
                          (type(frames).__name__ if not isinstance(frames, np.ndarray) else repr(tuple(frames.shape))))
     dtype = _frame_dtype(frames.dtype)
     shape = _check_shape(frames.shape[1:])
-    S = _check_max_shift(max_shift, shape)
+    S = _check_max_shift(max_shift, shape) if coarse is None else _check_coarse(coarse, max_shift, shape)[1]
     if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
         raise ValueError('iterations must be an integer >= 0, not %r' % (iterations,))
     import torch
@@ -388,7 +486,7 @@ def make_template(frames, max_shift=8, iterations=1, device=None):
             total += _widen(torch, chunk, uns).sum(0)
         tmpl = _rounded_mean(torch, total, N).to(torch.int16).cpu().numpy().view(dtype)
         for _ in range(int(iterations)):
-            mc = MotionCorrector(shape, N, dtype, tmpl, max_shift=S, fill=0, device=dev, chunk_frames=step)
+            mc = MotionCorrector(shape, N, dtype, tmpl, max_shift=S, fill=0, device=dev, chunk_frames=step, coarse=coarse)
             total.zero_()
             for a in range(0, N, step):
                 total += _widen(torch, mc.feed(np.ascontiguousarray(frames[a:a + step])), uns).sum(0)
@@ -397,15 +495,19 @@ def make_template(frames, max_shift=8, iterations=1, device=None):
 
 
 def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=200, source='series/raw', device=None,
-                           chunk_frames=None, blocks=None, max_dev=3, subpixel=False):
+                           chunk_frames=None, blocks=None, max_dev=3, subpixel=False, coarse=None):
     """(shifts, template): the (T, 2) int32 (dy, dx) of every frame of `source` of a dataset file against `template` -- built
     by make_template (one iteration) from the first min(T, template_frames) frames when none is given.  The recording is
     streamed once, memory-mapped or sliced, never read whole; nothing is corrected here: pass `shifts` to
     summarize_series_device / extract_traces_device.  blocks=(By, Bx): the (T, By, Bx, 2) int32 block shifts within
     +-max_dev of each frame's rigid shift instead (the template is still built rigidly); `shifts=` takes them as they are.
     subpixel=True: the fine shifts in sixteenths of a pixel instead, in the same shapes (the template is still built from
-    whole-pixel corrections); `fine_shifts=` takes them as they are."""
-    _check_max_shift(max_shift)
+    whole-pixel corrections); `fine_shifts=` takes them as they are.  coarse=c: every search, the template's included, is the
+    wide search (max_shift in [c, 16 c], rigid only); the shifts may then exceed 16 pixels, which `shifts=` takes as well."""
+    if coarse is None:
+        _check_max_shift(max_shift)
+    else:
+        _check_coarse(coarse, max_shift, None, blocks)
     subpixel = _check_subpixel(subpixel)
     if blocks is not None:
         _check_blocks(blocks, max_dev)
@@ -417,13 +519,14 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         shape = tuple(int(v) for v in frames.shape[1:])
-        S = _check_max_shift(max_shift, shape)
+        S = _check_max_shift(max_shift, shape) if coarse is None else _check_coarse(coarse, max_shift, shape, blocks)[1]
         if template is None:
-            template = make_template(np.asarray(frames[:min(T, int(template_frames))]), max_shift=S, iterations=1, device=device)
+            template = make_template(np.asarray(frames[:min(T, int(template_frames))]), max_shift=S, iterations=1, device=device,
+                                     coarse=coarse)
         if blocks is not None:
             _check_blocks(blocks, max_dev, shape, S)
         mc = MotionCorrector(shape, T, frames.dtype, template, max_shift=S, device=device, chunk_frames=chunk_frames, blocks=blocks,
-                             max_dev=max_dev, subpixel=subpixel)
+                             max_dev=max_dev, subpixel=subpixel, coarse=coarse)
         for a in range(0, T, mc.chunk_frames):
             mc.feed(np.asarray(frames[a:a + mc.chunk_frames]), correct=False)
         out = mc.fine_shifts() if subpixel else (mc.shifts() if blocks is None else mc.block_shifts())

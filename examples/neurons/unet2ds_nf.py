@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -121,7 +121,7 @@ def _neuropil_arg(text):
 
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
-           percentile=8, neuropil=None, refine=None, halo=2):
+           percentile=8, neuropil=None, refine=None, halo=2, coarse=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -129,6 +129,8 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     `series/mean`, and the traces are summed over the registered frames.  blocks=(By, Bx) with register: piecewise-rigid -- every
     block of the frame gets the rigid shift plus a residual within +-max_dev, and the frames are warped by the blended field.
     subpixel with register: every shift is refined to a sixteenth of a pixel and the frames are interpolated bilinearly.
+    coarse=C (2, 4 or 8) with register: the wide search -- a coarse shift on frames binned C x C, then the whole-pixel shifts within
+    +-C of it --, which lets S reach 16 C (`--register 48 --coarse 4`); rigid only.
     dff=WINDOW: instead of `kind`, the traces are dF/F against a rolling-percentile baseline over WINDOW frames (odd; `percentile`,
     default 8), after subtracting neuropil=(inner, outer, weight) times the trace of a ring around every ROI when given.
     refine=THR: a first pass over the recording computes every ROI's footprint map (the correlation of each pixel of the ROI and of
@@ -139,6 +141,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--blocks needs --register')
     if subpixel and register is None:
         raise ValueError('--subpixel needs --register')
+    if coarse is not None and register is None:
+        raise ValueError('--coarse needs --register')
+    if coarse is not None and blocks is not None:
+        raise ValueError('--coarse together with --blocks is not built: the piecewise-rigid mode needs --register <= 16')
     if dff is None and neuropil is not None:
         raise ValueError('--neuropil needs --dff')
     known = 'fine_shifts' if subpixel else 'shifts'
@@ -147,9 +153,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     shifts = {}
     if register is not None:
         for dspath in dspaths:
-            shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register, blocks=blocks, max_dev=max_dev, subpixel=subpixel)
-            logger.info('%s: registered within +-%d%s%s, largest |dy|, |dx| = %g, %g, valid rectangle %r' % (
-                dspath, register, '' if blocks is None else ' in %d x %d blocks within +-%d of that' % (blocks + (max_dev,)),
+            shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register, blocks=blocks, max_dev=max_dev, subpixel=subpixel,
+                                                          coarse=coarse)
+            logger.info('%s: registered within +-%d%s%s%s, largest |dy|, |dx| = %g, %g, valid rectangle %r' % (
+                dspath, register, '' if coarse is None else ' (wide search, binned %d x %d)' % (coarse, coarse), '' if blocks is None else ' in %d x %d blocks within +-%d of that' % (blocks + (max_dev,)),
                 ', refined to 1/16 pixel' if subpixel else '',
                 np.abs(shifts[dspath][..., 0]).max() / unit, np.abs(shifts[dspath][..., 1]).max() / unit,
                 valid_rectangle(shifts[dspath], tmpl.shape, fine=subpixel)))
@@ -217,6 +224,8 @@ if __name__ == '__main__':
                         type=_blocks_arg, metavar='ByxBx')
     sp_trc.add_argument('--max-dev', help='with --blocks: a block may deviate from the rigid shift by +-D pixels (default 3)', default=3,
                         type=int, metavar='D', dest='max_dev')
+    sp_trc.add_argument('--coarse', help='with --register: the wide search, a coarse shift on frames binned C x C first; S may then reach 16 C',
+                        default=None, type=int, choices=(2, 4, 8), metavar='C')
     sp_trc.add_argument('--subpixel', help='with --register: refine every shift to 1/16 pixel and interpolate the frames', action='store_true')
     sp_trc.add_argument('--dff', help='write dF/F against a rolling-percentile baseline over WINDOW frames (odd) instead of --kind', default=None,
                         type=int, metavar='WINDOW')

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 117
+#define DC_ABI_VERSION 118
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -641,7 +641,8 @@ int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float
  * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
  * examples/neurons/unet2ds_sj.py, were registered by an outside tool: it reads directories named ..._stabilized).  This is that
  * step: rigid, whole-pixel translation, found by exhaustive search within +-S, S <= DC_MOTION_MAX_SHIFT; the piecewise-rigid
- * mode built on it and the sub-pixel refinement of both follow below.  FFT methods are out of scope.  Integer
+ * mode built on it, the sub-pixel refinement of both and the two-level wide search (radii up to DC_MOTION_MAX_WIDE_SHIFT) follow
+ * below.  FFT methods are out of scope.  Integer
  * arithmetic only: every result is exact, so the chunking
  * of a recording never changes a bit.
  * frames: as for dc_series_accumulate (int16 / uint16 by is_unsigned, [tc][H][W] contiguous, 2-byte aligned); tmpl: [H][W] of the
@@ -739,6 +740,35 @@ int dc_motion_apply_sub(const void* frames, int is_unsigned, int tc, const int* 
                         dc_stream_t stream);
 int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, const int* fine_block_shifts, int By, int Bx, int H, int W, int fill,
                        void* out, dc_stream_t stream);
+
+/* ---- wide search: shifts beyond DC_MOTION_MAX_SHIFT by a two-level, coarse-to-fine search -------------------------------------
+ * The exhaustive search costs (2S+1)^2 passes over the interior, so its radius is capped at 16.  The wide search finds a coarse
+ * shift on frames and template binned c x c (the unchanged dc_motion_ssd + dc_motion_pick at radius Sc = ceil(S / c) <= 16), then
+ * scores the full-resolution shifts within +-D, D = c, of c times that pick.  Integers only, the sign convention above.  It is
+ * NOT the exhaustive argmin of radius S: it is that argmin whenever it lies within +-D of the clamped centre (below).
+ * c in {2, 4, 8}; S in [D, DC_MOTION_MAX_WIDE_SHIFT]; D <= DC_MOTION_MAX_DEV; H > 2S and W > 2S.
+ *   dc_motion_bin: out = [tc][Hc][Wc] of the frames' 16-bit type, Hc = floor(H / c), Wc = floor(W / c) (trailing rows and columns
+ *     are dropped): out[t][Y][X] = floor((sum over i, j in [0, c) of frame[cY+i][cX+j] + c^2/2) / c^2), the mean rounded half up,
+ *     the floor holding for negative sums.  The result lies between the cell's smallest and largest value.  Template and frames
+ *     are binned by this one function.  c not 2, 4 or 8: DC_EUNSUP; Hc or Wc == 0, or out overlapping frames: DC_EINVAL.
+ *   dc_motion_ssd_around: wscores = int64[tc][2D+1][2D+1], ey the slow axis (index ey + D), fully written (never pre-clear):
+ *     wscores[t][ey+D][ex+D] = sum over y in [S, H-S), x in [S, W-S) of (tmpl[y][x] - frame[y+cy+ey][x+cx+ex])^2 with the CENTRE
+ *     (cy, cx) = clamp(mult * rows[t], -(S-D), S-D) per component -- rows = int32[tc][2] (e.g. the coarse dc_motion_pick rows,
+ *     mult = c), read on the device, the product formed in 64 bits and clamped there: any int32 row and mult are legal and
+ *     nothing outside the frame is read.  These are the entries (cy+ey, cx+ex) of the dc_motion_ssd table of radius S: the same
+ *     pixels, the same bound (< 2^62).  D = 0 is legal (one score per frame).
+ *   dc_motion_pick_around: shifts = int32[tc][2], the TOTAL shift (dy, dx) = centre + (ey, ex) that minimises (wscore,
+ *     dy^2 + dx^2, dy, dx) lexicographically -- the order of dc_motion_pick over total shifts, not residuals, so the result equals
+ *     the exhaustive pick of radius S whenever that pick lies in the window.  best = int64[tc] (nullable: the picked score).
+ *     fine = int32[tc][2] (nullable): 16 * shift + q, q the REFINEMENT above of the picked residual within the window table --
+ *     q = 0 on an axis where the residual lies on the window's border (such a pick is not refined) or where the denominator is 0.
+ * S > 128, D > 8 or H * W > 2^30: DC_EUNSUP (-3); S < D or no interior: DC_EINVAL.  tc == 0 launches nothing. */
+#define DC_MOTION_MAX_WIDE_SHIFT 128
+int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H, int W, int c, void* out, dc_stream_t stream);
+int dc_motion_ssd_around(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, const int* rows,
+                         int mult, long* wscores, dc_stream_t stream);
+int dc_motion_pick_around(const long* wscores, const int* rows, int mult, int tc, int S, int D, int* shifts, long* best, int* fine,
+                          dc_stream_t stream);
 
 /* ---- UNet1D spike inference: traces in, spike probabilities out ------------------------------------------------------------
  * The reference's second model family, UNet1DSegmentation: the network unet1d (unet_1d_segmentation.py:49-148) as its predict()
