@@ -11,6 +11,10 @@
 // Wide search beside the exhaustive one, for shifts up to 128: frames and template binned c x c (dc_motion_bin), the coarse pick by
 // dc_motion_ssd + dc_motion_pick on the binned pair, then the full-resolution scores within +-c of c times that pick
 // (dc_motion_ssd_around) and the pick over total shifts (dc_motion_pick_around).
+// Every piece exists once.  The exhaustive entry points are the window ones at centre 0: motion_ssd_kernel scores the shifts within
+// +-D of a centre per frame (dc_motion_ssd: D = S, no centres) and motion_pick_kernel picks over centre + residual.  The two score
+// kernels (frame-wide tiles, tiles of a block) are built from the same four tile_* pieces around ssd_rows; the movers
+// motion_apply_kernel<SUB> and motion_warp_kernel<SUB> end in the same put8 / put1 (whole-pixel move or interpolation).
 #include "common.h"
 #include "motion_math.h"
 
@@ -78,36 +82,24 @@ __device__ __forceinline__ void ssd_rows(const uint16_t* __restrict__ ft, int st
   }
 }
 
-// One workgroup per tile of the template's INTERIOR (kWaves * R rows x 512 columns) and frame.  The frame tile with its S-wide halo
-// is staged in LDS once (values with the sign bit flipped for int16: both operands move by 32768, the difference does not) and
-// reused for all nd^2 shifts; a lane owns kPix consecutive interior pixels of R rows, whose template values stay in registers.
-// Per dy the lane keeps one 64-bit sum per dx, the wave adds them by shuffles, lane k takes the total of dx = k - S, and the
-// workgroup's nd^2 totals meet in LDS (integer atomics) before ONE 64-bit atomic per shift and workgroup goes to memory (integer
-// addition: the order does not matter, the result is bit-reproducible).
-template <int SMAX, int R>
-__global__ __launch_bounds__(kThreads) void motion_ssd_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
-                                                             const uint16_t* __restrict__ tmpl, int H, int W, int S,
-                                                             unsigned long long* __restrict__ scores, int tilesX) {
-  constexpr int NK = 2 * SMAX + 1, TH = kWaves * R;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nd = 2 * S + 1, stride = ssd_stride(S), rows = TH + 2 * S;
-  uint16_t* ft = reinterpret_cast<uint16_t*>(smem);
-  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + (size_t)rows * stride * sizeof(uint16_t));
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const int tx = blockIdx.x % tilesX, ty = blockIdx.x / tilesX;
-  const int i0 = tx * kTileW, j0 = ty * TH;              // the tile's first interior pixel = frame coordinates of LDS (0, 0)
-  const int IW = W - 2 * S, IH = H - 2 * S;
-  const int left = IW - i0 - kPix * lane, down = IH - j0 - wave * R;
-  const int np = left < 0 ? 0 : (left < kPix ? left : kPix);      // interior pixels of this lane
-  const int nr = down < 0 ? 0 : (down < R ? down : R);            // interior rows of this wave
-  const bool ragged = __ballot(np > 0 && np < kPix) != 0;
-  unsigned mk[kPix];
+// ---- the pieces of one score tile, shared by motion_ssd_kernel and motion_block_ssd_kernel ----------------------------------------
+// LDS of a score launch: the frame tile of th interior rows with its D-wide halo, then the (2D+1)^2 totals of the workgroup
+__host__ __device__ inline size_t tile_bytes(int th, int stride, int D) { return (size_t)(th + 2 * D) * stride * sizeof(uint16_t); }
+inline int ssd_lds(int th, int stride, int D) { return (int)tile_bytes(th, stride, D) + (2 * D + 1) * (2 * D + 1) * (int)sizeof(long long); }
+
+// the mask of a lane that owns np of its kPix pixels; true where some lane of the wave is ragged (0 < np < kPix)
+__device__ __forceinline__ bool tile_mask(int np, unsigned (&mk)[kPix]) {
 #pragma unroll
   for (int p = 0; p < kPix; ++p) mk[p] = p < np ? 0xffffffffu : 0u;
-  unsigned t2[R][kPix / 2];
+  return __ballot(np > 0 && np < kPix) != 0;
+}
+
+// the lane's template pixels, nr rows of np from t0 on (the sign bit flipped for int16), packed in pairs; 0 beyond nr and np
+template <int R>
+__device__ __forceinline__ void tile_tmpl(const uint16_t* __restrict__ t0, int W, int nr, int np, unsigned flip, unsigned (&t2)[R][kPix / 2]) {
 #pragma unroll
   for (int j = 0; j < R; ++j) {
-    const uint16_t* trow = tmpl + (long)(S + j0 + wave * R + j) * W + S + i0 + kPix * lane;
+    const uint16_t* trow = t0 + (long)j * W;
 #pragma unroll
     for (int q = 0; q < kPix / 2; ++q) {
       const unsigned lo = (j < nr && 2 * q < np) ? (trow[2 * q] ^ flip) : 0u;
@@ -115,38 +107,88 @@ __global__ __launch_bounds__(kThreads) void motion_ssd_kernel(const uint16_t* __
       t2[j][q] = lo | (hi << 16);
     }
   }
-  for (int f = blockIdx.y; f < tc; f += gridDim.y) {
-    const uint16_t* fr = frames + (long)f * H * W;
-    __syncthreads();                                     // the readers of the previous frame's tile and totals are done
-    for (int r = wave; r < rows; r += kWaves) {
-      const int gy = j0 + r;
-      for (int c = lane; c < stride; c += kWave) {
-        const int gx = i0 + c;
-        ft[r * stride + c] = (gy < H && gx < W) ? (uint16_t)(fr[(long)gy * W + gx] ^ flip) : (uint16_t)0;
+}
+
+// the frame window of rows x cols values whose LDS (0, 0) is frame (oy, ox), values with the sign bit flipped for int16 (both
+// operands move by 32768, the difference does not); 0 outside the frame, which the callers' origins make unreachable for a pixel
+// that counts: what is not found inside the frame is read by lanes without pixels only, or masked
+__device__ __forceinline__ void tile_stage(uint16_t* __restrict__ ft, int stride, const uint16_t* __restrict__ fr, int H, int W, int oy, int ox,
+                                           int rows, int cols, unsigned flip, int wave, int lane) {
+  for (int r = wave; r < rows; r += kWaves) {
+    const int gy = oy + r;
+    for (int c = lane; c < cols; c += kWave) {
+      const int gx = ox + c;
+      ft[r * stride + c] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? (uint16_t)(fr[(long)gy * W + gx] ^ flip) : (uint16_t)0;
+    }
+  }
+}
+
+// One staged window scored at all nd^2 residuals: per ey the lane (column col of its row group, rows row0 ..) keeps one 64-bit sum
+// per ex, the wave adds them by shuffles -- EVERY lane of the wave takes part, whether it owns pixels or not --, lane k takes the
+// total of ex = k - D and adds it to the workgroup's totals sc in LDS (an integer atomic).  sc is the caller's to zero and flush.
+template <int RMAX, int R>
+__device__ __forceinline__ void tile_score(const uint16_t* __restrict__ ft, int stride, int D, int nr, int np, bool ragged, int row0, int col,
+                                           int lane, const unsigned (&t2)[R][kPix / 2], const unsigned (&mk)[kPix],
+                                           unsigned long long* __restrict__ sc) {
+  constexpr int NK = 2 * RMAX + 1;
+  const int nd = 2 * D + 1;
+  for (int m = 0; m < nd; ++m) {
+    unsigned long long acc[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) acc[k] = 0;
+    if (np > 0 && nr > 0) {
+      if (ragged) ssd_rows<RMAX, R, true>(ft, stride, D, nd, nr, row0 + m, col, t2, mk, acc);
+      else ssd_rows<RMAX, R, false>(ft, stride, D, nd, nr, row0 + m, col, t2, mk, acc);
+    }
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      if (k < nd) {
+        const unsigned long long s = wave_sum64(acc[k]);
+        if (lane == k) mine = s;
       }
     }
+    if (lane < nd) atomicAdd(&sc[m * nd + lane], mine);
+  }
+}
+
+// The scores of the (2D+1)^2 shifts within +-D of a centre (cy, cx) per frame, summed over the radius-S interior.  One workgroup
+// per tile of that INTERIOR (kWaves * R rows x 512 columns) and frame.  The frame tile with its D-wide halo is staged in LDS once
+// and reused for all nd^2 shifts; a lane owns kPix consecutive interior pixels of R rows, whose template values stay in registers.
+// The workgroup's nd^2 totals meet in LDS (tile_score) before ONE 64-bit atomic per shift and workgroup goes to memory (integer
+// addition: the order does not matter, the result is bit-reproducible).
+// centres == nullptr (dc_motion_ssd, with D = S): centre 0, the exhaustive table; LDS (0, 0) is then frame (j0, i0).  Otherwise
+// (dc_motion_ssd_around) the centre is clamp(mult * centres[f], S - D), formed HERE: LDS (0, 0) is frame (S + j0 + cy - D,
+// S + i0 + cx - D), and because |cy| <= S - D the window's first row is >= 0 and its last, S + (H - 2S - 1) + cy + D, is
+// <= H - 1, likewise the columns -- whatever the table holds, nothing outside the frame is read for a pixel that counts.
+template <int RMAX, int R>
+__global__ __launch_bounds__(kThreads) void motion_ssd_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
+                                                             const uint16_t* __restrict__ tmpl, int H, int W, int S, int D,
+                                                             const int* __restrict__ centres, int mult,
+                                                             unsigned long long* __restrict__ scores, int tilesX) {
+  constexpr int TH = kWaves * R;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nd = 2 * D + 1, stride = ssd_stride(D), rows = TH + 2 * D;
+  uint16_t* ft = reinterpret_cast<uint16_t*>(smem);
+  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + tile_bytes(TH, stride, D));
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const int tx = blockIdx.x % tilesX, ty = blockIdx.x / tilesX;
+  const int i0 = tx * kTileW, j0 = ty * TH;              // the tile's first pixel, counted from the interior's corner (S, S)
+  const int IW = W - 2 * S, IH = H - 2 * S;
+  const int left = IW - i0 - kPix * lane, down = IH - j0 - wave * R;
+  const int np = left < 0 ? 0 : (left < kPix ? left : kPix);      // interior pixels of this lane
+  const int nr = down < 0 ? 0 : (down < R ? down : R);            // interior rows of this wave
+  unsigned mk[kPix], t2[R][kPix / 2];
+  const bool ragged = tile_mask(np, mk);
+  tile_tmpl<R>(tmpl + (long)(S + j0 + wave * R) * W + S + i0 + kPix * lane, W, nr, np, flip, t2);
+  for (int f = blockIdx.y; f < tc; f += gridDim.y) {
+    const int cy = centres ? dc_motion_centre(mult, centres[2 * f], S - D) : 0;
+    const int cx = centres ? dc_motion_centre(mult, centres[2 * f + 1], S - D) : 0;
+    __syncthreads();                                     // the readers of the previous frame's tile and totals are done
+    tile_stage(ft, stride, frames + (long)f * H * W, H, W, S + j0 + cy - D, S + i0 + cx - D, rows, stride, flip, wave, lane);
     for (int i = threadIdx.x; i < nd * nd; i += kThreads) sc[i] = 0;
     __syncthreads();
-    if (nr > 0) {                                        // wave-uniform
-      for (int m = 0; m < nd; ++m) {
-        unsigned long long acc[NK];
-#pragma unroll
-        for (int k = 0; k < NK; ++k) acc[k] = 0;
-        if (np > 0) {
-          if (ragged) ssd_rows<SMAX, R, true>(ft, stride, S, nd, nr, wave * R + m, lane, t2, mk, acc);
-          else ssd_rows<SMAX, R, false>(ft, stride, S, nd, nr, wave * R + m, lane, t2, mk, acc);
-        }
-        unsigned long long mine = 0;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-          if (k < nd) {
-            const unsigned long long s = wave_sum64(acc[k]);
-            if (lane == k) mine = s;
-          }
-        }
-        if (lane < nd) atomicAdd(&sc[m * nd + lane], mine);
-      }
-    }
+    if (nr > 0) tile_score<RMAX, R>(ft, stride, D, nr, np, ragged, wave * R, lane, lane, t2, mk, sc);        // wave-uniform
     __syncthreads();
     unsigned long long* dst = scores + (long)f * nd * nd;
     for (int i = threadIdx.x; i < nd * nd; i += kThreads) {
@@ -158,7 +200,8 @@ __global__ __launch_bounds__(kThreads) void motion_ssd_kernel(const uint16_t* __
 
 // One wave per score table: every lane scans the candidates lane, lane + 64, ... and the wave folds its 64 partial minima; the
 // order of motion_math.h is total, so the result is the unique minimum whatever the order of the comparisons.  Every lane returns it.
-// (cy, cx): the centre of a window table (dc_motion_pick_around: the candidates are ordered as total shifts), (0, 0) otherwise.
+// (cy, cx): the centre of a window table (motion_pick_kernel: the candidates are ordered as total shifts); the block pick orders
+// residuals and leaves it at (0, 0).
 __device__ __forceinline__ DcShiftCand pick_wave(const int64_t* __restrict__ sc, int S, int lane, int cy = 0, int cx = 0) {
   const int n = (2 * S + 1) * (2 * S + 1);
   DcShiftCand b = dc_motion_cand_around(sc, S, lane < n ? lane : 0, cy, cx);
@@ -177,121 +220,35 @@ __device__ __forceinline__ DcShiftCand pick_wave(const int64_t* __restrict__ sc,
   return b;
 }
 
-// One wave per frame.
-__global__ __launch_bounds__(kWave) void motion_pick_kernel(const int64_t* __restrict__ scores, int tc, int S, int* __restrict__ shifts,
-                                                           int64_t* __restrict__ best) {
-  const int n = (2 * S + 1) * (2 * S + 1), lane = threadIdx.x;
+// One wave per frame: the total shift centre + (ey, ex) under the order of motion_math.h over TOTAL shifts, and (fine non-null) its
+// refinement within the window table at the picked residual -- 0 on an axis where the residual lies on the window's border.
+// centres == nullptr (dc_motion_pick, with D = S): centre 0, the pick of an exhaustive table.
+__global__ __launch_bounds__(kWave) void motion_pick_kernel(const int64_t* __restrict__ wscores, const int* __restrict__ centres, int mult,
+                                                           int tc, int S, int D, int* __restrict__ shifts, int64_t* __restrict__ best,
+                                                           int* __restrict__ fine) {
+  const int n = (2 * D + 1) * (2 * D + 1), lane = threadIdx.x;
   for (int f = blockIdx.x; f < tc; f += gridDim.x) {
-    const DcShiftCand b = pick_wave(scores + (long)f * n, S, lane);
+    const int cy = centres ? dc_motion_centre(mult, centres[2 * f], S - D) : 0;
+    const int cx = centres ? dc_motion_centre(mult, centres[2 * f + 1], S - D) : 0;
+    const int64_t* sc = wscores + (long)f * n;
+    const DcShiftCand b = pick_wave(sc, D, lane, cy, cx);
     if (lane == 0) {
       shifts[2 * f] = b.dy;
       shifts[2 * f + 1] = b.dx;
       if (best) best[f] = b.score;
-    }
-  }
-}
-
-// 8 output values of one row that share a shift, o 16-byte aligned: one store of the 8 source values at (sy, sx .. sx + 7) of the
-// frame f, or of fill where all 8 lie outside it.  The source run starts at any 2-byte address: it is read as the 4 or 5 aligned
-// dwords that hold it and funnel-shifted.  false (nothing stored) where the run straddles the frame's edge.
-__device__ __forceinline__ bool move8(const uint16_t* __restrict__ f, long sy, long sx, int H, int W, unsigned fill2, uint16_t* __restrict__ o) {
-  uint4 v;
-  if (sy < 0 || sy >= H || sx + 8 <= 0 || sx >= W) {
-    v = make_uint4(fill2, fill2, fill2, fill2);
-  } else if (sx >= 0 && sx + 8 <= W) {
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(f + sy * W + sx);
-    const unsigned* p = reinterpret_cast<const unsigned*>(addr & ~(uintptr_t)3);
-    const unsigned w0 = p[0], w1 = p[1], w2 = p[2], w3 = p[3];
-    if (addr & 2) {
-      const unsigned w4 = p[4];
-      v = make_uint4((w0 >> 16) | (w1 << 16), (w1 >> 16) | (w2 << 16), (w2 >> 16) | (w3 << 16), (w3 >> 16) | (w4 << 16));
-    } else {
-      v = make_uint4(w0, w1, w2, w3);
-    }
-  } else {
-    return false;
-  }
-  *reinterpret_cast<uint4*>(o) = v;
-  return true;
-}
-
-// out[t][y][x] = frames[t][y + dy][x + dx] inside the frame, fill outside.  A thread moves 8 consecutive output values; the groups
-// are cut at multiples of 8 elements of the WHOLE output (not of the frame), so a group that lies in one row is one aligned
-// 16-byte store.  Its source run starts at any 2-byte address: it is read as the 4 or 5 aligned dwords that hold it (an aligned
-// dword that holds one value of the buffer lies inside the buffer's pages) and funnel-shifted.  Groups that cross a row, a frame
-// or the edge of the source go value by value.
-__global__ __launch_bounds__(kThreads) void motion_apply_kernel(const uint16_t* __restrict__ frames, int tc, const int* __restrict__ shifts,
-                                                               int H, int W, unsigned fill, uint16_t* __restrict__ out, int wide) {
-  const int HW = H * W;
-  const unsigned fill2 = fill | (fill << 16);
-  for (int t = blockIdx.y; t < tc; t += gridDim.y) {
-    const long dy = shifts[2 * t], dx = shifts[2 * t + 1];
-    const long base = (long)t * HW;
-    const int off = (int)(base & 7);
-    const int groups = (HW + off + 7) / 8;
-    const uint16_t* f = frames + base;
-    uint16_t* o = out + base;
-    for (int g = blockIdx.x * kThreads + threadIdx.x; g < groups; g += gridDim.x * kThreads) {
-      const int e0 = g * 8 - off;
-      const int a = e0 < 0 ? 0 : e0, b = e0 + 8 < HW ? e0 + 8 : HW;
-      int y = a / W, x = a - y * W;
-      bool done = false;
-      if (wide && b - a == 8 && x + 8 <= W) done = move8(f, y + dy, x + dx, H, W, fill2, o + a);
-      if (!done) {
-        for (int e = a; e < b; ++e) {
-          const long sy = y + dy, sx = x + dx;
-          o[e] = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? f[sy * W + sx] : (uint16_t)fill;
-          if (++x == W) { x = 0; ++y; }
-        }
+      if (fine) {
+        const DcSubShift q = dc_motion_refine_entry(sc, D, b.dy - cy, b.dx - cx);
+        fine[2 * f] = dc_motion_fine(b.dy, q.qy);
+        fine[2 * f + 1] = dc_motion_fine(b.dx, q.qx);
       }
     }
   }
 }
 
-// ---- sub-pixel: refine, interpolate (the definitions are in include/dcunet.h, the arithmetic in motion_math.h) ---------------------
-// One thread per frame: the pick's neighbours on both axes, five scores of a table the pick kernel has just read.
-__global__ __launch_bounds__(kThreads) void motion_refine_kernel(const int64_t* __restrict__ scores, const int* __restrict__ shifts, int tc,
-                                                                int S, int* __restrict__ fine) {
-  const long n = (2 * S + 1) * (2 * S + 1);
-  for (int f = blockIdx.x * kThreads + threadIdx.x; f < tc; f += gridDim.x * kThreads) {
-    const int dy = shifts[2 * f], dx = shifts[2 * f + 1];
-    const DcSubShift q = dc_motion_refine_entry(scores + f * n, S, dy, dx);
-    fine[2 * f] = dc_motion_fine(dy, q.qy);
-    fine[2 * f + 1] = dc_motion_fine(dx, q.qx);
-  }
-}
-
-// One thread per (frame, block): the residual the block pick added to the frame's clamped rigid shift, refined in the block's table.
-__global__ __launch_bounds__(kThreads) void motion_block_refine_kernel(const int64_t* __restrict__ bscores, const int* __restrict__ rigid,
-                                                                      const int* __restrict__ block_shifts, long items, int nblk, int S,
-                                                                      int D, int* __restrict__ fine) {
-  const long n = (2 * D + 1) * (2 * D + 1);
-  for (long it = (long)blockIdx.x * kThreads + threadIdx.x; it < items; it += (long)gridDim.x * kThreads) {
-    const long f = it / nblk;
-    const int by = block_shifts[2 * it], bx = block_shifts[2 * it + 1];
-    const int64_t ey = (int64_t)by - dc_motion_clamp(rigid[2 * f], S), ex = (int64_t)bx - dc_motion_clamp(rigid[2 * f + 1], S);
-    DcSubShift q;
-    q.qy = q.qx = 0;
-    if (ey >= -D && ey <= D && ex >= -D && ex <= D) q = dc_motion_refine_entry(bscores + it * n, D, (int)ey, (int)ex);
-    fine[2 * it] = dc_motion_fine(by, q.qy);
-    fine[2 * it + 1] = dc_motion_fine(bx, q.qx);
-  }
-}
-
-// One output value at the split fine shift: source (sy, sx) = (y + iy, x + ix), weights (fy, fx).  flip: 0x8000 for int16 (the
-// interpolation commutes with adding 32768 to every tap).
-__device__ __forceinline__ uint16_t sub1(const uint16_t* __restrict__ f, long sy, long sx, int fy, int fx, int H, int W, unsigned flip,
-                                         unsigned fill) {
-  if (sy < 0 || sx < 0 || sy + (fy > 0) >= H || sx + (fx > 0) >= W) return (uint16_t)fill;
-  const uint16_t* p = f + sy * W + sx;
-  const int a00 = (int)(p[0] ^ flip), a01 = fx ? (int)(p[1] ^ flip) : 0;
-  const int a10 = fy ? (int)(p[W] ^ flip) : 0, a11 = (fy && fx) ? (int)(p[W + 1] ^ flip) : 0;
-  return (uint16_t)((unsigned)dc_motion_interp(a00, a01, a10, a11, fy, fx) ^ flip);
-}
-
-// 8 (nine: 9) consecutive values from any 2-byte address p, out of the 4 or 5 aligned dwords that hold them: n[0 .. 3] = values
-// 0 .. 7 in pairs, the low half of n[4] = value 8.  The fifth dword is read only where it holds one of the values asked for (as in
-// move8: an aligned dword that holds one value of the buffer lies inside the buffer's pages).
+// ---- the movers' last step: 8 values of a row by one 16-byte store, or one value; whole pixels or (sub-pixel) interpolated ---------
+// 8 (nine: 9) consecutive values from any 2-byte address p, out of the 4 or 5 aligned dwords that hold them, funnel-shifted:
+// n[0 .. 3] = values 0 .. 7 in pairs, the low half of n[4] = value 8.  The fifth dword is read only where it holds one of the
+// values asked for (an aligned dword that holds one value of the buffer lies inside the buffer's pages).
 __device__ __forceinline__ void run9(const uint16_t* __restrict__ p, bool nine, unsigned (&n)[5]) {
   const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
   const unsigned* q = reinterpret_cast<const unsigned*>(addr & ~(uintptr_t)3);
@@ -304,6 +261,35 @@ __device__ __forceinline__ void run9(const uint16_t* __restrict__ p, bool nine, 
     n[0] = w0; n[1] = w1; n[2] = w2; n[3] = w3;
     n[4] = nine ? q[4] : 0u;
   }
+}
+
+// 8 output values of one row that share a shift, o 16-byte aligned: one store of the 8 source values at (sy, sx .. sx + 7) of the
+// frame f (a run that starts at any 2-byte address: run9), or of fill where all 8 lie outside it.  false (nothing stored) where
+// the run straddles the frame's edge.
+__device__ __forceinline__ bool move8(const uint16_t* __restrict__ f, long sy, long sx, int H, int W, unsigned fill2, uint16_t* __restrict__ o) {
+  uint4 v;
+  if (sy < 0 || sy >= H || sx + 8 <= 0 || sx >= W) {
+    v = make_uint4(fill2, fill2, fill2, fill2);
+  } else if (sx >= 0 && sx + 8 <= W) {
+    unsigned n[5];
+    run9(f + sy * W + sx, false, n);
+    v = make_uint4(n[0], n[1], n[2], n[3]);
+  } else {
+    return false;
+  }
+  *reinterpret_cast<uint4*>(o) = v;
+  return true;
+}
+
+// One output value at the split fine shift: source (sy, sx) = (y + iy, x + ix), weights (fy, fx).  flip: 0x8000 for int16 (the
+// interpolation commutes with adding 32768 to every tap).
+__device__ __forceinline__ uint16_t sub1(const uint16_t* __restrict__ f, long sy, long sx, int fy, int fx, int H, int W, unsigned flip,
+                                         unsigned fill) {
+  if (sy < 0 || sx < 0 || sy + (fy > 0) >= H || sx + (fx > 0) >= W) return (uint16_t)fill;
+  const uint16_t* p = f + sy * W + sx;
+  const int a00 = (int)(p[0] ^ flip), a01 = fx ? (int)(p[1] ^ flip) : 0;
+  const int a10 = fy ? (int)(p[W] ^ flip) : 0, a11 = (fy && fx) ? (int)(p[W + 1] ^ flip) : 0;
+  return (uint16_t)((unsigned)dc_motion_interp(a00, a01, a10, a11, fy, fx) ^ flip);
 }
 
 // 8 output values of one row that share a split fine shift, o 16-byte aligned: one store of the 8 interpolations between the source
@@ -341,20 +327,37 @@ __device__ __forceinline__ bool sub8(const uint16_t* __restrict__ f, long sy, lo
   return true;
 }
 
-// out[t][y][x] = the bilinear interpolation of frames[t] at the fine shift fine[t] (include/dcunet.h), fill where a used tap lies
-// outside the frame.  The shape of motion_apply_kernel: a thread produces 8 consecutive outputs, the groups cut at multiples of 8
-// elements of the WHOLE output, so a group that lies in one row is one aligned 16-byte store; its source is two runs of 9 values,
-// one per source row, each out of its own aligned dwords.  The split and the weights are uniform over the frame.  Groups that
-// cross a row, a frame or the source's edge go value by value.
-__global__ __launch_bounds__(kThreads) void motion_apply_sub_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
-                                                                   const int* __restrict__ fine, int H, int W, unsigned fill,
-                                                                   uint16_t* __restrict__ out, int wide) {
+// The group of 8 at (y, x .. x + 7) / the one value at (y, x) of the output, all at the shift (s0, s1): whole pixels, or (SUB) a
+// fine shift, which is split here (iy = floor(s0 / 16), weight fy = s0 - 16 iy; every fine shift the callers form fits an int32).
+// put8: false where nothing was stored (move8, sub8).  flip is unused without SUB.
+template <bool SUB>
+__device__ __forceinline__ bool put8(const uint16_t* __restrict__ f, long y, long x, long s0, long s1, int H, int W, unsigned flip, unsigned fill,
+                                     uint16_t* __restrict__ o) {
+  const long sy = y + (SUB ? dc_motion_floor16((int)s0) : s0), sx = x + (SUB ? dc_motion_floor16((int)s1) : s1);
+  if constexpr (SUB) return sub8(f, sy, sx, dc_motion_frac16((int)s0), dc_motion_frac16((int)s1), H, W, flip, fill | (fill << 16), o);
+  else return move8(f, sy, sx, H, W, fill | (fill << 16), o);
+}
+template <bool SUB>
+__device__ __forceinline__ uint16_t put1(const uint16_t* __restrict__ f, long y, long x, long s0, long s1, int H, int W, unsigned flip,
+                                         unsigned fill) {
+  const long sy = y + (SUB ? dc_motion_floor16((int)s0) : s0), sx = x + (SUB ? dc_motion_floor16((int)s1) : s1);
+  if constexpr (SUB) return sub1(f, sy, sx, dc_motion_frac16((int)s0), dc_motion_frac16((int)s1), H, W, flip, fill);
+  else return (sy >= 0 && sy < H && sx >= 0 && sx < W) ? f[sy * W + sx] : (uint16_t)fill;
+}
+
+// out[t][y][x] = frames[t][y + dy][x + dx] inside the frame, fill outside; SUB (dc_motion_apply_sub): the bilinear interpolation of
+// frames[t] at the fine shift shifts[t] (include/dcunet.h), fill where a used tap lies outside the frame.  A thread produces 8
+// consecutive output values; the groups are cut at multiples of 8 elements of the WHOLE output (not of the frame), so a group that
+// lies in one row is one aligned 16-byte store (put8: its source is one run of 8 values, or SUB two runs of 9, one per source row;
+// the split and the weights are uniform over the frame).  Groups that cross a row, a frame or the edge of the source go value by
+// value (put1).
+template <bool SUB>
+__global__ __launch_bounds__(kThreads) void motion_apply_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
+                                                               const int* __restrict__ shifts, int H, int W, unsigned fill,
+                                                               uint16_t* __restrict__ out, int wide) {
   const int HW = H * W;
-  const unsigned fill2 = fill | (fill << 16);
   for (int t = blockIdx.y; t < tc; t += gridDim.y) {
-    const int s0 = fine[2 * t], s1 = fine[2 * t + 1];
-    const long iy = dc_motion_floor16(s0), ix = dc_motion_floor16(s1);
-    const int fy = dc_motion_frac16(s0), fx = dc_motion_frac16(s1);
+    const long s0 = shifts[2 * t], s1 = shifts[2 * t + 1];
     const long base = (long)t * HW;
     const int off = (int)(base & 7);
     const int groups = (HW + off + 7) / 8;
@@ -364,15 +367,42 @@ __global__ __launch_bounds__(kThreads) void motion_apply_sub_kernel(const uint16
       const int e0 = g * 8 - off;
       const int a = e0 < 0 ? 0 : e0, b = e0 + 8 < HW ? e0 + 8 : HW;
       int y = a / W, x = a - y * W;
-      bool done = false;
-      if (wide && b - a == 8 && x + 8 <= W) done = sub8(f, y + iy, x + ix, fy, fx, H, W, flip, fill2, o + a);
-      if (!done) {
-        for (int e = a; e < b; ++e) {
-          o[e] = sub1(f, y + iy, x + ix, fy, fx, H, W, flip, fill);
-          if (++x == W) { x = 0; ++y; }
-        }
+      if (wide && b - a == 8 && x + 8 <= W && put8<SUB>(f, y, x, s0, s1, H, W, flip, fill, o + a)) continue;
+      for (int e = a; e < b; ++e) {
+        o[e] = put1<SUB>(f, y, x, s0, s1, H, W, flip, fill);
+        if (++x == W) { x = 0; ++y; }
       }
     }
+  }
+}
+
+// ---- sub-pixel: refine (the definitions are in include/dcunet.h, the arithmetic in motion_math.h; the interpolation is above) -----
+// One thread per frame: the pick's neighbours on both axes, five scores of a table the pick kernel has just read.
+__global__ __launch_bounds__(kThreads) void motion_refine_kernel(const int64_t* __restrict__ scores, const int* __restrict__ shifts, int tc,
+                                                                int S, int* __restrict__ fine) {
+  const long n = (2 * S + 1) * (2 * S + 1);
+  for (int f = blockIdx.x * kThreads + threadIdx.x; f < tc; f += gridDim.x * kThreads) {
+    const int dy = shifts[2 * f], dx = shifts[2 * f + 1];
+    const DcSubShift q = dc_motion_refine_entry(scores + f * n, S, dy, dx);
+    fine[2 * f] = dc_motion_fine(dy, q.qy);
+    fine[2 * f + 1] = dc_motion_fine(dx, q.qx);
+  }
+}
+
+// One thread per (frame, block): the residual the block pick added to the frame's clamped rigid shift, refined in the block's table.
+__global__ __launch_bounds__(kThreads) void motion_block_refine_kernel(const int64_t* __restrict__ bscores, const int* __restrict__ rigid,
+                                                                      const int* __restrict__ block_shifts, long items, int nblk, int S,
+                                                                      int D, int* __restrict__ fine) {
+  const long n = (2 * D + 1) * (2 * D + 1);
+  for (long it = (long)blockIdx.x * kThreads + threadIdx.x; it < items; it += (long)gridDim.x * kThreads) {
+    const long f = it / nblk;
+    const int by = block_shifts[2 * it], bx = block_shifts[2 * it + 1];
+    const int64_t ey = (int64_t)by - dc_motion_clamp(rigid[2 * f], S), ex = (int64_t)bx - dc_motion_clamp(rigid[2 * f + 1], S);
+    DcSubShift q;
+    q.qy = q.qx = 0;
+    if (ey >= -D && ey <= D && ex >= -D && ex <= D) q = dc_motion_refine_entry(bscores + it * n, D, (int)ey, (int)ex);
+    fine[2 * it] = dc_motion_fine(by, q.qy);
+    fine[2 * it + 1] = dc_motion_fine(bx, q.qx);
   }
 }
 
@@ -388,18 +418,19 @@ __host__ __device__ inline int bssd_stride(int D) { return kBlkTileW + ((2 * D +
 // and sweeps of 128 columns -- a wave is 16 lanes x 8 pixels wide and 4 lanes x 4 rows high, so a block 100 pixels wide keeps
 // 13 of 16 lanes busy.  Per tile the frame window around the RIGID shift (dy, dx) of the frame -- read here and clamped to
 // [-S, S], which is what keeps the window inside the frame: its first row is >= M + dy - D >= 0, its last <= H - M - 1 + dy + D
-// <= H - 1 -- is staged in LDS with its D-wide halo and scored by ssd_rows at every residual (ey, ex).  The (2D+1)^2 totals of
-// all tiles meet in LDS and leave with plain stores: every score is written, there is no global atomic and no zero launch.
+// <= H - 1 -- is staged in LDS with its D-wide halo and scored at every residual (ey, ex) by the tile_* pieces above, nr differing
+// per 16 lanes here.  The (2D+1)^2 totals of all tiles meet in LDS (zeroed once per frame) and leave with plain stores: every
+// score is written, there is no global atomic and no zero launch.
 template <int DMAX>
 __global__ __launch_bounds__(kThreads) void motion_block_ssd_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
                                                                    const uint16_t* __restrict__ tmpl, int H, int W, int S, int D, int By,
                                                                    int Bx, const int* __restrict__ rigid,
                                                                    unsigned long long* __restrict__ bscores) {
-  constexpr int NK = 2 * DMAX + 1, R = kBlkR;
+  constexpr int R = kBlkR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nd = 2 * D + 1, M = S + D, stride = bssd_stride(D);
   uint16_t* ft = reinterpret_cast<uint16_t*>(smem);
-  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + (size_t)(kBlkTileH + 2 * D) * stride * sizeof(uint16_t));
+  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + tile_bytes(kBlkTileH, stride, D));
   const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   const int cl = lane % kBlkLanesX, rg = wave * (kWave / kBlkLanesX) + lane / kBlkLanesX;
   const int bi = blockIdx.x / Bx, bj = blockIdx.x % Bx;
@@ -418,52 +449,16 @@ __global__ __launch_bounds__(kThreads) void motion_block_ssd_kernel(const uint16
         const int left = tw - kPix * cl, down = th - rg * R;
         const int np = left < 0 ? 0 : (left < kPix ? left : kPix);      // pixels of this lane
         const int nr = down < 0 ? 0 : (down < R ? down : R);            // rows of this lane
-        const bool ragged = __ballot(np > 0 && np < kPix) != 0;
-        unsigned mk[kPix];
-#pragma unroll
-        for (int p = 0; p < kPix; ++p) mk[p] = p < np ? 0xffffffffu : 0u;
-        unsigned t2[R][kPix / 2];
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-          const uint16_t* trow = tmpl + (long)(ty + rg * R + j) * W + tx + kPix * cl;
-#pragma unroll
-          for (int q = 0; q < kPix / 2; ++q) {
-            const unsigned lo = (j < nr && 2 * q < np) ? (trow[2 * q] ^ flip) : 0u;
-            const unsigned hi = (j < nr && 2 * q + 1 < np) ? (trow[2 * q + 1] ^ flip) : 0u;
-            t2[j][q] = lo | (hi << 16);
-          }
-        }
+        unsigned mk[kPix], t2[R][kPix / 2];
+        const bool ragged = tile_mask(np, mk);
+        tile_tmpl<R>(tmpl + (long)(ty + rg * R) * W + tx + kPix * cl, W, nr, np, flip, t2);
         // the window of this tile: th + 2D rows, tw + 2D columns rounded up to the 16-byte pieces the lanes read; LDS (0, 0) is
         // frame (ty + dy - D, tx + dx - D).  What is not staged is read by lanes without pixels only, or masked.
         const int srows = th + 2 * D, scols = ((tw + 7) & ~7) + ((2 * D + 7) & ~7);
-        const int oy = ty + dy - D, ox = tx + dx - D;
         __syncthreads();                                 // the readers of the previous tile are done
-        for (int r = wave; r < srows; r += kWaves) {
-          const int gy = oy + r;
-          for (int c = lane; c < scols; c += kWave) {
-            const int gx = ox + c;
-            ft[r * stride + c] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? (uint16_t)(fr[(long)gy * W + gx] ^ flip) : (uint16_t)0;
-          }
-        }
+        tile_stage(ft, stride, fr, H, W, ty + dy - D, tx + dx - D, srows, scols, flip, wave, lane);
         __syncthreads();
-        for (int m = 0; m < nd; ++m) {
-          unsigned long long acc[NK];
-#pragma unroll
-          for (int k = 0; k < NK; ++k) acc[k] = 0;
-          if (np > 0 && nr > 0) {
-            if (ragged) ssd_rows<DMAX, R, true>(ft, stride, D, nd, nr, rg * R + m, cl, t2, mk, acc);
-            else ssd_rows<DMAX, R, false>(ft, stride, D, nd, nr, rg * R + m, cl, t2, mk, acc);
-          }
-          unsigned long long mine = 0;
-#pragma unroll
-          for (int k = 0; k < NK; ++k) {
-            if (k < nd) {
-              const unsigned long long s = wave_sum64(acc[k]);
-              if (lane == k) mine = s;
-            }
-          }
-          if (lane < nd) atomicAdd(&sc[m * nd + lane], mine);
-        }
+        tile_score<DMAX, R>(ft, stride, D, nr, np, ragged, rg * R, cl, lane, t2, mk, sc);
       }
     }
     __syncthreads();
@@ -498,9 +493,8 @@ const int kWarpCols = 1024;            // its columns, at most
 // two multiplications per component, one where a group of 8 lies between the same two centres.
 // A thread moves 8 consecutive outputs of one row, cut at multiples of 8 elements of the WHOLE output as in motion_apply_kernel:
 // where the field is the same at all 8 (compared one by one: along a row it is monotone between two centres only) the group is
-// that kernel's aligned 16-byte store from 4 or 5 aligned source dwords; otherwise it goes value by value.
-// SUB (dc_motion_warp_sub): bs holds FINE block shifts, so the field is a fine shift per pixel; it is split, and the group is sub8's
-// aligned store where all 8 share it, sub1 value by value otherwise (flip: as for motion_apply_sub_kernel; unused without SUB).
+// that kernel's aligned 16-byte store (put8); otherwise it goes value by value (put1).
+// SUB (dc_motion_warp_sub): bs holds FINE block shifts, so the field is a fine shift per pixel, which put8 / put1 split.
 template <bool SUB>
 __global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* __restrict__ frames, int tc, const int* __restrict__ bs,
                                                               int By, int Bx, int H, int W, unsigned fill, uint16_t* __restrict__ out,
@@ -525,7 +519,6 @@ __global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* _
     rtap[threadIdx.x] = t.i0 | (t.w << 8);
   }
   const int HW = H * W;
-  const unsigned fill2 = fill | (fill << 16);
   for (int t = blockIdx.y; t < tc; t += gridDim.y) {
     const int* s = bs + (long)t * By * Bx * 2;
     __syncthreads();                                     // the taps are there; the readers of the previous frame's blends are done
@@ -570,38 +563,17 @@ __global__ __launch_bounds__(kThreads) void motion_warp_kernel(const uint16_t* _
           same = same && fy[k] == fy[0] && fx[k] == fx[0];
         }
       }
-      uint16_t* o = out + lo;
-      bool done = false;
-      if constexpr (SUB) {
-        // the field never leaves the int32 range of the block shifts
-        if (wide && n == 8 && same)
-          done = sub8(f, (long)y + dc_motion_floor16((int)fy[0]), (long)x + dc_motion_floor16((int)fx[0]), dc_motion_frac16((int)fy[0]),
-                      dc_motion_frac16((int)fx[0]), H, W, flip, fill2, o);
-        if (!done) {
+      uint16_t* o = out + lo;                            // the field never leaves the int32 range of the block shifts
+      if (wide && n == 8 && same && put8<SUB>(f, y, x, fy[0], fx[0], H, W, flip, fill, o)) continue;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            if (k < n)
-              o[k] = sub1(f, (long)y + dc_motion_floor16((int)fy[k]), (long)x + k + dc_motion_floor16((int)fx[k]), dc_motion_frac16((int)fy[k]),
-                          dc_motion_frac16((int)fx[k]), H, W, flip, fill);
-          }
-        }
-      } else {
-      if (wide && n == 8 && same) done = move8(f, y + fy[0], x + fx[0], H, W, fill2, o);
-      if (!done) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          if (k < n) {
-            const long sy = y + fy[k], sx = x + k + fx[k];
-            o[k] = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? f[sy * W + sx] : (uint16_t)fill;
-          }
-        }
-      }
+      for (int k = 0; k < 8; ++k) {
+        if (k < n) o[k] = put1<SUB>(f, y, (long)x + k, fy[k], fx[k], H, W, flip, fill);       // the column in 64 bits from the start
       }
     }
   }
 }
 
-// ---- wide search: bin, window scores, window pick (the definitions are in include/dcunet.h, the arithmetic in motion_math.h) -------
+// ---- wide search: bin (the definitions are in include/dcunet.h, the arithmetic in motion_math.h; window scores and pick are above) -
 // out[t][Y][X] = the rounded mean of the c x c cell (cY.., cX..) of frame t, c = 2^LG.  One memory-bound pass: a thread owns 8
 // consecutive input columns of the c rows of one binned row -- c 16-byte loads where the rows are 16-byte aligned (wide: W % 8 == 0
 // and an aligned base), value by value otherwise -- and stores the 8 / c bins they hold.  Neighbouring threads read neighbouring
@@ -654,109 +626,9 @@ __global__ __launch_bounds__(kThreads) void motion_bin_kernel(const uint16_t* __
   }
 }
 
-// dc_motion_ssd at the (2D+1)^2 shifts around a centre per frame: the tiling of motion_ssd_kernel -- one workgroup per tile of the
-// radius-S interior (kWaves * R rows x 512 columns) and frame, template values in registers, the frame tile with its D-wide halo in
-// LDS, ssd_rows over the residuals --, with the LDS window's origin moved by the frame's centre (cy, cx) = clamp(mult * rows[f],
-// S - D), formed HERE: LDS (0, 0) is frame (S + j0 + cy - D, S + i0 + cx - D), and because |cy| <= S - D the window's first row
-// is >= 0 and its last, S + (H - 2S - 1) + cy + D, is <= H - 1, likewise the columns -- whatever the table holds, nothing outside
-// the frame is read (what the staging loop does not find inside the frame is read by lanes without pixels only, or masked).
-template <int DMAX, int R>
-__global__ __launch_bounds__(kThreads) void motion_ssd_around_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc,
-                                                                    const uint16_t* __restrict__ tmpl, int H, int W, int S, int D,
-                                                                    const int* __restrict__ centres, int mult,
-                                                                    unsigned long long* __restrict__ wscores, int tilesX) {
-  constexpr int NK = 2 * DMAX + 1, TH = kWaves * R;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nd = 2 * D + 1, stride = ssd_stride(D), rows = TH + 2 * D;
-  uint16_t* ft = reinterpret_cast<uint16_t*>(smem);
-  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + (size_t)rows * stride * sizeof(uint16_t));
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const int tx = blockIdx.x % tilesX, ty = blockIdx.x / tilesX;
-  const int i0 = tx * kTileW, j0 = ty * TH;              // the tile's first pixel, counted from the interior's corner (S, S)
-  const int IW = W - 2 * S, IH = H - 2 * S;
-  const int left = IW - i0 - kPix * lane, down = IH - j0 - wave * R;
-  const int np = left < 0 ? 0 : (left < kPix ? left : kPix);      // interior pixels of this lane
-  const int nr = down < 0 ? 0 : (down < R ? down : R);            // interior rows of this wave
-  const bool ragged = __ballot(np > 0 && np < kPix) != 0;
-  unsigned mk[kPix];
-#pragma unroll
-  for (int p = 0; p < kPix; ++p) mk[p] = p < np ? 0xffffffffu : 0u;
-  unsigned t2[R][kPix / 2];
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const uint16_t* trow = tmpl + (long)(S + j0 + wave * R + j) * W + S + i0 + kPix * lane;
-#pragma unroll
-    for (int q = 0; q < kPix / 2; ++q) {
-      const unsigned lo = (j < nr && 2 * q < np) ? (trow[2 * q] ^ flip) : 0u;
-      const unsigned hi = (j < nr && 2 * q + 1 < np) ? (trow[2 * q + 1] ^ flip) : 0u;
-      t2[j][q] = lo | (hi << 16);
-    }
-  }
-  for (int f = blockIdx.y; f < tc; f += gridDim.y) {
-    const uint16_t* fr = frames + (long)f * H * W;
-    const int oy = S + j0 + dc_motion_centre(mult, centres[2 * f], S - D) - D;
-    const int ox = S + i0 + dc_motion_centre(mult, centres[2 * f + 1], S - D) - D;
-    __syncthreads();                                     // the readers of the previous frame's tile and totals are done
-    for (int r = wave; r < rows; r += kWaves) {
-      const int gy = oy + r;
-      for (int c = lane; c < stride; c += kWave) {
-        const int gx = ox + c;
-        ft[r * stride + c] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? (uint16_t)(fr[(long)gy * W + gx] ^ flip) : (uint16_t)0;
-      }
-    }
-    for (int i = threadIdx.x; i < nd * nd; i += kThreads) sc[i] = 0;
-    __syncthreads();
-    if (nr > 0) {                                        // wave-uniform
-      for (int m = 0; m < nd; ++m) {
-        unsigned long long acc[NK];
-#pragma unroll
-        for (int k = 0; k < NK; ++k) acc[k] = 0;
-        if (np > 0) {
-          if (ragged) ssd_rows<DMAX, R, true>(ft, stride, D, nd, nr, wave * R + m, lane, t2, mk, acc);
-          else ssd_rows<DMAX, R, false>(ft, stride, D, nd, nr, wave * R + m, lane, t2, mk, acc);
-        }
-        unsigned long long mine = 0;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-          if (k < nd) {
-            const unsigned long long s = wave_sum64(acc[k]);
-            if (lane == k) mine = s;
-          }
-        }
-        if (lane < nd) atomicAdd(&sc[m * nd + lane], mine);
-      }
-    }
-    __syncthreads();
-    unsigned long long* dst = wscores + (long)f * nd * nd;
-    for (int i = threadIdx.x; i < nd * nd; i += kThreads) {
-      const unsigned long long v = sc[i];
-      if (v) atomicAdd(dst + i, v);
-    }
-  }
-}
-
-// One wave per frame: the total shift centre + (ey, ex) under the order of motion_math.h over TOTAL shifts, and (fine non-null) its
-// refinement within the window table at the picked residual -- 0 on an axis where the residual lies on the window's border.
-__global__ __launch_bounds__(kWave) void motion_pick_around_kernel(const int64_t* __restrict__ wscores, const int* __restrict__ centres,
-                                                                  int mult, int tc, int S, int D, int* __restrict__ shifts,
-                                                                  int64_t* __restrict__ best, int* __restrict__ fine) {
-  const int n = (2 * D + 1) * (2 * D + 1), lane = threadIdx.x;
-  for (int f = blockIdx.x; f < tc; f += gridDim.x) {
-    const int cy = dc_motion_centre(mult, centres[2 * f], S - D), cx = dc_motion_centre(mult, centres[2 * f + 1], S - D);
-    const int64_t* sc = wscores + (long)f * n;
-    const DcShiftCand b = pick_wave(sc, D, lane, cy, cx);
-    if (lane == 0) {
-      shifts[2 * f] = b.dy;
-      shifts[2 * f + 1] = b.dx;
-      if (best) best[f] = b.score;
-      if (fine) {
-        const DcSubShift q = dc_motion_refine_entry(sc, D, b.dy - cy, b.dx - cx);
-        fine[2 * f] = dc_motion_fine(b.dy, q.qy);
-        fine[2 * f + 1] = dc_motion_fine(b.dx, q.qx);
-      }
-    }
-  }
-}
+// ---- launchers.  name: the entry point, for the messages ---------------------------------------------------------------------------
+// the frame dimension of a grid (the kernels stride over the frames beyond it)
+inline unsigned frame_dim(int tc) { return (unsigned)(tc < 65535 ? tc : 65535); }
 
 template <int LG>
 int launch_bin(const uint16_t* frames, int is_unsigned, int tc, int H, int W, uint16_t* out, hipStream_t stream) {
@@ -769,73 +641,129 @@ int launch_bin(const uint16_t* frames, int is_unsigned, int tc, int H, int W, ui
   return DC_OK;
 }
 
-template <int DMAX, int R>
-int launch_ssd_around(const uint16_t* frames, int is_unsigned, int tc, const uint16_t* tmpl, int H, int W, int S, int D, const int* rows,
-                      int mult, unsigned long long* wscores, hipStream_t stream) {
+template <int RMAX, int R>
+int launch_ssd(const char* name, const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, const int* centres,
+               int mult, unsigned long long* scores, hipStream_t stream) {
   static DcLdsAttr lds_attr;
   const int TH = kWaves * R;
-  const int nd = 2 * D + 1;
-  const int lds = (TH + 2 * D) * ssd_stride(D) * (int)sizeof(uint16_t) + nd * nd * (int)sizeof(unsigned long long);
-  const int lds_max = (TH + 2 * DMAX) * ssd_stride(DMAX) * (int)sizeof(uint16_t) + (2 * DMAX + 1) * (2 * DMAX + 1) * (int)sizeof(unsigned long long);
-  auto kern = motion_ssd_around_kernel<DMAX, R>;
-  if (int rc = dc_func_max_lds(lds_attr, reinterpret_cast<const void*>(kern), lds_max, "dc_motion_ssd_around")) return rc;
+  auto kern = motion_ssd_kernel<RMAX, R>;
+  if (int rc = dc_func_max_lds(lds_attr, reinterpret_cast<const void*>(kern), ssd_lds(TH, ssd_stride(RMAX), RMAX), name)) return rc;
   const int tilesX = dc_cdiv(W - 2 * S, kTileW), tilesY = dc_cdiv(H - 2 * S, TH);
-  const dim3 grid((unsigned)(tilesX * tilesY), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(kern, grid, block, lds, stream, frames, is_unsigned ? 0u : 0x8000u, tc, tmpl, H, W, S, D, rows, mult, wscores, tilesX);
-  DC_CHECK_LAUNCH("dc_motion_ssd_around");
+  const dim3 grid((unsigned)(tilesX * tilesY), frame_dim(tc)), block(kThreads);
+  hipLaunchKernelGGL(kern, grid, block, ssd_lds(TH, ssd_stride(D), D), stream, (const uint16_t*)frames, is_unsigned ? 0u : 0x8000u, tc,
+                     (const uint16_t*)tmpl, H, W, S, D, centres, mult, scores, tilesX);
+  DC_CHECK_LAUNCH(name);
   return DC_OK;
 }
 
+// The frame-wide scores: the zero launch (the score kernel leaves its totals by atomics), then the instantiation for the window
+// half-width D: D <= 4, D <= 8 (what a window table may ask for) or D <= 16 with 4 rows per wave (an exhaustive table, D = S)
+int launch_scores(const char* name, const char* zero_name, const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S,
+                  int D, const int* centres, int mult, long* scores, hipStream_t stream) {
+  if (tc == 0) return DC_OK;
+  const long n = (long)tc * (2 * D + 1) * (2 * D + 1);
+  unsigned long long* sc = (unsigned long long*)scores;
+  const int blocks = (int)(dc_cdiv(n, kThreads) < kZeroBlocks ? dc_cdiv(n, kThreads) : kZeroBlocks);
+  hipLaunchKernelGGL(motion_zero_kernel, dim3(blocks), dim3(kThreads), 0, stream, sc, n);
+  DC_CHECK_LAUNCH(zero_name);
+  if (D <= 4) return launch_ssd<4, 8>(name, frames, is_unsigned, tc, tmpl, H, W, S, D, centres, mult, sc, stream);
+  if (D <= 8) return launch_ssd<8, 8>(name, frames, is_unsigned, tc, tmpl, H, W, S, D, centres, mult, sc, stream);
+  return launch_ssd<16, 4>(name, frames, is_unsigned, tc, tmpl, H, W, S, D, centres, mult, sc, stream);
+}
+
 template <int DMAX>
-int launch_block_ssd(const uint16_t* frames, int is_unsigned, int tc, const uint16_t* tmpl, int H, int W, int S, int D, int By, int Bx,
+int launch_block_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, int By, int Bx,
                      const int* rigid, unsigned long long* bscores, hipStream_t stream) {
-  const int nd = 2 * D + 1;
-  const int lds = (kBlkTileH + 2 * D) * bssd_stride(D) * (int)sizeof(uint16_t) + nd * nd * (int)sizeof(unsigned long long);
-  const dim3 grid((unsigned)(By * Bx), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(motion_block_ssd_kernel<DMAX>, grid, block, lds, stream, frames, is_unsigned ? 0u : 0x8000u, tc, tmpl, H, W, S, D,
-                     By, Bx, rigid, bscores);
+  const dim3 grid((unsigned)(By * Bx), frame_dim(tc)), block(kThreads);
+  hipLaunchKernelGGL(motion_block_ssd_kernel<DMAX>, grid, block, ssd_lds(kBlkTileH, bssd_stride(D), D), stream, (const uint16_t*)frames,
+                     is_unsigned ? 0u : 0x8000u, tc, (const uint16_t*)tmpl, H, W, S, D, By, Bx, rigid, bscores);
   DC_CHECK_LAUNCH("dc_motion_block_ssd");
   return DC_OK;
 }
 
-template <int SMAX, int R>
-int launch_ssd(const uint16_t* frames, int is_unsigned, int tc, const uint16_t* tmpl, int H, int W, int S, unsigned long long* scores,
-               hipStream_t stream) {
-  static DcLdsAttr lds_attr;
-  const int TH = kWaves * R;
-  const int nd = 2 * S + 1;
-  const int lds = (TH + 2 * S) * ssd_stride(S) * (int)sizeof(uint16_t) + nd * nd * (int)sizeof(unsigned long long);
-  const int lds_max = (TH + 2 * SMAX) * ssd_stride(SMAX) * (int)sizeof(uint16_t) + (2 * SMAX + 1) * (2 * SMAX + 1) * (int)sizeof(unsigned long long);
-  auto kern = motion_ssd_kernel<SMAX, R>;
-  if (int rc = dc_func_max_lds(lds_attr, reinterpret_cast<const void*>(kern), lds_max, "dc_motion_ssd")) return rc;
-  const int tilesX = dc_cdiv(W - 2 * S, kTileW), tilesY = dc_cdiv(H - 2 * S, TH);
-  const dim3 grid((unsigned)(tilesX * tilesY), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(kern, grid, block, lds, stream, frames, is_unsigned ? 0u : 0x8000u, tc, tmpl, H, W, S, scores, tilesX);
-  DC_CHECK_LAUNCH("dc_motion_ssd");
+int launch_pick(const char* name, const long* scores, const int* centres, int mult, int tc, int S, int D, int* shifts, long* best, int* fine,
+                hipStream_t stream) {
+  if (tc == 0) return DC_OK;
+  hipLaunchKernelGGL(motion_pick_kernel, dim3(frame_dim(tc)), dim3(kWave), 0, stream, (const int64_t*)scores, centres, mult, tc, S, D, shifts,
+                     (int64_t*)best, fine);
+  DC_CHECK_LAUNCH(name);
   return DC_OK;
 }
 
+// flip: 0x8000 for int16 where the mover interpolates (SUB), unused otherwise.  wide: out is 16-byte aligned.
+template <bool SUB>
+int launch_apply(const char* name, const void* frames, unsigned flip, int tc, const int* shifts, int H, int W, int fill, void* out,
+                 hipStream_t stream) {
+  if (tc == 0) return DC_OK;
+  const int bx = dc_cdiv(dc_cdiv((long)H * W + 7, 8), kThreads);
+  const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), frame_dim(tc)), block(kThreads);
+  hipLaunchKernelGGL(motion_apply_kernel<SUB>, grid, block, 0, stream, (const uint16_t*)frames, flip, tc, shifts, H, W,
+                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)dc_aligned16(out));
+  DC_CHECK_LAUNCH(name);
+  return DC_OK;
+}
+
+template <bool SUB>
+int launch_warp(const char* name, const void* frames, unsigned flip, int tc, const int* block_shifts, int By, int Bx, int H, int W, int fill,
+                void* out, hipStream_t stream) {
+  if (tc == 0) return DC_OK;
+  const int tilesX = dc_cdiv(W, kWarpCols);
+  const long tiles = (long)tilesX * dc_cdiv(H, kWarpRows);              // H * W <= 2^30: at most 2^30 tiles
+  const dim3 grid((unsigned)tiles, frame_dim(tc)), block(kThreads);
+  hipLaunchKernelGGL(motion_warp_kernel<SUB>, grid, block, 0, stream, (const uint16_t*)frames, tc, block_shifts, By, Bx, H, W,
+                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)dc_aligned16(out), tilesX, flip);
+  DC_CHECK_LAUNCH(name);
+  return DC_OK;
+}
+
+// out[0 .. n) and frames[0 .. n) of 16-bit values do not overlap
+inline bool disjoint16(const void* frames, const void* out, uintptr_t n) {
+  const uintptr_t bytes = n * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
+  return bytes == 0 || fa + bytes <= oa || oa + bytes <= fa;
+}
+
 }  // namespace
+
+// Checks that several entry points share.  The messages carry the entry's name, so each takes it as a string literal.
+#define DC_REQUIRE_IMAGE(name, H, W) DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, name ": image %d x %d: H * W is limited to 2^30", H, W)
+
+// the four movers, after their sizes: the fill value, the alignment, out beside frames
+#define DC_REQUIRE_MOVE(name, frames, table, out, tc, H, W, fill)                                                                          \
+  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, name ": fill = %d is not a 16-bit value", fill);                                   \
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)table) & 3) == 0, DC_EINVAL, name ": misaligned buffer");      \
+  DC_REQUIRE(disjoint16(frames, out, (uintptr_t)tc * H * W), DC_EINVAL, name ": out overlaps frames")
+
+// the two warps, after their sizes: the block grid, the image, the rest of the movers' checks
+#define DC_REQUIRE_WARP(name, frames, table, out, tc, By, Bx, H, W, fill)                                                                  \
+  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, name ": %d x %d blocks: the grid is limited to %d x %d", \
+             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS);                                                                         \
+  DC_REQUIRE_IMAGE(name, H, W);                                                                                                            \
+  DC_REQUIRE(By <= H && Bx <= W, DC_EINVAL, name ": image %d x %d in %d x %d blocks: a block is empty", H, W, By, Bx);                      \
+  DC_REQUIRE_MOVE(name, frames, table, out, tc, H, W, fill)
+
+// the three piecewise entry points that take both radii and the block grid
+#define DC_REQUIRE_GRID(name, S, D, By, Bx)                                                                                              \
+  DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, name ": S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);           \
+  DC_REQUIRE(D <= DC_MOTION_MAX_DEV, DC_EUNSUP, name ": D = %d: the block deviation radius is limited to %d", D, DC_MOTION_MAX_DEV);      \
+  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, name ": %d x %d blocks: the grid is limited to %d x %d", \
+             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS)
+
+// the two window entry points: the radii
+#define DC_REQUIRE_WINDOW(name, S, D)                                                                                                        \
+  DC_REQUIRE(S <= DC_MOTION_MAX_WIDE_SHIFT, DC_EUNSUP, name ": S = %d: the wide search radius is limited to %d", S, DC_MOTION_MAX_WIDE_SHIFT); \
+  DC_REQUIRE(D <= DC_MOTION_MAX_DEV, DC_EUNSUP, name ": D = %d: the window half-width is limited to %d", D, DC_MOTION_MAX_DEV);               \
+  DC_REQUIRE(S >= D, DC_EINVAL, name ": S = %d is smaller than the window half-width D = %d", S, D)
 
 extern "C" int dc_motion_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, long* scores,
                              dc_stream_t stream) {
   DC_REQUIRE(frames && tmpl && scores, DC_EINVAL, "dc_motion_ssd: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_ssd: negative or zero size (tc %d, S %d, H %d, W %d)", tc, S, H, W);
   DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, "dc_motion_ssd: S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_ssd: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE_IMAGE("dc_motion_ssd", H, W);
   DC_REQUIRE(H > 2 * S && W > 2 * S, DC_EINVAL, "dc_motion_ssd: image %d x %d has no interior at S = %d (H > 2S and W > 2S)", H, W, S);
   DC_REQUIRE((((uintptr_t)frames | (uintptr_t)tmpl) & 1) == 0 && (((uintptr_t)scores) & 7) == 0, DC_EINVAL, "dc_motion_ssd: misaligned buffer");
-  if (tc == 0) return DC_OK;
-  const long n = (long)tc * (2 * S + 1) * (2 * S + 1);
-  unsigned long long* sc = (unsigned long long*)scores;
-  const int blocks = (int)(dc_cdiv(n, kThreads) < kZeroBlocks ? dc_cdiv(n, kThreads) : kZeroBlocks);
-  hipLaunchKernelGGL(motion_zero_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, sc, n);
-  DC_CHECK_LAUNCH("dc_motion_ssd(zero)");
-  const uint16_t* f = (const uint16_t*)frames;
-  const uint16_t* t = (const uint16_t*)tmpl;
-  if (S <= 4) return launch_ssd<4, 8>(f, is_unsigned, tc, t, H, W, S, sc, (hipStream_t)stream);
-  if (S <= 8) return launch_ssd<8, 8>(f, is_unsigned, tc, t, H, W, S, sc, (hipStream_t)stream);
-  return launch_ssd<16, 4>(f, is_unsigned, tc, t, H, W, S, sc, (hipStream_t)stream);
+  // the exhaustive table is the window of half-width S around centre 0
+  return launch_scores("dc_motion_ssd", "dc_motion_ssd(zero)", frames, is_unsigned, tc, tmpl, H, W, S, S, nullptr, 0, scores, (hipStream_t)stream);
 }
 
 extern "C" int dc_motion_pick(const long* scores, int tc, int S, int* shifts, long* best, dc_stream_t stream) {
@@ -843,37 +771,16 @@ extern "C" int dc_motion_pick(const long* scores, int tc, int S, int* shifts, lo
   DC_REQUIRE(tc >= 0 && S >= 0, DC_EINVAL, "dc_motion_pick: negative size (tc %d, S %d)", tc, S);
   DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, "dc_motion_pick: S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);
   DC_REQUIRE((((uintptr_t)scores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)shifts) & 3) == 0, DC_EINVAL, "dc_motion_pick: misaligned buffer");
-  if (tc == 0) return DC_OK;
-  hipLaunchKernelGGL(motion_pick_kernel, dim3((unsigned)(tc < 65535 ? tc : 65535)), dim3(kWave), 0, (hipStream_t)stream,
-                     (const int64_t*)scores, tc, S, shifts, (int64_t*)best);
-  DC_CHECK_LAUNCH("dc_motion_pick");
-  return DC_OK;
+  return launch_pick("dc_motion_pick", scores, nullptr, 0, tc, S, S, shifts, best, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int dc_motion_apply(const void* frames, int tc, const int* shifts, int H, int W, int fill, void* out, dc_stream_t stream) {
   DC_REQUIRE(frames && shifts && out, DC_EINVAL, "dc_motion_apply: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_apply: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_apply: image %d x %d: H * W is limited to 2^30", H, W);
-  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, "dc_motion_apply: fill = %d is not a 16-bit value", fill);
-  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)shifts) & 3) == 0, DC_EINVAL, "dc_motion_apply: misaligned buffer");
-  const uintptr_t bytes = (uintptr_t)tc * H * W * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
-  DC_REQUIRE(bytes == 0 || fa + bytes <= oa || oa + bytes <= fa, DC_EINVAL, "dc_motion_apply: out overlaps frames");
-  if (tc == 0) return DC_OK;
-  const int groups = dc_cdiv((long)H * W + 7, 8);
-  const int bx = dc_cdiv(groups, kThreads);
-  const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(motion_apply_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, shifts, H, W,
-                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0));
-  DC_CHECK_LAUNCH("dc_motion_apply");
-  return DC_OK;
+  DC_REQUIRE_IMAGE("dc_motion_apply", H, W);
+  DC_REQUIRE_MOVE("dc_motion_apply", frames, shifts, out, tc, H, W, fill);
+  return launch_apply<false>("dc_motion_apply", frames, 0u, tc, shifts, H, W, fill, out, (hipStream_t)stream);
 }
-
-// what the three piecewise entry points share: the radii and the block grid
-#define DC_REQUIRE_GRID(name, S, D, By, Bx)                                                                                              \
-  DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, name ": S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);           \
-  DC_REQUIRE(D <= DC_MOTION_MAX_DEV, DC_EUNSUP, name ": D = %d: the block deviation radius is limited to %d", D, DC_MOTION_MAX_DEV);      \
-  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, name ": %d x %d blocks: the grid is limited to %d x %d", \
-             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS)
 
 extern "C" int dc_motion_block_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, int By, int Bx,
                                    const int* rigid, long* bscores, dc_stream_t stream) {
@@ -881,17 +788,15 @@ extern "C" int dc_motion_block_ssd(const void* frames, int is_unsigned, int tc, 
   DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL,
              "dc_motion_block_ssd: negative or zero size (tc %d, S %d, D %d, H %d, W %d, blocks %d x %d)", tc, S, D, H, W, By, Bx);
   DC_REQUIRE_GRID("dc_motion_block_ssd", S, D, By, Bx);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_block_ssd: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE_IMAGE("dc_motion_block_ssd", H, W);
   DC_REQUIRE(dc_block_axis_ok(H, By, S + D) && dc_block_axis_ok(W, Bx, S + D), DC_EINVAL,
              "dc_motion_block_ssd: image %d x %d in %d x %d blocks: a block has no interior at S + D = %d", H, W, By, Bx, S + D);
   DC_REQUIRE((((uintptr_t)frames | (uintptr_t)tmpl) & 1) == 0 && (((uintptr_t)rigid) & 3) == 0 && (((uintptr_t)bscores) & 7) == 0, DC_EINVAL,
              "dc_motion_block_ssd: misaligned buffer");
   if (tc == 0) return DC_OK;
-  const uint16_t* f = (const uint16_t*)frames;
-  const uint16_t* t = (const uint16_t*)tmpl;
   unsigned long long* sc = (unsigned long long*)bscores;
-  if (D <= 4) return launch_block_ssd<4>(f, is_unsigned, tc, t, H, W, S, D, By, Bx, rigid, sc, (hipStream_t)stream);
-  return launch_block_ssd<8>(f, is_unsigned, tc, t, H, W, S, D, By, Bx, rigid, sc, (hipStream_t)stream);
+  if (D <= 4) return launch_block_ssd<4>(frames, is_unsigned, tc, tmpl, H, W, S, D, By, Bx, rigid, sc, (hipStream_t)stream);
+  return launch_block_ssd<8>(frames, is_unsigned, tc, tmpl, H, W, S, D, By, Bx, rigid, sc, (hipStream_t)stream);
 }
 
 extern "C" int dc_motion_block_pick(const long* bscores, const int* rigid, int tc, int By, int Bx, int S, int D, int* block_shifts, long* best,
@@ -915,22 +820,8 @@ extern "C" int dc_motion_warp(const void* frames, int tc, const int* block_shift
   DC_REQUIRE(frames && block_shifts && out, DC_EINVAL, "dc_motion_warp: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL, "dc_motion_warp: negative or zero size (tc %d, H %d, W %d, blocks %d x %d)",
              tc, H, W, By, Bx);
-  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, "dc_motion_warp: %d x %d blocks: the grid is limited to %d x %d",
-             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_warp: image %d x %d: H * W is limited to 2^30", H, W);
-  DC_REQUIRE(By <= H && Bx <= W, DC_EINVAL, "dc_motion_warp: image %d x %d in %d x %d blocks: a block is empty", H, W, By, Bx);
-  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, "dc_motion_warp: fill = %d is not a 16-bit value", fill);
-  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)block_shifts) & 3) == 0, DC_EINVAL, "dc_motion_warp: misaligned buffer");
-  const uintptr_t bytes = (uintptr_t)tc * H * W * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
-  DC_REQUIRE(bytes == 0 || fa + bytes <= oa || oa + bytes <= fa, DC_EINVAL, "dc_motion_warp: out overlaps frames");
-  if (tc == 0) return DC_OK;
-  const int tilesX = dc_cdiv(W, kWarpCols);
-  const long tiles = (long)tilesX * dc_cdiv(H, kWarpRows);              // H * W <= 2^30: at most 2^30 tiles
-  const dim3 grid((unsigned)tiles, (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(motion_warp_kernel<false>, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, block_shifts, By, Bx, H, W,
-                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0), tilesX, 0u);
-  DC_CHECK_LAUNCH("dc_motion_warp");
-  return DC_OK;
+  DC_REQUIRE_WARP("dc_motion_warp", frames, block_shifts, out, tc, By, Bx, H, W, fill);
+  return launch_warp<false>("dc_motion_warp", frames, 0u, tc, block_shifts, By, Bx, H, W, fill, out, (hipStream_t)stream);
 }
 
 extern "C" int dc_motion_refine(const long* scores, const int* shifts, int tc, int S, int* fine, dc_stream_t stream) {
@@ -965,19 +856,9 @@ extern "C" int dc_motion_apply_sub(const void* frames, int is_unsigned, int tc, 
                                    dc_stream_t stream) {
   DC_REQUIRE(frames && fine && out, DC_EINVAL, "dc_motion_apply_sub: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_apply_sub: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_apply_sub: image %d x %d: H * W is limited to 2^30", H, W);
-  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, "dc_motion_apply_sub: fill = %d is not a 16-bit value", fill);
-  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)fine) & 3) == 0, DC_EINVAL, "dc_motion_apply_sub: misaligned buffer");
-  const uintptr_t bytes = (uintptr_t)tc * H * W * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
-  DC_REQUIRE(bytes == 0 || fa + bytes <= oa || oa + bytes <= fa, DC_EINVAL, "dc_motion_apply_sub: out overlaps frames");
-  if (tc == 0) return DC_OK;
-  const int groups = dc_cdiv((long)H * W + 7, 8);
-  const int bx = dc_cdiv(groups, kThreads);
-  const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(motion_apply_sub_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, is_unsigned ? 0u : 0x8000u, tc, fine,
-                     H, W, (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0));
-  DC_CHECK_LAUNCH("dc_motion_apply_sub");
-  return DC_OK;
+  DC_REQUIRE_IMAGE("dc_motion_apply_sub", H, W);
+  DC_REQUIRE_MOVE("dc_motion_apply_sub", frames, fine, out, tc, H, W, fill);
+  return launch_apply<true>("dc_motion_apply_sub", frames, is_unsigned ? 0u : 0x8000u, tc, fine, H, W, fill, out, (hipStream_t)stream);
 }
 
 extern "C" int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, const int* fine_block_shifts, int By, int Bx, int H, int W,
@@ -985,23 +866,9 @@ extern "C" int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, c
   DC_REQUIRE(frames && fine_block_shifts && out, DC_EINVAL, "dc_motion_warp_sub: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL,
              "dc_motion_warp_sub: negative or zero size (tc %d, H %d, W %d, blocks %d x %d)", tc, H, W, By, Bx);
-  DC_REQUIRE(By <= DC_MOTION_MAX_BLOCKS && Bx <= DC_MOTION_MAX_BLOCKS, DC_EUNSUP, "dc_motion_warp_sub: %d x %d blocks: the grid is limited to %d x %d",
-             By, Bx, DC_MOTION_MAX_BLOCKS, DC_MOTION_MAX_BLOCKS);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_warp_sub: image %d x %d: H * W is limited to 2^30", H, W);
-  DC_REQUIRE(By <= H && Bx <= W, DC_EINVAL, "dc_motion_warp_sub: image %d x %d in %d x %d blocks: a block is empty", H, W, By, Bx);
-  DC_REQUIRE(fill >= -32768 && fill <= 65535, DC_EINVAL, "dc_motion_warp_sub: fill = %d is not a 16-bit value", fill);
-  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)fine_block_shifts) & 3) == 0, DC_EINVAL,
-             "dc_motion_warp_sub: misaligned buffer");
-  const uintptr_t bytes = (uintptr_t)tc * H * W * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
-  DC_REQUIRE(bytes == 0 || fa + bytes <= oa || oa + bytes <= fa, DC_EINVAL, "dc_motion_warp_sub: out overlaps frames");
-  if (tc == 0) return DC_OK;
-  const int tilesX = dc_cdiv(W, kWarpCols);
-  const long tiles = (long)tilesX * dc_cdiv(H, kWarpRows);
-  const dim3 grid((unsigned)tiles, (unsigned)(tc < 65535 ? tc : 65535)), block(kThreads);
-  hipLaunchKernelGGL(motion_warp_kernel<true>, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, fine_block_shifts, By, Bx, H, W,
-                     (unsigned)fill & 0xffffu, (uint16_t*)out, (int)((oa & 15) == 0), tilesX, is_unsigned ? 0u : 0x8000u);
-  DC_CHECK_LAUNCH("dc_motion_warp_sub");
-  return DC_OK;
+  DC_REQUIRE_WARP("dc_motion_warp_sub", frames, fine_block_shifts, out, tc, By, Bx, H, W, fill);
+  return launch_warp<true>("dc_motion_warp_sub", frames, is_unsigned ? 0u : 0x8000u, tc, fine_block_shifts, By, Bx, H, W, fill, out,
+                           (hipStream_t)stream);
 }
 
 extern "C" int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H, int W, int c, void* out, dc_stream_t stream) {
@@ -1009,7 +876,7 @@ extern "C" int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H,
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_bin: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
   const int lg = dc_motion_bin_log2(c);
   DC_REQUIRE(lg > 0, DC_EUNSUP, "dc_motion_bin: c = %d: the binning factor is limited to 2, 4 and 8", c);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_bin: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE_IMAGE("dc_motion_bin", H, W);
   DC_REQUIRE((H >> lg) > 0 && (W >> lg) > 0, DC_EINVAL, "dc_motion_bin: image %d x %d holds no %d x %d bin", H, W, c, c);
   DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0, DC_EINVAL, "dc_motion_bin: misaligned buffer");
   const uintptr_t fb = (uintptr_t)tc * H * W * 2, ob = (uintptr_t)tc * (H >> lg) * (W >> lg) * 2, fa = (uintptr_t)frames, oa = (uintptr_t)out;
@@ -1021,32 +888,18 @@ extern "C" int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H,
   return launch_bin<3>(f, is_unsigned, tc, H, W, (uint16_t*)out, (hipStream_t)stream);
 }
 
-// what the two window entry points share: the radii
-#define DC_REQUIRE_WINDOW(name, S, D)                                                                                                        \
-  DC_REQUIRE(S <= DC_MOTION_MAX_WIDE_SHIFT, DC_EUNSUP, name ": S = %d: the wide search radius is limited to %d", S, DC_MOTION_MAX_WIDE_SHIFT); \
-  DC_REQUIRE(D <= DC_MOTION_MAX_DEV, DC_EUNSUP, name ": D = %d: the window half-width is limited to %d", D, DC_MOTION_MAX_DEV);               \
-  DC_REQUIRE(S >= D, DC_EINVAL, name ": S = %d is smaller than the window half-width D = %d", S, D)
-
 extern "C" int dc_motion_ssd_around(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, const int* rows,
                                     int mult, long* wscores, dc_stream_t stream) {
   DC_REQUIRE(frames && tmpl && rows && wscores, DC_EINVAL, "dc_motion_ssd_around: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_ssd_around: negative or zero size (tc %d, S %d, D %d, H %d, W %d)",
              tc, S, D, H, W);
   DC_REQUIRE_WINDOW("dc_motion_ssd_around", S, D);
-  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_motion_ssd_around: image %d x %d: H * W is limited to 2^30", H, W);
+  DC_REQUIRE_IMAGE("dc_motion_ssd_around", H, W);
   DC_REQUIRE(H > 2 * S && W > 2 * S, DC_EINVAL, "dc_motion_ssd_around: image %d x %d has no interior at S = %d (H > 2S and W > 2S)", H, W, S);
   DC_REQUIRE((((uintptr_t)frames | (uintptr_t)tmpl) & 1) == 0 && (((uintptr_t)rows) & 3) == 0 && (((uintptr_t)wscores) & 7) == 0, DC_EINVAL,
              "dc_motion_ssd_around: misaligned buffer");
-  if (tc == 0) return DC_OK;
-  const long n = (long)tc * (2 * D + 1) * (2 * D + 1);
-  unsigned long long* sc = (unsigned long long*)wscores;
-  const int blocks = (int)(dc_cdiv(n, kThreads) < kZeroBlocks ? dc_cdiv(n, kThreads) : kZeroBlocks);
-  hipLaunchKernelGGL(motion_zero_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, sc, n);
-  DC_CHECK_LAUNCH("dc_motion_ssd_around(zero)");
-  const uint16_t* f = (const uint16_t*)frames;
-  const uint16_t* t = (const uint16_t*)tmpl;
-  if (D <= 4) return launch_ssd_around<4, 8>(f, is_unsigned, tc, t, H, W, S, D, rows, mult, sc, (hipStream_t)stream);
-  return launch_ssd_around<8, 8>(f, is_unsigned, tc, t, H, W, S, D, rows, mult, sc, (hipStream_t)stream);
+  return launch_scores("dc_motion_ssd_around", "dc_motion_ssd_around(zero)", frames, is_unsigned, tc, tmpl, H, W, S, D, rows, mult, wscores,
+                       (hipStream_t)stream);
 }
 
 extern "C" int dc_motion_pick_around(const long* wscores, const int* rows, int mult, int tc, int S, int D, int* shifts, long* best, int* fine,
@@ -1056,9 +909,5 @@ extern "C" int dc_motion_pick_around(const long* wscores, const int* rows, int m
   DC_REQUIRE_WINDOW("dc_motion_pick_around", S, D);
   DC_REQUIRE((((uintptr_t)wscores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL,
              "dc_motion_pick_around: misaligned buffer");
-  if (tc == 0) return DC_OK;
-  hipLaunchKernelGGL(motion_pick_around_kernel, dim3((unsigned)(tc < 65535 ? tc : 65535)), dim3(kWave), 0, (hipStream_t)stream,
-                     (const int64_t*)wscores, rows, mult, tc, S, D, shifts, (int64_t*)best, fine);
-  DC_CHECK_LAUNCH("dc_motion_pick_around");
-  return DC_OK;
+  return launch_pick("dc_motion_pick_around", wscores, rows, mult, tc, S, D, shifts, best, fine, (hipStream_t)stream);
 }

@@ -61,7 +61,8 @@ def _apply(L, frames, shifts, fill):
 #   (21, 35, 5, 2):   S = 5 on the S <= 8 instantiation
 #   (34, 528, 8, 2):  512 interior columns: every lane full, the path without the ragged-lane mask, all 64 lanes
 SSD_SHAPES = [(9, 9, 4, 1), (19, 23, 3, 5), (37, 70, 8, 33), (70, 150, 2, 3), (40, 40, 0, 4), (40, 41, 16, 2),
-              (11, 1040, 1, 2), (37, 531, 9, 1), (21, 35, 5, 2), (34, 528, 8, 2)]
+              (11, 1040, 1, 2), (37, 531, 9, 1), (21, 35, 5, 2), (34, 528, 8, 2),
+              (50, 560, 16, 1)]                          # S = 16: a full 512-column tile plus a 16-pixel one, two row tiles (16 + 2)
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
