@@ -20,8 +20,8 @@ chunk on the same stream, so one pass gives the maps AND the traces:
     corr, coords, inside = roi_footprints_device('dataset.hdf5', mask, halo=2)
 
 A pixel or a trace that is constant in time (a single frame included) and the pixel of a one-pixel ROI have a correlation of
-exactly 0 here; numpy divides 0 by 0 there.  Splitting one ROI into two is out of scope: the map makes the two halves visible,
-refine_rois keeps the larger.
+exactly 0 here; numpy divides 0 by 0 there.  The map cannot split one ROI into two (both halves correlate with the summed trace,
+and refine_rois keeps the larger): roi_pairs.py does, from the correlation of the ROI's pixels with each other.
 
 Importing this module needs neither torch nor the GPU; constructing a RoiFootprints does (there is no CPU fallback).
 """
@@ -74,12 +74,23 @@ def roi_support(rois, shape, halo=2):
     return [np.stack([f // shape[1], f % shape[1]], 1).astype(np.int64) for f in flat], inside
 
 
+def _largest_component(c):
+    """c: (n,2) integer [y,x], n >= 1 -> its largest 8-connected component as (m,2) int64 in flat-index order (labelled by
+    nf_metrics.mask_to_regions; ties: the component that holds the smallest flat index)."""
+    from .nf_metrics import mask_to_regions
+    y0, x0 = c.min(0)
+    m = np.zeros((int(c[:, 0].max() - y0) + 1, int(c[:, 1].max() - x0) + 1), bool)
+    m[c[:, 0] - y0, c[:, 1] - x0] = True
+    regions = mask_to_regions(m)                     # raster label order: the first of the largest holds the smallest flat index
+    best = regions[int(np.argmax([len(g) for g in regions]))]
+    return (best + np.array([y0, x0])).astype(np.int64)
+
+
 def refine_rois(coords, corr, shape, threshold=0.3, min_area=1):
     """-> (new_rois, kept).  Per ROI: the entries with corr >= threshold, of those the largest 8-connected component (ties: the one
     that holds the smallest flat index; labelled by nf_metrics.mask_to_regions), dropped if fewer than min_area pixels remain.
     new_rois: the survivors as (k,2) int64 [y,x] arrays in flat-index order; kept: the indices of the ROIs they came from.
     coords / corr: what RoiFootprints.support() / result('corr') return.  Host numpy only."""
-    from .nf_metrics import mask_to_regions
     H, W = _check_shape(shape)
     min_area = _as_int(min_area, 'min_area')
     if min_area < 1:
@@ -102,14 +113,10 @@ def refine_rois(coords, corr, shape, threshold=0.3, min_area=1):
         c = c[v.astype(np.float64) >= threshold]     # compared as doubles, whatever the map's dtype
         if len(c) == 0:
             continue
-        y0, x0 = c.min(0)
-        m = np.zeros((int(c[:, 0].max() - y0) + 1, int(c[:, 1].max() - x0) + 1), bool)
-        m[c[:, 0] - y0, c[:, 1] - x0] = True
-        regions = mask_to_regions(m)                 # raster label order: the first of the largest holds the smallest flat index
-        best = regions[int(np.argmax([len(g) for g in regions]))]
+        best = _largest_component(c)
         if len(best) < min_area:
             continue
-        new_rois.append((best + np.array([y0, x0])).astype(np.int64))
+        new_rois.append(best)
         kept.append(r)
     return new_rois, kept
 

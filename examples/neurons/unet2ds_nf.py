@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -32,7 +32,8 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
-                              estimate_shifts_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois)
+                              estimate_shifts_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
+                              split_rois_device)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -121,7 +122,7 @@ def _neuropil_arg(text):
 
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
-           percentile=8, neuropil=None, refine=None, halo=2, coarse=None):
+           percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -135,7 +136,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     default 8), after subtracting neuropil=(inner, outer, weight) times the trace of a ring around every ROI when given.
     refine=THR: a first pass over the recording computes every ROI's footprint map (the correlation of each pixel of the ROI and of
     a `halo` around it with the ROI's trace); every ROI is cut down (or grown) to the largest connected set of pixels with
-    correlation >= THR, ROIs with none are dropped, and the traces are those of the refined ROIs (a second pass)."""
+    correlation >= THR, ROIs with none are dropped, and the traces are those of the refined ROIs (a second pass).
+    split=GAP: one more pass over the recording (after the refinement, where both are given) computes the correlation of every
+    pixel of an ROI with every other one; an ROI whose pixels fall into two groups, each of at least `min_area` pixels and more
+    correlated within than across by GAP (deep_calcium_amd.split_rois), becomes two ROIs with a trace each."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -182,6 +186,12 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             if not rois:
                 logger.info('%s: no ROI survives the refinement, no traces file.' % name)
                 continue
+            mask = rois
+        if split is not None:
+            rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, **{known: shifts.get(dspath)})
+            before = int(np.count_nonzero(mask)) if isinstance(mask, np.ndarray) else sum(len(r) for r in mask)
+            logger.info('%s: split at gap >= %g (min area %d): %d of %d ROIs split, %d pixels dropped' % (
+                name, split, min_area, len(rois) - len(gaps), len(gaps), before - sum(len(r) for r in rois)))
             mask = rois
         if dff is not None:
             tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **{known: shifts.get(dspath)})
@@ -236,6 +246,10 @@ if __name__ == '__main__':
                         default=None, type=float, metavar='THR')
     sp_trc.add_argument('--halo', help='with --refine: how far beyond an ROI, in pixels, its footprint map reaches (0..16, default 2)', default=2,
                         type=int, metavar='N')
+    sp_trc.add_argument('--split', help='split every ROI whose pixels form two groups that correlate more within than across by GAP (default 0.1)',
+                        nargs='?', const=0.1, default=None, type=float, metavar='GAP')
+    sp_trc.add_argument('--min-area', help='with --split: the fewest pixels a part may have (default 8)', default=8, type=int, metavar='N',
+                        dest='min_area')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

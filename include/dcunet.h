@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 118
+#define DC_ABI_VERSION 119
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -599,6 +599,48 @@ int dc_roi_pixel_accumulate(const void* frames, int is_unsigned, int tc, long t0
 int dc_roi_trace_moments(const long* sums, long ld, int R, long T, long* rmom, dc_stream_t stream);
 int dc_roi_pixel_corr(const long* mom, int N, const int* row_off, const int* row_roi, int S, int R, const int* inside,
                       const long* rmom, long T, float* corr, dc_stream_t stream);
+
+/* ---- ROI pixel-pair correlation: the correlation of every pixel of an ROI with every other pixel of it ---------------------------
+ * An ROI is an 8-connected region of a mask predicted from ONE summary image, so two cells that touch are one ROI with one
+ * trace.  The footprint map above cannot separate them (both halves correlate with the summed trace); the correlation of the
+ * pixels with EACH OTHER can.  That is a k x k Gram matrix per ROI, accumulated over the recording beside the traces.  The
+ * reference has no counterpart; THESE DEFINITIONS ARE THE SPECIFICATION.  Integers until the last step, independent of how the
+ * recording was chunked.
+ * ROI r: k_r own pixels in flat-index order (no halo), x_i(t) the i-th of them in frame t.  Over all T frames:
+ *   a_i  = sum_t x_i(t)                       int64, exact, |a_i| < 2^47
+ *   g_ij = sum_t x_i(t) x_j(t), i <= j        int64, exact, |g_ij| <= 65535^2 T < 2^63
+ *   Cij  = T g_ij - a_i a_j                   exact in 128-bit integers (|T g| < 2^94, |a a| < 2^94)
+ *   corr_ij = dc_fp_corr of csrc/footprint_math.h on {Cii, Cij, Cjj}: (float)(f64(Cij) / (sqrt(f64(Cii)) * sqrt(f64(Cjj)))), each
+ *             numerator rounded ONCE to double, no fused multiply-add: within 1 float32 ulp, bit-symmetric, in [-1, 1], the
+ *             diagonal exactly 1 for a pixel that varies; row, column AND diagonal exactly 0 for a pixel that is constant in time
+ *             (T == 1 included; numpy: NaN).
+ * Limits: T <= DC_ROI_PIXEL_MAX_FRAMES and T * H * W <= DC_ROI_TRACE_MAX_VOLUME as above; k_r <= DC_ROI_PAIR_MAX_AREA;
+ * G = sum k_r^2 <= DC_ROI_PAIR_MAX_STATE (1 GiB of int64).  Beyond: DC_EUNSUP (-3).
+ * All pointers are DEVICE memory, there are no out-parameters and nothing is read on the host.
+ *   state: a = int64[P], P = sum k_r, in the order of roi_pix; g = int64[G]: ROI r owns a full k_r x k_r row-major square at
+ *     goff[r].  CALLER-OWNED AND CALLER-ZEROED before the first chunk; dc_roi_pair_accumulate ADDS the chunk's contribution to a
+ *     and to the entries i <= j of g.  The lower triangle is never read or written by it.
+ *   dc_roi_pair_accumulate: frames as for dc_roi_trace_accumulate, a chunk of tc frames.  roi_off int32[R + 1], roi_pix
+ *     int32[P] flat indices y * W + x, goff int64[R].  tiles int32[ntiles][3] = (r, ti, tj), ti <= tj: one workgroup per tile of
+ *     DC_ROI_PAIR_TILE x DC_ROI_PAIR_TILE pairs (rows ti * TILE.., columns tj * TILE.. of ROI r's square); the caller lists
+ *     every tile with ti <= tj < ceil(k_r / TILE) of every ROI ONCE.  The tile ti == tj also owns a for its pixels.  Every state
+ *     word is read, added to and written once per call by one thread of one workgroup: no atomics, the same bits for every
+ *     chunking and every run.  The frames are staged DC_ROI_PAIR_BATCH at a time.  A tile that names an ROI outside [0, R), with
+ *     tj < ti or outside the ROI, an ROI with k_r > DC_ROI_PAIR_MAX_AREA or whose square leaves [0, G) or whose pixels leave
+ *     [0, P) is skipped whole; a pixel index outside [0, H*W) is never dereferenced and counts as 0.  What the host can see of
+ *     the limits is refused: G > DC_ROI_PAIR_MAX_STATE, G > DC_ROI_PAIR_MAX_AREA * P, ntiles >= 2^31, or more tiles than R
+ *     ROIs of the largest area have.
+ *   dc_roi_pair_corr: corr float[G] in the layout of g: every (i, j) of every ROI's square is written, the lower triangle
+ *     included (it reads g at [min(i,j)][max(i,j)]).  An ROI that dc_roi_pair_accumulate would skip is skipped.
+ * R == 0, P == 0, G == 0, ntiles == 0 (and tc == 0 for the accumulation): 0, nothing launched. */
+#define DC_ROI_PAIR_TILE 64
+#define DC_ROI_PAIR_BATCH 32
+#define DC_ROI_PAIR_MAX_AREA 1024
+#define DC_ROI_PAIR_MAX_STATE 134217728L
+int dc_roi_pair_accumulate(const void* frames, int is_unsigned, int tc, const int* roi_off, const int* roi_pix, const long* goff,
+                           const int* tiles, long ntiles, int R, long* a, long* g, int P, long G, int H, int W, dc_stream_t stream);
+int dc_roi_pair_corr(const long* a, const long* g, const int* roi_off, const long* goff, int R, int P, long G, long T, float* corr,
+                     dc_stream_t stream);
 
 /* ---- dF/F traces: neuropil correction, rolling-percentile baseline, (F - F0) / F0 -----------------------------------------------
  * The step between ROI traces and spikes that the z-score above cannot replace: a recording bleaches and drifts, and every ROI
