@@ -30,7 +30,8 @@ _EXPORTS = {
     'footprints': ('RoiFootprints', 'roi_footprints_device', 'roi_support', 'refine_rois'),
     'roi_pairs': ('RoiPairCorr', 'roi_pair_corr_device', 'split_rois', 'split_rois_device'),
     'dff': ('TraceBaseline', 'neuropil_rois', 'dff_traces_device'),
-    'motion': ('MotionCorrector', 'make_template', 'estimate_shifts_device', 'valid_rectangle', 'fine_to_pixels'),
+    'motion': ('MotionCorrector', 'make_template', 'estimate_shifts_device', 'valid_rectangle', 'fine_to_pixels', 'BidiEstimator',
+               'pick_bidi', 'estimate_bidi_device'),
     'spikes': ('UNet1DSegmentation', 'predict_spikes_device'),
     'unet1d': ('UNet1DEngine',),
     'unet1d_train': ('UNet1DTrainEngine',),

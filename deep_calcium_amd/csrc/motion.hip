@@ -11,6 +11,9 @@
 // Wide search beside the exhaustive one, for shifts up to 128: frames and template binned c x c (dc_motion_bin), the coarse pick by
 // dc_motion_ssd + dc_motion_pick on the binned pair, then the full-resolution scores within +-c of c times that pick
 // (dc_motion_ssd_around) and the pick over total shifts (dc_motion_pick_around).
+// In front of all of it, the bidirectional scan-phase correction: the odd lines of every frame scored against their even neighbours
+// at every horizontal offset within +-P (dc_bidi_scores: bidi_scores_kernel, built from the same tile pieces) and moved by the one
+// offset the host picks for the recording (dc_bidi_apply: bidi_apply_kernel, the whole-pixel mover with a shift per row parity).
 // Every piece exists once.  The exhaustive entry points are the window ones at centre 0: motion_ssd_kernel scores the shifts within
 // +-D of a centre per frame (dc_motion_ssd: D = S, no centres) and motion_pick_kernel picks over centre + residual.  The two score
 // kernels (frame-wide tiles, tiles of a block) are built from the same four tile_* pieces around ssd_rows; the movers
@@ -626,6 +629,147 @@ __global__ __launch_bounds__(kThreads) void motion_bin_kernel(const uint16_t* __
   }
 }
 
+// ---- bidirectional scan-phase correction: line scores and the odd-row move (the definitions are in include/dcunet.h) -------------
+const int kBidiR = 4;                                          // odd rows a wave owns
+const int kBidiTH = kWaves * kBidiR;                           // odd rows of one workgroup's tile: 16
+const int kBidiRows = 2 * kBidiTH + 1;                         // frame rows of the tile: its odd rows and the even rows around them
+
+// LDS of a score launch: the tile's frame rows (the odd ones with their P-wide halo), then the 2P+1 totals of the workgroup
+__host__ __device__ inline size_t bidi_tile_bytes(int P) { return (size_t)kBidiRows * ssd_stride(P) * sizeof(uint16_t); }
+inline int bidi_lds(int P) { return (int)bidi_tile_bytes(P) + (2 * P + 1) * (int)sizeof(long long); }
+
+// The nr odd rows of one lane against their even neighbours, all nd offsets:  acc[k] += (2 f[y][x + k - P] - f[y-1][x] - f[y+1][x])^2.
+// LDS row 2 j + 1 is the lane's odd row j (column 0: P columns left of the tile's first interior pixel), rows 2 j and 2 j + 2 the even
+// rows around it (column 0: that pixel).  |e| <= 131070, so e^2 needs 34 bits: the product is formed in 64 bits from |e| (one
+// 32 x 32 -> 64 multiply-add).  A lane adds at most kBidiR * kPix = 32 of them per offset: < 2^39.  RAG as for ssd_rows.
+template <int PMAX, bool RAG>
+__device__ __forceinline__ void bidi_rows(const uint16_t* __restrict__ ft, int stride, int P, int nd, int nr, int row0, int lane,
+                                         const unsigned (&mk)[kPix], unsigned long long (&acc)[2 * PMAX + 1]) {
+  constexpr int NK = 2 * PMAX + 1, FW = kPix + 2 * PMAX;
+  uint4 up = *reinterpret_cast<const uint4*>(ft + (long)(2 * row0) * stride + kPix * lane);
+#pragma unroll
+  for (int j = 0; j < kBidiR; ++j) {
+    if (j < nr) {                                        // wave-uniform
+      const uint4 dn = *reinterpret_cast<const uint4*>(ft + (long)(2 * (row0 + j) + 2) * stride + kPix * lane);
+      const unsigned u2[kPix / 2] = {up.x, up.y, up.z, up.w}, d2[kPix / 2] = {dn.x, dn.y, dn.z, dn.w};
+      int n[kPix];
+#pragma unroll
+      for (int p = 0; p < kPix; ++p) n[p] = (int)((u2[p / 2] >> (16 * (p & 1))) & 0xffffu) + (int)((d2[p / 2] >> (16 * (p & 1))) & 0xffffu);
+      const uint4* src = reinterpret_cast<const uint4*>(ft + (long)(2 * (row0 + j) + 1) * stride + kPix * lane);
+      unsigned w[FW / 2];
+#pragma unroll
+      for (int q = 0; q < FW / 8; ++q) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (q * 8 < kPix + 2 * P) v = src[q];            // wave-uniform: the window is kPix + 2P values long
+        w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+      }
+      int fw[FW];
+#pragma unroll
+      for (int i = 0; i < FW; ++i) fw[i] = (int)((w[i / 2] >> (16 * (i & 1))) & 0xffffu);
+#pragma unroll
+      for (int k = 0; k < NK; ++k) {
+        if (k < nd) {                                    // wave-uniform
+#pragma unroll
+          for (int p = 0; p < kPix; ++p) {
+            int e = 2 * fw[p + k] - n[p];                // 18 bits and a sign
+            if (RAG) e = (int)((unsigned)e & mk[p]);
+            const unsigned a = (unsigned)(e < 0 ? -e : e);
+            acc[k] += (unsigned long long)a * a;
+          }
+        }
+      }
+      up = dn;
+    }
+  }
+}
+
+// scores[f][p + P] of include/dcunet.h.  One workgroup per tile of kBidiTH odd rows x 512 interior columns and frame.  The tile's
+// 2 * kBidiTH + 1 frame rows are staged in LDS once (values with the sign bit flipped for int16: all four terms of a difference
+// move by 32768, the difference does not) and reused for all 2P+1 offsets; a lane owns kPix consecutive interior columns of kBidiR
+// odd rows.  Outside the frame the tile holds 0, read by lanes without pixels only, or masked: a pixel that counts has
+// y + 1 <= H - 1 and P <= x - P, x + P <= W - 1.  The wave adds its sums by shuffles, the workgroup's totals meet in LDS, and ONE
+// 64-bit atomic per offset and workgroup goes to memory (integer addition: the order does not matter).
+template <int PMAX>
+__global__ __launch_bounds__(kThreads) void bidi_scores_kernel(const uint16_t* __restrict__ frames, unsigned flip, int tc, int H, int W, int P,
+                                                              unsigned long long* __restrict__ scores, int tilesX) {
+  constexpr int NK = 2 * PMAX + 1;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nd = 2 * P + 1, stride = ssd_stride(P);
+  uint16_t* ft = reinterpret_cast<uint16_t*>(smem);
+  unsigned long long* sc = reinterpret_cast<unsigned long long*>(smem + bidi_tile_bytes(P));
+  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  const int tx = blockIdx.x % tilesX, ty = blockIdx.x / tilesX;
+  const int i0 = tx * kTileW, j0 = ty * kBidiTH;         // the tile's first interior column, counted from P, and its first odd row, counted in odd rows
+  const int IW = W - 2 * P, NO = (H - 1) / 2;            // interior columns; odd rows y = 2 j + 1 with y + 1 <= H - 1
+  const int left = IW - i0 - kPix * lane, down = NO - j0 - wave * kBidiR;
+  const int np = left < 0 ? 0 : (left < kPix ? left : kPix);      // interior pixels of this lane
+  const int nr = down < 0 ? 0 : (down < kBidiR ? down : kBidiR);  // odd rows of this wave
+  unsigned mk[kPix];
+  const bool ragged = tile_mask(np, mk);
+  for (int f = blockIdx.y; f < tc; f += gridDim.y) {
+    const uint16_t* fr = frames + (long)f * H * W;
+    __syncthreads();                                     // the readers of the previous frame's tile and totals are done
+    for (int r = wave; r < kBidiRows; r += kWaves) {
+      // LDS row r is frame row 2 j0 + r; an odd row starts P columns left of the interior pixel an even row starts at
+      const int gy = 2 * j0 + r, ox = (r & 1) ? i0 : P + i0, cols = (r & 1) ? stride : kTileW;
+      for (int c = lane; c < cols; c += kWave) {
+        const int gx = ox + c;
+        ft[r * stride + c] = (gy < H && gx < W) ? (uint16_t)(fr[(long)gy * W + gx] ^ flip) : (uint16_t)0;
+      }
+    }
+    for (int i = threadIdx.x; i < nd; i += kThreads) sc[i] = 0;
+    __syncthreads();
+    if (nr > 0) {                                        // wave-uniform: EVERY lane of the wave takes part in the shuffles
+      unsigned long long acc[NK];
+#pragma unroll
+      for (int k = 0; k < NK; ++k) acc[k] = 0;
+      if (np > 0) {
+        if (ragged) bidi_rows<PMAX, true>(ft, stride, P, nd, nr, wave * kBidiR, lane, mk, acc);
+        else bidi_rows<PMAX, false>(ft, stride, P, nd, nr, wave * kBidiR, lane, mk, acc);
+      }
+      unsigned long long mine = 0;
+#pragma unroll
+      for (int k = 0; k < NK; ++k) {
+        if (k < nd) {
+          const unsigned long long s = wave_sum64(acc[k]);
+          if (lane == k) mine = s;
+        }
+      }
+      if (lane < nd) atomicAdd(&sc[lane], mine);
+    }
+    __syncthreads();
+    unsigned long long* dst = scores + (long)f * nd;
+    for (int i = threadIdx.x; i < nd; i += kThreads) {
+      const unsigned long long v = sc[i];
+      if (v) atomicAdd(dst + i, v);
+    }
+  }
+}
+
+// out[t][y][x] = frames[t][y][x + p] for odd y (fill where x + p leaves the row), frames[t][y][x] for even y: motion_apply_kernel
+// with the shift (0, p) on the odd rows and (0, 0) on the even ones -- the same groups of 8 of the WHOLE output, the same put8 / put1.
+__global__ __launch_bounds__(kThreads) void bidi_apply_kernel(const uint16_t* __restrict__ frames, int tc, int p, int H, int W, unsigned fill,
+                                                             uint16_t* __restrict__ out, int wide) {
+  const int HW = H * W;
+  for (int t = blockIdx.y; t < tc; t += gridDim.y) {
+    const long base = (long)t * HW;
+    const int off = (int)(base & 7);
+    const int groups = (HW + off + 7) / 8;
+    const uint16_t* f = frames + base;
+    uint16_t* o = out + base;
+    for (int g = blockIdx.x * kThreads + threadIdx.x; g < groups; g += gridDim.x * kThreads) {
+      const int e0 = g * 8 - off;
+      const int a = e0 < 0 ? 0 : e0, b = e0 + 8 < HW ? e0 + 8 : HW;
+      int y = a / W, x = a - y * W;
+      if (wide && b - a == 8 && x + 8 <= W && put8<false>(f, y, x, 0, (y & 1) ? p : 0, H, W, 0u, fill, o + a)) continue;
+      for (int e = a; e < b; ++e) {
+        o[e] = put1<false>(f, y, x, 0, (y & 1) ? p : 0, H, W, 0u, fill);
+        if (++x == W) { x = 0; ++y; }
+      }
+    }
+  }
+}
+
 // ---- launchers.  name: the entry point, for the messages ---------------------------------------------------------------------------
 // the frame dimension of a grid (the kernels stride over the frames beyond it)
 inline unsigned frame_dim(int tc) { return (unsigned)(tc < 65535 ? tc : 65535); }
@@ -910,4 +1054,53 @@ extern "C" int dc_motion_pick_around(const long* wscores, const int* rows, int m
   DC_REQUIRE((((uintptr_t)wscores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL,
              "dc_motion_pick_around: misaligned buffer");
   return launch_pick("dc_motion_pick_around", wscores, rows, mult, tc, S, D, shifts, best, fine, (hipStream_t)stream);
+}
+
+// ---- bidirectional scan-phase correction ------------------------------------------------------------------------------------------
+namespace {
+
+template <int PMAX>
+int launch_bidi_scores(const void* frames, int is_unsigned, int tc, int H, int W, int P, unsigned long long* scores, hipStream_t stream) {
+  const int tilesX = dc_cdiv(W - 2 * P, kTileW), tilesY = dc_cdiv((H - 1) / 2, kBidiTH);
+  const dim3 grid((unsigned)(tilesX * tilesY), frame_dim(tc)), block(kThreads);
+  hipLaunchKernelGGL(bidi_scores_kernel<PMAX>, grid, block, bidi_lds(P), stream, (const uint16_t*)frames, is_unsigned ? 0u : 0x8000u, tc, H, W, P,
+                     scores, tilesX);
+  DC_CHECK_LAUNCH("dc_bidi_scores");
+  return DC_OK;
+}
+
+}  // namespace
+
+extern "C" int dc_bidi_scores(const void* frames, int is_unsigned, int tc, int H, int W, int P, long* scores, dc_stream_t stream) {
+  DC_REQUIRE(frames && scores, DC_EINVAL, "dc_bidi_scores: null pointer");
+  DC_REQUIRE(tc >= 0 && P >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_bidi_scores: negative or zero size (tc %d, P %d, H %d, W %d)", tc, P, H, W);
+  DC_REQUIRE(P <= DC_BIDI_MAX_OFFSET, DC_EUNSUP, "dc_bidi_scores: P = %d: the offset radius is limited to %d", P, DC_BIDI_MAX_OFFSET);
+  DC_REQUIRE((long)H * W <= (1L << 28), DC_EUNSUP, "dc_bidi_scores: image %d x %d: H * W is limited to 2^28", H, W);
+  DC_REQUIRE(H >= 3 && W > 2 * P, DC_EINVAL, "dc_bidi_scores: image %d x %d has no odd line between two even ones, or no interior at P = %d (H >= 3 and W > 2P)",
+             H, W, P);
+  DC_REQUIRE((((uintptr_t)frames) & 1) == 0 && (((uintptr_t)scores) & 7) == 0, DC_EINVAL, "dc_bidi_scores: misaligned buffer");
+  if (tc == 0) return DC_OK;
+  // the zero launch (the score kernel leaves its totals by atomics), then the instantiation for the radius
+  const long n = (long)tc * (2 * P + 1);
+  unsigned long long* sc = (unsigned long long*)scores;
+  const int blocks = (int)(dc_cdiv(n, kThreads) < kZeroBlocks ? dc_cdiv(n, kThreads) : kZeroBlocks);
+  hipLaunchKernelGGL(motion_zero_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, sc, n);
+  DC_CHECK_LAUNCH("dc_bidi_scores(zero)");
+  if (P <= 4) return launch_bidi_scores<4>(frames, is_unsigned, tc, H, W, P, sc, (hipStream_t)stream);
+  if (P <= 8) return launch_bidi_scores<8>(frames, is_unsigned, tc, H, W, P, sc, (hipStream_t)stream);
+  return launch_bidi_scores<16>(frames, is_unsigned, tc, H, W, P, sc, (hipStream_t)stream);
+}
+
+extern "C" int dc_bidi_apply(const void* frames, int tc, int p, int H, int W, int fill, void* out, dc_stream_t stream) {
+  DC_REQUIRE(frames && out, DC_EINVAL, "dc_bidi_apply: null pointer");
+  DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_bidi_apply: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE_IMAGE("dc_bidi_apply", H, W);
+  DC_REQUIRE_MOVE("dc_bidi_apply", frames, nullptr, out, tc, H, W, fill);
+  if (tc == 0) return DC_OK;
+  const int bx = dc_cdiv(dc_cdiv((long)H * W + 7, 8), kThreads);
+  const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), frame_dim(tc)), block(kThreads);
+  hipLaunchKernelGGL(bidi_apply_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)frames, tc, p, H, W, (unsigned)fill & 0xffffu,
+                     (uint16_t*)out, (int)dc_aligned16(out));
+  DC_CHECK_LAUNCH("dc_bidi_apply");
+  return DC_OK;
 }

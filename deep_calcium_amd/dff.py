@@ -324,11 +324,11 @@ class TraceBaseline(object):
 
 
 def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=None, offset=0, source='series/raw', device=None,
-                      chunk_frames=None, shifts=None, fine_shifts=None):
+                      chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
     """The (R, T) dF/F traces (or any other kind of KINDS) of `rois` over `source` of a dataset file.  neuropil: None, or
     (inner, outer, weight): every ROI is corrected by its ring neuropil_rois(rois, shape, inner, outer).  The recording is read
     ONCE, by a single RoiTraceExtractor whose ROI list is the ROIs followed by the non-empty rings; combine, baseline and scale
-    then run on the sums where they lie.  shifts / fine_shifts: as for extract_traces_device."""
+    then run on the sums where they lie.  shifts / fine_shifts / bidi: as for extract_traces_device."""
     from .series import _open_series
     from .traces import RoiTraceExtractor
     _check_kind(kind)
@@ -363,7 +363,7 @@ def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=N
                     every.append(ring)
         combine_coefficients(areas, ring_areas, weight, offset)          # An * A over the limit: before the pass, not after it
         ext = RoiTraceExtractor(shape, T, frames.dtype, every, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                fine_shifts=fine_shifts)
+                                fine_shifts=fine_shifts, bidi=bidi)
         for a in range(0, T, ext.chunk_frames):
             ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
         tb = TraceBaseline.from_stacked(ext.sums_device(), areas, ring_rows, ring_areas, window, percentile=percentile, offset=offset,

@@ -125,9 +125,9 @@ class RoiFootprints(object):
     """Owns the device state of one recording's footprint maps and, through a RoiTraceExtractor of its own, of its traces; feed()
     the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, rois, halo=2, device=None, chunk_frames=None, shifts=None, fine_shifts=None):
+    def __init__(self, shape, n_frames, dtype, rois, halo=2, device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
         """halo: the Chebyshev radius, in [0, 16], by which every ROI's support reaches beyond its own pixels.  Everything else: as
-        for RoiTraceExtractor (shifts / fine_shifts move or interpolate each chunk before BOTH kernels read it)."""
+        for RoiTraceExtractor (bidi, then shifts / fine_shifts move or interpolate each chunk before BOTH kernels read it)."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         halo = _check_halo(halo)
@@ -145,7 +145,7 @@ class RoiFootprints(object):
         self.halo, self.n_entries = halo, int(self._bounds[-1])
         own = [np.stack([p.astype(np.int64) // shape[1], p.astype(np.int64) % shape[1]], 1) for p in pixels]
         self._ext = ext = RoiTraceExtractor(shape, n_frames, dtype, own, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                            fine_shifts=fine_shifts)
+                                            fine_shifts=fine_shifts, bidi=bidi)
         ext._stage_tag = 'footprints_stage'          # slots of its own: an extractor alive at the same time keeps its own
         ext._after_chunk = self._accumulate
         self.shape, self.n_frames, self.dtype, self.n_rois = shape, n_frames, ext.dtype, ext.n_rois
@@ -226,9 +226,10 @@ class RoiFootprints(object):
         return np.array([c[i].astype(np.float64).mean() for c, i in zip(corr, self._inside)], np.float64)
 
 
-def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None):
+def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None,
+                          bidi=0):
     """-> (corr, coords, inside) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk:
-    the recording is read once.  shifts / fine_shifts: as for extract_traces_device."""
+    the recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device."""
     from .series import _open_series
     _check_halo(halo)
     if shifts is not None and fine_shifts is not None:
@@ -239,7 +240,7 @@ def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         fp = RoiFootprints(tuple(frames.shape[1:]), T, frames.dtype, rois, halo=halo, device=device, chunk_frames=chunk_frames,
-                           shifts=shifts, fine_shifts=fine_shifts)
+                           shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
         for a in range(0, T, fp.chunk_frames):
             fp.feed(np.asarray(frames[a:a + fp.chunk_frames]))
         out = fp.result('corr'), fp.support(), fp.inside()

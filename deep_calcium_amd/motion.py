@@ -77,6 +77,33 @@ refined within the window table; a pick on the window's border is not refined (q
     shifts, coarse = mc.shifts(), mc.coarse_shifts()
     shifts, template = estimate_shifts_device('dataset.hdf5', max_shift=48, coarse=4)
 
+Bidirectional scan-phase correction (bidi=p): a resonant scanner draws even lines left to right and odd lines right to left, and a
+phase error between the sweeps displaces all odd lines horizontally by a constant few pixels.  That offset is found once per
+recording by an exhaustive search within +-max_offset (dc_bidi_scores, summed over frames, picked on the host) and undone as a
+pure move of the odd lines (dc_bidi_apply) BEFORE anything else reads a frame -- the template is built from corrected lines:
+
+    what          dtype            exactness
+    scores        int64            exact: (t, 2P+1), index p + P: the sum over odd y in [1, H-1), x in [P, W-P) of
+                                   (2 f[y, x+p] - f[y-1, x] - f[y+1, x])^2
+    totals        Python ints      exact: the scores summed over the frames fed (a sum over frames need not fit 64 bits)
+    offset        int              exact: argmin of (total, p^2, p) -- 0 wins every tie it is part of
+    corrected     the frames'      exact: out[y, x] = frame[y, x + p] for odd y (`fill` outside the row), even rows copied
+
+Sign convention: odd lines recorded as frame[y, x] = scene[y, x + b] are found as p = -b.
+
+    est = BidiEstimator((H, W), np.int16, max_offset=8)
+    for chunk in chunks: est.feed(chunk)
+    p = est.offset()
+    p, totals = estimate_bidi_device('dataset.hdf5')                          # the first 200 frames
+    mc = MotionCorrector((H, W), T, np.int16, template, max_shift=8, bidi=p)   # feed() returns frames with both corrections
+    shifts, template = estimate_shifts_device('dataset.hdf5', bidi=p)
+    img = summarize_series_device('dataset.hdf5', kind='corr', shifts=shifts, bidi=p)
+
+With sub-pixel shifts the columns outside valid_rectangle(..., bidi=p) hold blends of `fill`, as they already do at the frame's edge.
+The move leaves |p| columns of `fill` at one edge of the odd lines, which the shift search counts as a mismatch at every shift that
+reaches them: choose max_shift at least the largest expected shift plus |p|.
+Whole-pixel offsets, one per recording, odd lines only: a sub-pixel or per-frame offset is not built.
+
 Scope: shifts found by exhaustive whole-pixel search, max_shift <= 16 -- or by the two-level wide search, max_shift <= 128,
 rigid only --, max_dev <= 8, at most 32 x 32 blocks, refined to 1/16 pixel by a parabola fit, bilinear interpolation.  Template
 building with sub-pixel or block shifts, temporal smoothing of the shifts, FFT methods, other interpolation kernels,
@@ -86,7 +113,7 @@ Importing this module needs neither torch nor the GPU; constructing a MotionCorr
 """
 import numpy as np
 
-from .series import _CHUNK_BYTES, _TwoSlotStage, _check_device_frames, _frame_dtype, _open_series
+from .series import _CHUNK_BYTES, MAX_BIDI, _TwoSlotStage, _check_bidi, _check_device_frames, _frame_dtype, _open_series
 from .traces import _check_shape
 
 MAX_SHIFT = 16                        # DC_MOTION_MAX_SHIFT
@@ -132,6 +159,32 @@ def _check_coarse(coarse, max_shift, shape=None, blocks=None):
             raise ValueError('coarse = %d leaves no interior in the binned %d x %d frame at the coarse radius %d'
                              % (c, H // c, W // c, Sc))
     return c, S
+
+
+def _check_bidi_radius(max_offset, shape=None):
+    """max_offset of the scan-phase search -> P in [0, MAX_BIDI]; the frame must keep an odd line between two even ones and an
+    interior column: H >= 3 and W > 2P."""
+    if isinstance(max_offset, bool) or not isinstance(max_offset, (int, np.integer)):
+        raise ValueError('max_offset must be an integer in [0, %d], not %r' % (MAX_BIDI, max_offset))
+    P = int(max_offset)
+    if not 0 <= P <= MAX_BIDI:
+        raise ValueError('max_offset must be in [0, %d], not %d' % (MAX_BIDI, P))
+    if shape is not None:
+        if shape[0] < 3:
+            raise ValueError('a %d x %d frame has no odd line between two even ones: H >= 3' % (shape[0], shape[1]))
+        if shape[1] <= 2 * P:
+            raise ValueError('max_offset = %d leaves no interior column in a %d x %d frame: W > 2 * max_offset' % (P, shape[0], shape[1]))
+    return P
+
+
+def pick_bidi(totals):
+    """The offset of the 2P+1 totals (index p + P; any integers, Python ints beyond 64 bits included): the p that minimises
+    (total, p^2, p) -- 0 wins every tie it is part of, then the smaller |p|, then the negative one.  Host only."""
+    totals = [int(v) for v in totals]
+    if len(totals) < 1 or len(totals) % 2 != 1:
+        raise ValueError('totals must hold 2P+1 values, not %d' % len(totals))
+    P = len(totals) // 2
+    return min(range(-P, P + 1), key=lambda p: (totals[p + P], p * p, p))
 
 
 def block_edges(n, B):
@@ -188,19 +241,28 @@ def _check_template(template, shape, dtype):
     return np.ascontiguousarray(template)
 
 
-def valid_rectangle(shifts, shape, fine=False):
+def valid_rectangle(shifts, shape, fine=False, bidi=0):
     """((y0, y1), (x0, x1)): the rectangle every frame corrected by `shifts` (n, 2) covers with its own pixels,
     y in [max(0, -min dy), H - max(0, max dy)), likewise x.  Block shifts (n, By, Bx, 2) are taken one by one: the shift field
     never leaves their range, so the rectangle bounds the warped frames too.  fine=True: `shifts` are fine shifts (sixteenths of a
     pixel) and an interpolated pixel needs every tap it uses: y0 = max(0, -floor(min sy / 16)), y1 = H - max(0, ceil(max sy / 16)),
-    likewise x.  Host only."""
+    likewise x.  bidi=p: the odd lines were moved by p first (dc_bidi_apply), and an odd line is valid only where both moves stay
+    inside: the column limits are taken over the union of the x shifts and the x shifts plus p (plus 16 p with fine), by the same
+    formulas; shifts=None: no registration, the columns are [max(0, -p), W - max(0, p)).  With sub-pixel shifts the columns
+    outside this rectangle hold blends of `fill`, as they already do at the frame's edge.  Host only."""
     H, W = shape
     if not isinstance(fine, (bool, np.bool_)):
         raise ValueError('fine must be True or False, not %r' % (fine,))
+    p = _check_bidi(bidi, shape)
+    if shifts is None:
+        return (0, H), (max(0, -p), W - max(0, p))
     s = np.asarray(shifts).reshape(-1, 2).astype(np.int64)
     if len(s) == 0:
-        return (0, H), (0, W)
+        return (0, H), (max(0, -p), W - max(0, p))
     lo, hi = s.min(axis=0), s.max(axis=0)
+    if p:
+        k = p * SUBPIXEL if fine else p
+        lo[1], hi[1] = min(lo[1], lo[1] + k), max(hi[1], hi[1] + k)
     if fine:
         lo, hi = lo // SUBPIXEL, -((-hi) // SUBPIXEL)        # floor and ceiling for either sign
     return ((max(0, -int(lo[0])), H - max(0, int(hi[0]))), (max(0, -int(lo[1])), W - max(0, int(hi[1]))))
@@ -218,7 +280,7 @@ class MotionCorrector(object):
     """Owns the device state of one recording's registration; feed() the frames in order, in chunks of any size."""
 
     def __init__(self, shape, n_frames, dtype, template, max_shift=8, fill=0, device=None, chunk_frames=None, blocks=None,
-                 max_dev=3, subpixel=False, coarse=None):
+                 max_dev=3, subpixel=False, coarse=None, bidi=0):
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         H, W = shape
@@ -237,6 +299,7 @@ class MotionCorrector(object):
         if blocks is not None:
             By, Bx, self.max_dev = _check_blocks(blocks, max_dev, shape, self.max_shift)
             self.blocks = (By, Bx)
+        self.bidi = _check_bidi(bidi, shape)
         template = _check_template(template, shape, self.dtype)
         if chunk_frames is None:
             chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
@@ -283,6 +346,8 @@ class MotionCorrector(object):
             self._bscores = torch.empty((self.chunk_frames, By, Bx, nb, nb), dtype=torch.int64, device=dev)
         if self.subpixel:                  # the fine shifts (sixteenths) beside the whole-pixel picks they refine
             self._fine = torch.zeros((n_frames, 2) if self.blocks is None else (n_frames,) + self.blocks + (2,), dtype=torch.int32, device=dev)
+        if self.bidi:                      # one chunk of frames whose odd lines have been moved: what everything below reads
+            self._bidi_scratch = torch.empty((self.chunk_frames, H, W), dtype=torch.int16, device=dev)
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
@@ -293,6 +358,9 @@ class MotionCorrector(object):
         L, S = self.L, self.max_shift
         uns = int(self.dtype == np.dtype(np.uint16))
         rows = self._shifts.data_ptr() + 8 * self.fed
+        if self.bidi:                      # the scan-phase offset first: scores, picks and movers read the corrected lines
+            L.dc_bidi_apply(fp, tc, self.bidi, H, W, self.fill, self._bidi_scratch.data_ptr(), st)
+            fp = self._bidi_scratch.data_ptr()
         if self.coarse is not None:
             # the wide search: the exhaustive pick on the binned frames, then the full-resolution window around c times it
             c, (Hc, Wc), Sc = self.coarse, self._cshape, self._cradius
@@ -337,7 +405,8 @@ class MotionCorrector(object):
         and returns None.  With blocks: the frames are warped by the shift field, and their block shifts land in rows
         [fed, fed + t) of block_shifts_device().  With subpixel=True every pick is refined to a sixteenth of a pixel (rows
         [fed, fed + t) of fine_shifts_device()) and the frames are interpolated bilinearly at the fine shifts (or the fine
-        shift field), `fill` where a tap that is used lies outside the frame."""
+        shift field), `fill` where a tap that is used lies outside the frame.  With bidi=p every piece first has its odd lines
+        moved by p (dc_bidi_apply, `fill` where x + p leaves the row): the returned frames carry both corrections."""
         on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
         if not on_device and not isinstance(frames, np.ndarray):
             raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
@@ -445,8 +514,8 @@ class MotionCorrector(object):
     def valid(self):
         """((y0, y1), (x0, x1)): the rectangle every frame corrected so far covers with its own pixels."""
         if self.subpixel:
-            return valid_rectangle(self.fine_shifts(), self.shape, fine=True)
-        return valid_rectangle(self.shifts() if self.blocks is None else self.block_shifts(), self.shape)
+            return valid_rectangle(self.fine_shifts(), self.shape, fine=True, bidi=self.bidi)
+        return valid_rectangle(self.shifts() if self.blocks is None else self.block_shifts(), self.shape, bidi=self.bidi)
 
 
 def _rounded_mean(torch, total, n):
@@ -459,10 +528,11 @@ def _widen(torch, chunk, unsigned):
     return v & 0xffff if unsigned else v
 
 
-def make_template(frames, max_shift=8, iterations=1, device=None, coarse=None):
+def make_template(frames, max_shift=8, iterations=1, device=None, coarse=None, bidi=0):
     """A template for `frames` (N, H, W) numpy int16 / uint16: the rounded mean floor((2 * sum + N) / (2 N)) of the frames, then
     `iterations` times: register the frames to the template (fill 0) and take the rounded mean of the corrected frames.
-    coarse=c: the registration is the wide search (max_shift in [c, 16 c]).  Returns (H, W) of the frames' dtype."""
+    coarse=c: the registration is the wide search (max_shift in [c, 16 c]).  bidi=p: the odd lines of every frame are moved by p
+    first (dc_bidi_apply, fill 0), for the first mean as for the registration.  Returns (H, W) of the frames' dtype."""
     if not isinstance(frames, np.ndarray) or frames.ndim != 3 or frames.shape[0] < 1:
         raise ValueError('frames must be a (N, H, W) numpy array with N >= 1, not %s' %
                          (type(frames).__name__ if not isinstance(frames, np.ndarray) else repr(tuple(frames.shape))))
@@ -471,6 +541,7 @@ def make_template(frames, max_shift=8, iterations=1, device=None, coarse=None):
     S = _check_max_shift(max_shift, shape) if coarse is None else _check_coarse(coarse, max_shift, shape)[1]
     if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
         raise ValueError('iterations must be an integer >= 0, not %r' % (iterations,))
+    bidi = _check_bidi(bidi, shape)
     import torch
     if not torch.cuda.is_available():
         from ._lib import DcunetError
@@ -479,14 +550,21 @@ def make_template(frames, max_shift=8, iterations=1, device=None, coarse=None):
     N, (H, W) = int(frames.shape[0]), shape
     uns = dtype == np.dtype(np.uint16)
     step = max(1, _CHUNK_BYTES // (2 * H * W))
+    if bidi:
+        from ._lib import lib
+        L = lib()
     with torch.cuda.device(dev):
         total = torch.zeros((H, W), dtype=torch.int64, device=dev)
         for a in range(0, N, step):
             chunk = torch.from_numpy(np.array(frames[a:a + step]).view(np.int16)).to(dev)      # a copy: a file mapping is read-only
+            if bidi:                          # the first mean is one of corrected lines too
+                moved = torch.empty_like(chunk)
+                L.dc_bidi_apply(chunk.data_ptr(), int(chunk.shape[0]), bidi, H, W, 0, moved.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                chunk = moved
             total += _widen(torch, chunk, uns).sum(0)
         tmpl = _rounded_mean(torch, total, N).to(torch.int16).cpu().numpy().view(dtype)
         for _ in range(int(iterations)):
-            mc = MotionCorrector(shape, N, dtype, tmpl, max_shift=S, fill=0, device=dev, chunk_frames=step, coarse=coarse)
+            mc = MotionCorrector(shape, N, dtype, tmpl, max_shift=S, fill=0, device=dev, chunk_frames=step, coarse=coarse, bidi=bidi)
             total.zero_()
             for a in range(0, N, step):
                 total += _widen(torch, mc.feed(np.ascontiguousarray(frames[a:a + step])), uns).sum(0)
@@ -495,7 +573,7 @@ def make_template(frames, max_shift=8, iterations=1, device=None, coarse=None):
 
 
 def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=200, source='series/raw', device=None,
-                           chunk_frames=None, blocks=None, max_dev=3, subpixel=False, coarse=None):
+                           chunk_frames=None, blocks=None, max_dev=3, subpixel=False, coarse=None, bidi=0):
     """(shifts, template): the (T, 2) int32 (dy, dx) of every frame of `source` of a dataset file against `template` -- built
     by make_template (one iteration) from the first min(T, template_frames) frames when none is given.  The recording is
     streamed once, memory-mapped or sliced, never read whole; nothing is corrected here: pass `shifts` to
@@ -503,7 +581,10 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
     +-max_dev of each frame's rigid shift instead (the template is still built rigidly); `shifts=` takes them as they are.
     subpixel=True: the fine shifts in sixteenths of a pixel instead, in the same shapes (the template is still built from
     whole-pixel corrections); `fine_shifts=` takes them as they are.  coarse=c: every search, the template's included, is the
-    wide search (max_shift in [c, 16 c], rigid only); the shifts may then exceed 16 pixels, which `shifts=` takes as well."""
+    wide search (max_shift in [c, 16 c], rigid only); the shifts may then exceed 16 pixels, which `shifts=` takes as well.
+    bidi=p: the odd lines of every frame are moved by p first, for the template as for the search (estimate_bidi_device finds p);
+    pass the same bidi= to whatever takes the shifts."""
+    _check_bidi(bidi)
     if coarse is None:
         _check_max_shift(max_shift)
     else:
@@ -520,13 +601,14 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
         T = int(frames.shape[0])
         shape = tuple(int(v) for v in frames.shape[1:])
         S = _check_max_shift(max_shift, shape) if coarse is None else _check_coarse(coarse, max_shift, shape, blocks)[1]
+        bidi = _check_bidi(bidi, shape)
         if template is None:
             template = make_template(np.asarray(frames[:min(T, int(template_frames))]), max_shift=S, iterations=1, device=device,
-                                     coarse=coarse)
+                                     coarse=coarse, bidi=bidi)
         if blocks is not None:
             _check_blocks(blocks, max_dev, shape, S)
         mc = MotionCorrector(shape, T, frames.dtype, template, max_shift=S, device=device, chunk_frames=chunk_frames, blocks=blocks,
-                             max_dev=max_dev, subpixel=subpixel, coarse=coarse)
+                             max_dev=max_dev, subpixel=subpixel, coarse=coarse, bidi=bidi)
         for a in range(0, T, mc.chunk_frames):
             mc.feed(np.asarray(frames[a:a + mc.chunk_frames]), correct=False)
         out = mc.fine_shifts() if subpixel else (mc.shifts() if blocks is None else mc.block_shifts())
@@ -534,3 +616,119 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
         frames = None                        # a view of the file mapping: released before the file is closed
         close()
     return out, template
+
+
+class BidiEstimator(object):
+    """Owns the device state of one recording's scan-phase search: feed() frames in chunks of any size, then offset().  Every
+    frame gets its own 2P+1 exact scores (dc_bidi_scores); the offset is picked on the host from their sums over the frames."""
+
+    def __init__(self, shape, dtype, max_offset=8, device=None, chunk_frames=None):
+        # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
+        shape = _check_shape(shape)
+        H, W = shape
+        self.dtype = _frame_dtype(dtype)
+        self.max_offset = _check_bidi_radius(max_offset, shape)
+        if H * W > (1 << 28):
+            raise ValueError('shape must be (H, W) with H * W <= 2**28 for the scan-phase search, not %r' % (shape,))
+        if chunk_frames is None:
+            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 1:
+            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
+        self.shape, self.chunk_frames = shape, chunk_frames
+        self.fed = 0
+        self._stage = None
+        self._tables = []                  # one (t, 2P+1) int64 tensor per piece, in order
+
+        import torch
+        from . import net
+        from ._lib import lib
+        self._torch, self._net = torch, net
+        self.L = lib()
+        if not torch.cuda.is_available():
+            from ._lib import DcunetError
+            raise DcunetError('BidiEstimator needs a GPU (there is no CPU fallback)')
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+
+    def feed(self, frames):
+        """The next frames, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype (staged through two pinned
+        slots), or a contiguous (t, H, W) torch.int16 tensor on the estimator's device holding the recording's bits (read in
+        place).  Their scores become rows [fed, fed + t) of scores()."""
+        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
+        if not on_device and not isinstance(frames, np.ndarray):
+            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
+        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
+            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
+        if on_device:
+            _check_device_frames(self._torch, frames, self.dtype, self.device, 'estimator')
+        elif frames.dtype != self.dtype:
+            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
+        t = int(frames.shape[0])
+        if t < 1:
+            raise ValueError('frames must hold at least one frame')
+        torch = self._torch
+        H, W = self.shape
+        P, uns = self.max_offset, int(self.dtype == np.dtype(np.uint16))
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream(self.device)
+            st = main.cuda_stream
+
+            def piece(fp, tc):
+                table = torch.empty((tc, 2 * P + 1), dtype=torch.int64, device=self.device)      # fully written by the launch
+                self.L.dc_bidi_scores(fp, uns, tc, H, W, P, table.data_ptr(), st)
+                self._tables.append(table)
+                self.fed += tc
+            if on_device:
+                for a in range(0, t, self.chunk_frames):
+                    piece(frames.data_ptr() + 2 * a * H * W, min(self.chunk_frames, t - a))
+                frames.record_stream(main)
+            else:
+                if self._stage is None:          # names of its own: a corrector or summarizer alive at the same time keeps its slots
+                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'bidi_stage', (self.chunk_frames, H, W))
+                self._stage.run(frames, main, piece)
+        return self
+
+    def scores(self):
+        """(fed, 2P+1) int64 numpy array: the scores of every frame fed so far, index p + P."""
+        if not self._tables:
+            return np.zeros((0, 2 * self.max_offset + 1), np.int64)
+        return self._torch.cat(self._tables).cpu().numpy()
+
+    def totals(self):
+        """The 2P+1 sums of the scores over the frames fed, as Python ints (a sum over frames need not fit 64 bits)."""
+        sc = self.scores()
+        return [sum(int(v) for v in sc[:, k]) for k in range(sc.shape[1])]
+
+    def offset(self):
+        """The offset that minimises (total, p^2, p): pass it as bidi=."""
+        if self.fed < 1:
+            raise ValueError('offset() before any frame was fed')
+        return pick_bidi(self.totals())
+
+
+def estimate_bidi_device(dspath, max_offset=8, frames=200, source='series/raw', device=None):
+    """(offset, totals): the scan-phase offset of `source` of a dataset file, searched within +-max_offset over its first
+    min(T, frames) frames (frames=None: all of them), and the 2P+1 totals it was picked from (Python ints, index p + P).  The
+    recording is memory-mapped or sliced, never read whole.  Pass the offset as bidi= to MotionCorrector, estimate_shifts_device
+    and every reader of the recording."""
+    _check_bidi_radius(max_offset)
+    if frames is not None and (isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 1):
+        raise ValueError('frames must be None or an integer >= 1, not %r' % (frames,))
+    series, close = _open_series(dspath, source)
+    try:
+        if len(series.shape) != 3:
+            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(series.shape)))
+        T = int(series.shape[0])
+        n = T if frames is None else min(T, int(frames))
+        shape = tuple(int(v) for v in series.shape[1:])
+        est = BidiEstimator(shape, series.dtype, max_offset=max_offset, device=device,
+                            chunk_frames=min(n, max(1, _CHUNK_BYTES // (2 * max(1, shape[0] * shape[1])))))
+        for a in range(0, n, est.chunk_frames):
+            est.feed(np.asarray(series[a:min(n, a + est.chunk_frames)]))
+        totals = est.totals()
+    finally:
+        series = None                        # a view of the file mapping: released before the file is closed
+        close()
+    return pick_bidi(totals), totals

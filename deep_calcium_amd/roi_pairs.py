@@ -87,9 +87,9 @@ class RoiPairCorr(object):
     """Owns the device state of one recording's pixel-pair moments and, through a RoiTraceExtractor of its own, of its traces;
     feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None, fine_shifts=None):
+    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
         """rois: every form rois_to_csr takes; each ROI at most MAX_AREA pixels, all together at most MAX_STATE matrix entries
-        (ValueError naming the ROI).  Everything else: as for RoiTraceExtractor (shifts / fine_shifts move or interpolate each
+        (ValueError naming the ROI).  Everything else: as for RoiTraceExtractor (bidi, then shifts / fine_shifts move or interpolate each
         chunk before BOTH kernels read it)."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
@@ -104,7 +104,7 @@ class RoiPairCorr(object):
         self._roi_off_host, self._goff_host = roi_off.astype(np.int64), goff
         self.n_pixels, self.n_state, self.n_tiles = int(roi_off[-1]), G, len(tiles)
         self._ext = ext = RoiTraceExtractor(shape, n_frames, dtype, self._pixels, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                            fine_shifts=fine_shifts)
+                                            fine_shifts=fine_shifts, bidi=bidi)
         ext._stage_tag = 'roi_pairs_stage'           # slots of its own: an extractor alive at the same time keeps its own
         ext._after_chunk = self._accumulate
         self.shape, self.n_frames, self.dtype, self.n_rois = shape, n_frames, ext.dtype, ext.n_rois
@@ -263,9 +263,9 @@ def split_rois(pixels, corr, shape, min_gap=0.1, min_area=8, iterations=16):
     return new_rois, origin, gaps
 
 
-def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None):
+def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
     """-> (corr, pixels) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
-    recording is read once.  shifts / fine_shifts: as for extract_traces_device."""
+    recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device."""
     from .series import _open_series
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
@@ -275,7 +275,7 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         pc = RoiPairCorr(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                         fine_shifts=fine_shifts)
+                         fine_shifts=fine_shifts, bidi=bidi)
         for a in range(0, T, pc.chunk_frames):
             pc.feed(np.asarray(frames[a:a + pc.chunk_frames]))
         out = pc.result('corr'), pc.pixels()
@@ -286,10 +286,10 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
 
 
 def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, source='series/raw', device=None, chunk_frames=None,
-                      shifts=None, fine_shifts=None):
+                      shifts=None, fine_shifts=None, bidi=0):
     """-> (new_rois, origin, gaps) of split_rois for `rois` over `source` of a dataset file, in one pass over the recording.  ROIs
     of more than MAX_AREA or fewer than 2 * min_area pixels are not sent to the device and come back unchanged (gap NaN); when
-    no ROI is left the recording is not read at all."""
+    no ROI is left the recording is not read at all.  shifts / fine_shifts / bidi: as for extract_traces_device."""
     from .series import _open_series
     min_gap, min_area, iterations = _check_split_args(min_gap, min_area, iterations)
     if shifts is not None and fine_shifts is not None:
@@ -308,7 +308,7 @@ def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, sour
     corr = [None] * len(pixels)
     if sent:
         got, _ = roi_pair_corr_device(dspath, [pixels[r] for r in sent], source=source, device=device, chunk_frames=chunk_frames,
-                                      shifts=shifts, fine_shifts=fine_shifts)
+                                      shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
         for r, c in zip(sent, got):
             corr[r] = c
     return split_rois(pixels, corr, shape, min_gap=min_gap, min_area=min_area, iterations=iterations)

@@ -89,6 +89,23 @@ def _check_known_shifts(shifts, fine_shifts, n_frames, frame_shape):
     return _check_shifts(shifts, n_frames, frame_shape), False
 
 
+MAX_BIDI = 16                         # DC_BIDI_MAX_OFFSET: the largest radius of the scan-phase search
+
+
+def _check_bidi(bidi, shape=None):
+    """The `bidi=` keyword of MotionCorrector and every reader of known shifts: the whole-pixel offset the odd lines are moved by
+    before anything else reads a frame (dc_bidi_apply), 0 for none.  An integer that keeps a column of the odd lines, |bidi| < W.
+    Host only."""
+    if isinstance(bidi, bool) or not isinstance(bidi, (int, np.integer)):
+        raise ValueError('bidi must be an integer (the whole-pixel offset of the odd lines, 0 for none), not %r' % (bidi,))
+    p = int(bidi)
+    if not -2 ** 31 <= p < 2 ** 31:
+        raise ValueError('bidi must fit int32, not %d' % p)
+    if shape is not None and abs(p) >= shape[1]:
+        raise ValueError('bidi = %d leaves no column of the odd lines of a %d x %d frame: |bidi| < W' % (p, shape[0], shape[1]))
+    return p
+
+
 def _check_device_frames(torch, frames, dtype, device, owner):
     """A feed() argument that is a tensor: the recording's bits as a contiguous torch.int16 tensor on `device`."""
     if frames.dtype != torch.int16:
@@ -103,34 +120,45 @@ class _ShiftedChunks(object):
     """Known shifts applied on the way in (fill 0): the int32 (n_frames, 2) table on the device (dc_motion_apply) or the
     (n_frames, By, Bx, 2) block shifts (dc_motion_warp) and one scratch chunk the accumulate kernels read instead of the staged
     frames.  Frame `fed + i` of the recording gets row `fed + i`.  fine: the table holds fine shifts (sixteenths of a pixel), the
-    frames are interpolated (dc_motion_apply_sub, dc_motion_warp_sub: they are told the signedness)."""
+    frames are interpolated (dc_motion_apply_sub, dc_motion_warp_sub: they are told the signedness).  bidi != 0: the odd lines
+    are moved by it first (dc_bidi_apply, into a scratch chunk of its own); with shifts=None that is the only move."""
 
-    def __init__(self, torch, L, device, shifts, shape, fine=False, unsigned=0):
-        self._L, self.shape, self.fine, self._uns = L, shape, fine, int(unsigned)
-        if isinstance(shifts, np.ndarray):
-            shifts = torch.from_numpy(shifts)
-        self.shifts = shifts.to(device=device, dtype=torch.int32).contiguous()
-        self.blocks = tuple(int(v) for v in self.shifts.shape[1:3]) if self.shifts.dim() == 4 else None
+    def __init__(self, torch, L, device, shifts, shape, fine=False, unsigned=0, bidi=0):
+        self._L, self.shape, self.fine, self._uns, self.bidi = L, shape, fine, int(unsigned), int(bidi)
+        self.shifts, self.blocks = None, None
+        if shifts is not None:
+            if isinstance(shifts, np.ndarray):
+                shifts = torch.from_numpy(shifts)
+            self.shifts = shifts.to(device=device, dtype=torch.int32).contiguous()
+            self.blocks = tuple(int(v) for v in self.shifts.shape[1:3]) if self.shifts.dim() == 4 else None
         self.scratch = torch.empty(shape, dtype=torch.int16, device=device)
+        self._lines = torch.empty(shape, dtype=torch.int16, device=device) if self.bidi and self.shifts is not None else None
 
     def run(self, fp, tc, fed, st, launch):
         """launch(pointer to corrected frames, count, first frame) for the tc frames at fp, a scratch chunk at a time."""
         C, H, W = self.shape
         for a in range(0, tc, C):
             n = min(C, tc - a)
-            if self.fine and self.blocks is None:
-                self._L.dc_motion_apply_sub(fp + 2 * a * H * W, self._uns, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
+            src = fp + 2 * a * H * W
+            if self.bidi:
+                dst = self.scratch if self.shifts is None else self._lines
+                self._L.dc_bidi_apply(src, n, self.bidi, H, W, 0, dst.data_ptr(), st)
+                src = dst.data_ptr()
+            if self.shifts is None:
+                pass
+            elif self.fine and self.blocks is None:
+                self._L.dc_motion_apply_sub(src, self._uns, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
                                             self.scratch.data_ptr(), st)
             elif self.fine:
                 By, Bx = self.blocks
-                self._L.dc_motion_warp_sub(fp + 2 * a * H * W, self._uns, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
+                self._L.dc_motion_warp_sub(src, self._uns, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
                                            self.scratch.data_ptr(), st)
             elif self.blocks is None:
-                self._L.dc_motion_apply(fp + 2 * a * H * W, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
+                self._L.dc_motion_apply(src, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
                                         self.scratch.data_ptr(), st)
             else:
                 By, Bx = self.blocks
-                self._L.dc_motion_warp(fp + 2 * a * H * W, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
+                self._L.dc_motion_warp(src, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
                                        self.scratch.data_ptr(), st)
             launch(self.scratch.data_ptr(), n, fed + a)
 
@@ -178,12 +206,14 @@ class _TwoSlotStage(object):
 class SeriesSummarizer(object):
     """Owns the device state of one recording's summaries; feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None, fine_shifts=None):
+    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None, fine_shifts=None, bidi=0):
         """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
         MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before it is summarised.  Piecewise-rigid
         (n_frames, By, Bx, 2) block shifts (MotionCorrector.block_shifts_device()) are taken too: dc_motion_warp moves the chunk.
         fine_shifts: instead of shifts, the same shapes in sixteenths of a pixel (MotionCorrector.fine_shifts_device()): each
-        chunk is interpolated by dc_motion_apply_sub / dc_motion_warp_sub (fill 0)."""
+        chunk is interpolated by dc_motion_apply_sub / dc_motion_warp_sub (fill 0).
+        bidi: the whole-pixel offset of the odd lines (motion.estimate_bidi_device), undone by dc_bidi_apply (fill 0) before the
+        shift move; with no shifts it is the only move."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         try:
             shape = tuple(int(v) for v in shape)
@@ -207,6 +237,7 @@ class SeriesSummarizer(object):
         if chunk_frames < 1:
             raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
         shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
+        bidi = _check_bidi(bidi, shape)
         self.shape, self.n_frames, self.kinds = shape, n_frames, kinds
         self.chunk_frames = min(chunk_frames, n_frames)
         self.fed = 0
@@ -234,8 +265,8 @@ class SeriesSummarizer(object):
         self.max16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None
         self.xy = torch.empty((4, n), dtype=torch.int64, device=dev) if self._xy else None
         self._stage = _TwoSlotStage(torch, net, dev, 'series_stage', (self.chunk_frames, H, W))
-        self._shifted = None if shifts is None else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
-                                                                   self.dtype == np.dtype(np.uint16))
+        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
+                                                                                self.dtype == np.dtype(np.uint16), bidi)
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
@@ -380,12 +411,14 @@ def _open_series(dspath, source):
 
 
 def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
-                            shifts=None, fine_shifts=None):
+                            shifts=None, fine_shifts=None, bidi=0):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
     float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame, or
     its (T, By, Bx, 2) block shifts (motion.estimate_shifts_device), applied on the device on the way in.  fine_shifts: instead,
-    either shape in sixteenths of a pixel (estimate_shifts_device(subpixel=True)): the frames are interpolated on the way in."""
+    either shape in sixteenths of a pixel (estimate_shifts_device(subpixel=True)): the frames are interpolated on the way in.
+    bidi: the offset of the odd lines (motion.estimate_bidi_device), undone on the way in before the shifts."""
     _check_kind(kind)
+    _check_bidi(bidi)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     frames, close = _open_series(dspath, source)
@@ -394,7 +427,7 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
-                                kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts)
+                                kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
         for a in range(0, T, summ.chunk_frames):
             summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
         out = summ.result(kind, standardize=standardize)

@@ -24,7 +24,7 @@ Importing this module needs neither torch nor the GPU; constructing a RoiTraceEx
 """
 import numpy as np
 
-from .series import (_CHUNK_BYTES, _ShiftedChunks, _TwoSlotStage, _check_device_frames, _check_known_shifts, _frame_dtype,
+from .series import (_CHUNK_BYTES, _ShiftedChunks, _TwoSlotStage, _check_bidi, _check_device_frames, _check_known_shifts, _frame_dtype,
                      _open_series)
 
 KINDS = ('sum', 'mean', 'zscore')
@@ -105,12 +105,14 @@ def rois_to_csr(rois, shape):
 class RoiTraceExtractor(object):
     """Owns the device state of one recording's ROI traces; feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None, fine_shifts=None):
+    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
         """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
         MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before its ROIs are summed.  Piecewise-rigid
         (n_frames, By, Bx, 2) block shifts (MotionCorrector.block_shifts_device()) are taken too: dc_motion_warp moves the chunk.
         fine_shifts: instead of shifts, the same shapes in sixteenths of a pixel (MotionCorrector.fine_shifts_device()): each
-        chunk is interpolated by dc_motion_apply_sub / dc_motion_warp_sub (fill 0)."""
+        chunk is interpolated by dc_motion_apply_sub / dc_motion_warp_sub (fill 0).
+        bidi: the whole-pixel offset of the odd lines (motion.estimate_bidi_device), undone by dc_bidi_apply (fill 0) before the
+        shift move; with no shifts it is the only move."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         H, W = shape
@@ -125,6 +127,7 @@ class RoiTraceExtractor(object):
         if chunk_frames < 1:
             raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
         shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
+        bidi = _check_bidi(bidi, shape)
         self.shape, self.n_frames, self.areas = shape, n_frames, areas
         self.n_rois = len(areas)
         self.chunk_frames = min(chunk_frames, n_frames)
@@ -152,8 +155,8 @@ class RoiTraceExtractor(object):
         self._rows = len(row_roi)
         # every chunk writes its own columns of every row, so the state is never cleared
         self.sums = torch.empty((self.n_rois, n_frames), dtype=torch.int64, device=dev)
-        self._shifted = None if shifts is None else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
-                                                                   self.dtype == np.dtype(np.uint16))
+        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
+                                                                                self.dtype == np.dtype(np.uint16), bidi)
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
@@ -232,12 +235,14 @@ class RoiTraceExtractor(object):
 
 
 def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device=None, chunk_frames=None, shifts=None,
-                          fine_shifts=None):
+                          fine_shifts=None, bidi=0):
     """The (R,T) traces of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
     recording is memory-mapped or sliced, never read whole.  shifts: the (T, 2) (dy, dx) of every frame, or its (T, By, Bx, 2) block
     shifts (motion.estimate_shifts_device), applied on the device on the way in.  fine_shifts: instead, either shape in sixteenths
-    of a pixel (estimate_shifts_device(subpixel=True)): the frames are interpolated on the way in."""
+    of a pixel (estimate_shifts_device(subpixel=True)): the frames are interpolated on the way in.  bidi: the offset of the odd lines
+    (motion.estimate_bidi_device), undone on the way in before the shifts."""
     _check_kind(kind)
+    _check_bidi(bidi)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     frames, close = _open_series(dspath, source)
@@ -246,7 +251,7 @@ def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         ext = RoiTraceExtractor(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames,
-                                shifts=shifts, fine_shifts=fine_shifts)
+                                shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
         for a in range(0, T, ext.chunk_frames):
             ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
         out = ext.result(kind)

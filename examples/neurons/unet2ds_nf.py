@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -32,7 +32,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
-                              estimate_shifts_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
+                              estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
                               split_rois_device)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
@@ -122,7 +122,7 @@ def _neuropil_arg(text):
 
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
-           percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8):
+           percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -139,7 +139,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     correlation >= THR, ROIs with none are dropped, and the traces are those of the refined ROIs (a second pass).
     split=GAP: one more pass over the recording (after the refinement, where both are given) computes the correlation of every
     pixel of an ROI with every other one; an ROI whose pixels fall into two groups, each of at least `min_area` pixels and more
-    correlated within than across by GAP (deep_calcium_amd.split_rois), becomes two ROIs with a trace each."""
+    correlated within than across by GAP (deep_calcium_amd.split_rois), becomes two ROIs with a trace each.
+    bidi=P (with or without register): the scan-phase offset of the odd lines is searched within +-P over the first 200 frames of
+    `series/raw` first, and every later step -- the registration and its template, the summary the network segments, the
+    footprints, the split, the traces -- reads frames whose odd lines have been moved back by it."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -149,23 +152,36 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--coarse needs --register')
     if coarse is not None and blocks is not None:
         raise ValueError('--coarse together with --blocks is not built: the piecewise-rigid mode needs --register <= 16')
+    if bidi is not None and not 0 <= bidi <= 16:
+        raise ValueError('--bidi searches within +-P pixels, P in [0, 16], not %d' % bidi)
     if dff is None and neuropil is not None:
         raise ValueError('--neuropil needs --dff')
     known = 'fine_shifts' if subpixel else 'shifts'
     unit = 16 if subpixel else 1
     dspaths = nf_find_hdf5(dataset_name)
-    shifts = {}
+    shifts, offsets = {}, {}
+
+    def moves(p):
+        # the keywords of every reader of the recording: the known shifts and the scan-phase offset
+        return {known: shifts.get(p), 'bidi': offsets.get(p, 0)}
+    if bidi is not None:
+        for dspath in dspaths:
+            offsets[dspath], totals = estimate_bidi_device(dspath, max_offset=bidi, frames=200)
+            ranked = sorted(totals)
+            logger.info('%s: scan-phase offset %+d of the odd lines (searched within +-%d over the first 200 frames): total %d, '
+                        'runner-up %d, gap %d' % (dspath, offsets[dspath], bidi, ranked[0], ranked[min(1, len(ranked) - 1)],
+                                                  ranked[min(1, len(ranked) - 1)] - ranked[0]))
     if register is not None:
         for dspath in dspaths:
             shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register, blocks=blocks, max_dev=max_dev, subpixel=subpixel,
-                                                          coarse=coarse)
+                                                          coarse=coarse, bidi=offsets.get(dspath, 0))
             logger.info('%s: registered within +-%d%s%s%s, largest |dy|, |dx| = %g, %g, valid rectangle %r' % (
                 dspath, register, '' if coarse is None else ' (wide search, binned %d x %d)' % (coarse, coarse), '' if blocks is None else ' in %d x %d blocks within +-%d of that' % (blocks + (max_dev,)),
                 ', refined to 1/16 pixel' if subpixel else '',
                 np.abs(shifts[dspath][..., 0]).max() / unit, np.abs(shifts[dspath][..., 1]).max() / unit,
-                valid_rectangle(shifts[dspath], tmpl.shape, fine=subpixel)))
-        model = UNet2DSummary(cpdir=checkpoints_dir,
-                              series_summary_func=lambda p: summarize_series_device(p, kind='mean', **{known: shifts[p]}))
+                valid_rectangle(shifts[dspath], tmpl.shape, fine=subpixel, bidi=offsets.get(dspath, 0))))
+    if register is not None or bidi is not None:
+        model = UNet2DSummary(cpdir=checkpoints_dir, series_summary_func=lambda p: summarize_series_device(p, kind='mean', **moves(p)))
     else:
         model = UNet2DSummary(cpdir=checkpoints_dir)
     Mp, names = model.predict(dspaths, model_path=model_path, window_shape=(512, 512), save=False, augmentation=True)
@@ -175,7 +191,7 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             logger.info('%s: no neurons predicted, no traces file.' % name)
             continue
         if refine is not None:
-            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, **{known: shifts.get(dspath)})
+            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, **moves(dspath))
             rois, kept = refine_rois(coords, corr, mask.shape, threshold=refine)
             before = [set(map(tuple, c[i].tolist())) for c, i in zip(coords, inside)]
             after = dict((r, set(map(tuple, c.tolist()))) for r, c in zip(kept, rois))
@@ -188,15 +204,15 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                 continue
             mask = rois
         if split is not None:
-            rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, **{known: shifts.get(dspath)})
+            rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, **moves(dspath))
             before = int(np.count_nonzero(mask)) if isinstance(mask, np.ndarray) else sum(len(r) for r in mask)
             logger.info('%s: split at gap >= %g (min area %d): %d of %d ROIs split, %d pixels dropped' % (
                 name, split, min_area, len(rois) - len(gaps), len(gaps), before - sum(len(r) for r in rois)))
             mask = rois
         if dff is not None:
-            tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **{known: shifts.get(dspath)})
+            tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **moves(dspath))
         else:
-            tr = extract_traces_device(dspath, mask, kind=kind, **{known: shifts.get(dspath)})
+            tr = extract_traces_device(dspath, mask, kind=kind, **moves(dspath))
         out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
         logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
@@ -237,6 +253,8 @@ if __name__ == '__main__':
     sp_trc.add_argument('--coarse', help='with --register: the wide search, a coarse shift on frames binned C x C first; S may then reach 16 C',
                         default=None, type=int, choices=(2, 4, 8), metavar='C')
     sp_trc.add_argument('--subpixel', help='with --register: refine every shift to 1/16 pixel and interpolate the frames', action='store_true')
+    sp_trc.add_argument('--bidi', help='undo the scan-phase offset of the odd lines first: searched within +-P pixels (default 8, at most 16) '
+                        'over the first 200 frames', nargs='?', const=8, default=None, type=int, metavar='P')
     sp_trc.add_argument('--dff', help='write dF/F against a rolling-percentile baseline over WINDOW frames (odd) instead of --kind', default=None,
                         type=int, metavar='WINDOW')
     sp_trc.add_argument('--percentile', help='with --dff: the integer percentile of the baseline (default 8)', default=8, type=int, metavar='Q')

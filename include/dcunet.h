@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 119
+#define DC_ABI_VERSION 120
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -811,6 +811,29 @@ int dc_motion_ssd_around(const void* frames, int is_unsigned, int tc, const void
                          int mult, long* wscores, dc_stream_t stream);
 int dc_motion_pick_around(const long* wscores, const int* rows, int mult, int tc, int S, int D, int* shifts, long* best, int* fine,
                           dc_stream_t stream);
+
+/* ---- bidirectional scan-phase correction: the odd lines of a resonant-scanned recording moved against the even ones ------------
+ * A resonant scanner draws even lines left to right and odd lines right to left; a phase error between the two sweeps displaces
+ * all odd lines horizontally against the even ones by a constant few pixels.  This is the step in front of registration: one
+ * whole-pixel offset per recording, found by exhaustive search within +-P, 0 <= P <= DC_BIDI_MAX_OFFSET, and applied as a pure
+ * move of 16-bit values.  Integers only: every result is exact and the chunking of a recording never changes a bit.  A sub-pixel
+ * or per-frame offset is not built.  frames: as for dc_motion_ssd (int16 / uint16 by is_unsigned, [tc][H][W] contiguous).
+ * SIGN CONVENTION, in the motion section's words: an offset p means out[y][x] = frame[y][x + p] for ODD y and out[y][x] =
+ * frame[y][x] for even y.  Odd lines recorded as frame[y][x] = scene[y][x + b] are found as p = -b.
+ *   dc_bidi_scores: scores = int64[tc][2P+1], index p + P, fully written (never pre-clear):
+ *     scores[t][p+P] = sum over odd y in [1, H-1) and x in [P, W-P) of (2 f[y][x+p] - f[y-1][x] - f[y+1][x])^2 -- every candidate
+ *     sums the same pixels and never reads outside the frame; the two even neighbours cancel a vertical gradient to first order.
+ *     |e| <= 131070, so e^2 < 2^34 (formed in 64 bits), and with H * W <= 2^28 a score is below 2^61.  P = 0 is legal (one score
+ *     per frame).  H < 3 or W <= 2P: DC_EINVAL; P > 16 or H * W > 2^28: DC_EUNSUP (-3).  tc == 0 launches nothing.
+ *   THE PICK is the host's (the scores of the frames used are summed per offset first, in integers of any size): the offset
+ *     minimises (total, p^2, p) -- 0 wins every tie it is part of, then the smaller |p|, then the negative one: the order of
+ *     dc_motion_pick in one dimension.
+ *   dc_bidi_apply: the move above; `fill` (as for dc_motion_apply) goes where x + p leaves the row, even rows are copied.  p is
+ *     passed by value and any int32 is legal; |p| >= W gives all-fill odd rows; p = 0 is a copy.  out must not overlap frames
+ *     (DC_EINVAL); H * W > 2^30: DC_EUNSUP. */
+#define DC_BIDI_MAX_OFFSET 16
+int dc_bidi_scores(const void* frames, int is_unsigned, int tc, int H, int W, int P, long* scores, dc_stream_t stream);
+int dc_bidi_apply(const void* frames, int tc, int p, int H, int W, int fill, void* out, dc_stream_t stream);
 
 /* ---- UNet1D spike inference: traces in, spike probabilities out ------------------------------------------------------------
  * The reference's second model family, UNet1DSegmentation: the network unet1d (unet_1d_segmentation.py:49-148) as its predict()
