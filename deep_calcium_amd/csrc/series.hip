@@ -1,6 +1,7 @@
 // Series summaries on the device: the (H, W) images a recording (T, H, W) of 16-bit frames is reduced to before segmentation --
 // the reference's stored float16 mean and int16 max (datasets/nf.py:121-130), the true mean, max and temporal standard deviation,
-// the local correlation image, and the image standardisation of _summarize_series (unet_2d_summary.py:227-241).
+// the local correlation image, and the image standardisation of _summarize_series (unet_2d_summary.py:227-241) -- and, in front of
+// every reader of a recording, the temporal bins: the exact rounded means of b consecutive frames (dc_series_bin_time).
 //
 // Everything that can be exact is exact: the running sums are integers, the variance / covariance numerators are formed in 128-bit
 // integer arithmetic (series_math.h), and the float16 chain rounds once per frame from an IEEE double, as numpy does.  Nothing in
@@ -226,6 +227,104 @@ __global__ __launch_bounds__(kThreads) void image_standardize_kernel(const float
   }
 }
 
+// ---- temporal binning: out[j] = the rounded mean of b consecutive frames (the definitions are in include/dcunet.h) ------------------
+// One memory-bound pass that reads every input value once.  A work item is one output SLOT -- the n_out bins the call closes and,
+// behind them, the bin it leaves open -- times one group of 8 consecutive pixels: blockIdx.y strides over the slots, the x grid
+// over the groups, so a 64-frame chunk at b = 4 is 17 * H * W / 8 items and neighbouring lanes read neighbouring 16-byte pieces.
+// Slot j holds the chunk's frames [j b - phase, (j + 1) b - phase) that exist; only slot 0 starts from `carry` (phase > 0), only
+// the open slot writes it.  `carry` is updated in place, so where one call does both (phase > 0, a bin closed, a bin left open)
+// the open slot is no item of its own: the item of slot 0 adds it up and stores it AFTER it has read the old carry of the same
+// pixels (`ride`) -- an item of its own would race with that read.  16-byte loads and stores where every frame starts 16-byte
+// aligned (H * W % 8 == 0 and an aligned base; in, out and carry each on their own), value by value otherwise -- a ragged last
+// group included.
+const int kBinPix = 8;                // pixels per item
+const int kBinBlocksX = 4096;         // workgroups along the groups; the slots stride at 65535
+
+// s[k] += pixel k of the frames [i0, i1) of the chunk, for the n valid pixels of the group at f0 = frames + p0
+template <bool UNS>
+__device__ __forceinline__ void bin_add_frames(const uint16_t* __restrict__ f0, int i0, int i1, int HW, int n, int wide_in, int (&s)[kBinPix]) {
+  const uint16_t* f = f0 + (long)i0 * HW;
+#pragma unroll 4
+  for (int i = i0; i < i1; ++i, f += HW) {
+    unsigned w[kBinPix / 2];
+    if (wide_in) {                                       // H * W % 8 == 0: every group is whole
+      const uint4 v = *reinterpret_cast<const uint4*>(f);
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+      for (int q = 0; q < kBinPix / 2; ++q) {
+        const unsigned a = 2 * q < n ? f[2 * q] : 0u, c = 2 * q + 1 < n ? f[2 * q + 1] : 0u;
+        w[q] = a | (c << 16);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kBinPix; ++k) s[k] += widen<UNS>((uint16_t)((w[k / 2] >> (16 * (k & 1))) & 0xffffu));
+  }
+}
+
+__device__ __forceinline__ void bin_put_carry(int* __restrict__ c, int n, int wide_carry, const int (&s)[kBinPix]) {
+  if (wide_carry && n == kBinPix) {
+    *reinterpret_cast<int4*>(c) = make_int4(s[0], s[1], s[2], s[3]);
+    *reinterpret_cast<int4*>(c + 4) = make_int4(s[4], s[5], s[6], s[7]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < kBinPix; ++k)
+      if (k < n) c[k] = s[k];
+  }
+}
+
+// n_slots: the slots that are items of their own -- n_out, plus the open one unless it rides on slot 0
+template <bool UNS>
+__global__ __launch_bounds__(kThreads) void series_bin_time_kernel(const uint16_t* __restrict__ frames, int tc, int HW, int b, int phase,
+                                                                  uint32_t magic, int* carry, uint16_t* __restrict__ out, int n_out,
+                                                                  int n_slots, int ride, int wide_in, int wide_out, int wide_carry) {
+  const int G = (HW + kBinPix - 1) / kBinPix;
+  for (long j = blockIdx.y; j < n_slots; j += gridDim.y) {
+    const long lo = j * b - phase;
+    const int i0 = lo < 0 ? 0 : (int)lo, i1 = lo + b < tc ? (int)(lo + b) : tc;
+    const bool head = j == 0 && phase > 0, open = j >= n_out;
+    for (int g = blockIdx.x * kThreads + threadIdx.x; g < G; g += gridDim.x * kThreads) {
+      const int p0 = g * kBinPix;
+      const int n = HW - p0 < kBinPix ? HW - p0 : kBinPix;
+      int s[kBinPix];
+#pragma unroll
+      for (int k = 0; k < kBinPix; ++k) s[k] = 0;
+      if (head) {
+        if (wide_carry && n == kBinPix) {
+          const int4 c0 = *reinterpret_cast<const int4*>(carry + p0), c1 = *reinterpret_cast<const int4*>(carry + p0 + 4);
+          s[0] = c0.x; s[1] = c0.y; s[2] = c0.z; s[3] = c0.w; s[4] = c1.x; s[5] = c1.y; s[6] = c1.z; s[7] = c1.w;
+        } else {
+#pragma unroll
+          for (int k = 0; k < kBinPix; ++k)
+            if (k < n) s[k] = carry[p0 + k];
+        }
+      }
+      bin_add_frames<UNS>(frames + p0, i0, i1, HW, n, wide_in, s);
+      if (open) {                                        // head and open at once: no bin closes, the thread's own read came first
+        bin_put_carry(carry + p0, n, wide_carry, s);
+        continue;
+      }
+      unsigned r[kBinPix];
+#pragma unroll
+      for (int k = 0; k < kBinPix; ++k) r[k] = (unsigned)dc_series_bin_round(s[k], b, magic) & 0xffffu;
+      uint16_t* o = out + j * HW + p0;
+      if (wide_out) {
+        *reinterpret_cast<uint4*>(o) = make_uint4(r[0] | (r[1] << 16), r[2] | (r[3] << 16), r[4] | (r[5] << 16), r[6] | (r[7] << 16));
+      } else {
+#pragma unroll
+        for (int k = 0; k < kBinPix; ++k)
+          if (k < n) o[k] = (uint16_t)r[k];
+      }
+      if (head && ride) {                                // the open bin of these pixels: frames [n_out b - phase, tc)
+#pragma unroll
+        for (int k = 0; k < kBinPix; ++k) s[k] = 0;
+        bin_add_frames<UNS>(frames + p0, (int)((long)n_out * b - phase), tc, HW, n, wide_in, s);
+        bin_put_carry(carry + p0, n, wide_carry, s);
+      }
+    }
+  }
+}
+
 int series_check(const char* fn, const void* frames, int tc, long t0, int H, int W) {
   DC_REQUIRE(frames, DC_EINVAL, "%s: null pointer", fn);
   DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "%s: image %d x %d out of range", fn, H, W);
@@ -293,6 +392,42 @@ extern "C" int dc_series_finalize(const long* sum, const long* sumsq, const long
   hipLaunchKernelGGL(series_finalize_kernel, dim3((unsigned)dc_cdiv((long)H * W, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
                      (const int64_t*)sum, (const int64_t*)sumsq, (const int64_t*)xy, mean, sdev, corr, H, W, (int64_t)T);
   DC_CHECK_LAUNCH("dc_series_finalize");
+  return DC_OK;
+}
+
+extern "C" int dc_series_bin_time(const void* frames, int is_unsigned, int tc, int H, int W, int b, int phase, int* carry, void* out,
+                                  dc_stream_t stream) {
+  DC_REQUIRE(b >= 1, DC_EINVAL, "dc_series_bin_time: b = %d: a bin holds at least one frame", b);
+  DC_REQUIRE(b <= DC_SERIES_MAX_BIN_FRAMES, DC_EUNSUP, "dc_series_bin_time: b = %d: a bin is limited to %d frames", b, DC_SERIES_MAX_BIN_FRAMES);
+  DC_REQUIRE(phase >= 0 && phase < b, DC_EINVAL, "dc_series_bin_time: phase = %d outside [0, %d)", phase, b);
+  DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_series_bin_time: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_series_bin_time: image %d x %d: H * W is limited to 2^30", H, W);
+  if (tc == 0) return DC_OK;
+  const long seen = (long)phase + tc, n_out = seen / b;
+  const int rem = (int)(seen % b);
+  const bool uses_carry = phase > 0 || rem > 0;          // read by slot 0, written by the open slot: otherwise never followed
+  DC_REQUIRE(frames && (n_out == 0 || out) && (!uses_carry || carry), DC_EINVAL, "dc_series_bin_time: null pointer");
+  DC_REQUIRE((((uintptr_t)frames | (uintptr_t)out) & 1) == 0 && (((uintptr_t)carry) & 3) == 0, DC_EINVAL, "dc_series_bin_time: misaligned buffer");
+  const uintptr_t HW = (uintptr_t)H * W, fa = (uintptr_t)frames, fb = 2 * HW * (uintptr_t)tc, oa = (uintptr_t)out, ob = 2 * HW * (uintptr_t)n_out,
+                  ca = (uintptr_t)carry, cb = uses_carry ? 4 * HW : 0;
+  DC_REQUIRE(ob == 0 || fa + fb <= oa || oa + ob <= fa, DC_EINVAL, "dc_series_bin_time: out overlaps frames");
+  DC_REQUIRE(ob == 0 || cb == 0 || ca + cb <= oa || oa + ob <= ca, DC_EINVAL, "dc_series_bin_time: out overlaps carry");
+  DC_REQUIRE(cb == 0 || fa + fb <= ca || ca + cb <= fa, DC_EINVAL, "dc_series_bin_time: carry overlaps frames");
+  const int ride = (int)(phase > 0 && rem > 0 && n_out > 0);      // carry is read AND written: the open slot rides on slot 0's items
+  const long n_slots = n_out + (rem > 0 && !ride);
+  const bool whole = HW % kBinPix == 0;
+  const int wide_in = (int)(whole && dc_aligned16(frames)), wide_out = (int)(whole && dc_aligned16(out)), wide_carry = (int)dc_aligned16(carry);
+  const int bx = dc_cdiv(dc_cdiv((long)HW, kBinPix), kThreads);
+  const dim3 grid((unsigned)(bx < kBinBlocksX ? bx : kBinBlocksX), (unsigned)(n_slots < 65535 ? n_slots : 65535)), block(kThreads);
+  const uint32_t magic = dc_series_bin_magic(b);
+  const uint16_t* f = (const uint16_t*)frames;
+  if (is_unsigned)
+    hipLaunchKernelGGL(series_bin_time_kernel<true>, grid, block, 0, (hipStream_t)stream, f, tc, (int)HW, b, phase, magic, carry, (uint16_t*)out,
+                       (int)n_out, (int)n_slots, ride, wide_in, wide_out, wide_carry);
+  else
+    hipLaunchKernelGGL(series_bin_time_kernel<false>, grid, block, 0, (hipStream_t)stream, f, tc, (int)HW, b, phase, magic, carry, (uint16_t*)out,
+                       (int)n_out, (int)n_slots, ride, wide_in, wide_out, wide_carry);
+  DC_CHECK_LAUNCH("dc_series_bin_time");
   return DC_OK;
 }
 

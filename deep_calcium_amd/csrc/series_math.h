@@ -57,6 +57,18 @@ DC_HD double dc_f16_bits_to_f64(uint16_t h) {
   return dc_f64_of_bits(sign | ((uint64_t)(ex - 15 + 1023) << 52) | ((uint64_t)man << 42));
 }
 
+// ---- temporal binning (series.hip, dc_series_bin_time): the mean of b frames rounded half up, floor((2 s + b) / (2 b)) for any b in
+// [1, 64] and any sum s of b 16-bit values, negative ones included -- the rule of make_template and dc_motion_bin_round, which
+// shifts and so takes powers of two only.  The division is a multiplication by magic = floor(2^32 / 2b) + 1: the numerator is
+// first moved by 32768 * 2b to n = 2 s + b + 65536 b, which lies in [b, 3 * 2^22) for |s| <= 65535 b, so the quotient is the
+// floor of the signed one plus 32768; and n * magic / 2^32 exceeds n / 2b by less than n / 2^32 < 2^-8 < 1 / 2b, which cannot
+// reach the next integer.  tests/native/series_bin_check.cpp holds it against 64-bit floor division.
+DC_HD uint32_t dc_series_bin_magic(int b) { return (uint32_t)(0x100000000ull / (uint64_t)(2 * b)) + 1u; }
+DC_HD int dc_series_bin_round(int s, int b, uint32_t magic) {
+  const uint32_t n = (uint32_t)(2 * s + b + 65536 * b);
+  return (int)(uint32_t)(((uint64_t)n * magic) >> 32) - 32768;
+}
+
 // ---- signed 128-bit integers from two 64-bit words (two's complement: value = hi * 2^64 + lo) -----------------------------------
 struct DcI128 { uint64_t lo; int64_t hi; };
 

@@ -186,7 +186,8 @@ class RoiFootprints(object):
         return [i.copy() for i in self._inside]
 
     def traces(self, kind='mean'):
-        """RoiTraceExtractor.result(kind) of the same pass."""
+        """RoiTraceExtractor.result(kind) of the same pass.  Fed the output of a series.TemporalBinner, these are the traces of the
+        BINNED recording (n_frames // bin_frames samples of rounded means): a trace of every frame is another, unbinned pass."""
         return self._ext.result(kind)
 
     def sums_device(self):
@@ -227,22 +228,31 @@ class RoiFootprints(object):
 
 
 def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None,
-                          bidi=0):
+                          bin_frames=None, bidi=0):
     """-> (corr, coords, inside) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk:
-    the recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device."""
-    from .series import _open_series
+    the recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: None, or an integer b in
+    [1, 64]: the maps are those of the T // b rounded means of b consecutive corrected frames, correlated with the ROI traces of
+    that binned recording (series.TemporalBinner; the trailing T % b frames are dropped, 1 gives what None gives)."""
+    from .series import _check_bin_frames, _feed_binned, _open_series
     _check_halo(halo)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
+    if bin_frames is not None:
+        _check_bin_frames(bin_frames)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
-        fp = RoiFootprints(tuple(frames.shape[1:]), T, frames.dtype, rois, halo=halo, device=device, chunk_frames=chunk_frames,
-                           shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
-        for a in range(0, T, fp.chunk_frames):
-            fp.feed(np.asarray(frames[a:a + fp.chunk_frames]))
+        if bin_frames is None:
+            fp = RoiFootprints(tuple(frames.shape[1:]), T, frames.dtype, rois, halo=halo, device=device, chunk_frames=chunk_frames,
+                               shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
+            for a in range(0, T, fp.chunk_frames):
+                fp.feed(np.asarray(frames[a:a + fp.chunk_frames]))
+        else:
+            fp = _feed_binned(frames, bin_frames, lambda n, dev: RoiFootprints(tuple(frames.shape[1:]), n, frames.dtype, rois, halo=halo,
+                                                                               device=dev, chunk_frames=chunk_frames),
+                              device, chunk_frames, shifts, fine_shifts, bidi)
         out = fp.result('corr'), fp.support(), fp.inside()
     finally:
         frames = None                        # a view of the file mapping: released before the file is closed

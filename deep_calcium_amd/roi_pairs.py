@@ -140,7 +140,8 @@ class RoiPairCorr(object):
         return [p.copy() for p in self._pixels]
 
     def traces(self, kind='mean'):
-        """RoiTraceExtractor.result(kind) of the same pass."""
+        """RoiTraceExtractor.result(kind) of the same pass.  Fed the output of a series.TemporalBinner, these are the traces of the
+        BINNED recording (n_frames // bin_frames samples of rounded means): a trace of every frame is another, unbinned pass."""
         return self._ext.result(kind)
 
     def _squares(self, flat):
@@ -263,21 +264,31 @@ def split_rois(pixels, corr, shape, min_gap=0.1, min_area=8, iterations=16):
     return new_rois, origin, gaps
 
 
-def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
+def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None,
+                         bin_frames=None, bidi=0):
     """-> (corr, pixels) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
-    recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device."""
-    from .series import _open_series
+    recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: None, or an integer b in
+    [1, 64]: the matrices are those of the T // b rounded means of b consecutive corrected frames (series.TemporalBinner; the
+    trailing T % b frames are dropped, 1 gives what None gives)."""
+    from .series import _check_bin_frames, _feed_binned, _open_series
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
+    if bin_frames is not None:
+        _check_bin_frames(bin_frames)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
-        pc = RoiPairCorr(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                         fine_shifts=fine_shifts, bidi=bidi)
-        for a in range(0, T, pc.chunk_frames):
-            pc.feed(np.asarray(frames[a:a + pc.chunk_frames]))
+        if bin_frames is None:
+            pc = RoiPairCorr(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames, shifts=shifts,
+                             fine_shifts=fine_shifts, bidi=bidi)
+            for a in range(0, T, pc.chunk_frames):
+                pc.feed(np.asarray(frames[a:a + pc.chunk_frames]))
+        else:
+            pc = _feed_binned(frames, bin_frames, lambda n, dev: RoiPairCorr(tuple(frames.shape[1:]), n, frames.dtype, rois, device=dev,
+                                                                             chunk_frames=chunk_frames),
+                              device, chunk_frames, shifts, fine_shifts, bidi)
         out = pc.result('corr'), pc.pixels()
     finally:
         frames = None                        # a view of the file mapping: released before the file is closed
@@ -286,14 +297,18 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
 
 
 def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, source='series/raw', device=None, chunk_frames=None,
-                      shifts=None, fine_shifts=None, bidi=0):
+                      shifts=None, fine_shifts=None, bin_frames=None, bidi=0):
     """-> (new_rois, origin, gaps) of split_rois for `rois` over `source` of a dataset file, in one pass over the recording.  ROIs
     of more than MAX_AREA or fewer than 2 * min_area pixels are not sent to the device and come back unchanged (gap NaN); when
-    no ROI is left the recording is not read at all.  shifts / fine_shifts / bidi: as for extract_traces_device."""
-    from .series import _open_series
+    no ROI is left the recording is not read at all.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: as
+    for roi_pair_corr_device -- the pixel noise of a mean of b frames is lower by sqrt(b), which is what lets the rule part cells
+    it cannot part frame by frame; keep T // b well above 100, chance correlations split static regions below that."""
+    from .series import _check_bin_frames, _open_series
     min_gap, min_area, iterations = _check_split_args(min_gap, min_area, iterations)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
+    if bin_frames is not None:
+        _check_bin_frames(bin_frames)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
@@ -308,7 +323,7 @@ def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, sour
     corr = [None] * len(pixels)
     if sent:
         got, _ = roi_pair_corr_device(dspath, [pixels[r] for r in sent], source=source, device=device, chunk_frames=chunk_frames,
-                                      shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
+                                      shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, bin_frames=bin_frames)
         for r, c in zip(sent, got):
             corr[r] = c
     return split_rois(pixels, corr, shape, min_gap=min_gap, min_area=min_area, iterations=iterations)

@@ -18,6 +18,9 @@ are streamed once through the dc_series_* kernels (include/dcunet.h):
 
     UNet2DSummary(series_summary_func=functools.partial(summarize_series_device, kind='corr'))
 
+TemporalBinner (dc_series_bin_time) goes in front of any reader: the exact rounded means of b <= 64 consecutive frames, streamed,
+so that what is correlated is a transient and not the pixel noise of single frames (bin_frames= of the one-call functions).
+
 Importing this module needs neither torch nor the GPU; constructing a SeriesSummarizer does (there is no CPU fallback).
 """
 import numpy as np
@@ -362,6 +365,147 @@ class SeriesSummarizer(object):
         return self._standardize(img).cpu().numpy().reshape(H, W)
 
 
+MAX_BIN_FRAMES = 64                   # DC_SERIES_MAX_BIN_FRAMES: the frames of one temporal bin
+
+
+def _check_bin_frames(bin_frames, n_frames=None):
+    """The `bin_frames=` keyword: an integer in [1, MAX_BIN_FRAMES], and no more than the recording holds.  Host only."""
+    if isinstance(bin_frames, bool) or not isinstance(bin_frames, (int, np.integer)):
+        raise ValueError('bin_frames must be an integer in [1, %d], not %r' % (MAX_BIN_FRAMES, bin_frames))
+    b = int(bin_frames)
+    if not 1 <= b <= MAX_BIN_FRAMES:
+        raise ValueError('bin_frames must be in [1, %d], not %d' % (MAX_BIN_FRAMES, b))
+    if n_frames is not None and n_frames < b:
+        raise ValueError('bin_frames = %d, the recording has only %d frames' % (b, n_frames))
+    return b
+
+
+class TemporalBinner(object):
+    """Temporal binning in front of the readers: the recording's frames in, the means of `bin_frames` consecutive frames out, on
+    the device (dc_series_bin_time).  A bin's value is floor((2 s + b) / (2 b)) of the exact sum s of its b frames -- the mean
+    rounded half up, the rule of make_template and dc_motion_bin -- in the recording's own 16-bit type, so every reader takes the
+    binned frames as it takes the raw ones.  The trailing n_frames % bin_frames frames close no bin and are dropped, as
+    dc_motion_bin drops trailing rows.  Chunk boundaries never change a bit.
+
+        tb = TemporalBinner((H, W), T, np.int16, bin_frames=4)
+        reader = RoiPairCorr((H, W), tb.n_out, np.int16, rois)
+        for chunk in chunks:
+            binned = tb.feed(chunk)
+            if binned.shape[0]: reader.feed(binned)
+
+    n_out = n_frames // bin_frames; fed: frames consumed so far; emitted: bins written so far."""
+
+    def __init__(self, shape, n_frames, dtype, bin_frames=4, shifts=None, fine_shifts=None, bidi=0, device=None, chunk_frames=None):
+        """shifts / fine_shifts / bidi: as for SeriesSummarizer, applied BEFORE the sum (dc_bidi_apply, then the shift move, fill
+        0): the means are means of registered frames.  bin_frames: an integer in [1, 64], at most n_frames; 1 is a copy."""
+        # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
+        try:
+            shape = tuple(int(v) for v in shape)
+        except TypeError:
+            raise ValueError('shape must be (H, W), not %r' % (shape,))
+        if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] > (1 << 30):
+            raise ValueError('shape must be (H, W) with 1 <= H * W <= 2**30, not %r' % (shape,))
+        n_frames = int(n_frames)
+        if not 1 <= n_frames <= MAX_FRAMES:
+            raise ValueError('n_frames must be in [1, %d], not %d' % (MAX_FRAMES, n_frames))
+        self.dtype = _frame_dtype(dtype)
+        self.bin_frames = _check_bin_frames(bin_frames, n_frames)
+        H, W = shape
+        if chunk_frames is None:
+            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 1:
+            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
+        shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
+        bidi = _check_bidi(bidi, shape)
+        self.shape, self.n_frames = shape, n_frames
+        self.n_out = n_frames // self.bin_frames
+        self.chunk_frames = min(chunk_frames, n_frames)
+        self.fed = self.emitted = 0
+
+        import torch
+        from . import net
+        from ._lib import lib
+        self._torch, self._net = torch, net
+        self.L = lib()
+        if not torch.cuda.is_available():
+            from ._lib import DcunetError
+            raise DcunetError('TemporalBinner needs a GPU (there is no CPU fallback)')
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        dev = self.device
+        # the open bin's sum: read only once a call has left frames in it, so never cleared here
+        self._carry = torch.empty(H * W, dtype=torch.int32, device=dev)
+        self._stage = None
+        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
+                                                                                self.dtype == np.dtype(np.uint16), bidi)
+
+    def feed(self, frames):
+        """The next frames of the recording, any t >= 1: what SeriesSummarizer.feed takes (numpy or memmap chunks of the
+        recording's dtype, staged through two pinned slots; or a contiguous (t, H, W) torch.int16 tensor on the binner's device,
+        read in place).  -> the bins this feed closed: a contiguous (k, H, W) torch.int16 tensor on the device holding the bits of
+        the recording's dtype, k >= 0.  It is a FRESH allocation every time, written on the current stream: no later feed touches
+        it, and a reader fed on the same stream right away reads it after the kernels that wrote it."""
+        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
+        if not on_device and not isinstance(frames, np.ndarray):
+            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
+        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
+            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
+        if on_device:
+            _check_device_frames(self._torch, frames, self.dtype, self.device, 'binner')
+        elif frames.dtype != self.dtype:
+            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
+        if frames.shape[0] < 1 or self.fed + frames.shape[0] > self.n_frames:
+            raise ValueError('%d frames after %d fed: the recording was declared to have %d' %
+                             (frames.shape[0], self.fed, self.n_frames))
+        torch, L = self._torch, self.L
+        H, W = self.shape
+        b, uns = self.bin_frames, int(self.dtype == np.dtype(np.uint16))
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream(self.device)
+            st = main.cuda_stream
+            out = torch.empty(((self.fed % b + int(frames.shape[0])) // b, H, W), dtype=torch.int16, device=self.device)
+            first = self.emitted
+
+            def bin_time(fp, tc, t0):
+                k = (t0 % b + tc) // b
+                L.dc_series_bin_time(fp, uns, tc, H, W, b, t0 % b, self._carry.data_ptr(),
+                                     out.data_ptr() + 2 * H * W * (self.emitted - first) if k else None, st)
+                self.emitted += k
+
+            def consume(fp, tc):
+                if self._shifted is None:
+                    bin_time(fp, tc, self.fed)
+                else:
+                    self._shifted.run(fp, tc, self.fed, st, bin_time)
+                self.fed += tc
+            if on_device:
+                consume(frames.data_ptr(), int(frames.shape[0]))
+                frames.record_stream(main)
+            else:
+                if self._stage is None:          # names of its own: a reader alive at the same time keeps its slots
+                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'tbin_stage', (self.chunk_frames, H, W))
+                self._stage.run(frames, main, consume)
+        return out
+
+
+def _feed_binned(frames, bin_frames, reader_of, device, chunk_frames, shifts, fine_shifts, bidi):
+    """The binned pass of the one-call functions: a TemporalBinner that carries the corrections in front of
+    reader_of(n_frames // bin_frames, device), a reader declared with the binned length and no corrections of its own.  The
+    trailing frames that close no bin are not read.  -> the reader, fed."""
+    T = int(frames.shape[0])
+    tb = TemporalBinner(tuple(frames.shape[1:]), T, frames.dtype, bin_frames=bin_frames, shifts=shifts, fine_shifts=fine_shifts, bidi=bidi,
+                        device=device, chunk_frames=chunk_frames)
+    reader = reader_of(tb.n_out, tb.device)
+    used = tb.n_out * tb.bin_frames
+    for a in range(0, used, tb.chunk_frames):
+        binned = tb.feed(np.asarray(frames[a:min(a + tb.chunk_frames, used)]))
+        if binned.shape[0]:
+            reader.feed(binned)
+    return reader
+
+
 def _open_series(dspath, source):
     """(frames array-like of (T,H,W), close()) without reading the recording: .npz members and contiguous HDF5 datasets are
     memory-mapped, h5py datasets are sliced chunk by chunk."""
@@ -411,14 +555,19 @@ def _open_series(dspath, source):
 
 
 def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
-                            shifts=None, fine_shifts=None, bidi=0):
+                            shifts=None, fine_shifts=None, bin_frames=None, bidi=0):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
     float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame, or
     its (T, By, Bx, 2) block shifts (motion.estimate_shifts_device), applied on the device on the way in.  fine_shifts: instead,
     either shape in sixteenths of a pixel (estimate_shifts_device(subpixel=True)): the frames are interpolated on the way in.
-    bidi: the offset of the odd lines (motion.estimate_bidi_device), undone on the way in before the shifts."""
+    bidi: the offset of the odd lines (motion.estimate_bidi_device), undone on the way in before the shifts.
+    bin_frames: None, or an integer b in [1, 64]: the corrected frames pass through a TemporalBinner first and the summary is that
+    of the T // b rounded means of b consecutive frames (the trailing T % b frames are dropped; 1 gives what None gives).  `std`
+    and `corr` of a binned recording are not comparable with the unbinned ones."""
     _check_kind(kind)
     _check_bidi(bidi)
+    if bin_frames is not None:
+        _check_bin_frames(bin_frames)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     frames, close = _open_series(dspath, source)
@@ -426,10 +575,15 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
-        summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
-                                kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
-        for a in range(0, T, summ.chunk_frames):
-            summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
+        if bin_frames is None:
+            summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
+                                    kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
+            for a in range(0, T, summ.chunk_frames):
+                summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
+        else:
+            summ = _feed_binned(frames, bin_frames, lambda n, dev: SeriesSummarizer(tuple(frames.shape[1:]), n, frames.dtype, device=dev,
+                                                                                    chunk_frames=chunk_frames, kinds=(kind,)),
+                                device, chunk_frames, shifts, fine_shifts, bidi)
         out = summ.result(kind, standardize=standardize)
     finally:
         frames = None                        # a view of the file mapping: released before the file is closed

@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -121,8 +121,19 @@ def _neuropil_arg(text):
         raise argparse.ArgumentTypeError('expected INNER,OUTER,WEIGHT such as 2,12,0.7, not %r' % text)
 
 
+def _n_frames(dspath):
+    from deep_calcium_amd.series import _open_series
+    frames, close = _open_series(dspath, 'series/raw')
+    try:
+        return int(frames.shape[0])
+    finally:
+        frames = None
+        close()
+
+
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
-           percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None):
+           percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
+           bin_frames=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -142,7 +153,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     correlated within than across by GAP (deep_calcium_amd.split_rois), becomes two ROIs with a trace each.
     bidi=P (with or without register): the scan-phase offset of the odd lines is searched within +-P over the first 200 frames of
     `series/raw` first, and every later step -- the registration and its template, the summary the network segments, the
-    footprints, the split, the traces -- reads frames whose odd lines have been moved back by it."""
+    footprints, the split, the traces -- reads frames whose odd lines have been moved back by it.
+    bin_frames=B (with refine or split): those two passes correlate the rounded means of B consecutive corrected frames
+    (deep_calcium_amd.TemporalBinner: the pixel noise falls by sqrt(B), a transient of many frames survives; the trailing T % B
+    frames are dropped).  The traces that are written are always those of every frame.  Keep T // B well above 100."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -156,6 +170,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--bidi searches within +-P pixels, P in [0, 16], not %d' % bidi)
     if dff is None and neuropil is not None:
         raise ValueError('--neuropil needs --dff')
+    if bin_frames is not None and refine is None and split is None:
+        raise ValueError('--bin-frames needs --refine or --split: it bins the frames those passes correlate')
+    if bin_frames is not None and not 1 <= bin_frames <= 64:
+        raise ValueError('--bin-frames averages B consecutive frames, B in [1, 64], not %d' % bin_frames)
     known = 'fine_shifts' if subpixel else 'shifts'
     unit = 16 if subpixel else 1
     dspaths = nf_find_hdf5(dataset_name)
@@ -190,8 +208,12 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         if not mask.any():
             logger.info('%s: no neurons predicted, no traces file.' % name)
             continue
+        if bin_frames is not None:
+            T = _n_frames(dspath)
+            logger.info('%s: the refinement and the split read the means of %d consecutive frames: %d binned frames of %d'
+                        % (name, bin_frames, T // bin_frames, T))
         if refine is not None:
-            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, **moves(dspath))
+            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, bin_frames=bin_frames, **moves(dspath))
             rois, kept = refine_rois(coords, corr, mask.shape, threshold=refine)
             before = [set(map(tuple, c[i].tolist())) for c, i in zip(coords, inside)]
             after = dict((r, set(map(tuple, c.tolist()))) for r, c in zip(kept, rois))
@@ -204,7 +226,7 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                 continue
             mask = rois
         if split is not None:
-            rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, **moves(dspath))
+            rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, bin_frames=bin_frames, **moves(dspath))
             before = int(np.count_nonzero(mask)) if isinstance(mask, np.ndarray) else sum(len(r) for r in mask)
             logger.info('%s: split at gap >= %g (min area %d): %d of %d ROIs split, %d pixels dropped' % (
                 name, split, min_area, len(rois) - len(gaps), len(gaps), before - sum(len(r) for r in rois)))
@@ -268,6 +290,8 @@ if __name__ == '__main__':
                         nargs='?', const=0.1, default=None, type=float, metavar='GAP')
     sp_trc.add_argument('--min-area', help='with --split: the fewest pixels a part may have (default 8)', default=8, type=int, metavar='N',
                         dest='min_area')
+    sp_trc.add_argument('--bin-frames', help='with --refine / --split: correlate the means of B consecutive frames (1..64) instead of single frames',
+                        default=None, type=int, metavar='B', dest='bin_frames')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 120
+#define DC_ABI_VERSION 121
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -529,6 +529,21 @@ int dc_series_finalize(const long* sum, const long* sumsq, const long* xy, float
  * ws: float[dc_series_standardize_ws_floats()], 8-byte aligned.  in == out is allowed. */
 long dc_series_standardize_ws_floats(int H, int W);
 int dc_image_standardize(const float* in, float* out, float* ws, int H, int W, dc_stream_t stream);
+/* temporal binning: the means of b consecutive frames, streamed (no counterpart in datasets/nf.py:121-130 or
+ * unet_2d_summary.py:227-241; what is averaged before anything is correlated).  frames: [tc][H][W], int16 or uint16 by
+ * is_unsigned, 2-byte aligned.  carry: int32[H*W], 4-byte aligned, the sum of the `phase` frames of the open bin that earlier calls
+ * have seen, 0 <= phase < b.  The call consumes tc more frames, writes n_out = (phase + tc) / b frames of the same 16-bit type to
+ * `out` and leaves in `carry` the sum of the (phase + tc) % b frames of the bin that is still open:
+ *   out[j] = floor((2 s + b) / (2 b)), s the exact sum of the bin's b frames
+ * -- the mean rounded half up, the floor holding for negative sums (the rule of dc_motion_bin); it lies between the bin's
+ * smallest and largest value, and |s| <= 64 * 65535 < 2^22 fits int32.  carry is READ only when phase > 0 (never pre-cleared)
+ * and WRITTEN only when (phase + tc) % b > 0; a call with phase + tc < b writes no frame and only extends carry.  b = 1 is a copy;
+ * tc == 0 launches nothing.  Chunk boundaries never change a bit.
+ * DC_EINVAL (-1): b < 1, phase outside [0, b), a negative or zero size, a null pointer that would be followed, a misaligned
+ * buffer, out overlapping frames or carry (or carry overlapping frames).  DC_EUNSUP (-3): b > DC_SERIES_MAX_BIN_FRAMES, H * W > 2^30. */
+#define DC_SERIES_MAX_BIN_FRAMES 64
+int dc_series_bin_time(const void* frames, int is_unsigned, int tc, int H, int W, int b, int phase, int* carry, void* out,
+                       dc_stream_t stream);
 
 /* ---- ROI traces: a recording (T,H,W) of 16-bit frames + a set of ROIs -> one fluorescence trace per ROI -------------------
  * What the reference's spikes model reads from its dataset files: `traces`, a (no. ROIs, no. frames) matrix
