@@ -25,7 +25,7 @@ _EXPORTS = {
               'load_model_with_new_input_shape', 'metrics_from_sums'),
     'unet2ds': ('UNet2DSummary', 'INVERTIBLE_2D_AUGMENTATIONS', '_ValidationMetricsCB'),
     'nf_metrics': ('nf_mask_metrics',),
-    'series': ('SeriesSummarizer', 'summarize_series_device', 'TemporalBinner'),
+    'series': ('SeriesSummarizer', 'summarize_series_device', 'TemporalBinner', 'detrend_plan'),
     'traces': ('RoiTraceExtractor', 'rois_to_csr', 'extract_traces_device', 'write_traces_dataset'),
     'footprints': ('RoiFootprints', 'roi_footprints_device', 'roi_support', 'refine_rois'),
     'roi_pairs': ('RoiPairCorr', 'roi_pair_corr_device', 'split_rois', 'split_rois_device'),

@@ -9,6 +9,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "footprint_math.h"
+#include "detrend_math.h"
 
 namespace {
 
@@ -147,7 +148,103 @@ __global__ __launch_bounds__(kThreads) void roi_pixel_corr_kernel(const int64_t*
   }
 }
 
+// ---- detrended footprints: segment-pooled centred moments (include/dcunet.h, "Detrended correlations") -----------------------------
+// One workgroup per CSR row, one lane per entry, as in the accumulate kernel: the lane alone owns the entry's two pooled words and
+// its four planes of mom, which it folds with its ROI's segment moments (u, w of dc_roi_trace_moments over the segment's columns)
+// and clears for the next segment.
+__global__ __launch_bounds__(kThreads) void roi_pixel_fold_segment_kernel(int64_t* __restrict__ mom, long N, const int* __restrict__ row_off,
+                                                                         const int* __restrict__ row_roi, int R,
+                                                                         const int64_t* __restrict__ rmom, int64_t len, int64_t mult,
+                                                                         int64_t* __restrict__ pxx, int64_t* __restrict__ pxs) {
+  const int s = blockIdx.x;
+  const int r = row_roi ? row_roi[s] : s;
+  if (r < 0 || r >= R) return;                       // the accumulate kernel added nothing to such a row
+  long a0 = row_off[s], b0 = row_off[s + 1];
+  if (a0 < 0) a0 = 0;
+  if (b0 > N) b0 = N;
+  const int64_t u = rmom[r];
+  for (long e = a0 + threadIdx.x; e < b0; e += kThreads) {
+    const int64_t a = mom[e];
+    DcI128 c;
+    c.lo = (uint64_t)mom[2 * N + e];
+    c.hi = mom[3 * N + e];
+    dc_i128_store(pxx, e, dc_i128_add(dc_i128_load(pxx, e), dc_detrend_term(len, mult, mom[N + e], a, a)));
+    dc_i128_store(pxs, e, dc_i128_add(dc_i128_load(pxs, e), dc_detrend_term_wide(len, mult, c, a, u)));
+    mom[e] = 0; mom[N + e] = 0; mom[2 * N + e] = 0; mom[3 * N + e] = 0;
+  }
+}
+
+// the ROI's own pooled Css, one lane per ROI
+__global__ __launch_bounds__(kThreads) void roi_trace_fold_segment_kernel(const int64_t* __restrict__ rmom, int R, int64_t len, int64_t mult,
+                                                                         int64_t* __restrict__ pss) {
+  const long r = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (r >= R) return;
+  const int64_t u = rmom[r];
+  DcI128 w;
+  w.lo = (uint64_t)rmom[(long)R + r];
+  w.hi = rmom[2L * R + r];
+  dc_i128_store(pss, r, dc_i128_add(dc_i128_load(pss, r), dc_detrend_term_wide(len, mult, w, u, u)));
+}
+
+// pooled numerators -> the float32 map, in the form of roi_pixel_corr_kernel
+__global__ __launch_bounds__(kThreads) void roi_pixel_corr_pooled_kernel(const int64_t* __restrict__ pxx, const int64_t* __restrict__ pxs,
+                                                                        const int64_t* __restrict__ pss, long N,
+                                                                        const int* __restrict__ row_off, const int* __restrict__ row_roi,
+                                                                        int R, const int* __restrict__ inside, float* __restrict__ corr) {
+  const int s = blockIdx.x;
+  const int r = row_roi ? row_roi[s] : s;
+  long a0 = row_off[s], b0 = row_off[s + 1];
+  if (a0 < 0) a0 = 0;
+  if (b0 > N) b0 = N;
+  const bool named = r >= 0 && r < R;
+  DcI128 css = {0, 0};
+  if (named) css = dc_i128_load(pss, r);
+  for (long e = a0 + threadIdx.x; e < b0; e += kThreads)
+    corr[e] = named ? dc_fp_corr(dc_detrend_fp_numerators(dc_i128_load(pxx, e), dc_i128_load(pxs, e), css, inside[e] != 0)) : 0.f;
+}
+
 }  // namespace
+
+extern "C" int dc_roi_pixel_fold_segment(long* mom, int N, const int* row_off, const int* row_roi, int S, int R, const long* rmom, long len,
+                                         long mult, long* pooled_xx, long* pooled_xs, long* pooled_ss, int H, int W, dc_stream_t stream) {
+  DC_REQUIRE(mom && row_off && rmom && pooled_xx && pooled_xs && pooled_ss, DC_EINVAL, "dc_roi_pixel_fold_segment: null pointer");
+  DC_REQUIRE(N >= 0 && S >= 0 && R >= 0, DC_EINVAL, "dc_roi_pixel_fold_segment: negative count (N %d, S %d, R %d)", N, S, R);
+  DC_REQUIRE(row_roi || S == R, DC_EINVAL, "dc_roi_pixel_fold_segment: without row_roi every CSR row is an ROI, but S = %d and R = %d", S, R);
+  DC_REQUIRE((((uintptr_t)mom | (uintptr_t)rmom) & 7) == 0 && (((uintptr_t)row_off | (uintptr_t)row_roi) & 3) == 0 && dc_aligned16(pooled_xx) &&
+             dc_aligned16(pooled_xs) && dc_aligned16(pooled_ss), DC_EINVAL,
+             "dc_roi_pixel_fold_segment: misaligned buffer (the pooled words are 16-byte elements)");
+  DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "dc_roi_pixel_fold_segment: image %d x %d out of range", H, W);
+  DC_REQUIRE(len >= 1 && mult >= 1, DC_EINVAL, "dc_roi_pixel_fold_segment: a segment of %ld frames with mult %ld", len, mult);
+  DC_REQUIRE(dc_detrend_segment_ok(len, mult), DC_EUNSUP,
+             "dc_roi_pixel_fold_segment: len = %ld, mult = %ld: a segment beside others is limited to %d frames, one alone to %ld", len, mult,
+             DC_DETREND_MAX_SEGMENT, (long)DC_ROI_PIXEL_MAX_FRAMES);
+  DC_REQUIRE(dc_detrend_volume_ok(len, mult, (long)H * W), DC_EUNSUP,
+             "dc_roi_pixel_fold_segment: M = %ld on %d x %d: M * H * W is limited to 2^46", len * mult, H, W);
+  if (R == 0) return DC_OK;
+  hipLaunchKernelGGL(roi_trace_fold_segment_kernel, dim3((unsigned)dc_cdiv((long)R, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const int64_t*)rmom, R, (int64_t)len, (int64_t)mult, (int64_t*)pooled_ss);
+  DC_CHECK_LAUNCH("dc_roi_pixel_fold_segment(rois)");
+  if (N == 0 || S == 0) return DC_OK;
+  hipLaunchKernelGGL(roi_pixel_fold_segment_kernel, dim3((unsigned)S), dim3(kThreads), 0, (hipStream_t)stream, (int64_t*)mom, (long)N, row_off,
+                     row_roi, R, (const int64_t*)rmom, (int64_t)len, (int64_t)mult, (int64_t*)pooled_xx, (int64_t*)pooled_xs);
+  DC_CHECK_LAUNCH("dc_roi_pixel_fold_segment");
+  return DC_OK;
+}
+
+extern "C" int dc_roi_pixel_corr_pooled(const long* pooled_xx, const long* pooled_xs, const long* pooled_ss, int N, const int* row_off,
+                                        const int* row_roi, int S, int R, const int* inside, float* corr, dc_stream_t stream) {
+  DC_REQUIRE(pooled_xx && pooled_xs && pooled_ss && row_off && inside && corr, DC_EINVAL, "dc_roi_pixel_corr_pooled: null pointer");
+  DC_REQUIRE(N >= 0 && S >= 0 && R >= 0, DC_EINVAL, "dc_roi_pixel_corr_pooled: negative count (N %d, S %d, R %d)", N, S, R);
+  DC_REQUIRE(row_roi || S == R, DC_EINVAL, "dc_roi_pixel_corr_pooled: without row_roi every CSR row is an ROI, but S = %d and R = %d", S, R);
+  DC_REQUIRE(dc_aligned16(pooled_xx) && dc_aligned16(pooled_xs) && dc_aligned16(pooled_ss) &&
+             (((uintptr_t)row_off | (uintptr_t)row_roi | (uintptr_t)inside | (uintptr_t)corr) & 3) == 0, DC_EINVAL,
+             "dc_roi_pixel_corr_pooled: misaligned buffer (the pooled words are 16-byte elements)");
+  if (N == 0 || S == 0) return DC_OK;
+  hipLaunchKernelGGL(roi_pixel_corr_pooled_kernel, dim3((unsigned)S), dim3(kThreads), 0, (hipStream_t)stream, (const int64_t*)pooled_xx,
+                     (const int64_t*)pooled_xs, (const int64_t*)pooled_ss, (long)N, row_off, row_roi, R, inside, corr);
+  DC_CHECK_LAUNCH("dc_roi_pixel_corr_pooled");
+  return DC_OK;
+}
 
 extern "C" int dc_roi_pixel_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
                                        const int* row_roi, int S, int R, const long* sums, long ld, long* mom, int N, int H, int W,

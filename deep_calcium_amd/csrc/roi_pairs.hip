@@ -9,6 +9,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "pair_math.h"
+#include "detrend_math.h"
 
 namespace {
 
@@ -120,7 +121,99 @@ __global__ __launch_bounds__(kThreads) void roi_pair_corr_kernel(const int64_t* 
   }
 }
 
+// ---- detrended pairs: segment-pooled centred moments (include/dcunet.h, "Detrended correlations") --------------------------------
+// One workgroup per tile of the accumulate kernel's tile list, so the ROI, its square and the tile's bounds are found the same
+// way; the tile's kTile x kTile entries are walked row by row, consecutive lanes on consecutive 16-byte pooled words.  Entry
+// (i, j), i <= j, is owned by one thread of one workgroup: it adds mult * (len * g_ij - a_i a_j) to the pooled word and clears
+// g_ij for the next segment.  a is read by every tile of the ROI, so it is cleared behind the kernel, not in it.
+__global__ __launch_bounds__(kThreads) void roi_pair_fold_segment_kernel(const int64_t* __restrict__ a, int64_t* __restrict__ g,
+                                                                        const int* __restrict__ roi_off, const int64_t* __restrict__ goff,
+                                                                        const int* __restrict__ tiles, int R, long P, long G, int64_t len,
+                                                                        int64_t mult, int64_t* __restrict__ pooled) {
+  const int* tile = tiles + 3L * blockIdx.x;
+  const int r = tile[0], ti = tile[1], tj = tile[2];
+  if (r < 0 || r >= R || ti < 0 || tj < ti) return;
+  const long p0 = roi_off[r], p1 = roi_off[r + 1], go = goff[r];
+  if (!dc_pair_roi_ok(p0, p1, go, P, G, DC_ROI_PAIR_MAX_AREA)) return;
+  const long k = p1 - p0;
+  if ((long)tj * kTile >= k) return;
+  for (int e = threadIdx.x; e < kTile * kTile; e += kThreads) {
+    const long i = (long)ti * kTile + e / kTile, j = (long)tj * kTile + e % kTile;
+    if (i >= k || j >= k || i > j) continue;         // the lower triangle is never touched
+    const long w = go + i * k + j;
+    dc_i128_store(pooled, w, dc_i128_add(dc_i128_load(pooled, w), dc_detrend_term(len, mult, g[w], a[p0 + i], a[p0 + j])));
+    g[w] = 0;
+  }
+}
+
+// pooled numerators -> the float32 matrix, in the form of roi_pair_corr_kernel
+__global__ __launch_bounds__(kThreads) void roi_pair_corr_pooled_kernel(const int64_t* __restrict__ pooled, const int* __restrict__ roi_off,
+                                                                       const int64_t* __restrict__ goff, long P, long G,
+                                                                       float* __restrict__ corr) {
+  const int r = blockIdx.x;
+  const long p0 = roi_off[r], p1 = roi_off[r + 1], go = goff[r];
+  if (!dc_pair_roi_ok(p0, p1, go, P, G, DC_ROI_PAIR_MAX_AREA)) return;
+  const long k = p1 - p0;
+  for (long i = blockIdx.y; i < k; i += gridDim.y) {
+    DcFpNum n;
+    n.cxx = dc_i128_load(pooled, go + i * k + i);
+    for (long j = threadIdx.x; j < k; j += kThreads) {
+      const long lo = i < j ? i : j, hi = i < j ? j : i;
+      n.cxl = dc_i128_load(pooled, go + lo * k + hi);
+      n.cll = dc_i128_load(pooled, go + j * k + j);
+      corr[go + i * k + j] = dc_fp_corr(n);
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int dc_roi_pair_fold_segment(long* a, long* g, const int* roi_off, const long* goff, const int* tiles, long ntiles, int R, int P,
+                                        long G, long len, long mult, long* pooled, dc_stream_t stream) {
+  DC_REQUIRE(a && g && roi_off && goff && tiles && pooled, DC_EINVAL, "dc_roi_pair_fold_segment: null pointer");
+  DC_REQUIRE(ntiles >= 0 && R >= 0 && P >= 0 && G >= 0, DC_EINVAL, "dc_roi_pair_fold_segment: negative count (ntiles %ld, R %d, P %d, G %ld)",
+             ntiles, R, P, G);
+  DC_REQUIRE((((uintptr_t)roi_off | (uintptr_t)tiles) & 3) == 0 && (((uintptr_t)goff | (uintptr_t)a | (uintptr_t)g) & 7) == 0 &&
+             dc_aligned16(pooled), DC_EINVAL, "dc_roi_pair_fold_segment: misaligned buffer (the pooled words are 16-byte elements)");
+  DC_REQUIRE(len >= 1 && mult >= 1, DC_EINVAL, "dc_roi_pair_fold_segment: a segment of %ld frames with mult %ld", len, mult);
+  DC_REQUIRE(dc_detrend_segment_ok(len, mult), DC_EUNSUP,
+             "dc_roi_pair_fold_segment: len = %ld, mult = %ld: a segment beside others is limited to %d frames, one alone to %ld", len, mult,
+             DC_DETREND_MAX_SEGMENT, (long)DC_ROI_PIXEL_MAX_FRAMES);
+  DC_REQUIRE(G <= DC_ROI_PAIR_MAX_STATE, DC_EUNSUP, "dc_roi_pair_fold_segment: G = %ld words of state: limited to 2^27 = %ld", G,
+             (long)DC_ROI_PAIR_MAX_STATE);
+  DC_REQUIRE(G <= (long)DC_ROI_PAIR_MAX_AREA * P, DC_EUNSUP,
+             "dc_roi_pair_fold_segment: G = %ld exceeds %d * P = %ld: an ROI has more than %d pixels", G, DC_ROI_PAIR_MAX_AREA,
+             (long)DC_ROI_PAIR_MAX_AREA * P, DC_ROI_PAIR_MAX_AREA);
+  DC_REQUIRE(ntiles < (1L << 31), DC_EUNSUP, "dc_roi_pair_fold_segment: %ld tiles: one workgroup each, limited to 2^31 - 1", ntiles);
+  DC_REQUIRE(ntiles <= (long)R * dc_pair_tiles_of(DC_ROI_PAIR_MAX_AREA, DC_ROI_PAIR_TILE), DC_EUNSUP,
+             "dc_roi_pair_fold_segment: %ld tiles for %d ROIs: an ROI of at most %d pixels has %ld", ntiles, R, DC_ROI_PAIR_MAX_AREA,
+             (long)dc_pair_tiles_of(DC_ROI_PAIR_MAX_AREA, DC_ROI_PAIR_TILE));
+  if (ntiles == 0 || R == 0 || P == 0 || G == 0) return DC_OK;
+  hipLaunchKernelGGL(roi_pair_fold_segment_kernel, dim3((unsigned)ntiles), dim3(kThreads), 0, (hipStream_t)stream, (const int64_t*)a, (int64_t*)g,
+                     roi_off, (const int64_t*)goff, tiles, R, (long)P, G, (int64_t)len, (int64_t)mult, (int64_t*)pooled);
+  DC_CHECK_LAUNCH("dc_roi_pair_fold_segment");
+  const hipError_t e = hipMemsetAsync(a, 0, 8 * (size_t)P, (hipStream_t)stream);      // behind the kernel: every tile of an ROI reads its a
+  DC_REQUIRE(e == hipSuccess, DC_EHIP, "dc_roi_pair_fold_segment: hipMemsetAsync: %s", hipGetErrorString(e));
+  return DC_OK;
+}
+
+extern "C" int dc_roi_pair_corr_pooled(const long* pooled, const int* roi_off, const long* goff, int R, int P, long G, float* corr,
+                                       dc_stream_t stream) {
+  DC_REQUIRE(pooled && roi_off && goff && corr, DC_EINVAL, "dc_roi_pair_corr_pooled: null pointer");
+  DC_REQUIRE(R >= 0 && P >= 0 && G >= 0, DC_EINVAL, "dc_roi_pair_corr_pooled: negative count (R %d, P %d, G %ld)", R, P, G);
+  DC_REQUIRE(dc_aligned16(pooled) && (((uintptr_t)goff) & 7) == 0 && (((uintptr_t)roi_off | (uintptr_t)corr) & 3) == 0, DC_EINVAL,
+             "dc_roi_pair_corr_pooled: misaligned buffer (the pooled words are 16-byte elements)");
+  DC_REQUIRE(G <= DC_ROI_PAIR_MAX_STATE, DC_EUNSUP, "dc_roi_pair_corr_pooled: G = %ld words of state: limited to 2^27 = %ld", G,
+             (long)DC_ROI_PAIR_MAX_STATE);
+  DC_REQUIRE(G <= (long)DC_ROI_PAIR_MAX_AREA * P, DC_EUNSUP,
+             "dc_roi_pair_corr_pooled: G = %ld exceeds %d * P = %ld: an ROI has more than %d pixels", G, DC_ROI_PAIR_MAX_AREA,
+             (long)DC_ROI_PAIR_MAX_AREA * P, DC_ROI_PAIR_MAX_AREA);
+  if (R == 0 || P == 0 || G == 0) return DC_OK;
+  hipLaunchKernelGGL(roi_pair_corr_pooled_kernel, dim3((unsigned)R, kCorrRows), dim3(kThreads), 0, (hipStream_t)stream, (const int64_t*)pooled,
+                     roi_off, (const int64_t*)goff, (long)P, G, corr);
+  DC_CHECK_LAUNCH("dc_roi_pair_corr_pooled");
+  return DC_OK;
+}
 
 extern "C" int dc_roi_pair_accumulate(const void* frames, int is_unsigned, int tc, const int* roi_off, const int* roi_pix, const long* goff,
                                       const int* tiles, long ntiles, int R, long* a, long* g, int P, long G, int H, int W,

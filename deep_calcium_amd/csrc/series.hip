@@ -9,6 +9,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "series_math.h"
+#include "detrend_math.h"
 
 namespace {
 
@@ -181,6 +182,69 @@ __global__ __launch_bounds__(kThreads) void series_finalize_kernel(const int64_t
     const long owner = (dy > 0 || (dy == 0 && dx > 0)) ? p : q;
     const DcI128 num = central2(T, xy[slot * HW + owner], sx, sy);
     acc += dc_i128_to_f64(num) / sqrt(vpd * dc_i128_to_f64(vq));
+  }
+  corr[p] = cnt ? (float)(acc / (double)cnt) : 0.f;
+}
+
+// ---- detrended summaries: segment-pooled centred moments (the definitions are in include/dcunet.h, "Detrended correlations") ----------
+// At the end of a segment of `len` frames the segment's sums are folded into the pooled numerators: one lane per pixel, which
+// alone owns the pixel's pooled words (variance, the four pairs it is the EARLIER pixel of, total sum and maximum).  The
+// neighbours' segment sums are only read, and nothing of the segment state is written: the next segment's first accumulate
+// (t0 == 0) initialises it.  A neighbour outside the image contributes nothing: its slot stays 0.
+__global__ __launch_bounds__(kThreads) void series_fold_segment_kernel(const int64_t* __restrict__ sum, const int64_t* __restrict__ sumsq,
+                                                                      const int64_t* __restrict__ xy, const int* __restrict__ vmax,
+                                                                      int64_t len, int64_t mult, int64_t* __restrict__ pvar,
+                                                                      int64_t* __restrict__ pcov, int64_t* __restrict__ sum_total,
+                                                                      int* __restrict__ vmax_total, int H, int W) {
+  const long HW = (long)H * W, p = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (p >= HW) return;
+  const int y = (int)(p / W), x = (int)(p % W);
+  const int64_t sx = sum[p];
+  dc_i128_store(pvar, p, dc_i128_add(dc_i128_load(pvar, p), dc_detrend_term(len, mult, sumsq[p], sx, sx)));
+  sum_total[p] += sx;
+  const int vm = vmax[p], vt = vmax_total[p];
+  vmax_total[p] = vm > vt ? vm : vt;
+  if (!xy) return;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {                      // slot 0 right, 1 down, 2 down-right, 3 down-left
+    const int qy = y + (j > 0), qx = x + (j == 0 || j == 2) - (j == 3);
+    if (qy >= H || qx < 0 || qx >= W) continue;
+    const long q = (long)qy * W + qx, e = j * HW + p;
+    dc_i128_store(pcov, e, dc_i128_add(dc_i128_load(pcov, e), dc_detrend_term(len, mult, xy[e], sx, sum[q])));
+  }
+}
+
+// pooled numerators -> float32 images: the neighbour rule and the summation order of series_finalize_kernel, the numerators read
+// instead of formed
+__global__ __launch_bounds__(kThreads) void series_finalize_pooled_kernel(const int64_t* __restrict__ pvar, const int64_t* __restrict__ pcov,
+                                                                         const int64_t* __restrict__ sum_total, float* __restrict__ mean,
+                                                                         float* __restrict__ sd, float* __restrict__ corr, int H, int W,
+                                                                         int64_t M, int64_t T) {
+  const long HW = (long)H * W, p = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (p >= HW) return;
+  const int y = (int)(p / W), x = (int)(p % W);
+  const DcI128 vp = dc_i128_load(pvar, p);
+  if (mean) mean[p] = (float)((double)sum_total[p] / (double)T);
+  if (sd) sd[p] = (float)sqrt(dc_detrend_var(vp, M, T));
+  if (!corr) return;
+  const double vpd = dc_i128_to_f64(vp);
+  const bool flat = !dc_i128_is_positive(vp);
+  double acc = 0.0;
+  int cnt = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int dy = j < 3 ? -1 : (j < 5 ? 0 : 1);
+    const int dx = j < 3 ? j - 1 : (j == 3 ? -1 : (j == 4 ? 1 : j - 6));
+    const int qy = y + dy, qx = x + dx;
+    if (qy < 0 || qy >= H || qx < 0 || qx >= W) continue;
+    ++cnt;
+    if (flat) continue;
+    const long q = (long)qy * W + qx;
+    const DcI128 vq = dc_i128_load(pvar, q);
+    if (!dc_i128_is_positive(vq)) continue;
+    const int slot = dy == 0 ? 0 : (dx == 0 ? 1 : (dx == dy ? 2 : 3));
+    const long owner = (dy > 0 || (dy == 0 && dx > 0)) ? p : q;
+    acc += dc_i128_to_f64(dc_i128_load(pcov, slot * HW + owner)) / sqrt(vpd * dc_i128_to_f64(vq));
   }
   corr[p] = cnt ? (float)(acc / (double)cnt) : 0.f;
 }
@@ -392,6 +456,48 @@ extern "C" int dc_series_finalize(const long* sum, const long* sumsq, const long
   hipLaunchKernelGGL(series_finalize_kernel, dim3((unsigned)dc_cdiv((long)H * W, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
                      (const int64_t*)sum, (const int64_t*)sumsq, (const int64_t*)xy, mean, sdev, corr, H, W, (int64_t)T);
   DC_CHECK_LAUNCH("dc_series_finalize");
+  return DC_OK;
+}
+
+extern "C" int dc_series_fold_segment(const long* sum, const long* sumsq, const long* xy, const int* vmax, long len, long mult,
+                                      long* pooled_var, long* pooled_cov, long* sum_total, int* vmax_total, int H, int W,
+                                      dc_stream_t stream) {
+  DC_REQUIRE(sum && sumsq && vmax && pooled_var && sum_total && vmax_total, DC_EINVAL, "dc_series_fold_segment: null pointer");
+  DC_REQUIRE((xy == nullptr) == (pooled_cov == nullptr), DC_EINVAL, "dc_series_fold_segment: xy and pooled_cov come as a pair");
+  DC_REQUIRE((((uintptr_t)sum | (uintptr_t)sumsq | (uintptr_t)xy | (uintptr_t)sum_total) & 7) == 0 &&
+             (((uintptr_t)vmax | (uintptr_t)vmax_total) & 3) == 0 && dc_aligned16(pooled_var) && dc_aligned16(pooled_cov), DC_EINVAL,
+             "dc_series_fold_segment: misaligned state buffer (the pooled words are 16-byte elements)");
+  DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "dc_series_fold_segment: image %d x %d out of range", H, W);
+  DC_REQUIRE(len >= 1 && mult >= 1, DC_EINVAL, "dc_series_fold_segment: a segment of %ld frames with mult %ld", len, mult);
+  DC_REQUIRE(dc_detrend_segment_ok(len, mult), DC_EUNSUP,
+             "dc_series_fold_segment: len = %ld, mult = %ld: a segment beside others is limited to %d frames, one alone to %ld", len, mult,
+             DC_DETREND_MAX_SEGMENT, (long)DC_SERIES_MAX_FRAMES);
+  DC_REQUIRE(dc_detrend_volume_ok(len, mult, (long)H * W), DC_EUNSUP, "dc_series_fold_segment: M = %ld on %d x %d: M * H * W is limited to 2^46",
+             len * mult, H, W);
+  hipLaunchKernelGGL(series_fold_segment_kernel, dim3((unsigned)dc_cdiv((long)H * W, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const int64_t*)sum, (const int64_t*)sumsq, (const int64_t*)xy, vmax, (int64_t)len, (int64_t)mult, (int64_t*)pooled_var,
+                     (int64_t*)pooled_cov, (int64_t*)sum_total, vmax_total, H, W);
+  DC_CHECK_LAUNCH("dc_series_fold_segment");
+  return DC_OK;
+}
+
+extern "C" int dc_series_finalize_pooled(const long* pooled_var, const long* pooled_cov, const long* sum_total, float* mean, float* sdev,
+                                         float* corr, int H, int W, long M, long T, dc_stream_t stream) {
+  DC_REQUIRE(pooled_var && dc_aligned16(pooled_var) && dc_aligned16(pooled_cov) && (((uintptr_t)sum_total) & 7) == 0, DC_EINVAL,
+             "dc_series_finalize_pooled: null or misaligned state buffer (the pooled words are 16-byte elements)");
+  DC_REQUIRE((((uintptr_t)mean | (uintptr_t)sdev | (uintptr_t)corr) & 3) == 0, DC_EINVAL, "dc_series_finalize_pooled: misaligned image");
+  DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "dc_series_finalize_pooled: image %d x %d out of range", H, W);
+  DC_REQUIRE(T > 0 && M > 0, DC_EINVAL, "dc_series_finalize_pooled: M = %ld, T = %ld", M, T);
+  DC_REQUIRE(T <= DC_SERIES_MAX_FRAMES && M <= DC_SERIES_MAX_FRAMES, DC_EUNSUP,
+             "dc_series_finalize_pooled: M = %ld, T = %ld: each is limited to %ld", M, T, (long)DC_SERIES_MAX_FRAMES);
+  DC_REQUIRE(dc_detrend_volume_ok(M, 1, (long)H * W), DC_EUNSUP, "dc_series_finalize_pooled: M = %ld on %d x %d: M * H * W is limited to 2^46",
+             M, H, W);
+  DC_REQUIRE(corr == nullptr || pooled_cov != nullptr, DC_EINVAL, "dc_series_finalize_pooled: corr needs the pooled_cov state");
+  DC_REQUIRE(mean == nullptr || sum_total != nullptr, DC_EINVAL, "dc_series_finalize_pooled: mean needs the sum_total state");
+  hipLaunchKernelGGL(series_finalize_pooled_kernel, dim3((unsigned)dc_cdiv((long)H * W, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const int64_t*)pooled_var, (const int64_t*)pooled_cov, (const int64_t*)sum_total, mean, sdev, corr, H, W, (int64_t)M,
+                     (int64_t)T);
+  DC_CHECK_LAUNCH("dc_series_finalize_pooled");
   return DC_OK;
 }
 

@@ -23,6 +23,10 @@ A pixel or a trace that is constant in time (a single frame included) and the pi
 exactly 0 here; numpy divides 0 by 0 there.  The map cannot split one ROI into two (both halves correlate with the summed trace,
 and refine_rois keeps the larger): roi_pairs.py does, from the correlation of the ROI's pixels with each other.
 
+detrend_frames=L: pixel and trace are correlated within segments of L frames and the segments pooled (series.detrend_plan,
+dc_roi_pixel_fold_segment, dc_roi_pixel_corr_pooled), so that bleaching and drift common to all pixels do not push every entry of
+the map towards 1.  Piecewise-constant detrending: a trend inside a segment stays.
+
 Importing this module needs neither torch nor the GPU; constructing a RoiFootprints does (there is no CPU fallback).
 """
 import numpy as np
@@ -125,9 +129,14 @@ class RoiFootprints(object):
     """Owns the device state of one recording's footprint maps and, through a RoiTraceExtractor of its own, of its traces; feed()
     the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, rois, halo=2, device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
+    def __init__(self, shape, n_frames, dtype, rois, halo=2, device=None, chunk_frames=None, shifts=None, fine_shifts=None, detrend_frames=None,
+                 bidi=0):
         """halo: the Chebyshev radius, in [0, 16], by which every ROI's support reaches beyond its own pixels.  Everything else: as
-        for RoiTraceExtractor (bidi, then shifts / fine_shifts move or interpolate each chunk before BOTH kernels read it)."""
+        for RoiTraceExtractor (bidi, then shifts / fine_shifts move or interpolate each chunk before BOTH kernels read it).
+        detrend_frames: None, or an integer L in [2, 4096]: the maps are formed from centred moments pooled over the segments of
+        series.detrend_plan(n_frames, L) (dc_roi_trace_moments over the segment's columns and dc_roi_pixel_fold_segment at every
+        segment's end, dc_roi_pixel_corr_pooled): a trend that is constant within a segment is removed from pixel and trace
+        alike.  L > n_frames / 2 is one segment: the bits of None.  The traces of the same pass are not detrended."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         halo = _check_halo(halo)
@@ -136,6 +145,10 @@ class RoiFootprints(object):
             raise ValueError('n_frames must be >= 1 with n_frames * H * W <= 2**46, not %d' % n_frames)
         if n_frames > MAX_FRAMES:
             raise ValueError('n_frames must be <= 2**31 - 1, not %d' % n_frames)
+        self._seg = None
+        if detrend_frames is not None:
+            from .series import _Segments, _check_detrend_frames
+            self._seg = _Segments(n_frames, _check_detrend_frames(detrend_frames, n_frames, shape))
         pixels = _roi_pixels(rois, shape)
         flat, inside = _support(pixels, shape, halo)
         self._coords = [np.stack([f // shape[1], f % shape[1]], 1).astype(np.int64) for f in flat]
@@ -158,6 +171,11 @@ class RoiFootprints(object):
         self._flags = torch.from_numpy(np.concatenate(inside).astype(np.int32)).to(dev)
         self._rows = len(row_roi)
         self._mom = torch.zeros((4, self.n_entries), dtype=torch.int64, device=dev)      # a, b, c_lo, c_hi: the kernel adds
+        if self._seg is not None:        # pooled Cxx, Cxs per entry and Css per ROI: 16-byte {lo, hi} words; the segment's u, w
+            self._pxx = torch.zeros((self.n_entries, 2), dtype=torch.int64, device=dev)
+            self._pxs = torch.zeros((self.n_entries, 2), dtype=torch.int64, device=dev)
+            self._pss = torch.zeros((self.n_rois, 2), dtype=torch.int64, device=dev)
+            self._rmom = torch.empty((3, self.n_rois), dtype=torch.int64, device=dev)
         self._corr = None
 
     @property
@@ -165,6 +183,20 @@ class RoiFootprints(object):
         return self._ext.fed
 
     def _accumulate(self, fp, tc, t0, st):
+        H, W = self.shape
+        if self._seg is not None:        # cut at the segment boundaries; a segment that ends is folded, which leaves mom zero
+            for k, m, _, ends in self._seg.cut(t0, tc):
+                self._accumulate_frames(fp + k * H * W * 2, m, t0 + k, st)
+                if ends is not None:
+                    self.L.dc_roi_trace_moments(self._ext.sums.data_ptr() + 8 * ends[0], self.n_frames, self.n_rois, ends[1],
+                                                self._rmom.data_ptr(), st)
+                    self.L.dc_roi_pixel_fold_segment(self._mom.data_ptr(), self.n_entries, self._row_off.data_ptr(), self._row_roi.data_ptr(),
+                                                     self._rows, self.n_rois, self._rmom.data_ptr(), ends[1], ends[2], self._pxx.data_ptr(),
+                                                     self._pxs.data_ptr(), self._pss.data_ptr(), H, W, st)
+            return
+        self._accumulate_frames(fp, tc, t0, st)
+
+    def _accumulate_frames(self, fp, tc, t0, st):
         H, W = self.shape
         ext = self._ext
         self.L.dc_roi_pixel_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, t0, self._row_off.data_ptr(),
@@ -201,12 +233,17 @@ class RoiFootprints(object):
             torch, ext = self._torch, self._ext
             with torch.cuda.device(self.device):
                 st = torch.cuda.current_stream(self.device).cuda_stream
-                rmom = torch.empty((3, self.n_rois), dtype=torch.int64, device=self.device)
                 corr = torch.empty((self.n_entries,), dtype=torch.float32, device=self.device)
-                self.L.dc_roi_trace_moments(ext.sums.data_ptr(), self.n_frames, self.n_rois, self.n_frames, rmom.data_ptr(), st)
-                self.L.dc_roi_pixel_corr(self._mom.data_ptr(), self.n_entries, self._row_off.data_ptr(), self._row_roi.data_ptr(),
-                                         self._rows, self.n_rois, self._flags.data_ptr(), rmom.data_ptr(), self.n_frames,
-                                         corr.data_ptr(), st)
+                if self._seg is not None:
+                    self.L.dc_roi_pixel_corr_pooled(self._pxx.data_ptr(), self._pxs.data_ptr(), self._pss.data_ptr(), self.n_entries,
+                                                    self._row_off.data_ptr(), self._row_roi.data_ptr(), self._rows, self.n_rois,
+                                                    self._flags.data_ptr(), corr.data_ptr(), st)
+                else:
+                    rmom = torch.empty((3, self.n_rois), dtype=torch.int64, device=self.device)
+                    self.L.dc_roi_trace_moments(ext.sums.data_ptr(), self.n_frames, self.n_rois, self.n_frames, rmom.data_ptr(), st)
+                    self.L.dc_roi_pixel_corr(self._mom.data_ptr(), self.n_entries, self._row_off.data_ptr(), self._row_roi.data_ptr(),
+                                             self._rows, self.n_rois, self._flags.data_ptr(), rmom.data_ptr(), self.n_frames,
+                                             corr.data_ptr(), st)
             self._corr = corr.cpu().numpy()
         return self._corr
 
@@ -216,6 +253,11 @@ class RoiFootprints(object):
         _check_kind(kind)
         if self.fed != self.n_frames:
             raise ValueError('result() after %d of %d frames' % (self.fed, self.n_frames))
+        if kind == 'moments' and self._seg is not None:      # the pooled numerators, exact, with M: integers before any float
+            from .series import _pooled_ints
+            xx, xs = _pooled_ints(self._pxx.cpu().numpy()), _pooled_ints(self._pxs.cpu().numpy())
+            ss = _pooled_ints(self._pss.cpu().numpy())
+            return [dict(Cxx=x, Cxs=y, Css=ss[r], M=self._seg.M) for r, (x, y) in enumerate(zip(self._split(xx), self._split(xs)))]
         if kind == 'moments':
             m = self._mom.cpu().numpy()
             a, b = m[0].astype(object), m[1].astype(object)
@@ -228,13 +270,17 @@ class RoiFootprints(object):
 
 
 def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None,
-                          bin_frames=None, bidi=0):
+                          bin_frames=None, detrend_frames=None, bidi=0):
     """-> (corr, coords, inside) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk:
     the recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: None, or an integer b in
     [1, 64]: the maps are those of the T // b rounded means of b consecutive corrected frames, correlated with the ROI traces of
-    that binned recording (series.TemporalBinner; the trailing T % b frames are dropped, 1 gives what None gives)."""
-    from .series import _check_bin_frames, _feed_binned, _open_series
+    that binned recording (series.TemporalBinner; the trailing T % b frames are dropped, 1 gives what None gives).  detrend_frames: None, or an
+    integer L in [2, 4096]: the correlations are pooled over segments of L frames (RoiFootprints); binning comes first and L counts
+    binned frames.  Results at different L are not comparable with each other or with None."""
+    from .series import _check_bin_frames, _check_detrend_frames, _feed_binned, _open_series
     _check_halo(halo)
+    if detrend_frames is not None:
+        _check_detrend_frames(detrend_frames)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     if bin_frames is not None:
@@ -246,12 +292,13 @@ def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None
         T = int(frames.shape[0])
         if bin_frames is None:
             fp = RoiFootprints(tuple(frames.shape[1:]), T, frames.dtype, rois, halo=halo, device=device, chunk_frames=chunk_frames,
-                               shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
+                               shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
             for a in range(0, T, fp.chunk_frames):
                 fp.feed(np.asarray(frames[a:a + fp.chunk_frames]))
         else:
             fp = _feed_binned(frames, bin_frames, lambda n, dev: RoiFootprints(tuple(frames.shape[1:]), n, frames.dtype, rois, halo=halo,
-                                                                               device=dev, chunk_frames=chunk_frames),
+                                                                               device=dev, chunk_frames=chunk_frames,
+                                                                               detrend_frames=detrend_frames),
                               device, chunk_frames, shifts, fine_shifts, bidi)
         out = fp.result('corr'), fp.support(), fp.inside()
     finally:

@@ -41,6 +41,12 @@ two cells are split in 38 scenes with no pixel misassigned or dropped (the other
 and a single cell (uniform or with a Gaussian profile) and a static region never are; at amplitude 40 / sigma 40 the two cells are
 split in 12 of 40 scenes, at 30 / 60 in none.
 
+A recording that bleaches or drifts: a decay common to all pixels pushes every correlation towards 1 and hides the two groups (on
+the scene above at T = 1024, a decay to half the brightness takes the rule from 40 of 40 scenes to 0).  detrend_frames=L correlates
+within segments of L frames and pools them (series.detrend_plan, dc_roi_pair_fold_segment, dc_roi_pair_corr_pooled): all 40 come
+back at L = 128 with no pixel wrong.  Short segments also remove real slow covariance (at amplitude 40 / sigma 40 without decay: 21
+scenes with None, 15 at L = 128, 8 at L = 64): use the longest L that removes the trend.
+
 Importing this module needs neither torch nor the GPU; constructing a RoiPairCorr does (there is no CPU fallback).
 """
 import numpy as np
@@ -87,10 +93,15 @@ class RoiPairCorr(object):
     """Owns the device state of one recording's pixel-pair moments and, through a RoiTraceExtractor of its own, of its traces;
     feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
+    def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None, fine_shifts=None, detrend_frames=None,
+                 bidi=0):
         """rois: every form rois_to_csr takes; each ROI at most MAX_AREA pixels, all together at most MAX_STATE matrix entries
         (ValueError naming the ROI).  Everything else: as for RoiTraceExtractor (bidi, then shifts / fine_shifts move or interpolate each
-        chunk before BOTH kernels read it)."""
+        chunk before BOTH kernels read it).
+        detrend_frames: None, or an integer L in [2, 4096]: the matrices are formed from centred moments pooled over the segments
+        of series.detrend_plan(n_frames, L) (dc_roi_pair_fold_segment at every segment's end, dc_roi_pair_corr_pooled): a trend
+        that is constant within a segment is removed.  L > n_frames / 2 is one segment: the bits of None.  The traces of the same
+        pass are not detrended."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         n_frames = int(n_frames)
@@ -98,6 +109,10 @@ class RoiPairCorr(object):
             raise ValueError('n_frames must be >= 1 with n_frames * H * W <= 2**46, not %d' % n_frames)
         if n_frames > MAX_FRAMES:
             raise ValueError('n_frames must be <= 2**31 - 1, not %d' % n_frames)
+        self._seg = None
+        if detrend_frames is not None:
+            from .series import _Segments, _check_detrend_frames
+            self._seg = _Segments(n_frames, _check_detrend_frames(detrend_frames, n_frames, shape))
         pixels = _roi_pixels(rois, shape)
         roi_off, goff, tiles, G = pair_layout([len(p) for p in pixels])
         self._pixels = [np.stack([p.astype(np.int64) // shape[1], p.astype(np.int64) % shape[1]], 1) for p in pixels]
@@ -117,6 +132,7 @@ class RoiPairCorr(object):
         self._tiles = torch.from_numpy(np.ascontiguousarray(tiles)).to(dev)
         self._a = torch.zeros((self.n_pixels,), dtype=torch.int64, device=dev)           # the kernel adds
         self._g = torch.zeros((G,), dtype=torch.int64, device=dev)
+        self._pooled = torch.zeros((G, 2), dtype=torch.int64, device=dev) if self._seg is not None else None      # 16-byte {lo, hi} words
         self._corr = None
 
     @property
@@ -124,6 +140,18 @@ class RoiPairCorr(object):
         return self._ext.fed
 
     def _accumulate(self, fp, tc, t0, st):
+        H, W = self.shape
+        if self._seg is not None:        # cut at the segment boundaries; a segment that ends is folded, which leaves a and g zero
+            for k, m, _, ends in self._seg.cut(t0, tc):
+                self._accumulate_frames(fp + k * H * W * 2, m, st)
+                if ends is not None:
+                    self.L.dc_roi_pair_fold_segment(self._a.data_ptr(), self._g.data_ptr(), self._roi_off.data_ptr(), self._goff.data_ptr(),
+                                                    self._tiles.data_ptr(), self.n_tiles, self.n_rois, self.n_pixels, self.n_state,
+                                                    ends[1], ends[2], self._pooled.data_ptr(), st)
+            return
+        self._accumulate_frames(fp, tc, st)
+
+    def _accumulate_frames(self, fp, tc, st):
         H, W = self.shape
         self.L.dc_roi_pair_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, self._roi_off.data_ptr(), self._roi_pix.data_ptr(),
                                       self._goff.data_ptr(), self._tiles.data_ptr(), self.n_tiles, self.n_rois, self._a.data_ptr(),
@@ -157,19 +185,31 @@ class RoiPairCorr(object):
             with torch.cuda.device(self.device):
                 st = torch.cuda.current_stream(self.device).cuda_stream
                 corr = torch.empty((self.n_state,), dtype=torch.float32, device=self.device)
-                self.L.dc_roi_pair_corr(self._a.data_ptr(), self._g.data_ptr(), self._roi_off.data_ptr(), self._goff.data_ptr(), self.n_rois,
-                                        self.n_pixels, self.n_state, self.n_frames, corr.data_ptr(), st)
+                if self._seg is not None:
+                    self.L.dc_roi_pair_corr_pooled(self._pooled.data_ptr(), self._roi_off.data_ptr(), self._goff.data_ptr(), self.n_rois,
+                                                   self.n_pixels, self.n_state, corr.data_ptr(), st)
+                else:
+                    self.L.dc_roi_pair_corr(self._a.data_ptr(), self._g.data_ptr(), self._roi_off.data_ptr(), self._goff.data_ptr(), self.n_rois,
+                                            self.n_pixels, self.n_state, self.n_frames, corr.data_ptr(), st)
             self._corr = corr.cpu().numpy()
         return self._corr
 
     def result(self, kind='corr'):
         """'corr': a list of R float32 (k, k) matrices aligned with pixels(); 'moments': per ROI a dict of object arrays of exact
-        Python ints, a (k,) and g (k, k), g symmetric (the device keeps i <= j; the other half is mirrored here)."""
+        Python ints, a (k,) and g (k, k), g symmetric (the device keeps i <= j; the other half is mirrored here) -- with
+        detrend_frames: dict(N (k, k) symmetric, the pooled numerators; M)."""
         _check_kind(kind)
         if self.fed != self.n_frames:
             raise ValueError('result() after %d of %d frames' % (self.fed, self.n_frames))
         if kind == 'corr':
             return [c.copy() for c in self._squares(self._corr_flat())]
+        if self._seg is not None:        # the pooled numerators N(x_i, x_j), exact, with M: integers before any float
+            from .series import _pooled_ints
+            out = []
+            for n in self._squares(_pooled_ints(self._pooled.cpu().numpy())):
+                n = np.triu(n)
+                out.append(dict(N=n + np.triu(n, 1).T, M=self._seg.M))
+            return out
         a = self._a.cpu().numpy().astype(object)
         out = []
         for r, g in enumerate(self._squares(self._g.cpu().numpy())):
@@ -265,16 +305,19 @@ def split_rois(pixels, corr, shape, min_gap=0.1, min_area=8, iterations=16):
 
 
 def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None,
-                         bin_frames=None, bidi=0):
+                         bin_frames=None, detrend_frames=None, bidi=0):
     """-> (corr, pixels) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
     recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: None, or an integer b in
     [1, 64]: the matrices are those of the T // b rounded means of b consecutive corrected frames (series.TemporalBinner; the
-    trailing T % b frames are dropped, 1 gives what None gives)."""
-    from .series import _check_bin_frames, _feed_binned, _open_series
+    trailing T % b frames are dropped, 1 gives what None gives).  detrend_frames: None, or an integer L in [2, 4096]: the
+    correlations are pooled over segments of L frames (RoiPairCorr); binning comes first and L counts binned frames."""
+    from .series import _check_bin_frames, _check_detrend_frames, _feed_binned, _open_series
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     if bin_frames is not None:
         _check_bin_frames(bin_frames)
+    if detrend_frames is not None:
+        _check_detrend_frames(detrend_frames)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
@@ -282,12 +325,12 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
         T = int(frames.shape[0])
         if bin_frames is None:
             pc = RoiPairCorr(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                             fine_shifts=fine_shifts, bidi=bidi)
+                             fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
             for a in range(0, T, pc.chunk_frames):
                 pc.feed(np.asarray(frames[a:a + pc.chunk_frames]))
         else:
             pc = _feed_binned(frames, bin_frames, lambda n, dev: RoiPairCorr(tuple(frames.shape[1:]), n, frames.dtype, rois, device=dev,
-                                                                             chunk_frames=chunk_frames),
+                                                                             chunk_frames=chunk_frames, detrend_frames=detrend_frames),
                               device, chunk_frames, shifts, fine_shifts, bidi)
         out = pc.result('corr'), pc.pixels()
     finally:
@@ -297,13 +340,18 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
 
 
 def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, source='series/raw', device=None, chunk_frames=None,
-                      shifts=None, fine_shifts=None, bin_frames=None, bidi=0):
+                      shifts=None, fine_shifts=None, bin_frames=None, detrend_frames=None, bidi=0):
     """-> (new_rois, origin, gaps) of split_rois for `rois` over `source` of a dataset file, in one pass over the recording.  ROIs
     of more than MAX_AREA or fewer than 2 * min_area pixels are not sent to the device and come back unchanged (gap NaN); when
     no ROI is left the recording is not read at all.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: as
     for roi_pair_corr_device -- the pixel noise of a mean of b frames is lower by sqrt(b), which is what lets the rule part cells
-    it cannot part frame by frame; keep T // b well above 100, chance correlations split static regions below that."""
-    from .series import _check_bin_frames, _open_series
+    it cannot part frame by frame; keep T // b well above 100, chance correlations split static regions below that.  detrend_frames:
+    as for roi_pair_corr_device -- a decay common to all pixels pushes every whole-recording correlation towards 1 and hides the
+    two groups; pooling over segments of L frames gives them back.  Short segments also remove real slow covariance: results at
+    different L are not comparable with each other or with None."""
+    from .series import _check_bin_frames, _check_detrend_frames, _open_series
+    if detrend_frames is not None:
+        _check_detrend_frames(detrend_frames)
     min_gap, min_area, iterations = _check_split_args(min_gap, min_area, iterations)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
@@ -323,7 +371,7 @@ def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, sour
     corr = [None] * len(pixels)
     if sent:
         got, _ = roi_pair_corr_device(dspath, [pixels[r] for r in sent], source=source, device=device, chunk_frames=chunk_frames,
-                                      shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, bin_frames=bin_frames)
+                                      shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, bin_frames=bin_frames, detrend_frames=detrend_frames)
         for r, c in zip(sent, got):
             corr[r] = c
     return split_rois(pixels, corr, shape, min_gap=min_gap, min_area=min_area, iterations=iterations)

@@ -21,6 +21,11 @@ are streamed once through the dc_series_* kernels (include/dcunet.h):
 TemporalBinner (dc_series_bin_time) goes in front of any reader: the exact rounded means of b <= 64 consecutive frames, streamed,
 so that what is correlated is a transient and not the pixel noise of single frames (bin_frames= of the one-call functions).
 
+detrend_frames=L (SeriesSummarizer, and RoiFootprints / RoiPairCorr, which share detrend_plan): `std` and `corr` are formed from
+centred moments pooled over segments of L frames (dc_series_fold_segment, dc_series_finalize_pooled), exact integers until the last
+step, so that bleaching and drift common to all pixels do not push every correlation towards 1.  Piecewise-constant detrending: a
+trend inside a segment stays; results at different L are not comparable with each other or with None.
+
 Importing this module needs neither torch nor the GPU; constructing a SeriesSummarizer does (there is no CPU fallback).
 """
 import numpy as np
@@ -119,6 +124,62 @@ def _check_device_frames(torch, frames, dtype, device, owner):
         raise ValueError('a device tensor must be contiguous')
 
 
+MIN_DETREND_FRAMES = 2
+MAX_DETREND_FRAMES = 4096             # DC_DETREND_MAX_FRAMES: the frames of one detrending segment
+MAX_DETREND_VOLUME = 1 << 46          # M * H * W up to which the pooled 128-bit numerators fit (csrc/detrend_math.h)
+
+
+def detrend_plan(T, L):
+    """The segments of a recording of T frames detrended with `detrend_frames=L` -> [(t_start, len, mult)]: n = max(1, T // L)
+    segments, n - 1 of L frames and a last one of L_last = T - (n - 1) L frames (L <= L_last < 2 L); T < 2 L: one segment of T
+    frames.  mult = M / len with M = L * L_last (M = T when n == 1): L_last for a full segment, L for the last, 1 alone.  Host only."""
+    T, L = int(T), int(L)
+    if T < 1 or L < 1:
+        raise ValueError('detrend_plan(T = %d, L = %d): both must be >= 1' % (T, L))
+    n = max(1, T // L)
+    if n == 1:
+        return [(0, T, 1)]
+    last = T - (n - 1) * L
+    return [(s * L, L, last) for s in range(n - 1)] + [((n - 1) * L, last, L)]
+
+
+def _check_detrend_frames(detrend_frames, n_frames=None, shape=None):
+    """The `detrend_frames=` keyword: an integer L in [2, MAX_DETREND_FRAMES]; with the declared n_frames (and the frame shape)
+    M * H * W <= 2**46, M = L * L_last of detrend_plan (M = n_frames for one segment).  Host only."""
+    if isinstance(detrend_frames, bool) or not isinstance(detrend_frames, (int, np.integer)):
+        raise ValueError('detrend_frames must be an integer in [%d, %d], not %r' % (MIN_DETREND_FRAMES, MAX_DETREND_FRAMES, detrend_frames))
+    L = int(detrend_frames)
+    if not MIN_DETREND_FRAMES <= L <= MAX_DETREND_FRAMES:
+        raise ValueError('detrend_frames must be in [%d, %d], not %d' % (MIN_DETREND_FRAMES, MAX_DETREND_FRAMES, L))
+    if n_frames is not None and shape is not None:
+        plan = detrend_plan(n_frames, L)
+        M = plan[0][1] * plan[0][2]
+        if M * shape[0] * shape[1] > MAX_DETREND_VOLUME:
+            raise ValueError('detrend_frames = %d on %d frames of %d x %d: M * H * W = %d * %d is limited to 2**46'
+                             % (L, n_frames, shape[0], shape[1], M, shape[0] * shape[1]))
+    return L
+
+
+class _Segments(object):
+    """Where a reader in detrend mode stands: cut(t0, tc) yields (offset in the chunk, frames, frame within the segment, the
+    segment (t_start, len, mult) when the piece ends it, else None) for the frames [t0, t0 + tc) of the recording."""
+
+    def __init__(self, n_frames, L):
+        self.plan = detrend_plan(n_frames, L)
+        self.L, self.n, self.n_frames = L, len(self.plan), n_frames
+        self.M = self.plan[0][1] * self.plan[0][2]
+        self.last = self.plan[-1][1]
+
+    def cut(self, t0, tc):
+        k = 0
+        while k < tc:
+            s = min((t0 + k) // self.L, self.n - 1)
+            start, length, _ = self.plan[s]
+            m = min(tc - k, start + length - (t0 + k))
+            yield k, m, t0 + k - start, (self.plan[s] if t0 + k + m == start + length else None)
+            k += m
+
+
 class _ShiftedChunks(object):
     """Known shifts applied on the way in (fill 0): the int32 (n_frames, 2) table on the device (dc_motion_apply) or the
     (n_frames, By, Bx, 2) block shifts (dc_motion_warp) and one scratch chunk the accumulate kernels read instead of the staged
@@ -206,17 +267,27 @@ class _TwoSlotStage(object):
             self._read[k] = done
 
 
+def _pooled_ints(words):
+    """int64 (..., 2) {lo, hi} pooled words -> an object array of exact Python ints, hi * 2^64 + lo."""
+    return words[..., 1].astype(object) * (1 << 64) + words[..., 0].view(np.uint64).astype(object)
+
+
 class SeriesSummarizer(object):
     """Owns the device state of one recording's summaries; feed() the frames in order, in chunks of any size, then result()."""
 
-    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None, fine_shifts=None, bidi=0):
+    def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None, fine_shifts=None, detrend_frames=None,
+                 bidi=0):
         """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
         MotionCorrector.shifts_device()): each chunk is moved by dc_motion_apply (fill 0) before it is summarised.  Piecewise-rigid
         (n_frames, By, Bx, 2) block shifts (MotionCorrector.block_shifts_device()) are taken too: dc_motion_warp moves the chunk.
         fine_shifts: instead of shifts, the same shapes in sixteenths of a pixel (MotionCorrector.fine_shifts_device()): each
         chunk is interpolated by dc_motion_apply_sub / dc_motion_warp_sub (fill 0).
         bidi: the whole-pixel offset of the odd lines (motion.estimate_bidi_device), undone by dc_bidi_apply (fill 0) before the
-        shift move; with no shifts it is the only move."""
+        shift move; with no shifts it is the only move.
+        detrend_frames: None, or an integer L in [2, 4096]: `std` and `corr` are formed from centred moments pooled over the
+        segments of detrend_plan(n_frames, L) (dc_series_fold_segment at every segment's end, dc_series_finalize_pooled), which
+        removes every trend that is constant within a segment; `mean` and `max` are those of the whole recording; `mean16` /
+        `max16` are not served.  L > n_frames / 2 is one segment: the `corr` bits of None."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         try:
             shape = tuple(int(v) for v in shape)
@@ -233,6 +304,11 @@ class SeriesSummarizer(object):
             raise ValueError('kinds is empty')
         for k in kinds:
             _check_kind(k)
+        self._seg = None
+        if detrend_frames is not None:
+            self._seg = _Segments(n_frames, _check_detrend_frames(detrend_frames, n_frames, shape))
+            if 'mean16' in kinds or 'max16' in kinds:
+                raise ValueError('mean16 / max16 are the stored summaries of the whole recording: not served with detrend_frames')
         H, W = shape
         if chunk_frames is None:
             chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
@@ -267,6 +343,11 @@ class SeriesSummarizer(object):
         self.mean16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None      # float16 BITS
         self.max16 = torch.empty(n, dtype=torch.int16, device=dev) if self._chain else None
         self.xy = torch.empty((4, n), dtype=torch.int64, device=dev) if self._xy else None
+        if self._seg is not None:        # the pooled numerators: 16-byte {lo, hi} words, added to by every fold
+            self._pvar = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+            self._pcov = torch.zeros((4, n, 2), dtype=torch.int64, device=dev) if self._xy else None
+            self._sum_total = torch.zeros(n, dtype=torch.int64, device=dev)
+            self._vmax_total = torch.full((n,), -2 ** 31, dtype=torch.int32, device=dev)
         self._stage = _TwoSlotStage(torch, net, dev, 'series_stage', (self.chunk_frames, H, W))
         self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
                                                                                 self.dtype == np.dtype(np.uint16), bidi)
@@ -297,13 +378,25 @@ class SeriesSummarizer(object):
             main = self._stream()
             st = main.cuda_stream
 
-            def accumulate(fp, tc, t0):
-                L.dc_series_accumulate(fp, uns, tc, t0, self.n_frames,
+            def accumulate_frames(fp, tc, t0, n_total=self.n_frames):
+                L.dc_series_accumulate(fp, uns, tc, t0, n_total,
                                        self.mean16.data_ptr() if self._chain else None,
                                        self.max16.data_ptr() if self._chain else None,
                                        self.sum.data_ptr(), self.sumsq.data_ptr(), self.vmax.data_ptr(), H, W, st)
                 if self._xy:
                     L.dc_series_accumulate_xy(fp, uns, tc, t0, self.xy.data_ptr(), H, W, st)
+
+            def accumulate_segments(fp, tc, t0):
+                # a chunk is cut at the segment boundaries: the part before one is accumulated from its own frame pointer with
+                # t0 counted from the segment's start (0 initialises the state), then the segment is folded
+                for k, m, within, ends in self._seg.cut(t0, tc):
+                    accumulate_frames(fp + k * H * W * 2, m, within, within + m)
+                    if ends is not None:
+                        L.dc_series_fold_segment(self.sum.data_ptr(), self.sumsq.data_ptr(), self.xy.data_ptr() if self._xy else None,
+                                                 self.vmax.data_ptr(), ends[1], ends[2], self._pvar.data_ptr(),
+                                                 self._pcov.data_ptr() if self._xy else None, self._sum_total.data_ptr(),
+                                                 self._vmax_total.data_ptr(), H, W, st)
+            accumulate = accumulate_frames if self._seg is None else accumulate_segments
 
             def reduce(fp, tc):
                 if self._shifted is None:
@@ -325,11 +418,26 @@ class SeriesSummarizer(object):
             H, W = self.shape
             with torch.cuda.device(self.device):
                 out = torch.empty((3, H * W), dtype=torch.float32, device=self.device)
+                if self._seg is not None:
+                    L.dc_series_finalize_pooled(self._pvar.data_ptr(), self._pcov.data_ptr() if self._xy else None,
+                                                self._sum_total.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                                out[2].data_ptr() if self._xy else None, H, W, self._seg.M, self.n_frames,
+                                                self._stream().cuda_stream)
+                    self._images = out
+                    return out
                 L.dc_series_finalize(self.sum.data_ptr(), self.sumsq.data_ptr(), self.xy.data_ptr() if self._xy else None,
                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr() if self._xy else None,
                                      H, W, self.n_frames, self._stream().cuda_stream)
             self._images = out
         return self._images
+
+    def _pooled_moments(self):
+        """Detrend mode: the pooled numerators as exact Python ints -- dict(M, T, var (H,W) object array of N(x,x), cov (4,H,W) of
+        N(x, neighbour) for right, down, down-right, down-left (None without 'corr'; 0 where the neighbour is outside))."""
+        H, W = self.shape
+        var = _pooled_ints(self._pvar.cpu().numpy()).reshape(H, W)
+        cov = _pooled_ints(self._pcov.cpu().numpy()).reshape(4, H, W) if self._xy else None
+        return dict(M=self._seg.M, T=self.n_frames, var=var, cov=cov)
 
     def _standardize(self, img):
         torch, L = self._torch, self.L
@@ -341,13 +449,20 @@ class SeriesSummarizer(object):
 
     def result(self, kind, standardize=False):
         """The (H,W) summary: float32 (float16 for 'mean16', int16 for 'max16').  standardize=True: (img - mean) / std of the
-        float32 image, as _summarize_series does with series/mean -- always float32."""
+        float32 image, as _summarize_series does with series/mean -- always float32.  With detrend_frames, 'moments' gives the
+        pooled numerators as exact Python ints: dict(M, T, var (H,W), cov (4,H,W) or None)."""
+        if kind == 'moments' and self._seg is not None:
+            if self.fed != self.n_frames:
+                raise ValueError('result() after %d of %d frames' % (self.fed, self.n_frames))
+            return self._pooled_moments()
         _check_kind(kind, self.kinds)
         if self.fed != self.n_frames:
             raise ValueError('result() after %d of %d frames' % (self.fed, self.n_frames))
         torch = self._torch
         H, W = self.shape
-        if kind == 'mean16':
+        if kind == 'max' and self._seg is not None:
+            raw = self._vmax_total.cpu().numpy().astype(np.float32).reshape(H, W)
+        elif kind == 'mean16':
             raw = self.mean16.cpu().numpy().view(np.float16).reshape(H, W)
         elif kind == 'max16':
             raw = self.max16.cpu().numpy().reshape(H, W)
@@ -555,7 +670,7 @@ def _open_series(dspath, source):
 
 
 def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
-                            shifts=None, fine_shifts=None, bin_frames=None, bidi=0):
+                            shifts=None, fine_shifts=None, bin_frames=None, detrend_frames=None, bidi=0):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
     float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame, or
     its (T, By, Bx, 2) block shifts (motion.estimate_shifts_device), applied on the device on the way in.  fine_shifts: instead,
@@ -563,11 +678,17 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
     bidi: the offset of the odd lines (motion.estimate_bidi_device), undone on the way in before the shifts.
     bin_frames: None, or an integer b in [1, 64]: the corrected frames pass through a TemporalBinner first and the summary is that
     of the T // b rounded means of b consecutive frames (the trailing T % b frames are dropped; 1 gives what None gives).  `std`
-    and `corr` of a binned recording are not comparable with the unbinned ones."""
+    and `corr` of a binned recording are not comparable with the unbinned ones.
+    detrend_frames: None, or an integer L in [2, 4096]: `std` and `corr` pooled over segments of L frames (SeriesSummarizer); with
+    bin_frames, L counts binned frames.  Results at different L are not comparable with each other or with None."""
     _check_kind(kind)
     _check_bidi(bidi)
     if bin_frames is not None:
         _check_bin_frames(bin_frames)
+    if detrend_frames is not None:
+        _check_detrend_frames(detrend_frames)
+        if kind in ('mean16', 'max16'):
+            raise ValueError('mean16 / max16 are the stored summaries of the whole recording: not served with detrend_frames')
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     frames, close = _open_series(dspath, source)
@@ -577,12 +698,13 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
         T = int(frames.shape[0])
         if bin_frames is None:
             summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
-                                    kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
+                                    kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
             for a in range(0, T, summ.chunk_frames):
                 summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
         else:
             summ = _feed_binned(frames, bin_frames, lambda n, dev: SeriesSummarizer(tuple(frames.shape[1:]), n, frames.dtype, device=dev,
-                                                                                    chunk_frames=chunk_frames, kinds=(kind,)),
+                                                                                    chunk_frames=chunk_frames, kinds=(kind,),
+                                                                                    detrend_frames=detrend_frames),
                                 device, chunk_frames, shifts, fine_shifts, bidi)
         out = summ.result(kind, standardize=standardize)
     finally:

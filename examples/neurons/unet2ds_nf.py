@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
                               estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
-                              split_rois_device)
+                              split_rois_device, detrend_plan)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -133,7 +133,7 @@ def _n_frames(dspath):
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
-           bin_frames=None):
+           bin_frames=None, detrend=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -156,7 +156,11 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     footprints, the split, the traces -- reads frames whose odd lines have been moved back by it.
     bin_frames=B (with refine or split): those two passes correlate the rounded means of B consecutive corrected frames
     (deep_calcium_amd.TemporalBinner: the pixel noise falls by sqrt(B), a transient of many frames survives; the trailing T % B
-    frames are dropped).  The traces that are written are always those of every frame.  Keep T // B well above 100."""
+    frames are dropped).  The traces that are written are always those of every frame.  Keep T // B well above 100.
+    detrend=L (with refine or split): those two passes correlate WITHIN segments of L frames (binned frames with bin_frames) and pool
+    the segments (`detrend_frames=` of the readers): bleaching and drift that are common to all pixels no longer push every
+    correlation towards 1.  Piecewise-constant detrending: a trend inside a segment stays, and short segments also remove real slow
+    covariance.  The traces that are written are not detrended (--dff is for that)."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -174,6 +178,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--bin-frames needs --refine or --split: it bins the frames those passes correlate')
     if bin_frames is not None and not 1 <= bin_frames <= 64:
         raise ValueError('--bin-frames averages B consecutive frames, B in [1, 64], not %d' % bin_frames)
+    if detrend is not None and refine is None and split is None:
+        raise ValueError('--detrend needs --refine or --split: it detrends the correlations those passes form')
+    if detrend is not None and not 2 <= detrend <= 4096:
+        raise ValueError('--detrend correlates within segments of L frames, L in [2, 4096], not %d' % detrend)
     known = 'fine_shifts' if subpixel else 'shifts'
     unit = 16 if subpixel else 1
     dspaths = nf_find_hdf5(dataset_name)
@@ -212,8 +220,13 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             T = _n_frames(dspath)
             logger.info('%s: the refinement and the split read the means of %d consecutive frames: %d binned frames of %d'
                         % (name, bin_frames, T // bin_frames, T))
+        if detrend is not None:
+            n = _n_frames(dspath) // (bin_frames or 1)
+            plan = detrend_plan(n, detrend)
+            logger.info('%s: the refinement and the split correlate within segments of L = %d frames: %d segments over %d frames, L_last = %d'
+                        % (name, detrend, len(plan), n, plan[-1][1]))
         if refine is not None:
-            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, bin_frames=bin_frames, **moves(dspath))
+            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, bin_frames=bin_frames, detrend_frames=detrend, **moves(dspath))
             rois, kept = refine_rois(coords, corr, mask.shape, threshold=refine)
             before = [set(map(tuple, c[i].tolist())) for c, i in zip(coords, inside)]
             after = dict((r, set(map(tuple, c.tolist()))) for r, c in zip(kept, rois))
@@ -226,7 +239,8 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                 continue
             mask = rois
         if split is not None:
-            rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, bin_frames=bin_frames, **moves(dspath))
+            rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, bin_frames=bin_frames, detrend_frames=detrend,
+                                                   **moves(dspath))
             before = int(np.count_nonzero(mask)) if isinstance(mask, np.ndarray) else sum(len(r) for r in mask)
             logger.info('%s: split at gap >= %g (min area %d): %d of %d ROIs split, %d pixels dropped' % (
                 name, split, min_area, len(rois) - len(gaps), len(gaps), before - sum(len(r) for r in rois)))
@@ -292,6 +306,8 @@ if __name__ == '__main__':
                         dest='min_area')
     sp_trc.add_argument('--bin-frames', help='with --refine / --split: correlate the means of B consecutive frames (1..64) instead of single frames',
                         default=None, type=int, metavar='B', dest='bin_frames')
+    sp_trc.add_argument('--detrend', help='with --refine / --split: correlate within segments of L frames (2..4096; binned frames with --bin-frames) and pool them',
+                        default=None, type=int, metavar='L')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

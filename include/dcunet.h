@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 121
+#define DC_ABI_VERSION 122
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -656,6 +656,63 @@ int dc_roi_pair_accumulate(const void* frames, int is_unsigned, int tc, const in
                            const int* tiles, long ntiles, int R, long* a, long* g, int P, long G, int H, int W, dc_stream_t stream);
 int dc_roi_pair_corr(const long* a, const long* g, const int* roi_off, const long* goff, int R, int P, long G, long T, float* corr,
                      dc_stream_t stream);
+
+/* ---- Detrended correlations: centred moments pooled over segments of the recording ----------------------------------------------
+ * A recording bleaches and drifts.  A decay common to all pixels is a signal every pixel shares: it pushes every whole-recording
+ * correlation above (the series `corr` image, the footprint maps, the pixel-pair matrices) towards 1.  Correlating WITHIN segments
+ * of L frames and pooling removes every trend that is constant inside a segment -- piecewise-constant detrending; a trend inside a
+ * segment stays.  The reference has no counterpart; THESE DEFINITIONS ARE THE SPECIFICATION.  Integers until the last step, no
+ * look-ahead, independent of how the recording was chunked.
+ * The T frames are cut into n = max(1, T / L) segments: n - 1 of L frames and a last one of L_last = T - (n - 1) L frames
+ * (L <= L_last < 2 L); T < 2 L: one segment of T frames.  M = L * L_last (M = T when n == 1), mult_s = M / L_s: L_last for a full
+ * segment, L for the last, 1 when n == 1 -- so len * mult == M for every segment.  For any two series x, y a reader correlates,
+ * with the exact sums a_s = sum x, a'_s = sum y, g_s = sum x y over segment s:
+ *   N(x, y) = sum_s mult_s (L_s g_s - a_s a'_s)       exact in 128-bit integers: M times the pooled within-segment cross sum
+ *   corr    = today's arithmetic on {N(x,x), N(x,y), N(y,y)}: dc_fp_corr for pairs and footprints (the footprint rule for an
+ *             inside entry is linear, Cxl = Cxs - Cxx, Cll = Css - 2 Cxs + Cxx, and is applied to the pooled numerators),
+ *             dc_series_finalize's neighbour mean for the series image.  With n == 1 the numerators are T g - a a': the same bits
+ *             as the undetrended entry points give.
+ *   std     = (float)sqrt(f64(N(x,x)) / f64(M * T)): population, within 1 float32 ulp of the exact value.
+ * Limits: 2 <= L <= DC_DETREND_MAX_FRAMES; a segment beside others has len, mult <= 2 L - 1 <= 8191, one alone mult == 1 and
+ * len <= 2^31 - 1; all limits of the undetrended entry points; and M * H * W <= 2^46, which keeps the largest numerator, the
+ * footprint Css, below 2^124 (csrc/detrend_math.h derives the magnitudes).  Beyond: DC_EUNSUP (-3); len < 1 or mult < 1:
+ * DC_EINVAL.  All pointers are DEVICE memory, there are no out-parameters and nothing is read on the host.
+ * A POOLED WORD is one 16-byte {lo, hi} element (two's complement, value = hi * 2^64 + lo) of a 16-byte aligned int64 buffer;
+ * the pooled state is CALLER-OWNED AND CALLER-ZEROED.  Every state word is owned by one thread of one workgroup: no atomics, the
+ * same bits for every chunking and every run.  The caller accumulates a segment with the undetrended accumulate entry points
+ * and calls the fold at the segment's last frame.
+ *   dc_series_fold_segment: sum, sumsq, xy (nullable, then pooled_cov is null too), vmax: the state of dc_series_accumulate /
+ *     dc_series_accumulate_xy over the len frames of the segment.  pooled_var: H * W words, += mult (len sumsq - sum^2);
+ *     pooled_cov: 4 * H * W words in the layout of xy, += mult (len xy[j] - sum_p sum_q(j)), a neighbour outside the image adds
+ *     nothing.  sum_total int64[H * W] += sum (zeroed by the caller), vmax_total int32[H * W] = max(vmax_total, vmax) (set to
+ *     INT32_MIN by the caller): the whole recording's sum and maximum.  The segment state is NOT cleared: the next segment's first
+ *     accumulate passes t0 == 0, which initialises it.
+ *   dc_series_finalize_pooled: mean (nullable; needs sum_total) = (float)(double(sum_total) / double(T)), sdev (nullable), corr
+ *     (nullable; needs pooled_cov): the neighbour rule and summation order of dc_series_finalize; a pair with a non-positive
+ *     N(x,x) counts 0.
+ *   dc_roi_pair_fold_segment: a, g, roi_off, goff, tiles as for dc_roi_pair_accumulate, one workgroup per tile.  pooled: G words in
+ *     the layout of g; entry i <= j += mult (len g_ij - a_i a_j), the lower triangle is never touched.  LEAVES a AND g ZERO (the
+ *     kernel clears the g word it owns, a is cleared by a stream-ordered memset behind it).
+ *   dc_roi_pair_corr_pooled: corr float[G] as dc_roi_pair_corr writes it, the lower triangle mirrored: bit-symmetric, the diagonal
+ *     exactly 1 for a pixel that varies within some segment; row, column and diagonal exactly 0 for one constant within every segment.
+ *   dc_roi_pixel_fold_segment: mom and the CSR as for dc_roi_pixel_accumulate over the segment; rmom = int64[3 * R], what
+ *     dc_roi_trace_moments gives for the segment's columns (sums + t_start, T = len).  pooled_xx, pooled_xs: N words each,
+ *     += mult (len b - a^2) and mult (len c - a u); pooled_ss: R words, += mult (len w - u^2).  CLEARS the four planes of mom of
+ *     every entry it folds.  A row whose row_roi is outside [0, R) is skipped.
+ *   dc_roi_pixel_corr_pooled: corr float[N] by the inside / halo rule and dc_fp_corr; the entries of a row whose row_roi is outside
+ *     [0, R) get 0. */
+#define DC_DETREND_MAX_FRAMES 4096
+int dc_series_fold_segment(const long* sum, const long* sumsq, const long* xy, const int* vmax, long len, long mult, long* pooled_var,
+                           long* pooled_cov, long* sum_total, int* vmax_total, int H, int W, dc_stream_t stream);
+int dc_series_finalize_pooled(const long* pooled_var, const long* pooled_cov, const long* sum_total, float* mean, float* sdev, float* corr,
+                              int H, int W, long M, long T, dc_stream_t stream);
+int dc_roi_pair_fold_segment(long* a, long* g, const int* roi_off, const long* goff, const int* tiles, long ntiles, int R, int P, long G,
+                             long len, long mult, long* pooled, dc_stream_t stream);
+int dc_roi_pair_corr_pooled(const long* pooled, const int* roi_off, const long* goff, int R, int P, long G, float* corr, dc_stream_t stream);
+int dc_roi_pixel_fold_segment(long* mom, int N, const int* row_off, const int* row_roi, int S, int R, const long* rmom, long len, long mult,
+                              long* pooled_xx, long* pooled_xs, long* pooled_ss, int H, int W, dc_stream_t stream);
+int dc_roi_pixel_corr_pooled(const long* pooled_xx, const long* pooled_xs, const long* pooled_ss, int N, const int* row_off,
+                             const int* row_roi, int S, int R, const int* inside, float* corr, dc_stream_t stream);
 
 /* ---- dF/F traces: neuropil correction, rolling-percentile baseline, (F - F0) / F0 -----------------------------------------------
  * The step between ROI traces and spikes that the z-score above cannot replace: a recording bleaches and drifts, and every ROI
