@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
                               estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
-                              split_rois_device, detrend_plan)
+                              split_rois_device, detrend_plan, merge_rois_device)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -133,7 +133,7 @@ def _n_frames(dspath):
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
-           bin_frames=None, detrend=None):
+           bin_frames=None, detrend=None, merge=None, merge_dist=2):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -160,7 +160,12 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     detrend=L (with refine or split): those two passes correlate WITHIN segments of L frames (binned frames with bin_frames) and pool
     the segments (`detrend_frames=` of the readers): bleaching and drift that are common to all pixels no longer push every
     correlation towards 1.  Piecewise-constant detrending: a trend inside a segment stays, and short segments also remove real slow
-    covariance.  The traces that are written are not detrended (--dff is for that)."""
+    covariance.  The traces that are written are not detrended (--dff is for that).
+    merge=THR: one more pass over the recording (after the refinement and the split, where given) sums every ROI's trace; ROIs whose
+    pixels lie within `merge_dist` pixels of each other (Chebyshev; 2: one blank pixel between) and whose traces correlate at THR or
+    above become one ROI (deep_calcium_amd.merge_rois: single linkage, one round) -- one cell that the mask delivers in fragments is
+    counted once.  detrend applies to this correlation too, and a recording that bleaches needs it: a common decay pushes every
+    trace pair towards 1 and merges distinct neighbours."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -178,10 +183,14 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--bin-frames needs --refine or --split: it bins the frames those passes correlate')
     if bin_frames is not None and not 1 <= bin_frames <= 64:
         raise ValueError('--bin-frames averages B consecutive frames, B in [1, 64], not %d' % bin_frames)
-    if detrend is not None and refine is None and split is None:
-        raise ValueError('--detrend needs --refine or --split: it detrends the correlations those passes form')
+    if detrend is not None and refine is None and split is None and merge is None:
+        raise ValueError('--detrend needs --refine or --split (or --merge): it detrends the correlations those passes form')
     if detrend is not None and not 2 <= detrend <= 4096:
         raise ValueError('--detrend correlates within segments of L frames, L in [2, 4096], not %d' % detrend)
+    if merge is not None and merge != merge:
+        raise ValueError('--merge joins ROIs whose traces correlate at THR or above: THR must be a number, not NaN')
+    if not 0 <= merge_dist <= 16:
+        raise ValueError('--merge-dist is the largest gap between two fragments in pixels, D in [0, 16], not %d' % merge_dist)
     known = 'fine_shifts' if subpixel else 'shifts'
     unit = 16 if subpixel else 1
     dspaths = nf_find_hdf5(dataset_name)
@@ -245,6 +254,13 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             logger.info('%s: split at gap >= %g (min area %d): %d of %d ROIs split, %d pixels dropped' % (
                 name, split, min_area, len(rois) - len(gaps), len(gaps), before - sum(len(r) for r in rois)))
             mask = rois
+        if merge is not None:
+            rois, origin, pairs, corr = merge_rois_device(dspath, mask, max_dist=merge_dist, threshold=merge, detrend_frames=detrend,
+                                                          **moves(dspath))
+            logger.info('%s: merged at trace corr >= %g (within %d pixels%s): %d candidate pairs, %d accepted, %d ROIs -> %d' % (
+                name, merge, merge_dist, '' if detrend is None else ', within segments of L = %d of all %d frames' % (detrend, _n_frames(dspath)),
+                len(pairs), int(np.count_nonzero(corr >= merge)), sum(len(o) for o in origin), len(rois)))
+            mask = rois
         if dff is not None:
             tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **moves(dspath))
         else:
@@ -306,8 +322,12 @@ if __name__ == '__main__':
                         dest='min_area')
     sp_trc.add_argument('--bin-frames', help='with --refine / --split: correlate the means of B consecutive frames (1..64) instead of single frames',
                         default=None, type=int, metavar='B', dest='bin_frames')
-    sp_trc.add_argument('--detrend', help='with --refine / --split: correlate within segments of L frames (2..4096; binned frames with --bin-frames) and pool them',
+    sp_trc.add_argument('--detrend', help='with --refine / --split / --merge: correlate within segments of L frames (2..4096; binned frames with --bin-frames) and pool them',
                         default=None, type=int, metavar='L')
+    sp_trc.add_argument('--merge', help='merge neighbouring ROIs whose traces correlate at THR or above (default 0.8) into one; --detrend applies',
+                        nargs='?', const=0.8, default=None, type=float, metavar='THR')
+    sp_trc.add_argument('--merge-dist', help='with --merge: the largest distance in pixels between two ROIs that may be merged (0..16, default 2)',
+                        default=2, type=int, metavar='D', dest='merge_dist')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

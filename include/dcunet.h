@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 122
+#define DC_ABI_VERSION 123
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -713,6 +713,35 @@ int dc_roi_pixel_fold_segment(long* mom, int N, const int* row_off, const int* r
                               long* pooled_xx, long* pooled_xs, long* pooled_ss, int H, int W, dc_stream_t stream);
 int dc_roi_pixel_corr_pooled(const long* pooled_xx, const long* pooled_xs, const long* pooled_ss, int N, const int* row_off,
                              const int* row_roi, int S, int R, const int* inside, float* corr, dc_stream_t stream);
+
+/* ---- ROI trace-pair correlation: the correlation over time of the traces of two ROIs ----------------------------------------------
+ * The opposite mistake to the one the pixel-pair matrices catch: ONE cell that arrives as SEVERAL ROIs (a nucleus-excluded ring
+ * broken into arcs, a cell cut by a one-pixel line of sub-threshold probability).  What decides a merge is the correlation of the
+ * traces of two neighbouring ROIs, and its inputs already lie on the device after the streaming pass: the int64 sums of
+ * dc_roi_trace_accumulate.  No further pass over the recording.  The reference has no counterpart; THESE DEFINITIONS ARE THE
+ * SPECIFICATION.  Integers until the last step; the same bits every run and for every launch geometry.
+ * sums = int64 rows of stride ld >= T (a column offset is the caller's pointer arithmetic: 8-byte alignment only), R rows.
+ * pairs = int32[P][2] = (i, j): any order, i == j allowed, a pair may appear twice.  x = sums[i], y = sums[j].
+ * seg_len = 0: one segment of T frames.  Otherwise L = seg_len in [2, DC_DETREND_MAX_FRAMES] and the T frames are cut as in the
+ * section above: n = max(1, T / L) segments, the last absorbing the remainder, M = L * L_last (M = T when n == 1), mult_s = M / L_s.
+ * L > T / 2 is one segment: the bits of seg_len = 0.
+ *   dc_trace_pair_moments: num = int64[P][6] = {Nxx_lo, Nxx_hi, Nxy_lo, Nxy_hi, Nyy_lo, Nyy_hi} (two's complement, hi * 2^64 + lo),
+ *     N(x, y) = sum_s mult_s (L_s g_s - a_s a'_s) with a_s = sum x, a'_s = sum y in int64 and g_s = sum x y in 128 bits; Nxx = N(x, x),
+ *     Nxy = N(x, y), Nyy = N(y, y): every pair is self-contained.  Every word of every p < P is written, each by one thread; a pair
+ *     that names a row outside [0, R) gets zeros; nothing at or beyond P is touched.  No atomics.
+ *     RANGE: exact whenever |S| * max(M, T) <= 2^62 for every value read -- e.g. |S| <= 2^16 A (an ROI of A 16-bit pixels) with
+ *     max(M, T) * A <= 2^46, the volume limits above; then |N| <= 2^124 (csrc/trace_pair_math.h derives it).  THE CALLER PROMISES
+ *     this (not checked), as for dc_trace_baseline.  Neuropil-corrected numerators (|N| < 2^62) are outside it.
+ *   dc_trace_pair_corr: corr float[P] = dc_fp_corr of csrc/footprint_math.h on {Nxx, Nxy, Nyy}: (float)(f64(Nxy) / (sqrt(f64(Nxx)) *
+ *     sqrt(f64(Nyy)))), each numerator rounded ONCE to double, no fused multiply-add: within 1 float32 ulp, in [-1, 1], the same
+ *     bits for (i, j) and (j, i); exactly 1 for i == j on a row that varies, exactly 0 where either row is constant within every
+ *     segment (zero numerators, so also for a pair that names no row), exactly -1 for a row against its mirror image c - x.
+ * Refused: a null pointer, a negative size, ld < T, a misaligned buffer, seg_len < 0 or == 1: DC_EINVAL (-1); T > 2^31 - 1,
+ * seg_len > DC_DETREND_MAX_FRAMES, P > DC_TRACE_PAIR_MAX_PAIRS: DC_EUNSUP (-3).  P == 0, R == 0 or T == 0: 0, nothing launched.
+ * All pointers are DEVICE memory, there are no out-parameters and nothing is read on the host. */
+#define DC_TRACE_PAIR_MAX_PAIRS 16777216L
+int dc_trace_pair_moments(const long* sums, long ld, int R, long T, int seg_len, const int* pairs, long P, long* num, dc_stream_t stream);
+int dc_trace_pair_corr(const long* num, long P, float* corr, dc_stream_t stream);
 
 /* ---- dF/F traces: neuropil correction, rolling-percentile baseline, (F - F0) / F0 -----------------------------------------------
  * The step between ROI traces and spikes that the z-score above cannot replace: a recording bleaches and drifts, and every ROI
