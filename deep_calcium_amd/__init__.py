@@ -30,6 +30,7 @@ _EXPORTS = {
     'footprints': ('RoiFootprints', 'roi_footprints_device', 'roi_support', 'refine_rois'),
     'roi_pairs': ('RoiPairCorr', 'roi_pair_corr_device', 'split_rois', 'split_rois_device'),
     'merge': ('TracePairCorr', 'roi_neighbours', 'merge_rois', 'merge_rois_device'),
+    'frames': ('FrameQuality', 'FrameFilter', 'frame_quality_device', 'flag_frames', 'hold_index'),
     'dff': ('TraceBaseline', 'neuropil_rois', 'dff_traces_device'),
     'motion': ('MotionCorrector', 'make_template', 'estimate_shifts_device', 'valid_rectangle', 'fine_to_pixels', 'BidiEstimator',
                'pick_bidi', 'estimate_bidi_device'),

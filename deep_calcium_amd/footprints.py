@@ -270,13 +270,15 @@ class RoiFootprints(object):
 
 
 def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None,
-                          bin_frames=None, detrend_frames=None, bidi=0):
+                          bin_frames=None, detrend_frames=None, keep=None, bidi=0):
     """-> (corr, coords, inside) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk:
     the recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: None, or an integer b in
     [1, 64]: the maps are those of the T // b rounded means of b consecutive corrected frames, correlated with the ROI traces of
     that binned recording (series.TemporalBinner; the trailing T % b frames are dropped, 1 gives what None gives).  detrend_frames: None, or an
     integer L in [2, 4096]: the correlations are pooled over segments of L frames (RoiFootprints); binning comes first and L counts
-    binned frames.  Results at different L are not comparable with each other or with None."""
+    binned frames.  Results at different L are not comparable with each other or with None.  keep: None, or a (T,) array of booleans
+    (frames.flag_frames): the frames marked False are left out after bidi and the shifts and before binning and detrending, whose b
+    and L then count kept frames; all True gives what None gives."""
     from .series import _check_bin_frames, _check_detrend_frames, _feed_binned, _open_series
     _check_halo(halo)
     if detrend_frames is not None:
@@ -285,12 +287,20 @@ def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     if bin_frames is not None:
         _check_bin_frames(bin_frames)
+    if keep is not None:
+        from .frames import _check_keep, _feed_kept
+        keep = _check_keep(keep)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
-        if bin_frames is None:
+        if keep is not None:
+            fp = _feed_kept(frames, keep, bin_frames, lambda n, dev: RoiFootprints(tuple(frames.shape[1:]), n, frames.dtype, rois, halo=halo,
+                                                                                   device=dev, chunk_frames=chunk_frames,
+                                                                                   detrend_frames=detrend_frames),
+                            device, chunk_frames, shifts, fine_shifts, bidi)
+        elif bin_frames is None:
             fp = RoiFootprints(tuple(frames.shape[1:]), T, frames.dtype, rois, halo=halo, device=device, chunk_frames=chunk_frames,
                                shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
             for a in range(0, T, fp.chunk_frames):

@@ -274,13 +274,15 @@ def merge_rois(pixels, pairs, corr, shape, threshold=0.8):
 
 
 def merge_rois_device(dspath, rois, max_dist=2, threshold=0.8, detrend_frames=None, source='series/raw', device=None, chunk_frames=None,
-                      shifts=None, fine_shifts=None, bidi=0):
+                      shifts=None, fine_shifts=None, keep=None, bidi=0):
     """-> (new_rois, origin, pairs, corr): merge_rois of `rois` (any form rois_to_csr takes) over `source` of a dataset file.  The
     candidates are roi_neighbours(rois, shape, max_dist); ONE streaming pass through a RoiTraceExtractor gives every ROI's sums, and
     dc_trace_pair_moments / dc_trace_pair_corr run on them where they lie.  With no candidate pair the recording is not read at
     all.  detrend_frames: None, or an integer L in [2, 4096] -- on a recording that bleaches or drifts every trace pair
     correlates; pooling within segments of L frames takes the common trend out (TracePairCorr).  shifts / fine_shifts / bidi: as for
-    extract_traces_device.  pairs: int32 (P, 2); corr: float32 (P,)."""
+    extract_traces_device.  keep: None, or a (T,) array of booleans (frames.flag_frames): the pairs are correlated over the kept
+    columns of the sums only (a torch index, no kernel), and L counts kept frames; all True gives what None gives.
+    pairs: int32 (P, 2); corr: float32 (P,)."""
     from .series import _check_bidi, _check_detrend_frames, _open_series
     from .traces import RoiTraceExtractor
     max_dist = _check_max_dist(max_dist)
@@ -290,22 +292,31 @@ def merge_rois_device(dspath, rois, max_dist=2, threshold=0.8, detrend_frames=No
     _check_bidi(bidi)
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
+    if keep is not None:
+        from .frames import _check_keep
+        keep = _check_keep(keep)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
+        if keep is not None:
+            keep = _check_keep(keep, T)
         shape = _check_shape(tuple(frames.shape[1:]))
         pixels = [_coords(p, shape[1]) for p in _roi_pixels(rois, shape)]
         pairs = roi_neighbours(pixels, shape, max_dist)
         corr = np.zeros((0,), np.float32)
         if len(pairs):
-            _check_range(T, [len(p) for p in pixels], detrend_frames)          # before the GPU is touched or the recording read
+            _check_range(T if keep is None else int(keep.sum()), [len(p) for p in pixels], detrend_frames)          # before the GPU is touched or the recording read
             ext = RoiTraceExtractor(shape, T, frames.dtype, pixels, device=device, chunk_frames=chunk_frames, shifts=shifts,
                                     fine_shifts=fine_shifts, bidi=bidi)
             for a in range(0, T, ext.chunk_frames):
                 ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
-            corr = TracePairCorr(ext.sums_device(), ext.areas_host(), pairs, detrend_frames=detrend_frames, device=ext.device).result('corr')
+            sums = ext.sums_device()
+            if keep is not None:                     # the kept columns, in order: a fresh contiguous tensor
+                import torch
+                sums = sums[:, torch.from_numpy(np.flatnonzero(keep)).to(ext.device)]
+            corr = TracePairCorr(sums, ext.areas_host(), pairs, detrend_frames=detrend_frames, device=ext.device).result('corr')
     finally:
         frames = None                        # a view of the file mapping: released before the file is closed
         close()

@@ -305,12 +305,14 @@ def split_rois(pixels, corr, shape, min_gap=0.1, min_area=8, iterations=16):
 
 
 def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_frames=None, shifts=None, fine_shifts=None,
-                         bin_frames=None, detrend_frames=None, bidi=0):
+                         bin_frames=None, detrend_frames=None, keep=None, bidi=0):
     """-> (corr, pixels) of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
     recording is read once.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: None, or an integer b in
     [1, 64]: the matrices are those of the T // b rounded means of b consecutive corrected frames (series.TemporalBinner; the
     trailing T % b frames are dropped, 1 gives what None gives).  detrend_frames: None, or an integer L in [2, 4096]: the
-    correlations are pooled over segments of L frames (RoiPairCorr); binning comes first and L counts binned frames."""
+    correlations are pooled over segments of L frames (RoiPairCorr); binning comes first and L counts binned frames.  keep: None, or
+    a (T,) array of booleans (frames.flag_frames): the frames marked False are left out after bidi and the shifts and before binning
+    and detrending, whose b and L then count kept frames; all True gives what None gives."""
     from .series import _check_bin_frames, _check_detrend_frames, _feed_binned, _open_series
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
@@ -318,12 +320,19 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
         _check_bin_frames(bin_frames)
     if detrend_frames is not None:
         _check_detrend_frames(detrend_frames)
+    if keep is not None:
+        from .frames import _check_keep, _feed_kept
+        keep = _check_keep(keep)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
-        if bin_frames is None:
+        if keep is not None:
+            pc = _feed_kept(frames, keep, bin_frames, lambda n, dev: RoiPairCorr(tuple(frames.shape[1:]), n, frames.dtype, rois, device=dev,
+                                                                                 chunk_frames=chunk_frames, detrend_frames=detrend_frames),
+                            device, chunk_frames, shifts, fine_shifts, bidi)
+        elif bin_frames is None:
             pc = RoiPairCorr(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames, shifts=shifts,
                              fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
             for a in range(0, T, pc.chunk_frames):
@@ -340,7 +349,7 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
 
 
 def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, source='series/raw', device=None, chunk_frames=None,
-                      shifts=None, fine_shifts=None, bin_frames=None, detrend_frames=None, bidi=0):
+                      shifts=None, fine_shifts=None, bin_frames=None, detrend_frames=None, keep=None, bidi=0):
     """-> (new_rois, origin, gaps) of split_rois for `rois` over `source` of a dataset file, in one pass over the recording.  ROIs
     of more than MAX_AREA or fewer than 2 * min_area pixels are not sent to the device and come back unchanged (gap NaN); when
     no ROI is left the recording is not read at all.  shifts / fine_shifts / bidi: as for extract_traces_device.  bin_frames: as
@@ -348,7 +357,8 @@ def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, sour
     it cannot part frame by frame; keep T // b well above 100, chance correlations split static regions below that.  detrend_frames:
     as for roi_pair_corr_device -- a decay common to all pixels pushes every whole-recording correlation towards 1 and hides the
     two groups; pooling over segments of L frames gives them back.  Short segments also remove real slow covariance: results at
-    different L are not comparable with each other or with None."""
+    different L are not comparable with each other or with None.  keep: as for roi_pair_corr_device -- three flash frames in a
+    thousand push every pixel pair towards 1 as bleaching does; leaving them out gives the two groups back."""
     from .series import _check_bin_frames, _check_detrend_frames, _open_series
     if detrend_frames is not None:
         _check_detrend_frames(detrend_frames)
@@ -357,6 +367,9 @@ def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, sour
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     if bin_frames is not None:
         _check_bin_frames(bin_frames)
+    if keep is not None:
+        from .frames import _check_keep
+        keep = _check_keep(keep)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
@@ -371,7 +384,8 @@ def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, sour
     corr = [None] * len(pixels)
     if sent:
         got, _ = roi_pair_corr_device(dspath, [pixels[r] for r in sent], source=source, device=device, chunk_frames=chunk_frames,
-                                      shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, bin_frames=bin_frames, detrend_frames=detrend_frames)
+                                      shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, bin_frames=bin_frames, detrend_frames=detrend_frames,
+                                      keep=keep)
         for r, c in zip(sent, got):
             corr[r] = c
     return split_rois(pixels, corr, shape, min_gap=min_gap, min_area=min_area, iterations=iterations)

@@ -670,7 +670,7 @@ def _open_series(dspath, source):
 
 
 def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
-                            shifts=None, fine_shifts=None, bin_frames=None, detrend_frames=None, bidi=0):
+                            shifts=None, fine_shifts=None, bin_frames=None, detrend_frames=None, keep=None, bidi=0):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
     float32 summary (standardised like _summarize_series's by default).  shifts: the (T, 2) (dy, dx) of every frame, or
     its (T, By, Bx, 2) block shifts (motion.estimate_shifts_device), applied on the device on the way in.  fine_shifts: instead,
@@ -680,7 +680,9 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
     of the T // b rounded means of b consecutive frames (the trailing T % b frames are dropped; 1 gives what None gives).  `std`
     and `corr` of a binned recording are not comparable with the unbinned ones.
     detrend_frames: None, or an integer L in [2, 4096]: `std` and `corr` pooled over segments of L frames (SeriesSummarizer); with
-    bin_frames, L counts binned frames.  Results at different L are not comparable with each other or with None."""
+    bin_frames, L counts binned frames.  Results at different L are not comparable with each other or with None.
+    keep: None, or a (T,) array of booleans (frames.flag_frames): the frames marked False are left out by a frames.FrameFilter after
+    bidi and the shifts and before binning and detrending, whose b and L then count kept frames; all True gives what None gives."""
     _check_kind(kind)
     _check_bidi(bidi)
     if bin_frames is not None:
@@ -691,12 +693,20 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
             raise ValueError('mean16 / max16 are the stored summaries of the whole recording: not served with detrend_frames')
     if shifts is not None and fine_shifts is not None:
         raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
+    if keep is not None:
+        from .frames import _check_keep, _feed_kept
+        keep = _check_keep(keep)
     frames, close = _open_series(dspath, source)
     try:
         if len(frames.shape) != 3:
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
-        if bin_frames is None:
+        if keep is not None:
+            summ = _feed_kept(frames, keep, bin_frames, lambda n, dev: SeriesSummarizer(tuple(frames.shape[1:]), n, frames.dtype, device=dev,
+                                                                                        chunk_frames=chunk_frames, kinds=(kind,),
+                                                                                        detrend_frames=detrend_frames),
+                              device, chunk_frames, shifts, fine_shifts, bidi)
+        elif bin_frames is None:
             summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
                                     kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
             for a in range(0, T, summ.chunk_frames):

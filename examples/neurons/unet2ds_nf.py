@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
                               estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
-                              split_rois_device, detrend_plan, merge_rois_device)
+                              split_rois_device, detrend_plan, merge_rois_device, make_template, frame_quality_device, flag_frames)
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -133,7 +133,7 @@ def _n_frames(dspath):
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
-           bin_frames=None, detrend=None, merge=None, merge_dist=2):
+           bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -165,7 +165,13 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     pixels lie within `merge_dist` pixels of each other (Chebyshev; 2: one blank pixel between) and whose traces correlate at THR or
     above become one ROI (deep_calcium_amd.merge_rois: single linkage, one round) -- one cell that the mask delivers in fragments is
     counted once.  detrend applies to this correlation too, and a recording that bleaches needs it: a common decay pushes every
-    trace pair towards 1 and merges distinct neighbours."""
+    trace pair towards 1 and merges distinct neighbours.
+    drop_artefacts=K: one more pass over the recording (after bidi and register, with their corrections) scores every frame -- its
+    mean and its correlation with the template over the rectangle every corrected frame covers (deep_calcium_amd.FrameQuality); the
+    template is the registration's, or without one the rounded mean of the first 200 frames.  Frames whose mean lies more than K
+    scaled median absolute deviations from the median, or whose correlation lies that far BELOW it (deep_calcium_amd.flag_frames),
+    are artefact frames -- a stimulation flash, a gated PMT, a z-jump: the summary the network segments, the refinement, the split
+    and the merge leave them out (`keep=`).  The traces that are written keep every frame."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -189,16 +195,26 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--detrend correlates within segments of L frames, L in [2, 4096], not %d' % detrend)
     if merge is not None and merge != merge:
         raise ValueError('--merge joins ROIs whose traces correlate at THR or above: THR must be a number, not NaN')
+    if drop_artefacts is not None and not drop_artefacts > 0:
+        raise ValueError('--drop-artefacts flags frames beyond K scaled median absolute deviations, K > 0, not %r' % (drop_artefacts,))
     if not 0 <= merge_dist <= 16:
         raise ValueError('--merge-dist is the largest gap between two fragments in pixels, D in [0, 16], not %d' % merge_dist)
     known = 'fine_shifts' if subpixel else 'shifts'
     unit = 16 if subpixel else 1
     dspaths = nf_find_hdf5(dataset_name)
-    shifts, offsets = {}, {}
+    shifts, offsets, templates, keeps = {}, {}, {}, {}
 
     def moves(p):
         # the keywords of every reader of the recording: the known shifts and the scan-phase offset
         return {known: shifts.get(p), 'bidi': offsets.get(p, 0)}
+
+    def kept(p):
+        # and of every reader that correlates: the frames --drop-artefacts leaves out
+        return dict(moves(p), keep=keeps.get(p))
+
+    def n_read(p):
+        # the frames those readers see: b and L count kept frames
+        return int(keeps[p].sum()) if p in keeps else _n_frames(p)
     if bidi is not None:
         for dspath in dspaths:
             offsets[dspath], totals = estimate_bidi_device(dspath, max_offset=bidi, frames=200)
@@ -210,13 +226,33 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         for dspath in dspaths:
             shifts[dspath], tmpl = estimate_shifts_device(dspath, max_shift=register, blocks=blocks, max_dev=max_dev, subpixel=subpixel,
                                                           coarse=coarse, bidi=offsets.get(dspath, 0))
+            templates[dspath] = tmpl
             logger.info('%s: registered within +-%d%s%s%s, largest |dy|, |dx| = %g, %g, valid rectangle %r' % (
                 dspath, register, '' if coarse is None else ' (wide search, binned %d x %d)' % (coarse, coarse), '' if blocks is None else ' in %d x %d blocks within +-%d of that' % (blocks + (max_dev,)),
                 ', refined to 1/16 pixel' if subpixel else '',
                 np.abs(shifts[dspath][..., 0]).max() / unit, np.abs(shifts[dspath][..., 1]).max() / unit,
                 valid_rectangle(shifts[dspath], tmpl.shape, fine=subpixel, bidi=offsets.get(dspath, 0))))
-    if register is not None or bidi is not None:
-        model = UNet2DSummary(cpdir=checkpoints_dir, series_summary_func=lambda p: summarize_series_device(p, kind='mean', **moves(p)))
+    if drop_artefacts is not None:
+        from deep_calcium_amd.series import _open_series
+        for dspath in dspaths:
+            if dspath not in templates:              # no registration: the rounded mean of the first 200 frames, lines corrected
+                frames, close = _open_series(dspath, 'series/raw')
+                try:
+                    templates[dspath] = make_template(np.asarray(frames[:200]), max_shift=0, iterations=0, bidi=offsets.get(dspath, 0))
+                finally:
+                    frames = None
+                    close()
+            tmpl = templates[dspath]
+            rect = valid_rectangle(shifts[dspath], tmpl.shape, fine=subpixel, bidi=offsets.get(dspath, 0)) if dspath in shifts else None
+            mean, corr = frame_quality_device(dspath, template=tmpl, rect=rect, **moves(dspath))
+            keeps[dspath] = flag_frames(mean, corr, k=drop_artefacts)
+            flagged = np.flatnonzero(~keeps[dspath])
+            logger.info('%s: %d of %d frames flagged as artefacts at K = %g (scored over %s; mean %g +- %g, corr %g): %s' % (
+                dspath, len(flagged), len(mean), drop_artefacts, 'the whole frame' if rect is None else 'the valid rectangle %r' % (rect,),
+                np.median(mean), 1.4826 * np.median(np.abs(mean - np.median(mean))), np.median(corr),
+                ' '.join(str(t) for t in flagged) or 'none'))
+    if register is not None or bidi is not None or drop_artefacts is not None:
+        model = UNet2DSummary(cpdir=checkpoints_dir, series_summary_func=lambda p: summarize_series_device(p, kind='mean', **kept(p)))
     else:
         model = UNet2DSummary(cpdir=checkpoints_dir)
     Mp, names = model.predict(dspaths, model_path=model_path, window_shape=(512, 512), save=False, augmentation=True)
@@ -226,39 +262,39 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             logger.info('%s: no neurons predicted, no traces file.' % name)
             continue
         if bin_frames is not None:
-            T = _n_frames(dspath)
+            T = n_read(dspath)
             logger.info('%s: the refinement and the split read the means of %d consecutive frames: %d binned frames of %d'
                         % (name, bin_frames, T // bin_frames, T))
         if detrend is not None:
-            n = _n_frames(dspath) // (bin_frames or 1)
+            n = n_read(dspath) // (bin_frames or 1)
             plan = detrend_plan(n, detrend)
             logger.info('%s: the refinement and the split correlate within segments of L = %d frames: %d segments over %d frames, L_last = %d'
                         % (name, detrend, len(plan), n, plan[-1][1]))
         if refine is not None:
-            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, bin_frames=bin_frames, detrend_frames=detrend, **moves(dspath))
-            rois, kept = refine_rois(coords, corr, mask.shape, threshold=refine)
+            corr, coords, inside = roi_footprints_device(dspath, mask, halo=halo, bin_frames=bin_frames, detrend_frames=detrend, **kept(dspath))
+            rois, kept_rois = refine_rois(coords, corr, mask.shape, threshold=refine)
             before = [set(map(tuple, c[i].tolist())) for c, i in zip(coords, inside)]
-            after = dict((r, set(map(tuple, c.tolist()))) for r, c in zip(kept, rois))
+            after = dict((r, set(map(tuple, c.tolist()))) for r, c in zip(kept_rois, rois))
             logger.info('%s: refined at corr >= %g (halo %d): %d of %d ROIs dropped, %d pixels removed, %d added' % (
-                name, refine, halo, len(coords) - len(kept), len(coords),
+                name, refine, halo, len(coords) - len(kept_rois), len(coords),
                 sum(len(b - after.get(r, set())) for r, b in enumerate(before)),
-                sum(len(after[r] - before[r]) for r in kept)))
+                sum(len(after[r] - before[r]) for r in kept_rois)))
             if not rois:
                 logger.info('%s: no ROI survives the refinement, no traces file.' % name)
                 continue
             mask = rois
         if split is not None:
             rois, origin, gaps = split_rois_device(dspath, mask, min_gap=split, min_area=min_area, bin_frames=bin_frames, detrend_frames=detrend,
-                                                   **moves(dspath))
+                                                   **kept(dspath))
             before = int(np.count_nonzero(mask)) if isinstance(mask, np.ndarray) else sum(len(r) for r in mask)
             logger.info('%s: split at gap >= %g (min area %d): %d of %d ROIs split, %d pixels dropped' % (
                 name, split, min_area, len(rois) - len(gaps), len(gaps), before - sum(len(r) for r in rois)))
             mask = rois
         if merge is not None:
             rois, origin, pairs, corr = merge_rois_device(dspath, mask, max_dist=merge_dist, threshold=merge, detrend_frames=detrend,
-                                                          **moves(dspath))
+                                                          **kept(dspath))
             logger.info('%s: merged at trace corr >= %g (within %d pixels%s): %d candidate pairs, %d accepted, %d ROIs -> %d' % (
-                name, merge, merge_dist, '' if detrend is None else ', within segments of L = %d of all %d frames' % (detrend, _n_frames(dspath)),
+                name, merge, merge_dist, '' if detrend is None else ', within segments of L = %d of all %d frames' % (detrend, n_read(dspath)),
                 len(pairs), int(np.count_nonzero(corr >= merge)), sum(len(o) for o in origin), len(rois)))
             mask = rois
         if dff is not None:
@@ -328,6 +364,9 @@ if __name__ == '__main__':
                         nargs='?', const=0.8, default=None, type=float, metavar='THR')
     sp_trc.add_argument('--merge-dist', help='with --merge: the largest distance in pixels between two ROIs that may be merged (0..16, default 2)',
                         default=2, type=int, metavar='D', dest='merge_dist')
+    sp_trc.add_argument('--drop-artefacts', help='score every frame first and leave artefact frames (a flash, a gated PMT, a z-jump: mean or template '
+                        'correlation beyond K scaled MADs, default 8) out of the summary, --refine, --split and --merge; the traces keep every frame',
+                        nargs='?', const=8.0, default=None, type=float, metavar='K', dest='drop_artefacts')
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')

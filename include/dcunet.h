@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 123
+#define DC_ABI_VERSION 124
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -742,6 +742,39 @@ int dc_roi_pixel_corr_pooled(const long* pooled_xx, const long* pooled_xs, const
 #define DC_TRACE_PAIR_MAX_PAIRS 16777216L
 int dc_trace_pair_moments(const long* sums, long ld, int R, long T, int seg_len, const int* pairs, long P, long* num, dc_stream_t stream);
 int dc_trace_pair_corr(const long* num, long P, float* corr, dc_stream_t stream);
+
+/* ---- Frame quality: per-frame scores that find artefact frames, and the gather that leaves them out --------------------------------
+ * A stimulation-light flash, a gated (dark) PMT frame, a z-jump: in such a frame ALL pixels move together, so three of them in a
+ * thousand push every pixel-pair and trace-pair correlation towards 1, become the `max` image and inflate `std`.  What finds them
+ * is a score per frame, computed where the frames already are; the rule on the scores is the host's (frames.flag_frames).  The
+ * reference has no counterpart; THESE DEFINITIONS ARE THE SPECIFICATION.  Integers until the last step; the same bits every run
+ * and for every launch geometry.
+ * frames = tc dense H x W frames of 16 bits, int16 or uint16 (is_unsigned); tmpl = NULL or one H x W image of the SAME type (what
+ * make_template returns).  The rectangle is rows [y0, y1), columns [x0, x1) of the frame, n = (y1 - y0) * (x1 - x0) pixels
+ * (valid_rectangle's, or the whole frame); 2-byte alignment of frames and tmpl is all that is asked.
+ *   dc_frame_moments: moments = int64[tc][3] = {a, b, c} per frame over the rectangle: a = sum x, b = sum x^2, c = sum x * tmpl
+ *     (0 with tmpl == NULL).  n <= DC_FRAME_MAX_PIXELS = 2^28 keeps |a| < 2^44, b < 2^60, |c| < 2^60 (csrc/frame_math.h).  The
+ *     rows are zeroed by the call itself (never pre-clear) and the workgroups' partial sums are added with 64-bit integer atomics:
+ *     integer addition, so the order changes no bit.  Nothing at or beyond tc is touched.  The template's own sums ta = sum tmpl,
+ *     tb = sum tmpl^2 are this function run on the template as a chunk of one frame.
+ *   dc_frame_quality: mean[f] = (float)((double)a / (double)n); corr[f] (corr may be NULL) = dc_fp_corr of csrc/footprint_math.h on
+ *     the 128-bit numerators {n b - a a, n c - a ta, n tb - ta ta}: (float)(f64(Nxt) / (sqrt(f64(Nxx)) * sqrt(f64(Ntt)))), each
+ *     numerator rounded ONCE to double, no fused multiply-add: within 1 float32 ulp, in [-1, 1]; exactly 0 for a frame or a
+ *     template that is constant over the rectangle (n == 1 included), exactly 1 for a frame equal to a template that varies,
+ *     exactly -1 for frame = k - tmpl.  THE CALLER TIES THE ARGUMENTS TOGETHER (not checked, nothing here can): n must be the pixel
+ *     count of the very rectangle that was passed to dc_frame_moments for these moments, and ta, tb the template's sums over that
+ *     same rectangle; a mismatch gives wrong means and correlations without an error.
+ *   dc_frame_gather: out[i] = frames[idx[i]] for i < k, a move of 16-bit values; idx = int32[k] in DEVICE memory; an entry outside
+ *     [0, tc) gives an all-zero frame and is never followed.  out must not overlap frames.  k == 0 launches nothing.
+ * Refused: a null pointer that would be followed, a negative or zero size, a rectangle that is empty or leaves the frame, n < 1, a
+ * misaligned buffer (moments 8 bytes, mean / corr / idx 4, frames 2), out overlapping frames: DC_EINVAL (-1); n > 2^28 or
+ * H * W > 2^30: DC_EUNSUP (-3).  tc == 0: 0, nothing launched.  All pointers are DEVICE memory, there are no out-parameters and
+ * nothing is read on the host. */
+#define DC_FRAME_MAX_PIXELS 268435456L
+int dc_frame_moments(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int y0, int y1, int x0, int x1,
+                     long* moments, dc_stream_t stream);
+int dc_frame_quality(const long* moments, int tc, long n, long ta, long tb, float* mean, float* corr, dc_stream_t stream);
+int dc_frame_gather(const void* frames, int tc, const int* idx, int k, int H, int W, void* out, dc_stream_t stream);
 
 /* ---- dF/F traces: neuropil correction, rolling-percentile baseline, (F - F0) / F0 -----------------------------------------------
  * The step between ROI traces and spikes that the z-score above cannot replace: a recording bleaches and drifts, and every ROI
