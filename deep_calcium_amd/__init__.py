@@ -31,6 +31,7 @@ _EXPORTS = {
     'roi_pairs': ('RoiPairCorr', 'roi_pair_corr_device', 'split_rois', 'split_rois_device'),
     'merge': ('TracePairCorr', 'roi_neighbours', 'merge_rois', 'merge_rois_device'),
     'frames': ('FrameQuality', 'FrameFilter', 'frame_quality_device', 'flag_frames', 'hold_index'),
+    'weighted': ('WeightedTraceExtractor', 'weighted_traces_device', 'footprint_weights', 'exclude_overlap', 'roi_gram', 'demix_traces'),
     'dff': ('TraceBaseline', 'neuropil_rois', 'dff_traces_device'),
     'motion': ('MotionCorrector', 'make_template', 'estimate_shifts_device', 'valid_rectangle', 'fine_to_pixels', 'BidiEstimator',
                'pick_bidi', 'estimate_bidi_device'),

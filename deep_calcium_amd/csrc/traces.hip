@@ -7,8 +7,11 @@
 // (series_math.h) and rounded to double once.  Nothing in this file may be contracted into a fused multiply-add or reassociated:
 // the pragma below and the per-file flag in _build.py.
 #pragma clang fp contract(off)
+#include <type_traits>
+
 #include "common.h"
 #include "series_math.h"
+#include "wtrace_math.h"
 
 namespace {
 
@@ -29,6 +32,13 @@ __device__ __forceinline__ int wave_sum(int v) {
   return v;
 }
 
+// the weighted form: not one term w x fits int32 (wtrace_math.h), so the lanes' partial sums and their reduction are 64 bits wide
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
 // columns [t0, t0 + tc) of all R rows <- 0: what the atomic form of the accumulate kernel adds into
 __global__ __launch_bounds__(kThreads) void roi_trace_zero_kernel(int64_t* __restrict__ sums, long ld, long t0, int tc, int R) {
   const long n = (long)R * tc;
@@ -41,12 +51,17 @@ __global__ __launch_bounds__(kThreads) void roi_trace_zero_kernel(int64_t* __res
 // index in flight per lane --, sums in int32, reduces across the wave and adds the piece into its int64 totals.  One value per
 // (row, frame) leaves the workgroup: a plain store when rows are ROIs (row_roi == null), an integer atomic into the column the
 // same call has zeroed when several rows share an ROI (integer addition: the order does not matter).
-template <bool UNS>
+// WGT (dc_roi_wtrace_accumulate): every entry carries a 16-bit weight, staged beside its index; a term is w x, formed and summed in
+// int64 (wtrace_math.h derives why no 32-bit partial survives a weight).  Without WGT nothing differs: no weights in LDS, int32
+// partial sums within a piece.
+template <bool UNS, bool WGT>
 __global__ __launch_bounds__(kThreads) void roi_trace_accumulate_kernel(const uint16_t* __restrict__ frames, int tc, long t0,
                                                                        const int* __restrict__ row_off, const int* __restrict__ row_pix,
-                                                                       const int* __restrict__ row_roi, int R, int64_t* __restrict__ sums,
-                                                                       long ld, long HW, int tiles) {
+                                                                       const uint16_t* __restrict__ row_wgt, const int* __restrict__ row_roi,
+                                                                       int R, int64_t* __restrict__ sums, long ld, long HW, int tiles) {
+  typedef typename std::conditional<WGT, int64_t, int>::type part_t;
   __shared__ int pix[kPiece];
+  __shared__ uint16_t wgt[WGT ? kPiece : 1];
   const int s = blockIdx.x, wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   const long a = row_off[s], b = row_off[s + 1];
   const int r = row_roi ? row_roi[s] : s;
@@ -64,17 +79,25 @@ __global__ __launch_bounds__(kThreads) void roi_trace_accumulate_kernel(const ui
       for (int i = threadIdx.x; i < m; i += kThreads) {
         const int q = row_pix[p0 + i];
         pix[i] = (q >= 0 && q < HW) ? q : -1;
+        if (WGT) wgt[i] = row_wgt[p0 + i];
       }
       __syncthreads();
-      int v[kFpw];
+      part_t v[kFpw];
 #pragma unroll
       for (int k = 0; k < kFpw; ++k) v[k] = 0;
       for (int i = lane; i < m; i += kWave) {
         const int q = pix[i];
         if (q < 0) continue;
+        if (WGT) {
+          const int w = wgt[i];
 #pragma unroll
-        for (int k = 0; k < kFpw; ++k)
-          if (k < nf) v[k] += widen<UNS>(f[(long)k * HW + q]);
+          for (int k = 0; k < kFpw; ++k)
+            if (k < nf) v[k] += dc_wtrace_term(w, widen<UNS>(f[(long)k * HW + q]));
+        } else {
+#pragma unroll
+          for (int k = 0; k < kFpw; ++k)
+            if (k < nf) v[k] += widen<UNS>(f[(long)k * HW + q]);
+        }
       }
 #pragma unroll
       for (int k = 0; k < kFpw; ++k) acc[k] += wave_sum(v[k]);
@@ -145,39 +168,61 @@ __global__ __launch_bounds__(kThreads) void roi_trace_finalize_kernel(const int6
 
 }  // namespace
 
-extern "C" int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
-                                       const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream) {
-  DC_REQUIRE(frames && row_off && row_pix && sums, DC_EINVAL, "dc_roi_trace_accumulate: null pointer");
-  DC_REQUIRE(S >= 0 && R >= 0 && tc >= 0 && t0 >= 0, DC_EINVAL, "dc_roi_trace_accumulate: negative count (S %d, R %d, tc %d, t0 %ld)", S, R,
-             tc, t0);
-  DC_REQUIRE(row_roi || S == R, DC_EINVAL, "dc_roi_trace_accumulate: without row_roi every CSR row is an ROI, but S = %d and R = %d", S, R);
-  DC_REQUIRE(ld >= t0 + tc, DC_EINVAL, "dc_roi_trace_accumulate: ld = %ld is below t0 + tc = %ld", ld, t0 + tc);
-  DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "dc_roi_trace_accumulate: image %d x %d out of range", H, W);
-  DC_REQUIRE((((uintptr_t)frames) & 1) == 0 && (((uintptr_t)row_off | (uintptr_t)row_pix | (uintptr_t)row_roi) & 3) == 0 &&
-             (((uintptr_t)sums) & 7) == 0, DC_EINVAL, "dc_roi_trace_accumulate: misaligned buffer");
+// the two accumulate entry points: one set of checks and one launch, row_wgt == null for the unweighted one
+static int roi_accumulate(const char* who, bool weighted, const void* frames, int is_unsigned, int tc, long t0, const int* row_off,
+                          const int* row_pix, const unsigned short* row_wgt, const int* row_roi, int S, int R, long* sums, long ld, int H, int W,
+                          dc_stream_t stream) {
+  DC_REQUIRE(frames && row_off && row_pix && sums && (row_wgt || !weighted), DC_EINVAL, "%s: null pointer", who);
+  DC_REQUIRE(S >= 0 && R >= 0 && tc >= 0 && t0 >= 0, DC_EINVAL, "%s: negative count (S %d, R %d, tc %d, t0 %ld)", who, S, R, tc, t0);
+  DC_REQUIRE(row_roi || S == R, DC_EINVAL, "%s: without row_roi every CSR row is an ROI, but S = %d and R = %d", who, S, R);
+  DC_REQUIRE(ld >= t0 + tc, DC_EINVAL, "%s: ld = %ld is below t0 + tc = %ld", who, ld, t0 + tc);
+  DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "%s: image %d x %d out of range", who, H, W);
+  DC_REQUIRE(((((uintptr_t)frames) | (uintptr_t)row_wgt) & 1) == 0 && (((uintptr_t)row_off | (uintptr_t)row_pix | (uintptr_t)row_roi) & 3) == 0 &&
+             (((uintptr_t)sums) & 7) == 0, DC_EINVAL, "%s: misaligned buffer", who);
   const long HW = (long)H * W;
-  DC_REQUIRE(t0 + tc <= DC_ROI_TRACE_MAX_VOLUME / HW, DC_EUNSUP,
-             "dc_roi_trace_accumulate: %ld frames of %d x %d: T * H * W is limited to 2^46 = %ld", t0 + tc, H, W, (long)DC_ROI_TRACE_MAX_VOLUME);
+  DC_REQUIRE(t0 + tc <= DC_ROI_TRACE_MAX_VOLUME / HW, DC_EUNSUP, "%s: %ld frames of %d x %d: T * H * W is limited to 2^46 = %ld", who, t0 + tc, H, W,
+             (long)DC_ROI_TRACE_MAX_VOLUME);
   if (R == 0 || tc == 0) return DC_OK;
   int64_t* out = (int64_t*)sums;
   if (row_roi) {
     const long n = (long)R * tc;
     const int blocks = (int)(dc_cdiv(n, kThreads) < kZeroBlocks ? dc_cdiv(n, kThreads) : kZeroBlocks);
     hipLaunchKernelGGL(roi_trace_zero_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, out, ld, t0, tc, R);
-    DC_CHECK_LAUNCH("dc_roi_trace_accumulate(zero)");
+    char zero_name[64];
+    snprintf(zero_name, sizeof zero_name, "%s(zero)", who);
+    DC_CHECK_LAUNCH(zero_name);
     if (S == 0) return DC_OK;
   }
   const int tiles = dc_cdiv(tc, kTile);
   const dim3 grid((unsigned)S, (unsigned)(tiles < 65535 ? tiles : 65535)), block(kThreads);
   const uint16_t* f = (const uint16_t*)frames;
-  if (is_unsigned)
-    hipLaunchKernelGGL((roi_trace_accumulate_kernel<true>), grid, block, 0, (hipStream_t)stream, f, tc, t0, row_off, row_pix, row_roi, R, out,
-                       ld, HW, tiles);
-  else
-    hipLaunchKernelGGL((roi_trace_accumulate_kernel<false>), grid, block, 0, (hipStream_t)stream, f, tc, t0, row_off, row_pix, row_roi, R, out,
-                       ld, HW, tiles);
-  DC_CHECK_LAUNCH("dc_roi_trace_accumulate");
+  const uint16_t* w = (const uint16_t*)row_wgt;
+#define DC_ROI_ACC(UNS, WGT)                                                                                                              \
+  hipLaunchKernelGGL((roi_trace_accumulate_kernel<UNS, WGT>), grid, block, 0, (hipStream_t)stream, f, tc, t0, row_off, row_pix, w, row_roi, R, \
+                     out, ld, HW, tiles)
+  if (weighted) {
+    if (is_unsigned) DC_ROI_ACC(true, true);
+    else DC_ROI_ACC(false, true);
+  } else {
+    if (is_unsigned) DC_ROI_ACC(true, false);
+    else DC_ROI_ACC(false, false);
+  }
+#undef DC_ROI_ACC
+  DC_CHECK_LAUNCH(who);
   return DC_OK;
+}
+
+extern "C" int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
+                                       const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream) {
+  return roi_accumulate("dc_roi_trace_accumulate", false, frames, is_unsigned, tc, t0, row_off, row_pix, nullptr, row_roi, S, R, sums, ld, H, W,
+                        stream);
+}
+
+extern "C" int dc_roi_wtrace_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
+                                        const unsigned short* row_wgt, const int* row_roi, int S, int R, long* sums, long ld, int H, int W,
+                                        dc_stream_t stream) {
+  return roi_accumulate("dc_roi_wtrace_accumulate", true, frames, is_unsigned, tc, t0, row_off, row_pix, row_wgt, row_roi, S, R, sums, ld, H, W,
+                        stream);
 }
 
 extern "C" int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,

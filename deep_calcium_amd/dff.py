@@ -324,11 +324,13 @@ class TraceBaseline(object):
 
 
 def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=None, offset=0, source='series/raw', device=None,
-                      chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
+                      chunk_frames=None, weights=None, shifts=None, fine_shifts=None, bidi=0):
     """The (R, T) dF/F traces (or any other kind of KINDS) of `rois` over `source` of a dataset file.  neuropil: None, or
     (inner, outer, weight): every ROI is corrected by its ring neuropil_rois(rois, shape, inner, outer).  The recording is read
     ONCE, by a single RoiTraceExtractor whose ROI list is the ROIs followed by the non-empty rings; combine, baseline and scale
-    then run on the sums where they lie.  shifts / fine_shifts / bidi: as for extract_traces_device."""
+    then run on the sums where they lie.  shifts / fine_shifts / bidi: as for extract_traces_device.
+    weights: None, or one integer array per ROI (weighted.WeightedTraceExtractor; rois is then a list of (k,2) arrays or region dicts):
+    the ROI sums are the weighted ones and the weight sum W_r stands where the area stood.  The rings stay unweighted."""
     from .series import _open_series
     from .traces import RoiTraceExtractor
     _check_kind(kind)
@@ -351,9 +353,15 @@ def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=N
             raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         shape = _check_shape(frames.shape[1:])
-        pixels = _roi_pixels(rois, shape)
+        if weights is not None:
+            from .weighted import _check_wsums, _weighted_entries
+            entries = _weighted_entries(rois, weights, shape)
+            pixels = [f.astype(np.int32) for f, _ in entries]
+            areas = _check_wsums(entries, T)                             # W_r
+        else:
+            pixels = _roi_pixels(rois, shape)
+            areas = np.array([len(p) for p in pixels], np.int64)
         R = len(pixels)
-        areas = np.array([len(p) for p in pixels], np.int64)
         ring_rows, ring_areas = np.full(R, -1, np.int64), np.zeros(R, np.int64)
         every = [np.stack([p // shape[1], p % shape[1]], 1) for p in pixels]
         if neuropil is not None:
@@ -362,8 +370,14 @@ def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=N
                     ring_rows[r], ring_areas[r] = len(every), len(ring)
                     every.append(ring)
         combine_coefficients(areas, ring_areas, weight, offset)          # An * A over the limit: before the pass, not after it
-        ext = RoiTraceExtractor(shape, T, frames.dtype, every, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                fine_shifts=fine_shifts, bidi=bidi)
+        if weights is not None:                                          # one weighted pass: a ring pixel has weight 1
+            from .weighted import WeightedTraceExtractor
+            every_w = [w for _, w in entries] + [np.ones(len(c), np.int64) for c in every[R:]]
+            ext = WeightedTraceExtractor(shape, T, frames.dtype, every, every_w, device=device, chunk_frames=chunk_frames, shifts=shifts,
+                                         fine_shifts=fine_shifts, bidi=bidi)
+        else:
+            ext = RoiTraceExtractor(shape, T, frames.dtype, every, device=device, chunk_frames=chunk_frames, shifts=shifts,
+                                    fine_shifts=fine_shifts, bidi=bidi)
         for a in range(0, T, ext.chunk_frames):
             ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
         tb = TraceBaseline.from_stacked(ext.sums_device(), areas, ring_rows, ring_areas, window, percentile=percentile, offset=offset,

@@ -161,13 +161,16 @@ class RoiTraceExtractor(object):
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
 
-    def _accumulate(self, fp, tc, st):
+    def _launch(self, fp, tc, t0, st):
+        """The sums of one chunk (weighted.WeightedTraceExtractor: the weighted entry point instead)."""
         H, W = self.shape
+        self.L.dc_roi_trace_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, t0, self._row_off.data_ptr(),
+                                       self._row_pix.data_ptr(), self._row_roi.data_ptr(), self._rows, self.n_rois,
+                                       self.sums.data_ptr(), self.n_frames, H, W, st)
 
+    def _accumulate(self, fp, tc, st):
         def accumulate(fp, tc, t0):
-            self.L.dc_roi_trace_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, t0, self._row_off.data_ptr(),
-                                           self._row_pix.data_ptr(), self._row_roi.data_ptr(), self._rows, self.n_rois,
-                                           self.sums.data_ptr(), self.n_frames, H, W, st)
+            self._launch(fp, tc, t0, st)
             if self._after_chunk is not None:     # a second reader of the same frames, behind the sums (footprints.RoiFootprints)
                 self._after_chunk(fp, tc, t0, st)
         if self._shifted is None:

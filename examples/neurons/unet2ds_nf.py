@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -33,7 +33,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
                               estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
-                              split_rois_device, detrend_plan, merge_rois_device, make_template, frame_quality_device, flag_frames)
+                              split_rois_device, detrend_plan, merge_rois_device, make_template, frame_quality_device, flag_frames,
+                              footprint_weights, exclude_overlap, weighted_traces_device)
+from deep_calcium_amd.weighted import shared_pixels            # noqa: E402
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -133,7 +135,7 @@ def _n_frames(dspath):
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
-           bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None):
+           bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None, weighted=None, overlap='keep'):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -171,7 +173,13 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     template is the registration's, or without one the rounded mean of the first 200 frames.  Frames whose mean lies more than K
     scaled median absolute deviations from the median, or whose correlation lies that far BELOW it (deep_calcium_amd.flag_frames),
     are artefact frames -- a stimulation flash, a gated PMT, a z-jump: the summary the network segments, the refinement, the split
-    and the merge leave them out (`keep=`).  The traces that are written keep every frame."""
+    and the merge leave them out (`keep=`).  The traces that are written keep every frame.
+    weighted=FLOOR: after the refinement, the split and the merge, one more footprint pass over the final ROIs; every pixel gets the
+    weight floor(256 max(corr, 0) + 0.5) of its correlation with its ROI's trace (deep_calcium_amd.footprint_weights; pixels with
+    corr < FLOOR or weight 0 are dropped, ROIs left empty too) and the traces are the weighted ones (kind, or dF/F with the weight
+    sum where the area stood).  overlap (with weighted): 'keep' -- a pixel two ROIs share counts for both --, 'exclude' -- shared
+    pixels are dropped from all --, 'demix' -- the least-squares coefficients of the footprints (deep_calcium_amd.demix_traces,
+    float64; z-scored with --kind zscore); not together with dff, whose kernels take integers."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -197,6 +205,14 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--merge joins ROIs whose traces correlate at THR or above: THR must be a number, not NaN')
     if drop_artefacts is not None and not drop_artefacts > 0:
         raise ValueError('--drop-artefacts flags frames beyond K scaled median absolute deviations, K > 0, not %r' % (drop_artefacts,))
+    if overlap not in ('keep', 'exclude', 'demix'):
+        raise ValueError('--overlap is keep, exclude or demix, not %r' % (overlap,))
+    if overlap != 'keep' and weighted is None:
+        raise ValueError('--overlap needs --weighted')
+    if overlap == 'demix' and dff is not None:
+        raise ValueError('--overlap demix gives float64 coefficients, --dff takes integer sums: not together')
+    if weighted is not None and weighted != weighted:
+        raise ValueError('--weighted drops pixels whose correlation is below FLOOR: FLOOR must be a number, not NaN')
     if not 0 <= merge_dist <= 16:
         raise ValueError('--merge-dist is the largest gap between two fragments in pixels, D in [0, 16], not %d' % merge_dist)
     known = 'fine_shifts' if subpixel else 'shifts'
@@ -297,7 +313,28 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                 name, merge, merge_dist, '' if detrend is None else ', within segments of L = %d of all %d frames' % (detrend, n_read(dspath)),
                 len(pairs), int(np.count_nonzero(corr >= merge)), sum(len(o) for o in origin), len(rois)))
             mask = rois
-        if dff is not None:
+        if weighted is not None:
+            corr, coords, inside = roi_footprints_device(dspath, mask, halo=0, bin_frames=bin_frames, detrend_frames=detrend, **kept(dspath))
+            rois, weights, kept_rois = footprint_weights(coords, corr, inside=inside, floor=weighted)
+            if not rois:
+                logger.info('%s: no pixel reaches corr >= %g, no traces file.' % (name, weighted))
+                continue
+            frame_shape = np.asarray(mp).shape[-2:]
+            found = shared_pixels(rois, frame_shape)
+            logger.info('%s: weighted at corr >= %g: %d of %d ROIs kept, %d pixels dropped, %d shared pixels found (--overlap %s)' % (
+                name, weighted, len(kept_rois), len(coords), sum(int(i.sum()) for i in inside) - sum(len(r) for r in rois), found, overlap))
+            if overlap == 'exclude':
+                rois, weights, kept_rois = exclude_overlap(rois, frame_shape, weights)
+                if not rois:
+                    logger.info('%s: every pixel is shared, no traces file.' % name)
+                    continue
+            if dff is not None:
+                tr = dff_traces_device(dspath, rois, dff, percentile=percentile, neuropil=neuropil, weights=weights, **moves(dspath))
+            elif overlap == 'demix':
+                tr = weighted_traces_device(dspath, rois, weights, kind='zscore' if kind == 'zscore' else 'demix', overlap='demix', **moves(dspath))
+            else:
+                tr = weighted_traces_device(dspath, rois, weights, kind=kind, **moves(dspath))
+        elif dff is not None:
             tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **moves(dspath))
         else:
             tr = extract_traces_device(dspath, mask, kind=kind, **moves(dspath))
@@ -367,8 +404,17 @@ if __name__ == '__main__':
     sp_trc.add_argument('--drop-artefacts', help='score every frame first and leave artefact frames (a flash, a gated PMT, a z-jump: mean or template '
                         'correlation beyond K scaled MADs, default 8) out of the summary, --refine, --split and --merge; the traces keep every frame',
                         nargs='?', const=8.0, default=None, type=float, metavar='K', dest='drop_artefacts')
+    sp_trc.add_argument('--weighted', help='weight every pixel of the final ROIs by its correlation with its ROI\'s trace (one more footprint pass; '
+                        'pixels below FLOOR, default 0, are dropped) and write weighted traces; with --dff the weights are used there',
+                        nargs='?', const=0.0, default=None, type=float, metavar='FLOOR')
+    sp_trc.add_argument('--overlap', help='with --weighted: pixels that two ROIs share count for both (keep), are dropped (exclude) or are '
+                        'demixed by least squares (demix: float64 coefficients; not with --dff)', default='keep', choices=('keep', 'exclude', 'demix'))
     args = vars(ap.parse_args())
     if 'which' not in args:
         ap.error('choose an action: train, evaluate, predict or traces')
+    if args['which'] == 'traces' and args['overlap'] == 'demix' and args['dff'] is not None:
+        ap.error('--overlap demix gives float64 coefficients, --dff takes integer sums: not together')
+    if args['which'] == 'traces' and args['overlap'] != 'keep' and args['weighted'] is None:
+        ap.error('--overlap needs --weighted')
     f = {'train': training, 'evaluate': evaluation, 'predict': prediction, 'traces': traces}[args.pop('which')]
     f(**args)

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 124
+#define DC_ABI_VERSION 125
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -575,6 +575,23 @@ int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0
                             const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);
 int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,
                           dc_stream_t stream);
+
+/* ---- Weighted ROI traces: every entry of an ROI carries a 16-bit weight --------------------------------------------------------
+ * dc_roi_wtrace_accumulate is dc_roi_trace_accumulate, word for word, with one more array: row_wgt uint16[row_off[S]], DEVICE
+ * memory, 2-byte aligned, row_wgt[e] the weight of entry e of row_pix.  sums[r][t0 + t] = the exact int64 sum of w_e * x_e over
+ * ROI r's entries in frame t.  ANY uint16 weight is legal: |w x| <= 65535^2 < 2^32, and at most 2^30 entries per ROI keep
+ * |S| < 2^62 (csrc/wtrace_math.h derives what 32 bits can hold of this: nothing, so the kernel sums in int64 from the first term).
+ * Everything else is inherited: an index outside [0, H*W) contributes 0 and is never dereferenced; an index listed twice counts
+ * once per listing, each with its own weight; an empty row, a row_roi outside [0, R) and row_roi == NULL with S == R behave as
+ * above; columns [t0, t0 + tc) of ALL R rows are fully written and nothing else is touched; the same bits for every chunking,
+ * every cut of ROIs into rows, every launch geometry and every run.  Error codes as above; a null or odd-address row_wgt:
+ * DC_EINVAL.
+ * The weight sum W_r = sum of w over ROI r stands where the area stood in dc_roi_trace_finalize, dc_trace_baseline* and
+ * dc_trace_pair_*: mean = S / W is the weighted mean, the z-score is area-free, and |S| <= 65535 W holds term by term.  THE CALLER
+ * PROMISES 1 <= W_r <= 2^31 - 1 and T * W_r <= 2^46 (the volume limit above, with W for H * W). */
+int dc_roi_wtrace_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
+                             const unsigned short* row_wgt, const int* row_roi, int S, int R, long* sums, long ld, int H, int W,
+                             dc_stream_t stream);
 
 /* ---- ROI footprint maps: the correlation of every pixel of an ROI's support with the ROI's own trace ---------------------------
  * The one decision of the chain that never looks at the recording is which pixels belong to a neuron (the ROIs are the regions
