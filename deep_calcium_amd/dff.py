@@ -26,7 +26,8 @@ Importing this module needs neither torch nor the GPU; constructing a TraceBasel
 """
 import numpy as np
 
-from .traces import _check_shape, _roi_pixels
+from ._reader import _read_recording
+from .traces import RoiTraceExtractor, _check_shape, _roi_pixels
 
 KINDS = ('num', 'baseline_sum', 'f', 'baseline', 'dff')
 MAX_HALF = 2047                       # DC_TRACE_BASELINE_MAX_HALF: the longest window is 4095 frames
@@ -331,8 +332,6 @@ def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=N
     then run on the sums where they lie.  shifts / fine_shifts / bidi: as for extract_traces_device.
     weights: None, or one integer array per ROI (weighted.WeightedTraceExtractor; rois is then a list of (k,2) arrays or region dicts):
     the ROI sums are the weighted ones and the weight sum W_r stands where the area stood.  The rings stay unweighted."""
-    from .series import _open_series
-    from .traces import RoiTraceExtractor
     _check_kind(kind)
     window_half(window)
     _check_percentile(percentile)
@@ -345,14 +344,11 @@ def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=N
             raise ValueError('neuropil must be None or (inner, outer, weight), not %r' % (neuropil,))
         inner, outer = _check_ring(inner, outer)
         weight_256ths(weight)
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        shape = _check_shape(frames.shape[1:])
+    stacked = []
+
+    def reader_of(shape, T, dtype, **kw):
+        """One extractor whose ROI list is the ROIs followed by the non-empty rings, built from the shape before the pass."""
+        shape = _check_shape(shape)
         if weights is not None:
             from .weighted import _check_wsums, _weighted_entries
             entries = _weighted_entries(rois, weights, shape)
@@ -370,20 +366,12 @@ def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=N
                     ring_rows[r], ring_areas[r] = len(every), len(ring)
                     every.append(ring)
         combine_coefficients(areas, ring_areas, weight, offset)          # An * A over the limit: before the pass, not after it
-        if weights is not None:                                          # one weighted pass: a ring pixel has weight 1
-            from .weighted import WeightedTraceExtractor
-            every_w = [w for _, w in entries] + [np.ones(len(c), np.int64) for c in every[R:]]
-            ext = WeightedTraceExtractor(shape, T, frames.dtype, every, every_w, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                         fine_shifts=fine_shifts, bidi=bidi)
-        else:
-            ext = RoiTraceExtractor(shape, T, frames.dtype, every, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                    fine_shifts=fine_shifts, bidi=bidi)
-        for a in range(0, T, ext.chunk_frames):
-            ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
-        tb = TraceBaseline.from_stacked(ext.sums_device(), areas, ring_rows, ring_areas, window, percentile=percentile, offset=offset,
-                                        weight=weight, device=ext.device)
-        out = tb.result(kind)
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
-    return out
+        stacked.extend((areas, ring_rows, ring_areas))
+        if weights is None:
+            return RoiTraceExtractor(shape, T, dtype, every, **kw)
+        from .weighted import WeightedTraceExtractor                     # one weighted pass: a ring pixel has weight 1
+        return WeightedTraceExtractor(shape, T, dtype, every, [w for _, w in entries] + [np.ones(len(c), np.int64) for c in every[R:]], **kw)
+    ext = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi)
+    areas, ring_rows, ring_areas = stacked
+    return TraceBaseline.from_stacked(ext.sums_device(), areas, ring_rows, ring_areas, window, percentile=percentile, offset=offset,
+                                      weight=weight, device=ext.device).result(kind)

@@ -31,8 +31,9 @@ Importing this module needs neither torch nor the GPU; constructing a RoiFootpri
 """
 import numpy as np
 
+from ._reader import _check_n_frames, _read_recording
 from .dff import _as_int, _dilate
-from .traces import MAX_VOLUME, RoiTraceExtractor, _check_shape, _roi_pixels, rois_to_csr
+from .traces import MAX_VOLUME, _LeadingExtractor, _check_shape, _roi_pixels, rois_to_csr
 
 KINDS = ('moments', 'corr', 'coherence')
 MAX_HALO = 16
@@ -140,9 +141,7 @@ class RoiFootprints(object):
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
         halo = _check_halo(halo)
-        n_frames = int(n_frames)
-        if n_frames < 1 or n_frames * shape[0] * shape[1] > MAX_VOLUME:
-            raise ValueError('n_frames must be >= 1 with n_frames * H * W <= 2**46, not %d' % n_frames)
+        n_frames = _check_n_frames(n_frames, shape, max_volume=MAX_VOLUME)
         if n_frames > MAX_FRAMES:
             raise ValueError('n_frames must be <= 2**31 - 1, not %d' % n_frames)
         self._seg = None
@@ -157,10 +156,9 @@ class RoiFootprints(object):
         self._bounds = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
         self.halo, self.n_entries = halo, int(self._bounds[-1])
         own = [np.stack([p.astype(np.int64) // shape[1], p.astype(np.int64) % shape[1]], 1) for p in pixels]
-        self._ext = ext = RoiTraceExtractor(shape, n_frames, dtype, own, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                            fine_shifts=fine_shifts, bidi=bidi)
-        ext._stage_tag = 'footprints_stage'          # slots of its own: an extractor alive at the same time keeps its own
-        ext._after_chunk = self._accumulate
+        # slots of its own: an extractor alive at the same time keeps its own
+        self._ext = ext = _LeadingExtractor('footprints_stage', self._accumulate, shape, n_frames, dtype, own, device=device,
+                                            chunk_frames=chunk_frames, shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
         self.shape, self.n_frames, self.dtype, self.n_rois = shape, n_frames, ext.dtype, ext.n_rois
         self.chunk_frames, self.device, self.L = ext.chunk_frames, ext.device, ext.L
         torch = self._torch = ext._torch
@@ -279,39 +277,12 @@ def roi_footprints_device(dspath, rois, halo=2, source='series/raw', device=None
     binned frames.  Results at different L are not comparable with each other or with None.  keep: None, or a (T,) array of booleans
     (frames.flag_frames): the frames marked False are left out after bidi and the shifts and before binning and detrending, whose b
     and L then count kept frames; all True gives what None gives."""
-    from .series import _check_bin_frames, _check_detrend_frames, _feed_binned, _open_series
+    from .series import _check_detrend_frames
     _check_halo(halo)
     if detrend_frames is not None:
         _check_detrend_frames(detrend_frames)
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    if bin_frames is not None:
-        _check_bin_frames(bin_frames)
-    if keep is not None:
-        from .frames import _check_keep, _feed_kept
-        keep = _check_keep(keep)
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        if keep is not None:
-            fp = _feed_kept(frames, keep, bin_frames, lambda n, dev: RoiFootprints(tuple(frames.shape[1:]), n, frames.dtype, rois, halo=halo,
-                                                                                   device=dev, chunk_frames=chunk_frames,
-                                                                                   detrend_frames=detrend_frames),
-                            device, chunk_frames, shifts, fine_shifts, bidi)
-        elif bin_frames is None:
-            fp = RoiFootprints(tuple(frames.shape[1:]), T, frames.dtype, rois, halo=halo, device=device, chunk_frames=chunk_frames,
-                               shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
-            for a in range(0, T, fp.chunk_frames):
-                fp.feed(np.asarray(frames[a:a + fp.chunk_frames]))
-        else:
-            fp = _feed_binned(frames, bin_frames, lambda n, dev: RoiFootprints(tuple(frames.shape[1:]), n, frames.dtype, rois, halo=halo,
-                                                                               device=dev, chunk_frames=chunk_frames,
-                                                                               detrend_frames=detrend_frames),
-                              device, chunk_frames, shifts, fine_shifts, bidi)
-        out = fp.result('corr'), fp.support(), fp.inside()
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
-    return out
+
+    def reader_of(shape, n_frames, dtype, **kw):
+        return RoiFootprints(shape, n_frames, dtype, rois, halo=halo, detrend_frames=detrend_frames, **kw)
+    fp = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi, bin_frames, keep)
+    return fp.result('corr'), fp.support(), fp.inside()

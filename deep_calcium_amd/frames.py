@@ -28,8 +28,7 @@ Importing this module needs neither torch nor the GPU; constructing a FrameQuali
 """
 import numpy as np
 
-from .series import (_CHUNK_BYTES, MAX_FRAMES, _check_bidi, _check_device_frames, _check_known_shifts, _frame_dtype, _open_series,
-                     _ShiftedChunks, _TwoSlotStage)
+from ._reader import _FrameReader, _check_device_frames, _is_device_tensor, _read_recording
 
 KINDS = ('moments', 'mean', 'corr')
 MAX_PIXELS = 1 << 28                  # DC_FRAME_MAX_PIXELS: the pixels of the rectangle up to which the int64 sums hold
@@ -38,25 +37,6 @@ MAX_PIXELS = 1 << 28                  # DC_FRAME_MAX_PIXELS: the pixels of the r
 def _check_kind(kind):
     if kind not in KINDS:
         raise ValueError('frame quality kind %r is not one of %s' % (kind, ', '.join(KINDS)))
-
-
-def _check_frame_args(shape, n_frames, dtype, chunk_frames):
-    try:
-        shape = tuple(int(v) for v in shape)
-    except TypeError:
-        raise ValueError('shape must be (H, W), not %r' % (shape,))
-    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] > (1 << 30):
-        raise ValueError('shape must be (H, W) with 1 <= H * W <= 2**30, not %r' % (shape,))
-    n_frames = int(n_frames)
-    if not 1 <= n_frames <= MAX_FRAMES:
-        raise ValueError('n_frames must be in [1, %d], not %d' % (MAX_FRAMES, n_frames))
-    dtype = _frame_dtype(dtype)
-    if chunk_frames is None:
-        chunk_frames = max(1, _CHUNK_BYTES // (2 * shape[0] * shape[1]))
-    chunk_frames = int(chunk_frames)
-    if chunk_frames < 1:
-        raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-    return shape, n_frames, dtype, min(chunk_frames, n_frames)
 
 
 def _check_rect(rect, shape):
@@ -138,44 +118,10 @@ def hold_index(keep):
     return kept[np.maximum(pos, 0)]
 
 
-def _is_device_tensor(x):
-    return not isinstance(x, np.ndarray) and hasattr(x, 'is_cuda') and hasattr(x, 'data_ptr')
-
-
-def _check_feed(owner, frames, name):
-    """The argument of a feed(): shape, dtype and count against the declaration -> whether it lies on the device."""
-    on_device = _is_device_tensor(frames)
-    if not on_device and not isinstance(frames, np.ndarray):
-        raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
-    if len(frames.shape) != 3 or tuple(frames.shape[1:]) != owner.shape:
-        raise ValueError('frames must be (t, %d, %d), not %r' % (owner.shape + (tuple(frames.shape),)))
-    if on_device:
-        _check_device_frames(owner._torch, frames, owner.dtype, owner.device, name)
-    elif frames.dtype != owner.dtype:
-        raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, owner.dtype))
-    if frames.shape[0] < 1 or owner.fed + frames.shape[0] > owner.n_frames:
-        raise ValueError('%d frames after %d fed: the recording was declared to have %d' % (frames.shape[0], owner.fed, owner.n_frames))
-    return on_device
-
-
-def _open_device(owner, device, name):
-    import torch
-    from . import net
-    from ._lib import lib
-    owner._torch, owner._net = torch, net
-    owner.L = lib()
-    if not torch.cuda.is_available():
-        from ._lib import DcunetError
-        raise DcunetError('%s needs a GPU (there is no CPU fallback)' % name)
-    owner.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    if owner.device.index is None:
-        owner.device = torch.device('cuda', torch.cuda.current_device())
-    return torch
-
-
-class FrameQuality(object):
+class FrameQuality(_FrameReader):
     """Owns the per-frame sums of one recording; feed() the frames in order, in chunks of any size, then result().  Chunk
     boundaries never change a bit."""
+    _stage_tag, _noun = 'fqual_stage', 'frame quality'
 
     def __init__(self, shape, n_frames, dtype, template=None, rect=None, shifts=None, fine_shifts=None, bidi=0, device=None, chunk_frames=None):
         """template: None, or the (H, W) image of the recording's dtype the frames are correlated with (motion.make_template's,
@@ -184,7 +130,8 @@ class FrameQuality(object):
         frame really holds, at most 2**28.  shifts / fine_shifts / bidi: as for SeriesSummarizer, applied BEFORE the sums: the
         scores are those of the corrected frames."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
-        shape, n_frames, self.dtype, chunk = _check_frame_args(shape, n_frames, dtype, chunk_frames)
+        self._declare(shape, n_frames, dtype, chunk_frames, shifts, fine_shifts, bidi)
+        shape = self.shape
         self.rect = _check_rect(rect, shape)
         tmpl_on_device = template is not None and _is_device_tensor(template)
         if template is not None and not tmpl_on_device:
@@ -194,16 +141,11 @@ class FrameQuality(object):
                                                                                                                tuple(template.shape))))
         elif tmpl_on_device and tuple(template.shape) != shape:
             raise ValueError('template must be a %d x %d image, not %r' % (shape + (tuple(template.shape),)))
-        shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
-        bidi = _check_bidi(bidi, shape)
-        self.shape, self.n_frames, self.chunk_frames = shape, n_frames, chunk
         self.n_pixels = (self.rect[1] - self.rect[0]) * (self.rect[3] - self.rect[2])
-        self.fed = 0
 
-        torch = _open_device(self, device, 'FrameQuality')
+        torch = self._open(device, 'FrameQuality')
         dev = self.device
         H, W = shape
-        uns = int(self.dtype == np.dtype(np.uint16))
         self._tmpl, self._tsums = None, None
         with torch.cuda.device(dev):
             if template is not None:
@@ -214,44 +156,15 @@ class FrameQuality(object):
                     self._tmpl = torch.from_numpy(np.ascontiguousarray(template).view(np.int16)).to(dev)
                 # ta = sum tmpl, tb = sum tmpl^2 over the rectangle: the template as a chunk of one frame
                 self._tsums = torch.empty((1, 3), dtype=torch.int64, device=dev)
-                self.L.dc_frame_moments(self._tmpl.data_ptr(), uns, 1, None, H, W, self.rect[0], self.rect[1], self.rect[2], self.rect[3],
+                self.L.dc_frame_moments(self._tmpl.data_ptr(), self._unsigned, 1, None, H, W, self.rect[0], self.rect[1], self.rect[2], self.rect[3],
                                         self._tsums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
             # rows [0, fed) are written, each by the call that reads its frame: never cleared here
-            self._moments = torch.empty((n_frames, 3), dtype=torch.int64, device=dev)
-        self._stage = None
-        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (chunk, H, W), fine, uns, bidi)
+            self._moments = torch.empty((self.n_frames, 3), dtype=torch.int64, device=dev)
 
-    def feed(self, frames):
-        """The next frames of the recording, any t >= 1: what SeriesSummarizer.feed takes (numpy or memmap chunks of the
-        recording's dtype, staged through two pinned slots; or a contiguous (t, H, W) torch.int16 tensor on the device, read in
-        place)."""
-        on_device = _check_feed(self, frames, 'frame quality')
-        torch, L = self._torch, self.L
-        H, W = self.shape
-        y0, y1, x0, x1 = self.rect
-        uns = int(self.dtype == np.dtype(np.uint16))
-        with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream(self.device)
-            st = main.cuda_stream
-
-            def moments(fp, tc, t0):
-                L.dc_frame_moments(fp, uns, tc, self._tmpl.data_ptr() if self._tmpl is not None else None, H, W, y0, y1, x0, x1,
-                                   self._moments.data_ptr() + 24 * t0, st)
-
-            def consume(fp, tc):
-                if self._shifted is None:
-                    moments(fp, tc, self.fed)
-                else:
-                    self._shifted.run(fp, tc, self.fed, st, moments)
-                self.fed += tc
-            if on_device:
-                consume(frames.data_ptr(), int(frames.shape[0]))
-                frames.record_stream(main)
-            else:
-                if self._stage is None:          # names of its own: a reader alive at the same time keeps its slots
-                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'fqual_stage', (self.chunk_frames, H, W))
-                self._stage.run(frames, main, consume)
-        return self
+    def _chunk(self, fp, tc, t0, st):
+        (H, W), (y0, y1, x0, x1) = self.shape, self.rect
+        self.L.dc_frame_moments(fp, self._unsigned, tc, self._tmpl.data_ptr() if self._tmpl is not None else None, H, W, y0, y1, x0, x1,
+                                self._moments.data_ptr() + 24 * t0, st)
 
     def result_device(self, kind):
         """result(kind) as a tensor on the device, for the frames fed so far."""
@@ -282,113 +195,52 @@ def frame_quality_device(dspath, template=None, rect=None, source='series/raw', 
                          bidi=0):
     """-> (mean, corr or None), float32 (T,) each: the scores of every frame of `source` of a dataset file, streamed chunk by
     chunk through a FrameQuality; the recording is read once.  corr is None without a template."""
-    _check_bidi(bidi)
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        fq = FrameQuality(tuple(frames.shape[1:]), T, frames.dtype, template=template, rect=rect, shifts=shifts, fine_shifts=fine_shifts,
-                          bidi=bidi, device=device, chunk_frames=chunk_frames)
-        for a in range(0, T, fq.chunk_frames):
-            fq.feed(np.asarray(frames[a:a + fq.chunk_frames]))
-        out = fq.result('mean'), (fq.result('corr') if template is not None else None)
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
-    return out
+    def reader_of(shape, n_frames, dtype, **kw):
+        return FrameQuality(shape, n_frames, dtype, template=template, rect=rect, **kw)
+    fq = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi)
+    return fq.result('mean'), (fq.result('corr') if template is not None else None)
 
 
-class FrameFilter(object):
+class FrameFilter(_FrameReader):
     """Leaves frames out in front of the readers: the recording's frames in, the kept ones out, on the device (dc_frame_gather).
     Built like TemporalBinner: every reader takes the kept frames as it takes the raw ones, declared with n_out frames.
 
     n_out = keep.sum(); fed: frames consumed so far; emitted: frames written so far."""
+    _stage_tag, _noun = 'ffilt_stage', 'frame filter'
 
     def __init__(self, shape, n_frames, dtype, keep, shifts=None, fine_shifts=None, bidi=0, device=None, chunk_frames=None):
         """keep: (n_frames,) booleans, True for a frame that stays (flag_frames); at least one.  shifts / fine_shifts / bidi: as for
         SeriesSummarizer, applied BEFORE the gather (dc_bidi_apply, then the shift move, fill 0): the rows of the tables are
         those of the recording's frames, not of the kept ones."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
-        shape, n_frames, self.dtype, chunk = _check_frame_args(shape, n_frames, dtype, chunk_frames)
-        self.keep = _check_keep(keep, n_frames)
-        shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
-        bidi = _check_bidi(bidi, shape)
-        self.shape, self.n_frames, self.chunk_frames = shape, n_frames, chunk
+        self._declare(shape, n_frames, dtype, chunk_frames, shifts, fine_shifts, bidi)
+        self.keep = _check_keep(keep, self.n_frames)
         self._kept = np.flatnonzero(self.keep).astype(np.int32)
         self.n_out = int(self._kept.shape[0])
-        self.fed = self.emitted = 0
+        self.emitted = 0
 
-        torch = _open_device(self, device, 'FrameFilter')
-        H, W = shape
+        torch = self._open(device, 'FrameFilter')
         self._kept_dev = torch.from_numpy(self._kept).to(self.device)      # the kept frames' indices in the recording, ascending
-        self._stage = None
-        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, self.device, shifts, (chunk, H, W), fine,
-                                                                                self.dtype == np.dtype(np.uint16), bidi)
 
     def feed(self, frames):
         """The next frames of the recording, any t >= 1: what SeriesSummarizer.feed takes.  -> the kept ones among them: a
         contiguous (k, H, W) torch.int16 tensor on the device holding the bits of the recording's dtype, k >= 0.  It is a FRESH
         allocation every time, written on the current stream: no later feed touches it, and a reader fed on the same stream
-        right away reads it after the kernels that wrote it."""
-        on_device = _check_feed(self, frames, 'frame filter')
-        torch, L = self._torch, self.L
+        right away reads it after the kernels that wrote it.  A feed that keeps nothing moves nothing, upload and corrections
+        included."""
+        return super(FrameFilter, self).feed(frames)
+
+    def _begin_feed(self, t):
+        lo, hi = (int(v) for v in np.searchsorted(self._kept, (self.fed, self.fed + t)))
+        out = self._torch.empty((hi - lo,) + self.shape, dtype=self._torch.int16, device=self.device)
+        self._dst = out.data_ptr()           # where the next kept frame goes
+        return out, hi > lo
+
+    def _chunk(self, fp, tc, t0, st):
         H, W = self.shape
-        t = int(frames.shape[0])
-        with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream(self.device)
-            st = main.cuda_stream
-            lo, hi = (int(v) for v in np.searchsorted(self._kept, (self.fed, self.fed + t)))
-            out = torch.empty((hi - lo, H, W), dtype=torch.int16, device=self.device)
-            first = self.emitted
-
-            def gather(fp, tc, t0):
-                a, b = (int(v) for v in np.searchsorted(self._kept, (t0, t0 + tc)))
-                if b > a:
-                    idx = self._kept_dev[a:b] - t0                 # the positions within these tc frames
-                    L.dc_frame_gather(fp, tc, idx.data_ptr(), b - a, H, W, out.data_ptr() + 2 * H * W * (self.emitted - first), st)
-                    self.emitted += b - a
-
-            def consume(fp, tc):
-                if hi > lo:                                        # a feed that keeps nothing moves nothing, corrections included
-                    if self._shifted is None:
-                        gather(fp, tc, self.fed)
-                    else:
-                        self._shifted.run(fp, tc, self.fed, st, gather)
-                self.fed += tc
-            if on_device:
-                consume(frames.data_ptr(), t)
-                frames.record_stream(main)
-            elif hi > lo:
-                if self._stage is None:          # names of its own: a reader alive at the same time keeps its slots
-                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'ffilt_stage', (self.chunk_frames, H, W))
-                self._stage.run(frames, main, consume)
-            else:
-                self.fed += t
-        return out
-
-
-def _feed_kept(frames, keep, bin_frames, reader_of, device, chunk_frames, shifts, fine_shifts, bidi):
-    """The filtered pass of the one-call functions, the mechanism of series._feed_binned: a FrameFilter that carries the
-    corrections, then (bin_frames) a TemporalBinner declared with the kept frames, in front of reader_of(n, device), a reader
-    declared with what reaches it and no corrections of its own.  -> the reader, fed."""
-    from .series import TemporalBinner, _check_bin_frames
-    T = int(frames.shape[0])
-    shape = tuple(frames.shape[1:])
-    keep = _check_keep(keep, T)
-    if bin_frames is not None:
-        _check_bin_frames(bin_frames, int(keep.sum()))                 # before the GPU is touched: b counts kept frames
-    ff = FrameFilter(shape, T, frames.dtype, keep, shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, device=device, chunk_frames=chunk_frames)
-    tb = None
-    if bin_frames is not None:
-        tb = TemporalBinner(shape, ff.n_out, frames.dtype, bin_frames=bin_frames, device=ff.device, chunk_frames=chunk_frames)
-    reader = reader_of(ff.n_out if tb is None else tb.n_out, ff.device)
-    for a in range(0, T, ff.chunk_frames):
-        part = ff.feed(np.asarray(frames[a:a + ff.chunk_frames]))
-        if tb is not None and part.shape[0]:
-            part = tb.feed(part)
-        if part.shape[0]:
-            reader.feed(part)
-    return reader
+        a, b = (int(v) for v in np.searchsorted(self._kept, (t0, t0 + tc)))
+        if b > a:
+            idx = self._kept_dev[a:b] - t0                 # the positions within these tc frames
+            self.L.dc_frame_gather(fp, tc, idx.data_ptr(), b - a, H, W, self._dst, st)
+            self._dst += 2 * H * W * (b - a)
+            self.emitted += b - a

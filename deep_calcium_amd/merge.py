@@ -283,42 +283,38 @@ def merge_rois_device(dspath, rois, max_dist=2, threshold=0.8, detrend_frames=No
     extract_traces_device.  keep: None, or a (T,) array of booleans (frames.flag_frames): the pairs are correlated over the kept
     columns of the sums only (a torch index, no kernel), and L counts kept frames; all True gives what None gives.
     pairs: int32 (P, 2); corr: float32 (P,)."""
-    from .series import _check_bidi, _check_detrend_frames, _open_series
+    from ._reader import _read_recording
+    from .frames import _check_keep
+    from .series import _check_detrend_frames
     from .traces import RoiTraceExtractor
     max_dist = _check_max_dist(max_dist)
     threshold = _check_threshold(threshold)
     if detrend_frames is not None:
         _check_detrend_frames(detrend_frames)
-    _check_bidi(bidi)
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     if keep is not None:
-        from .frames import _check_keep
         keep = _check_keep(keep)
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        if keep is not None:
-            keep = _check_keep(keep, T)
-        shape = _check_shape(tuple(frames.shape[1:]))
+    found = []
+
+    def reader_of(shape, T, dtype, **kw):
+        """The candidates come from the shape; with none of them there is no reader, and the recording is not read."""
+        kept = keep if keep is None else _check_keep(keep, T)
+        shape = _check_shape(shape)
         pixels = [_coords(p, shape[1]) for p in _roi_pixels(rois, shape)]
         pairs = roi_neighbours(pixels, shape, max_dist)
-        corr = np.zeros((0,), np.float32)
-        if len(pairs):
-            _check_range(T if keep is None else int(keep.sum()), [len(p) for p in pixels], detrend_frames)          # before the GPU is touched or the recording read
-            ext = RoiTraceExtractor(shape, T, frames.dtype, pixels, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                    fine_shifts=fine_shifts, bidi=bidi)
-            for a in range(0, T, ext.chunk_frames):
-                ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
-            sums = ext.sums_device()
-            if keep is not None:                     # the kept columns, in order: a fresh contiguous tensor
-                import torch
-                sums = sums[:, torch.from_numpy(np.flatnonzero(keep)).to(ext.device)]
-            corr = TracePairCorr(sums, ext.areas_host(), pairs, detrend_frames=detrend_frames, device=ext.device).result('corr')
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
+        found.extend((shape, pixels, pairs, kept))
+        if not len(pairs):
+            return None
+        # before the GPU is touched or the recording read
+        _check_range(T if kept is None else int(kept.sum()), [len(p) for p in pixels], detrend_frames)
+        return RoiTraceExtractor(shape, T, dtype, pixels, **kw)
+    ext = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi)
+    shape, pixels, pairs, kept = found
+    corr = np.zeros((0,), np.float32)
+    if ext is not None:
+        sums = ext.sums_device()
+        if kept is not None:                     # the kept columns, in order: a fresh contiguous tensor
+            import torch
+            sums = sums[:, torch.from_numpy(np.flatnonzero(kept)).to(ext.device)]
+        corr = TracePairCorr(sums, ext.areas_host(), pairs, detrend_frames=detrend_frames, device=ext.device).result('corr')
     new_rois, origin = merge_rois(pixels, pairs, corr, shape, threshold=threshold)
     return new_rois, origin, pairs, corr

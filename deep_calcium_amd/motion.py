@@ -113,8 +113,8 @@ Importing this module needs neither torch nor the GPU; constructing a MotionCorr
 """
 import numpy as np
 
-from .series import _CHUNK_BYTES, MAX_BIDI, _TwoSlotStage, _check_bidi, _check_device_frames, _frame_dtype, _open_series
-from .traces import _check_shape
+from ._reader import _CHUNK_BYTES, _FrameReader, _check_bidi, _check_shape, _frame_dtype, _open_device
+from .series import MAX_BIDI, _open_recording
 
 MAX_SHIFT = 16                        # DC_MOTION_MAX_SHIFT
 MAX_DEV = 8                           # DC_MOTION_MAX_DEV
@@ -276,18 +276,16 @@ def fine_to_pixels(fine):
     return a.astype(np.float64) / SUBPIXEL
 
 
-class MotionCorrector(object):
+class MotionCorrector(_FrameReader):
     """Owns the device state of one recording's registration; feed() the frames in order, in chunks of any size."""
+    _stage_tag, _noun = 'motion_stage', 'corrector'
 
     def __init__(self, shape, n_frames, dtype, template, max_shift=8, fill=0, device=None, chunk_frames=None, blocks=None,
                  max_dev=3, subpixel=False, coarse=None, bidi=0):
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
-        shape = _check_shape(shape)
+        self._declare(shape, n_frames, dtype, chunk_frames, max_frames=None)
+        shape, n_frames = self.shape, self.n_frames
         H, W = shape
-        n_frames = int(n_frames)
-        if n_frames < 1:
-            raise ValueError('n_frames must be >= 1, not %d' % n_frames)
-        self.dtype = _frame_dtype(dtype)
         self.coarse = None
         if coarse is None:
             self.max_shift = _check_max_shift(max_shift, shape)
@@ -299,30 +297,11 @@ class MotionCorrector(object):
         if blocks is not None:
             By, Bx, self.max_dev = _check_blocks(blocks, max_dev, shape, self.max_shift)
             self.blocks = (By, Bx)
-        self.bidi = _check_bidi(bidi, shape)
+        self.bidi = _check_bidi(bidi, shape)         # its own move, with its own fill: not the base's corrections
         template = _check_template(template, shape, self.dtype)
-        if chunk_frames is None:
-            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
-        chunk_frames = int(chunk_frames)
-        if chunk_frames < 1:
-            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        self.shape, self.n_frames = shape, n_frames
-        self.chunk_frames = min(chunk_frames, n_frames)
-        self.fed = 0
-        self._stage = None
         self._last = 0
 
-        import torch
-        from . import net
-        from ._lib import lib
-        self._torch, self._net = torch, net
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('MotionCorrector needs a GPU (there is no CPU fallback)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        torch = self._open(device, 'MotionCorrector')
         dev, nd = self.device, 2 * (self.max_shift if self.coarse is None else self.coarse) + 1
         self.template = template
         self._tmpl = torch.from_numpy(template.view(np.int16)).to(dev)
@@ -337,7 +316,7 @@ class MotionCorrector(object):
             self._cscores = torch.empty((self.chunk_frames, 2 * Sc + 1, 2 * Sc + 1), dtype=torch.int64, device=dev)
             self._coarse = torch.zeros((n_frames, 2), dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):
-                self.L.dc_motion_bin(self._tmpl.data_ptr(), int(self.dtype == np.dtype(np.uint16)), 1, H, W, c, self._tmpl_c.data_ptr(),
+                self.L.dc_motion_bin(self._tmpl.data_ptr(), self._unsigned, 1, H, W, c, self._tmpl_c.data_ptr(),
                                      self._stream().cuda_stream)
                 self._stream().synchronize()         # feed() may run on another stream
         if self.blocks is not None:
@@ -349,23 +328,21 @@ class MotionCorrector(object):
         if self.bidi:                      # one chunk of frames whose odd lines have been moved: what everything below reads
             self._bidi_scratch = torch.empty((self.chunk_frames, H, W), dtype=torch.int16, device=dev)
 
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device)
-
-    def _register(self, fp, tc, out, st):
-        """The launches of one piece of at most chunk_frames frames at fp; out: where the corrected frames go, or None."""
+    def _register(self, fp, tc, t0, out, st):
+        """The launches of one piece of at most chunk_frames frames at fp, frames [t0, t0 + tc); out: where the corrected frames
+        go, or None."""
         H, W = self.shape
         L, S = self.L, self.max_shift
-        uns = int(self.dtype == np.dtype(np.uint16))
-        rows = self._shifts.data_ptr() + 8 * self.fed
+        uns = self._unsigned
+        rows = self._shifts.data_ptr() + 8 * t0
         if self.bidi:                      # the scan-phase offset first: scores, picks and movers read the corrected lines
             L.dc_bidi_apply(fp, tc, self.bidi, H, W, self.fill, self._bidi_scratch.data_ptr(), st)
             fp = self._bidi_scratch.data_ptr()
         if self.coarse is not None:
             # the wide search: the exhaustive pick on the binned frames, then the full-resolution window around c times it
             c, (Hc, Wc), Sc = self.coarse, self._cshape, self._cradius
-            crows = self._coarse.data_ptr() + 8 * self.fed
-            frows = self._fine.data_ptr() + 8 * self.fed if self.subpixel else None
+            crows = self._coarse.data_ptr() + 8 * t0
+            frows = self._fine.data_ptr() + 8 * t0 if self.subpixel else None
             L.dc_motion_bin(fp, uns, tc, H, W, c, self._binned.data_ptr(), st)
             L.dc_motion_ssd(self._binned.data_ptr(), uns, tc, self._tmpl_c.data_ptr(), Hc, Wc, Sc, self._cscores.data_ptr(), st)
             L.dc_motion_pick(self._cscores.data_ptr(), tc, Sc, crows, None, st)
@@ -376,26 +353,39 @@ class MotionCorrector(object):
             L.dc_motion_pick(self._scores.data_ptr(), tc, S, rows, None, st)
         if self.blocks is not None:
             (By, Bx), D = self.blocks, self.max_dev
-            brows = self._bshifts.data_ptr() + 8 * By * Bx * self.fed
+            brows = self._bshifts.data_ptr() + 8 * By * Bx * t0
             L.dc_motion_block_ssd(fp, uns, tc, self._tmpl.data_ptr(), H, W, S, D, By, Bx, rows, self._bscores.data_ptr(), st)
             L.dc_motion_block_pick(self._bscores.data_ptr(), rows, tc, By, Bx, S, D, brows, None, st)
             if self.subpixel:
-                frows = self._fine.data_ptr() + 8 * By * Bx * self.fed
+                frows = self._fine.data_ptr() + 8 * By * Bx * t0
                 L.dc_motion_block_refine(self._bscores.data_ptr(), rows, brows, tc, By, Bx, S, D, frows, st)
                 if out is not None:
                     L.dc_motion_warp_sub(fp, uns, tc, frows, By, Bx, H, W, self.fill, out, st)
             elif out is not None:
                 L.dc_motion_warp(fp, tc, brows, By, Bx, H, W, self.fill, out, st)
         elif self.subpixel:
-            frows = self._fine.data_ptr() + 8 * self.fed
+            frows = self._fine.data_ptr() + 8 * t0
             if self.coarse is None:        # the wide search has refined its pick within the window table already
                 L.dc_motion_refine(self._scores.data_ptr(), rows, tc, S, frows, st)
             if out is not None:
                 L.dc_motion_apply_sub(fp, uns, tc, frows, H, W, self.fill, out, st)
         elif out is not None:
             L.dc_motion_apply(fp, tc, rows, H, W, self.fill, out, st)
-        self.fed += tc
         self._last = tc
+
+    def _begin_feed(self, t):
+        out = self._torch.empty((t,) + self.shape, dtype=self._torch.int16, device=self.device) if self._correct else None
+        self._dst = out.data_ptr() if self._correct else None      # where the next corrected frame goes
+        return out, True
+
+    def _chunk(self, fp, tc, t0, st):
+        """A resident tensor arrives whole: it is registered in pieces of chunk_frames, the size of the score tables."""
+        H, W = self.shape
+        for a in range(0, tc, self.chunk_frames):
+            n = min(self.chunk_frames, tc - a)
+            self._register(fp + 2 * a * H * W, n, t0 + a, self._dst, st)
+            if self._dst is not None:
+                self._dst += 2 * n * H * W
 
     def feed(self, frames, correct=True):
         """The next frames of the recording, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype (staged
@@ -407,38 +397,8 @@ class MotionCorrector(object):
         [fed, fed + t) of fine_shifts_device()) and the frames are interpolated bilinearly at the fine shifts (or the fine
         shift field), `fill` where a tap that is used lies outside the frame.  With bidi=p every piece first has its odd lines
         moved by p (dc_bidi_apply, `fill` where x + p leaves the row): the returned frames carry both corrections."""
-        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
-        if not on_device and not isinstance(frames, np.ndarray):
-            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
-        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
-            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
-        if on_device:
-            _check_device_frames(self._torch, frames, self.dtype, self.device, 'corrector')
-        elif frames.dtype != self.dtype:
-            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
-        t = int(frames.shape[0])
-        if t < 1 or self.fed + t > self.n_frames:
-            raise ValueError('%d frames after %d fed: the recording was declared to have %d' % (t, self.fed, self.n_frames))
-        torch = self._torch
-        H, W = self.shape
-        with torch.cuda.device(self.device):
-            main = self._stream()
-            st = main.cuda_stream
-            out = torch.empty((t, H, W), dtype=torch.int16, device=self.device) if correct else None
-            done = [0]
-
-            def piece(fp, tc):
-                self._register(fp, tc, out.data_ptr() + 2 * done[0] * H * W if correct else None, st)
-                done[0] += tc
-            if on_device:
-                for a in range(0, t, self.chunk_frames):
-                    piece(frames.data_ptr() + 2 * a * H * W, min(self.chunk_frames, t - a))
-                frames.record_stream(main)
-            else:
-                if self._stage is None:          # names of its own: a summarizer or extractor alive at the same time keeps its slots
-                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'motion_stage', (self.chunk_frames, H, W))
-                self._stage.run(frames, main, piece)
-        return out
+        self._correct = correct
+        return super(MotionCorrector, self).feed(frames)
 
     def shifts_device(self):
         """The int32 (n_frames, 2) tensor of (dy, dx) rows on the device; rows [0, fed) are set."""
@@ -542,17 +502,10 @@ def make_template(frames, max_shift=8, iterations=1, device=None, coarse=None, b
     if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
         raise ValueError('iterations must be an integer >= 0, not %r' % (iterations,))
     bidi = _check_bidi(bidi, shape)
-    import torch
-    if not torch.cuda.is_available():
-        from ._lib import DcunetError
-        raise DcunetError('make_template needs a GPU (there is no CPU fallback)')
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    torch, _, L, dev = _open_device(device, 'make_template')
     N, (H, W) = int(frames.shape[0]), shape
     uns = dtype == np.dtype(np.uint16)
     step = max(1, _CHUNK_BYTES // (2 * H * W))
-    if bidi:
-        from ._lib import lib
-        L = lib()
     with torch.cuda.device(dev):
         total = torch.zeros((H, W), dtype=torch.int64, device=dev)
         for a in range(0, N, step):
@@ -594,10 +547,8 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
         _check_blocks(blocks, max_dev)
     if isinstance(template_frames, bool) or not isinstance(template_frames, (int, np.integer)) or template_frames < 1:
         raise ValueError('template_frames must be an integer >= 1, not %r' % (template_frames,))
-    frames, close = _open_series(dspath, source)
+    frames, close = _open_recording(dspath, source)
     try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
         T = int(frames.shape[0])
         shape = tuple(int(v) for v in frames.shape[1:])
         S = _check_max_shift(max_shift, shape) if coarse is None else _check_coarse(coarse, max_shift, shape, blocks)[1]
@@ -618,66 +569,40 @@ def estimate_shifts_device(dspath, template=None, max_shift=8, template_frames=2
     return out, template
 
 
-class BidiEstimator(object):
+class BidiEstimator(_FrameReader):
     """Owns the device state of one recording's scan-phase search: feed() frames in chunks of any size, then offset().  Every
-    frame gets its own 2P+1 exact scores (dc_bidi_scores); the offset is picked on the host from their sums over the frames."""
+    frame gets its own 2P+1 exact scores (dc_bidi_scores); the offset is picked on the host from their sums over the frames.
+    A reader of no declared length, whose resident input is scored in pieces of chunk_frames: the declaration checks, the device,
+    the checks of feed()'s argument and the stage are the base's, feed() is its own."""
+    _stage_tag, _noun = 'bidi_stage', 'estimator'
 
     def __init__(self, shape, dtype, max_offset=8, device=None, chunk_frames=None):
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
-        shape = _check_shape(shape)
-        H, W = shape
-        self.dtype = _frame_dtype(dtype)
-        self.max_offset = _check_bidi_radius(max_offset, shape)
-        if H * W > (1 << 28):
-            raise ValueError('shape must be (H, W) with H * W <= 2**28 for the scan-phase search, not %r' % (shape,))
-        if chunk_frames is None:
-            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
-        chunk_frames = int(chunk_frames)
-        if chunk_frames < 1:
-            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        self.shape, self.chunk_frames = shape, chunk_frames
-        self.fed = 0
-        self._stage = None
+        self._declare(shape, None, dtype, chunk_frames)
+        self.max_offset = _check_bidi_radius(max_offset, self.shape)
+        if self.shape[0] * self.shape[1] > (1 << 28):
+            raise ValueError('shape must be (H, W) with H * W <= 2**28 for the scan-phase search, not %r' % (self.shape,))
         self._tables = []                  # one (t, 2P+1) int64 tensor per piece, in order
-
-        import torch
-        from . import net
-        from ._lib import lib
-        self._torch, self._net = torch, net
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('BidiEstimator needs a GPU (there is no CPU fallback)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        self._open(device, 'BidiEstimator')
 
     def feed(self, frames):
         """The next frames, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype (staged through two pinned
         slots), or a contiguous (t, H, W) torch.int16 tensor on the estimator's device holding the recording's bits (read in
         place).  Their scores become rows [fed, fed + t) of scores()."""
-        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
-        if not on_device and not isinstance(frames, np.ndarray):
-            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
-        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
-            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
-        if on_device:
-            _check_device_frames(self._torch, frames, self.dtype, self.device, 'estimator')
-        elif frames.dtype != self.dtype:
-            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
+        on_device = self._check_frames(frames)
         t = int(frames.shape[0])
         if t < 1:
             raise ValueError('frames must hold at least one frame')
         torch = self._torch
         H, W = self.shape
-        P, uns = self.max_offset, int(self.dtype == np.dtype(np.uint16))
+        P = self.max_offset
         with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream(self.device)
+            main = self._stream()
             st = main.cuda_stream
 
             def piece(fp, tc):
                 table = torch.empty((tc, 2 * P + 1), dtype=torch.int64, device=self.device)      # fully written by the launch
-                self.L.dc_bidi_scores(fp, uns, tc, H, W, P, table.data_ptr(), st)
+                self.L.dc_bidi_scores(fp, self._unsigned, tc, H, W, P, table.data_ptr(), st)
                 self._tables.append(table)
                 self.fed += tc
             if on_device:
@@ -685,9 +610,7 @@ class BidiEstimator(object):
                     piece(frames.data_ptr() + 2 * a * H * W, min(self.chunk_frames, t - a))
                 frames.record_stream(main)
             else:
-                if self._stage is None:          # names of its own: a corrector or summarizer alive at the same time keeps its slots
-                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'bidi_stage', (self.chunk_frames, H, W))
-                self._stage.run(frames, main, piece)
+                self._staged().run(frames, main, piece)
         return self
 
     def scores(self):
@@ -716,10 +639,8 @@ def estimate_bidi_device(dspath, max_offset=8, frames=200, source='series/raw', 
     _check_bidi_radius(max_offset)
     if frames is not None and (isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 1):
         raise ValueError('frames must be None or an integer >= 1, not %r' % (frames,))
-    series, close = _open_series(dspath, source)
+    series, close = _open_recording(dspath, source)
     try:
-        if len(series.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(series.shape)))
         T = int(series.shape[0])
         n = T if frames is None else min(T, int(frames))
         shape = tuple(int(v) for v in series.shape[1:])

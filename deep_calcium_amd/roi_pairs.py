@@ -51,9 +51,10 @@ Importing this module needs neither torch nor the GPU; constructing a RoiPairCor
 """
 import numpy as np
 
+from ._reader import _check_n_frames, _read_recording
 from .dff import _as_int
 from .footprints import MAX_FRAMES, _largest_component
-from .traces import MAX_VOLUME, RoiTraceExtractor, _check_shape, _roi_pixels
+from .traces import MAX_VOLUME, _LeadingExtractor, _check_shape, _roi_pixels
 
 KINDS = ('moments', 'corr')
 TILE = 64                             # DC_ROI_PAIR_TILE: the edge, in pairs, of one workgroup's tile of an ROI's square
@@ -104,9 +105,7 @@ class RoiPairCorr(object):
         pass are not detrended."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         shape = _check_shape(shape)
-        n_frames = int(n_frames)
-        if n_frames < 1 or n_frames * shape[0] * shape[1] > MAX_VOLUME:
-            raise ValueError('n_frames must be >= 1 with n_frames * H * W <= 2**46, not %d' % n_frames)
+        n_frames = _check_n_frames(n_frames, shape, max_volume=MAX_VOLUME)
         if n_frames > MAX_FRAMES:
             raise ValueError('n_frames must be <= 2**31 - 1, not %d' % n_frames)
         self._seg = None
@@ -118,10 +117,9 @@ class RoiPairCorr(object):
         self._pixels = [np.stack([p.astype(np.int64) // shape[1], p.astype(np.int64) % shape[1]], 1) for p in pixels]
         self._roi_off_host, self._goff_host = roi_off.astype(np.int64), goff
         self.n_pixels, self.n_state, self.n_tiles = int(roi_off[-1]), G, len(tiles)
-        self._ext = ext = RoiTraceExtractor(shape, n_frames, dtype, self._pixels, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                            fine_shifts=fine_shifts, bidi=bidi)
-        ext._stage_tag = 'roi_pairs_stage'           # slots of its own: an extractor alive at the same time keeps its own
-        ext._after_chunk = self._accumulate
+        # slots of its own: an extractor alive at the same time keeps its own
+        self._ext = ext = _LeadingExtractor('roi_pairs_stage', self._accumulate, shape, n_frames, dtype, self._pixels, device=device,
+                                            chunk_frames=chunk_frames, shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
         self.shape, self.n_frames, self.dtype, self.n_rois = shape, n_frames, ext.dtype, ext.n_rois
         self.chunk_frames, self.device, self.L = ext.chunk_frames, ext.device, ext.L
         torch = self._torch = ext._torch
@@ -313,39 +311,14 @@ def roi_pair_corr_device(dspath, rois, source='series/raw', device=None, chunk_f
     correlations are pooled over segments of L frames (RoiPairCorr); binning comes first and L counts binned frames.  keep: None, or
     a (T,) array of booleans (frames.flag_frames): the frames marked False are left out after bidi and the shifts and before binning
     and detrending, whose b and L then count kept frames; all True gives what None gives."""
-    from .series import _check_bin_frames, _check_detrend_frames, _feed_binned, _open_series
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    if bin_frames is not None:
-        _check_bin_frames(bin_frames)
+    from .series import _check_detrend_frames
     if detrend_frames is not None:
         _check_detrend_frames(detrend_frames)
-    if keep is not None:
-        from .frames import _check_keep, _feed_kept
-        keep = _check_keep(keep)
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        if keep is not None:
-            pc = _feed_kept(frames, keep, bin_frames, lambda n, dev: RoiPairCorr(tuple(frames.shape[1:]), n, frames.dtype, rois, device=dev,
-                                                                                 chunk_frames=chunk_frames, detrend_frames=detrend_frames),
-                            device, chunk_frames, shifts, fine_shifts, bidi)
-        elif bin_frames is None:
-            pc = RoiPairCorr(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                             fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
-            for a in range(0, T, pc.chunk_frames):
-                pc.feed(np.asarray(frames[a:a + pc.chunk_frames]))
-        else:
-            pc = _feed_binned(frames, bin_frames, lambda n, dev: RoiPairCorr(tuple(frames.shape[1:]), n, frames.dtype, rois, device=dev,
-                                                                             chunk_frames=chunk_frames, detrend_frames=detrend_frames),
-                              device, chunk_frames, shifts, fine_shifts, bidi)
-        out = pc.result('corr'), pc.pixels()
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
-    return out
+
+    def reader_of(shape, n_frames, dtype, **kw):
+        return RoiPairCorr(shape, n_frames, dtype, rois, detrend_frames=detrend_frames, **kw)
+    pc = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi, bin_frames, keep)
+    return pc.result('corr'), pc.pixels()
 
 
 def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, source='series/raw', device=None, chunk_frames=None,
@@ -359,25 +332,18 @@ def split_rois_device(dspath, rois, min_gap=0.1, min_area=8, iterations=16, sour
     two groups; pooling over segments of L frames gives them back.  Short segments also remove real slow covariance: results at
     different L are not comparable with each other or with None.  keep: as for roi_pair_corr_device -- three flash frames in a
     thousand push every pixel pair towards 1 as bleaching does; leaving them out gives the two groups back."""
-    from .series import _check_bin_frames, _check_detrend_frames, _open_series
+    from .series import _check_bin_frames, _check_detrend_frames
     if detrend_frames is not None:
         _check_detrend_frames(detrend_frames)
     min_gap, min_area, iterations = _check_split_args(min_gap, min_area, iterations)
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
     if bin_frames is not None:
         _check_bin_frames(bin_frames)
     if keep is not None:
         from .frames import _check_keep
         keep = _check_keep(keep)
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        shape = _check_shape(tuple(frames.shape[1:]))
-    finally:
-        frames = None
-        close()
+    shape = []                               # the frame shape alone: a reader of None reads nothing
+    _read_recording(dspath, source, lambda hw, n_frames, dtype, **kw: shape.extend(hw), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
+    shape = _check_shape(shape)
     flat = _roi_pixels(rois, shape)
     pixels = [np.stack([p.astype(np.int64) // shape[1], p.astype(np.int64) % shape[1]], 1) for p in flat]
     sent = [r for r, p in enumerate(pixels) if 2 * min_area <= len(p) <= MAX_AREA]

@@ -30,9 +30,12 @@ Importing this module needs neither torch nor the GPU; constructing a SeriesSumm
 """
 import numpy as np
 
+# the checks and constants that moved to _reader stay importable from here
+from ._reader import MAX_FRAMES, _CHUNK_BYTES, _check_bidi, _check_known_shifts, _check_shifts, _frame_dtype  # noqa: F401
+from ._reader import _FrameReader, _read_recording
+
 KINDS = ('mean16', 'max16', 'mean', 'max', 'std', 'corr')
-MAX_FRAMES = 2147483647               # DC_SERIES_MAX_FRAMES: what the int64 state holds
-_CHUNK_BYTES = 32 << 20               # default staging chunk: long enough to hide the launches, short enough to pin twice
+MAX_BIDI = 16                         # DC_BIDI_MAX_OFFSET: the largest radius of the scan-phase search
 
 
 def _check_kind(kind, kinds=KINDS):
@@ -40,88 +43,6 @@ def _check_kind(kind, kinds=KINDS):
         raise ValueError('summary kind %r is not one of %s' % (kind, ', '.join(KINDS)))
     if kind not in kinds:
         raise ValueError('summary kind %r was not requested (kinds=%r)' % (kind, tuple(kinds)))
-
-
-def _frame_dtype(dtype):
-    try:
-        dt = np.dtype(dtype)
-    except TypeError:
-        raise ValueError('frames must be int16 or uint16, not %r' % (dtype,))
-    if dt not in (np.dtype(np.int16), np.dtype(np.uint16)):
-        raise ValueError('frames must be int16 or uint16, not %s' % dt)
-    return dt
-
-
-_MAX_BLOCKS = 32                      # DC_MOTION_MAX_BLOCKS
-
-
-def _shifts_shape_ok(shape, n_frames, frame_shape):
-    """(n_frames, 2): one rigid (dy, dx) per frame; (n_frames, By, Bx, 2): one per block of a grid that fits the frame."""
-    shape = tuple(shape)
-    if shape == (n_frames, 2):
-        return True
-    if len(shape) != 4 or shape[0] != n_frames or shape[3] != 2:
-        return False
-    limit = (_MAX_BLOCKS, _MAX_BLOCKS) if frame_shape is None else (min(_MAX_BLOCKS, frame_shape[0]), min(_MAX_BLOCKS, frame_shape[1]))
-    return 1 <= shape[1] <= limit[0] and 1 <= shape[2] <= limit[1]
-
-
-def _check_shifts(shifts, n_frames, frame_shape=None, name='shifts'):
-    """The `shifts=` keyword of SeriesSummarizer / RoiTraceExtractor: None, an (n_frames, 2) integer numpy array of (dy, dx) rows
-    (-> contiguous int32) or an (n_frames, 2) integer tensor (checked, returned as it is); or the piecewise-rigid
-    (n_frames, By, Bx, 2) block shifts of either kind, By and Bx in [1, 32] and no more blocks than pixels.  `fine_shifts=`
-    (name='fine_shifts': sixteenths of a pixel) is held to the same checks.  Host only."""
-    if shifts is None:
-        return None
-    what = '%s must be an integer (n_frames, 2) = (%d, 2) array of (dy, dx), or (%d, By, Bx, 2) block shifts with By, Bx in [1, %d]' \
-        % (name, n_frames, n_frames, _MAX_BLOCKS)
-    if not isinstance(shifts, np.ndarray) and hasattr(shifts, 'is_cuda') and hasattr(shifts, 'data_ptr'):
-        if not _shifts_shape_ok(shifts.shape, n_frames, frame_shape) or shifts.dtype.is_floating_point or shifts.dtype.is_complex:
-            raise ValueError('%s, not %s %r' % (what, shifts.dtype, tuple(shifts.shape)))
-        return shifts
-    a = np.asarray(shifts)
-    if not _shifts_shape_ok(a.shape, n_frames, frame_shape) or a.dtype.kind not in 'iu':
-        raise ValueError('%s, not %s %r' % (what, a.dtype, tuple(a.shape)))
-    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError('%s must fit int32' % name)
-    return np.ascontiguousarray(a.astype(np.int32))
-
-
-def _check_known_shifts(shifts, fine_shifts, n_frames, frame_shape):
-    """`shifts=` and `fine_shifts=` of a consumer of known shifts -> (the checked table or None, whether it is fine).  Giving both
-    is a ValueError.  Host only."""
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    if fine_shifts is not None:
-        return _check_shifts(fine_shifts, n_frames, frame_shape, name='fine_shifts'), True
-    return _check_shifts(shifts, n_frames, frame_shape), False
-
-
-MAX_BIDI = 16                         # DC_BIDI_MAX_OFFSET: the largest radius of the scan-phase search
-
-
-def _check_bidi(bidi, shape=None):
-    """The `bidi=` keyword of MotionCorrector and every reader of known shifts: the whole-pixel offset the odd lines are moved by
-    before anything else reads a frame (dc_bidi_apply), 0 for none.  An integer that keeps a column of the odd lines, |bidi| < W.
-    Host only."""
-    if isinstance(bidi, bool) or not isinstance(bidi, (int, np.integer)):
-        raise ValueError('bidi must be an integer (the whole-pixel offset of the odd lines, 0 for none), not %r' % (bidi,))
-    p = int(bidi)
-    if not -2 ** 31 <= p < 2 ** 31:
-        raise ValueError('bidi must fit int32, not %d' % p)
-    if shape is not None and abs(p) >= shape[1]:
-        raise ValueError('bidi = %d leaves no column of the odd lines of a %d x %d frame: |bidi| < W' % (p, shape[0], shape[1]))
-    return p
-
-
-def _check_device_frames(torch, frames, dtype, device, owner):
-    """A feed() argument that is a tensor: the recording's bits as a contiguous torch.int16 tensor on `device`."""
-    if frames.dtype != torch.int16:
-        raise ValueError('a device tensor must be torch.int16 (the bits of the %s frames), not %s' % (dtype, frames.dtype))
-    if not frames.is_cuda or frames.device != device:
-        raise ValueError('the tensor is on %s, the %s on %s' % (frames.device, owner, device))
-    if not frames.is_contiguous():
-        raise ValueError('a device tensor must be contiguous')
 
 
 MIN_DETREND_FRAMES = 2
@@ -180,100 +101,14 @@ class _Segments(object):
             k += m
 
 
-class _ShiftedChunks(object):
-    """Known shifts applied on the way in (fill 0): the int32 (n_frames, 2) table on the device (dc_motion_apply) or the
-    (n_frames, By, Bx, 2) block shifts (dc_motion_warp) and one scratch chunk the accumulate kernels read instead of the staged
-    frames.  Frame `fed + i` of the recording gets row `fed + i`.  fine: the table holds fine shifts (sixteenths of a pixel), the
-    frames are interpolated (dc_motion_apply_sub, dc_motion_warp_sub: they are told the signedness).  bidi != 0: the odd lines
-    are moved by it first (dc_bidi_apply, into a scratch chunk of its own); with shifts=None that is the only move."""
-
-    def __init__(self, torch, L, device, shifts, shape, fine=False, unsigned=0, bidi=0):
-        self._L, self.shape, self.fine, self._uns, self.bidi = L, shape, fine, int(unsigned), int(bidi)
-        self.shifts, self.blocks = None, None
-        if shifts is not None:
-            if isinstance(shifts, np.ndarray):
-                shifts = torch.from_numpy(shifts)
-            self.shifts = shifts.to(device=device, dtype=torch.int32).contiguous()
-            self.blocks = tuple(int(v) for v in self.shifts.shape[1:3]) if self.shifts.dim() == 4 else None
-        self.scratch = torch.empty(shape, dtype=torch.int16, device=device)
-        self._lines = torch.empty(shape, dtype=torch.int16, device=device) if self.bidi and self.shifts is not None else None
-
-    def run(self, fp, tc, fed, st, launch):
-        """launch(pointer to corrected frames, count, first frame) for the tc frames at fp, a scratch chunk at a time."""
-        C, H, W = self.shape
-        for a in range(0, tc, C):
-            n = min(C, tc - a)
-            src = fp + 2 * a * H * W
-            if self.bidi:
-                dst = self.scratch if self.shifts is None else self._lines
-                self._L.dc_bidi_apply(src, n, self.bidi, H, W, 0, dst.data_ptr(), st)
-                src = dst.data_ptr()
-            if self.shifts is None:
-                pass
-            elif self.fine and self.blocks is None:
-                self._L.dc_motion_apply_sub(src, self._uns, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
-                                            self.scratch.data_ptr(), st)
-            elif self.fine:
-                By, Bx = self.blocks
-                self._L.dc_motion_warp_sub(src, self._uns, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
-                                           self.scratch.data_ptr(), st)
-            elif self.blocks is None:
-                self._L.dc_motion_apply(src, n, self.shifts.data_ptr() + 8 * (fed + a), H, W, 0,
-                                        self.scratch.data_ptr(), st)
-            else:
-                By, Bx = self.blocks
-                self._L.dc_motion_warp(src, n, self.shifts.data_ptr() + 8 * By * Bx * (fed + a), By, Bx, H, W, 0,
-                                       self.scratch.data_ptr(), st)
-            launch(self.scratch.data_ptr(), n, fed + a)
-
-
-class _TwoSlotStage(object):
-    """Two pinned host slots and two device slots of `shape` = (C, H, W) int16: the H2D copy of chunk k + 1 (copy stream) runs
-    beside the kernels on chunk k (the caller's stream); events hand the slots back and forth.  The pinned slots are cached by
-    name (net._pinned): every user passes a `tag` of its own, so two users alive at once never share a slot."""
-
-    def __init__(self, torch, net, device, tag, shape):
-        self._torch, self.chunk_frames = torch, int(shape[0])
-        self._host = [net._pinned('%s%d' % (tag, k), shape, torch.int16, entry=True) for k in range(2)]
-        self._dev = [torch.empty(shape, dtype=torch.int16, device=device) for _ in range(2)]
-        with torch.cuda.device(device):
-            self._copy_stream = torch.cuda.Stream(device=device)
-        self._read = [None, None]         # event behind the last kernel that read device slot k
-        self._slot = 0
-
-    def run(self, frames, main, launch):
-        """Cuts `frames` (numpy, 16-bit) into chunks, uploads each and calls launch(device pointer, frames in the chunk), which
-        enqueues the chunk's kernels on `main`.  Called with the device current."""
-        torch = self._torch
-        for a in range(0, frames.shape[0], self.chunk_frames):
-            part = frames[a:a + self.chunk_frames]
-            tc, k = part.shape[0], self._slot
-            self._slot ^= 1
-            host, dev = self._host[k], self._dev[k]
-            if host[1] is not None:
-                host[1].synchronize()                  # the copy that last read this pinned slot has finished
-            host[0].numpy()[:tc] = part.view(np.int16)         # same bits; the kernels are told the signedness
-            with torch.cuda.stream(self._copy_stream):
-                if self._read[k] is not None:
-                    self._copy_stream.wait_event(self._read[k])      # the kernels on chunk k - 2 are done with the slot
-                dev[:tc].copy_(host[0][:tc], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(self._copy_stream)
-            host[1] = ev
-            main.wait_event(ev)
-            launch(dev.data_ptr(), tc)
-            done = torch.cuda.Event()
-            done.record(main)
-            self._read[k] = done
-
-
 def _pooled_ints(words):
     """int64 (..., 2) {lo, hi} pooled words -> an object array of exact Python ints, hi * 2^64 + lo."""
     return words[..., 1].astype(object) * (1 << 64) + words[..., 0].view(np.uint64).astype(object)
 
 
-class SeriesSummarizer(object):
+class SeriesSummarizer(_FrameReader):
     """Owns the device state of one recording's summaries; feed() the frames in order, in chunks of any size, then result()."""
+    _stage_tag, _noun = 'series_stage', 'summarizer'
 
     def __init__(self, shape, n_frames, dtype, device=None, chunk_frames=None, kinds=KINDS, shifts=None, fine_shifts=None, detrend_frames=None,
                  bidi=0):
@@ -289,16 +124,7 @@ class SeriesSummarizer(object):
         removes every trend that is constant within a segment; `mean` and `max` are those of the whole recording; `mean16` /
         `max16` are not served.  L > n_frames / 2 is one segment: the `corr` bits of None."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
-        try:
-            shape = tuple(int(v) for v in shape)
-        except TypeError:
-            raise ValueError('shape must be (H, W), not %r' % (shape,))
-        if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] > (1 << 30):
-            raise ValueError('shape must be (H, W) with 1 <= H * W <= 2**30, not %r' % (shape,))
-        n_frames = int(n_frames)
-        if not 1 <= n_frames <= MAX_FRAMES:
-            raise ValueError('n_frames must be in [1, %d], not %d' % (MAX_FRAMES, n_frames))
-        self.dtype = _frame_dtype(dtype)
+        self._declare(shape, n_frames, dtype, chunk_frames, shifts, fine_shifts, bidi)
         kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
         if not kinds:
             raise ValueError('kinds is empty')
@@ -306,34 +132,14 @@ class SeriesSummarizer(object):
             _check_kind(k)
         self._seg = None
         if detrend_frames is not None:
-            self._seg = _Segments(n_frames, _check_detrend_frames(detrend_frames, n_frames, shape))
+            self._seg = _Segments(self.n_frames, _check_detrend_frames(detrend_frames, self.n_frames, self.shape))
             if 'mean16' in kinds or 'max16' in kinds:
                 raise ValueError('mean16 / max16 are the stored summaries of the whole recording: not served with detrend_frames')
-        H, W = shape
-        if chunk_frames is None:
-            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
-        chunk_frames = int(chunk_frames)
-        if chunk_frames < 1:
-            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
-        bidi = _check_bidi(bidi, shape)
-        self.shape, self.n_frames, self.kinds = shape, n_frames, kinds
-        self.chunk_frames = min(chunk_frames, n_frames)
-        self.fed = 0
+        self.kinds = kinds
         self._images = None
 
-        import torch
-        from . import net
-        from ._lib import lib
-        self._torch, self._net = torch, net
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('SeriesSummarizer needs a GPU (there is no CPU fallback)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        dev, n = self.device, H * W
+        torch = self._open(device, 'SeriesSummarizer')
+        dev, n = self.device, self.shape[0] * self.shape[1]
         self._chain = 'mean16' in kinds or 'max16' in kinds
         self._xy = 'corr' in kinds
         # state: written by the chunk with t0 == 0, so never cleared here
@@ -348,69 +154,30 @@ class SeriesSummarizer(object):
             self._pcov = torch.zeros((4, n, 2), dtype=torch.int64, device=dev) if self._xy else None
             self._sum_total = torch.zeros(n, dtype=torch.int64, device=dev)
             self._vmax_total = torch.full((n,), -2 ** 31, dtype=torch.int32, device=dev)
-        self._stage = _TwoSlotStage(torch, net, dev, 'series_stage', (self.chunk_frames, H, W))
-        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
-                                                                                self.dtype == np.dtype(np.uint16), bidi)
 
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device)
-
-    def feed(self, frames):
-        """The next frames of the recording, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype, or a
-        contiguous (t, H, W) torch.int16 tensor on the summarizer's device holding the recording's bits (read in place, no
-        staging; the signedness is the declared dtype's) -- what MotionCorrector.feed() returns."""
-        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
-        if not on_device and not isinstance(frames, np.ndarray):
-            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
-        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
-            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
-        if on_device:
-            _check_device_frames(self._torch, frames, self.dtype, self.device, 'summarizer')
-        elif frames.dtype != self.dtype:
-            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
-        if frames.shape[0] < 1 or self.fed + frames.shape[0] > self.n_frames:
-            raise ValueError('%d frames after %d fed: the recording was declared to have %d' %
-                             (frames.shape[0], self.fed, self.n_frames))
-        torch, L = self._torch, self.L
+    def _chunk(self, fp, tc, t0, st):
         H, W = self.shape
-        uns = int(self.dtype == np.dtype(np.uint16))
-        with torch.cuda.device(self.device):
-            main = self._stream()
-            st = main.cuda_stream
-
-            def accumulate_frames(fp, tc, t0, n_total=self.n_frames):
-                L.dc_series_accumulate(fp, uns, tc, t0, n_total,
-                                       self.mean16.data_ptr() if self._chain else None,
-                                       self.max16.data_ptr() if self._chain else None,
-                                       self.sum.data_ptr(), self.sumsq.data_ptr(), self.vmax.data_ptr(), H, W, st)
-                if self._xy:
-                    L.dc_series_accumulate_xy(fp, uns, tc, t0, self.xy.data_ptr(), H, W, st)
-
-            def accumulate_segments(fp, tc, t0):
-                # a chunk is cut at the segment boundaries: the part before one is accumulated from its own frame pointer with
-                # t0 counted from the segment's start (0 initialises the state), then the segment is folded
-                for k, m, within, ends in self._seg.cut(t0, tc):
-                    accumulate_frames(fp + k * H * W * 2, m, within, within + m)
-                    if ends is not None:
-                        L.dc_series_fold_segment(self.sum.data_ptr(), self.sumsq.data_ptr(), self.xy.data_ptr() if self._xy else None,
-                                                 self.vmax.data_ptr(), ends[1], ends[2], self._pvar.data_ptr(),
-                                                 self._pcov.data_ptr() if self._xy else None, self._sum_total.data_ptr(),
-                                                 self._vmax_total.data_ptr(), H, W, st)
-            accumulate = accumulate_frames if self._seg is None else accumulate_segments
-
-            def reduce(fp, tc):
-                if self._shifted is None:
-                    accumulate(fp, tc, self.fed)
-                else:
-                    self._shifted.run(fp, tc, self.fed, st, accumulate)
-                self.fed += tc
-            if on_device:
-                reduce(frames.data_ptr(), int(frames.shape[0]))
-                frames.record_stream(main)
-            else:
-                self._stage.run(frames, main, reduce)
         self._images = None
-        return self
+        if self._seg is None:
+            return self._accumulate(fp, tc, t0, self.n_frames, st)
+        # a chunk is cut at the segment boundaries: the part before one is accumulated from its own frame pointer with t0
+        # counted from the segment's start (0 initialises the state), then the segment is folded
+        for k, m, within, ends in self._seg.cut(t0, tc):
+            self._accumulate(fp + k * H * W * 2, m, within, within + m, st)
+            if ends is not None:
+                self.L.dc_series_fold_segment(self.sum.data_ptr(), self.sumsq.data_ptr(), self.xy.data_ptr() if self._xy else None,
+                                              self.vmax.data_ptr(), ends[1], ends[2], self._pvar.data_ptr(),
+                                              self._pcov.data_ptr() if self._xy else None, self._sum_total.data_ptr(),
+                                              self._vmax_total.data_ptr(), H, W, st)
+
+    def _accumulate(self, fp, tc, t0, n_total, st):
+        H, W = self.shape
+        self.L.dc_series_accumulate(fp, self._unsigned, tc, t0, n_total,
+                                    self.mean16.data_ptr() if self._chain else None,
+                                    self.max16.data_ptr() if self._chain else None,
+                                    self.sum.data_ptr(), self.sumsq.data_ptr(), self.vmax.data_ptr(), H, W, st)
+        if self._xy:
+            self.L.dc_series_accumulate_xy(fp, self._unsigned, tc, t0, self.xy.data_ptr(), H, W, st)
 
     def _finalize(self):
         if self._images is None:
@@ -495,7 +262,7 @@ def _check_bin_frames(bin_frames, n_frames=None):
     return b
 
 
-class TemporalBinner(object):
+class TemporalBinner(_FrameReader):
     """Temporal binning in front of the readers: the recording's frames in, the means of `bin_frames` consecutive frames out, on
     the device (dc_series_bin_time).  A bin's value is floor((2 s + b) / (2 b)) of the exact sum s of its b frames -- the mean
     rounded half up, the rule of make_template and dc_motion_bin -- in the recording's own 16-bit type, so every reader takes the
@@ -509,52 +276,20 @@ class TemporalBinner(object):
             if binned.shape[0]: reader.feed(binned)
 
     n_out = n_frames // bin_frames; fed: frames consumed so far; emitted: bins written so far."""
+    _stage_tag, _noun = 'tbin_stage', 'binner'
 
     def __init__(self, shape, n_frames, dtype, bin_frames=4, shifts=None, fine_shifts=None, bidi=0, device=None, chunk_frames=None):
         """shifts / fine_shifts / bidi: as for SeriesSummarizer, applied BEFORE the sum (dc_bidi_apply, then the shift move, fill
         0): the means are means of registered frames.  bin_frames: an integer in [1, 64], at most n_frames; 1 is a copy."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
-        try:
-            shape = tuple(int(v) for v in shape)
-        except TypeError:
-            raise ValueError('shape must be (H, W), not %r' % (shape,))
-        if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] > (1 << 30):
-            raise ValueError('shape must be (H, W) with 1 <= H * W <= 2**30, not %r' % (shape,))
-        n_frames = int(n_frames)
-        if not 1 <= n_frames <= MAX_FRAMES:
-            raise ValueError('n_frames must be in [1, %d], not %d' % (MAX_FRAMES, n_frames))
-        self.dtype = _frame_dtype(dtype)
-        self.bin_frames = _check_bin_frames(bin_frames, n_frames)
-        H, W = shape
-        if chunk_frames is None:
-            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
-        chunk_frames = int(chunk_frames)
-        if chunk_frames < 1:
-            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
-        bidi = _check_bidi(bidi, shape)
-        self.shape, self.n_frames = shape, n_frames
-        self.n_out = n_frames // self.bin_frames
-        self.chunk_frames = min(chunk_frames, n_frames)
-        self.fed = self.emitted = 0
+        self._declare(shape, n_frames, dtype, chunk_frames, shifts, fine_shifts, bidi)
+        self.bin_frames = _check_bin_frames(bin_frames, self.n_frames)
+        self.n_out = self.n_frames // self.bin_frames
+        self.emitted = 0
 
-        import torch
-        from . import net
-        from ._lib import lib
-        self._torch, self._net = torch, net
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('TemporalBinner needs a GPU (there is no CPU fallback)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        dev = self.device
+        torch = self._open(device, 'TemporalBinner')
         # the open bin's sum: read only once a call has left frames in it, so never cleared here
-        self._carry = torch.empty(H * W, dtype=torch.int32, device=dev)
-        self._stage = None
-        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
-                                                                                self.dtype == np.dtype(np.uint16), bidi)
+        self._carry = torch.empty(self.shape[0] * self.shape[1], dtype=torch.int32, device=self.device)
 
     def feed(self, frames):
         """The next frames of the recording, any t >= 1: what SeriesSummarizer.feed takes (numpy or memmap chunks of the
@@ -562,63 +297,19 @@ class TemporalBinner(object):
         read in place).  -> the bins this feed closed: a contiguous (k, H, W) torch.int16 tensor on the device holding the bits of
         the recording's dtype, k >= 0.  It is a FRESH allocation every time, written on the current stream: no later feed touches
         it, and a reader fed on the same stream right away reads it after the kernels that wrote it."""
-        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
-        if not on_device and not isinstance(frames, np.ndarray):
-            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
-        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
-            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
-        if on_device:
-            _check_device_frames(self._torch, frames, self.dtype, self.device, 'binner')
-        elif frames.dtype != self.dtype:
-            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
-        if frames.shape[0] < 1 or self.fed + frames.shape[0] > self.n_frames:
-            raise ValueError('%d frames after %d fed: the recording was declared to have %d' %
-                             (frames.shape[0], self.fed, self.n_frames))
-        torch, L = self._torch, self.L
-        H, W = self.shape
-        b, uns = self.bin_frames, int(self.dtype == np.dtype(np.uint16))
-        with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream(self.device)
-            st = main.cuda_stream
-            out = torch.empty(((self.fed % b + int(frames.shape[0])) // b, H, W), dtype=torch.int16, device=self.device)
-            first = self.emitted
+        return super(TemporalBinner, self).feed(frames)
 
-            def bin_time(fp, tc, t0):
-                k = (t0 % b + tc) // b
-                L.dc_series_bin_time(fp, uns, tc, H, W, b, t0 % b, self._carry.data_ptr(),
-                                     out.data_ptr() + 2 * H * W * (self.emitted - first) if k else None, st)
-                self.emitted += k
+    def _begin_feed(self, t):
+        out = self._torch.empty(((self.fed % self.bin_frames + t) // self.bin_frames,) + self.shape, dtype=self._torch.int16, device=self.device)
+        self._dst = out.data_ptr()           # where the next bin goes
+        return out, True
 
-            def consume(fp, tc):
-                if self._shifted is None:
-                    bin_time(fp, tc, self.fed)
-                else:
-                    self._shifted.run(fp, tc, self.fed, st, bin_time)
-                self.fed += tc
-            if on_device:
-                consume(frames.data_ptr(), int(frames.shape[0]))
-                frames.record_stream(main)
-            else:
-                if self._stage is None:          # names of its own: a reader alive at the same time keeps its slots
-                    self._stage = _TwoSlotStage(torch, self._net, self.device, 'tbin_stage', (self.chunk_frames, H, W))
-                self._stage.run(frames, main, consume)
-        return out
-
-
-def _feed_binned(frames, bin_frames, reader_of, device, chunk_frames, shifts, fine_shifts, bidi):
-    """The binned pass of the one-call functions: a TemporalBinner that carries the corrections in front of
-    reader_of(n_frames // bin_frames, device), a reader declared with the binned length and no corrections of its own.  The
-    trailing frames that close no bin are not read.  -> the reader, fed."""
-    T = int(frames.shape[0])
-    tb = TemporalBinner(tuple(frames.shape[1:]), T, frames.dtype, bin_frames=bin_frames, shifts=shifts, fine_shifts=fine_shifts, bidi=bidi,
-                        device=device, chunk_frames=chunk_frames)
-    reader = reader_of(tb.n_out, tb.device)
-    used = tb.n_out * tb.bin_frames
-    for a in range(0, used, tb.chunk_frames):
-        binned = tb.feed(np.asarray(frames[a:min(a + tb.chunk_frames, used)]))
-        if binned.shape[0]:
-            reader.feed(binned)
-    return reader
+    def _chunk(self, fp, tc, t0, st):
+        (H, W), b = self.shape, self.bin_frames
+        k = (t0 % b + tc) // b
+        self.L.dc_series_bin_time(fp, self._unsigned, tc, H, W, b, t0 % b, self._carry.data_ptr(), self._dst if k else None, st)
+        self._dst += 2 * H * W * k
+        self.emitted += k
 
 
 def _open_series(dspath, source):
@@ -669,6 +360,16 @@ def _open_series(dspath, source):
     return node, close                 # h5py: sliced chunk by chunk
 
 
+def _open_recording(dspath, source):
+    """_open_series, and the check that what it opened is a (T,H,W) recording (closed again if it is not)."""
+    frames, close = _open_series(dspath, source)
+    if len(frames.shape) != 3:
+        shape, frames = tuple(frames.shape), None
+        close()
+        raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, shape))
+    return frames, close
+
+
 def summarize_series_device(dspath, kind='mean', standardize=True, source='series/raw', device=None, chunk_frames=None,
                             shifts=None, fine_shifts=None, bin_frames=None, detrend_frames=None, keep=None, bidi=0):
     """Drop-in `series_summary_func`: streams `source` of the dataset through a SeriesSummarizer and returns the (H,W)
@@ -684,40 +385,13 @@ def summarize_series_device(dspath, kind='mean', standardize=True, source='serie
     keep: None, or a (T,) array of booleans (frames.flag_frames): the frames marked False are left out by a frames.FrameFilter after
     bidi and the shifts and before binning and detrending, whose b and L then count kept frames; all True gives what None gives."""
     _check_kind(kind)
-    _check_bidi(bidi)
-    if bin_frames is not None:
-        _check_bin_frames(bin_frames)
     if detrend_frames is not None:
         _check_detrend_frames(detrend_frames)
         if kind in ('mean16', 'max16'):
             raise ValueError('mean16 / max16 are the stored summaries of the whole recording: not served with detrend_frames')
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    if keep is not None:
-        from .frames import _check_keep, _feed_kept
-        keep = _check_keep(keep)
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        if keep is not None:
-            summ = _feed_kept(frames, keep, bin_frames, lambda n, dev: SeriesSummarizer(tuple(frames.shape[1:]), n, frames.dtype, device=dev,
-                                                                                        chunk_frames=chunk_frames, kinds=(kind,),
-                                                                                        detrend_frames=detrend_frames),
-                              device, chunk_frames, shifts, fine_shifts, bidi)
-        elif bin_frames is None:
-            summ = SeriesSummarizer(tuple(frames.shape[1:]), T, frames.dtype, device=device, chunk_frames=chunk_frames,
-                                    kinds=(kind,), shifts=shifts, fine_shifts=fine_shifts, bidi=bidi, detrend_frames=detrend_frames)
-            for a in range(0, T, summ.chunk_frames):
-                summ.feed(np.asarray(frames[a:a + summ.chunk_frames]))
-        else:
-            summ = _feed_binned(frames, bin_frames, lambda n, dev: SeriesSummarizer(tuple(frames.shape[1:]), n, frames.dtype, device=dev,
-                                                                                    chunk_frames=chunk_frames, kinds=(kind,),
-                                                                                    detrend_frames=detrend_frames),
-                                device, chunk_frames, shifts, fine_shifts, bidi)
-        out = summ.result(kind, standardize=standardize)
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
+
+    def reader_of(shape, n_frames, dtype, **kw):
+        return SeriesSummarizer(shape, n_frames, dtype, kinds=(kind,), detrend_frames=detrend_frames, **kw)
+    summ = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi, bin_frames, keep)
+    out = summ.result(kind, standardize=standardize)
     return np.asarray(out, dtype=np.float32)

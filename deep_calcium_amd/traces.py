@@ -24,8 +24,7 @@ Importing this module needs neither torch nor the GPU; constructing a RoiTraceEx
 """
 import numpy as np
 
-from .series import (_CHUNK_BYTES, _ShiftedChunks, _TwoSlotStage, _check_bidi, _check_device_frames, _check_known_shifts, _frame_dtype,
-                     _open_series)
+from ._reader import _FrameReader, _check_shape, _read_recording
 
 KINDS = ('sum', 'mean', 'zscore')
 # Longest CSR row handed to the kernel: a longer ROI is cut into rows of this many pixels, so that one whole-image ROI among
@@ -38,16 +37,6 @@ MAX_VOLUME = 1 << 46                  # DC_ROI_TRACE_MAX_VOLUME: T * H * W up to
 def _check_kind(kind):
     if kind not in KINDS:
         raise ValueError('trace kind %r is not one of %s' % (kind, ', '.join(KINDS)))
-
-
-def _check_shape(shape):
-    try:
-        shape = tuple(int(v) for v in shape)
-    except TypeError:
-        raise ValueError('shape must be (H, W), not %r' % (shape,))
-    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] > (1 << 30):
-        raise ValueError('shape must be (H, W) with 1 <= H * W <= 2**30, not %r' % (shape,))
-    return shape
 
 
 def _roi_pixels(rois, shape):
@@ -102,8 +91,9 @@ def rois_to_csr(rois, shape):
     return areas, row_off, row_pix, row_roi
 
 
-class RoiTraceExtractor(object):
+class RoiTraceExtractor(_FrameReader):
     """Owns the device state of one recording's ROI traces; feed() the frames in order, in chunks of any size, then result()."""
+    _stage_tag, _noun = 'traces_stage', 'extractor'
 
     def __init__(self, shape, n_frames, dtype, rois, device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
         """shifts: None, or the (n_frames, 2) integer (dy, dx) of every frame (numpy or a device tensor, e.g.
@@ -114,39 +104,11 @@ class RoiTraceExtractor(object):
         bidi: the whole-pixel offset of the odd lines (motion.estimate_bidi_device), undone by dc_bidi_apply (fill 0) before the
         shift move; with no shifts it is the only move."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
-        shape = _check_shape(shape)
-        H, W = shape
-        n_frames = int(n_frames)
-        if n_frames < 1 or n_frames * H * W > MAX_VOLUME:
-            raise ValueError('n_frames must be >= 1 with n_frames * H * W <= 2**46, not %d' % n_frames)
-        self.dtype = _frame_dtype(dtype)
-        areas, row_off, row_pix, row_roi = rois_to_csr(rois, shape)
-        if chunk_frames is None:
-            chunk_frames = max(1, _CHUNK_BYTES // (2 * H * W))
-        chunk_frames = int(chunk_frames)
-        if chunk_frames < 1:
-            raise ValueError('chunk_frames must be >= 1, not %d' % chunk_frames)
-        shifts, fine = _check_known_shifts(shifts, fine_shifts, n_frames, shape)
-        bidi = _check_bidi(bidi, shape)
-        self.shape, self.n_frames, self.areas = shape, n_frames, areas
-        self.n_rois = len(areas)
-        self.chunk_frames = min(chunk_frames, n_frames)
-        self.fed = 0
-        self._stage = None
-        self._stage_tag = 'traces_stage'
-        self._after_chunk = None
+        self._declare(shape, n_frames, dtype, chunk_frames, shifts, fine_shifts, bidi, max_volume=MAX_VOLUME)
+        areas, row_off, row_pix, row_roi = rois_to_csr(rois, self.shape)
+        self.areas, self.n_rois = areas, len(areas)
 
-        import torch
-        from . import net
-        from ._lib import lib
-        self._torch, self._net = torch, net
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('RoiTraceExtractor needs a GPU (there is no CPU fallback)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        torch = self._open(device, 'RoiTraceExtractor')
         dev = self.device
         self._areas = torch.from_numpy(areas).to(dev)
         self._row_off = torch.from_numpy(row_off).to(dev)
@@ -154,61 +116,17 @@ class RoiTraceExtractor(object):
         self._row_roi = torch.from_numpy(row_roi).to(dev)
         self._rows = len(row_roi)
         # every chunk writes its own columns of every row, so the state is never cleared
-        self.sums = torch.empty((self.n_rois, n_frames), dtype=torch.int64, device=dev)
-        self._shifted = None if shifts is None and not bidi else _ShiftedChunks(torch, self.L, dev, shifts, (self.chunk_frames, H, W), fine,
-                                                                                self.dtype == np.dtype(np.uint16), bidi)
-
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device)
+        self.sums = torch.empty((self.n_rois, self.n_frames), dtype=torch.int64, device=dev)
 
     def _launch(self, fp, tc, t0, st):
         """The sums of one chunk (weighted.WeightedTraceExtractor: the weighted entry point instead)."""
         H, W = self.shape
-        self.L.dc_roi_trace_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, t0, self._row_off.data_ptr(),
+        self.L.dc_roi_trace_accumulate(fp, self._unsigned, tc, t0, self._row_off.data_ptr(),
                                        self._row_pix.data_ptr(), self._row_roi.data_ptr(), self._rows, self.n_rois,
                                        self.sums.data_ptr(), self.n_frames, H, W, st)
 
-    def _accumulate(self, fp, tc, st):
-        def accumulate(fp, tc, t0):
-            self._launch(fp, tc, t0, st)
-            if self._after_chunk is not None:     # a second reader of the same frames, behind the sums (footprints.RoiFootprints)
-                self._after_chunk(fp, tc, t0, st)
-        if self._shifted is None:
-            accumulate(fp, tc, self.fed)
-        else:
-            self._shifted.run(fp, tc, self.fed, st, accumulate)
-        self.fed += tc
-
-    def feed(self, frames):
-        """The next frames of the recording, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype (staged
-        through two pinned slots, the upload of one chunk beside the kernel on the previous one), or a contiguous (t, H, W)
-        torch.int16 tensor on the extractor's device holding the recording's bits (read in place, no staging; the signedness
-        is the declared dtype's)."""
-        on_device = not isinstance(frames, np.ndarray) and hasattr(frames, 'is_cuda') and hasattr(frames, 'data_ptr')
-        if not on_device and not isinstance(frames, np.ndarray):
-            raise ValueError('frames must be a numpy array (or memmap) or a CUDA tensor, not %s' % type(frames).__name__)
-        if len(frames.shape) != 3 or tuple(frames.shape[1:]) != self.shape:
-            raise ValueError('frames must be (t, %d, %d), not %r' % (self.shape + (tuple(frames.shape),)))
-        if on_device:
-            _check_device_frames(self._torch, frames, self.dtype, self.device, 'extractor')
-        elif frames.dtype != self.dtype:
-            raise ValueError('frames are %s, the recording was declared %s' % (frames.dtype, self.dtype))
-        if frames.shape[0] < 1 or self.fed + frames.shape[0] > self.n_frames:
-            raise ValueError('%d frames after %d fed: the recording was declared to have %d' %
-                             (frames.shape[0], self.fed, self.n_frames))
-        torch = self._torch
-        with torch.cuda.device(self.device):
-            main = self._stream()
-            st = main.cuda_stream
-            if on_device:
-                self._accumulate(frames.data_ptr(), int(frames.shape[0]), st)
-                frames.record_stream(main)
-            else:
-                if self._stage is None:          # names of its own: a SeriesSummarizer alive at the same time keeps its slots
-                    H, W = self.shape
-                    self._stage = _TwoSlotStage(torch, self._net, self.device, self._stage_tag, (self.chunk_frames, H, W))
-                self._stage.run(frames, main, lambda fp, tc: self._accumulate(fp, tc, st))
-        return self
+    def _chunk(self, fp, tc, t0, st):
+        self._launch(fp, tc, t0, st)
 
     def sums_device(self):
         """The (R, T) int64 sums where they lie, on the device, once every frame has been fed: what dff.TraceBaseline reads in
@@ -237,6 +155,19 @@ class RoiTraceExtractor(object):
         return out.cpu().numpy()
 
 
+class _LeadingExtractor(RoiTraceExtractor):
+    """The extractor a second reader of the same chunks owns (footprints.RoiFootprints, roi_pairs.RoiPairCorr): staging slots
+    under the owner's name, and the owner's launches then(fp, tc, t0, st) behind the sums of every chunk, on the same stream."""
+
+    def __init__(self, stage_tag, then, *args, **kw):
+        self._stage_tag, self._then = stage_tag, then
+        super(_LeadingExtractor, self).__init__(*args, **kw)
+
+    def _chunk(self, fp, tc, t0, st):
+        self._launch(fp, tc, t0, st)
+        self._then(fp, tc, t0, st)
+
+
 def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device=None, chunk_frames=None, shifts=None,
                           fine_shifts=None, bidi=0):
     """The (R,T) traces of `rois` (any form rois_to_csr takes) over `source` of a dataset file, streamed chunk by chunk: the
@@ -245,23 +176,10 @@ def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device
     of a pixel (estimate_shifts_device(subpixel=True)): the frames are interpolated on the way in.  bidi: the offset of the odd lines
     (motion.estimate_bidi_device), undone on the way in before the shifts."""
     _check_kind(kind)
-    _check_bidi(bidi)
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        ext = RoiTraceExtractor(tuple(frames.shape[1:]), T, frames.dtype, rois, device=device, chunk_frames=chunk_frames,
-                                shifts=shifts, fine_shifts=fine_shifts, bidi=bidi)
-        for a in range(0, T, ext.chunk_frames):
-            ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
-        out = ext.result(kind)
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
-    return out
+    def reader_of(shape, n_frames, dtype, **kw):
+        return RoiTraceExtractor(shape, n_frames, dtype, rois, **kw)
+    ext = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi)
+    return ext.result(kind)
 
 
 def write_traces_dataset(path, traces, name, spikes=None):

@@ -30,6 +30,7 @@ Importing this module needs neither torch nor the GPU; constructing a WeightedTr
 """
 import numpy as np
 
+from ._reader import _read_recording
 from .traces import RoiTraceExtractor, _check_kind, _check_shape, _roi_pixels
 
 MAX_WEIGHT = 65535                    # any uint16 is a legal weight
@@ -108,6 +109,7 @@ def _as_coords(flat, W):
 
 class WeightedTraceExtractor(RoiTraceExtractor):
     """A RoiTraceExtractor whose accumulate call is dc_roi_wtrace_accumulate: feed() as there, then result()."""
+    _stage_tag = 'wtraces_stage'
 
     def __init__(self, shape, n_frames, dtype, rois, weights, device=None, chunk_frames=None, shifts=None, fine_shifts=None, bidi=0):
         """rois: a list of (k,2) [y,x] arrays or region dicts; weights: a list of (k,) integer arrays in [0, 65535], aligned entry
@@ -132,11 +134,10 @@ class WeightedTraceExtractor(RoiTraceExtractor):
         self.areas = wsums.astype(np.int32)               # W_r stands where the area stood (finalize, TraceBaseline, TracePairCorr)
         self._areas = self._torch.from_numpy(self.areas).to(self.device)
         self._row_wgt = self._torch.from_numpy(row_wgt.view(np.int16)).to(self.device)
-        self._stage_tag = 'wtraces_stage'
 
     def _launch(self, fp, tc, t0, st):
         H, W = self.shape
-        self.L.dc_roi_wtrace_accumulate(fp, int(self.dtype == np.dtype(np.uint16)), tc, t0, self._row_off.data_ptr(),
+        self.L.dc_roi_wtrace_accumulate(fp, self._unsigned, tc, t0, self._row_off.data_ptr(),
                                         self._row_pix.data_ptr(), self._row_wgt.data_ptr(), self._row_roi.data_ptr(), self._rows,
                                         self.n_rois, self.sums.data_ptr(), self.n_frames, H, W, st)
 
@@ -348,33 +349,18 @@ def weighted_traces_device(dspath, rois, weights=None, kind='mean', overlap='kee
     it), 'exclude' (shared pixels are dropped first; an ROI left without a pixel is a ValueError), 'demix' (demix_traces of the
     sums; kind is then 'demix', the float64 coefficients, or 'zscore', their population z-score in float64 numpy).  shifts /
     fine_shifts / bidi: as for extract_traces_device."""
-    from .series import _check_bidi, _open_series
     _check_overlap(overlap, kind)
-    _check_bidi(bidi)
-    if shifts is not None and fine_shifts is not None:
-        raise ValueError('give shifts= (whole pixels) or fine_shifts= (sixteenths of a pixel), not both')
-    frames, close = _open_series(dspath, source)
-    try:
-        if len(frames.shape) != 3:
-            raise ValueError('%s of %s is not a (T,H,W) recording: %r' % (source, dspath, tuple(frames.shape)))
-        T = int(frames.shape[0])
-        shape = _check_shape(frames.shape[1:])
-        rois, weights = _prepare(rois, weights, shape, overlap)
-        gram = None
+    gram = []
+
+    def reader_of(shape, n_frames, dtype, **kw):
+        shape = _check_shape(shape)
+        own, wgt = _prepare(rois, weights, shape, overlap)
         if overlap == 'demix':
-            gram = roi_gram(rois, weights, shape)
-            demix_traces(np.zeros((len(gram), 1), np.int64), gram)          # a group that cannot be demixed: before the pass, not after it
-        ext = WeightedTraceExtractor(shape, T, frames.dtype, rois, weights, device=device, chunk_frames=chunk_frames, shifts=shifts,
-                                     fine_shifts=fine_shifts, bidi=bidi)
-        for a in range(0, T, ext.chunk_frames):
-            ext.feed(np.asarray(frames[a:a + ext.chunk_frames]))
-        if overlap == 'demix':
-            out = demix_traces(ext.result('sum'), gram)
-            if kind == 'zscore':
-                out = zscore64(out)
-        else:
-            out = ext.result(kind)
-    finally:
-        frames = None                        # a view of the file mapping: released before the file is closed
-        close()
-    return out
+            gram.append(roi_gram(own, wgt, shape))
+            demix_traces(np.zeros((len(gram[0]), 1), np.int64), gram[0])    # a group that cannot be demixed: before the pass, not after it
+        return WeightedTraceExtractor(shape, n_frames, dtype, own, wgt, **kw)
+    ext = _read_recording(dspath, source, reader_of, device, chunk_frames, shifts, fine_shifts, bidi)
+    if overlap != 'demix':
+        return ext.result(kind)
+    out = demix_traces(ext.result('sum'), gram[0])
+    return zscore64(out) if kind == 'zscore' else out
