@@ -1,0 +1,216 @@
+// Spikes by deconvolution on the device (include/dcunet.h, "Spikes by deconvolution"): float (R,T) traces, dF/F as dc_trace_baseline
+// leaves them -> the non-negative AR(1) calcium c and the spikes s = c[t] - g c[t-1] that fit them best, by the pool-merging
+// (OASIS-style) forward pass of csrc/deconv_math.h.  The reference has no counterpart; the header's definitions are the
+// specification.  A trace is a strictly sequential computation, so the forward kernel gives one LANE to a trace and the memory
+// layout is the work: the traces are row-major, so a wave's lanes would read at stride ld; a tile of 64 traces x 64 frames is
+// staged through LDS with coalesced row reads instead and every lane then walks its own row of the tile.  The top pool stays in
+// registers; the pools below it lie in the caller's workspace as [depth][R] planes, so the lanes of a wave that stand at the
+// same depth touch one line.  Nothing here may be contracted or reassociated: the pragma of deconv_math.h and the per-file flag
+// in _build.py.
+#pragma clang fp contract(off)
+#include <vector>
+
+#include "common.h"
+#include "deconv_math.h"
+
+namespace {
+
+const int kLanes = 64;                       // traces per workgroup: one wave, one lane per trace
+const int kFrames = 64;                      // frames per staged tile
+const int kPitch = kFrames + 1;              // elements per tile row: lane l reads word l * 65 + k, one bank each (float), two (double)
+const int kFillThreads = 256;
+
+// The workspace: three planes of R * T 8-byte words, pool i of trace r at word i * R + r of each.
+struct DeviceStack {
+  double* v;
+  double* w;
+  int2* tl;                                  // (t0, l)
+  long R, r;
+  __device__ __forceinline__ DcPool load(int32_t i) const {
+    const long at = (long)i * R + r;
+    DcPool p;
+    p.v = v[at];
+    p.w = w[at];
+    const int2 x = tl[at];
+    p.t0 = x.x;
+    p.l = x.y;
+    return p;
+  }
+  __device__ __forceinline__ void store(int32_t i, const DcPool& p) {
+    const long at = (long)i * R + r;
+    v[at] = p.v;
+    w[at] = p.w;
+    tl[at] = make_int2(p.t0, p.l);
+  }
+};
+
+// One workgroup of one wave per 64 traces.  Rows r >= R and frames t >= T of a ragged tile are neither read nor written.
+template <typename In>
+__global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g,
+                                                               const double* __restrict__ G, const double* __restrict__ lam,
+                                                               const double* __restrict__ smin, double* ws, int* __restrict__ pools) {
+  __shared__ In tile[kLanes * kPitch];
+  const int lane = threadIdx.x;
+  const long r0 = (long)blockIdx.x * kLanes;
+  const long r = r0 + lane;
+  const bool mine = r < R;
+  const int rows = R - r0 < kLanes ? (int)(R - r0) : kLanes;
+  const long plane = (long)R * T;
+  DeviceStack st = {ws, ws + plane, reinterpret_cast<int2*>(ws + 2 * plane), (long)R, r};
+  const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
+  DcPool top = dc_deconv_new(0.0, 0);
+  int32_t n = 0;
+  for (long f0 = 0; f0 < T; f0 += kFrames) {
+    const int frames = T - f0 < kFrames ? (int)(T - f0) : kFrames;
+    __syncthreads();                                                 // the previous tile has been consumed
+    if (lane < frames) {
+#pragma unroll 8
+      for (int j = 0; j < rows; ++j) tile[j * kPitch + lane] = y[(r0 + j) * ld + f0 + lane];
+    }
+    __syncthreads();
+    if (mine) {
+      for (int k = 0; k < frames; ++k) {
+        const long t = f0 + k;
+        const double x = (double)tile[lane * kPitch + k] - dc_deconv_mu(la, g, t, T);
+        dc_deconv_push(top, n, st, x, t, G, sm);
+      }
+    }
+  }
+  if (mine) {
+    st.store(n - 1, top);                                            // T >= 1: n >= 1.  The fill kernel reads the workspace only
+    pools[r] = n;
+  }
+}
+
+// One thread per sample (r, t): the pool that holds frame t is the last whose start is <= t (the starts ascend), found by
+// bisection over the trace's n pools.  Every output element is written, each by one product or one multiply-subtract.
+__global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double* __restrict__ ws, const int* __restrict__ pools, int R, long T,
+                                                                  double g, const double* __restrict__ G, double* __restrict__ calcium,
+                                                                  double* __restrict__ spikes) {
+  const long plane = (long)R * T;
+  const long idx = (long)blockIdx.x * kFillThreads + threadIdx.x;
+  if (idx >= plane) return;
+  const long r = idx / T;
+  const int32_t t = (int32_t)(idx - r * T);
+  const double* v = ws;
+  const int2* tl = reinterpret_cast<const int2*>(ws + 2 * plane);
+  int32_t lo = 0, hi = pools[r] - 1;                                 // pool lo starts at or before t, pool hi + 1 (if any) after it
+  while (lo < hi) {
+    const int32_t mid = lo + (hi - lo + 1) / 2;                      // lo < mid <= hi
+    if (tl[(long)mid * R + r].x <= t) lo = mid;
+    else hi = mid - 1;
+  }
+  const int2 own = tl[(long)lo * R + r];
+  const int32_t k = t - own.x;
+  const double c = dc_deconv_calcium(v[(long)lo * R + r], G[k]);
+  double s = 0.0;
+  if (k == 0 && lo > 0) {
+    const long below = (long)(lo - 1) * R + r;
+    s = dc_deconv_spike(c, g, dc_deconv_calcium(v[below], G[tl[below].y - 1]));
+  }
+  calcium[idx] = c;
+  spikes[idx] = s;
+}
+
+struct HostStack {
+  std::vector<DcPool>* pools;
+  DcPool load(int32_t i) const { return (*pools)[(size_t)i]; }
+  void store(int32_t i, const DcPool& p) { (*pools)[(size_t)i] = p; }
+};
+
+template <typename In>
+void deconv_host_row(const In* y, long T, double g, const double* G, double lam, double smin, std::vector<DcPool>& pool, double* calcium,
+                     double* spikes, int* pools) {
+  HostStack st = {&pool};
+  DcPool top = dc_deconv_new(0.0, 0);
+  int32_t n = 0;
+  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, (double)y[t] - dc_deconv_mu(lam, g, t, T), t, G, smin);
+  st.store(n - 1, top);
+  *pools = n;
+  for (int32_t i = 0; i < n; ++i) {
+    const DcPool& p = pool[(size_t)i];
+    for (int32_t k = 0; k < p.l; ++k) {
+      calcium[p.t0 + k] = dc_deconv_calcium(p.v, G[k]);
+      spikes[p.t0 + k] = 0.0;
+    }
+    if (i > 0) spikes[p.t0] = dc_deconv_spike(calcium[p.t0], g, calcium[p.t0 - 1]);
+  }
+}
+
+int check_counts(const char* who, const void* y, int is_f64, long ld, int R, long T) {
+  DC_REQUIRE(y, DC_EINVAL, "%s: null pointer", who);
+  DC_REQUIRE(is_f64 == 0 || is_f64 == 1, DC_EINVAL, "%s: is_f64 = %d is neither 0 nor 1", who, is_f64);
+  DC_REQUIRE(R >= 0 && T >= 0, DC_EINVAL, "%s: negative count (R %d, T %ld)", who, R, T);
+  DC_REQUIRE(ld >= T, DC_EINVAL, "%s: ld = %ld is below T = %ld", who, ld, T);
+  return DC_OK;
+}
+
+int check_limits(const char* who, int R, long T, double g) {
+  DC_REQUIRE(g > 0.0 && g < 1.0, DC_EINVAL, "%s: g = %g is outside (0, 1)", who, g);      // a NaN fails both comparisons
+  DC_REQUIRE(T <= DC_TRACE_DECONV_MAX_FRAMES, DC_EUNSUP, "%s: T = %ld is over the limit of %ld frames", who, T, DC_TRACE_DECONV_MAX_FRAMES);
+  DC_REQUIRE((long)R * T <= DC_TRACE_DECONV_MAX_SAMPLES, DC_EUNSUP, "%s: R * T = %ld is over the limit of %ld samples", who, (long)R * T,
+             DC_TRACE_DECONV_MAX_SAMPLES);
+  return DC_OK;
+}
+
+}  // namespace
+
+extern "C" long dc_trace_deconv_ws_bytes(int R, long T) {
+  if (R <= 0 || T <= 0 || T > DC_TRACE_DECONV_MAX_FRAMES || (long)R * T > DC_TRACE_DECONV_MAX_SAMPLES) return 0;
+  return 24L * R * T;
+}
+
+extern "C" int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, long T, double g, const double* G, const double* lam,
+                                   const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream) {
+  const char* who = "dc_trace_deconv_ar1";
+  DC_REQUIRE(G && lam && smin && ws && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
+  int rc = check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  rc = check_limits(who, R, T, g);
+  if (rc != DC_OK) return rc;
+  DC_REQUIRE((((uintptr_t)G | (uintptr_t)lam | (uintptr_t)smin | (uintptr_t)ws | (uintptr_t)calcium | (uintptr_t)spikes) & 7) == 0 &&
+                 (((uintptr_t)pools) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+             DC_EINVAL, "%s: misaligned buffer", who);
+  if (R == 0 || T == 0) return DC_OK;
+  const unsigned groups = (unsigned)(((long)R + kLanes - 1) / kLanes);                      // <= 2^25: no cap
+  if (is_f64)
+    hipLaunchKernelGGL(deconv_forward_kernel<double>, dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const double*)y, ld, R, T, g, G, lam,
+                       smin, (double*)ws, pools);
+  else
+    hipLaunchKernelGGL(deconv_forward_kernel<float>, dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const float*)y, ld, R, T, g, G, lam,
+                       smin, (double*)ws, pools);
+  DC_CHECK_LAUNCH(who);
+  const unsigned blocks = (unsigned)(((long)R * T + kFillThreads - 1) / kFillThreads);      // <= 2^23: no cap
+  hipLaunchKernelGGL(deconv_fill_kernel, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)stream, (const double*)ws, pools, R, T, g, G, calcium,
+                     spikes);
+  DC_CHECK_LAUNCH(who);
+  return DC_OK;
+}
+
+extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int R, long T, const double* G, const double* lam,
+                                        const double* smin, double* calcium, double* spikes, int* pools) {
+  const char* who = "dc_trace_deconv_ar1_host";
+  DC_REQUIRE(G && lam && smin && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
+  DC_REQUIRE((((uintptr_t)G | (uintptr_t)lam | (uintptr_t)smin | (uintptr_t)calcium | (uintptr_t)spikes) & 7) == 0 &&
+                 (((uintptr_t)pools) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+             DC_EINVAL, "%s: misaligned buffer", who);
+  int rc = check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  if (R == 0 || T == 0) return DC_OK;                                // G is not read: without frames it need not hold g
+  DC_REQUIRE(G[0] == 1.0, DC_EINVAL, "%s: G[0] = %g is not 1", who, G[0]);
+  const double g = G[1];
+  rc = check_limits(who, R, T, g);
+  if (rc != DC_OK) return rc;
+  for (int r = 0; r < R; ++r)
+    DC_REQUIRE(lam[r] >= 0.0 && smin[r] >= 0.0, DC_EINVAL, "%s: trace %d: lam = %g, smin = %g: neither may be negative", who, r, lam[r], smin[r]);
+  std::vector<DcPool> pool((size_t)T);
+  for (int r = 0; r < R; ++r) {
+    double* c = calcium + (long)r * T;
+    double* s = spikes + (long)r * T;
+    if (is_f64)
+      deconv_host_row((const double*)y + (long)r * ld, T, g, G, lam[r], smin[r], pool, c, s, pools + r);
+    else
+      deconv_host_row((const float*)y + (long)r * ld, T, g, G, lam[r], smin[r], pool, c, s, pools + r);
+  }
+  return DC_OK;
+}

@@ -1,0 +1,90 @@
+// The arithmetic of the AR(1) deconvolution (include/dcunet.h, "Spikes by deconvolution"; csrc/deconv.hip): the push / merge step
+// of the pool stack and the two output formulas.  Plain C++ like footprint_math.h, so the same inline functions compile for the
+// device kernels, for the host entry point dc_trace_deconv_ar1_host and into a stand-alone host program
+// (tests/native/deconv_math_check.cpp, run under the address / undefined-behaviour sanitizers).  The result is defined bit for bit:
+// IEEE double adds, multiplies, one division per merge and comparisons in the order written here.  No fused multiply-add and no
+// reassociation anywhere: the pragma below, and -ffp-contract=off for deconv.hip in _build.py.
+#pragma once
+#pragma clang fp contract(off)
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define DC_DECONV_HD __host__ __device__ inline
+#else
+#define DC_DECONV_HD inline
+#endif
+
+// A pool: `l` consecutive frames from t0 on whose calcium is v G[k], k = 0 .. l - 1; w is the weight of v in a merge.
+struct DcPool {
+  double v, w;
+  int32_t t0, l;
+};
+
+// what is subtracted from frame t of a trace of T frames: the L1 penalty lam on the spikes, written as a shift of the data
+DC_DECONV_HD double dc_deconv_mu(double lam, double g, long t, long T) { return t < T - 1 ? lam * (1.0 - g) : lam; }
+
+DC_DECONV_HD DcPool dc_deconv_new(double x, long t) {
+  DcPool q;
+  q.v = x;
+  q.w = 1.0;
+  q.t0 = (int32_t)t;
+  q.l = 1;
+  return q;
+}
+
+// does q, the pool above p, start below what p has decayed to (a = G[p.l]) plus the smallest spike allowed?
+DC_DECONV_HD bool dc_deconv_violates(const DcPool& p, const DcPool& q, double a, double smin) { return q.v < a * p.v + smin; }
+
+// p and the pool q above it as one pool; a = G[p.l].  The parentheses are the evaluation order.
+DC_DECONV_HD DcPool dc_deconv_merge(const DcPool& p, const DcPool& q, double a) {
+  const double num = p.w * p.v + (a * q.w) * q.v;
+  const double den = p.w + (a * a) * q.w;
+  DcPool m;
+  m.v = num / den;
+  m.w = den;
+  m.t0 = p.t0;
+  m.l = p.l + q.l;
+  return m;
+}
+
+// One frame of the forward pass.  The stack holds n pools: `top` is the highest (meaningless while n == 0), the n - 1 below it lie
+// in `st`, pool i at st.load(i) / st.store(i, .).  Pushes the pool (x, 1, t, 1) and merges downwards while the pool below the top
+// is violated.  A pool of st is only read when it is compared and only written when a new pool comes to lie above it, so a
+// frame that merges nothing stores once and loads nothing.
+template <class Stack>
+DC_DECONV_HD void dc_deconv_push(DcPool& top, int32_t& n, Stack& st, double x, long t, const double* G, double smin) {
+  DcPool cur = dc_deconv_new(x, t);
+  if (n == 0) {
+    top = cur;
+    n = 1;
+    return;
+  }
+  int32_t m = n - 1;                         // the pools of st that lie below cur
+  DcPool p = top;                            // the pool right below cur:
+  bool held = true;                          //   the old top, which st does not hold (true), or pool m - 1 of st (false)
+  bool below = true;                         // is there a pool below cur at all
+  for (;;) {
+    const double a = G[p.l];
+    if (!dc_deconv_violates(p, cur, a, smin)) break;
+    cur = dc_deconv_merge(p, cur, a);
+    if (held) held = false;                  // the old top is gone
+    else --m;                                // pool m - 1 of st is gone
+    if (m == 0) {
+      below = false;
+      break;
+    }
+    p = st.load(m - 1);
+  }
+  if (below && held) st.store(m++, p);       // nothing merged: the old top becomes the highest pool of st
+  top = cur;
+  n = m + 1;
+}
+
+// calcium of frame t0 + k of a pool of value v: b G[k] with b = v where v > 0 and +0.0 otherwise
+DC_DECONV_HD double dc_deconv_calcium(double v, double Gk) {
+  const double b = v > 0.0 ? v : 0.0;
+  return b * Gk;
+}
+
+// the spike at the first frame of a pool that has a pool below it: c is its own calcium there, cprev the calcium one frame earlier
+DC_DECONV_HD double dc_deconv_spike(double c, double g, double cprev) { return c - g * cprev; }

@@ -1,0 +1,216 @@
+"""Spikes by deconvolution on the device: non-negative AR(1) deconvolution of dF/F traces, without a trained model.
+
+The last stage of the chain for a user who has no UNet1D model file.  Calcium c[t] = g c[t-1] + s[t] with s >= 0 is fitted to every
+trace by an OASIS-style pool-merging forward pass; the reference has no counterpart, the definitions in include/dcunet.h ("Spikes by
+deconvolution") are the specification, and csrc/deconv_math.h is their one implementation: IEEE double operations in a fixed order,
+so the results are defined bit for bit.
+
+    kind      dtype     what
+    calcium   float64   c: per pool, b G[k] with b = max(v, +0.0)
+    spikes    float64   s = c[t] - g c[t-1] at the first frame of every pool but the first, +0.0 elsewhere; an event is s > 0
+    pools     int32     the number of pools of each trace
+
+    g = ar1_gamma(tau=1.0, fps=30.0)
+    dec = TraceDeconvolver(tb.result_device('dff'), g, s_min=3.0 * trace_noise(tb.result('dff')), lam=0.0)
+    c, s, n = dec.result('calcium'), dec.result('spikes'), dec.result('pools')
+
+    c, s = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau=1.0, fps=30.0, k=3.0)    # dff_traces_device, then the above
+
+Not built: AR(2), estimating g from the autocovariance, the noise-constrained search for lam, a baseline term (feed dF/F, whose
+baseline is 0).
+
+Importing this module needs neither torch nor the GPU; constructing a TraceDeconvolver does (there is no CPU fallback).
+"""
+import numpy as np
+
+KINDS = ('calcium', 'spikes', 'pools')
+MAX_FRAMES = 1 << 24                  # DC_TRACE_DECONV_MAX_FRAMES
+MAX_SAMPLES = 1 << 31                 # DC_TRACE_DECONV_MAX_SAMPLES
+
+
+def _check_kind(kind):
+    if kind not in KINDS:
+        raise ValueError('deconvolution kind %r is not one of %s' % (kind, ', '.join(KINDS)))
+
+
+# ---- the host helpers: definitions, float64 numpy -----------------------------------------------------------------------------------
+def ar1_gamma(tau, fps):
+    """g = exp(-1 / (tau * fps)): the decay per frame of an indicator whose decay time is tau seconds, recorded at fps frames a second."""
+    try:
+        tau, fps = float(tau), float(fps)
+    except (TypeError, ValueError):
+        raise ValueError('tau and fps must be numbers, not %r and %r' % (tau, fps))
+    if not (0.0 < tau < np.inf and 0.0 < fps < np.inf):
+        raise ValueError('tau and fps must be positive and finite, not %r and %r' % (tau, fps))
+    return _check_gamma(float(np.exp(-1.0 / (tau * fps))))
+
+
+def _check_gamma(g):
+    try:
+        g = float(g)
+    except (TypeError, ValueError):
+        raise ValueError('g must be a number in (0, 1), not %r' % (g,))
+    if not 0.0 < g < 1.0:                      # NaN fails both comparisons
+        raise ValueError('g must be inside (0, 1), not %r' % (g,))
+    return g
+
+
+def ar1_table(g, T):
+    """G, float64[T + 1]: G[0] = 1, G[l] = G[l-1] * g by repeated multiplication (never pow: the table IS the definition)."""
+    g = _check_gamma(g)
+    if isinstance(T, (bool, np.bool_)) or not isinstance(T, (int, np.integer)) or T < 0:
+        raise ValueError('T must be a non-negative integer, not %r' % (T,))
+    G = np.empty(int(T) + 1, np.float64)
+    G[0] = 1.0
+    G[1:] = g
+    return np.multiply.accumulate(G)           # a sequential left fold: G[l] = G[l-1] * g
+
+
+def trace_noise(y):
+    """Per row of an (R, T) matrix: d = diff(float64(y)), sigma = 1.4826 * median(|d - median(d)|) / sqrt(2), the robust noise of
+    the trace from its first difference.  0.0 for T < 3.  float64[R]."""
+    y = np.asarray(y)
+    if y.ndim != 2 or y.dtype.kind not in 'fiu':
+        raise ValueError('traces must be a numeric (R, T) matrix, not %s %r' % (y.dtype, y.shape))
+    R, T = y.shape
+    if T < 3:
+        return np.zeros(R, np.float64)
+    d = np.diff(y.astype(np.float64), axis=1)
+    return 1.4826 * np.median(np.abs(d - np.median(d, axis=1, keepdims=True)), axis=1) / np.sqrt(2.0)
+
+
+def _per_trace(x, what, R):
+    """A scalar or a length-R array of finite doubles >= 0 -> float64[R]."""
+    try:
+        a = np.asarray(x, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a number or %d numbers, not %r' % (what, R, x))
+    if a.ndim == 0:
+        a = np.full(R, float(a), np.float64)
+    if a.shape != (R,):
+        raise ValueError('%s must be a scalar or one value per trace (%d), not shape %r' % (what, R, a.shape))
+    bad = np.flatnonzero(~(np.isfinite(a) & (a >= 0.0)))
+    if bad.size:
+        raise ValueError('%s must be finite and >= 0: trace %d has %r' % (what, int(bad[0]), float(a[bad[0]])))
+    return np.ascontiguousarray(a)
+
+
+def _is_device_tensor(x):
+    return not isinstance(x, np.ndarray) and hasattr(x, 'is_cuda') and hasattr(x, 'data_ptr')
+
+
+def _check_traces(y):
+    """(R, T) float32 or float64, numpy or a device tensor -> (R, T, is_f64); ValueError otherwise."""
+    if _is_device_tensor(y):
+        if not y.is_cuda or str(y.dtype) not in ('torch.float32', 'torch.float64') or y.dim() != 2:
+            raise ValueError('traces must be an (R, T) float32 or float64 tensor on the device, not %s %r' % (y.dtype, tuple(y.shape)))
+        if y.shape[1] > 1 and y.stride(1) != 1 or y.shape[0] > 1 and y.stride(0) < y.shape[1]:
+            raise ValueError('traces: the rows of a device tensor must be contiguous (strides %r)' % (tuple(y.stride()),))
+        f64 = str(y.dtype) == 'torch.float64'
+    elif isinstance(y, np.ndarray):
+        if y.ndim != 2 or y.dtype not in (np.float32, np.float64):
+            raise ValueError('traces must be an (R, T) float32 or float64 array, not %s %r' % (y.dtype, y.shape))
+        f64 = y.dtype == np.float64
+    else:
+        raise ValueError('traces must be a numpy array or a device tensor, not %s' % type(y).__name__)
+    R, T = int(y.shape[0]), int(y.shape[1])
+    if R < 1 or T < 1:
+        raise ValueError('traces are empty: %r' % ((R, T),))
+    if T > MAX_FRAMES:
+        raise ValueError('T = %d frames is over the limit of 2**24' % T)
+    if R * T > MAX_SAMPLES:
+        raise ValueError('R * T = %d samples is over the limit of 2**31' % (R * T))
+    if isinstance(y, np.ndarray):
+        bad = np.flatnonzero(~np.isfinite(y).all(axis=1))
+        if bad.size:
+            raise ValueError('traces: row %d holds a value that is not finite' % int(bad[0]))
+    return R, T, f64
+
+
+class TraceDeconvolver(object):
+    """Owns the device state of one deconvolution: the traces, the table G, the workspace of pools and the three results.  The
+    kernels run at most once; result() only copies."""
+
+    def __init__(self, traces, g, s_min=0.0, lam=0.0, device=None):
+        """traces: (R, T) float32 or float64, numpy (checked for non-finite values) or a tensor already on the device (read in
+        place, never written; THE CALLER PROMISES FINITE VALUES).  g in (0, 1).  s_min, lam: a scalar or one value per trace, >= 0."""
+        # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
+        R, T, f64 = _check_traces(traces)
+        self.g = _check_gamma(g)
+        smin = _per_trace(s_min, 's_min', R)
+        lam = _per_trace(lam, 'lam', R)
+        table = ar1_table(self.g, T)
+        self.n_traces, self.n_frames = R, T
+
+        import torch
+        from ._lib import lib
+        self._torch = torch
+        self.L = lib()
+        if not torch.cuda.is_available():
+            from ._lib import DcunetError
+            raise DcunetError('TraceDeconvolver needs a GPU (there is no CPU fallback)')
+        if device is not None:
+            dev = torch.device(device)
+        elif _is_device_tensor(traces):
+            dev = traces.device
+        else:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        self.device = dev
+        if _is_device_tensor(traces):
+            if traces.device != dev:
+                raise ValueError('traces are on %s, the deconvolution runs on %s' % (traces.device, dev))
+            y = traces
+        else:
+            y = torch.from_numpy(np.ascontiguousarray(traces)).to(dev)
+        self._y, self._f64 = y, f64
+        self._ld = int(y.stride(0)) if R > 1 else max(int(y.stride(0)), T)
+        self._G = torch.from_numpy(table).to(dev)
+        self._smin = torch.from_numpy(smin).to(dev)
+        self._lam = torch.from_numpy(lam).to(dev)
+        self._out = None
+
+    def _run(self):
+        if self._out is None:
+            torch, R, T = self._torch, self.n_traces, self.n_frames
+            with torch.cuda.device(self.device):
+                ws = torch.empty(self.L.dc_trace_deconv_ws_bytes(R, T) // 8, dtype=torch.float64, device=self.device)
+                c = torch.empty((R, T), dtype=torch.float64, device=self.device)
+                s = torch.empty((R, T), dtype=torch.float64, device=self.device)
+                n = torch.empty(R, dtype=torch.int32, device=self.device)
+                self.L.dc_trace_deconv_ar1(self._y.data_ptr(), int(self._f64), self._ld, R, T, self.g, self._G.data_ptr(), self._lam.data_ptr(),
+                                           self._smin.data_ptr(), ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(),
+                                           torch.cuda.current_stream(self.device).cuda_stream)
+            self._out = dict(calcium=c, spikes=s, pools=n)        # the workspace goes back to the allocator (stream-ordered)
+        return self._out
+
+    def result_device(self, kind='spikes'):
+        """result(kind) as a tensor on the device (the object's own state: do not write to it)."""
+        _check_kind(kind)
+        return self._run()[kind]
+
+    def result(self, kind='spikes'):
+        """(R, T) float64 for 'calcium' and 'spikes', int32[R] for 'pools'."""
+        return self.result_device(kind).cpu().numpy()
+
+
+def deconvolve_traces_device(dspath, rois, window, tau, fps, k=3.0, lam=0.0, **dff_kw):
+    """-> (calcium, spikes), float64 (R, T): the dF/F traces of `rois` over a dataset file (dff_traces_device(dspath, rois, window,
+    **dff_kw)) deconvolved with g = ar1_gamma(tau, fps), s_min = k * trace_noise(dff) per trace and the penalty lam."""
+    g = ar1_gamma(tau, fps)
+    try:
+        k = float(k)
+    except (TypeError, ValueError):
+        raise ValueError('k must be a number >= 0, not %r' % (k,))
+    if not 0.0 <= k < np.inf:
+        raise ValueError('k must be finite and >= 0, not %r' % (k,))
+    if np.ndim(lam) != 0:
+        raise ValueError('lam must be a scalar here, not shape %r' % (np.shape(lam),))
+    _per_trace(lam, 'lam', 1)
+    if dff_kw.get('kind', 'dff') != 'dff':
+        raise ValueError('the deconvolution takes dF/F: kind = %r is not supported' % (dff_kw['kind'],))
+    from .dff import dff_traces_device
+    dff = dff_traces_device(dspath, rois, window, **dff_kw)
+    dec = TraceDeconvolver(dff, g, s_min=k * trace_noise(dff), lam=lam, device=dff_kw.get('device'))
+    return dec.result('calcium'), dec.result('spikes')

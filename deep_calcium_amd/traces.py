@@ -182,9 +182,11 @@ def extract_traces_device(dspath, rois, kind='mean', source='series/raw', device
     return ext.result(kind)
 
 
-def write_traces_dataset(path, traces, name, spikes=None):
+def write_traces_dataset(path, traces, name, spikes=None, extra=None):
     """A dataset file of the spikes model's schema (unet_1d_segmentation.py:182-187): the attribute `name`, `traces` (R,T) and,
-    when given, `spikes` (R,T) as uint8.  HDF5 through hdf5_min.Writer; a path ending in .npz gets the same members instead."""
+    when given, `spikes` (R,T) as uint8.  HDF5 through hdf5_min.Writer; a path ending in .npz gets the same members instead.
+    extra: None, or a dict of name -> numeric (R,T) array, written as further datasets in their own dtype (the `calcium` and
+    `deconvolved` of deep_calcium_amd.deconv); with None the file is what it was before the argument existed, byte for byte."""
     traces = np.asarray(traces)
     if traces.ndim != 2 or traces.dtype.kind not in 'fiu':
         raise ValueError('traces must be a numeric (R,T) matrix, not %s %r' % (traces.dtype, traces.shape))
@@ -193,10 +195,19 @@ def write_traces_dataset(path, traces, name, spikes=None):
         if spikes.shape != traces.shape:
             raise ValueError('spikes are %r, traces %r' % (spikes.shape, traces.shape))
         spikes = spikes.astype(np.uint8)
+    more = []
+    for key, value in (extra or {}).items():
+        value = np.asarray(value)
+        if not isinstance(key, str) or not key or '/' in key or key in ('traces', 'spikes', 'name'):
+            raise ValueError('extra: %r cannot name a further dataset' % (key,))
+        if value.shape != traces.shape or value.dtype.kind not in 'fiu':
+            raise ValueError('extra[%r] is %s %r, the traces are %r' % (key, value.dtype, value.shape, traces.shape))
+        more.append((key, value))
     if str(path).endswith('.npz'):
         members = dict(traces=traces, name=np.array(str(name)))
         if spikes is not None:
             members['spikes'] = spikes
+        members.update(more)
         np.savez(path, **members)
         return path
     from . import hdf5_min
@@ -205,5 +216,7 @@ def write_traces_dataset(path, traces, name, spikes=None):
     w.create_dataset('traces', data=traces)
     if spikes is not None:
         w.create_dataset('spikes', data=spikes)
+    for key, value in more:
+        w.create_dataset(key, data=value)
     w.save(path)
     return path

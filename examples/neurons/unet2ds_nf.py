@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve TAU --fps F [--spike-k K]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -34,7 +34,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
                               estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
                               split_rois_device, detrend_plan, merge_rois_device, make_template, frame_quality_device, flag_frames,
-                              footprint_weights, exclude_overlap, weighted_traces_device)
+                              footprint_weights, exclude_overlap, weighted_traces_device, TraceDeconvolver, ar1_gamma, trace_noise)
 from deep_calcium_amd.weighted import shared_pixels            # noqa: E402
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
@@ -135,7 +135,8 @@ def _n_frames(dspath):
 
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
-           bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None, weighted=None, overlap='keep'):
+           bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None, weighted=None, overlap='keep', deconvolve=None,
+           fps=None, spike_k=3.0):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -179,7 +180,11 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     corr < FLOOR or weight 0 are dropped, ROIs left empty too) and the traces are the weighted ones (kind, or dF/F with the weight
     sum where the area stood).  overlap (with weighted): 'keep' -- a pixel two ROIs share counts for both --, 'exclude' -- shared
     pixels are dropped from all --, 'demix' -- the least-squares coefficients of the footprints (deep_calcium_amd.demix_traces,
-    float64; z-scored with --kind zscore); not together with dff, whose kernels take integers."""
+    float64; z-scored with --kind zscore); not together with dff, whose kernels take integers.
+    deconvolve=TAU (with dff and fps=F): spikes without a trained model -- the dF/F traces are deconvolved on the GPU with the AR(1)
+    decay g = exp(-1 / (TAU F)) (TAU: the indicator's decay time in seconds, F: frames a second) and the smallest spike
+    spike_k * sigma_hat of every trace (deep_calcium_amd.TraceDeconvolver, trace_noise); the file gets the float64 datasets
+    `calcium` and `deconvolved` (the spikes; an event is a value > 0) beside `traces`."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -193,6 +198,13 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--bidi searches within +-P pixels, P in [0, 16], not %d' % bidi)
     if dff is None and neuropil is not None:
         raise ValueError('--neuropil needs --dff')
+    if deconvolve is not None and dff is None:
+        raise ValueError('--deconvolve needs --dff: the deconvolution has no baseline term')
+    if deconvolve is not None and fps is None:
+        raise ValueError('--deconvolve needs --fps: the decay per frame is exp(-1 / (TAU * fps))')
+    if deconvolve is not None and not spike_k >= 0:
+        raise ValueError('--spike-k is the smallest spike in units of the trace noise, K >= 0, not %r' % (spike_k,))
+    g = None if deconvolve is None else ar1_gamma(deconvolve, fps)
     if bin_frames is not None and refine is None and split is None:
         raise ValueError('--bin-frames needs --refine or --split: it bins the frames those passes correlate')
     if bin_frames is not None and not 1 <= bin_frames <= 64:
@@ -338,7 +350,16 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             tr = dff_traces_device(dspath, mask, dff, percentile=percentile, neuropil=neuropil, **moves(dspath))
         else:
             tr = extract_traces_device(dspath, mask, kind=kind, **moves(dspath))
-        out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name)
+        extra = None
+        if g is not None:
+            sigma = trace_noise(tr)
+            dec = TraceDeconvolver(tr, g, s_min=spike_k * sigma)
+            extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
+            events = (extra['deconvolved'] > 0).sum(1)
+            logger.info('%s: deconvolved with g = %.6f (tau %g s at %g frames/s), s_min = %g sigma_hat, median sigma_hat %.4g: '
+                        'events per ROI min / median / max = %d / %g / %d' % (name, g, deconvolve, fps, spike_k, float(np.median(sigma)),
+                                                                              int(events.min()), float(np.median(events)), int(events.max())))
+        out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name, extra=extra)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
         logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
 
@@ -385,6 +406,12 @@ if __name__ == '__main__':
     sp_trc.add_argument('--percentile', help='with --dff: the integer percentile of the baseline (default 8)', default=8, type=int, metavar='Q')
     sp_trc.add_argument('--neuropil', help='with --dff: subtract WEIGHT times the trace of the ring INNER < distance <= OUTER (e.g. 2,12,0.7)',
                         default=None, type=_neuropil_arg, metavar='INNER,OUTER,WEIGHT')
+    sp_trc.add_argument('--deconvolve', help='with --dff and --fps: deconvolve the dF/F traces (non-negative AR(1), no trained model) with the '
+                        'indicator decay time TAU in seconds; writes `calcium` and `deconvolved` beside `traces`', default=None, type=float,
+                        metavar='TAU')
+    sp_trc.add_argument('--fps', help='with --deconvolve: the frame rate of the recording in frames per second', default=None, type=float, metavar='F')
+    sp_trc.add_argument('--spike-k', help='with --deconvolve: the smallest spike allowed, in units of every trace\'s noise (default 3)', default=3.0,
+                        type=float, metavar='K', dest='spike_k')
     sp_trc.add_argument('--refine', help='refine every ROI by its footprint map first: keep the pixels whose correlation with the trace is >= THR',
                         default=None, type=float, metavar='THR')
     sp_trc.add_argument('--halo', help='with --refine: how far beyond an ROI, in pixels, its footprint map reaches (0..16, default 2)', default=2,
@@ -414,6 +441,10 @@ if __name__ == '__main__':
         ap.error('choose an action: train, evaluate, predict or traces')
     if args['which'] == 'traces' and args['overlap'] == 'demix' and args['dff'] is not None:
         ap.error('--overlap demix gives float64 coefficients, --dff takes integer sums: not together')
+    if args['which'] == 'traces' and args['deconvolve'] is not None and args['dff'] is None:
+        ap.error('--deconvolve needs --dff: the deconvolution has no baseline term')
+    if args['which'] == 'traces' and args['deconvolve'] is not None and args['fps'] is None:
+        ap.error('--deconvolve needs --fps')
     if args['which'] == 'traces' and args['overlap'] != 'keep' and args['weighted'] is None:
         ap.error('--overlap needs --weighted')
     f = {'train': training, 'evaluate': evaluation, 'predict': prediction, 'traces': traces}[args.pop('which')]

@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 125
+#define DC_ABI_VERSION 126
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -829,6 +829,50 @@ int dc_trace_combine(const long* sums, long ld, const int* np_row, const long* c
                      long* num, dc_stream_t stream);
 int dc_trace_baseline(const long* num, long ld, int R, long T, int half, int q, long* base, float* dff, dc_stream_t stream);
 int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float* out, dc_stream_t stream);
+
+/* ---- Spikes by deconvolution: non-negative AR(1) deconvolution of a trace, without a trained model ---------------------------
+ * The last stage of the chain for a user who has no UNet1D model file: calcium c[t] = g c[t-1] + s[t] with s >= 0 is fitted to
+ * every trace by the pool-merging (OASIS-style) forward pass below.  The reference has no counterpart; THESE DEFINITIONS ARE THE
+ * SPECIFICATION.  A trace is sequential, but it consists only of IEEE double adds, multiplies, one division per merge and
+ * comparisons: with the operation order fixed (csrc/deconv_math.h, no fused multiply-add, no reassociation) and the powers of g
+ * taken from one table, the result is defined bit for bit, on the device and on the host.
+ * Inputs
+ *   y[r][t]  float32 or float64 rows of stride ld >= T (is_f64 = 0 / 1); float32 is widened to double exactly.  THE CALLER
+ *            PROMISES FINITE VALUES (not checked on the device; the Python layer checks host arrays).  Feed dF/F: there is no
+ *            baseline term.
+ *   G[0..T]  double, T + 1 entries: G[0] = 1, G[l] = G[l-1] * g, built ONCE ON THE HOST by that loop of multiplications, never by
+ *            pow().  g = G[1], 0 < g < 1.
+ *   lam[r] >= 0, smin[r] >= 0: doubles per trace, the L1 penalty on the spikes and the smallest spike allowed.
+ * Forward pass, per trace: a stack of pools (v, w, t0, l).  For t = 0 .. T - 1:
+ *   push (y[t] - mu, 1.0, t, 1), mu = lam * (1.0 - g) for t < T - 1 and mu = lam for t = T - 1;
+ *   with p the pool below the top pool q: while the stack holds at least two pools and v_q < G[l_p] * v_p + smin, merge
+ *     a = G[l_p];  num = w_p * v_p + (a * w_q) * v_q;  den = w_p + (a * a) * w_q;  v_p = num / den;  w_p = den;  l_p += l_q;  pop q.
+ *   The parentheses are the evaluation order.
+ * Outputs, float64 and dense, every element written (the caller need not clear them):
+ *   calcium[r][t0_i + k] = b_i * G[k] for 0 <= k < l_i, b_i = v_i where v_i > 0.0 and +0.0 otherwise;
+ *   spikes[r][t0_i] = calcium[t0_i] - g * calcium[t0_i - 1] for every pool i >= 1, exactly +0.0 at every other frame, frame 0
+ *     included.  Not clamped: with smin = 0 it can be below zero by rounding only.  An event is spikes > 0.
+ *   pools[r]: int32, the final number of pools.
+ * Not built: AR(2); estimating g from the autocovariance; the noise-constrained search for lam; a baseline term; a wave-parallel
+ * segment merge (it would change the operation order and so the bits); integer-exact arithmetic (the pool values are not closed
+ * under any fixed-point format).
+ *   dc_trace_deconv_ws_bytes: the workspace of dc_trace_deconv_ar1, 24 * R * T bytes (0 for an empty or unsupported shape).
+ *   dc_trace_deconv_ar1: forward pass (one lane per trace, 64 traces per workgroup), then the fill (one thread per sample).  All
+ *     pointers are DEVICE memory.  g is passed by value and must equal G[1].  ws holds the pools below the top one as [depth][R]
+ *     planes (v, w, (t0, l)); its contents afterwards are the final stacks.  lam and smin are not read on the host: THE CALLER
+ *     PROMISES lam, smin >= 0.  T > 2^24 or R * T > 2^31: DC_EUNSUP (-3).  g outside (0, 1), a null pointer, a negative count,
+ *     ld < T or a misaligned buffer (8 bytes; 4 for float32 y and for pools): -1.  R == 0 or T == 0: 0, nothing launched.
+ *   dc_trace_deconv_ar1_host: the same arithmetic (the same header) compiled for the host, over HOST pointers, one trace after the
+ *     other on the calling thread; it allocates T pools of host memory for the duration of the call.  g = G[1]; G[0] != 1, a
+ *     negative or NaN lam[r] or smin[r]: -1; otherwise the codes above.  The speed baseline, and the bit-for-bit check of the
+ *     library against the oracle on a machine without a GPU. */
+#define DC_TRACE_DECONV_MAX_FRAMES 16777216L
+#define DC_TRACE_DECONV_MAX_SAMPLES 2147483648L
+long dc_trace_deconv_ws_bytes(int R, long T);
+int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, long T, double g, const double* G, const double* lam,
+                        const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream);
+int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int R, long T, const double* G, const double* lam, const double* smin,
+                             double* calcium, double* spikes, int* pools);
 
 /* ---- rigid motion correction: register the frames of a recording to a template ------------------------------------------------
  * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
