@@ -11,12 +11,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libdcunet.so')
-SOURCES = ['common.cpp', 'comm.cpp', 'nf_score.cpp', 'tape.cpp', 'igemm_conv.hip', 'igemm_f16x3.hip', 'igemm_pp.hip', 'wgrad.hip', 'wgrad_f16x3.hip', 'bwd_joint.hip', 'conv_c1.hip', 'elementwise.hip', 'series.hip', 'traces.hip', 'footprints.hip', 'roi_pairs.hip', 'trace_pairs.hip', 'frame_quality.hip', 'dff.hip', 'deconv.hip', 'spikes.hip', 'spikes_train.hip', 'motion.hip']
+SOURCES = ['common.cpp', 'comm.cpp', 'nf_score.cpp', 'tape.cpp', 'igemm_conv.hip', 'igemm_f16x3.hip', 'igemm_pp.hip', 'wgrad.hip', 'wgrad_f16x3.hip', 'bwd_joint.hip', 'conv_c1.hip', 'elementwise.hip', 'series.hip', 'traces.hip', 'footprints.hip', 'roi_pairs.hip', 'trace_pairs.hip', 'frame_quality.hip', 'dff.hip', 'deconv.hip', 'trace_dyn.hip', 'spikes.hip', 'spikes_train.hip', 'motion.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
-# per-file flags.  Arithmetic that must round like numpy's: no fused multiply-add (nf_score.cpp: host code only; series.hip, traces.hip, footprints.hip, roi_pairs.hip, trace_pairs.hip, frame_quality.hip, dff.hip, deconv.hip: their kernels too)
+# per-file flags.  Arithmetic that must round like numpy's: no fused multiply-add (nf_score.cpp: host code only; series.hip, traces.hip, footprints.hip, roi_pairs.hip, trace_pairs.hip, frame_quality.hip, dff.hip, deconv.hip, trace_dyn.hip: their kernels too)
 FILE_FLAGS = {'nf_score.cpp': ['-ffp-contract=off'], 'series.hip': ['-ffp-contract=off'], 'traces.hip': ['-ffp-contract=off'],
               'footprints.hip': ['-ffp-contract=off'], 'roi_pairs.hip': ['-ffp-contract=off'], 'trace_pairs.hip': ['-ffp-contract=off'],
-              'frame_quality.hip': ['-ffp-contract=off'], 'dff.hip': ['-ffp-contract=off'], 'deconv.hip': ['-ffp-contract=off']}
+              'frame_quality.hip': ['-ffp-contract=off'], 'dff.hip': ['-ffp-contract=off'], 'deconv.hip': ['-ffp-contract=off'],
+              'trace_dyn.hip': ['-ffp-contract=off']}
 
 
 def _hipcc():

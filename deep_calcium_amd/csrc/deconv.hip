@@ -45,10 +45,13 @@ struct DeviceStack {
 };
 
 // One workgroup of one wave per 64 traces.  Rows r >= R and frames t >= T of a ragged tile are neither read nor written.
-template <typename In>
-__global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g,
-                                                               const double* __restrict__ G, const double* __restrict__ lam,
-                                                               const double* __restrict__ smin, double* ws, int* __restrict__ pools) {
+// Each = false: one decay g and one table G for all traces (dc_trace_deconv_ar1).  Each = true: trace r has the decay gs[r] and
+// the table row G + r * ldG (dc_trace_deconv_ar1_each); the arithmetic of a trace is the same, only where its g and G come from.
+template <typename In, bool Each>
+__global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g_all,
+                                                               const double* __restrict__ gs, const double* __restrict__ G_all, long ldG,
+                                                               const double* __restrict__ lam, const double* __restrict__ smin, double* ws,
+                                                               int* __restrict__ pools) {
   __shared__ In tile[kLanes * kPitch];
   const int lane = threadIdx.x;
   const long r0 = (long)blockIdx.x * kLanes;
@@ -58,6 +61,8 @@ __global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __rest
   const long plane = (long)R * T;
   DeviceStack st = {ws, ws + plane, reinterpret_cast<int2*>(ws + 2 * plane), (long)R, r};
   const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
+  const double g = Each ? (mine ? gs[r] : 0.5) : g_all;
+  const double* __restrict__ G = Each && mine ? G_all + r * ldG : G_all;
   DcPool top = dc_deconv_new(0.0, 0);
   int32_t n = 0;
   for (long f0 = 0; f0 < T; f0 += kFrames) {
@@ -84,14 +89,17 @@ __global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __rest
 
 // One thread per sample (r, t): the pool that holds frame t is the last whose start is <= t (the starts ascend), found by
 // bisection over the trace's n pools.  Every output element is written, each by one product or one multiply-subtract.
+template <bool Each>
 __global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double* __restrict__ ws, const int* __restrict__ pools, int R, long T,
-                                                                  double g, const double* __restrict__ G, double* __restrict__ calcium,
-                                                                  double* __restrict__ spikes) {
+                                                                  double g_all, const double* __restrict__ gs, const double* __restrict__ G_all,
+                                                                  long ldG, double* __restrict__ calcium, double* __restrict__ spikes) {
   const long plane = (long)R * T;
   const long idx = (long)blockIdx.x * kFillThreads + threadIdx.x;
   if (idx >= plane) return;
   const long r = idx / T;
   const int32_t t = (int32_t)(idx - r * T);
+  const double g = Each ? gs[r] : g_all;
+  const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
   const double* v = ws;
   const int2* tl = reinterpret_cast<const int2*>(ws + 2 * plane);
   int32_t lo = 0, hi = pools[r] - 1;                                 // pool lo starts at or before t, pool hi + 1 (if any) after it
@@ -153,6 +161,25 @@ int check_limits(const char* who, int R, long T, double g) {
   return DC_OK;
 }
 
+// the forward pass, then the fill; the arguments have been checked
+template <bool Each>
+int launch_deconv(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
+                  const double* lam, const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream) {
+  const unsigned groups = (unsigned)(((long)R + kLanes - 1) / kLanes);                      // <= 2^25: no cap
+  if (is_f64)
+    hipLaunchKernelGGL((deconv_forward_kernel<double, Each>), dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const double*)y, ld, R, T, g,
+                       gs, G, ldG, lam, smin, (double*)ws, pools);
+  else
+    hipLaunchKernelGGL((deconv_forward_kernel<float, Each>), dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const float*)y, ld, R, T, g, gs,
+                       G, ldG, lam, smin, (double*)ws, pools);
+  DC_CHECK_LAUNCH(who);
+  const unsigned blocks = (unsigned)(((long)R * T + kFillThreads - 1) / kFillThreads);      // <= 2^23: no cap
+  hipLaunchKernelGGL(deconv_fill_kernel<Each>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)stream, (const double*)ws, pools, R, T, g, gs, G,
+                     ldG, calcium, spikes);
+  DC_CHECK_LAUNCH(who);
+  return DC_OK;
+}
+
 }  // namespace
 
 extern "C" long dc_trace_deconv_ws_bytes(int R, long T) {
@@ -172,19 +199,24 @@ extern "C" int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, lo
                  (((uintptr_t)pools) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
              DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  const unsigned groups = (unsigned)(((long)R + kLanes - 1) / kLanes);                      // <= 2^25: no cap
-  if (is_f64)
-    hipLaunchKernelGGL(deconv_forward_kernel<double>, dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const double*)y, ld, R, T, g, G, lam,
-                       smin, (double*)ws, pools);
-  else
-    hipLaunchKernelGGL(deconv_forward_kernel<float>, dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const float*)y, ld, R, T, g, G, lam,
-                       smin, (double*)ws, pools);
-  DC_CHECK_LAUNCH(who);
-  const unsigned blocks = (unsigned)(((long)R * T + kFillThreads - 1) / kFillThreads);      // <= 2^23: no cap
-  hipLaunchKernelGGL(deconv_fill_kernel, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)stream, (const double*)ws, pools, R, T, g, G, calcium,
-                     spikes);
-  DC_CHECK_LAUNCH(who);
-  return DC_OK;
+  return launch_deconv<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, lam, smin, ws, calcium, spikes, pools, stream);
+}
+
+extern "C" int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int R, long T, const double* g, const double* G, long ldG,
+                                        const double* lam, const double* smin, void* ws, double* calcium, double* spikes, int* pools,
+                                        dc_stream_t stream) {
+  const char* who = "dc_trace_deconv_ar1_each";
+  DC_REQUIRE(g && G && lam && smin && ws && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
+  int rc = check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
+  rc = check_limits(who, R, T, 0.5);                                 // the decays lie in device memory: THE CALLER PROMISES 0 < g[r] < 1
+  if (rc != DC_OK) return rc;
+  DC_REQUIRE((((uintptr_t)g | (uintptr_t)G | (uintptr_t)lam | (uintptr_t)smin | (uintptr_t)ws | (uintptr_t)calcium | (uintptr_t)spikes) & 7) == 0 &&
+                 (((uintptr_t)pools) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+             DC_EINVAL, "%s: misaligned buffer", who);
+  if (R == 0 || T == 0) return DC_OK;
+  return launch_deconv<true>(who, y, is_f64, ld, R, T, 0.0, g, G, ldG, lam, smin, ws, calcium, spikes, pools, stream);
 }
 
 extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int R, long T, const double* G, const double* lam,

@@ -16,7 +16,10 @@ so the results are defined bit for bit.
 
     c, s = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau=1.0, fps=30.0, k=3.0)    # dff_traces_device, then the above
 
-Not built: AR(2), estimating g from the autocovariance, the noise-constrained search for lam, a baseline term (feed dF/F, whose
+    c, s, info = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau='auto', details=True)     # g estimated from the traces
+    dec = TraceDeconvolver(dff_dev, g_each, s_min=3.0 * sigma)          # one decay per trace (deep_calcium_amd.dynamics.pick_gamma)
+
+Not built: AR(2), optimising g by the residual, the noise-constrained search for lam, a baseline term (feed dF/F, whose
 baseline is 0).
 
 Importing this module needs neither torch nor the GPU; constructing a TraceDeconvolver does (there is no CPU fallback).
@@ -95,6 +98,20 @@ def _per_trace(x, what, R):
     return np.ascontiguousarray(a)
 
 
+def _per_trace_gamma(g, R):
+    """One decay per trace, each inside (0, 1) -> float64[R]."""
+    try:
+        a = np.asarray(g, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('g must be a number or %d numbers in (0, 1), not %r' % (R, g))
+    if a.shape != (R,):
+        raise ValueError('g must be a scalar or one value per trace (%d), not shape %r' % (R, a.shape))
+    bad = np.flatnonzero(~((a > 0.0) & (a < 1.0)))                 # NaN fails both comparisons
+    if bad.size:
+        raise ValueError('g must be inside (0, 1): trace %d has %r' % (int(bad[0]), float(a[bad[0]])))
+    return np.ascontiguousarray(a)
+
+
 def _is_device_tensor(x):
     return not isinstance(x, np.ndarray) and hasattr(x, 'is_cuda') and hasattr(x, 'data_ptr')
 
@@ -133,13 +150,19 @@ class TraceDeconvolver(object):
 
     def __init__(self, traces, g, s_min=0.0, lam=0.0, device=None):
         """traces: (R, T) float32 or float64, numpy (checked for non-finite values) or a tensor already on the device (read in
-        place, never written; THE CALLER PROMISES FINITE VALUES).  g in (0, 1).  s_min, lam: a scalar or one value per trace, >= 0."""
+        place, never written; THE CALLER PROMISES FINITE VALUES).  g in (0, 1): a scalar -- one decay and one table for all traces
+        -- or an array of one value per trace (e.g. pick_gamma's g_each): the tables are then built on the device, one row per
+        trace, and trace r gets the bits a scalar g[r] would give it.  s_min, lam: a scalar or one value per trace, >= 0."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         R, T, f64 = _check_traces(traces)
-        self.g = _check_gamma(g)
+        self._each = np.ndim(g) != 0
+        if self._each:
+            self.g = _per_trace_gamma(g, R)
+        else:
+            self.g = _check_gamma(g)
         smin = _per_trace(s_min, 's_min', R)
         lam = _per_trace(lam, 'lam', R)
-        table = ar1_table(self.g, T)
+        table = None if self._each else ar1_table(self.g, T)
         self.n_traces, self.n_frames = R, T
 
         import torch
@@ -166,7 +189,7 @@ class TraceDeconvolver(object):
             y = torch.from_numpy(np.ascontiguousarray(traces)).to(dev)
         self._y, self._f64 = y, f64
         self._ld = int(y.stride(0)) if R > 1 else max(int(y.stride(0)), T)
-        self._G = torch.from_numpy(table).to(dev)
+        self._G = torch.from_numpy(self.g if self._each else table).to(dev)       # per trace: the decays; the tables come in _run()
         self._smin = torch.from_numpy(smin).to(dev)
         self._lam = torch.from_numpy(lam).to(dev)
         self._out = None
@@ -179,6 +202,15 @@ class TraceDeconvolver(object):
                 c = torch.empty((R, T), dtype=torch.float64, device=self.device)
                 s = torch.empty((R, T), dtype=torch.float64, device=self.device)
                 n = torch.empty(R, dtype=torch.int32, device=self.device)
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                if self._each:
+                    tables = torch.empty((R, T + 1), dtype=torch.float64, device=self.device)
+                    self.L.dc_ar1_tables(self._G.data_ptr(), R, T, tables.data_ptr(), T + 1, stream)
+                    self.L.dc_trace_deconv_ar1_each(self._y.data_ptr(), int(self._f64), self._ld, R, T, self._G.data_ptr(), tables.data_ptr(), T + 1,
+                                                    self._lam.data_ptr(), self._smin.data_ptr(), ws.data_ptr(), c.data_ptr(), s.data_ptr(),
+                                                    n.data_ptr(), stream)
+                    self._out = dict(calcium=c, spikes=s, pools=n)    # the tables go back to the allocator with the workspace
+                    return self._out
                 self.L.dc_trace_deconv_ar1(self._y.data_ptr(), int(self._f64), self._ld, R, T, self.g, self._G.data_ptr(), self._lam.data_ptr(),
                                            self._smin.data_ptr(), ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(),
                                            torch.cuda.current_stream(self.device).cuda_stream)
@@ -195,10 +227,25 @@ class TraceDeconvolver(object):
         return self.result_device(kind).cpu().numpy()
 
 
-def deconvolve_traces_device(dspath, rois, window, tau, fps, k=3.0, lam=0.0, **dff_kw):
+def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0, details=False, lags=5, g_min=0.05, g_max=0.998, **dff_kw):
     """-> (calcium, spikes), float64 (R, T): the dF/F traces of `rois` over a dataset file (dff_traces_device(dspath, rois, window,
-    **dff_kw)) deconvolved with g = ar1_gamma(tau, fps), s_min = k * trace_noise(dff) per trace and the penalty lam."""
-    g = ar1_gamma(tau, fps)
+    **dff_kw)) deconvolved with s_min = k * sigma_hat per trace and the penalty lam.  tau: a number -- the decay time in seconds,
+    g = ar1_gamma(tau, fps) --, 'auto' -- the decay is estimated per trace from the dF/F (deep_calcium_amd.dynamics: TraceDynamics
+    with `lags`, then pick_gamma with g_min, g_max) and the pooled median serves all traces --, or 'each' -- every trace is
+    deconvolved with its own estimate.  fps is needed for a number only.  details=True -> (calcium, spikes, info), info =
+    dict(g=the decay used, a float or float64[R] for 'each'; g_raw=, status=, pooled= what pick_gamma gave, None for a number;
+    sigma=sigma_hat float64[R])."""
+    mode = tau if isinstance(tau, str) else None
+    if mode is not None and mode not in ('auto', 'each'):
+        raise ValueError("tau must be a number of seconds, 'auto' or 'each', not %r" % (tau,))
+    if mode is None:
+        g = ar1_gamma(tau, fps)
+    else:
+        from .dynamics import _check_lags, pick_gamma
+        _check_lags(lags)
+        pick_gamma(np.array([0.5]), g_min, g_max)                    # the bounds, before anything is opened
+        if fps is not None:
+            ar1_gamma(1.0, fps)
     try:
         k = float(k)
     except (TypeError, ValueError):
@@ -212,5 +259,18 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps, k=3.0, lam=0.0, **d
         raise ValueError('the deconvolution takes dF/F: kind = %r is not supported' % (dff_kw['kind'],))
     from .dff import dff_traces_device
     dff = dff_traces_device(dspath, rois, window, **dff_kw)
-    dec = TraceDeconvolver(dff, g, s_min=k * trace_noise(dff), lam=lam, device=dff_kw.get('device'))
+    if mode is None:
+        sigma = trace_noise(dff)
+        dec = TraceDeconvolver(dff, g, s_min=k * sigma, lam=lam, device=dff_kw.get('device'))
+        info = dict(g=g, g_raw=None, status=None, sigma=sigma, pooled=None)
+    else:
+        from .dynamics import TraceDynamics
+        dyn = TraceDynamics(dff, lags=lags, device=dff_kw.get('device'))
+        sigma, g_raw = dyn.result('noise'), dyn.result('g_raw')
+        g_each, status, g_pool = pick_gamma(g_raw, g_min, g_max)
+        g = g_pool if mode == 'auto' else g_each
+        dec = TraceDeconvolver(dyn.traces_device, g, s_min=k * sigma, lam=lam, device=dyn.device)
+        info = dict(g=g, g_raw=g_raw, status=status, sigma=sigma, pooled=g_pool)
+    if details:
+        return dec.result('calcium'), dec.result('spikes'), info
     return dec.result('calcium'), dec.result('spikes')

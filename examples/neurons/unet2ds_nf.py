@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve TAU --fps F [--spike-k K]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve auto|each|TAU [--fps F] [--spike-k K]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -34,7 +34,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, write_traces_dataset,      # noqa: E402
                               estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
                               split_rois_device, detrend_plan, merge_rois_device, make_template, frame_quality_device, flag_frames,
-                              footprint_weights, exclude_overlap, weighted_traces_device, TraceDeconvolver, ar1_gamma, trace_noise)
+                              footprint_weights, exclude_overlap, weighted_traces_device, TraceDeconvolver, ar1_gamma, trace_noise,
+                              TraceDynamics, pick_gamma, ar1_tau)
 from deep_calcium_amd.weighted import shared_pixels            # noqa: E402
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
@@ -123,6 +124,16 @@ def _neuropil_arg(text):
         raise argparse.ArgumentTypeError('expected INNER,OUTER,WEIGHT such as 2,12,0.7, not %r' % text)
 
 
+def _deconvolve_arg(text):
+    """'auto' | 'each' | a decay time in seconds."""
+    if text in ('auto', 'each'):
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected auto, each or the decay time TAU in seconds, not %r' % text)
+
+
 def _n_frames(dspath):
     from deep_calcium_amd.series import _open_series
     frames, close = _open_series(dspath, 'series/raw')
@@ -184,7 +195,9 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     deconvolve=TAU (with dff and fps=F): spikes without a trained model -- the dF/F traces are deconvolved on the GPU with the AR(1)
     decay g = exp(-1 / (TAU F)) (TAU: the indicator's decay time in seconds, F: frames a second) and the smallest spike
     spike_k * sigma_hat of every trace (deep_calcium_amd.TraceDeconvolver, trace_noise); the file gets the float64 datasets
-    `calcium` and `deconvolved` (the spikes; an event is a value > 0) beside `traces`."""
+    `calcium` and `deconvolved` (the spikes; an event is a value > 0) beside `traces`.  deconvolve='auto' or 'each' (fps optional):
+    the decay is estimated from the dF/F itself, per trace, from its autocovariance (deep_calcium_amd.TraceDynamics, pick_gamma);
+    'auto' deconvolves every trace with the pooled median, 'each' with the trace's own estimate."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -200,11 +213,16 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--neuropil needs --dff')
     if deconvolve is not None and dff is None:
         raise ValueError('--deconvolve needs --dff: the deconvolution has no baseline term')
-    if deconvolve is not None and fps is None:
+    estimated = isinstance(deconvolve, str)
+    if estimated and deconvolve not in ('auto', 'each'):
+        raise ValueError('--deconvolve takes auto, each or the decay time TAU in seconds, not %r' % (deconvolve,))
+    if deconvolve is not None and not estimated and fps is None:
         raise ValueError('--deconvolve needs --fps: the decay per frame is exp(-1 / (TAU * fps))')
     if deconvolve is not None and not spike_k >= 0:
         raise ValueError('--spike-k is the smallest spike in units of the trace noise, K >= 0, not %r' % (spike_k,))
-    g = None if deconvolve is None else ar1_gamma(deconvolve, fps)
+    g = None if deconvolve is None or estimated else ar1_gamma(deconvolve, fps)
+    if estimated and fps is not None:
+        ar1_gamma(1.0, fps)
     if bin_frames is not None and refine is None and split is None:
         raise ValueError('--bin-frames needs --refine or --split: it bins the frames those passes correlate')
     if bin_frames is not None and not 1 <= bin_frames <= 64:
@@ -351,7 +369,22 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         else:
             tr = extract_traces_device(dspath, mask, kind=kind, **moves(dspath))
         extra = None
-        if g is not None:
+        if estimated:
+            dyn = TraceDynamics(tr)
+            sigma = dyn.result('noise')
+            g_each, status, g_pool = pick_gamma(dyn.result('g_raw'))
+            dec = TraceDeconvolver(dyn.traces_device, g_pool if deconvolve == 'auto' else g_each, s_min=spike_k * sigma)
+            extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
+            events = (extra['deconvolved'] > 0).sum(1)
+            logger.info('%s: decay estimated from the traces (--deconvolve %s): pooled g = %.6f%s, per trace min / median / max = %.6f / %.6f / '
+                        '%.6f%s; status fine / raised / lowered / replaced = %d / %d / %d / %d; s_min = %g sigma_hat, median sigma_hat %.4g: '
+                        'events per ROI min / median / max = %d / %g / %d' % (
+                            name, deconvolve, g_pool, '' if fps is None else ' (tau %.4g s at %g frames/s)' % (ar1_tau(g_pool, fps), fps),
+                            float(g_each.min()), float(np.median(g_each)), float(g_each.max()),
+                            '' if fps is None else ' (tau %.4g / %.4g / %.4g s)' % tuple(ar1_tau(float(v), fps) for v in (g_each.min(), np.median(g_each), g_each.max())),
+                            int((status == 0).sum()), int((status == 1).sum()), int((status == 2).sum()), int((status == 3).sum()),
+                            spike_k, float(np.median(sigma)), int(events.min()), float(np.median(events)), int(events.max())))
+        elif g is not None:
             sigma = trace_noise(tr)
             dec = TraceDeconvolver(tr, g, s_min=spike_k * sigma)
             extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
@@ -406,9 +439,10 @@ if __name__ == '__main__':
     sp_trc.add_argument('--percentile', help='with --dff: the integer percentile of the baseline (default 8)', default=8, type=int, metavar='Q')
     sp_trc.add_argument('--neuropil', help='with --dff: subtract WEIGHT times the trace of the ring INNER < distance <= OUTER (e.g. 2,12,0.7)',
                         default=None, type=_neuropil_arg, metavar='INNER,OUTER,WEIGHT')
-    sp_trc.add_argument('--deconvolve', help='with --dff and --fps: deconvolve the dF/F traces (non-negative AR(1), no trained model) with the '
-                        'indicator decay time TAU in seconds; writes `calcium` and `deconvolved` beside `traces`', default=None, type=float,
-                        metavar='TAU')
+    sp_trc.add_argument('--deconvolve', help='with --dff: deconvolve the dF/F traces (non-negative AR(1), no trained model); TAU: the indicator '
+                        'decay time in seconds (needs --fps); auto: the decay is estimated from the traces, the pooled median serves all; each: '
+                        'every trace gets its own estimate; writes `calcium` and `deconvolved` beside `traces`', default=None, type=_deconvolve_arg,
+                        metavar='auto|each|TAU')
     sp_trc.add_argument('--fps', help='with --deconvolve: the frame rate of the recording in frames per second', default=None, type=float, metavar='F')
     sp_trc.add_argument('--spike-k', help='with --deconvolve: the smallest spike allowed, in units of every trace\'s noise (default 3)', default=3.0,
                         type=float, metavar='K', dest='spike_k')
@@ -443,7 +477,7 @@ if __name__ == '__main__':
         ap.error('--overlap demix gives float64 coefficients, --dff takes integer sums: not together')
     if args['which'] == 'traces' and args['deconvolve'] is not None and args['dff'] is None:
         ap.error('--deconvolve needs --dff: the deconvolution has no baseline term')
-    if args['which'] == 'traces' and args['deconvolve'] is not None and args['fps'] is None:
+    if args['which'] == 'traces' and args['deconvolve'] is not None and not isinstance(args['deconvolve'], str) and args['fps'] is None:
         ap.error('--deconvolve needs --fps')
     if args['which'] == 'traces' and args['overlap'] != 'keep' and args['weighted'] is None:
         ap.error('--overlap needs --weighted')

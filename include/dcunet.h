@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 126
+#define DC_ABI_VERSION 127
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -853,7 +853,7 @@ int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float
  *   spikes[r][t0_i] = calcium[t0_i] - g * calcium[t0_i - 1] for every pool i >= 1, exactly +0.0 at every other frame, frame 0
  *     included.  Not clamped: with smin = 0 it can be below zero by rounding only.  An event is spikes > 0.
  *   pools[r]: int32, the final number of pools.
- * Not built: AR(2); estimating g from the autocovariance; the noise-constrained search for lam; a baseline term; a wave-parallel
+ * Not built: AR(2); optimising g by the residual; the noise-constrained search for lam; a baseline term; a wave-parallel
  * segment merge (it would change the operation order and so the bits); integer-exact arithmetic (the pool values are not closed
  * under any fixed-point format).
  *   dc_trace_deconv_ws_bytes: the workspace of dc_trace_deconv_ar1, 24 * R * T bytes (0 for an empty or unsupported shape).
@@ -873,6 +873,57 @@ int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, long T, doubl
                         const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream);
 int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int R, long T, const double* G, const double* lam, const double* smin,
                              double* calcium, double* spikes, int* pools);
+
+/* ---- Trace dynamics: noise and AR(1) decay -----------------------------------------------------------------------------------
+ * The one parameter of the deconvolution above that had no data-driven default: the decay g, which depends on indicator,
+ * expression level, temperature and cell type.  Per trace, from the whole trace: the robust noise sigma of its first difference
+ * (what sets smin), its autocovariance xc at lags 0 .. lags, and CaImAn's least-squares AR(1) coefficient with the noise removed
+ * at lag 0 only.  The reference has no counterpart; THESE DEFINITIONS ARE THE SPECIFICATION (csrc/trace_dyn_math.h is their one
+ * implementation: IEEE doubles, no fused multiply-add, no reassociation).  y, ld, is_f64 as above; float32 is widened exactly.
+ *   noise, by VALUE (order-free): d[t] = y[t+1] - y[t], t in [0, T-1).  med(x) of n values: the (n-1)/2-th smallest for odd n,
+ *     (x_(n/2-1) + x_(n/2)) / 2.0 for even n.  m = med(d), mad = med(|d - m|), sigma = (1.4826 * mad) / sqrt(2.0); sigma = 0.0 for
+ *     T < 3.  Bit-equal to numpy's 1.4826 * median(|d - median(d)|) / sqrt(2) (deep_calcium_amd.deconv.trace_noise).
+ *   fold(f, n), FIXED ORDER, W = DC_TRACE_DYN_LANES = 256: (1) for j in [0, W): P[j] = +0.0, then for t = j, j + W, ... < n
+ *     ascending P[j] = P[j] + f(t); (2) for h = 128, 64, ..., 1 and every j < h: P[j] = P[j] + P[j+h]; (3) the result is P[0].
+ *     n <= 0 gives +0.0.
+ *   autocovariance: mean = fold(y, T) / (double)T; for l = 0 .. lags: q_l = fold(t -> (y[t] - mean) * (y[t+l] - mean), T - l),
+ *     xc_l = q_l / (double)T.  lags in [1, DC_TRACE_DYN_MAX_LAGS].
+ *   decay: A_0 = xc_0 - sn * sn, A_i = xc_i for 1 <= i < lags, b_i = xc_(i+1); num = the left fold from +0.0 of A_i * b_i over
+ *     ascending i, den the same of A_i * A_i; g_raw = num / den.  g_raw = NaN (undefined) when T < lags + 2, when den == 0.0 or
+ *     when the quotient is not finite.  sn is the sigma above unless the caller passes its own.  Adding a constant to the trace
+ *     does not change the estimate.  g_raw is NOT clamped to (0, 1): that is the caller's (deep_calcium_amd.pick_gamma).
+ * All pointers are DEVICE memory (except for the _host entry), there are no out-parameters and nothing is read on the host.
+ * Columns >= T of a padded row are never read.  Every output word is written by one thread; no floating-point atomics.
+ *   dc_trace_noise: sigma = double[R].  One 256-thread workgroup per trace (at most DC_TRACE_DYN_MAX_GROUPS workgroups: beyond,
+ *     a workgroup walks several traces); the medians by a radix descent over a monotone 64-bit key of the double, no workspace.
+ *   dc_trace_ar1_estimate: xc = double (R, lags + 1) dense, g_raw = double[R].  sn = double[R] or NULL: the noise that enters
+ *     A_0.  sigma = double[R] or NULL: where given, the noise above is computed and written; with sn == NULL it is also what
+ *     enters A_0, and sigma must then be given.  One launch, one workgroup per trace, capped as above.
+ *   dc_ar1_tables: G[r][0] = 1.0, G[r][l] = G[r][l-1] * g[r] for l = 1 .. T; g = double[R], rows of stride ldG >= T + 1 (entries
+ *     beyond T are not written).  Row r is bit-equal to the host's table of g[r].  T == 0 writes the one entry per row.
+ *   dc_trace_deconv_ar1_each: dc_trace_deconv_ar1 with a decay and a table row per trace: g = double[R] in DEVICE memory, G the
+ *     rows dc_ar1_tables writes.  Trace r gives the bits of dc_trace_deconv_ar1 run on that trace alone with g[r].  The same
+ *     workspace (dc_trace_deconv_ws_bytes).  THE CALLER PROMISES 0 < g[r] < 1 and G[r][1] == g[r] (not checked: nothing is read
+ *     on the host).  ldG < T + 1: -1; otherwise the codes of dc_trace_deconv_ar1.
+ *   dc_trace_ar1_estimate_host: dc_trace_ar1_estimate compiled for the host (the same header), over HOST pointers, one trace
+ *     after the other on the calling thread, the medians by std::nth_element; it allocates T - 1 doubles for the duration of the
+ *     call.  The speed baseline, and the bit-for-bit check of the library against the oracle on a machine without a GPU.
+ * Limits as for the deconvolution: T > 2^24 or R * T > 2^31: DC_EUNSUP (-3).  A null or misaligned pointer (8 bytes; 4 for
+ * float32 y), ld < T, a negative count, lags outside [1, 16]: -1.  R == 0 or T == 0: 0, nothing launched (dc_ar1_tables: R == 0).
+ * Not built: AR(2); refining g by the deconvolution residual; noise from the power spectrum; per-segment estimates; weights on
+ * the lags. */
+#define DC_TRACE_DYN_LANES 256
+#define DC_TRACE_DYN_MAX_LAGS 16
+#define DC_TRACE_DYN_MAX_GROUPS 8192
+int dc_trace_noise(const void* y, int is_f64, long ld, int R, long T, double* sigma, dc_stream_t stream);
+int dc_trace_ar1_estimate(const void* y, int is_f64, long ld, int R, long T, int lags, const double* sn, double* sigma, double* xc,
+                          double* g_raw, dc_stream_t stream);
+int dc_ar1_tables(const double* g, int R, long T, double* G, long ldG, dc_stream_t stream);
+int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int R, long T, const double* g, const double* G, long ldG,
+                             const double* lam, const double* smin, void* ws, double* calcium, double* spikes, int* pools,
+                             dc_stream_t stream);
+int dc_trace_ar1_estimate_host(const void* y, int is_f64, long ld, int R, long T, int lags, const double* sn, double* sigma, double* xc,
+                               double* g_raw);
 
 /* ---- rigid motion correction: register the frames of a recording to a template ------------------------------------------------
  * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
