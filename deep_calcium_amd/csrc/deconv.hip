@@ -5,13 +5,16 @@
 // layout is the work: the traces are row-major, so a wave's lanes would read at stride ld; a tile of 64 traces x 64 frames is
 // staged through LDS with coalesced row reads instead and every lane then walks its own row of the tile.  The top pool stays in
 // registers; the pools below it lie in the caller's workspace as [depth][R] planes, so the lanes of a wave that stand at the
-// same depth touch one line.  Nothing here may be contracted or reassociated: the pragma of deconv_math.h and the per-file flag
-// in _build.py.
+// same depth touch one line.  The noise-constrained search (csrc/deconv_search_math.h) runs that forward pass once a round, with
+// the searched parameter in the device array the pass reads anyway, and between two passes one launch that folds the residual of
+// the stacks and moves every trace's bracket: nothing is read back.  Nothing here may be contracted or reassociated: the pragma of
+// deconv_math.h and the per-file flag in _build.py.
 #pragma clang fp contract(off)
 #include <vector>
 
 #include "common.h"
 #include "deconv_math.h"
+#include "deconv_search_math.h"
 
 namespace {
 
@@ -19,6 +22,8 @@ const int kLanes = 64;                       // traces per workgroup: one wave, 
 const int kFrames = 64;                      // frames per staged tile
 const int kPitch = kFrames + 1;              // elements per tile row: lane l reads word l * 65 + k, one bank each (float), two (double)
 const int kFillThreads = 256;
+const int kSearchThreads = DC_DYN_LANES;     // the residual: one thread per lane of the fold
+const int kSearchMaxGroups = 8192;           // DC_TRACE_DECONV_SEARCH_MAX_GROUPS: beyond, a workgroup walks several traces
 
 // The workspace: three planes of R * T 8-byte words, pool i of trace r at word i * R + r of each.
 struct DeviceStack {
@@ -120,6 +125,100 @@ __global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double*
   spikes[idx] = s;
 }
 
+// ---- the noise-constrained search (csrc/deconv_search_math.h) ---------------------------------------------------------------------
+// The state of the searches: five planes of R 8-byte words -- lo, hi, rss_lo, target (doubles), phase (an integer).
+struct SearchState {
+  double* w;
+  long R;
+  __device__ __forceinline__ DcSearch load(long r) const {
+    DcSearch s;
+    s.lo = w[r];
+    s.hi = w[R + r];
+    s.rss_lo = w[2 * R + r];
+    s.target = w[3 * R + r];
+    s.phase = (int32_t) reinterpret_cast<const long*>(w + 4 * R)[r];
+    return s;
+  }
+  __device__ __forceinline__ void store(long r, const DcSearch& s) {
+    w[r] = s.lo;
+    w[R + r] = s.hi;
+    w[2 * R + r] = s.rss_lo;
+    w[3 * R + r] = s.target;
+    reinterpret_cast<long*>(w + 4 * R)[r] = s.phase;
+  }
+};
+
+// one thread per trace: the state before round 0, and round 0's parameter
+__global__ __launch_bounds__(kSearchThreads) void deconv_search_begin_kernel(const double* __restrict__ sigma, int R, long T, double* state,
+                                                                             double* __restrict__ param) {
+  const long r = (long)blockIdx.x * kSearchThreads + threadIdx.x;
+  if (r >= R) return;
+  SearchState st = {state, (long)R};
+  st.store(r, dc_search_begin(sigma[r], T));
+  param[r] = 0.0;
+}
+
+// The residual of the stacks the forward pass left in the workspace, then one step of the search.  One workgroup of 256 threads per
+// trace: thread j owns lane j of the fold, t = j, j + 256, ... (coalesced reads of y); the pool of t is found as the fill kernel
+// finds it, by bisection over the ascending starts, from the pool of the thread's previous frame upwards and only when t has left
+// that pool.  The tree through LDS is the header's; thread 0 then moves the bracket and writes the parameter the next forward
+// pass reads (last: p*, RSS(p*) and the status instead).  Every word has one writer; frames t >= T of a row are never read.
+template <typename In, bool Each>
+__global__ __launch_bounds__(kSearchThreads) void deconv_residual_step_kernel(const In* __restrict__ y, long ld, int R, long T,
+                                                                              const double* __restrict__ G_all, long ldG,
+                                                                              const double* __restrict__ ws, const int* __restrict__ pools, int last,
+                                                                              double* state, double* param, double* __restrict__ rss,
+                                                                              int* __restrict__ status) {
+  __shared__ double red[kSearchThreads];
+  const int tid = threadIdx.x;
+  const long plane = (long)R * T;
+  const double* v = ws;
+  const int2* tl = reinterpret_cast<const int2*>(ws + 2 * plane);
+  for (long r = blockIdx.x; r < R; r += gridDim.x) {
+    const In* __restrict__ row = y + r * ld;
+    const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
+    const int32_t n = pools[r];
+    int32_t at = 0, start = 0, end = 0;                              // the pool of the previous frame: [start, end); none yet
+    double val = 0.0;
+    double s = 0.0;
+    for (long t = tid; t < T; t += kSearchThreads) {
+      if (t >= end) {
+        int32_t lo = at, hi = n - 1;                                 // pool lo starts at or before t, pool hi + 1 (if any) after it
+        while (lo < hi) {
+          const int32_t mid = lo + (hi - lo + 1) / 2;                // lo < mid <= hi
+          if (tl[(long)mid * R + r].x <= t) lo = mid;
+          else hi = mid - 1;
+        }
+        const int2 own = tl[(long)lo * R + r];
+        at = lo;
+        start = own.x;
+        end = own.x + own.y;
+        val = v[(long)lo * R + r];
+      }
+      s = s + dc_search_term((double)row[t], dc_deconv_calcium(val, G[t - start]));
+    }
+    red[tid] = s;
+    for (int h = kSearchThreads / 2; h >= 1; h >>= 1) {
+      __syncthreads();
+      if (tid < h) red[tid] = red[tid] + red[tid + h];
+    }
+    if (tid == 0) {
+      SearchState st = {state, (long)R};
+      DcSearch q = st.load(r);
+      const double next = dc_search_step(q, param[r], red[0]);
+      st.store(r, q);
+      if (last) {
+        param[r] = q.lo;
+        rss[r] = q.rss_lo;
+        status[r] = dc_search_status(q);
+      } else {
+        param[r] = next;
+      }
+    }
+    __syncthreads();                                                 // red is free for the next trace
+  }
+}
+
 struct HostStack {
   std::vector<DcPool>* pools;
   DcPool load(int32_t i) const { return (*pools)[(size_t)i]; }
@@ -161,10 +260,10 @@ int check_limits(const char* who, int R, long T, double g) {
   return DC_OK;
 }
 
-// the forward pass, then the fill; the arguments have been checked
+// the forward pass; the arguments have been checked
 template <bool Each>
-int launch_deconv(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
-                  const double* lam, const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream) {
+int launch_forward(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
+                   const double* lam, const double* smin, void* ws, int* pools, dc_stream_t stream) {
   const unsigned groups = (unsigned)(((long)R + kLanes - 1) / kLanes);                      // <= 2^25: no cap
   if (is_f64)
     hipLaunchKernelGGL((deconv_forward_kernel<double, Each>), dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const double*)y, ld, R, T, g,
@@ -173,6 +272,15 @@ int launch_deconv(const char* who, const void* y, int is_f64, long ld, int R, lo
     hipLaunchKernelGGL((deconv_forward_kernel<float, Each>), dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const float*)y, ld, R, T, g, gs,
                        G, ldG, lam, smin, (double*)ws, pools);
   DC_CHECK_LAUNCH(who);
+  return DC_OK;
+}
+
+// the forward pass, then the fill; the arguments have been checked
+template <bool Each>
+int launch_deconv(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
+                  const double* lam, const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream) {
+  const int rc = launch_forward<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, ws, pools, stream);
+  if (rc != DC_OK) return rc;
   const unsigned blocks = (unsigned)(((long)R * T + kFillThreads - 1) / kFillThreads);      // <= 2^23: no cap
   hipLaunchKernelGGL(deconv_fill_kernel<Each>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)stream, (const double*)ws, pools, R, T, g, gs, G,
                      ldG, calcium, spikes);
@@ -243,6 +351,138 @@ extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int 
       deconv_host_row((const double*)y + (long)r * ld, T, g, G, lam[r], smin[r], pool, c, s, pools + r);
     else
       deconv_host_row((const float*)y + (long)r * ld, T, g, G, lam[r], smin[r], pool, c, s, pools + r);
+  }
+  return DC_OK;
+}
+
+// ---- the noise-constrained search --------------------------------------------------------------------------------------------------
+namespace {
+
+// the residual of the stacks in ws and one step of every search; the arguments have been checked
+template <bool Each>
+int launch_residual_step(const char* who, const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws,
+                         const int* pools, int last, void* state, double* param, double* rss, int* status, dc_stream_t stream) {
+  const unsigned groups = (unsigned)(R < kSearchMaxGroups ? R : kSearchMaxGroups);
+  if (is_f64)
+    hipLaunchKernelGGL((deconv_residual_step_kernel<double, Each>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)stream, (const double*)y, ld,
+                       R, T, G, ldG, (const double*)ws, pools, last, (double*)state, param, rss, status);
+  else
+    hipLaunchKernelGGL((deconv_residual_step_kernel<float, Each>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)stream, (const float*)y, ld, R,
+                       T, G, ldG, (const double*)ws, pools, last, (double*)state, param, rss, status);
+  DC_CHECK_LAUNCH(who);
+  return DC_OK;
+}
+
+// round 0, the rounds and the final pass; the arguments have been checked
+template <bool Each>
+int launch_constrained(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
+                       int which, const double* sigma, const double* other, int rounds, void* ws, void* state, double* calcium, double* spikes,
+                       int* pools, double* param, double* rss, int* status, dc_stream_t stream) {
+  const double* lam = which == DC_SEARCH_LAM ? param : other;
+  const double* smin = which == DC_SEARCH_LAM ? other : param;
+  const unsigned begin = (unsigned)(((long)R + kSearchThreads - 1) / kSearchThreads);
+  hipLaunchKernelGGL(deconv_search_begin_kernel, dim3(begin), dim3(kSearchThreads), 0, (hipStream_t)stream, sigma, R, T, (double*)state, param);
+  DC_CHECK_LAUNCH(who);
+  for (int round = 0; round <= rounds; ++round) {
+    int rc = launch_forward<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, ws, pools, stream);
+    if (rc != DC_OK) return rc;
+    rc = launch_residual_step<Each>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, round == rounds, state, param, rss, status, stream);
+    if (rc != DC_OK) return rc;
+  }
+  return launch_deconv<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, ws, calcium, spikes, pools, stream);
+}
+
+int check_search(const char* who, int which, int rounds) {
+  DC_REQUIRE(which == DC_SEARCH_SMIN || which == DC_SEARCH_LAM, DC_EINVAL, "%s: which = %d is neither 0 (smin) nor 1 (lam)", who, which);
+  DC_REQUIRE(rounds >= 1 && rounds <= DC_SEARCH_MAX_ROUNDS, DC_EINVAL, "%s: rounds = %d is outside [1, %d]", who, rounds, DC_SEARCH_MAX_ROUNDS);
+  return DC_OK;
+}
+
+}  // namespace
+
+extern "C" long dc_trace_deconv_search_state_bytes(int R) { return R <= 0 ? 0 : 40L * R; }
+
+extern "C" int dc_trace_deconv_ar1_constrained(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
+                                               long ldG, int which, const double* sigma, const double* fixed_other, int rounds, void* ws,
+                                               void* state, double* calcium, double* spikes, int* pools, double* param, double* rss,
+                                               int* status, dc_stream_t stream) {
+  const char* who = "dc_trace_deconv_ar1_constrained";
+  DC_REQUIRE(G && sigma && fixed_other && ws && state && calcium && spikes && pools && param && rss && status, DC_EINVAL, "%s: null pointer", who);
+  int rc = check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  rc = check_search(who, which, rounds);
+  if (rc != DC_OK) return rc;
+  if (gs) DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
+  rc = check_limits(who, R, T, gs ? 0.5 : g);                        // per trace, the decays lie in device memory: THE CALLER PROMISES 0 < gs[r] < 1
+  if (rc != DC_OK) return rc;                                        // sigma, fixed_other likewise: THE CALLER PROMISES 0 <= sigma[r] < 2^500, finite, and fixed_other[r] >= 0
+  DC_REQUIRE((((uintptr_t)gs | (uintptr_t)G | (uintptr_t)sigma | (uintptr_t)fixed_other | (uintptr_t)ws | (uintptr_t)state | (uintptr_t)calcium |
+                (uintptr_t)spikes | (uintptr_t)param | (uintptr_t)rss) & 7) == 0 &&
+                 ((((uintptr_t)pools) | ((uintptr_t)status)) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+             DC_EINVAL, "%s: misaligned buffer", who);
+  if (R == 0 || T == 0) return DC_OK;
+  if (gs)
+    return launch_constrained<true>(who, y, is_f64, ld, R, T, 0.0, gs, G, ldG, which, sigma, fixed_other, rounds, ws, state, calcium, spikes, pools,
+                                    param, rss, status, stream);
+  return launch_constrained<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, which, sigma, fixed_other, rounds, ws, state, calcium, spikes, pools,
+                                   param, rss, status, stream);
+}
+
+extern "C" int dc_trace_deconv_search_step(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws,
+                                           const int* pools, int last, void* state, double* param, double* rss, int* status,
+                                           dc_stream_t stream) {
+  const char* who = "dc_trace_deconv_search_step";
+  DC_REQUIRE(G && ws && pools && state && param && rss && status, DC_EINVAL, "%s: null pointer", who);
+  int rc = check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  DC_REQUIRE(last == 0 || last == 1, DC_EINVAL, "%s: last = %d is neither 0 nor 1", who, last);
+  DC_REQUIRE(ldG == 0 || ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is neither 0 nor at least T + 1 = %ld", who, ldG, T + 1);
+  rc = check_limits(who, R, T, 0.5);
+  if (rc != DC_OK) return rc;
+  DC_REQUIRE((((uintptr_t)G | (uintptr_t)ws | (uintptr_t)state | (uintptr_t)param | (uintptr_t)rss) & 7) == 0 &&
+                 ((((uintptr_t)pools) | ((uintptr_t)status)) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+             DC_EINVAL, "%s: misaligned buffer", who);
+  if (R == 0 || T == 0) return DC_OK;
+  if (ldG) return launch_residual_step<true>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, last, state, param, rss, status, stream);
+  return launch_residual_step<false>(who, y, is_f64, ld, R, T, G, 0, ws, pools, last, state, param, rss, status, stream);
+}
+
+extern "C" int dc_trace_deconv_ar1_constrained_host(const void* y, int is_f64, long ld, int R, long T, const double* G, int which,
+                                                    const double* sigma, const double* fixed_other, int rounds, double* calcium, double* spikes,
+                                                    int* pools, double* param, double* rss, int* status) {
+  const char* who = "dc_trace_deconv_ar1_constrained_host";
+  DC_REQUIRE(G && sigma && fixed_other && calcium && spikes && pools && param && rss && status, DC_EINVAL, "%s: null pointer", who);
+  DC_REQUIRE((((uintptr_t)G | (uintptr_t)sigma | (uintptr_t)fixed_other | (uintptr_t)calcium | (uintptr_t)spikes | (uintptr_t)param | (uintptr_t)rss) & 7) == 0 &&
+                 ((((uintptr_t)pools) | ((uintptr_t)status)) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+             DC_EINVAL, "%s: misaligned buffer", who);
+  int rc = check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  rc = check_search(who, which, rounds);
+  if (rc != DC_OK) return rc;
+  if (R == 0 || T == 0) return DC_OK;                                // G is not read: without frames it need not hold g
+  DC_REQUIRE(G[0] == 1.0, DC_EINVAL, "%s: G[0] = %g is not 1", who, G[0]);
+  const double g = G[1];
+  rc = check_limits(who, R, T, g);
+  if (rc != DC_OK) return rc;
+  for (int r = 0; r < R; ++r) {
+    DC_REQUIRE(sigma[r] >= 0.0 && sigma[r] < 0x1p500, DC_EINVAL, "%s: trace %d: sigma = %g is outside [0, 2^500)", who, r, sigma[r]);
+    DC_REQUIRE(fixed_other[r] >= 0.0, DC_EINVAL, "%s: trace %d: the fixed parameter %g is negative", who, r, fixed_other[r]);
+  }
+  std::vector<DcPool> pool((size_t)T);
+  std::vector<double> scratch((size_t)T);
+  for (int r = 0; r < R; ++r) {
+    double* c = calcium + (long)r * T;
+    double* s = spikes + (long)r * T;
+    if (is_f64) {
+      const double* row = (const double*)y + (long)r * ld;
+      dc_search_host(row, T, g, G, which, sigma[r], fixed_other[r], rounds, pool, scratch.data(), param + r, rss + r, status + r);
+      deconv_host_row(row, T, g, G, which == DC_SEARCH_LAM ? param[r] : fixed_other[r], which == DC_SEARCH_LAM ? fixed_other[r] : param[r], pool, c, s,
+                      pools + r);
+    } else {
+      const float* row = (const float*)y + (long)r * ld;
+      dc_search_host(row, T, g, G, which, sigma[r], fixed_other[r], rounds, pool, scratch.data(), param + r, rss + r, status + r);
+      deconv_host_row(row, T, g, G, which == DC_SEARCH_LAM ? param[r] : fixed_other[r], which == DC_SEARCH_LAM ? fixed_other[r] : param[r], pool, c, s,
+                      pools + r);
+    }
   }
   return DC_OK;
 }

@@ -19,21 +19,56 @@ so the results are defined bit for bit.
     c, s, info = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau='auto', details=True)     # g estimated from the traces
     dec = TraceDeconvolver(dff_dev, g_each, s_min=3.0 * sigma)          # one decay per trace (deep_calcium_amd.dynamics.pick_gamma)
 
-Not built: AR(2), optimising g by the residual, the noise-constrained search for lam, a baseline term (feed dF/F, whose
-baseline is 0).
+The threshold without a k: constrain='s_min' (or 'lam') searches that parameter per trace, on the device, for the largest value
+tried whose residual stays within the noise, RSS(p) <= sigma^2 T (the header's "noise-constrained search"); the object then also
+gives
+
+    param     float64   p*, the value found
+    rss       float64   RSS(p*)
+    target    float64   (sigma * sigma) * T
+    status    int32     0 bracketed, 1 p* = 0 (the residual reaches the noise unconstrained), 2 never bracketed (slack at p*)
+
+    dec = TraceDeconvolver(dff_dev, g, constrain='s_min')               # sigma = the trace noise, computed on the device
+    c, s, info = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau='auto', k='noise', details=True)
+
+Search s_min for events (spikes > 0) and lam for a denoised calcium: the L1 solution's spikes > 0 is a poor event detector.
+
+Not built: AR(2), optimising g by the residual, a baseline term (feed dF/F, whose baseline is 0); for the search: both
+parameters at once, a warm start, the closed-form lam update of OASIS, a joint search over g.
 
 Importing this module needs neither torch nor the GPU; constructing a TraceDeconvolver does (there is no CPU fallback).
 """
 import numpy as np
 
 KINDS = ('calcium', 'spikes', 'pools')
+SEARCH_KINDS = ('param', 'rss', 'target', 'status')       # of a constrained object only
+CONSTRAIN = {'s_min': 0, 'lam': 1}    # DC_TRACE_DECONV_SEARCH_SMIN, DC_TRACE_DECONV_SEARCH_LAM
+MAX_ROUNDS = 64                       # DC_TRACE_DECONV_SEARCH_MAX_ROUNDS
+MAX_SIGMA = 2.0 ** 500
 MAX_FRAMES = 1 << 24                  # DC_TRACE_DECONV_MAX_FRAMES
 MAX_SAMPLES = 1 << 31                 # DC_TRACE_DECONV_MAX_SAMPLES
 
 
-def _check_kind(kind):
+def _check_kind(kind, constrained=False):
+    if constrained and kind in SEARCH_KINDS:
+        return
     if kind not in KINDS:
         raise ValueError('deconvolution kind %r is not one of %s' % (kind, ', '.join(KINDS)))
+
+
+def _check_rounds(rounds):
+    if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= MAX_ROUNDS:
+        raise ValueError('rounds must be an integer in [1, %d], not %r' % (MAX_ROUNDS, rounds))
+    return int(rounds)
+
+
+def _check_sigma(sigma, R):
+    """The noise the search is held to: a scalar or one value per trace, finite, >= 0 and below 2**500 -> float64[R]."""
+    sigma = _per_trace(sigma, 'sigma', R)
+    bad = np.flatnonzero(sigma >= MAX_SIGMA)
+    if bad.size:
+        raise ValueError('sigma must be below 2**500: trace %d has %r' % (int(bad[0]), float(sigma[bad[0]])))
+    return sigma
 
 
 # ---- the host helpers: definitions, float64 numpy -----------------------------------------------------------------------------------
@@ -148,11 +183,15 @@ class TraceDeconvolver(object):
     """Owns the device state of one deconvolution: the traces, the table G, the workspace of pools and the three results.  The
     kernels run at most once; result() only copies."""
 
-    def __init__(self, traces, g, s_min=0.0, lam=0.0, device=None):
+    def __init__(self, traces, g, s_min=0.0, lam=0.0, constrain=None, sigma=None, rounds=24, device=None):
         """traces: (R, T) float32 or float64, numpy (checked for non-finite values) or a tensor already on the device (read in
         place, never written; THE CALLER PROMISES FINITE VALUES).  g in (0, 1): a scalar -- one decay and one table for all traces
         -- or an array of one value per trace (e.g. pick_gamma's g_each): the tables are then built on the device, one row per
-        trace, and trace r gets the bits a scalar g[r] would give it.  s_min, lam: a scalar or one value per trace, >= 0."""
+        trace, and trace r gets the bits a scalar g[r] would give it.  s_min, lam: a scalar or one value per trace, >= 0.
+        constrain: None, or 's_min' / 'lam': that parameter is searched per trace (it must then be left at 0) in `rounds` rounds,
+        [1, 64], against sigma: None -- the noise of every trace, computed on the device where the traces lie --, a scalar or one
+        value per trace (finite, >= 0, below 2**500), numpy or a float64 tensor on the device (read in place; THE CALLER PROMISES
+        THAT RANGE)."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         R, T, f64 = _check_traces(traces)
         self._each = np.ndim(g) != 0
@@ -162,6 +201,22 @@ class TraceDeconvolver(object):
             self.g = _check_gamma(g)
         smin = _per_trace(s_min, 's_min', R)
         lam = _per_trace(lam, 'lam', R)
+        self.constrain = constrain
+        if constrain is None:
+            if sigma is not None:
+                raise ValueError('sigma is the noise the search is held to: it needs constrain=')
+        else:
+            if not isinstance(constrain, str) or constrain not in CONSTRAIN:
+                raise ValueError("constrain must be None, 's_min' or 'lam', not %r" % (constrain,))
+            if (smin if constrain == 's_min' else lam).any():
+                raise ValueError('%s is searched (constrain=%r): it cannot also be given' % (constrain, constrain))
+            self.rounds = _check_rounds(rounds)
+            if _is_device_tensor(sigma):
+                if not sigma.is_cuda or str(sigma.dtype) != 'torch.float64' or tuple(sigma.shape) != (R,) or not sigma.is_contiguous():
+                    raise ValueError('sigma must be a contiguous float64 tensor of %d values on the device, not %s %r'
+                                     % (R, sigma.dtype, tuple(sigma.shape)))
+            elif sigma is not None:
+                sigma = _check_sigma(sigma, R)
         table = None if self._each else ar1_table(self.g, T)
         self.n_traces, self.n_frames = R, T
 
@@ -193,6 +248,11 @@ class TraceDeconvolver(object):
         self._smin = torch.from_numpy(smin).to(dev)
         self._lam = torch.from_numpy(lam).to(dev)
         self._out = None
+        if constrain is not None:
+            if _is_device_tensor(sigma) and sigma.device != dev:
+                raise ValueError('sigma is on %s, the deconvolution runs on %s' % (sigma.device, dev))
+            # None: the trace noise, computed in _run() and never leaving the device
+            self._sigma = sigma if sigma is None or _is_device_tensor(sigma) else torch.from_numpy(sigma).to(dev)
 
     def _run(self):
         if self._out is None:
@@ -203,6 +263,9 @@ class TraceDeconvolver(object):
                 s = torch.empty((R, T), dtype=torch.float64, device=self.device)
                 n = torch.empty(R, dtype=torch.int32, device=self.device)
                 stream = torch.cuda.current_stream(self.device).cuda_stream
+                if self.constrain is not None:
+                    self._out = self._run_constrained(ws, c, s, n, stream)
+                    return self._out
                 if self._each:
                     tables = torch.empty((R, T + 1), dtype=torch.float64, device=self.device)
                     self.L.dc_ar1_tables(self._G.data_ptr(), R, T, tables.data_ptr(), T + 1, stream)
@@ -217,13 +280,46 @@ class TraceDeconvolver(object):
             self._out = dict(calcium=c, spikes=s, pools=n)        # the workspace goes back to the allocator (stream-ordered)
         return self._out
 
+    def _run_constrained(self, ws, c, s, n, stream):
+        """The whole search and the final pass, enqueued by one call: nothing is read back in between."""
+        torch, R, T, L = self._torch, self.n_traces, self.n_frames, self.L
+        y = self._y.data_ptr()
+        if self._sigma is None:
+            self._sigma = torch.empty(R, dtype=torch.float64, device=self.device)
+            L.dc_trace_noise(y, int(self._f64), self._ld, R, T, self._sigma.data_ptr(), stream)
+        state = torch.empty(L.dc_trace_deconv_search_state_bytes(R) // 8, dtype=torch.float64, device=self.device)
+        param = torch.empty(R, dtype=torch.float64, device=self.device)
+        rss = torch.empty(R, dtype=torch.float64, device=self.device)
+        status = torch.empty(R, dtype=torch.int32, device=self.device)
+        other = self._lam if self.constrain == 's_min' else self._smin
+        if self._each:
+            tables = torch.empty((R, T + 1), dtype=torch.float64, device=self.device)
+            L.dc_ar1_tables(self._G.data_ptr(), R, T, tables.data_ptr(), T + 1, stream)
+            g, gs, G, ldG = 0.0, self._G.data_ptr(), tables.data_ptr(), T + 1
+        else:
+            g, gs, G, ldG = self.g, None, self._G.data_ptr(), 0
+        L.dc_trace_deconv_ar1_constrained(y, int(self._f64), self._ld, R, T, g, gs, G, ldG, CONSTRAIN[self.constrain], self._sigma.data_ptr(),
+                                          other.data_ptr(), self.rounds, ws.data_ptr(), state.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(),
+                                          param.data_ptr(), rss.data_ptr(), status.data_ptr(), stream)
+        # plane 3 of the state holds the targets; the rest goes back to the allocator with the workspace
+        return dict(calcium=c, spikes=s, pools=n, param=param, rss=rss, status=status, target=state[3 * R:4 * R].clone())
+
+    @property
+    def sigma_device(self):
+        """The noise a constrained object was held to, float64[R] on the device (computed there when none was given)."""
+        if self.constrain is None:
+            raise ValueError('an unconstrained deconvolution has no sigma')
+        self._run()
+        return self._sigma
+
     def result_device(self, kind='spikes'):
         """result(kind) as a tensor on the device (the object's own state: do not write to it)."""
-        _check_kind(kind)
+        _check_kind(kind, self.constrain is not None)
         return self._run()[kind]
 
     def result(self, kind='spikes'):
-        """(R, T) float64 for 'calcium' and 'spikes', int32[R] for 'pools'."""
+        """(R, T) float64 for 'calcium' and 'spikes', int32[R] for 'pools'; of a constrained object also float64[R] for 'param',
+        'rss' and 'target' and int32[R] for 'status'."""
         return self.result_device(kind).cpu().numpy()
 
 
@@ -234,7 +330,9 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
     with `lags`, then pick_gamma with g_min, g_max) and the pooled median serves all traces --, or 'each' -- every trace is
     deconvolved with its own estimate.  fps is needed for a number only.  details=True -> (calcium, spikes, info), info =
     dict(g=the decay used, a float or float64[R] for 'each'; g_raw=, status=, pooled= what pick_gamma gave, None for a number;
-    sigma=sigma_hat float64[R])."""
+    sigma=sigma_hat float64[R]).  k='noise': no k at all -- s_min is searched per trace so that the residual stays within the
+    noise (TraceDeconvolver(constrain='s_min'), held to the same sigma_hat, which stays on the device); info then also has
+    s_min= the thresholds found, rss= their residuals and search_status= (0 bracketed, 1 s_min = 0, 2 never bracketed)."""
     mode = tau if isinstance(tau, str) else None
     if mode is not None and mode not in ('auto', 'each'):
         raise ValueError("tau must be a number of seconds, 'auto' or 'each', not %r" % (tau,))
@@ -246,12 +344,17 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
         pick_gamma(np.array([0.5]), g_min, g_max)                    # the bounds, before anything is opened
         if fps is not None:
             ar1_gamma(1.0, fps)
-    try:
-        k = float(k)
-    except (TypeError, ValueError):
-        raise ValueError('k must be a number >= 0, not %r' % (k,))
-    if not 0.0 <= k < np.inf:
-        raise ValueError('k must be finite and >= 0, not %r' % (k,))
+    search = isinstance(k, str)
+    if search:
+        if k != 'noise':
+            raise ValueError("k must be a number >= 0 or 'noise', not %r" % (k,))
+    else:
+        try:
+            k = float(k)
+        except (TypeError, ValueError):
+            raise ValueError('k must be a number >= 0, not %r' % (k,))
+        if not 0.0 <= k < np.inf:
+            raise ValueError('k must be finite and >= 0, not %r' % (k,))
     if np.ndim(lam) != 0:
         raise ValueError('lam must be a scalar here, not shape %r' % (np.shape(lam),))
     _per_trace(lam, 'lam', 1)
@@ -260,8 +363,12 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
     from .dff import dff_traces_device
     dff = dff_traces_device(dspath, rois, window, **dff_kw)
     if mode is None:
-        sigma = trace_noise(dff)
-        dec = TraceDeconvolver(dff, g, s_min=k * sigma, lam=lam, device=dff_kw.get('device'))
+        if search:
+            dec = TraceDeconvolver(dff, g, lam=lam, constrain='s_min', device=dff_kw.get('device'))
+            sigma = dec.sigma_device.cpu().numpy()
+        else:
+            sigma = trace_noise(dff)
+            dec = TraceDeconvolver(dff, g, s_min=k * sigma, lam=lam, device=dff_kw.get('device'))
         info = dict(g=g, g_raw=None, status=None, sigma=sigma, pooled=None)
     else:
         from .dynamics import TraceDynamics
@@ -269,8 +376,13 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
         sigma, g_raw = dyn.result('noise'), dyn.result('g_raw')
         g_each, status, g_pool = pick_gamma(g_raw, g_min, g_max)
         g = g_pool if mode == 'auto' else g_each
-        dec = TraceDeconvolver(dyn.traces_device, g, s_min=k * sigma, lam=lam, device=dyn.device)
+        if search:
+            dec = TraceDeconvolver(dyn.traces_device, g, lam=lam, constrain='s_min', sigma=dyn.result_device('noise'), device=dyn.device)
+        else:
+            dec = TraceDeconvolver(dyn.traces_device, g, s_min=k * sigma, lam=lam, device=dyn.device)
         info = dict(g=g, g_raw=g_raw, status=status, sigma=sigma, pooled=g_pool)
+    if search:
+        info.update(s_min=dec.result('param'), rss=dec.result('rss'), search_status=dec.result('status'))
     if details:
         return dec.result('calcium'), dec.result('spikes'), info
     return dec.result('calcium'), dec.result('spikes')

@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve auto|each|TAU [--fps F] [--spike-k K]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve auto|each|TAU [--fps F] [--spike-k K | --spike-constrain s_min|lam]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -147,7 +147,7 @@ def _n_frames(dspath):
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
            bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None, weighted=None, overlap='keep', deconvolve=None,
-           fps=None, spike_k=3.0):
+           fps=None, spike_k=3.0, spike_constrain=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -197,7 +197,9 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     spike_k * sigma_hat of every trace (deep_calcium_amd.TraceDeconvolver, trace_noise); the file gets the float64 datasets
     `calcium` and `deconvolved` (the spikes; an event is a value > 0) beside `traces`.  deconvolve='auto' or 'each' (fps optional):
     the decay is estimated from the dF/F itself, per trace, from its autocovariance (deep_calcium_amd.TraceDynamics, pick_gamma);
-    'auto' deconvolves every trace with the pooled median, 'each' with the trace's own estimate."""
+    'auto' deconvolves every trace with the pooled median, 'each' with the trace's own estimate.  spike_constrain='s_min' or 'lam':
+    no spike_k -- that parameter is searched per trace on the GPU until the residual equals the noise (TraceDeconvolver(constrain=));
+    s_min is the one for events, lam gives a denoised calcium."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -218,6 +220,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--deconvolve takes auto, each or the decay time TAU in seconds, not %r' % (deconvolve,))
     if deconvolve is not None and not estimated and fps is None:
         raise ValueError('--deconvolve needs --fps: the decay per frame is exp(-1 / (TAU * fps))')
+    if spike_constrain is not None and deconvolve is None:
+        raise ValueError('--spike-constrain needs --deconvolve')
+    if spike_constrain not in (None, 's_min', 'lam'):
+        raise ValueError('--spike-constrain takes s_min or lam, not %r' % (spike_constrain,))
     if deconvolve is not None and not spike_k >= 0:
         raise ValueError('--spike-k is the smallest spike in units of the trace noise, K >= 0, not %r' % (spike_k,))
     g = None if deconvolve is None or estimated else ar1_gamma(deconvolve, fps)
@@ -373,7 +379,11 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             dyn = TraceDynamics(tr)
             sigma = dyn.result('noise')
             g_each, status, g_pool = pick_gamma(dyn.result('g_raw'))
-            dec = TraceDeconvolver(dyn.traces_device, g_pool if deconvolve == 'auto' else g_each, s_min=spike_k * sigma)
+            if spike_constrain is not None:
+                dec = TraceDeconvolver(dyn.traces_device, g_pool if deconvolve == 'auto' else g_each, constrain=spike_constrain,
+                                       sigma=dyn.result_device('noise'))
+            else:
+                dec = TraceDeconvolver(dyn.traces_device, g_pool if deconvolve == 'auto' else g_each, s_min=spike_k * sigma)
             extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
             events = (extra['deconvolved'] > 0).sum(1)
             logger.info('%s: decay estimated from the traces (--deconvolve %s): pooled g = %.6f%s, per trace min / median / max = %.6f / %.6f / '
@@ -383,15 +393,24 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                             float(g_each.min()), float(np.median(g_each)), float(g_each.max()),
                             '' if fps is None else ' (tau %.4g / %.4g / %.4g s)' % tuple(ar1_tau(float(v), fps) for v in (g_each.min(), np.median(g_each), g_each.max())),
                             int((status == 0).sum()), int((status == 1).sum()), int((status == 2).sum()), int((status == 3).sum()),
-                            spike_k, float(np.median(sigma)), int(events.min()), float(np.median(events)), int(events.max())))
+                            0.0 if spike_constrain == 'lam' else spike_k, float(np.median(sigma)), int(events.min()), float(np.median(events)),
+                            int(events.max())))
         elif g is not None:
             sigma = trace_noise(tr)
-            dec = TraceDeconvolver(tr, g, s_min=spike_k * sigma)
+            dec = TraceDeconvolver(tr, g, s_min=spike_k * sigma) if spike_constrain is None else TraceDeconvolver(tr, g, constrain=spike_constrain)
             extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
             events = (extra['deconvolved'] > 0).sum(1)
             logger.info('%s: deconvolved with g = %.6f (tau %g s at %g frames/s), s_min = %g sigma_hat, median sigma_hat %.4g: '
-                        'events per ROI min / median / max = %d / %g / %d' % (name, g, deconvolve, fps, spike_k, float(np.median(sigma)),
-                                                                              int(events.min()), float(np.median(events)), int(events.max())))
+                        'events per ROI min / median / max = %d / %g / %d' % (name, g, deconvolve, fps, 0.0 if spike_constrain == 'lam' else spike_k,
+                                                                              float(np.median(sigma)), int(events.min()), float(np.median(events)),
+                                                                              int(events.max())))
+        if extra is not None and spike_constrain is not None:
+            found, st = dec.result('param'), dec.result('status')
+            ratio = found[sigma > 0] / sigma[sigma > 0] if (sigma > 0).any() else np.zeros(1)
+            logger.info('%s: %s searched per trace until the residual equals the noise (--spike-constrain: the s_min = K sigma_hat of the line '
+                        'above was not used): %s / sigma_hat min / median / max = %.3g / %.3g / %.3g; status bracketed / zero / never bracketed = %d / %d / %d'
+                        % (name, spike_constrain, spike_constrain, float(ratio.min()), float(np.median(ratio)), float(ratio.max()),
+                           int((st == 0).sum()), int((st == 1).sum()), int((st == 2).sum())))
         out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name, extra=extra)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
         logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
@@ -446,6 +465,8 @@ if __name__ == '__main__':
     sp_trc.add_argument('--fps', help='with --deconvolve: the frame rate of the recording in frames per second', default=None, type=float, metavar='F')
     sp_trc.add_argument('--spike-k', help='with --deconvolve: the smallest spike allowed, in units of every trace\'s noise (default 3)', default=3.0,
                         type=float, metavar='K', dest='spike_k')
+    sp_trc.add_argument('--spike-constrain', help='with --deconvolve, instead of --spike-k: search s_min (for events) or lam (for a denoised calcium) '
+                        'per trace until the residual equals the trace noise', default=None, choices=('s_min', 'lam'), dest='spike_constrain')
     sp_trc.add_argument('--refine', help='refine every ROI by its footprint map first: keep the pixels whose correlation with the trace is >= THR',
                         default=None, type=float, metavar='THR')
     sp_trc.add_argument('--halo', help='with --refine: how far beyond an ROI, in pixels, its footprint map reaches (0..16, default 2)', default=2,
@@ -479,6 +500,11 @@ if __name__ == '__main__':
         ap.error('--deconvolve needs --dff: the deconvolution has no baseline term')
     if args['which'] == 'traces' and args['deconvolve'] is not None and not isinstance(args['deconvolve'], str) and args['fps'] is None:
         ap.error('--deconvolve needs --fps')
+    if args['which'] == 'traces' and args['spike_constrain'] is not None:
+        if any(a == '--spike-k' or a.startswith('--spike-k=') for a in sys.argv[1:]):
+            ap.error('--spike-constrain searches the threshold: not together with --spike-k')
+        if args['deconvolve'] is None:
+            ap.error('--spike-constrain needs --deconvolve')
     if args['which'] == 'traces' and args['overlap'] != 'keep' and args['weighted'] is None:
         ap.error('--overlap needs --weighted')
     f = {'train': training, 'evaluate': evaluation, 'predict': prediction, 'traces': traces}[args.pop('which')]

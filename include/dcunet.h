@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 127
+#define DC_ABI_VERSION 128
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -853,9 +853,8 @@ int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float
  *   spikes[r][t0_i] = calcium[t0_i] - g * calcium[t0_i - 1] for every pool i >= 1, exactly +0.0 at every other frame, frame 0
  *     included.  Not clamped: with smin = 0 it can be below zero by rounding only.  An event is spikes > 0.
  *   pools[r]: int32, the final number of pools.
- * Not built: AR(2); optimising g by the residual; the noise-constrained search for lam; a baseline term; a wave-parallel
- * segment merge (it would change the operation order and so the bits); integer-exact arithmetic (the pool values are not closed
- * under any fixed-point format).
+ * Not built: AR(2); optimising g by the residual; a baseline term; a wave-parallel segment merge (it would change the operation
+ * order and so the bits); integer-exact arithmetic (the pool values are not closed under any fixed-point format).
  *   dc_trace_deconv_ws_bytes: the workspace of dc_trace_deconv_ar1, 24 * R * T bytes (0 for an empty or unsupported shape).
  *   dc_trace_deconv_ar1: forward pass (one lane per trace, 64 traces per workgroup), then the fill (one thread per sample).  All
  *     pointers are DEVICE memory.  g is passed by value and must equal G[1].  ws holds the pools below the top one as [depth][R]
@@ -865,7 +864,50 @@ int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float
  *   dc_trace_deconv_ar1_host: the same arithmetic (the same header) compiled for the host, over HOST pointers, one trace after the
  *     other on the calling thread; it allocates T pools of host memory for the duration of the call.  g = G[1]; G[0] != 1, a
  *     negative or NaN lam[r] or smin[r]: -1; otherwise the codes above.  The speed baseline, and the bit-for-bit check of the
- *     library against the oracle on a machine without a GPU. */
+ *     library against the oracle on a machine without a GPU.
+ * The noise-constrained search: one of the two parameters is not given but found, per trace, so that the residual equals the
+ * noise (OASIS, CaImAn's constrained foopsi): the largest p tried with RSS(p) <= sigma^2 T.  csrc/deconv_search_math.h is the one
+ * implementation.  which = DC_TRACE_DECONV_SEARCH_SMIN (0) or DC_TRACE_DECONV_SEARCH_LAM (1) names the searched parameter; the
+ * other one stays at fixed_other[r] >= 0.  sigma[r]: finite, >= 0 and below 2^500.  rounds = N in [1, 64].
+ *   RSS(p): the forward pass above with the searched parameter at p; c[t] = the calcium output; d_t = (double)y[t] - c[t];
+ *     RSS = fold(t -> d_t * d_t, T), the fold of "Trace dynamics" below (256 lane sums, then the tree); the product is rounded
+ *     once.
+ *   target = (sigma * sigma) * (double)T.
+ *   round 0: p = 0.0, r0 = RSS(0).  If !(r0 < target): p* = 0, status 1, rss = r0 (the residual reaches the noise unconstrained;
+ *     sigma = 0 ends here).  Otherwise lo = 0, rss_lo = r0, hi = sigma, expanding.
+ *   rounds 1 .. N: p = expanding ? hi : 0.5 * (lo + hi); r = RSS(p).  r <= target: lo = p, rss_lo = r, and hi = hi + hi while
+ *     expanding.  Otherwise hi = p and the search stops expanding for good.
+ *   end: p* = lo, rss = rss_lo, status = expanding ? 2 : 0.  Status 2: never bracketed, the constraint is still slack at p*.
+ *   calcium, spikes, pools: the outputs above at p*, the bits dc_trace_deconv_ar1 gives for that parameter.
+ *   Promised: RSS(p*) <= target for status 0 and 2; for status 0 also RSS(hi) > target, and after e expanding rounds (the one
+ *     that failed included) and N - e bisections hi - lo = 2^max(e-2, 0) sigma / 2^(N-e), to the rounding of the midpoints.
+ *     RSS is monotone in lam, so p* is the constrained optimum to that resolution; it is NOT monotone in smin, where only the
+ *     invariant holds.
+ *   dc_trace_deconv_search_state_bytes: the state of dc_trace_deconv_ar1_constrained, 40 * R bytes (0 for R <= 0): five planes of
+ *     R 8-byte words, lo, hi, rss_lo, target (doubles) and the phase (an integer); afterwards plane 3 holds the targets.
+ *   dc_trace_deconv_ar1_constrained: enqueues round 0, the N rounds and the final pass -- N + 2 forward passes, each but the last
+ *     followed by one residual-and-step launch (one workgroup of 256 threads per trace, at most
+ *     DC_TRACE_DECONV_SEARCH_MAX_GROUPS workgroups: beyond, a workgroup walks several traces), then the fill -- with no host
+ *     synchronisation and nothing read back.  All pointers are DEVICE memory.  gs == NULL: one decay g (by value, = G[1]) and
+ *     one table G for all traces, ldG is not used.  Otherwise trace r uses gs[r] and the row G + r * ldG, as in
+ *     dc_trace_deconv_ar1_each below, and g is not used.  ws: dc_trace_deconv_ws_bytes.  param = double[R], rss = double[R],
+ *     status = int32[R]; param is also the array the forward passes read the searched parameter from.  THE CALLER PROMISES
+ *     sigma and fixed_other in the ranges above (not checked: nothing is read on the host) and, per trace, 0 < gs[r] < 1 =
+ *     G[r][1].  which or rounds out of range, ldG < T + 1 with gs given: -1; otherwise the codes of dc_trace_deconv_ar1.
+ *   dc_trace_deconv_search_step: one residual-and-step launch alone, what dc_trace_deconv_ar1_constrained enqueues after every
+ *     forward pass but the final one: the residual of the stacks in ws (pools[r] of them per trace), then the step of every
+ *     trace's search in `state`, which writes the next parameter to param (last = 1: p*, rss and status instead).  ldG = 0: one
+ *     table for all traces; ldG >= T + 1: row r of G.  THE CALLER PROMISES that ws, pools, state and param are those of a
+ *     dc_trace_deconv_ar1_constrained call on the same y, R and T.  It is here to be timed by itself.
+ *   dc_trace_deconv_ar1_constrained_host: the same arithmetic (the same headers) compiled for the host, over HOST pointers, one
+ *     decay for all traces (g = G[1]), one trace after the other on the calling thread; sigma and fixed_other are checked (-1).
+ *     The speed baseline, and the bit-for-bit check against the oracle on a machine without a GPU.
+ * Not built for the search: AR(2); both parameters at once; a warm start (every round is a full forward pass); the OASIS closed-
+ * form update of lam (it would change the operation order); a joint search over g. */
+#define DC_TRACE_DECONV_SEARCH_SMIN 0
+#define DC_TRACE_DECONV_SEARCH_LAM 1
+#define DC_TRACE_DECONV_SEARCH_MAX_ROUNDS 64
+#define DC_TRACE_DECONV_SEARCH_MAX_GROUPS 8192
 #define DC_TRACE_DECONV_MAX_FRAMES 16777216L
 #define DC_TRACE_DECONV_MAX_SAMPLES 2147483648L
 long dc_trace_deconv_ws_bytes(int R, long T);
@@ -873,6 +915,16 @@ int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, long T, doubl
                         const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream);
 int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int R, long T, const double* G, const double* lam, const double* smin,
                              double* calcium, double* spikes, int* pools);
+long dc_trace_deconv_search_state_bytes(int R);
+int dc_trace_deconv_ar1_constrained(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
+                                    int which, const double* sigma, const double* fixed_other, int rounds, void* ws, void* state,
+                                    double* calcium, double* spikes, int* pools, double* param, double* rss, int* status,
+                                    dc_stream_t stream);
+int dc_trace_deconv_search_step(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws,
+                                const int* pools, int last, void* state, double* param, double* rss, int* status, dc_stream_t stream);
+int dc_trace_deconv_ar1_constrained_host(const void* y, int is_f64, long ld, int R, long T, const double* G, int which, const double* sigma,
+                                         const double* fixed_other, int rounds, double* calcium, double* spikes, int* pools, double* param,
+                                         double* rss, int* status);
 
 /* ---- Trace dynamics: noise and AR(1) decay -----------------------------------------------------------------------------------
  * The one parameter of the deconvolution above that had no data-driven default: the decay g, which depends on indicator,
