@@ -9,6 +9,8 @@ Importing this module needs neither torch nor the GPU.
 """
 import numpy as np
 
+from ._matrix import _is_device_tensor
+
 MAX_FRAMES = 2147483647               # DC_SERIES_MAX_FRAMES: what the int64 state holds
 _CHUNK_BYTES = 32 << 20               # default staging chunk: long enough to hide the launches, short enough to pin twice
 _MAX_BLOCKS = 32                      # DC_MOTION_MAX_BLOCKS
@@ -117,10 +119,6 @@ def _check_bidi(bidi, shape=None):
     if shape is not None and abs(p) >= shape[1]:
         raise ValueError('bidi = %d leaves no column of the odd lines of a %d x %d frame: |bidi| < W' % (p, shape[0], shape[1]))
     return p
-
-
-def _is_device_tensor(x):
-    return not isinstance(x, np.ndarray) and hasattr(x, 'is_cuda') and hasattr(x, 'data_ptr')
 
 
 def _check_device_frames(torch, frames, dtype, device, owner):

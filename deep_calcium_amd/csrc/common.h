@@ -64,6 +64,9 @@ bool dc_take_bracket(hipEvent_t* before, hipEvent_t* after);
 static inline int dc_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline bool dc_is_pow2(long v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline bool dc_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// every one of the pointers is a multiple of mask + 1 bytes; a null pointer is, so an optional buffer that is absent passes
+template <typename... P>
+static inline bool dc_aligned(uintptr_t mask, const P*... p) { return ((... | (uintptr_t)p) & mask) == 0; }
 
 // Counter-based dropout RNG: keep-decision for element `idx` under `seed` (same bits in fwd and bwd).
 __device__ __forceinline__ uint32_t dc_hash32(uint64_t seed, uint64_t idx) {

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "deconv_math.h"
 #include "deconv_search_math.h"
+#include "trace_matrix.h"
 
 namespace {
 
@@ -92,8 +93,20 @@ __global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __rest
   }
 }
 
-// One thread per sample (r, t): the pool that holds frame t is the last whose start is <= t (the starts ascend), found by
-// bisection over the trace's n pools.  Every output element is written, each by one product or one multiply-subtract.
+// The pool of trace r that holds frame t: the last whose start is <= t.  The starts ascend, so a bisection finds it; pool lo starts
+// at or before t, pool hi + 1 (if any) after it.  t in the caller's own integer type: the comparison stays as wide as it was there.
+template <typename Frame>
+__device__ __forceinline__ int32_t pool_of(const int2* tl, long R, long r, int32_t lo, int32_t hi, Frame t) {
+  while (lo < hi) {
+    const int32_t mid = lo + (hi - lo + 1) / 2;                      // lo < mid <= hi
+    if (tl[(long)mid * R + r].x <= t) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// One thread per sample (r, t): pool_of over the trace's n pools.  Every output element is written, each by one product or one
+// multiply-subtract.
 template <bool Each>
 __global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double* __restrict__ ws, const int* __restrict__ pools, int R, long T,
                                                                   double g_all, const double* __restrict__ gs, const double* __restrict__ G_all,
@@ -107,12 +120,7 @@ __global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double*
   const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
   const double* v = ws;
   const int2* tl = reinterpret_cast<const int2*>(ws + 2 * plane);
-  int32_t lo = 0, hi = pools[r] - 1;                                 // pool lo starts at or before t, pool hi + 1 (if any) after it
-  while (lo < hi) {
-    const int32_t mid = lo + (hi - lo + 1) / 2;                      // lo < mid <= hi
-    if (tl[(long)mid * R + r].x <= t) lo = mid;
-    else hi = mid - 1;
-  }
+  const int32_t lo = pool_of(tl, R, r, 0, pools[r] - 1, t);
   const int2 own = tl[(long)lo * R + r];
   const int32_t k = t - own.x;
   const double c = dc_deconv_calcium(v[(long)lo * R + r], G[k]);
@@ -160,8 +168,8 @@ __global__ __launch_bounds__(kSearchThreads) void deconv_search_begin_kernel(con
 
 // The residual of the stacks the forward pass left in the workspace, then one step of the search.  One workgroup of 256 threads per
 // trace: thread j owns lane j of the fold, t = j, j + 256, ... (coalesced reads of y); the pool of t is found as the fill kernel
-// finds it, by bisection over the ascending starts, from the pool of the thread's previous frame upwards and only when t has left
-// that pool.  The tree through LDS is the header's; thread 0 then moves the bracket and writes the parameter the next forward
+// finds it (pool_of), from the pool of the thread's previous frame upwards and only when t has left that pool.  The tree through
+// LDS is dc_dyn_fold_tree of trace_dyn_math.h; thread 0 then moves the bracket and writes the parameter the next forward
 // pass reads (last: p*, RSS(p*) and the status instead).  Every word has one writer; frames t >= T of a row are never read.
 template <typename In, bool Each>
 __global__ __launch_bounds__(kSearchThreads) void deconv_residual_step_kernel(const In* __restrict__ y, long ld, int R, long T,
@@ -183,26 +191,17 @@ __global__ __launch_bounds__(kSearchThreads) void deconv_residual_step_kernel(co
     double s = 0.0;
     for (long t = tid; t < T; t += kSearchThreads) {
       if (t >= end) {
-        int32_t lo = at, hi = n - 1;                                 // pool lo starts at or before t, pool hi + 1 (if any) after it
-        while (lo < hi) {
-          const int32_t mid = lo + (hi - lo + 1) / 2;                // lo < mid <= hi
-          if (tl[(long)mid * R + r].x <= t) lo = mid;
-          else hi = mid - 1;
-        }
-        const int2 own = tl[(long)lo * R + r];
-        at = lo;
+        at = pool_of(tl, R, r, at, n - 1, t);
+        const int2 own = tl[(long)at * R + r];
         start = own.x;
         end = own.x + own.y;
-        val = v[(long)lo * R + r];
+        val = v[(long)at * R + r];
       }
       s = s + dc_search_term((double)row[t], dc_deconv_calcium(val, G[t - start]));
     }
     red[tid] = s;
-    for (int h = kSearchThreads / 2; h >= 1; h >>= 1) {
-      __syncthreads();
-      if (tid < h) red[tid] = red[tid] + red[tid + h];
-    }
-    if (tid == 0) {
+    dc_dyn_fold_tree(red, 1);                                        // its last barrier frees red[1 ..] for the next trace
+    if (tid == 0) {                                                  // red[0] is thread 0's own: read here, written next after this
       SearchState st = {state, (long)R};
       DcSearch q = st.load(r);
       const double next = dc_search_step(q, param[r], red[0]);
@@ -215,24 +214,13 @@ __global__ __launch_bounds__(kSearchThreads) void deconv_residual_step_kernel(co
         param[r] = next;
       }
     }
-    __syncthreads();                                                 // red is free for the next trace
   }
 }
-
-struct HostStack {
-  std::vector<DcPool>* pools;
-  DcPool load(int32_t i) const { return (*pools)[(size_t)i]; }
-  void store(int32_t i, const DcPool& p) { (*pools)[(size_t)i] = p; }
-};
 
 template <typename In>
 void deconv_host_row(const In* y, long T, double g, const double* G, double lam, double smin, std::vector<DcPool>& pool, double* calcium,
                      double* spikes, int* pools) {
-  HostStack st = {&pool};
-  DcPool top = dc_deconv_new(0.0, 0);
-  int32_t n = 0;
-  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, (double)y[t] - dc_deconv_mu(lam, g, t, T), t, G, smin);
-  st.store(n - 1, top);
+  const int32_t n = dc_deconv_forward_host(y, T, g, G, lam, smin, pool);
   *pools = n;
   for (int32_t i = 0; i < n; ++i) {
     const DcPool& p = pool[(size_t)i];
@@ -244,20 +232,9 @@ void deconv_host_row(const In* y, long T, double g, const double* G, double lam,
   }
 }
 
-int check_counts(const char* who, const void* y, int is_f64, long ld, int R, long T) {
-  DC_REQUIRE(y, DC_EINVAL, "%s: null pointer", who);
-  DC_REQUIRE(is_f64 == 0 || is_f64 == 1, DC_EINVAL, "%s: is_f64 = %d is neither 0 nor 1", who, is_f64);
-  DC_REQUIRE(R >= 0 && T >= 0, DC_EINVAL, "%s: negative count (R %d, T %ld)", who, R, T);
-  DC_REQUIRE(ld >= T, DC_EINVAL, "%s: ld = %ld is below T = %ld", who, ld, T);
-  return DC_OK;
-}
-
 int check_limits(const char* who, int R, long T, double g) {
   DC_REQUIRE(g > 0.0 && g < 1.0, DC_EINVAL, "%s: g = %g is outside (0, 1)", who, g);      // a NaN fails both comparisons
-  DC_REQUIRE(T <= DC_TRACE_DECONV_MAX_FRAMES, DC_EUNSUP, "%s: T = %ld is over the limit of %ld frames", who, T, DC_TRACE_DECONV_MAX_FRAMES);
-  DC_REQUIRE((long)R * T <= DC_TRACE_DECONV_MAX_SAMPLES, DC_EUNSUP, "%s: R * T = %ld is over the limit of %ld samples", who, (long)R * T,
-             DC_TRACE_DECONV_MAX_SAMPLES);
-  return DC_OK;
+  return dc_trace_check_limits(who, R, T);
 }
 
 // the forward pass; the arguments have been checked
@@ -299,13 +276,11 @@ extern "C" int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, lo
                                    const double* smin, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream) {
   const char* who = "dc_trace_deconv_ar1";
   DC_REQUIRE(G && lam && smin && ws && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
-  int rc = check_counts(who, y, is_f64, ld, R, T);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   rc = check_limits(who, R, T, g);
   if (rc != DC_OK) return rc;
-  DC_REQUIRE((((uintptr_t)G | (uintptr_t)lam | (uintptr_t)smin | (uintptr_t)ws | (uintptr_t)calcium | (uintptr_t)spikes) & 7) == 0 &&
-                 (((uintptr_t)pools) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
-             DC_EINVAL, "%s: misaligned buffer", who);
+  DC_REQUIRE(dc_aligned(7, G, lam, smin, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
   return launch_deconv<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, lam, smin, ws, calcium, spikes, pools, stream);
 }
@@ -315,14 +290,12 @@ extern "C" int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int 
                                         dc_stream_t stream) {
   const char* who = "dc_trace_deconv_ar1_each";
   DC_REQUIRE(g && G && lam && smin && ws && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
-  int rc = check_counts(who, y, is_f64, ld, R, T);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
   rc = check_limits(who, R, T, 0.5);                                 // the decays lie in device memory: THE CALLER PROMISES 0 < g[r] < 1
   if (rc != DC_OK) return rc;
-  DC_REQUIRE((((uintptr_t)g | (uintptr_t)G | (uintptr_t)lam | (uintptr_t)smin | (uintptr_t)ws | (uintptr_t)calcium | (uintptr_t)spikes) & 7) == 0 &&
-                 (((uintptr_t)pools) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
-             DC_EINVAL, "%s: misaligned buffer", who);
+  DC_REQUIRE(dc_aligned(7, g, G, lam, smin, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
   return launch_deconv<true>(who, y, is_f64, ld, R, T, 0.0, g, G, ldG, lam, smin, ws, calcium, spikes, pools, stream);
 }
@@ -331,10 +304,8 @@ extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int 
                                         const double* smin, double* calcium, double* spikes, int* pools) {
   const char* who = "dc_trace_deconv_ar1_host";
   DC_REQUIRE(G && lam && smin && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
-  DC_REQUIRE((((uintptr_t)G | (uintptr_t)lam | (uintptr_t)smin | (uintptr_t)calcium | (uintptr_t)spikes) & 7) == 0 &&
-                 (((uintptr_t)pools) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
-             DC_EINVAL, "%s: misaligned buffer", who);
-  int rc = check_counts(who, y, is_f64, ld, R, T);
+  DC_REQUIRE(dc_aligned(7, G, lam, smin, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   if (R == 0 || T == 0) return DC_OK;                                // G is not read: without frames it need not hold g
   DC_REQUIRE(G[0] == 1.0, DC_EINVAL, "%s: G[0] = %g is not 1", who, G[0]);
@@ -408,16 +379,15 @@ extern "C" int dc_trace_deconv_ar1_constrained(const void* y, int is_f64, long l
                                                int* status, dc_stream_t stream) {
   const char* who = "dc_trace_deconv_ar1_constrained";
   DC_REQUIRE(G && sigma && fixed_other && ws && state && calcium && spikes && pools && param && rss && status, DC_EINVAL, "%s: null pointer", who);
-  int rc = check_counts(who, y, is_f64, ld, R, T);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   rc = check_search(who, which, rounds);
   if (rc != DC_OK) return rc;
   if (gs) DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
   rc = check_limits(who, R, T, gs ? 0.5 : g);                        // per trace, the decays lie in device memory: THE CALLER PROMISES 0 < gs[r] < 1
   if (rc != DC_OK) return rc;                                        // sigma, fixed_other likewise: THE CALLER PROMISES 0 <= sigma[r] < 2^500, finite, and fixed_other[r] >= 0
-  DC_REQUIRE((((uintptr_t)gs | (uintptr_t)G | (uintptr_t)sigma | (uintptr_t)fixed_other | (uintptr_t)ws | (uintptr_t)state | (uintptr_t)calcium |
-                (uintptr_t)spikes | (uintptr_t)param | (uintptr_t)rss) & 7) == 0 &&
-                 ((((uintptr_t)pools) | ((uintptr_t)status)) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+  DC_REQUIRE(dc_aligned(7, gs, G, sigma, fixed_other, ws, state, calcium, spikes, param, rss) && dc_aligned(3, pools, status) &&
+                 dc_trace_aligned(y, is_f64),
              DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
   if (gs)
@@ -432,15 +402,13 @@ extern "C" int dc_trace_deconv_search_step(const void* y, int is_f64, long ld, i
                                            dc_stream_t stream) {
   const char* who = "dc_trace_deconv_search_step";
   DC_REQUIRE(G && ws && pools && state && param && rss && status, DC_EINVAL, "%s: null pointer", who);
-  int rc = check_counts(who, y, is_f64, ld, R, T);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(last == 0 || last == 1, DC_EINVAL, "%s: last = %d is neither 0 nor 1", who, last);
   DC_REQUIRE(ldG == 0 || ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is neither 0 nor at least T + 1 = %ld", who, ldG, T + 1);
   rc = check_limits(who, R, T, 0.5);
   if (rc != DC_OK) return rc;
-  DC_REQUIRE((((uintptr_t)G | (uintptr_t)ws | (uintptr_t)state | (uintptr_t)param | (uintptr_t)rss) & 7) == 0 &&
-                 ((((uintptr_t)pools) | ((uintptr_t)status)) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
-             DC_EINVAL, "%s: misaligned buffer", who);
+  DC_REQUIRE(dc_aligned(7, G, ws, state, param, rss) && dc_aligned(3, pools, status) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
   if (ldG) return launch_residual_step<true>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, last, state, param, rss, status, stream);
   return launch_residual_step<false>(who, y, is_f64, ld, R, T, G, 0, ws, pools, last, state, param, rss, status, stream);
@@ -451,10 +419,9 @@ extern "C" int dc_trace_deconv_ar1_constrained_host(const void* y, int is_f64, l
                                                     int* pools, double* param, double* rss, int* status) {
   const char* who = "dc_trace_deconv_ar1_constrained_host";
   DC_REQUIRE(G && sigma && fixed_other && calcium && spikes && pools && param && rss && status, DC_EINVAL, "%s: null pointer", who);
-  DC_REQUIRE((((uintptr_t)G | (uintptr_t)sigma | (uintptr_t)fixed_other | (uintptr_t)calcium | (uintptr_t)spikes | (uintptr_t)param | (uintptr_t)rss) & 7) == 0 &&
-                 ((((uintptr_t)pools) | ((uintptr_t)status)) & 3) == 0 && (((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0,
+  DC_REQUIRE(dc_aligned(7, G, sigma, fixed_other, calcium, spikes, param, rss) && dc_aligned(3, pools, status) && dc_trace_aligned(y, is_f64),
              DC_EINVAL, "%s: misaligned buffer", who);
-  int rc = check_counts(who, y, is_f64, ld, R, T);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   rc = check_search(who, which, rounds);
   if (rc != DC_OK) return rc;

@@ -1,7 +1,8 @@
 // The arithmetic of the AR(1) deconvolution (include/dcunet.h, "Spikes by deconvolution"; csrc/deconv.hip): the push / merge step
-// of the pool stack and the two output formulas.  Plain C++ like footprint_math.h, so the same inline functions compile for the
-// device kernels, for the host entry point dc_trace_deconv_ar1_host and into a stand-alone host program
-// (tests/native/deconv_math_check.cpp, run under the address / undefined-behaviour sanitizers).  The result is defined bit for bit:
+// of the pool stack, the two output formulas and, in a host-only tail, the forward pass of one trace.  Plain C++ like
+// footprint_math.h, so the same inline functions compile for the device kernels, for the host entry point dc_trace_deconv_ar1_host
+// and into a stand-alone host program (tests/native/deconv_math_check.cpp, run under the address / undefined-behaviour sanitizers).
+// The result is defined bit for bit:
 // IEEE double adds, multiplies, one division per merge and comparisons in the order written here.  No fused multiply-add and no
 // reassociation anywhere: the pragma below, and -ffp-contract=off for deconv.hip in _build.py.
 #pragma once
@@ -88,3 +89,24 @@ DC_DECONV_HD double dc_deconv_calcium(double v, double Gk) {
 
 // the spike at the first frame of a pool that has a pool below it: c is its own calcium there, cprev the calcium one frame earlier
 DC_DECONV_HD double dc_deconv_spike(double c, double g, double cprev) { return c - g * cprev; }
+
+// ---- the host restatement: dc_trace_deconv_ar1_host, the search of deconv_search_math.h and the stand-alone checks -----------------
+// (host functions: no attribute)
+#include <vector>
+
+struct DcHostStack {
+  std::vector<DcPool>* pools;
+  DcPool load(int32_t i) const { return (*pools)[(size_t)i]; }
+  void store(int32_t i, const DcPool& p) { (*pools)[(size_t)i] = p; }
+};
+
+// the forward pass of one trace of T >= 1 frames into pool[0 .. n), which needs T entries; -> n
+template <typename In>
+inline int32_t dc_deconv_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, std::vector<DcPool>& pool) {
+  DcHostStack st = {&pool};
+  DcPool top = dc_deconv_new(0.0, 0);
+  int32_t n = 0;
+  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, (double)y[t] - dc_deconv_mu(lam, g, t, T), t, G, smin);
+  st.store(n - 1, top);
+  return n;
+}

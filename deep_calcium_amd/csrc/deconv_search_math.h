@@ -2,8 +2,9 @@
 // residual term, the step that moves one trace's bracket, and the host restatement of the whole search.  Plain C++ like
 // deconv_math.h, which it builds on: the same inline functions compile for the device kernels of csrc/deconv.hip, for the host entry
 // point dc_trace_deconv_ar1_constrained_host and into a stand-alone host program (tests/native/deconv_search_check.cpp, run under
-// the address / undefined-behaviour sanitizers).  The fold of the residual is the one of trace_dyn_math.h.  Defined bit for bit: no
-// fused multiply-add and no reassociation (the pragma below, and -ffp-contract=off for deconv.hip in _build.py).
+// the address / undefined-behaviour sanitizers).  The host forward pass is deconv_math.h's, the fold of the residual the one of
+// trace_dyn_math.h.  Defined bit for bit: no fused multiply-add and no reassociation (the pragma below, and -ffp-contract=off for
+// deconv.hip in _build.py).
 #pragma once
 #pragma clang fp contract(off)
 #include "deconv_math.h"
@@ -71,23 +72,6 @@ DC_DECONV_HD int32_t dc_search_status(const DcSearch& s) { return s.phase == DC_
 
 // ---- the host restatement: dc_trace_deconv_ar1_constrained_host and the stand-alone check ------------------------------------------
 // (host functions: no attribute)
-struct DcSearchHostStack {
-  std::vector<DcPool>* pools;
-  DcPool load(int32_t i) const { return (*pools)[(size_t)i]; }
-  void store(int32_t i, const DcPool& p) { (*pools)[(size_t)i] = p; }
-};
-
-// the forward pass of one trace of T >= 1 frames into pool[0 .. n); -> n
-template <typename In>
-inline int32_t dc_search_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, std::vector<DcPool>& pool) {
-  DcSearchHostStack st = {&pool};
-  DcPool top = dc_deconv_new(0.0, 0);
-  int32_t n = 0;
-  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, (double)y[t] - dc_deconv_mu(lam, g, t, T), t, G, smin);
-  st.store(n - 1, top);
-  return n;
-}
-
 // RSS of the stack pool[0 .. n): c is T doubles of scratch
 template <typename In>
 inline double dc_search_rss_host(const In* y, long T, const double* G, const std::vector<DcPool>& pool, int32_t n, double* c) {
@@ -105,7 +89,7 @@ inline void dc_search_host(const In* y, long T, double g, const double* G, int w
   DcSearch s = dc_search_begin(sigma, T);
   double p = 0.0;
   for (int round = 0; round <= rounds; ++round) {
-    const int32_t n = which == DC_SEARCH_LAM ? dc_search_forward_host(y, T, g, G, p, other, pool) : dc_search_forward_host(y, T, g, G, other, p, pool);
+    const int32_t n = which == DC_SEARCH_LAM ? dc_deconv_forward_host(y, T, g, G, p, other, pool) : dc_deconv_forward_host(y, T, g, G, other, p, pool);
     p = dc_search_step(s, p, dc_search_rss_host(y, T, G, pool, n, c));
   }
   *param = s.lo;

@@ -5,7 +5,7 @@
 //   the noise is two medians, found by VALUE with an 8-bit radix descent over a monotone 64-bit key of the double -- eight
 //     counting passes per order statistic over the trace (d and |d - m| are recomputed from y on every pass, so there is no
 //     workspace; the trace comes from L2 after the first), integer LDS atomics only, which are order-free;
-//   the fold is 256 lane sums (thread j takes t = j, j + 256, ...: coalesced) and a tree through LDS, in the header's order;
+//   the fold is 256 lane sums (thread j takes t = j, j + 256, ...: coalesced) and the header's tree through LDS (dc_dyn_fold_tree);
 //   for the autocovariance a tile of 256 frames plus `lags` halo is staged into LDS as centred doubles: the lags + 1 shifted
 //     reads of a thread are consecutive 8-byte words (lane l reads word l + shift: 32 lanes cover the 64 banks once), and every
 //     thread keeps its lags + 1 lane sums in registers.
@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "trace_dyn_math.h"
+#include "trace_matrix.h"
 
 namespace {
 
@@ -115,17 +116,6 @@ __device__ double noise_dev(const In* __restrict__ y, long T, SelectShared& sh) 
   return dc_dyn_sigma(median_dev(y, T - 1, true, m, sh));
 }
 
-// the tree of the fold over `rows` rows of 256 lane sums each; the results are red[row * 256]
-__device__ __forceinline__ void fold_tree(double* red, int rows) {
-  const int tid = threadIdx.x;
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    __syncthreads();
-    if (tid < h)
-      for (int l = 0; l < rows; ++l) red[l * kThreads + tid] = red[l * kThreads + tid] + red[l * kThreads + tid + h];
-  }
-  __syncthreads();
-}
-
 // Frames t >= T of a row (the padding up to ld) are never read.
 template <typename In>
 __global__ __launch_bounds__(kThreads) void trace_noise_kernel(const In* __restrict__ y, long ld, int R, long T, double* __restrict__ sigma) {
@@ -156,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void trace_ar1_estimate_kernel(const In* 
     double s = 0.0;
     for (long t = tid; t < T; t += kThreads) s = s + (double)row[t];
     red[tid] = s;
-    fold_tree(red, 1);
+    dc_dyn_fold_tree(red, 1);
     const double mean = red[0] / (double)T;
     // q_l = fold(t -> c[t] c[t + l], T - l), c = y - mean: lane sums in registers
     double acc[DC_DYN_MAX_LAGS + 1];
@@ -178,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void trace_ar1_estimate_kernel(const In* 
 #pragma unroll
     for (int l = 0; l <= DC_DYN_MAX_LAGS; ++l)
       if (l <= lags) red[l * kThreads + tid] = acc[l];
-    fold_tree(red, lags + 1);
+    dc_dyn_fold_tree(red, lags + 1);
     if (tid <= lags) {
       const double v = red[tid * kThreads] / (double)T;
       cov[tid] = v;
@@ -212,21 +202,17 @@ __global__ __launch_bounds__(kTabLanes) void ar1_tables_kernel(const double* __r
   }
 }
 
+// one matrix of traces: what every entry point that takes one refuses, in this order
 int check_traces(const char* who, const void* y, int is_f64, long ld, int R, long T) {
-  DC_REQUIRE(y, DC_EINVAL, "%s: null pointer", who);
-  DC_REQUIRE(is_f64 == 0 || is_f64 == 1, DC_EINVAL, "%s: is_f64 = %d is neither 0 nor 1", who, is_f64);
-  DC_REQUIRE(R >= 0 && T >= 0, DC_EINVAL, "%s: negative count (R %d, T %ld)", who, R, T);
-  DC_REQUIRE(ld >= T, DC_EINVAL, "%s: ld = %ld is below T = %ld", who, ld, T);
-  DC_REQUIRE((((uintptr_t)y) & (is_f64 ? 7 : 3)) == 0, DC_EINVAL, "%s: misaligned buffer", who);
-  DC_REQUIRE(T <= DC_TRACE_DECONV_MAX_FRAMES, DC_EUNSUP, "%s: T = %ld is over the limit of %ld frames", who, T, DC_TRACE_DECONV_MAX_FRAMES);
-  DC_REQUIRE((long)R * T <= DC_TRACE_DECONV_MAX_SAMPLES, DC_EUNSUP, "%s: R * T = %ld is over the limit of %ld samples", who, (long)R * T,
-             DC_TRACE_DECONV_MAX_SAMPLES);
-  return DC_OK;
+  const int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  DC_REQUIRE(dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
+  return dc_trace_check_limits(who, R, T);
 }
 
 int check_estimate(const char* who, int lags, const double* sn, const double* sigma, const double* xc, const double* g_raw) {
   DC_REQUIRE(xc && g_raw && (sn || sigma), DC_EINVAL, "%s: null pointer", who);
-  DC_REQUIRE((((uintptr_t)sn | (uintptr_t)sigma | (uintptr_t)xc | (uintptr_t)g_raw) & 7) == 0, DC_EINVAL, "%s: misaligned buffer", who);
+  DC_REQUIRE(dc_aligned(7, sn, sigma, xc, g_raw), DC_EINVAL, "%s: misaligned buffer", who);
   DC_REQUIRE(lags >= 1 && lags <= DC_TRACE_DYN_MAX_LAGS, DC_EINVAL, "%s: lags = %d is outside [1, %d]", who, lags, DC_TRACE_DYN_MAX_LAGS);
   return DC_OK;
 }
@@ -238,7 +224,7 @@ unsigned groups_for(int R) { return (unsigned)(R < kGridCap ? R : kGridCap); }
 extern "C" int dc_trace_noise(const void* y, int is_f64, long ld, int R, long T, double* sigma, dc_stream_t stream) {
   const char* who = "dc_trace_noise";
   DC_REQUIRE(sigma, DC_EINVAL, "%s: null pointer", who);
-  DC_REQUIRE((((uintptr_t)sigma) & 7) == 0, DC_EINVAL, "%s: misaligned buffer", who);
+  DC_REQUIRE(dc_aligned(7, sigma), DC_EINVAL, "%s: misaligned buffer", who);
   const int rc = check_traces(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   if (R == 0 || T == 0) return DC_OK;
@@ -271,12 +257,11 @@ extern "C" int dc_trace_ar1_estimate(const void* y, int is_f64, long ld, int R, 
 extern "C" int dc_ar1_tables(const double* g, int R, long T, double* G, long ldG, dc_stream_t stream) {
   const char* who = "dc_ar1_tables";
   DC_REQUIRE(g && G, DC_EINVAL, "%s: null pointer", who);
-  DC_REQUIRE((((uintptr_t)g | (uintptr_t)G) & 7) == 0, DC_EINVAL, "%s: misaligned buffer", who);
+  DC_REQUIRE(dc_aligned(7, g, G), DC_EINVAL, "%s: misaligned buffer", who);
   DC_REQUIRE(R >= 0 && T >= 0, DC_EINVAL, "%s: negative count (R %d, T %ld)", who, R, T);
   DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
-  DC_REQUIRE(T <= DC_TRACE_DECONV_MAX_FRAMES, DC_EUNSUP, "%s: T = %ld is over the limit of %ld frames", who, T, DC_TRACE_DECONV_MAX_FRAMES);
-  DC_REQUIRE((long)R * T <= DC_TRACE_DECONV_MAX_SAMPLES, DC_EUNSUP, "%s: R * T = %ld is over the limit of %ld samples", who, (long)R * T,
-             DC_TRACE_DECONV_MAX_SAMPLES);
+  const int rc = dc_trace_check_limits(who, R, T);
+  if (rc != DC_OK) return rc;
   if (R == 0) return DC_OK;                                          // T == 0 still has the entry G[r][0]
   const unsigned groups = (unsigned)(((long)R + kTabLanes - 1) / kTabLanes);                 // <= 2^25: no cap
   hipLaunchKernelGGL(ar1_tables_kernel, dim3(groups), dim3(kTabLanes), 0, (hipStream_t)stream, g, R, T, G, ldG);

@@ -66,7 +66,21 @@ DC_DYN_HD double dc_dyn_decay(const double* xc, int lags, double sn, long T) {
 #include <algorithm>
 #include <vector>
 
-// fold(f, n): 256 lane sums over t = j, j + 256, ... ascending, from +0.0; then the tree h = 128 .. 1, P[j] = P[j] + P[j + h]
+// fold(f, n): 256 lane sums over t = j, j + 256, ... ascending, from +0.0; then the tree h = 128 .. 1, P[j] = P[j] + P[j + h].
+// On the device (trace_dyn.hip, deconv.hip) thread j of a 256-thread workgroup forms lane sum j and dc_dyn_fold_tree is the tree:
+// `rows` folds at once, the lane sums of fold l at red[l * 256 + j] in LDS, its result at red[l * 256]; a barrier before every
+// step and one after the last.
+#if defined(__HIPCC__)
+__device__ __forceinline__ void dc_dyn_fold_tree(double* red, int rows) {
+  const int tid = threadIdx.x;
+  for (int h = DC_DYN_LANES / 2; h >= 1; h >>= 1) {
+    __syncthreads();
+    if (tid < h)
+      for (int l = 0; l < rows; ++l) red[l * DC_DYN_LANES + tid] = red[l * DC_DYN_LANES + tid] + red[l * DC_DYN_LANES + tid + h];
+  }
+  __syncthreads();
+}
+#endif
 template <class F>
 inline double dc_dyn_fold_host(F f, long n) {
   double P[DC_DYN_LANES];

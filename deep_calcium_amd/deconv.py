@@ -40,6 +40,8 @@ Importing this module needs neither torch nor the GPU; constructing a TraceDecon
 """
 import numpy as np
 
+from ._matrix import _MatrixStage, _check_matrix, _is_device_tensor
+
 KINDS = ('calcium', 'spikes', 'pools')
 SEARCH_KINDS = ('param', 'rss', 'target', 'status')       # of a constrained object only
 CONSTRAIN = {'s_min': 0, 'lam': 1}    # DC_TRACE_DECONV_SEARCH_SMIN, DC_TRACE_DECONV_SEARCH_LAM
@@ -147,27 +149,9 @@ def _per_trace_gamma(g, R):
     return np.ascontiguousarray(a)
 
 
-def _is_device_tensor(x):
-    return not isinstance(x, np.ndarray) and hasattr(x, 'is_cuda') and hasattr(x, 'data_ptr')
-
-
 def _check_traces(y):
     """(R, T) float32 or float64, numpy or a device tensor -> (R, T, is_f64); ValueError otherwise."""
-    if _is_device_tensor(y):
-        if not y.is_cuda or str(y.dtype) not in ('torch.float32', 'torch.float64') or y.dim() != 2:
-            raise ValueError('traces must be an (R, T) float32 or float64 tensor on the device, not %s %r' % (y.dtype, tuple(y.shape)))
-        if y.shape[1] > 1 and y.stride(1) != 1 or y.shape[0] > 1 and y.stride(0) < y.shape[1]:
-            raise ValueError('traces: the rows of a device tensor must be contiguous (strides %r)' % (tuple(y.stride()),))
-        f64 = str(y.dtype) == 'torch.float64'
-    elif isinstance(y, np.ndarray):
-        if y.ndim != 2 or y.dtype not in (np.float32, np.float64):
-            raise ValueError('traces must be an (R, T) float32 or float64 array, not %s %r' % (y.dtype, y.shape))
-        f64 = y.dtype == np.float64
-    else:
-        raise ValueError('traces must be a numpy array or a device tensor, not %s' % type(y).__name__)
-    R, T = int(y.shape[0]), int(y.shape[1])
-    if R < 1 or T < 1:
-        raise ValueError('traces are empty: %r' % ((R, T),))
+    R, T = _check_matrix(y, 'traces', ('float32', 'float64'))
     if T > MAX_FRAMES:
         raise ValueError('T = %d frames is over the limit of 2**24' % T)
     if R * T > MAX_SAMPLES:
@@ -176,12 +160,13 @@ def _check_traces(y):
         bad = np.flatnonzero(~np.isfinite(y).all(axis=1))
         if bad.size:
             raise ValueError('traces: row %d holds a value that is not finite' % int(bad[0]))
-    return R, T, f64
+    return R, T, str(y.dtype).endswith('float64')
 
 
-class TraceDeconvolver(object):
+class TraceDeconvolver(_MatrixStage):
     """Owns the device state of one deconvolution: the traces, the table G, the workspace of pools and the three results.  The
     kernels run at most once; result() only copies."""
+    _noun = 'deconvolution'
 
     def __init__(self, traces, g, s_min=0.0, lam=0.0, constrain=None, sigma=None, rounds=24, device=None):
         """traces: (R, T) float32 or float64, numpy (checked for non-finite values) or a tensor already on the device (read in
@@ -220,89 +205,60 @@ class TraceDeconvolver(object):
         table = None if self._each else ar1_table(self.g, T)
         self.n_traces, self.n_frames = R, T
 
-        import torch
-        from ._lib import lib
-        self._torch = torch
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('TraceDeconvolver needs a GPU (there is no CPU fallback)')
-        if device is not None:
-            dev = torch.device(device)
-        elif _is_device_tensor(traces):
-            dev = traces.device
-        else:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        self.device = dev
-        if _is_device_tensor(traces):
-            if traces.device != dev:
-                raise ValueError('traces are on %s, the deconvolution runs on %s' % (traces.device, dev))
-            y = traces
-        else:
-            y = torch.from_numpy(np.ascontiguousarray(traces)).to(dev)
-        self._y, self._f64 = y, f64
-        self._ld = int(y.stride(0)) if R > 1 else max(int(y.stride(0)), T)
-        self._G = torch.from_numpy(self.g if self._each else table).to(dev)       # per trace: the decays; the tables come in _run()
-        self._smin = torch.from_numpy(smin).to(dev)
-        self._lam = torch.from_numpy(lam).to(dev)
+        self._open(device, like=traces)
+        self._y, self._f64 = self._resident(traces, 'traces'), f64
+        self._ld = self._row_stride(self._y, T)
+        self._G = self._resident(self.g if self._each else table, 'g')         # per trace: the decays; the tables come in _decay()
+        self._smin = self._resident(smin, 's_min')
+        self._lam = self._resident(lam, 'lam')
         self._out = None
         if constrain is not None:
-            if _is_device_tensor(sigma) and sigma.device != dev:
-                raise ValueError('sigma is on %s, the deconvolution runs on %s' % (sigma.device, dev))
             # None: the trace noise, computed in _run() and never leaving the device
-            self._sigma = sigma if sigma is None or _is_device_tensor(sigma) else torch.from_numpy(sigma).to(dev)
+            self._sigma = sigma if sigma is None else self._resident(sigma, 'the values of sigma')
+
+    def _decay(self, stream):
+        """-> (g, gs, G, ldG) as the entry points take them: one decay and one table for all traces, or the decays and one table row
+        per trace, built here.  G is the tensor, not its pointer: the caller holds it until its launches are enqueued, then it goes
+        back to the allocator with the workspace."""
+        if not self._each:
+            return self.g, None, self._G, 0
+        R, T = self.n_traces, self.n_frames
+        tables = self._empty((R, T + 1), 'float64')
+        self.L.dc_ar1_tables(self._G.data_ptr(), R, T, tables.data_ptr(), T + 1, stream)
+        return 0.0, self._G.data_ptr(), tables, T + 1
 
     def _run(self):
-        if self._out is None:
-            torch, R, T = self._torch, self.n_traces, self.n_frames
-            with torch.cuda.device(self.device):
-                ws = torch.empty(self.L.dc_trace_deconv_ws_bytes(R, T) // 8, dtype=torch.float64, device=self.device)
-                c = torch.empty((R, T), dtype=torch.float64, device=self.device)
-                s = torch.empty((R, T), dtype=torch.float64, device=self.device)
-                n = torch.empty(R, dtype=torch.int32, device=self.device)
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                if self.constrain is not None:
-                    self._out = self._run_constrained(ws, c, s, n, stream)
-                    return self._out
-                if self._each:
-                    tables = torch.empty((R, T + 1), dtype=torch.float64, device=self.device)
-                    self.L.dc_ar1_tables(self._G.data_ptr(), R, T, tables.data_ptr(), T + 1, stream)
-                    self.L.dc_trace_deconv_ar1_each(self._y.data_ptr(), int(self._f64), self._ld, R, T, self._G.data_ptr(), tables.data_ptr(), T + 1,
-                                                    self._lam.data_ptr(), self._smin.data_ptr(), ws.data_ptr(), c.data_ptr(), s.data_ptr(),
-                                                    n.data_ptr(), stream)
-                    self._out = dict(calcium=c, spikes=s, pools=n)    # the tables go back to the allocator with the workspace
-                    return self._out
-                self.L.dc_trace_deconv_ar1(self._y.data_ptr(), int(self._f64), self._ld, R, T, self.g, self._G.data_ptr(), self._lam.data_ptr(),
-                                           self._smin.data_ptr(), ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(),
-                                           torch.cuda.current_stream(self.device).cuda_stream)
-            self._out = dict(calcium=c, spikes=s, pools=n)        # the workspace goes back to the allocator (stream-ordered)
-        return self._out
-
-    def _run_constrained(self, ws, c, s, n, stream):
-        """The whole search and the final pass, enqueued by one call: nothing is read back in between."""
-        torch, R, T, L = self._torch, self.n_traces, self.n_frames, self.L
-        y = self._y.data_ptr()
-        if self._sigma is None:
-            self._sigma = torch.empty(R, dtype=torch.float64, device=self.device)
-            L.dc_trace_noise(y, int(self._f64), self._ld, R, T, self._sigma.data_ptr(), stream)
-        state = torch.empty(L.dc_trace_deconv_search_state_bytes(R) // 8, dtype=torch.float64, device=self.device)
-        param = torch.empty(R, dtype=torch.float64, device=self.device)
-        rss = torch.empty(R, dtype=torch.float64, device=self.device)
-        status = torch.empty(R, dtype=torch.int32, device=self.device)
-        other = self._lam if self.constrain == 's_min' else self._smin
-        if self._each:
-            tables = torch.empty((R, T + 1), dtype=torch.float64, device=self.device)
-            L.dc_ar1_tables(self._G.data_ptr(), R, T, tables.data_ptr(), T + 1, stream)
-            g, gs, G, ldG = 0.0, self._G.data_ptr(), tables.data_ptr(), T + 1
-        else:
-            g, gs, G, ldG = self.g, None, self._G.data_ptr(), 0
-        L.dc_trace_deconv_ar1_constrained(y, int(self._f64), self._ld, R, T, g, gs, G, ldG, CONSTRAIN[self.constrain], self._sigma.data_ptr(),
-                                          other.data_ptr(), self.rounds, ws.data_ptr(), state.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(),
-                                          param.data_ptr(), rss.data_ptr(), status.data_ptr(), stream)
-        # plane 3 of the state holds the targets; the rest goes back to the allocator with the workspace
-        return dict(calcium=c, spikes=s, pools=n, param=param, rss=rss, status=status, target=state[3 * R:4 * R].clone())
+        """Everything is enqueued by one call, the whole search included: nothing is read back in between."""
+        if self._out is not None:
+            return self._out
+        R, T, L = self.n_traces, self.n_frames, self.L
+        ws = self._empty(L.dc_trace_deconv_ws_bytes(R, T) // 8, 'float64')     # it goes back to the allocator (stream-ordered)
+        c, s, n = self._empty((R, T), 'float64'), self._empty((R, T), 'float64'), self._empty(R, 'int32')
+        out = dict(calcium=c, spikes=s, pools=n)
+        y, f64 = self._y.data_ptr(), int(self._f64)
+        with self._torch.cuda.device(self.device):
+            stream = self._stream()
+            if self.constrain is not None and self._sigma is None:
+                self._sigma = self._empty(R, 'float64')
+                L.dc_trace_noise(y, f64, self._ld, R, T, self._sigma.data_ptr(), stream)
+            g, gs, G, ldG = self._decay(stream)
+            if self.constrain is not None:
+                state = self._empty(L.dc_trace_deconv_search_state_bytes(R) // 8, 'float64')
+                out.update(param=self._empty(R, 'float64'), rss=self._empty(R, 'float64'), status=self._empty(R, 'int32'))
+                other = self._lam if self.constrain == 's_min' else self._smin
+                L.dc_trace_deconv_ar1_constrained(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, CONSTRAIN[self.constrain],
+                                                  self._sigma.data_ptr(), other.data_ptr(), self.rounds, ws.data_ptr(), state.data_ptr(),
+                                                  c.data_ptr(), s.data_ptr(), n.data_ptr(), out['param'].data_ptr(), out['rss'].data_ptr(),
+                                                  out['status'].data_ptr(), stream)
+                out['target'] = state[3 * R:4 * R].clone()         # plane 3 of the state holds the targets
+            elif self._each:
+                L.dc_trace_deconv_ar1_each(y, f64, self._ld, R, T, gs, G.data_ptr(), ldG, self._lam.data_ptr(), self._smin.data_ptr(),
+                                           ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(), stream)
+            else:
+                L.dc_trace_deconv_ar1(y, f64, self._ld, R, T, g, G.data_ptr(), self._lam.data_ptr(), self._smin.data_ptr(), ws.data_ptr(),
+                                      c.data_ptr(), s.data_ptr(), n.data_ptr(), stream)
+        self._out = out
+        return out
 
     @property
     def sigma_device(self):
@@ -313,14 +269,11 @@ class TraceDeconvolver(object):
         return self._sigma
 
     def result_device(self, kind='spikes'):
-        """result(kind) as a tensor on the device (the object's own state: do not write to it)."""
+        """result(kind) as a tensor on the device (the object's own state: do not write to it): (R, T) float64 for 'calcium' and
+        'spikes', int32[R] for 'pools'; of a constrained object also float64[R] for 'param', 'rss' and 'target' and int32[R] for
+        'status'."""
         _check_kind(kind, self.constrain is not None)
         return self._run()[kind]
-
-    def result(self, kind='spikes'):
-        """(R, T) float64 for 'calcium' and 'spikes', int32[R] for 'pools'; of a constrained object also float64[R] for 'param',
-        'rss' and 'target' and int32[R] for 'status'."""
-        return self.result_device(kind).cpu().numpy()
 
 
 def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0, details=False, lags=5, g_min=0.05, g_max=0.998, **dff_kw):

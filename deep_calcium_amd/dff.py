@@ -26,6 +26,7 @@ Importing this module needs neither torch nor the GPU; constructing a TraceBasel
 """
 import numpy as np
 
+from ._matrix import _MatrixStage, _check_matrix, _is_device_tensor                # noqa: F401 (the last: importable from here as before)
 from ._reader import _read_recording
 from .traces import RoiTraceExtractor, _check_shape, _roi_pixels
 
@@ -171,33 +172,15 @@ def neuropil_rois(rois, shape, inner=2, outer=12):
 
 
 # ---- the device state ---------------------------------------------------------------------------------------------------------
-def _is_device_tensor(x):
-    return not isinstance(x, np.ndarray) and hasattr(x, 'is_cuda') and hasattr(x, 'data_ptr')
-
-
 def _check_sums(x, what, shape=None):
     """(R, T) int64, numpy or a device tensor -> its shape; ValueError otherwise."""
-    if _is_device_tensor(x):
-        if not x.is_cuda or str(x.dtype) != 'torch.int64' or x.dim() != 2:
-            raise ValueError('%s must be an (R, T) int64 tensor on the device, not %s %r' % (what, x.dtype, tuple(x.shape)))
-        if x.shape[1] > 1 and x.stride(1) != 1 or x.shape[0] > 1 and x.stride(0) < x.shape[1]:
-            raise ValueError('%s: the rows of a device tensor must be contiguous (strides %r)' % (what, tuple(x.stride())))
-    elif isinstance(x, np.ndarray):
-        if x.ndim != 2 or x.dtype != np.int64:
-            raise ValueError('%s must be an (R, T) int64 array, not %s %r' % (what, x.dtype, x.shape))
-    else:
-        raise ValueError('%s must be a numpy array or a device tensor, not %s' % (what, type(x).__name__))
-    got = (int(x.shape[0]), int(x.shape[1]))
-    if got[0] < 1 or got[1] < 1:
-        raise ValueError('%s is empty: %r' % (what, got))
-    if shape is not None and got != shape:
-        raise ValueError('%s is %r, the sums are %r' % (what, got, shape))
-    return got
+    return _check_matrix(x, what, ('int64',), shape)
 
 
-class TraceBaseline(object):
+class TraceBaseline(_MatrixStage):
     """Owns the device state of one recording's dF/F: the numerators N, their rolling-percentile baseline B and the float
     results.  Every kernel runs at most once; result() only copies."""
+    _noun = 'baseline'
 
     def __init__(self, sums, areas, window, percentile=8, offset=0, neuropil_sums=None, neuropil_areas=None, weight=0.7, device=None):
         """sums: (R, T) int64, numpy or a tensor already on the device (read in place).  areas: the R pixel counts.  window: the
@@ -240,47 +223,22 @@ class TraceBaseline(object):
         self.n_rois, self.n_frames = R, T
         self._den_host = coeff[3]
 
-        import torch
-        from ._lib import lib
-        self._torch = torch
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('TraceBaseline needs a GPU (there is no CPU fallback)')
-        on_device = _is_device_tensor(sums)
-        if device is not None:
-            dev = torch.device(device)
-        elif on_device:
-            dev = sums.device
-        else:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        self.device = dev
-
-        def resident(x, what):
-            if _is_device_tensor(x):
-                if x.device != dev:
-                    raise ValueError('%s are on %s, the baseline runs on %s' % (what, x.device, dev))
-                return x
-            return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        src = resident(sums, 'sums')
+        torch = self._open(device, like=sums)
+        dev = self.device
+        src = self._resident(sums, 'sums')
         if neuropil_sums is not None and (np_row >= 0).any():
-            src = torch.cat([src, resident(neuropil_sums, 'neuropil_sums')], 0)       # one matrix: np_row names rows >= R
+            src = torch.cat([src, self._resident(neuropil_sums, 'neuropil_sums')], 0)       # one matrix: np_row names rows >= R
         self._src = src
-        self._ld = int(src.stride(0)) if src.shape[0] > 1 else max(int(src.stride(0)), T)
+        self._ld = self._row_stride(src, T)
         self._np_row = torch.from_numpy(np_row).to(dev)
         self._ca, self._cb, self._cc, self._den = [torch.from_numpy(c).to(dev) for c in coeff[:4]]
         self._num = self._base = self._dff = None
 
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
-
     def _numerators(self):
         if self._num is None:
-            torch, R, T = self._torch, self.n_rois, self.n_frames
-            with torch.cuda.device(self.device):
-                num = torch.empty((R, T), dtype=torch.int64, device=self.device)
+            R, T = self.n_rois, self.n_frames
+            num = self._empty((R, T), 'int64')
+            with self._torch.cuda.device(self.device):
                 self.L.dc_trace_combine(self._src.data_ptr(), self._ld, self._np_row.data_ptr(), self._ca.data_ptr(), self._cb.data_ptr(),
                                         self._cc.data_ptr(), R, T, num.data_ptr(), self._stream())
             self._num = num
@@ -288,20 +246,19 @@ class TraceBaseline(object):
 
     def _baseline(self):
         if self._base is None:
-            torch, R, T = self._torch, self.n_rois, self.n_frames
+            R, T = self.n_rois, self.n_frames
             num = self._numerators()
-            with torch.cuda.device(self.device):
-                base = torch.empty((R, T), dtype=torch.int64, device=self.device)
-                dff = torch.empty((R, T), dtype=torch.float32, device=self.device)
+            base, dff = self._empty((R, T), 'int64'), self._empty((R, T), 'float32')
+            with self._torch.cuda.device(self.device):
                 self.L.dc_trace_baseline(num.data_ptr(), T, R, T, self.half, self.percentile, base.data_ptr(), dff.data_ptr(),
                                          self._stream())
             self._base, self._dff = base, dff
         return self._base, self._dff
 
     def _scaled(self, x):
-        torch, R, T = self._torch, self.n_rois, self.n_frames
-        with torch.cuda.device(self.device):
-            out = torch.empty((R, T), dtype=torch.float32, device=self.device)
+        R, T = self.n_rois, self.n_frames
+        out = self._empty((R, T), 'float32')
+        with self._torch.cuda.device(self.device):
             self.L.dc_trace_scale(x.data_ptr(), T, self._den.data_ptr(), R, T, out.data_ptr(), self._stream())
         return out
 
@@ -310,7 +267,8 @@ class TraceBaseline(object):
         return self._den_host.copy()
 
     def result_device(self, kind='dff'):
-        """result(kind) as a tensor on the device (int64 results are the object's own state: do not write to them)."""
+        """result(kind) as a tensor on the device (int64 results are the object's own state: do not write to them): (R, T), int64
+        for 'num' and 'baseline_sum', float32 for 'f', 'baseline' and 'dff'."""
         _check_kind(kind)
         if kind == 'num':
             return self._numerators()
@@ -318,10 +276,6 @@ class TraceBaseline(object):
             return self._scaled(self._numerators())
         base, dff = self._baseline()
         return base if kind == 'baseline_sum' else dff if kind == 'dff' else self._scaled(base)
-
-    def result(self, kind='dff'):
-        """(R, T): int64 for 'num' and 'baseline_sum', float32 for 'f', 'baseline' and 'dff'."""
-        return self.result_device(kind).cpu().numpy()
 
 
 def dff_traces_device(dspath, rois, window, percentile=8, kind='dff', neuropil=None, offset=0, source='series/raw', device=None,

@@ -25,7 +25,8 @@ Importing this module needs neither torch nor the GPU; constructing a TraceDynam
 """
 import numpy as np
 
-from .deconv import _check_gamma, _check_traces, _is_device_tensor, _per_trace
+from ._matrix import _MatrixStage
+from .deconv import _check_gamma, _check_traces, _per_trace
 
 KINDS = ('noise', 'autocov', 'g_raw')
 LANES = 256                           # DC_TRACE_DYN_LANES: the width of the fold
@@ -89,8 +90,9 @@ def pick_gamma(g_raw, g_min=0.05, g_max=0.998, fallback=None):
     return np.ascontiguousarray(g_each, dtype=np.float64), status, g_pool
 
 
-class TraceDynamics(object):
+class TraceDynamics(_MatrixStage):
     """Owns the device state of one estimate: the traces and the three results.  The kernel runs at most once; result() only copies."""
+    _noun = 'estimate'
 
     def __init__(self, traces, lags=5, sn=None, device=None):
         """traces: (R, T) float32 or float64, numpy (checked for non-finite values) or a tensor already on the device (read in
@@ -102,55 +104,29 @@ class TraceDynamics(object):
         sn = None if sn is None else _per_trace(sn, 'sn', R)
         self.n_traces, self.n_frames = R, T
 
-        import torch
-        from ._lib import lib
-        self._torch = torch
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('TraceDynamics needs a GPU (there is no CPU fallback)')
-        if device is not None:
-            dev = torch.device(device)
-        elif _is_device_tensor(traces):
-            dev = traces.device
-        else:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        self.device = dev
-        if _is_device_tensor(traces):
-            if traces.device != dev:
-                raise ValueError('traces are on %s, the estimate runs on %s' % (traces.device, dev))
-            y = traces
-        else:
-            y = torch.from_numpy(np.ascontiguousarray(traces)).to(dev)
-        self.traces_device = y                    # what a TraceDeconvolver can be given next: no second upload
+        self._open(device, like=traces)
+        self.traces_device = self._resident(traces, 'traces')      # what a TraceDeconvolver can be given next: no second upload
         self._f64 = f64
-        self._ld = int(y.stride(0)) if R > 1 else max(int(y.stride(0)), T)
-        self._sn = None if sn is None else torch.from_numpy(sn).to(dev)
+        self._ld = self._row_stride(self.traces_device, T)
+        self._sn = None if sn is None else self._resident(sn, 'sn')
         self._out = None
 
     def _run(self):
         if self._out is None:
-            torch, R, T = self._torch, self.n_traces, self.n_frames
-            with torch.cuda.device(self.device):
-                sigma = torch.empty(R, dtype=torch.float64, device=self.device)
-                xc = torch.empty((R, self.lags + 1), dtype=torch.float64, device=self.device)
-                g_raw = torch.empty(R, dtype=torch.float64, device=self.device)
+            R, T = self.n_traces, self.n_frames
+            sigma, xc, g_raw = self._empty(R, 'float64'), self._empty((R, self.lags + 1), 'float64'), self._empty(R, 'float64')
+            with self._torch.cuda.device(self.device):
                 self.L.dc_trace_ar1_estimate(self.traces_device.data_ptr(), int(self._f64), self._ld, R, T, self.lags,
                                              None if self._sn is None else self._sn.data_ptr(), sigma.data_ptr(), xc.data_ptr(),
-                                             g_raw.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+                                             g_raw.data_ptr(), self._stream())
             self._out = dict(noise=sigma, autocov=xc, g_raw=g_raw)
         return self._out
 
     def result_device(self, kind='g_raw'):
-        """result(kind) as a tensor on the device (the object's own state: do not write to it)."""
+        """result(kind) as a tensor on the device (the object's own state: do not write to it): float64, [R] for 'noise' and
+        'g_raw', (R, lags + 1) for 'autocov'."""
         _check_kind(kind)
         return self._run()[kind]
-
-    def result(self, kind='g_raw'):
-        """float64: [R] for 'noise' and 'g_raw', (R, lags + 1) for 'autocov'."""
-        return self.result_device(kind).cpu().numpy()
 
 
 def estimate_ar1_device(traces, lags=5, sn=None, g_min=0.05, g_max=0.998, fallback=None, device=None):

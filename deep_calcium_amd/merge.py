@@ -35,7 +35,8 @@ Importing this module needs neither torch nor the GPU; constructing a TracePairC
 """
 import numpy as np
 
-from .dff import _as_int, _check_areas, _check_sums, _dilate, _is_device_tensor
+from ._matrix import _MatrixStage
+from .dff import _as_int, _check_areas, _check_sums, _dilate
 from .footprints import MAX_FRAMES
 from .traces import MAX_VOLUME, _check_shape, _roi_pixels
 
@@ -133,9 +134,10 @@ def _check_range(T, areas, detrend_frames):
     return L, M
 
 
-class TracePairCorr(object):
+class TracePairCorr(_MatrixStage):
     """Owns the device state of the trace-pair correlation of one list of candidate pairs.  Every kernel runs at most once;
     result() only copies."""
+    _noun = 'pair correlation'
 
     def __init__(self, sums, areas, pairs, detrend_frames=None, device=None):
         """sums: (R, T) int64, numpy or a tensor already on the device (read in place: RoiTraceExtractor.sums_device()).  areas: the R
@@ -153,35 +155,11 @@ class TracePairCorr(object):
         self.seg_len, self.M = L, M
         self._pairs_host = pairs
 
-        import torch
-        from ._lib import lib
-        self._torch = torch
-        self.L = lib()
-        if not torch.cuda.is_available():
-            from ._lib import DcunetError
-            raise DcunetError('TracePairCorr needs a GPU (there is no CPU fallback)')
-        on_device = _is_device_tensor(sums)
-        if device is not None:
-            dev = torch.device(device)
-        elif on_device:
-            dev = sums.device
-        else:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        self.device = dev
-        if on_device:
-            if sums.device != dev:
-                raise ValueError('sums are on %s, the pair correlation runs on %s' % (sums.device, dev))
-            self._src = sums
-        else:
-            self._src = torch.from_numpy(np.ascontiguousarray(sums)).to(dev)
-        self._ld = int(self._src.stride(0)) if R > 1 else max(int(self._src.stride(0)), T)
-        self._pairs = torch.from_numpy(pairs).to(dev)
+        torch = self._open(device, like=sums)
+        self._src = self._resident(sums, 'sums')
+        self._ld = self._row_stride(self._src, T)
+        self._pairs = torch.from_numpy(pairs).to(self.device)
         self._num = self._corr = None
-
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
 
     def pairs(self):
         """The (P, 2) int32 pairs, in the order of the results."""
@@ -189,9 +167,8 @@ class TracePairCorr(object):
 
     def _numerators(self):
         if self._num is None:
-            torch = self._torch
-            with torch.cuda.device(self.device):
-                num = torch.empty((self.n_pairs, 6), dtype=torch.int64, device=self.device)
+            num = self._empty((self.n_pairs, 6), 'int64')
+            with self._torch.cuda.device(self.device):
                 if self.n_pairs:
                     self.L.dc_trace_pair_moments(self._src.data_ptr(), self._ld, self.n_rois, self.n_frames, self.seg_len,
                                                  self._pairs.data_ptr(), self.n_pairs, num.data_ptr(), self._stream())
@@ -206,9 +183,8 @@ class TracePairCorr(object):
         if kind == 'moments':
             return num
         if self._corr is None:
-            torch = self._torch
-            with torch.cuda.device(self.device):
-                corr = torch.empty((self.n_pairs,), dtype=torch.float32, device=self.device)
+            corr = self._empty((self.n_pairs,), 'float32')
+            with self._torch.cuda.device(self.device):
                 if self.n_pairs:
                     self.L.dc_trace_pair_corr(num.data_ptr(), self.n_pairs, corr.data_ptr(), self._stream())
             self._corr = corr

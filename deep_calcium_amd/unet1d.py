@@ -64,15 +64,9 @@ class UNet1DEngine(object):
         self.nfb, self.margin = nfb, margin
         self.plan = conv_plan(nfb)
 
-        import torch
-        from ._lib import DcunetError, lib
+        from ._reader import _open_device
+        torch, _, self.L, self.device = _open_device(device, 'UNet1DEngine')
         self._torch = torch
-        self.L = lib()
-        if not torch.cuda.is_available():
-            raise DcunetError('UNet1DEngine needs a GPU (there is no CPU fallback)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
 
         # one flat upload; every array starts on a 16-byte boundary (the kernels read kernels / scale / shift as float4)
         offs, n = [], 0

@@ -106,15 +106,9 @@ class UNet1DTrainEngine(object):
         self.plan = conv_plan(self.nfb)
         weights = initial_weights(self.nfb, conv_kernel_init, seed)
 
-        import torch
-        from ._lib import DcunetError, lib
+        from ._reader import _open_device
+        torch, _, self.L, self.device = _open_device(device, 'UNet1DTrainEngine')
         self._torch = torch
-        self.L = lib()
-        if not torch.cuda.is_available():
-            raise DcunetError('UNet1DTrainEngine needs a GPU (there is no CPU fallback)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
 
         # flat layout: trainable arrays first (Adam's range), the moving statistics behind; 16-byte aligned starts
         shapes = expected_shapes(self.nfb)

@@ -75,8 +75,8 @@ static void run_trace(const std::vector<In>& y, double g, int which, double sigm
   dc_search_host(y.data(), T, g, G.data(), which, sigma, other, rounds, pool, c.data(), &param, &rss, &status);
   const double target = dc_search_target(sigma, T);
   auto residual = [&](double p) {
-    const int32_t n = which == DC_SEARCH_LAM ? dc_search_forward_host(y.data(), T, g, G.data(), p, other, pool)
-                                             : dc_search_forward_host(y.data(), T, g, G.data(), other, p, pool);
+    const int32_t n = which == DC_SEARCH_LAM ? dc_deconv_forward_host(y.data(), T, g, G.data(), p, other, pool)
+                                             : dc_deconv_forward_host(y.data(), T, g, G.data(), other, p, pool);
     return dc_search_rss_host(y.data(), T, G.data(), pool, n, c.data());
   };
   const double r0 = residual(0.0), again = residual(param);
