@@ -33,8 +33,22 @@ gives
 
 Search s_min for events (spikes > 0) and lam for a denoised calcium: the L1 solution's spikes > 0 is a poor event detector.
 
-Not built: AR(2), optimising g by the residual, a baseline term (feed dF/F, whose baseline is 0); for the search: both
-parameters at once, a warm start, the closed-form lam update of OASIS, a joint search over g.
+A baseline: dF/F over a low rolling percentile sits about one noise sigma above zero in its quiet stretches, and the non-negative
+model pays for a constant with spurious spikes.  baseline= takes one constant per trace off the data inside the forward pass --
+given, or with 'fit' estimated on the device (the header's "A baseline in the deconvolution": a clamped Newton step on the mean
+residual, baseline_rounds of them at fixed parameters, or one a round inside the noise-constrained search).  calcium stays c,
+without the baseline: the fitted trace is c + baseline.
+
+    baseline  float64   b per trace: the values used (zeros without baseline=)
+
+    dec = TraceDeconvolver(dff_dev, g, constrain='s_min', baseline='fit')        # threshold and baseline found together: recommended
+    c, s, info = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau='auto', k='noise', baseline='fit', details=True)
+
+With a fixed threshold the fit is only as good as the threshold: one that is too high misses events, whose fluorescence is then
+absorbed into the baseline.
+
+Not built: AR(2), optimising g by the residual, a time-varying baseline; for the search: both parameters at once, a warm start,
+the closed-form lam update of OASIS, a joint search over g.
 
 Importing this module needs neither torch nor the GPU; constructing a TraceDeconvolver does (there is no CPU fallback).
 """
@@ -46,6 +60,7 @@ KINDS = ('calcium', 'spikes', 'pools')
 SEARCH_KINDS = ('param', 'rss', 'target', 'status')       # of a constrained object only
 CONSTRAIN = {'s_min': 0, 'lam': 1}    # DC_TRACE_DECONV_SEARCH_SMIN, DC_TRACE_DECONV_SEARCH_LAM
 MAX_ROUNDS = 64                       # DC_TRACE_DECONV_SEARCH_MAX_ROUNDS
+MAX_BASELINE_ROUNDS = 64              # DC_TRACE_DECONV_BASE_MAX_ROUNDS
 MAX_SIGMA = 2.0 ** 500
 MAX_FRAMES = 1 << 24                  # DC_TRACE_DECONV_MAX_FRAMES
 MAX_SAMPLES = 1 << 31                 # DC_TRACE_DECONV_MAX_SAMPLES
@@ -62,6 +77,38 @@ def _check_rounds(rounds):
     if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= MAX_ROUNDS:
         raise ValueError('rounds must be an integer in [1, %d], not %r' % (MAX_ROUNDS, rounds))
     return int(rounds)
+
+
+def _check_baseline(baseline, rounds, R, constrained):
+    """baseline= of TraceDeconvolver -> None (the default: no baseline at all), 'fit', a float64[R] array or a device tensor."""
+    if isinstance(baseline, str):
+        if baseline != 'fit':
+            raise ValueError("baseline must be a number, one value per trace or 'fit', not %r" % (baseline,))
+        if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= MAX_BASELINE_ROUNDS:
+            raise ValueError('baseline_rounds must be an integer in [1, %d], not %r' % (MAX_BASELINE_ROUNDS, rounds))
+        return 'fit'
+    if _is_device_tensor(baseline):
+        if not baseline.is_cuda or str(baseline.dtype) != 'torch.float64' or tuple(baseline.shape) != (R,) or not baseline.is_contiguous():
+            raise ValueError('baseline must be a contiguous float64 tensor of %d values on the device, not %s %r'
+                             % (R, baseline.dtype, tuple(baseline.shape)))
+    else:
+        try:
+            a = np.asarray(baseline, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("baseline must be a number, one value per trace or 'fit', not %r" % (baseline,))
+        if a.ndim == 0:
+            if float(a) == 0.0:
+                return None
+            a = np.full(R, float(a), np.float64)
+        if a.shape != (R,):
+            raise ValueError('baseline must be a scalar or one value per trace (%d), not shape %r' % (R, a.shape))
+        bad = np.flatnonzero(~np.isfinite(a))
+        if bad.size:
+            raise ValueError('baseline must be finite: trace %d has %r' % (int(bad[0]), float(a[bad[0]])))
+        baseline = np.ascontiguousarray(a)
+    if constrained:
+        raise ValueError("a given baseline cannot go with constrain=: the search fits it (baseline='fit') or has none")
+    return baseline
 
 
 def _check_sigma(sigma, R):
@@ -168,7 +215,7 @@ class TraceDeconvolver(_MatrixStage):
     kernels run at most once; result() only copies."""
     _noun = 'deconvolution'
 
-    def __init__(self, traces, g, s_min=0.0, lam=0.0, constrain=None, sigma=None, rounds=24, device=None):
+    def __init__(self, traces, g, s_min=0.0, lam=0.0, constrain=None, sigma=None, rounds=24, device=None, baseline=0.0, baseline_rounds=8):
         """traces: (R, T) float32 or float64, numpy (checked for non-finite values) or a tensor already on the device (read in
         place, never written; THE CALLER PROMISES FINITE VALUES).  g in (0, 1): a scalar -- one decay and one table for all traces
         -- or an array of one value per trace (e.g. pick_gamma's g_each): the tables are then built on the device, one row per
@@ -176,7 +223,10 @@ class TraceDeconvolver(_MatrixStage):
         constrain: None, or 's_min' / 'lam': that parameter is searched per trace (it must then be left at 0) in `rounds` rounds,
         [1, 64], against sigma: None -- the noise of every trace, computed on the device where the traces lie --, a scalar or one
         value per trace (finite, >= 0, below 2**500), numpy or a float64 tensor on the device (read in place; THE CALLER PROMISES
-        THAT RANGE)."""
+        THAT RANGE).  baseline: one constant per trace that leaves the data inside the forward pass -- a scalar, one value per
+        trace (finite), a float64 tensor on the device (read in place; THE CALLER PROMISES FINITE VALUES), or 'fit': estimated
+        per trace on the device from 0, by baseline_rounds steps in [1, 64] at the given s_min and lam, or, with constrain=,
+        by one step in every round of the search (baseline_rounds is then not used).  A given baseline cannot go with constrain=."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         R, T, f64 = _check_traces(traces)
         self._each = np.ndim(g) != 0
@@ -202,6 +252,9 @@ class TraceDeconvolver(_MatrixStage):
                                      % (R, sigma.dtype, tuple(sigma.shape)))
             elif sigma is not None:
                 sigma = _check_sigma(sigma, R)
+        self.baseline = _check_baseline(baseline, baseline_rounds, R, constrain is not None)
+        self._fit = isinstance(self.baseline, str)                     # 'fit'; otherwise None or the values given
+        self.baseline_rounds = int(baseline_rounds) if self._fit else None
         table = None if self._each else ar1_table(self.g, T)
         self.n_traces, self.n_frames = R, T
 
@@ -212,6 +265,7 @@ class TraceDeconvolver(_MatrixStage):
         self._smin = self._resident(smin, 's_min')
         self._lam = self._resident(lam, 'lam')
         self._out = None
+        self._base = None if self.baseline is None or self._fit else self._resident(self.baseline, 'the baselines')
         if constrain is not None:
             # None: the trace noise, computed in _run() and never leaving the device
             self._sigma = sigma if sigma is None else self._resident(sigma, 'the values of sigma')
@@ -242,7 +296,9 @@ class TraceDeconvolver(_MatrixStage):
                 self._sigma = self._empty(R, 'float64')
                 L.dc_trace_noise(y, f64, self._ld, R, T, self._sigma.data_ptr(), stream)
             g, gs, G, ldG = self._decay(stream)
-            if self.constrain is not None:
+            if self.baseline is not None:
+                self._run_baseline(out, ws, y, f64, g, gs, G, ldG, stream)
+            elif self.constrain is not None:
                 state = self._empty(L.dc_trace_deconv_search_state_bytes(R) // 8, 'float64')
                 out.update(param=self._empty(R, 'float64'), rss=self._empty(R, 'float64'), status=self._empty(R, 'int32'))
                 other = self._lam if self.constrain == 's_min' else self._smin
@@ -260,6 +316,31 @@ class TraceDeconvolver(_MatrixStage):
         self._out = out
         return out
 
+    def _run_baseline(self, out, ws, y, f64, g, gs, G, ldG, stream):
+        """The launches of an object with a baseline: given (forward and fill), fitted at fixed parameters, or searched jointly."""
+        R, T, L = self.n_traces, self.n_frames, self.L
+        c, s, n = out['calcium'], out['spikes'], out['pools']
+        if not self._fit:
+            L.dc_trace_deconv_ar1_base(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, self._lam.data_ptr(), self._smin.data_ptr(),
+                                       self._base.data_ptr(), ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(), stream)
+            out['baseline'] = self._base
+            return
+        with self._torch.cuda.device(self.device):
+            base = self._torch.zeros(R, dtype=self._torch.float64, device=self.device)      # b_0 = 0; the entry points write b here
+        out['baseline'] = base
+        if self.constrain is None:
+            L.dc_trace_deconv_ar1_fit_base(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, self._lam.data_ptr(), self._smin.data_ptr(),
+                                           self.baseline_rounds, ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(), base.data_ptr(), stream)
+            return
+        state = self._empty(L.dc_trace_deconv_base_state_bytes(R) // 8, 'float64')
+        out.update(param=self._empty(R, 'float64'), rss=self._empty(R, 'float64'), status=self._empty(R, 'int32'))
+        other = self._lam if self.constrain == 's_min' else self._smin
+        L.dc_trace_deconv_ar1_constrained_base(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, CONSTRAIN[self.constrain],
+                                               self._sigma.data_ptr(), other.data_ptr(), self.rounds, ws.data_ptr(), state.data_ptr(),
+                                               c.data_ptr(), s.data_ptr(), n.data_ptr(), out['param'].data_ptr(), base.data_ptr(),
+                                               out['rss'].data_ptr(), out['status'].data_ptr(), stream)
+        out['target'] = state[3 * R:4 * R].clone()             # plane 3 of the state holds the targets
+
     @property
     def sigma_device(self):
         """The noise a constrained object was held to, float64[R] on the device (computed there when none was given)."""
@@ -271,12 +352,19 @@ class TraceDeconvolver(_MatrixStage):
     def result_device(self, kind='spikes'):
         """result(kind) as a tensor on the device (the object's own state: do not write to it): (R, T) float64 for 'calcium' and
         'spikes', int32[R] for 'pools'; of a constrained object also float64[R] for 'param', 'rss' and 'target' and int32[R] for
-        'status'."""
+        'status'; float64[R] for 'baseline', the constants taken off the traces (zeros where none was asked for)."""
+        if kind == 'baseline':
+            out = self._run()
+            if 'baseline' not in out:
+                with self._torch.cuda.device(self.device):
+                    out['baseline'] = self._torch.zeros(self.n_traces, dtype=self._torch.float64, device=self.device)
+            return out['baseline']
         _check_kind(kind, self.constrain is not None)
         return self._run()[kind]
 
 
-def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0, details=False, lags=5, g_min=0.05, g_max=0.998, **dff_kw):
+def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0, details=False, lags=5, g_min=0.05, g_max=0.998, baseline=0.0,
+                             **dff_kw):
     """-> (calcium, spikes), float64 (R, T): the dF/F traces of `rois` over a dataset file (dff_traces_device(dspath, rois, window,
     **dff_kw)) deconvolved with s_min = k * sigma_hat per trace and the penalty lam.  tau: a number -- the decay time in seconds,
     g = ar1_gamma(tau, fps) --, 'auto' -- the decay is estimated per trace from the dF/F (deep_calcium_amd.dynamics: TraceDynamics
@@ -285,7 +373,11 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
     dict(g=the decay used, a float or float64[R] for 'each'; g_raw=, status=, pooled= what pick_gamma gave, None for a number;
     sigma=sigma_hat float64[R]).  k='noise': no k at all -- s_min is searched per trace so that the residual stays within the
     noise (TraceDeconvolver(constrain='s_min'), held to the same sigma_hat, which stays on the device); info then also has
-    s_min= the thresholds found, rss= their residuals and search_status= (0 bracketed, 1 s_min = 0, 2 never bracketed)."""
+    s_min= the thresholds found, rss= their residuals and search_status= (0 bracketed, 1 s_min = 0, 2 never bracketed).
+    baseline: TraceDeconvolver's -- a scalar, or 'fit': one constant per trace estimated on the device; info['baseline'] is
+    float64[R], the values used.  Recommended: k='noise' with baseline='fit' -- dF/F over a low percentile sits about one sigma
+    above zero when the cell is quiet, which the search alone pays for with spurious events.  With a numeric k the fit is only as
+    good as the threshold (one that is too high lets missed events lift the baseline)."""
     mode = tau if isinstance(tau, str) else None
     if mode is not None and mode not in ('auto', 'each'):
         raise ValueError("tau must be a number of seconds, 'auto' or 'each', not %r" % (tau,))
@@ -311,17 +403,20 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
     if np.ndim(lam) != 0:
         raise ValueError('lam must be a scalar here, not shape %r' % (np.shape(lam),))
     _per_trace(lam, 'lam', 1)
+    if not isinstance(baseline, str) and (_is_device_tensor(baseline) or np.ndim(baseline) != 0):
+        raise ValueError("baseline must be a scalar or 'fit' here, not %s" % type(baseline).__name__)
+    with_base = _check_baseline(baseline, 8, 1, search) is not None
     if dff_kw.get('kind', 'dff') != 'dff':
         raise ValueError('the deconvolution takes dF/F: kind = %r is not supported' % (dff_kw['kind'],))
     from .dff import dff_traces_device
     dff = dff_traces_device(dspath, rois, window, **dff_kw)
     if mode is None:
         if search:
-            dec = TraceDeconvolver(dff, g, lam=lam, constrain='s_min', device=dff_kw.get('device'))
+            dec = TraceDeconvolver(dff, g, lam=lam, constrain='s_min', device=dff_kw.get('device'), baseline=baseline)
             sigma = dec.sigma_device.cpu().numpy()
         else:
             sigma = trace_noise(dff)
-            dec = TraceDeconvolver(dff, g, s_min=k * sigma, lam=lam, device=dff_kw.get('device'))
+            dec = TraceDeconvolver(dff, g, s_min=k * sigma, lam=lam, device=dff_kw.get('device'), baseline=baseline)
         info = dict(g=g, g_raw=None, status=None, sigma=sigma, pooled=None)
     else:
         from .dynamics import TraceDynamics
@@ -330,10 +425,13 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
         g_each, status, g_pool = pick_gamma(g_raw, g_min, g_max)
         g = g_pool if mode == 'auto' else g_each
         if search:
-            dec = TraceDeconvolver(dyn.traces_device, g, lam=lam, constrain='s_min', sigma=dyn.result_device('noise'), device=dyn.device)
+            dec = TraceDeconvolver(dyn.traces_device, g, lam=lam, constrain='s_min', sigma=dyn.result_device('noise'), device=dyn.device,
+                                   baseline=baseline)
         else:
-            dec = TraceDeconvolver(dyn.traces_device, g, s_min=k * sigma, lam=lam, device=dyn.device)
+            dec = TraceDeconvolver(dyn.traces_device, g, s_min=k * sigma, lam=lam, device=dyn.device, baseline=baseline)
         info = dict(g=g, g_raw=g_raw, status=status, sigma=sigma, pooled=g_pool)
+    if with_base:
+        info['baseline'] = dec.result('baseline')
     if search:
         info.update(s_min=dec.result('param'), rss=dec.result('rss'), search_status=dec.result('status'))
     if details:

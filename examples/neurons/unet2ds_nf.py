@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve auto|each|TAU [--fps F] [--spike-k K | --spike-constrain s_min|lam]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve auto|each|TAU [--fps F] [--spike-k K | --spike-constrain s_min|lam] [--spike-baseline fit|VALUE]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -134,6 +134,16 @@ def _deconvolve_arg(text):
         raise argparse.ArgumentTypeError('expected auto, each or the decay time TAU in seconds, not %r' % text)
 
 
+def _baseline_arg(text):
+    """'fit' | a constant."""
+    if text == 'fit':
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected fit or a constant VALUE, not %r' % text)
+
+
 def _n_frames(dspath):
     from deep_calcium_amd.series import _open_series
     frames, close = _open_series(dspath, 'series/raw')
@@ -147,7 +157,7 @@ def _n_frames(dspath):
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
            bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None, weighted=None, overlap='keep', deconvolve=None,
-           fps=None, spike_k=3.0, spike_constrain=None):
+           fps=None, spike_k=3.0, spike_constrain=None, spike_baseline=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -199,7 +209,11 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     the decay is estimated from the dF/F itself, per trace, from its autocovariance (deep_calcium_amd.TraceDynamics, pick_gamma);
     'auto' deconvolves every trace with the pooled median, 'each' with the trace's own estimate.  spike_constrain='s_min' or 'lam':
     no spike_k -- that parameter is searched per trace on the GPU until the residual equals the noise (TraceDeconvolver(constrain=));
-    s_min is the one for events, lam gives a denoised calcium."""
+    s_min is the one for events, lam gives a denoised calcium.  spike_baseline='fit': one constant per trace is fitted inside the
+    deconvolution, on the GPU (TraceDeconvolver(baseline='fit')): dF/F over a low percentile sits about one sigma_hat above zero
+    when the cell is quiet, which costs spurious events; recommended together with spike_constrain, since with a spike_k that is
+    too high the missed events lift the fitted baseline.  spike_baseline=VALUE (not with spike_constrain): that constant is taken
+    off every trace."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -224,6 +238,14 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--spike-constrain needs --deconvolve')
     if spike_constrain not in (None, 's_min', 'lam'):
         raise ValueError('--spike-constrain takes s_min or lam, not %r' % (spike_constrain,))
+    if spike_baseline is not None and deconvolve is None:
+        raise ValueError('--spike-baseline needs --deconvolve')
+    if spike_baseline is not None and spike_baseline != 'fit':
+        if isinstance(spike_baseline, str) or not np.isfinite(spike_baseline):
+            raise ValueError('--spike-baseline takes fit or a finite constant, not %r' % (spike_baseline,))
+        if spike_constrain is not None:
+            raise ValueError('--spike-baseline VALUE cannot go with --spike-constrain: the search fits the baseline (fit) or has none')
+    base_kw = {} if spike_baseline is None else dict(baseline=spike_baseline)
     if deconvolve is not None and not spike_k >= 0:
         raise ValueError('--spike-k is the smallest spike in units of the trace noise, K >= 0, not %r' % (spike_k,))
     g = None if deconvolve is None or estimated else ar1_gamma(deconvolve, fps)
@@ -381,9 +403,9 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
             g_each, status, g_pool = pick_gamma(dyn.result('g_raw'))
             if spike_constrain is not None:
                 dec = TraceDeconvolver(dyn.traces_device, g_pool if deconvolve == 'auto' else g_each, constrain=spike_constrain,
-                                       sigma=dyn.result_device('noise'))
+                                       sigma=dyn.result_device('noise'), **base_kw)
             else:
-                dec = TraceDeconvolver(dyn.traces_device, g_pool if deconvolve == 'auto' else g_each, s_min=spike_k * sigma)
+                dec = TraceDeconvolver(dyn.traces_device, g_pool if deconvolve == 'auto' else g_each, s_min=spike_k * sigma, **base_kw)
             extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
             events = (extra['deconvolved'] > 0).sum(1)
             logger.info('%s: decay estimated from the traces (--deconvolve %s): pooled g = %.6f%s, per trace min / median / max = %.6f / %.6f / '
@@ -397,7 +419,8 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                             int(events.max())))
         elif g is not None:
             sigma = trace_noise(tr)
-            dec = TraceDeconvolver(tr, g, s_min=spike_k * sigma) if spike_constrain is None else TraceDeconvolver(tr, g, constrain=spike_constrain)
+            dec = (TraceDeconvolver(tr, g, s_min=spike_k * sigma, **base_kw) if spike_constrain is None else
+                   TraceDeconvolver(tr, g, constrain=spike_constrain, **base_kw))
             extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
             events = (extra['deconvolved'] > 0).sum(1)
             logger.info('%s: deconvolved with g = %.6f (tau %g s at %g frames/s), s_min = %g sigma_hat, median sigma_hat %.4g: '
@@ -411,6 +434,11 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                         'above was not used): %s / sigma_hat min / median / max = %.3g / %.3g / %.3g; status bracketed / zero / never bracketed = %d / %d / %d'
                         % (name, spike_constrain, spike_constrain, float(ratio.min()), float(np.median(ratio)), float(ratio.max()),
                            int((st == 0).sum()), int((st == 1).sum()), int((st == 2).sum())))
+        if extra is not None and spike_baseline is not None:
+            b = dec.result('baseline')
+            ratio = b[sigma > 0] / sigma[sigma > 0] if (sigma > 0).any() else np.zeros(1)
+            logger.info('%s: a baseline per trace in the deconvolution (--spike-baseline %s): baseline / sigma_hat min / median / max = '
+                        '%.3g / %.3g / %.3g' % (name, spike_baseline, float(ratio.min()), float(np.median(ratio)), float(ratio.max())))
         out = write_traces_dataset('%s/%s_traces.hdf5' % (model.cpdir, name), tr, name, extra=extra)
         logger.info('%s: %d traces of %d frames -> %s' % (name, tr.shape[0], tr.shape[1], out))
         logger.info('spikes: python examples/spikes/unet1d.py predict %s --model unet1d_model.hdf5' % out)
@@ -467,6 +495,9 @@ if __name__ == '__main__':
                         type=float, metavar='K', dest='spike_k')
     sp_trc.add_argument('--spike-constrain', help='with --deconvolve, instead of --spike-k: search s_min (for events) or lam (for a denoised calcium) '
                         'per trace until the residual equals the trace noise', default=None, choices=('s_min', 'lam'), dest='spike_constrain')
+    sp_trc.add_argument('--spike-baseline', help='with --deconvolve: fit one constant per trace inside the deconvolution (fit; recommended with '
+                        '--spike-constrain), or take VALUE off every trace (not with --spike-constrain)', default=None, type=_baseline_arg,
+                        metavar='fit|VALUE', dest='spike_baseline')
     sp_trc.add_argument('--refine', help='refine every ROI by its footprint map first: keep the pixels whose correlation with the trace is >= THR',
                         default=None, type=float, metavar='THR')
     sp_trc.add_argument('--halo', help='with --refine: how far beyond an ROI, in pixels, its footprint map reaches (0..16, default 2)', default=2,
@@ -505,6 +536,11 @@ if __name__ == '__main__':
             ap.error('--spike-constrain searches the threshold: not together with --spike-k')
         if args['deconvolve'] is None:
             ap.error('--spike-constrain needs --deconvolve')
+    if args['which'] == 'traces' and args['spike_baseline'] is not None:
+        if args['deconvolve'] is None:
+            ap.error('--spike-baseline needs --deconvolve')
+        if args['spike_baseline'] != 'fit' and args['spike_constrain'] is not None:
+            ap.error('--spike-baseline VALUE cannot go with --spike-constrain: the search fits the baseline (fit) or has none')
     if args['which'] == 'traces' and args['overlap'] != 'keep' and args['weighted'] is None:
         ap.error('--overlap needs --weighted')
     f = {'train': training, 'evaluate': evaluation, 'predict': prediction, 'traces': traces}[args.pop('which')]

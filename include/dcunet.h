@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 128
+#define DC_ABI_VERSION 129
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -838,8 +838,8 @@ int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float
  * taken from one table, the result is defined bit for bit, on the device and on the host.
  * Inputs
  *   y[r][t]  float32 or float64 rows of stride ld >= T (is_f64 = 0 / 1); float32 is widened to double exactly.  THE CALLER
- *            PROMISES FINITE VALUES (not checked on the device; the Python layer checks host arrays).  Feed dF/F: there is no
- *            baseline term.
+ *            PROMISES FINITE VALUES (not checked on the device; the Python layer checks host arrays).  Feed dF/F; a constant
+ *            baseline per trace can be given or fitted ("A baseline in the deconvolution" below).
  *   G[0..T]  double, T + 1 entries: G[0] = 1, G[l] = G[l-1] * g, built ONCE ON THE HOST by that loop of multiplications, never by
  *            pow().  g = G[1], 0 < g < 1.
  *   lam[r] >= 0, smin[r] >= 0: doubles per trace, the L1 penalty on the spikes and the smallest spike allowed.
@@ -853,7 +853,7 @@ int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float
  *   spikes[r][t0_i] = calcium[t0_i] - g * calcium[t0_i - 1] for every pool i >= 1, exactly +0.0 at every other frame, frame 0
  *     included.  Not clamped: with smin = 0 it can be below zero by rounding only.  An event is spikes > 0.
  *   pools[r]: int32, the final number of pools.
- * Not built: AR(2); optimising g by the residual; a baseline term; a wave-parallel segment merge (it would change the operation
+ * Not built: AR(2); optimising g by the residual; a time-varying baseline; a wave-parallel segment merge (it would change the operation
  * order and so the bits); integer-exact arithmetic (the pool values are not closed under any fixed-point format).
  *   dc_trace_deconv_ws_bytes: the workspace of dc_trace_deconv_ar1, 24 * R * T bytes (0 for an empty or unsupported shape).
  *   dc_trace_deconv_ar1: forward pass (one lane per trace, 64 traces per workgroup), then the fill (one thread per sample).  All
@@ -903,7 +903,52 @@ int dc_trace_scale(const long* x, long ld, const long* den, int R, long T, float
  *     decay for all traces (g = G[1]), one trace after the other on the calling thread; sigma and fixed_other are checked (-1).
  *     The speed baseline, and the bit-for-bit check against the oracle on a machine without a GPU.
  * Not built for the search: AR(2); both parameters at once; a warm start (every round is a full forward pass); the OASIS closed-
- * form update of lam (it would change the operation order); a joint search over g. */
+ * form update of lam (it would change the operation order); a joint search over g.
+ * A baseline in the deconvolution: one constant b = base[r] per trace, given or fitted.  dF/F over a low rolling percentile sits
+ * about one noise sigma above zero in its quiet stretches; the non-negative model has no term for a constant and pays for the
+ * offset with spurious spikes.  csrc/deconv_base_math.h is the one implementation.  base = double[R], finite.
+ *   forward pass: the pushed value is x = ((double)y[t] - b) - mu, in that order; z - 0.0 is z for every double, so b = 0 gives the
+ *     bits of the entry points above.  calcium stays c, without the baseline: the fitted trace is c + b.
+ *   for the stacks a forward pass at (p, b) left: d_t = ((double)y[t] - b) - calcium[t]; RSS = fold(d_t * d_t, T); S = fold(d_t, T);
+ *     A = fold(a_t, T) with a_t = +0.0 except at the first frame of a pool with v > 0, where, l the pool's length and g = G[1],
+ *     u = (1.0 - G[l]) / (1.0 - g), q = (1.0 - G[l] * G[l]) / (1.0 - g * g), a_t = (u * u) / q.  Within a pool v is the G-weighted
+ *     least-squares value, so for the current partition d(sum c)/db = -A and T - A is -T dphi/db of the mean residual phi = S / T.
+ *   baseline step: den = 1.0 - A / (double)T; if !(den > 0.25) den = 0.25; b' = b + (S / (double)T) / den.  A clamped Newton step on
+ *     phi(b) = 0, the stationarity condition in b of both the lam and the smin problem (the penalty does not involve b).
+ *   fit at fixed parameters, rounds = N in [1, DC_TRACE_DECONV_BASE_MAX_ROUNDS]: from b_0 = base on entry, N times a forward pass at
+ *     b and the step; then the forward pass and the fill at b_N, which base holds afterwards.  With a threshold that is too high
+ *     the missed events' fluorescence is absorbed into b: fit the baseline together with the noise-constrained search.
+ *   joint search (which, sigma, fixed_other, rounds = N as above; the state gains b, carried, and b_lo):
+ *     round 0: p = 0, b = b_0, r0 = RSS; no baseline step (at p = 0 the baseline is not identifiable).  !(r0 < target): status 1,
+ *       p* = 0, b* = b_0.  Otherwise lo = 0, b_lo = b_0, rss_lo = r0, hi = sigma, expanding.
+ *     rounds 1 .. N: p = expanding ? hi : 0.5 * (lo + hi).  Pass A at (p, b) gives S and A, hence b'.  Pass B at (p, b') gives
+ *       r = RSS.  r <= target: lo = p, b_lo = b', rss_lo = r, and hi = hi + hi while expanding.  Otherwise hi = p and the expansion
+ *       is over.  Either way b = b' is carried into the next round.
+ *     end: p* = lo, b* = b_lo, rss = rss_lo, statuses as above; one last forward pass and the fill at (p*, b*).
+ *     Promised: RSS(p*, b*) <= target for status 0 and 2, evaluated at exactly that pair (so it does not depend on b having
+ *       converged); the outputs are the bits dc_trace_deconv_ar1_base gives at (p*, b*); the bracket-width formula above.  NOT
+ *       promised: that b* is the exact minimiser, or (smin) that no larger threshold also satisfies the constraint.
+ *   dc_trace_deconv_ar1_base: forward pass and fill with the baseline base[r].  gs == NULL: one decay g (by value, = G[1]) and one
+ *     table; otherwise gs[r] and the row G + r * ldG, as in dc_trace_deconv_ar1_constrained.  THE CALLER PROMISES FINITE base.
+ *   dc_trace_deconv_ar1_fit_base: the fit: N forward passes, each followed by one launch of the residual kernel (DC_TRACE_DECONV_BASE_FIT),
+ *     then forward and fill; nothing is read back.  base is read (b_0) and written (b_N).
+ *   dc_trace_deconv_base_state_bytes: the state of dc_trace_deconv_ar1_constrained_base, 56 * R bytes (0 for R <= 0): the five
+ *     planes of the plain search, then b and b_lo; plane 3 holds the targets.
+ *   dc_trace_deconv_ar1_constrained_base: the joint search: 2 N + 2 forward passes, each but the last followed by one launch of the
+ *     residual kernel, then the fill; no host synchronisation, nothing read back.  base is read (b_0) and written (b*); param and
+ *     base are also the arrays the forward passes read.  Promises and codes as for dc_trace_deconv_ar1_constrained.
+ *   dc_trace_deconv_base_step: one launch of the residual kernel alone: RSS, S and A of the stacks in ws (pools[r] of them per
+ *     trace) at base[r] in one sweep -- one workgroup of 256 threads per trace, at most DC_TRACE_DECONV_SEARCH_MAX_GROUPS workgroups --,
+ *     then by mode: DC_TRACE_DECONV_BASE_FIT (0) base[r] = b' (state, param, rss and status may be NULL); _PASS_A (1) the same
+ *     for every search that is not finished, b kept in the state; _PASS_B (2) the step of the search, the next parameter to
+ *     param; _PASS_LAST (3) that step, then p*, b*, rss and status.  sums = NULL, or double[3][R]: the three folds.  ldG = 0: one
+ *     table for all traces; ldG >= T + 1: row r of G; g = G[1] of that table.  THE CALLER PROMISES that ws, pools, state, param and
+ *     base are those of one of the two calls above on the same y, R and T.  It is here to be timed by itself.
+ *   dc_trace_deconv_ar1_fit_base_host, dc_trace_deconv_ar1_constrained_base_host: the same arithmetic (the same headers) compiled
+ *     for the host, over HOST pointers, one trace after the other on the calling thread.  ldG = 0: one table for all traces,
+ *     otherwise row r of G; g = G[1] of the table.  What is read is checked (-1), a baseline that is not finite included.  The fit
+ *     also takes rounds = 0: the given baseline, the host twin of dc_trace_deconv_ar1_base.
+ * Not built for the baseline: a time-varying baseline; a joint search over g; AR(2). */
 #define DC_TRACE_DECONV_SEARCH_SMIN 0
 #define DC_TRACE_DECONV_SEARCH_LAM 1
 #define DC_TRACE_DECONV_SEARCH_MAX_ROUNDS 64
@@ -925,6 +970,29 @@ int dc_trace_deconv_search_step(const void* y, int is_f64, long ld, int R, long 
 int dc_trace_deconv_ar1_constrained_host(const void* y, int is_f64, long ld, int R, long T, const double* G, int which, const double* sigma,
                                          const double* fixed_other, int rounds, double* calcium, double* spikes, int* pools, double* param,
                                          double* rss, int* status);
+#define DC_TRACE_DECONV_BASE_MAX_ROUNDS 64
+#define DC_TRACE_DECONV_BASE_FIT 0
+#define DC_TRACE_DECONV_BASE_PASS_A 1
+#define DC_TRACE_DECONV_BASE_PASS_B 2
+#define DC_TRACE_DECONV_BASE_PASS_LAST 3
+long dc_trace_deconv_base_state_bytes(int R);
+int dc_trace_deconv_ar1_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
+                             const double* lam, const double* smin, const double* base, void* ws, double* calcium, double* spikes, int* pools,
+                             dc_stream_t stream);
+int dc_trace_deconv_ar1_fit_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
+                                 const double* lam, const double* smin, int rounds, void* ws, double* calcium, double* spikes, int* pools,
+                                 double* base, dc_stream_t stream);
+int dc_trace_deconv_ar1_constrained_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
+                                         long ldG, int which, const double* sigma, const double* fixed_other, int rounds, void* ws, void* state,
+                                         double* calcium, double* spikes, int* pools, double* param, double* base, double* rss, int* status,
+                                         dc_stream_t stream);
+int dc_trace_deconv_base_step(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws, const int* pools,
+                              int mode, void* state, double* param, double* base, double* rss, int* status, double* sums, dc_stream_t stream);
+int dc_trace_deconv_ar1_fit_base_host(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const double* lam,
+                                      const double* smin, int rounds, double* calcium, double* spikes, int* pools, double* base);
+int dc_trace_deconv_ar1_constrained_base_host(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, int which,
+                                              const double* sigma, const double* fixed_other, int rounds, double* calcium, double* spikes,
+                                              int* pools, double* param, double* base, double* rss, int* status);
 
 /* ---- Trace dynamics: noise and AR(1) decay -----------------------------------------------------------------------------------
  * The one parameter of the deconvolution above that had no data-driven default: the decay g, which depends on indicator,
