@@ -5,11 +5,13 @@
 // layout is the work: the traces are row-major, so a wave's lanes would read at stride ld; a tile of 64 traces x 64 frames is
 // staged through LDS with coalesced row reads instead and every lane then walks its own row of the tile.  The top pool stays in
 // registers; the pools below it lie in the caller's workspace as [depth][R] planes, so the lanes of a wave that stand at the
-// same depth touch one line.  The noise-constrained search (csrc/deconv_search_math.h) runs that forward pass once a round, with
-// the searched parameter in the device array the pass reads anyway, and between two passes one launch that folds the residual of
-// the stacks and moves every trace's bracket: nothing is read back.  Nothing here may be contracted or reassociated: the pragma of
+// same depth touch one line.  The noise-constrained search (csrc/deconv_search_math.h) and the fit of a baseline
+// (csrc/deconv_base_math.h) run that forward pass once or twice a round, with the searched parameter and the baseline in the device
+// arrays the pass reads anyway, and between two passes one launch of the sweep kernel, which folds the residual of the stacks and
+// moves every trace's bracket or baseline: nothing is read back.  Nothing here may be contracted or reassociated: the pragma of
 // deconv_math.h and the per-file flag in _build.py.
 #pragma clang fp contract(off)
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -24,31 +26,52 @@ const int kLanes = 64;                       // traces per workgroup: one wave, 
 const int kFrames = 64;                      // frames per staged tile
 const int kPitch = kFrames + 1;              // elements per tile row: lane l reads word l * 65 + k, one bank each (float), two (double)
 const int kFillThreads = 256;
-const int kSearchThreads = DC_DYN_LANES;     // the residual: one thread per lane of the fold
+const int kSearchThreads = DC_DYN_LANES;     // the sweep: one thread per lane of the fold
 const int kSearchMaxGroups = 8192;           // DC_TRACE_DECONV_SEARCH_MAX_GROUPS: beyond, a workgroup walks several traces
 
-// The workspace: three planes of R * T 8-byte words, pool i of trace r at word i * R + r of each.
-struct DeviceStack {
+// The workspace: three planes of R * T 8-byte words, pool i of trace r at word i * R + r of each.  Only the forward kernel stores.
+struct StackView {
   double* v;
   double* w;
   int2* tl;                                  // (t0, l)
-  long R, r;
-  __device__ __forceinline__ DcPool load(int32_t i) const {
-    const long at = (long)i * R + r;
+  long R;
+  __device__ __forceinline__ StackView(const double* ws, int R_, long T)
+      : v(const_cast<double*>(ws)), w(v + (long)R_ * T), tl(reinterpret_cast<int2*>(v + 2 * ((long)R_ * T))), R(R_) {}
+  __device__ __forceinline__ long at(int32_t i, long r) const { return (long)i * R + r; }
+  __device__ __forceinline__ DcPool load(int32_t i, long r) const {
     DcPool p;
-    p.v = v[at];
-    p.w = w[at];
-    const int2 x = tl[at];
+    p.v = v[at(i, r)];
+    p.w = w[at(i, r)];
+    const int2 x = tl[at(i, r)];
     p.t0 = x.x;
     p.l = x.y;
     return p;
   }
-  __device__ __forceinline__ void store(int32_t i, const DcPool& p) {
-    const long at = (long)i * R + r;
-    v[at] = p.v;
-    w[at] = p.w;
-    tl[at] = make_int2(p.t0, p.l);
+  __device__ __forceinline__ void store(int32_t i, long r, const DcPool& p) const {
+    v[at(i, r)] = p.v;
+    w[at(i, r)] = p.w;
+    tl[at(i, r)] = make_int2(p.t0, p.l);
   }
+  // The pool of trace r that holds frame t: the last whose start is <= t.  The starts ascend, so a bisection finds it; pool lo
+  // starts at or before t, pool hi + 1 (if any) after it.  t in the caller's own integer type: the comparison stays as wide as it
+  // was there.
+  template <typename Frame>
+  __device__ __forceinline__ int32_t pool_of(long r, int32_t lo, int32_t hi, Frame t) const {
+    while (lo < hi) {
+      const int32_t mid = lo + (hi - lo + 1) / 2;                    // lo < mid <= hi
+      if (tl[at(mid, r)].x <= t) lo = mid;
+      else hi = mid - 1;
+    }
+    return lo;
+  }
+};
+
+// the stack of one trace, as dc_deconv_push takes it
+struct DeviceStack {
+  StackView s;
+  long r;
+  __device__ __forceinline__ DcPool load(int32_t i) const { return s.load(i, r); }
+  __device__ __forceinline__ void store(int32_t i, const DcPool& p) { s.store(i, r, p); }
 };
 
 // One workgroup of one wave per 64 traces.  Rows r >= R and frames t >= T of a ragged tile are neither read nor written.
@@ -66,8 +89,7 @@ __global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __rest
   const long r = r0 + lane;
   const bool mine = r < R;
   const int rows = R - r0 < kLanes ? (int)(R - r0) : kLanes;
-  const long plane = (long)R * T;
-  DeviceStack st = {ws, ws + plane, reinterpret_cast<int2*>(ws + 2 * plane), (long)R, r};
+  DeviceStack st = {StackView(ws, R, T), r};
   const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
   const double g = Each ? (mine ? gs[r] : 0.5) : g_all;
   const double* __restrict__ G = Each && mine ? G_all + r * ldG : G_all;
@@ -97,48 +119,34 @@ __global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __rest
   }
 }
 
-// The pool of trace r that holds frame t: the last whose start is <= t.  The starts ascend, so a bisection finds it; pool lo starts
-// at or before t, pool hi + 1 (if any) after it.  t in the caller's own integer type: the comparison stays as wide as it was there.
-template <typename Frame>
-__device__ __forceinline__ int32_t pool_of(const int2* tl, long R, long r, int32_t lo, int32_t hi, Frame t) {
-  while (lo < hi) {
-    const int32_t mid = lo + (hi - lo + 1) / 2;                      // lo < mid <= hi
-    if (tl[(long)mid * R + r].x <= t) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // One thread per sample (r, t): pool_of over the trace's n pools.  Every output element is written, each by one product or one
 // multiply-subtract.
 template <bool Each>
 __global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double* __restrict__ ws, const int* __restrict__ pools, int R, long T,
                                                                   double g_all, const double* __restrict__ gs, const double* __restrict__ G_all,
                                                                   long ldG, double* __restrict__ calcium, double* __restrict__ spikes) {
-  const long plane = (long)R * T;
   const long idx = (long)blockIdx.x * kFillThreads + threadIdx.x;
-  if (idx >= plane) return;
+  if (idx >= (long)R * T) return;
   const long r = idx / T;
   const int32_t t = (int32_t)(idx - r * T);
   const double g = Each ? gs[r] : g_all;
   const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
-  const double* v = ws;
-  const int2* tl = reinterpret_cast<const int2*>(ws + 2 * plane);
-  const int32_t lo = pool_of(tl, R, r, 0, pools[r] - 1, t);
-  const int2 own = tl[(long)lo * R + r];
-  const int32_t k = t - own.x;
-  const double c = dc_deconv_calcium(v[(long)lo * R + r], G[k]);
+  const StackView st(ws, R, T);
+  const int32_t lo = st.pool_of(r, 0, pools[r] - 1, t);
+  const int32_t k = t - st.tl[st.at(lo, r)].x;
+  const double c = dc_deconv_calcium(st.v[st.at(lo, r)], G[k]);
   double s = 0.0;
   if (k == 0 && lo > 0) {
-    const long below = (long)(lo - 1) * R + r;
-    s = dc_deconv_spike(c, g, dc_deconv_calcium(v[below], G[tl[below].y - 1]));
+    const long below = st.at(lo - 1, r);
+    s = dc_deconv_spike(c, g, dc_deconv_calcium(st.v[below], G[st.tl[below].y - 1]));
   }
   calcium[idx] = c;
   spikes[idx] = s;
 }
 
-// ---- the noise-constrained search (csrc/deconv_search_math.h) ---------------------------------------------------------------------
-// The state of the searches: five planes of R 8-byte words -- lo, hi, rss_lo, target (doubles), phase (an integer).
+// ---- the sweep over the stacks: the noise-constrained search (csrc/deconv_search_math.h), the baseline (csrc/deconv_base_math.h) ----
+// The state of the searches: planes of R 8-byte words -- lo, hi, rss_lo, target (doubles), phase (an integer): five for the plain
+// search; the joint search has two more, b (carried) and b_lo.
 struct SearchState {
   double* w;
   long R;
@@ -158,123 +166,383 @@ struct SearchState {
     w[3 * R + r] = s.target;
     reinterpret_cast<long*>(w + 4 * R)[r] = s.phase;
   }
+  __device__ __forceinline__ DcBaseSearch load_joint(long r) const {
+    DcBaseSearch q;
+    q.s = load(r);
+    q.b = w[5 * R + r];
+    q.b_lo = w[6 * R + r];
+    return q;
+  }
+  __device__ __forceinline__ void store(long r, const DcBaseSearch& q) {
+    store(r, q.s);
+    w[5 * R + r] = q.b;
+    w[6 * R + r] = q.b_lo;
+  }
 };
 
-// one thread per trace: the state before round 0, and round 0's parameter
-__global__ __launch_bounds__(kSearchThreads) void deconv_search_begin_kernel(const double* __restrict__ sigma, int R, long T, double* state,
-                                                                             double* __restrict__ param) {
+// one thread per trace: the state before round 0 (Base: base holds b_0 and stays), and round 0's parameter
+template <bool Base>
+__global__ __launch_bounds__(kSearchThreads) void deconv_begin_kernel(const double* __restrict__ sigma, const double* __restrict__ base, int R,
+                                                                      long T, double* state, double* __restrict__ param) {
   const long r = (long)blockIdx.x * kSearchThreads + threadIdx.x;
   if (r >= R) return;
   SearchState st = {state, (long)R};
-  st.store(r, dc_search_begin(sigma[r], T));
+  if constexpr (Base) st.store(r, dc_base_search_begin(sigma[r], T, base[r]));
+  else st.store(r, dc_search_begin(sigma[r], T));
   param[r] = 0.0;
 }
 
-// The residual of the stacks the forward pass left in the workspace, then one step of the search.  One workgroup of 256 threads per
-// trace: thread j owns lane j of the fold, t = j, j + 256, ... (coalesced reads of y); the pool of t is found as the fill kernel
-// finds it (pool_of), from the pool of the thread's previous frame upwards and only when t has left that pool.  The tree through
-// LDS is dc_dyn_fold_tree of trace_dyn_math.h; thread 0 then moves the bracket and writes the parameter the next forward
-// pass reads (last: p*, RSS(p*) and the status instead).  Every word has one writer; frames t >= T of a row are never read.
-template <typename In, bool Each>
-__global__ __launch_bounds__(kSearchThreads) void deconv_residual_step_kernel(const In* __restrict__ y, long ld, int R, long T,
-                                                                              const double* __restrict__ G_all, long ldG,
-                                                                              const double* __restrict__ ws, const int* __restrict__ pools, int last,
-                                                                              double* state, double* param, double* __restrict__ rss,
-                                                                              int* __restrict__ status) {
-  __shared__ double red[kSearchThreads];
+// What thread 0 does with the folds of a trace, and where it writes: `mode` is DC_BASE_*; state, param, rss and status are not
+// touched in the mode DC_BASE_FIT; base belongs to the sweeps with a baseline; sums, where given, takes their three folds as planes
+// of R doubles.
+struct SweepOut {
+  int mode;
+  double* state;
+  double* param;
+  double* base;
+  double* rss;
+  int* status;
+  double* sums;
+};
+
+// The pool that holds the frame a thread of the sweep stands at: pool `at` of the trace, frames [start, end), of value val.  A
+// thread's frames ascend, so it seeks from its previous pool upwards, and only when a frame t >= end has left that pool.
+struct PoolCursor {
+  int32_t at = 0, start = 0, end = 0;        // no pool yet: frame 0 seeks
+  double val = 0.0;
+  __device__ __forceinline__ int32_t length() const { return end - start; }
+  __device__ __forceinline__ void seek(const StackView& st, long r, int32_t n, long t) {
+    at = st.pool_of(r, at, n - 1, t);
+    const int2 own = st.tl[st.at(at, r)];
+    start = own.x;
+    end = own.x + own.y;
+    val = st.v[st.at(at, r)];
+  }
+};
+
+// thread 0 of the plain search: one step on RSS(p); the bracket moves and the next parameter is written (the last pass: p*, RSS(p*)
+// and the status instead)
+__device__ __forceinline__ void search_tail(const SweepOut& o, long r, long R, double RSS) {
+  SearchState st = {o.state, R};
+  DcSearch q = st.load(r);
+  const double next = dc_search_step(q, o.param[r], RSS);
+  st.store(r, q);
+  if (o.mode == DC_BASE_PASS_LAST) {
+    o.param[r] = q.lo;
+    o.rss[r] = q.rss_lo;
+    o.status[r] = dc_search_status(q);
+  } else {
+    o.param[r] = next;
+  }
+}
+
+// thread 0 of the sweeps with a baseline b: the baseline step (DC_BASE_FIT; DC_BASE_PASS_A, which also keeps it in the state) or the
+// step of the joint search (DC_BASE_PASS_B; DC_BASE_PASS_LAST writes p*, b*, the residual and the status)
+__device__ __forceinline__ void base_tail(const SweepOut& o, long r, long R, long T, double b, double RSS, double S, double A) {
+  if (o.sums) {
+    o.sums[r] = RSS;
+    o.sums[R + r] = S;
+    o.sums[2 * R + r] = A;
+  }
+  if (o.mode == DC_BASE_FIT) {
+    o.base[r] = dc_base_step(b, S, A, T);
+    return;
+  }
+  SearchState st = {o.state, R};
+  DcBaseSearch x = st.load_joint(r);
+  if (o.mode == DC_BASE_PASS_A) {
+    o.base[r] = dc_base_search_newton(x, S, A, T);
+    st.store(r, x);
+    return;
+  }
+  const double next = dc_base_search_step(x, o.param[r], RSS);
+  st.store(r, x);
+  if (o.mode == DC_BASE_PASS_LAST) {
+    o.param[r] = x.s.lo;
+    o.base[r] = x.b_lo;
+    o.rss[r] = x.s.rss_lo;
+    o.status[r] = dc_search_status(x.s);
+  } else {
+    o.param[r] = next;
+  }
+}
+
+// The folds of the stacks the forward pass left in the workspace, then thread 0's turn.  One workgroup of 256 threads per trace (at
+// most 8192 workgroups: beyond, a workgroup walks several traces): thread j owns lane j of every fold, t = j, j + 256, ... (coalesced
+// reads of y), each lane sum s = s + term in ascending t from +0.0; the pool of t is found as the fill kernel finds it, through the
+// thread's PoolCursor.  Base = false folds the residual term of the plain search into red[256]; Base = true takes the baseline
+// base[r] off the data and folds RSS, S and A of deconv_base_math.h into red[3 * 256].  The tree through LDS is dc_dyn_fold_tree of
+// trace_dyn_math.h.  Its results red[0], red[256] and red[512] are thread 0's own words, and its last barrier frees the others for
+// the next trace; it also lies between every thread's read of base[r] and thread 0's write.  Every word has one writer; frames
+// t >= T of a row and rows r >= R are never read.
+template <typename In, bool Each, bool Base>
+__global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* __restrict__ y, long ld, int R, long T,
+                                                                      const double* __restrict__ G_all, long ldG,
+                                                                      const double* __restrict__ ws, const int* __restrict__ pools,
+                                                                      const SweepOut out) {
+  const int folds = Base ? 3 : 1;
+  __shared__ double red[folds * kSearchThreads];
   const int tid = threadIdx.x;
-  const long plane = (long)R * T;
-  const double* v = ws;
-  const int2* tl = reinterpret_cast<const int2*>(ws + 2 * plane);
+  const StackView st(ws, R, T);
   for (long r = blockIdx.x; r < R; r += gridDim.x) {
     const In* __restrict__ row = y + r * ld;
     const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
+    const double g = Base ? G[1] : 0.0;                              // T >= 1: the table has the entry
+    const double b = Base ? out.base[r] : 0.0;
     const int32_t n = pools[r];
-    int32_t at = 0, start = 0, end = 0;                              // the pool of the previous frame: [start, end); none yet
-    double val = 0.0;
-    double s = 0.0;
+    PoolCursor pool;
+    double Gl = 1.0;
+    double q = 0.0, s = 0.0, a = 0.0;
     for (long t = tid; t < T; t += kSearchThreads) {
-      if (t >= end) {
-        at = pool_of(tl, R, r, at, n - 1, t);
-        const int2 own = tl[(long)at * R + r];
-        start = own.x;
-        end = own.x + own.y;
-        val = v[(long)at * R + r];
+      if (t >= pool.end) {
+        pool.seek(st, r, n, t);
+        if constexpr (Base) Gl = G[pool.length()];
       }
-      s = s + dc_search_term((double)row[t], dc_deconv_calcium(val, G[t - start]));
-    }
-    red[tid] = s;
-    dc_dyn_fold_tree(red, 1);                                        // its last barrier frees red[1 ..] for the next trace
-    if (tid == 0) {                                                  // red[0] is thread 0's own: read here, written next after this
-      SearchState st = {state, (long)R};
-      DcSearch q = st.load(r);
-      const double next = dc_search_step(q, param[r], red[0]);
-      st.store(r, q);
-      if (last) {
-        param[r] = q.lo;
-        rss[r] = q.rss_lo;
-        status[r] = dc_search_status(q);
+      const double c = dc_deconv_calcium(pool.val, G[t - pool.start]);
+      if constexpr (Base) {
+        const double d = dc_base_resid((double)row[t], b, c);
+        q = q + d * d;
+        s = s + d;
+        a = a + dc_base_gain_at(pool.val, t, pool.start, g, Gl);
       } else {
-        param[r] = next;
+        q = q + dc_search_term((double)row[t], c);
       }
     }
-  }
-}
-
-template <typename In>
-void deconv_host_row(const In* y, long T, double g, const double* G, double lam, double smin, std::vector<DcPool>& pool, double* calcium,
-                     double* spikes, int* pools) {
-  const int32_t n = dc_deconv_forward_host(y, T, g, G, lam, smin, pool);
-  *pools = n;
-  for (int32_t i = 0; i < n; ++i) {
-    const DcPool& p = pool[(size_t)i];
-    for (int32_t k = 0; k < p.l; ++k) {
-      calcium[p.t0 + k] = dc_deconv_calcium(p.v, G[k]);
-      spikes[p.t0 + k] = 0.0;
+    red[tid] = q;
+    if constexpr (Base) {
+      red[kSearchThreads + tid] = s;
+      red[2 * kSearchThreads + tid] = a;
     }
-    if (i > 0) spikes[p.t0] = dc_deconv_spike(calcium[p.t0], g, calcium[p.t0 - 1]);
+    dc_dyn_fold_tree(red, folds);
+    if (tid == 0) {
+      if constexpr (Base) base_tail(out, r, R, T, b, red[0], red[kSearchThreads], red[2 * kSearchThreads]);
+      else search_tail(out, r, R, red[0]);
+    }
   }
 }
 
+// ---- the launches: the arguments have been checked -----------------------------------------------------------------------------------
+// What every launch of a call shares.  One decay g and one table G for all traces (gs == nullptr, ldG == 0), or the decays gs and
+// the table rows G + r * ldG; base == nullptr: no baseline, the kernels of the entry points that have none.
+struct Args {
+  const char* who;
+  const void* y;
+  int is_f64;
+  long ld;
+  int R;
+  long T;
+  double g;
+  const double *gs, *G;
+  long ldG;
+  const double *lam, *smin, *base;
+  void* ws;
+  int* pools;
+  dc_stream_t stream;
+};
+
+// a flag of the call as a template argument of its kernel: launch(std::true_type()) or launch(std::false_type())
+template <class F>
+void with_flag(bool flag, F launch) {
+  if (flag) launch(std::true_type());
+  else launch(std::false_type());
+}
+
+// In, Each and Base of the forward and sweep kernels from the call: launch(In(), each, base), the last two as with_flag gives them
+template <class F>
+void with_kernel_of(const Args& a, F launch) {
+  with_flag(a.ldG != 0, [&](auto each) {
+    with_flag(a.base != nullptr, [&](auto base) {
+      if (a.is_f64) launch(double(), each, base);
+      else launch(float(), each, base);
+    });
+  });
+}
+
+int launch_forward(const Args& a) {
+  const unsigned groups = (unsigned)(((long)a.R + kLanes - 1) / kLanes);                    // <= 2^25: no cap
+  with_kernel_of(a, [&](auto in, auto each, auto base) {
+    using In = decltype(in);
+    hipLaunchKernelGGL((deconv_forward_kernel<In, decltype(each)::value, decltype(base)::value>), dim3(groups), dim3(kLanes), 0, (hipStream_t)a.stream,
+                       (const In*)a.y, a.ld, a.R, a.T, a.g, a.gs, a.G, a.ldG, a.lam, a.smin, a.base, (double*)a.ws, a.pools);
+  });
+  DC_CHECK_LAUNCH(a.who);
+  return DC_OK;
+}
+
+// the forward pass, then the fill
+int launch_deconv(const Args& a, double* calcium, double* spikes) {
+  const int rc = launch_forward(a);
+  if (rc != DC_OK) return rc;
+  const unsigned blocks = (unsigned)(((long)a.R * a.T + kFillThreads - 1) / kFillThreads);  // <= 2^23: no cap
+  with_flag(a.ldG != 0, [&](auto each) {
+    hipLaunchKernelGGL(deconv_fill_kernel<decltype(each)::value>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)a.stream, (const double*)a.ws,
+                       a.pools, a.R, a.T, a.g, a.gs, a.G, a.ldG, calcium, spikes);
+  });
+  DC_CHECK_LAUNCH(a.who);
+  return DC_OK;
+}
+
+// the folds of the stacks in ws and what out.mode does with them
+int launch_sweep(const Args& a, const SweepOut& out) {
+  const unsigned groups = (unsigned)(a.R < kSearchMaxGroups ? a.R : kSearchMaxGroups);
+  with_kernel_of(a, [&](auto in, auto each, auto base) {
+    using In = decltype(in);
+    hipLaunchKernelGGL((deconv_sweep_kernel<In, decltype(each)::value, decltype(base)::value>), dim3(groups), dim3(kSearchThreads), 0,
+                       (hipStream_t)a.stream, (const In*)a.y, a.ld, a.R, a.T, a.G, a.ldG, (const double*)a.ws, a.pools, out);
+  });
+  DC_CHECK_LAUNCH(a.who);
+  return DC_OK;
+}
+
+// one pass: the forward pass, then the sweep over the stacks it left
+int launch_pass(const Args& a, const SweepOut& out) {
+  const int rc = launch_forward(a);
+  return rc != DC_OK ? rc : launch_sweep(a, out);
+}
+
+// `rounds` baseline steps, then the forward pass and the fill at b_N
+int launch_fit_base(const Args& a, int rounds, double* base, double* calcium, double* spikes) {
+  for (int round = 0; round < rounds; ++round) {
+    const int rc = launch_pass(a, {DC_BASE_FIT, nullptr, nullptr, base, nullptr, nullptr, nullptr});
+    if (rc != DC_OK) return rc;
+  }
+  return launch_deconv(a, calcium, spikes);
+}
+
+// The search: round 0, the rounds and the final pass.  out.param is the array the forward passes read the searched parameter from,
+// `other` the fixed one.  With a baseline to fit (a.base, which is out.base) a round is two passes: pass A, the baseline step at
+// (p, b), then pass B, the search step on RSS at (p, b').
+int launch_constrained(Args a, int which, const double* sigma, const double* other, int rounds, SweepOut out, double* calcium, double* spikes) {
+  a.lam = which == DC_SEARCH_LAM ? out.param : other;
+  a.smin = which == DC_SEARCH_LAM ? other : out.param;
+  const unsigned begin = (unsigned)(((long)a.R + kSearchThreads - 1) / kSearchThreads);
+  with_flag(a.base != nullptr, [&](auto base) {
+    hipLaunchKernelGGL(deconv_begin_kernel<decltype(base)::value>, dim3(begin), dim3(kSearchThreads), 0, (hipStream_t)a.stream, sigma, a.base, a.R,
+                       a.T, out.state, out.param);
+  });
+  DC_CHECK_LAUNCH(a.who);
+  for (int round = 0; round <= rounds; ++round) {
+    if (a.base && round > 0) {
+      out.mode = DC_BASE_PASS_A;
+      const int rc = launch_pass(a, out);
+      if (rc != DC_OK) return rc;
+    }
+    out.mode = round == rounds ? DC_BASE_PASS_LAST : DC_BASE_PASS_B;
+    const int rc = launch_pass(a, out);
+    if (rc != DC_OK) return rc;
+  }
+  return launch_deconv(a, calcium, spikes);
+}
+
+// ---- the checks the entry points share ----------------------------------------------------------------------------------------------
 int check_limits(const char* who, int R, long T, double g) {
   DC_REQUIRE(g > 0.0 && g < 1.0, DC_EINVAL, "%s: g = %g is outside (0, 1)", who, g);      // a NaN fails both comparisons
   return dc_trace_check_limits(who, R, T);
 }
 
-// the forward pass; the arguments have been checked
-template <bool Each, bool Base>
-int launch_forward_as(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
-                      const double* lam, const double* smin, const double* base, void* ws, int* pools, dc_stream_t stream) {
-  const unsigned groups = (unsigned)(((long)R + kLanes - 1) / kLanes);                      // <= 2^25: no cap
-  if (is_f64)
-    hipLaunchKernelGGL((deconv_forward_kernel<double, Each, Base>), dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const double*)y, ld, R, T,
-                       g, gs, G, ldG, lam, smin, base, (double*)ws, pools);
-  else
-    hipLaunchKernelGGL((deconv_forward_kernel<float, Each, Base>), dim3(groups), dim3(kLanes), 0, (hipStream_t)stream, (const float*)y, ld, R, T, g,
-                       gs, G, ldG, lam, smin, base, (double*)ws, pools);
-  DC_CHECK_LAUNCH(who);
+// what the device entry points with a decay per trace or one for all share
+int check_decay(const char* who, int R, long T, double g, const double* gs, long ldG) {
+  if (gs) DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
+  return check_limits(who, R, T, gs ? 0.5 : g);                      // per trace, the decays lie in device memory: THE CALLER PROMISES 0 < gs[r] < 1
+}
+
+// ldG of the entry points that take a table and no decay: 0, one table for all traces, or the stride of one row per trace
+int check_table_stride(const char* who, long ldG, long T) {
+  DC_REQUIRE(ldG == 0 || ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is neither 0 nor at least T + 1 = %ld", who, ldG, T + 1);
   return DC_OK;
 }
 
-// base == nullptr: no baseline, the kernel of the entry points that have none
-template <bool Each>
-int launch_forward(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
-                   const double* lam, const double* smin, const double* base, void* ws, int* pools, dc_stream_t stream) {
-  if (base) return launch_forward_as<Each, true>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, base, ws, pools, stream);
-  return launch_forward_as<Each, false>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, nullptr, ws, pools, stream);
+int check_search(const char* who, int which, int rounds) {
+  DC_REQUIRE(which == DC_SEARCH_SMIN || which == DC_SEARCH_LAM, DC_EINVAL, "%s: which = %d is neither 0 (smin) nor 1 (lam)", who, which);
+  DC_REQUIRE(rounds >= 1 && rounds <= DC_SEARCH_MAX_ROUNDS, DC_EINVAL, "%s: rounds = %d is outside [1, %d]", who, rounds, DC_SEARCH_MAX_ROUNDS);
+  return DC_OK;
 }
 
-// the forward pass, then the fill; the arguments have been checked
-template <bool Each>
-int launch_deconv(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
-                  const double* lam, const double* smin, const double* base, void* ws, double* calcium, double* spikes, int* pools,
-                  dc_stream_t stream) {
-  const int rc = launch_forward<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, base, ws, pools, stream);
-  if (rc != DC_OK) return rc;
-  const unsigned blocks = (unsigned)(((long)R * T + kFillThreads - 1) / kFillThreads);      // <= 2^23: no cap
-  hipLaunchKernelGGL(deconv_fill_kernel<Each>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)stream, (const double*)ws, pools, R, T, g, gs, G,
-                     ldG, calcium, spikes);
-  DC_CHECK_LAUNCH(who);
+// ---- the host entry points: one trace at a time through the host restatements of the three headers ----------------------------------
+// The ranges of what a host entry point reads per trace, trace by trace; an array the entry point does not take is nullptr (lam goes
+// with smin, sigma with other).
+int check_host_ranges(const char* who, int R, const double* lam, const double* smin, const double* sigma, const double* other, const double* base) {
+  for (int r = 0; r < R; ++r) {
+    if (lam) DC_REQUIRE(lam[r] >= 0.0 && smin[r] >= 0.0, DC_EINVAL, "%s: trace %d: lam = %g, smin = %g: neither may be negative", who, r, lam[r], smin[r]);
+    if (sigma) {
+      DC_REQUIRE(sigma[r] >= 0.0 && sigma[r] < 0x1p500, DC_EINVAL, "%s: trace %d: sigma = %g is outside [0, 2^500)", who, r, sigma[r]);
+      DC_REQUIRE(other[r] >= 0.0, DC_EINVAL, "%s: trace %d: the fixed parameter %g is negative", who, r, other[r]);
+    }
+    if (base) DC_REQUIRE(base[r] - base[r] == 0.0, DC_EINVAL, "%s: trace %d: the baseline %g is not finite", who, r, base[r]);
+  }
+  return DC_OK;
+}
+
+// the one table of the host entry points that take no ldG: it holds the decay; R, T >= 1
+int check_host_table(const char* who, int R, long T, const double* G) {
+  DC_REQUIRE(G[0] == 1.0, DC_EINVAL, "%s: G[0] = %g is not 1", who, G[0]);
+  return check_limits(who, R, T, G[1]);
+}
+
+// the decay and the table of trace r on the host: one table for all (ldG == 0) or row r; -> DC_OK where the row holds a decay
+int host_table(const char* who, const double* G, long ldG, int r, long T, const double** row, double* g) {
+  *row = G + (long)r * ldG;
+  DC_REQUIRE((*row)[0] == 1.0, DC_EINVAL, "%s: trace %d: G[0] = %g is not 1", who, r, (*row)[0]);
+  *g = (*row)[1];
+  DC_REQUIRE(*g > 0.0 && *g < 1.0, DC_EINVAL, "%s: trace %d: g = %g is outside (0, 1)", who, r, *g);
+  return DC_OK;
+}
+
+// one trace of a host entry point: its row, decay and table, and the scratch of the header functions (T pools, T doubles twice)
+template <typename Row>
+struct HostTrace {
+  int r;
+  Row y;                                     // const float* or const double*
+  double g;
+  const double* G;
+  std::vector<DcPool>& pool;
+  double* c;
+  double* a;
+};
+
+// what the outputs of a trace are computed at
+struct HostFit {
+  double lam, smin, b;
+};
+
+// after a search: p, the value found for the parameter `which`, beside the fixed one
+HostFit host_fit_found(int which, double p, double other, double b) {
+  if (which == DC_SEARCH_LAM) return {p, other, b};
+  return {other, p, b};
+}
+
+// calcium, spikes and the pool count of one trace at `at`
+template <typename Row>
+void host_row(const HostTrace<Row>& h, long T, const HostFit& at, double* calcium, double* spikes, int* pools) {
+  const int32_t n = dc_base_forward_host(h.y, T, h.g, h.G, at.lam, at.smin, at.b, h.pool);
+  *pools = n;
+  dc_deconv_calcium_host(h.pool, n, h.G, calcium);
+  for (long t = 0; t < T; ++t) spikes[t] = 0.0;
+  for (int32_t i = 1; i < n; ++i) {
+    const int32_t t0 = h.pool[(size_t)i].t0;
+    spikes[t0] = dc_deconv_spike(calcium[t0], h.g, calcium[t0 - 1]);
+  }
+}
+
+// The rows of a host entry point; R, T >= 1.  fit(h), a generic lambda, gets trace h.r with its row as the type it has, does what
+// the entry point does before the outputs and returns what they are computed at.
+template <class F>
+int host_rows(const char* who, const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, double* calcium, double* spikes,
+              int* pools, F fit) {
+  std::vector<DcPool> pool((size_t)T);
+  std::vector<double> scratch(2 * (size_t)T);
+  for (int r = 0; r < R; ++r) {
+    const double* row_G;
+    double g;
+    const int rc = host_table(who, G, ldG, r, T, &row_G, &g);
+    if (rc != DC_OK) return rc;
+    auto one = [&](auto row) {
+      const HostTrace<decltype(row)> h = {r, row, g, row_G, pool, scratch.data(), scratch.data() + T};
+      host_row(h, T, fit(h), calcium + (long)r * T, spikes + (long)r * T, pools + r);
+    };
+    if (is_f64) one((const double*)y + (long)r * ld);
+    else one((const float*)y + (long)r * ld);
+  }
   return DC_OK;
 }
 
@@ -291,11 +559,11 @@ extern "C" int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, lo
   DC_REQUIRE(G && lam && smin && ws && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
   int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
-  rc = check_limits(who, R, T, g);
+  rc = check_decay(who, R, T, g, nullptr, 0);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(dc_aligned(7, G, lam, smin, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_deconv<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, lam, smin, nullptr, ws, calcium, spikes, pools, stream);
+  return launch_deconv({who, y, is_f64, ld, R, T, g, nullptr, G, 0, lam, smin, nullptr, ws, pools, stream}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int R, long T, const double* g, const double* G, long ldG,
@@ -305,12 +573,11 @@ extern "C" int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int 
   DC_REQUIRE(g && G && lam && smin && ws && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
   int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
-  DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
-  rc = check_limits(who, R, T, 0.5);                                 // the decays lie in device memory: THE CALLER PROMISES 0 < g[r] < 1
+  rc = check_decay(who, R, T, 0.0, g, ldG);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(dc_aligned(7, g, G, lam, smin, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_deconv<true>(who, y, is_f64, ld, R, T, 0.0, g, G, ldG, lam, smin, nullptr, ws, calcium, spikes, pools, stream);
+  return launch_deconv({who, y, is_f64, ld, R, T, 0.0, g, G, ldG, lam, smin, nullptr, ws, pools, stream}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int R, long T, const double* G, const double* lam,
@@ -321,69 +588,14 @@ extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int 
   int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   if (R == 0 || T == 0) return DC_OK;                                // G is not read: without frames it need not hold g
-  DC_REQUIRE(G[0] == 1.0, DC_EINVAL, "%s: G[0] = %g is not 1", who, G[0]);
-  const double g = G[1];
-  rc = check_limits(who, R, T, g);
+  rc = check_host_table(who, R, T, G);
   if (rc != DC_OK) return rc;
-  for (int r = 0; r < R; ++r)
-    DC_REQUIRE(lam[r] >= 0.0 && smin[r] >= 0.0, DC_EINVAL, "%s: trace %d: lam = %g, smin = %g: neither may be negative", who, r, lam[r], smin[r]);
-  std::vector<DcPool> pool((size_t)T);
-  for (int r = 0; r < R; ++r) {
-    double* c = calcium + (long)r * T;
-    double* s = spikes + (long)r * T;
-    if (is_f64)
-      deconv_host_row((const double*)y + (long)r * ld, T, g, G, lam[r], smin[r], pool, c, s, pools + r);
-    else
-      deconv_host_row((const float*)y + (long)r * ld, T, g, G, lam[r], smin[r], pool, c, s, pools + r);
-  }
-  return DC_OK;
+  rc = check_host_ranges(who, R, lam, smin, nullptr, nullptr, nullptr);
+  if (rc != DC_OK) return rc;
+  return host_rows(who, y, is_f64, ld, R, T, G, 0, calcium, spikes, pools, [&](const auto& h) { return HostFit{lam[h.r], smin[h.r], 0.0}; });
 }
 
 // ---- the noise-constrained search --------------------------------------------------------------------------------------------------
-namespace {
-
-// the residual of the stacks in ws and one step of every search; the arguments have been checked
-template <bool Each>
-int launch_residual_step(const char* who, const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws,
-                         const int* pools, int last, void* state, double* param, double* rss, int* status, dc_stream_t stream) {
-  const unsigned groups = (unsigned)(R < kSearchMaxGroups ? R : kSearchMaxGroups);
-  if (is_f64)
-    hipLaunchKernelGGL((deconv_residual_step_kernel<double, Each>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)stream, (const double*)y, ld,
-                       R, T, G, ldG, (const double*)ws, pools, last, (double*)state, param, rss, status);
-  else
-    hipLaunchKernelGGL((deconv_residual_step_kernel<float, Each>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)stream, (const float*)y, ld, R,
-                       T, G, ldG, (const double*)ws, pools, last, (double*)state, param, rss, status);
-  DC_CHECK_LAUNCH(who);
-  return DC_OK;
-}
-
-// round 0, the rounds and the final pass; the arguments have been checked
-template <bool Each>
-int launch_constrained(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
-                       int which, const double* sigma, const double* other, int rounds, void* ws, void* state, double* calcium, double* spikes,
-                       int* pools, double* param, double* rss, int* status, dc_stream_t stream) {
-  const double* lam = which == DC_SEARCH_LAM ? param : other;
-  const double* smin = which == DC_SEARCH_LAM ? other : param;
-  const unsigned begin = (unsigned)(((long)R + kSearchThreads - 1) / kSearchThreads);
-  hipLaunchKernelGGL(deconv_search_begin_kernel, dim3(begin), dim3(kSearchThreads), 0, (hipStream_t)stream, sigma, R, T, (double*)state, param);
-  DC_CHECK_LAUNCH(who);
-  for (int round = 0; round <= rounds; ++round) {
-    int rc = launch_forward<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, nullptr, ws, pools, stream);
-    if (rc != DC_OK) return rc;
-    rc = launch_residual_step<Each>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, round == rounds, state, param, rss, status, stream);
-    if (rc != DC_OK) return rc;
-  }
-  return launch_deconv<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, nullptr, ws, calcium, spikes, pools, stream);
-}
-
-int check_search(const char* who, int which, int rounds) {
-  DC_REQUIRE(which == DC_SEARCH_SMIN || which == DC_SEARCH_LAM, DC_EINVAL, "%s: which = %d is neither 0 (smin) nor 1 (lam)", who, which);
-  DC_REQUIRE(rounds >= 1 && rounds <= DC_SEARCH_MAX_ROUNDS, DC_EINVAL, "%s: rounds = %d is outside [1, %d]", who, rounds, DC_SEARCH_MAX_ROUNDS);
-  return DC_OK;
-}
-
-}  // namespace
-
 extern "C" long dc_trace_deconv_search_state_bytes(int R) { return R <= 0 ? 0 : 40L * R; }
 
 extern "C" int dc_trace_deconv_ar1_constrained(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
@@ -396,18 +608,14 @@ extern "C" int dc_trace_deconv_ar1_constrained(const void* y, int is_f64, long l
   if (rc != DC_OK) return rc;
   rc = check_search(who, which, rounds);
   if (rc != DC_OK) return rc;
-  if (gs) DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
-  rc = check_limits(who, R, T, gs ? 0.5 : g);                        // per trace, the decays lie in device memory: THE CALLER PROMISES 0 < gs[r] < 1
+  rc = check_decay(who, R, T, g, gs, ldG);
   if (rc != DC_OK) return rc;                                        // sigma, fixed_other likewise: THE CALLER PROMISES 0 <= sigma[r] < 2^500, finite, and fixed_other[r] >= 0
   DC_REQUIRE(dc_aligned(7, gs, G, sigma, fixed_other, ws, state, calcium, spikes, param, rss) && dc_aligned(3, pools, status) &&
                  dc_trace_aligned(y, is_f64),
              DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  if (gs)
-    return launch_constrained<true>(who, y, is_f64, ld, R, T, 0.0, gs, G, ldG, which, sigma, fixed_other, rounds, ws, state, calcium, spikes, pools,
-                                    param, rss, status, stream);
-  return launch_constrained<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, which, sigma, fixed_other, rounds, ws, state, calcium, spikes, pools,
-                                   param, rss, status, stream);
+  return launch_constrained({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, nullptr, nullptr, nullptr, ws, pools, stream}, which, sigma, fixed_other,
+                            rounds, {0, (double*)state, param, nullptr, rss, status, nullptr}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_search_step(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws,
@@ -418,13 +626,15 @@ extern "C" int dc_trace_deconv_search_step(const void* y, int is_f64, long ld, i
   int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(last == 0 || last == 1, DC_EINVAL, "%s: last = %d is neither 0 nor 1", who, last);
-  DC_REQUIRE(ldG == 0 || ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is neither 0 nor at least T + 1 = %ld", who, ldG, T + 1);
-  rc = check_limits(who, R, T, 0.5);
+  rc = check_table_stride(who, ldG, T);
+  if (rc != DC_OK) return rc;
+  rc = dc_trace_check_limits(who, R, T);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(dc_aligned(7, G, ws, state, param, rss) && dc_aligned(3, pools, status) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  if (ldG) return launch_residual_step<true>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, last, state, param, rss, status, stream);
-  return launch_residual_step<false>(who, y, is_f64, ld, R, T, G, 0, ws, pools, last, state, param, rss, status, stream);
+  // the sweep only reads ws and pools
+  return launch_sweep({who, y, is_f64, ld, R, T, 0.0, nullptr, G, ldG, nullptr, nullptr, nullptr, const_cast<void*>(ws), const_cast<int*>(pools), stream},
+                      {last ? DC_BASE_PASS_LAST : DC_BASE_PASS_B, (double*)state, param, nullptr, rss, status, nullptr});
 }
 
 extern "C" int dc_trace_deconv_ar1_constrained_host(const void* y, int is_f64, long ld, int R, long T, const double* G, int which,
@@ -439,234 +649,18 @@ extern "C" int dc_trace_deconv_ar1_constrained_host(const void* y, int is_f64, l
   rc = check_search(who, which, rounds);
   if (rc != DC_OK) return rc;
   if (R == 0 || T == 0) return DC_OK;                                // G is not read: without frames it need not hold g
-  DC_REQUIRE(G[0] == 1.0, DC_EINVAL, "%s: G[0] = %g is not 1", who, G[0]);
-  const double g = G[1];
-  rc = check_limits(who, R, T, g);
+  rc = check_host_table(who, R, T, G);
   if (rc != DC_OK) return rc;
-  for (int r = 0; r < R; ++r) {
-    DC_REQUIRE(sigma[r] >= 0.0 && sigma[r] < 0x1p500, DC_EINVAL, "%s: trace %d: sigma = %g is outside [0, 2^500)", who, r, sigma[r]);
-    DC_REQUIRE(fixed_other[r] >= 0.0, DC_EINVAL, "%s: trace %d: the fixed parameter %g is negative", who, r, fixed_other[r]);
-  }
-  std::vector<DcPool> pool((size_t)T);
-  std::vector<double> scratch((size_t)T);
-  for (int r = 0; r < R; ++r) {
-    double* c = calcium + (long)r * T;
-    double* s = spikes + (long)r * T;
-    if (is_f64) {
-      const double* row = (const double*)y + (long)r * ld;
-      dc_search_host(row, T, g, G, which, sigma[r], fixed_other[r], rounds, pool, scratch.data(), param + r, rss + r, status + r);
-      deconv_host_row(row, T, g, G, which == DC_SEARCH_LAM ? param[r] : fixed_other[r], which == DC_SEARCH_LAM ? fixed_other[r] : param[r], pool, c, s,
-                      pools + r);
-    } else {
-      const float* row = (const float*)y + (long)r * ld;
-      dc_search_host(row, T, g, G, which, sigma[r], fixed_other[r], rounds, pool, scratch.data(), param + r, rss + r, status + r);
-      deconv_host_row(row, T, g, G, which == DC_SEARCH_LAM ? param[r] : fixed_other[r], which == DC_SEARCH_LAM ? fixed_other[r] : param[r], pool, c, s,
-                      pools + r);
-    }
-  }
-  return DC_OK;
+  rc = check_host_ranges(who, R, nullptr, nullptr, sigma, fixed_other, nullptr);
+  if (rc != DC_OK) return rc;
+  return host_rows(who, y, is_f64, ld, R, T, G, 0, calcium, spikes, pools, [&](const auto& h) {
+    const int r = h.r;
+    dc_search_host(h.y, T, h.g, h.G, which, sigma[r], fixed_other[r], rounds, h.pool, h.c, param + r, rss + r, status + r);
+    return host_fit_found(which, param[r], fixed_other[r], 0.0);
+  });
 }
 
 // ---- a baseline in the deconvolution (csrc/deconv_base_math.h) -----------------------------------------------------------------------
-namespace {
-
-// The state of the joint searches: seven planes of R 8-byte words -- the five of SearchState, then b (carried) and b_lo.
-struct BaseSearchState {
-  double* w;
-  long R;
-  __device__ __forceinline__ DcBaseSearch load(long r) const {
-    SearchState st = {w, R};
-    DcBaseSearch q;
-    q.s = st.load(r);
-    q.b = w[5 * R + r];
-    q.b_lo = w[6 * R + r];
-    return q;
-  }
-  __device__ __forceinline__ void store(long r, const DcBaseSearch& q) {
-    SearchState st = {w, R};
-    st.store(r, q.s);
-    w[5 * R + r] = q.b;
-    w[6 * R + r] = q.b_lo;
-  }
-};
-
-// one thread per trace: the state before round 0 (base holds b_0 and stays), and round 0's parameter
-__global__ __launch_bounds__(kSearchThreads) void deconv_base_begin_kernel(const double* __restrict__ sigma, const double* __restrict__ base, int R,
-                                                                           long T, double* state, double* __restrict__ param) {
-  const long r = (long)blockIdx.x * kSearchThreads + threadIdx.x;
-  if (r >= R) return;
-  BaseSearchState st = {state, (long)R};
-  st.store(r, dc_base_search_begin(sigma[r], T, base[r]));
-  param[r] = 0.0;
-}
-
-// The three folds of the stacks the forward pass left in the workspace at the baseline base[r] -- RSS, S and A of
-// deconv_base_math.h, in one sweep shaped like deconv_residual_step_kernel's: thread j owns lane j of each fold, t = j, j + 256, ...;
-// the pool of t is looked up (pool_of) only when t has left the pool of the thread's previous frame.  The tree runs over the three
-// folds at once (dc_dyn_fold_tree, rows = 3); its results red[0], red[256] and red[512] are thread 0's own words.  Thread 0 then does
-// what `mode` says: the baseline step (DC_BASE_FIT; DC_BASE_PASS_A, which also keeps it in the state) or the step of the search
-// (DC_BASE_PASS_B; DC_BASE_PASS_LAST writes p*, b*, the residual and the status).  sums, where given, takes the three folds as planes
-// of R doubles.  Every word has one writer; frames t >= T of a row are never read.
-template <typename In, bool Each>
-__global__ __launch_bounds__(kSearchThreads) void deconv_base_step_kernel(const In* __restrict__ y, long ld, int R, long T,
-                                                                          const double* __restrict__ G_all, long ldG,
-                                                                          const double* __restrict__ ws, const int* __restrict__ pools, int mode,
-                                                                          double* state, double* param, double* base, double* __restrict__ rss,
-                                                                          int* __restrict__ status, double* __restrict__ sums) {
-  __shared__ double red[3 * kSearchThreads];
-  const int tid = threadIdx.x;
-  const long plane = (long)R * T;
-  const double* v = ws;
-  const int2* tl = reinterpret_cast<const int2*>(ws + 2 * plane);
-  for (long r = blockIdx.x; r < R; r += gridDim.x) {
-    const In* __restrict__ row = y + r * ld;
-    const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
-    const double g = G[1];                                           // T >= 1: the table has the entry
-    const double b = base[r];                                        // thread 0 writes it after the tree: its barriers lie between
-    const int32_t n = pools[r];
-    int32_t at = 0, start = 0, end = 0;                              // the pool of the previous frame: [start, end); none yet
-    double val = 0.0, Gl = 1.0;
-    double q = 0.0, s = 0.0, a = 0.0;
-    for (long t = tid; t < T; t += kSearchThreads) {
-      if (t >= end) {
-        at = pool_of(tl, R, r, at, n - 1, t);
-        const int2 own = tl[(long)at * R + r];
-        start = own.x;
-        end = own.x + own.y;
-        val = v[(long)at * R + r];
-        Gl = G[own.y];
-      }
-      const double d = dc_base_resid((double)row[t], b, dc_deconv_calcium(val, G[t - start]));
-      q = q + d * d;
-      s = s + d;
-      a = a + dc_base_gain_at(val, t, start, g, Gl);
-    }
-    red[tid] = q;
-    red[kSearchThreads + tid] = s;
-    red[2 * kSearchThreads + tid] = a;
-    dc_dyn_fold_tree(red, 3);                                        // its last barrier frees all but thread 0's words for the next trace
-    if (tid == 0) {
-      const double RSS = red[0], S = red[kSearchThreads], A = red[2 * kSearchThreads];
-      if (sums) {
-        sums[r] = RSS;
-        sums[(long)R + r] = S;
-        sums[2L * R + r] = A;
-      }
-      if (mode == DC_BASE_FIT) {
-        base[r] = dc_base_step(b, S, A, T);
-      } else {
-        BaseSearchState st = {state, (long)R};
-        DcBaseSearch x = st.load(r);
-        if (mode == DC_BASE_PASS_A) {
-          base[r] = dc_base_search_newton(x, S, A, T);
-          st.store(r, x);
-        } else {
-          const double next = dc_base_search_step(x, param[r], RSS);
-          st.store(r, x);
-          if (mode == DC_BASE_PASS_LAST) {
-            param[r] = x.s.lo;
-            base[r] = x.b_lo;
-            rss[r] = x.s.rss_lo;
-            status[r] = dc_search_status(x.s);
-          } else {
-            param[r] = next;
-          }
-        }
-      }
-    }
-  }
-}
-
-// the three folds of the stacks in ws and what `mode` does with them; the arguments have been checked
-template <bool Each>
-int launch_base_step(const char* who, const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws,
-                     const int* pools, int mode, void* state, double* param, double* base, double* rss, int* status, double* sums,
-                     dc_stream_t stream) {
-  const unsigned groups = (unsigned)(R < kSearchMaxGroups ? R : kSearchMaxGroups);
-  if (is_f64)
-    hipLaunchKernelGGL((deconv_base_step_kernel<double, Each>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)stream, (const double*)y, ld, R,
-                       T, G, ldG, (const double*)ws, pools, mode, (double*)state, param, base, rss, status, sums);
-  else
-    hipLaunchKernelGGL((deconv_base_step_kernel<float, Each>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)stream, (const float*)y, ld, R, T,
-                       G, ldG, (const double*)ws, pools, mode, (double*)state, param, base, rss, status, sums);
-  DC_CHECK_LAUNCH(who);
-  return DC_OK;
-}
-
-// `rounds` baseline steps, then the forward pass and the fill at b_N; the arguments have been checked
-template <bool Each>
-int launch_fit_base(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
-                    const double* lam, const double* smin, int rounds, void* ws, double* calcium, double* spikes, int* pools, double* base,
-                    dc_stream_t stream) {
-  for (int round = 0; round < rounds; ++round) {
-    int rc = launch_forward<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, base, ws, pools, stream);
-    if (rc != DC_OK) return rc;
-    rc = launch_base_step<Each>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, DC_BASE_FIT, nullptr, nullptr, base, nullptr, nullptr, nullptr, stream);
-    if (rc != DC_OK) return rc;
-  }
-  return launch_deconv<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, base, ws, calcium, spikes, pools, stream);
-}
-
-// round 0, the rounds of two passes each and the final pass; the arguments have been checked
-template <bool Each>
-int launch_constrained_base(const char* who, const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
-                            long ldG, int which, const double* sigma, const double* other, int rounds, void* ws, void* state, double* calcium,
-                            double* spikes, int* pools, double* param, double* base, double* rss, int* status, dc_stream_t stream) {
-  const double* lam = which == DC_SEARCH_LAM ? param : other;
-  const double* smin = which == DC_SEARCH_LAM ? other : param;
-  const unsigned begin = (unsigned)(((long)R + kSearchThreads - 1) / kSearchThreads);
-  hipLaunchKernelGGL(deconv_base_begin_kernel, dim3(begin), dim3(kSearchThreads), 0, (hipStream_t)stream, sigma, (const double*)base, R, T,
-                     (double*)state, param);
-  DC_CHECK_LAUNCH(who);
-  for (int round = 0; round <= rounds; ++round) {
-    int rc;
-    if (round > 0) {                                                 // pass A: the baseline step at (p, b)
-      rc = launch_forward<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, base, ws, pools, stream);
-      if (rc != DC_OK) return rc;
-      rc = launch_base_step<Each>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, DC_BASE_PASS_A, state, param, base, rss, status, nullptr, stream);
-      if (rc != DC_OK) return rc;
-    }
-    rc = launch_forward<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, base, ws, pools, stream);      // pass B: RSS at (p, b')
-    if (rc != DC_OK) return rc;
-    rc = launch_base_step<Each>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, round == rounds ? DC_BASE_PASS_LAST : DC_BASE_PASS_B, state, param, base,
-                                rss, status, nullptr, stream);
-    if (rc != DC_OK) return rc;
-  }
-  return launch_deconv<Each>(who, y, is_f64, ld, R, T, g, gs, G, ldG, lam, smin, base, ws, calcium, spikes, pools, stream);
-}
-
-// what the device entry points with a decay per trace or one for all share
-int check_decay(const char* who, int R, long T, double g, const double* gs, long ldG) {
-  if (gs) DC_REQUIRE(ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is below T + 1 = %ld", who, ldG, T + 1);
-  return check_limits(who, R, T, gs ? 0.5 : g);                      // per trace, the decays lie in device memory: THE CALLER PROMISES 0 < gs[r] < 1
-}
-
-// the decay and the table of trace r on the host: one table for all (ldG == 0) or row r; -> DC_OK where the row holds a decay
-int host_table(const char* who, const double* G, long ldG, int r, long T, const double** row, double* g) {
-  *row = G + (long)r * ldG;
-  DC_REQUIRE((*row)[0] == 1.0, DC_EINVAL, "%s: trace %d: G[0] = %g is not 1", who, r, (*row)[0]);
-  *g = (*row)[1];
-  DC_REQUIRE(*g > 0.0 && *g < 1.0, DC_EINVAL, "%s: trace %d: g = %g is outside (0, 1)", who, r, *g);
-  return DC_OK;
-}
-
-template <typename In>
-void base_host_row(const In* y, long T, double g, const double* G, double lam, double smin, double b, std::vector<DcPool>& pool, double* calcium,
-                   double* spikes, int* pools) {
-  const int32_t n = dc_base_forward_host(y, T, g, G, lam, smin, b, pool);
-  *pools = n;
-  for (int32_t i = 0; i < n; ++i) {
-    const DcPool& p = pool[(size_t)i];
-    for (int32_t k = 0; k < p.l; ++k) {
-      calcium[p.t0 + k] = dc_deconv_calcium(p.v, G[k]);
-      spikes[p.t0 + k] = 0.0;
-    }
-    if (i > 0) spikes[p.t0] = dc_deconv_spike(calcium[p.t0], g, calcium[p.t0 - 1]);
-  }
-}
-
-}  // namespace
-
 extern "C" long dc_trace_deconv_base_state_bytes(int R) { return R <= 0 ? 0 : 56L * R; }
 
 extern "C" int dc_trace_deconv_ar1_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G, long ldG,
@@ -681,8 +675,7 @@ extern "C" int dc_trace_deconv_ar1_base(const void* y, int is_f64, long ld, int 
   DC_REQUIRE(dc_aligned(7, gs, G, lam, smin, base, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL,
              "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  if (gs) return launch_deconv<true>(who, y, is_f64, ld, R, T, 0.0, gs, G, ldG, lam, smin, base, ws, calcium, spikes, pools, stream);
-  return launch_deconv<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, lam, smin, base, ws, calcium, spikes, pools, stream);
+  return launch_deconv({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, lam, smin, base, ws, pools, stream}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_fit_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
@@ -698,8 +691,7 @@ extern "C" int dc_trace_deconv_ar1_fit_base(const void* y, int is_f64, long ld, 
   DC_REQUIRE(dc_aligned(7, gs, G, lam, smin, ws, calcium, spikes, base) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL,
              "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  if (gs) return launch_fit_base<true>(who, y, is_f64, ld, R, T, 0.0, gs, G, ldG, lam, smin, rounds, ws, calcium, spikes, pools, base, stream);
-  return launch_fit_base<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, lam, smin, rounds, ws, calcium, spikes, pools, base, stream);
+  return launch_fit_base({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, lam, smin, base, ws, pools, stream}, rounds, base, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_constrained_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
@@ -719,11 +711,8 @@ extern "C" int dc_trace_deconv_ar1_constrained_base(const void* y, int is_f64, l
                  dc_trace_aligned(y, is_f64),
              DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  if (gs)
-    return launch_constrained_base<true>(who, y, is_f64, ld, R, T, 0.0, gs, G, ldG, which, sigma, fixed_other, rounds, ws, state, calcium, spikes,
-                                         pools, param, base, rss, status, stream);
-  return launch_constrained_base<false>(who, y, is_f64, ld, R, T, g, nullptr, G, 0, which, sigma, fixed_other, rounds, ws, state, calcium, spikes,
-                                        pools, param, base, rss, status, stream);
+  return launch_constrained({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, nullptr, nullptr, base, ws, pools, stream}, which, sigma, fixed_other,
+                            rounds, {0, (double*)state, param, base, rss, status, nullptr}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_base_step(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const void* ws,
@@ -735,14 +724,16 @@ extern "C" int dc_trace_deconv_base_step(const void* y, int is_f64, long ld, int
   if (mode != DC_BASE_FIT) DC_REQUIRE(state && param && rss && status, DC_EINVAL, "%s: null pointer", who);
   int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
-  DC_REQUIRE(ldG == 0 || ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is neither 0 nor at least T + 1 = %ld", who, ldG, T + 1);
-  rc = check_limits(who, R, T, 0.5);
+  rc = check_table_stride(who, ldG, T);
+  if (rc != DC_OK) return rc;
+  rc = dc_trace_check_limits(who, R, T);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(dc_aligned(7, G, ws, state, param, base, rss, sums) && dc_aligned(3, pools, status) && dc_trace_aligned(y, is_f64), DC_EINVAL,
              "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  if (ldG) return launch_base_step<true>(who, y, is_f64, ld, R, T, G, ldG, ws, pools, mode, state, param, base, rss, status, sums, stream);
-  return launch_base_step<false>(who, y, is_f64, ld, R, T, G, 0, ws, pools, mode, state, param, base, rss, status, sums, stream);
+  // the sweep only reads ws and pools
+  return launch_sweep({who, y, is_f64, ld, R, T, 0.0, nullptr, G, ldG, nullptr, nullptr, base, const_cast<void*>(ws), const_cast<int*>(pools), stream},
+                      {mode, (double*)state, param, base, rss, status, sums});
 }
 
 extern "C" int dc_trace_deconv_ar1_fit_base_host(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, const double* lam,
@@ -754,34 +745,18 @@ extern "C" int dc_trace_deconv_ar1_fit_base_host(const void* y, int is_f64, long
   int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
   if (rc != DC_OK) return rc;
   DC_REQUIRE(rounds >= 0 && rounds <= DC_BASE_MAX_ROUNDS, DC_EINVAL, "%s: rounds = %d is outside [0, %d]", who, rounds, DC_BASE_MAX_ROUNDS);
-  DC_REQUIRE(ldG == 0 || ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is neither 0 nor at least T + 1 = %ld", who, ldG, T + 1);
+  rc = check_table_stride(who, ldG, T);
+  if (rc != DC_OK) return rc;
   if (R == 0 || T == 0) return DC_OK;                                // G is not read: without frames it need not hold g
   rc = dc_trace_check_limits(who, R, T);
   if (rc != DC_OK) return rc;
-  for (int r = 0; r < R; ++r) {
-    DC_REQUIRE(lam[r] >= 0.0 && smin[r] >= 0.0, DC_EINVAL, "%s: trace %d: lam = %g, smin = %g: neither may be negative", who, r, lam[r], smin[r]);
-    DC_REQUIRE(base[r] - base[r] == 0.0, DC_EINVAL, "%s: trace %d: the baseline %g is not finite", who, r, base[r]);
-  }
-  std::vector<DcPool> pool((size_t)T);
-  std::vector<double> scratch(2 * (size_t)T);
-  for (int r = 0; r < R; ++r) {
-    const double* row_G;
-    double g;
-    rc = host_table(who, G, ldG, r, T, &row_G, &g);
-    if (rc != DC_OK) return rc;
-    double* c = calcium + (long)r * T;
-    double* s = spikes + (long)r * T;
-    if (is_f64) {
-      const double* row = (const double*)y + (long)r * ld;
-      base[r] = dc_base_fit_host(row, T, g, row_G, lam[r], smin[r], base[r], rounds, pool, scratch.data(), scratch.data() + T);
-      base_host_row(row, T, g, row_G, lam[r], smin[r], base[r], pool, c, s, pools + r);
-    } else {
-      const float* row = (const float*)y + (long)r * ld;
-      base[r] = dc_base_fit_host(row, T, g, row_G, lam[r], smin[r], base[r], rounds, pool, scratch.data(), scratch.data() + T);
-      base_host_row(row, T, g, row_G, lam[r], smin[r], base[r], pool, c, s, pools + r);
-    }
-  }
-  return DC_OK;
+  rc = check_host_ranges(who, R, lam, smin, nullptr, nullptr, base);
+  if (rc != DC_OK) return rc;
+  return host_rows(who, y, is_f64, ld, R, T, G, ldG, calcium, spikes, pools, [&](const auto& h) {
+    const int r = h.r;
+    base[r] = dc_base_fit_host(h.y, T, h.g, h.G, lam[r], smin[r], base[r], rounds, h.pool, h.c, h.a);
+    return HostFit{lam[r], smin[r], base[r]};
+  });
 }
 
 extern "C" int dc_trace_deconv_ar1_constrained_base_host(const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, int which,
@@ -795,38 +770,16 @@ extern "C" int dc_trace_deconv_ar1_constrained_base_host(const void* y, int is_f
   if (rc != DC_OK) return rc;
   rc = check_search(who, which, rounds);
   if (rc != DC_OK) return rc;
-  DC_REQUIRE(ldG == 0 || ldG >= T + 1, DC_EINVAL, "%s: ldG = %ld is neither 0 nor at least T + 1 = %ld", who, ldG, T + 1);
+  rc = check_table_stride(who, ldG, T);
+  if (rc != DC_OK) return rc;
   if (R == 0 || T == 0) return DC_OK;                                // G is not read: without frames it need not hold g
   rc = dc_trace_check_limits(who, R, T);
   if (rc != DC_OK) return rc;
-  for (int r = 0; r < R; ++r) {
-    DC_REQUIRE(sigma[r] >= 0.0 && sigma[r] < 0x1p500, DC_EINVAL, "%s: trace %d: sigma = %g is outside [0, 2^500)", who, r, sigma[r]);
-    DC_REQUIRE(fixed_other[r] >= 0.0, DC_EINVAL, "%s: trace %d: the fixed parameter %g is negative", who, r, fixed_other[r]);
-    DC_REQUIRE(base[r] - base[r] == 0.0, DC_EINVAL, "%s: trace %d: the baseline %g is not finite", who, r, base[r]);
-  }
-  std::vector<DcPool> pool((size_t)T);
-  std::vector<double> scratch(2 * (size_t)T);
-  for (int r = 0; r < R; ++r) {
-    const double* row_G;
-    double g;
-    rc = host_table(who, G, ldG, r, T, &row_G, &g);
-    if (rc != DC_OK) return rc;
-    double* c = calcium + (long)r * T;
-    double* s = spikes + (long)r * T;
-    const double b0 = base[r];
-    if (is_f64) {
-      const double* row = (const double*)y + (long)r * ld;
-      dc_base_search_host(row, T, g, row_G, which, sigma[r], fixed_other[r], b0, rounds, pool, scratch.data(), scratch.data() + T, param + r, base + r,
-                          rss + r, status + r);
-      base_host_row(row, T, g, row_G, which == DC_SEARCH_LAM ? param[r] : fixed_other[r], which == DC_SEARCH_LAM ? fixed_other[r] : param[r], base[r],
-                    pool, c, s, pools + r);
-    } else {
-      const float* row = (const float*)y + (long)r * ld;
-      dc_base_search_host(row, T, g, row_G, which, sigma[r], fixed_other[r], b0, rounds, pool, scratch.data(), scratch.data() + T, param + r, base + r,
-                          rss + r, status + r);
-      base_host_row(row, T, g, row_G, which == DC_SEARCH_LAM ? param[r] : fixed_other[r], which == DC_SEARCH_LAM ? fixed_other[r] : param[r], base[r],
-                    pool, c, s, pools + r);
-    }
-  }
-  return DC_OK;
+  rc = check_host_ranges(who, R, nullptr, nullptr, sigma, fixed_other, base);
+  if (rc != DC_OK) return rc;
+  return host_rows(who, y, is_f64, ld, R, T, G, ldG, calcium, spikes, pools, [&](const auto& h) {
+    const int r = h.r;
+    dc_base_search_host(h.y, T, h.g, h.G, which, sigma[r], fixed_other[r], base[r], rounds, h.pool, h.c, h.a, param + r, base + r, rss + r, status + r);
+    return host_fit_found(which, param[r], fixed_other[r], base[r]);
+  });
 }

@@ -17,10 +17,7 @@
 #define DC_BASE_PASS_B 2                     // the search step: the bracket moves, the next parameter is written
 #define DC_BASE_PASS_LAST 3                  // the search step of the last round: p*, b*, RSS(p*, b*) and the status are written
 
-// the frame that the forward pass pushes, before the penalty's shift: the baseline leaves the data first
-DC_DECONV_HD double dc_base_data(double y, double b) { return y - b; }
-
-// d_t = ((double)y[t] - b) - calcium[t]
+// d_t = ((double)y[t] - b) - calcium[t]; dc_base_data is deconv_math.h's, where the forward pass takes b off the data
 DC_DECONV_HD double dc_base_resid(double y, double b, double c) { return dc_base_data(y, b) - c; }
 
 // a_t at the first frame of a pool of l frames whose value is above zero; Gl = G[l].  (sum G)^2 / sum G^2 over the pool's frames,
@@ -72,18 +69,7 @@ DC_DECONV_HD double dc_base_search_step(DcBaseSearch& q, double p, double r) {
 }
 
 // ---- the host restatement: the host entry points and the stand-alone check ---------------------------------------------------------
-// (host functions: no attribute)
-// the forward pass of deconv_math.h with the baseline b taken off every frame
-template <typename In>
-inline int32_t dc_base_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, double b, std::vector<DcPool>& pool) {
-  DcHostStack st = {&pool};
-  DcPool top = dc_deconv_new(0.0, 0);
-  int32_t n = 0;
-  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, dc_base_data((double)y[t], b) - dc_deconv_mu(lam, g, t, T), t, G, smin);
-  st.store(n - 1, top);
-  return n;
-}
-
+// (host functions: no attribute; the forward pass with a baseline is deconv_math.h's dc_base_forward_host)
 struct DcBaseSums {
   double rss, S, A;
 };
@@ -92,12 +78,10 @@ struct DcBaseSums {
 template <typename In>
 inline DcBaseSums dc_base_sums_host(const In* y, long T, const double* G, double b, const std::vector<DcPool>& pool, int32_t n, double* c, double* a) {
   const double g = G[1];
+  dc_deconv_calcium_host(pool, n, G, c);
   for (int32_t i = 0; i < n; ++i) {
     const DcPool& p = pool[(size_t)i];
-    for (int32_t k = 0; k < p.l; ++k) {
-      c[p.t0 + k] = dc_deconv_calcium(p.v, G[k]);
-      a[p.t0 + k] = dc_base_gain_at(p.v, p.t0 + k, p.t0, g, G[p.l]);
-    }
+    for (int32_t k = 0; k < p.l; ++k) a[p.t0 + k] = dc_base_gain_at(p.v, p.t0 + k, p.t0, g, G[p.l]);
   }
   DcBaseSums s;
   s.rss = dc_dyn_fold_host([&](long t) { const double d = dc_base_resid((double)y[t], b, c[t]); return d * d; }, T);

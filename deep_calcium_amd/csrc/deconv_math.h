@@ -24,6 +24,9 @@ struct DcPool {
 // what is subtracted from frame t of a trace of T frames: the L1 penalty lam on the spikes, written as a shift of the data
 DC_DECONV_HD double dc_deconv_mu(double lam, double g, long t, long T) { return t < T - 1 ? lam * (1.0 - g) : lam; }
 
+// the frame that the forward pass pushes, before the penalty's shift: the baseline b of deconv_base_math.h leaves the data first
+DC_DECONV_HD double dc_base_data(double y, double b) { return y - b; }
+
 DC_DECONV_HD DcPool dc_deconv_new(double x, long t) {
   DcPool q;
   q.v = x;
@@ -100,13 +103,28 @@ struct DcHostStack {
   void store(int32_t i, const DcPool& p) { (*pools)[(size_t)i] = p; }
 };
 
-// the forward pass of one trace of T >= 1 frames into pool[0 .. n), which needs T entries; -> n
+// the forward pass of one trace of T >= 1 frames, the baseline b taken off every frame, into pool[0 .. n), which needs T entries; -> n
 template <typename In>
-inline int32_t dc_deconv_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, std::vector<DcPool>& pool) {
+inline int32_t dc_base_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, double b, std::vector<DcPool>& pool) {
   DcHostStack st = {&pool};
   DcPool top = dc_deconv_new(0.0, 0);
   int32_t n = 0;
-  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, (double)y[t] - dc_deconv_mu(lam, g, t, T), t, G, smin);
+  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, dc_base_data((double)y[t], b) - dc_deconv_mu(lam, g, t, T), t, G, smin);
   st.store(n - 1, top);
   return n;
+}
+
+// Without a baseline: b = +0.0 gives the same bits, because x - (+0.0) == x for every double x under round-to-nearest, -0.0 and the
+// infinities included, so (y - 0.0) - mu and y - mu are one value.
+template <typename In>
+inline int32_t dc_deconv_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, std::vector<DcPool>& pool) {
+  return dc_base_forward_host(y, T, g, G, lam, smin, 0.0, pool);
+}
+
+// the calcium of the stack pool[0 .. n) of a trace, frame by frame: c takes one double per frame
+inline void dc_deconv_calcium_host(const std::vector<DcPool>& pool, int32_t n, const double* G, double* c) {
+  for (int32_t i = 0; i < n; ++i) {
+    const DcPool& p = pool[(size_t)i];
+    for (int32_t k = 0; k < p.l; ++k) c[p.t0 + k] = dc_deconv_calcium(p.v, G[k]);
+  }
 }

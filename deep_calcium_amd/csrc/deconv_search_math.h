@@ -75,10 +75,7 @@ DC_DECONV_HD int32_t dc_search_status(const DcSearch& s) { return s.phase == DC_
 // RSS of the stack pool[0 .. n): c is T doubles of scratch
 template <typename In>
 inline double dc_search_rss_host(const In* y, long T, const double* G, const std::vector<DcPool>& pool, int32_t n, double* c) {
-  for (int32_t i = 0; i < n; ++i) {
-    const DcPool& p = pool[(size_t)i];
-    for (int32_t k = 0; k < p.l; ++k) c[p.t0 + k] = dc_deconv_calcium(p.v, G[k]);
-  }
+  dc_deconv_calcium_host(pool, n, G, c);
   return dc_dyn_fold_host([&](long t) { return dc_search_term((double)y[t], c[t]); }, T);
 }
 

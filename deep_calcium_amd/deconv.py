@@ -73,10 +73,15 @@ def _check_kind(kind, constrained=False):
         raise ValueError('deconvolution kind %r is not one of %s' % (kind, ', '.join(KINDS)))
 
 
-def _check_rounds(rounds):
-    if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= MAX_ROUNDS:
-        raise ValueError('rounds must be an integer in [1, %d], not %r' % (MAX_ROUNDS, rounds))
+def _check_rounds(rounds, name, limit):
+    if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= limit:
+        raise ValueError('%s must be an integer in [1, %d], not %r' % (name, limit, rounds))
     return int(rounds)
+
+
+def _check_device_vector(x, what, R):
+    if not x.is_cuda or str(x.dtype) != 'torch.float64' or tuple(x.shape) != (R,) or not x.is_contiguous():
+        raise ValueError('%s must be a contiguous float64 tensor of %d values on the device, not %s %r' % (what, R, x.dtype, tuple(x.shape)))
 
 
 def _check_baseline(baseline, rounds, R, constrained):
@@ -84,13 +89,10 @@ def _check_baseline(baseline, rounds, R, constrained):
     if isinstance(baseline, str):
         if baseline != 'fit':
             raise ValueError("baseline must be a number, one value per trace or 'fit', not %r" % (baseline,))
-        if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= MAX_BASELINE_ROUNDS:
-            raise ValueError('baseline_rounds must be an integer in [1, %d], not %r' % (MAX_BASELINE_ROUNDS, rounds))
+        _check_rounds(rounds, 'baseline_rounds', MAX_BASELINE_ROUNDS)
         return 'fit'
     if _is_device_tensor(baseline):
-        if not baseline.is_cuda or str(baseline.dtype) != 'torch.float64' or tuple(baseline.shape) != (R,) or not baseline.is_contiguous():
-            raise ValueError('baseline must be a contiguous float64 tensor of %d values on the device, not %s %r'
-                             % (R, baseline.dtype, tuple(baseline.shape)))
+        _check_device_vector(baseline, 'baseline', R)
     else:
         try:
             a = np.asarray(baseline, dtype=np.float64)
@@ -245,11 +247,9 @@ class TraceDeconvolver(_MatrixStage):
                 raise ValueError("constrain must be None, 's_min' or 'lam', not %r" % (constrain,))
             if (smin if constrain == 's_min' else lam).any():
                 raise ValueError('%s is searched (constrain=%r): it cannot also be given' % (constrain, constrain))
-            self.rounds = _check_rounds(rounds)
+            self.rounds = _check_rounds(rounds, 'rounds', MAX_ROUNDS)
             if _is_device_tensor(sigma):
-                if not sigma.is_cuda or str(sigma.dtype) != 'torch.float64' or tuple(sigma.shape) != (R,) or not sigma.is_contiguous():
-                    raise ValueError('sigma must be a contiguous float64 tensor of %d values on the device, not %s %r'
-                                     % (R, sigma.dtype, tuple(sigma.shape)))
+                _check_device_vector(sigma, 'sigma', R)
             elif sigma is not None:
                 sigma = _check_sigma(sigma, R)
         self.baseline = _check_baseline(baseline, baseline_rounds, R, constrain is not None)
@@ -296,50 +296,40 @@ class TraceDeconvolver(_MatrixStage):
                 self._sigma = self._empty(R, 'float64')
                 L.dc_trace_noise(y, f64, self._ld, R, T, self._sigma.data_ptr(), stream)
             g, gs, G, ldG = self._decay(stream)
-            if self.baseline is not None:
-                self._run_baseline(out, ws, y, f64, g, gs, G, ldG, stream)
-            elif self.constrain is not None:
-                state = self._empty(L.dc_trace_deconv_search_state_bytes(R) // 8, 'float64')
+            traces = (y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG)
+            lam, smin = self._lam.data_ptr(), self._smin.data_ptr()
+            results = (c.data_ptr(), s.data_ptr(), n.data_ptr())
+            if self._fit:
+                out['baseline'] = self._torch.zeros(R, dtype=self._torch.float64, device=self.device)  # b_0 = 0; the entry points write b here
+                base = out['baseline'].data_ptr()
+            elif self.baseline is not None:
+                out['baseline'] = self._base
+                base = self._base.data_ptr()
+            search = self.constrain is not None
+            if search:                                             # what either search takes, with a baseline to fit or without one
+                state_bytes = L.dc_trace_deconv_base_state_bytes if self._fit else L.dc_trace_deconv_search_state_bytes
+                state = self._empty(state_bytes(R) // 8, 'float64')
                 out.update(param=self._empty(R, 'float64'), rss=self._empty(R, 'float64'), status=self._empty(R, 'int32'))
                 other = self._lam if self.constrain == 's_min' else self._smin
-                L.dc_trace_deconv_ar1_constrained(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, CONSTRAIN[self.constrain],
-                                                  self._sigma.data_ptr(), other.data_ptr(), self.rounds, ws.data_ptr(), state.data_ptr(),
-                                                  c.data_ptr(), s.data_ptr(), n.data_ptr(), out['param'].data_ptr(), out['rss'].data_ptr(),
-                                                  out['status'].data_ptr(), stream)
-                out['target'] = state[3 * R:4 * R].clone()         # plane 3 of the state holds the targets
+                head = traces + (CONSTRAIN[self.constrain], self._sigma.data_ptr(), other.data_ptr(), self.rounds, ws.data_ptr(),
+                                 state.data_ptr()) + results + (out['param'].data_ptr(),)
+                found = (out['rss'].data_ptr(), out['status'].data_ptr())
+            if search and self._fit:                               # the threshold and the baseline, jointly
+                L.dc_trace_deconv_ar1_constrained_base(*head, base, *found, stream)
+            elif search:
+                L.dc_trace_deconv_ar1_constrained(*head, *found, stream)
+            elif self._fit:                                        # the baseline at fixed parameters
+                L.dc_trace_deconv_ar1_fit_base(*traces, lam, smin, self.baseline_rounds, ws.data_ptr(), *results, base, stream)
+            elif self.baseline is not None:                        # a given baseline
+                L.dc_trace_deconv_ar1_base(*traces, lam, smin, base, ws.data_ptr(), *results, stream)
             elif self._each:
-                L.dc_trace_deconv_ar1_each(y, f64, self._ld, R, T, gs, G.data_ptr(), ldG, self._lam.data_ptr(), self._smin.data_ptr(),
-                                           ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(), stream)
+                L.dc_trace_deconv_ar1_each(y, f64, self._ld, R, T, gs, G.data_ptr(), ldG, lam, smin, ws.data_ptr(), *results, stream)
             else:
-                L.dc_trace_deconv_ar1(y, f64, self._ld, R, T, g, G.data_ptr(), self._lam.data_ptr(), self._smin.data_ptr(), ws.data_ptr(),
-                                      c.data_ptr(), s.data_ptr(), n.data_ptr(), stream)
+                L.dc_trace_deconv_ar1(y, f64, self._ld, R, T, g, G.data_ptr(), lam, smin, ws.data_ptr(), *results, stream)
+            if search:
+                out['target'] = state[3 * R:4 * R].clone()         # plane 3 of the state holds the targets
         self._out = out
         return out
-
-    def _run_baseline(self, out, ws, y, f64, g, gs, G, ldG, stream):
-        """The launches of an object with a baseline: given (forward and fill), fitted at fixed parameters, or searched jointly."""
-        R, T, L = self.n_traces, self.n_frames, self.L
-        c, s, n = out['calcium'], out['spikes'], out['pools']
-        if not self._fit:
-            L.dc_trace_deconv_ar1_base(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, self._lam.data_ptr(), self._smin.data_ptr(),
-                                       self._base.data_ptr(), ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(), stream)
-            out['baseline'] = self._base
-            return
-        with self._torch.cuda.device(self.device):
-            base = self._torch.zeros(R, dtype=self._torch.float64, device=self.device)      # b_0 = 0; the entry points write b here
-        out['baseline'] = base
-        if self.constrain is None:
-            L.dc_trace_deconv_ar1_fit_base(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, self._lam.data_ptr(), self._smin.data_ptr(),
-                                           self.baseline_rounds, ws.data_ptr(), c.data_ptr(), s.data_ptr(), n.data_ptr(), base.data_ptr(), stream)
-            return
-        state = self._empty(L.dc_trace_deconv_base_state_bytes(R) // 8, 'float64')
-        out.update(param=self._empty(R, 'float64'), rss=self._empty(R, 'float64'), status=self._empty(R, 'int32'))
-        other = self._lam if self.constrain == 's_min' else self._smin
-        L.dc_trace_deconv_ar1_constrained_base(y, f64, self._ld, R, T, g, gs, G.data_ptr(), ldG, CONSTRAIN[self.constrain],
-                                               self._sigma.data_ptr(), other.data_ptr(), self.rounds, ws.data_ptr(), state.data_ptr(),
-                                               c.data_ptr(), s.data_ptr(), n.data_ptr(), out['param'].data_ptr(), base.data_ptr(),
-                                               out['rss'].data_ptr(), out['status'].data_ptr(), stream)
-        out['target'] = state[3 * R:4 * R].clone()             # plane 3 of the state holds the targets
 
     @property
     def sigma_device(self):

@@ -274,6 +274,37 @@ def test_one_residual_launch_alone(L, each):
     assert ref.same_bits(b3[:R].cpu().numpy(), dev.state[5 * R:6 * R].cpu().numpy())        # plane 5: b, carried
 
 
+@pytest.mark.parametrize('each', (False, True))
+def test_the_plain_sweep_and_the_baseline_sweep_at_zero_fold_the_same_rss(L, each):
+    """On the stacks one dc_trace_deconv_ar1_base call left, dc_trace_deconv_base_step at b = 0 and dc_trace_deconv_search_step
+    fold the same residual, bit for bit: (y - 0.0) - c is y - c.  The search step gets a state of zeros -- phase START, target 0 --,
+    so it records rss_lo = RSS, finishes (RSS >= 0 is never below the target) and, being the last, writes RSS out with status 1
+    and p* = 0.  Neither launch writes the workspace or beyond row R."""
+    R, T = 70, 300
+    y64, sigma = _mixed(R, T, 13)
+    y = y64.astype(np.float32)
+    g = np.array([GAMMAS[r % 3] for r in range(R)]) if each else GAMMAS[1]
+    dev = _Device(L, y, g, 3)
+    dev.given(0.01, 0.4 * sigma, 0.0)
+    before = dev.ws.clone()
+    base, sums = dev.vector(0.0, True), dev.full(3 * R + GUARD)
+    L.dc_trace_deconv_base_step(dev.d.data_ptr(), dev.f64, dev.ld, R, T, dev.G.data_ptr(), dev.ldG, dev.ws.data_ptr(), dev.n.data_ptr(), br.FIT, None,
+                                None, base.data_ptr(), None, None, sums.data_ptr(), dev.stream)
+    state = dev.full(5 * R + GUARD)
+    state[:5 * R] = 0.0
+    param, rss, status = dev.vector(0.0, True), dev.full(R + GUARD), dev.full(R + GUARD, torch.int32)
+    L.dc_trace_deconv_search_step(dev.d.data_ptr(), dev.f64, dev.ld, R, T, dev.G.data_ptr(), dev.ldG, dev.ws.data_ptr(), dev.n.data_ptr(), 1,
+                                  state.data_ptr(), param.data_ptr(), rss.data_ptr(), status.data_ptr(), dev.stream)
+    dev.check()
+    want = sums.cpu().numpy()
+    assert rss[:R].cpu().numpy().tobytes() == want[:R].tobytes() and (want[:R] > 0).any()
+    assert (status[:R].cpu().numpy() == 1).all() and param[:R].cpu().numpy().tobytes() == np.zeros(R).tobytes()
+    assert dev.ws.cpu().numpy().tobytes() == before.cpu().numpy().tobytes()
+    for name, a in (('sums', sums[3 * R:]), ('base', base[R:]), ('state', state[5 * R:]), ('param', param[R:]), ('rss', rss[R:])):
+        assert (a.cpu().numpy() == CANARY).all(), name
+    assert (status[R:].cpu().numpy() == -7).all()
+
+
 def test_trace_deconvolver_with_a_baseline(L):
     """TraceDeconvolver(baseline=) end to end: 'fit' at fixed parameters and with the search, a given scalar, array and resident
     tensor (read in place, never written), numpy and resident traces; 'baseline' of every object."""
