@@ -33,7 +33,7 @@ _EXPORTS = {
     'frames': ('FrameQuality', 'FrameFilter', 'frame_quality_device', 'flag_frames', 'hold_index'),
     'weighted': ('WeightedTraceExtractor', 'weighted_traces_device', 'footprint_weights', 'exclude_overlap', 'roi_gram', 'demix_traces'),
     'dff': ('TraceBaseline', 'neuropil_rois', 'dff_traces_device'),
-    'deconv': ('TraceDeconvolver', 'deconvolve_traces_device', 'ar1_gamma', 'ar1_table', 'trace_noise'),
+    'deconv': ('TraceDeconvolver', 'deconvolve_traces_device', 'ar1_gamma', 'ar1_table', 'ar2_table', 'trace_noise'),
     'dynamics': ('TraceDynamics', 'estimate_ar1_device', 'ar1_tau', 'pick_gamma'),
     'motion': ('MotionCorrector', 'make_template', 'estimate_shifts_device', 'valid_rectangle', 'fine_to_pixels', 'BidiEstimator',
                'pick_bidi', 'estimate_bidi_device'),

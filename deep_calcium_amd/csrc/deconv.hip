@@ -8,8 +8,10 @@
 // same depth touch one line.  The noise-constrained search (csrc/deconv_search_math.h) and the fit of a baseline
 // (csrc/deconv_base_math.h) run that forward pass once or twice a round, with the searched parameter and the baseline in the device
 // arrays the pass reads anyway, and between two passes one launch of the sweep kernel, which folds the residual of the stacks and
-// moves every trace's bracket or baseline: nothing is read back.  Nothing here may be contracted or reassociated: the pragma of
-// deconv_math.h and the per-file flag in _build.py.
+// moves every trace's bracket or baseline: nothing is read back.  The AR(2) model (csrc/deconv_ar2_math.h, "A rise time in the
+// deconvolution") runs through the same walk over the tiles, the same sweep and the same search; its pools carry two data moments
+// and lie in five planes.  Nothing here may be contracted or reassociated: the pragma of deconv_math.h and the per-file flag in
+// _build.py.
 #pragma clang fp contract(off)
 #include <type_traits>
 #include <vector>
@@ -18,6 +20,7 @@
 #include "deconv_math.h"
 #include "deconv_search_math.h"
 #include "deconv_base_math.h"
+#include "deconv_ar2_math.h"
 #include "trace_matrix.h"
 
 namespace {
@@ -29,29 +32,14 @@ const int kFillThreads = 256;
 const int kSearchThreads = DC_DYN_LANES;     // the sweep: one thread per lane of the fold
 const int kSearchMaxGroups = 8192;           // DC_TRACE_DECONV_SEARCH_MAX_GROUPS: beyond, a workgroup walks several traces
 
-// The workspace: three planes of R * T 8-byte words, pool i of trace r at word i * R + r of each.  Only the forward kernel stores.
-struct StackView {
-  double* v;
-  double* w;
+// The workspace: planes of R * T 8-byte words, pool i of trace r at word i * R + r of each.  Only the forward kernels store.  What
+// the AR(1) and the AR(2) stacks share: the plane of (t0, l), which follows the planes of doubles, and the search in it.
+struct StackIndex {
   int2* tl;                                  // (t0, l)
   long R;
-  __device__ __forceinline__ StackView(const double* ws, int R_, long T)
-      : v(const_cast<double*>(ws)), w(v + (long)R_ * T), tl(reinterpret_cast<int2*>(v + 2 * ((long)R_ * T))), R(R_) {}
+  __device__ __forceinline__ StackIndex(const double* ws, int doubles, int R_, long T)
+      : tl(reinterpret_cast<int2*>(const_cast<double*>(ws) + doubles * ((long)R_ * T))), R(R_) {}
   __device__ __forceinline__ long at(int32_t i, long r) const { return (long)i * R + r; }
-  __device__ __forceinline__ DcPool load(int32_t i, long r) const {
-    DcPool p;
-    p.v = v[at(i, r)];
-    p.w = w[at(i, r)];
-    const int2 x = tl[at(i, r)];
-    p.t0 = x.x;
-    p.l = x.y;
-    return p;
-  }
-  __device__ __forceinline__ void store(int32_t i, long r, const DcPool& p) const {
-    v[at(i, r)] = p.v;
-    w[at(i, r)] = p.w;
-    tl[at(i, r)] = make_int2(p.t0, p.l);
-  }
   // The pool of trace r that holds frame t: the last whose start is <= t.  The starts ascend, so a bisection finds it; pool lo
   // starts at or before t, pool hi + 1 (if any) after it.  t in the caller's own integer type: the comparison stays as wide as it
   // was there.
@@ -66,36 +54,92 @@ struct StackView {
   }
 };
 
-// the stack of one trace, as dc_deconv_push takes it
-struct DeviceStack {
-  StackView s;
-  long r;
-  __device__ __forceinline__ DcPool load(int32_t i) const { return s.load(i, r); }
-  __device__ __forceinline__ void store(int32_t i, const DcPool& p) { s.store(i, r, p); }
+// the AR(1) stacks: three planes, v, w and (t0, l)
+struct StackView : StackIndex {
+  double* v;
+  double* w;
+  __device__ __forceinline__ StackView(const double* ws, int R_, long T)
+      : StackIndex(ws, 2, R_, T), v(const_cast<double*>(ws)), w(v + (long)R_ * T) {}
+  // what a pool's calcium is computed from, for the cursor of the sweep
+  __device__ __forceinline__ void value(long word, double& val, double& below) const {
+    val = v[word];
+    below = 0.0;
+  }
+  __device__ __forceinline__ DcPool load(int32_t i, long r) const {
+    DcPool p;
+    p.v = v[at(i, r)];
+    p.w = w[at(i, r)];
+    const int2 x = tl[at(i, r)];
+    p.t0 = x.x;
+    p.l = x.y;
+    return p;
+  }
+  __device__ __forceinline__ void store(int32_t i, long r, const DcPool& p) const {
+    v[at(i, r)] = p.v;
+    w[at(i, r)] = p.w;
+    tl[at(i, r)] = make_int2(p.t0, p.l);
+  }
 };
 
-// One workgroup of one wave per 64 traces.  Rows r >= R and frames t >= T of a ragged tile are neither read nor written.
-// Each = false: one decay g and one table G for all traces (dc_trace_deconv_ar1).  Each = true: trace r has the decay gs[r] and
-// the table row G + r * ldG (dc_trace_deconv_ar1_each); the arithmetic of a trace is the same, only where its g and G come from.
-// Base = true: the baseline base[r] leaves every frame of trace r before the penalty's shift (csrc/deconv_base_math.h).
-template <typename In, bool Each, bool Base>
-__global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g_all,
-                                                               const double* __restrict__ gs, const double* __restrict__ G_all, long ldG,
-                                                               const double* __restrict__ lam, const double* __restrict__ smin,
-                                                               const double* __restrict__ base, double* ws, int* __restrict__ pools) {
-  __shared__ In tile[kLanes * kPitch];
+// the AR(2) stacks: five planes, v, u, A, B and (t0, l).  v could be had again from A, u and l; it is kept, a load for a division
+struct StackView2 : StackIndex {
+  double *v, *u, *A, *B;
+  __device__ __forceinline__ StackView2(const double* ws, int R_, long T)
+      : StackIndex(ws, 4, R_, T), v(const_cast<double*>(ws)), u(v + (long)R_ * T), A(u + (long)R_ * T), B(A + (long)R_ * T) {}
+  __device__ __forceinline__ void value(long word, double& val, double& below) const {
+    val = v[word];
+    below = u[word];
+  }
+  __device__ __forceinline__ DcPool2 load(int32_t i, long r) const {
+    DcPool2 p;
+    p.v = v[at(i, r)];
+    p.u = u[at(i, r)];
+    p.A = A[at(i, r)];
+    p.B = B[at(i, r)];
+    const int2 x = tl[at(i, r)];
+    p.t0 = x.x;
+    p.l = x.y;
+    return p;
+  }
+  // a pool without its moments: what its calcium takes (v, u, t0, l); A and B are +0.0 and not read
+  __device__ __forceinline__ DcPool2 load_fit(int32_t i, long r) const {
+    DcPool2 p;
+    p.v = v[at(i, r)];
+    p.u = u[at(i, r)];
+    p.A = 0.0;
+    p.B = 0.0;
+    const int2 x = tl[at(i, r)];
+    p.t0 = x.x;
+    p.l = x.y;
+    return p;
+  }
+  __device__ __forceinline__ void store(int32_t i, long r, const DcPool2& p) const {
+    v[at(i, r)] = p.v;
+    u[at(i, r)] = p.u;
+    A[at(i, r)] = p.A;
+    B[at(i, r)] = p.B;
+    tl[at(i, r)] = make_int2(p.t0, p.l);
+  }
+};
+
+// the stack of one trace, as dc_deconv_push and dc_ar2_push take it
+template <class View, class Pool>
+struct DeviceStack {
+  View s;
+  long r;
+  __device__ __forceinline__ Pool load(int32_t i) const { return s.load(i, r); }
+  __device__ __forceinline__ void store(int32_t i, const Pool& p) { s.store(i, r, p); }
+};
+
+// The walk of a workgroup of one wave over its 64 traces: a tile of 64 traces x 64 frames at a time is staged through `tile`
+// (kLanes * kPitch elements of LDS) with coalesced row reads, then lane `lane` walks its own row of the tile, frame(t, y[r][t])
+// in ascending t, where its trace exists.  Rows r >= R and frames t >= T of a ragged tile are neither read nor written.
+template <typename In, class F>
+__device__ __forceinline__ void walk_tiles(In* tile, const In* __restrict__ y, long ld, int R, long T, F frame) {
   const int lane = threadIdx.x;
   const long r0 = (long)blockIdx.x * kLanes;
-  const long r = r0 + lane;
-  const bool mine = r < R;
+  const bool mine = r0 + lane < R;
   const int rows = R - r0 < kLanes ? (int)(R - r0) : kLanes;
-  DeviceStack st = {StackView(ws, R, T), r};
-  const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
-  const double g = Each ? (mine ? gs[r] : 0.5) : g_all;
-  const double* __restrict__ G = Each && mine ? G_all + r * ldG : G_all;
-  const double b = Base && mine ? base[r] : 0.0;
-  DcPool top = dc_deconv_new(0.0, 0);
-  int32_t n = 0;
   for (long f0 = 0; f0 < T; f0 += kFrames) {
     const int frames = T - f0 < kFrames ? (int)(T - f0) : kFrames;
     __syncthreads();                                                 // the previous tile has been consumed
@@ -105,16 +149,62 @@ __global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __rest
     }
     __syncthreads();
     if (mine) {
-      for (int k = 0; k < frames; ++k) {
-        const long t = f0 + k;
-        const double y_t = (double)tile[lane * kPitch + k];
-        const double x = (Base ? dc_base_data(y_t, b) : y_t) - dc_deconv_mu(la, g, t, T);
-        dc_deconv_push(top, n, st, x, t, G, sm);
-      }
+      for (int k = 0; k < frames; ++k) frame(f0 + k, (double)tile[lane * kPitch + k]);
     }
   }
+}
+
+// One workgroup of one wave per 64 traces (walk_tiles).
+// Each = false: one decay g and one table G for all traces (dc_trace_deconv_ar1).  Each = true: trace r has the decay gs[r] and
+// the table row G + r * ldG (dc_trace_deconv_ar1_each); the arithmetic of a trace is the same, only where its g and G come from.
+// Base = true: the baseline base[r] leaves every frame of trace r before the penalty's shift (csrc/deconv_base_math.h).
+template <typename In, bool Each, bool Base>
+__global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g_all,
+                                                               const double* __restrict__ gs, const double* __restrict__ G_all, long ldG,
+                                                               const double* __restrict__ lam, const double* __restrict__ smin,
+                                                               const double* __restrict__ base, double* ws, int* __restrict__ pools) {
+  __shared__ In tile[kLanes * kPitch];
+  const long r = (long)blockIdx.x * kLanes + threadIdx.x;
+  const bool mine = r < R;
+  DeviceStack<StackView, DcPool> st = {StackView(ws, R, T), r};
+  const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
+  const double g = Each ? (mine ? gs[r] : 0.5) : g_all;
+  const double* __restrict__ G = Each && mine ? G_all + r * ldG : G_all;
+  const double b = Base && mine ? base[r] : 0.0;
+  DcPool top = dc_deconv_new(0.0, 0);
+  int32_t n = 0;
+  walk_tiles(tile, y, ld, R, T, [&](long t, double y_t) {
+    const double x = (Base ? dc_base_data(y_t, b) : y_t) - dc_deconv_mu(la, g, t, T);
+    dc_deconv_push(top, n, st, x, t, G, sm);
+  });
   if (mine) {
     st.store(n - 1, top);                                            // T >= 1: n >= 1.  The fill kernel reads the workspace only
+    pools[r] = n;
+  }
+}
+
+// The AR(2) forward pass (csrc/deconv_ar2_math.h): the same walk, one lane per trace; one pair of coefficients and one table H of
+// three rows for all traces.
+template <typename In, bool Base>
+__global__ __launch_bounds__(kLanes) void deconv_ar2_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g1, double g2,
+                                                                   const double* __restrict__ H, long ldH, const double* __restrict__ lam,
+                                                                   const double* __restrict__ smin, const double* __restrict__ base, double* ws,
+                                                                   int* __restrict__ pools) {
+  __shared__ In tile[kLanes * kPitch];
+  const long r = (long)blockIdx.x * kLanes + threadIdx.x;
+  const bool mine = r < R;
+  DeviceStack<StackView2, DcPool2> st = {StackView2(ws, R, T), r};
+  const DcAr2 m = dc_ar2_model(g1, g2, H, ldH);
+  const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
+  const double b = Base && mine ? base[r] : 0.0;
+  DcPool2 top = dc_ar2_new(0.0, 0);
+  int32_t n = 0;
+  walk_tiles(tile, y, ld, R, T, [&](long t, double y_t) {
+    const double x = (Base ? dc_base_data(y_t, b) : y_t) - dc_ar2_mu(la, g1, g2, t, T);
+    dc_ar2_push(top, n, st, x, t, m, sm);
+  });
+  if (mine) {
+    st.store(n - 1, top);                                            // T >= 1: n >= 1
     pools[r] = n;
   }
 }
@@ -139,6 +229,30 @@ __global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double*
   if (k == 0 && lo > 0) {
     const long below = st.at(lo - 1, r);
     s = dc_deconv_spike(c, g, dc_deconv_calcium(st.v[below], G[st.tl[below].y - 1]));
+  }
+  calcium[idx] = c;
+  spikes[idx] = s;
+}
+
+// The AR(2) fill: one thread per sample, as above; the spike of a pool's first frame takes the last two values of the pool below.
+__global__ __launch_bounds__(kFillThreads) void deconv_ar2_fill_kernel(const double* __restrict__ ws, const int* __restrict__ pools, int R, long T,
+                                                                      double g1, double g2, const double* __restrict__ H, long ldH,
+                                                                      double* __restrict__ calcium, double* __restrict__ spikes) {
+  const long idx = (long)blockIdx.x * kFillThreads + threadIdx.x;
+  if (idx >= (long)R * T) return;
+  const long r = idx / T;
+  const int32_t t = (int32_t)(idx - r * T);
+  const DcAr2 m = dc_ar2_model(g1, g2, H, ldH);
+  const StackView2 st(ws, R, T);
+  const int32_t lo = st.pool_of(r, 0, pools[r] - 1, t);
+  const long own = st.at(lo, r);
+  const int32_t k = t - st.tl[own].x;
+  const double c = dc_ar2_calc(m, st.v[own], st.u[own], k);
+  double s = 0.0;
+  if (k == 0 && lo > 0) {
+    double last, sec;
+    dc_ar2_tail(m, st.load_fit(lo - 1, r), last, sec);
+    s = dc_ar2_spike(m, c, last, sec);
   }
   calcium[idx] = c;
   spikes[idx] = s;
@@ -205,18 +319,20 @@ struct SweepOut {
   double* sums;
 };
 
-// The pool that holds the frame a thread of the sweep stands at: pool `at` of the trace, frames [start, end), of value val.  A
-// thread's frames ascend, so it seeks from its previous pool upwards, and only when a frame t >= end has left that pool.
+// The pool that holds the frame a thread of the sweep stands at: pool `at` of the trace, frames [start, end), of value val, above
+// the calcium `below` (AR(2); +0.0 and unused for AR(1)).  A thread's frames ascend, so it seeks from its previous pool upwards,
+// and only when a frame t >= end has left that pool.
 struct PoolCursor {
   int32_t at = 0, start = 0, end = 0;        // no pool yet: frame 0 seeks
-  double val = 0.0;
+  double val = 0.0, below = 0.0;
   __device__ __forceinline__ int32_t length() const { return end - start; }
-  __device__ __forceinline__ void seek(const StackView& st, long r, int32_t n, long t) {
+  template <class View>
+  __device__ __forceinline__ void seek(const View& st, long r, int32_t n, long t) {
     at = st.pool_of(r, at, n - 1, t);
     const int2 own = st.tl[st.at(at, r)];
     start = own.x;
     end = own.x + own.y;
-    val = st.v[st.at(at, r)];
+    st.value(st.at(at, r), val, below);
   }
 };
 
@@ -274,16 +390,18 @@ __device__ __forceinline__ void base_tail(const SweepOut& o, long r, long R, lon
 // base[r] off the data and folds RSS, S and A of deconv_base_math.h into red[3 * 256].  The tree through LDS is dc_dyn_fold_tree of
 // trace_dyn_math.h.  Its results red[0], red[256] and red[512] are thread 0's own words, and its last barrier frees the others for
 // the next trace; it also lies between every thread's read of base[r] and thread 0's write.  Every word has one writer; frames
-// t >= T of a row and rows r >= R are never read.
-template <typename In, bool Each, bool Base>
+// t >= T of a row and rows r >= R are never read.  Ar2: the stacks are those of the AR(2) pass, G_all is its table of three rows
+// of stride ldG and g1, g2 its coefficients (Each and Base are then false): the plain search's residual, nothing else differs.
+template <typename In, bool Each, bool Base, bool Ar2>
 __global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* __restrict__ y, long ld, int R, long T,
-                                                                      const double* __restrict__ G_all, long ldG,
+                                                                      const double* __restrict__ G_all, long ldG, double g1, double g2,
                                                                       const double* __restrict__ ws, const int* __restrict__ pools,
                                                                       const SweepOut out) {
+  static_assert(!Ar2 || (!Each && !Base), "the AR(2) sweep has one table and no baseline");
   const int folds = Base ? 3 : 1;
   __shared__ double red[folds * kSearchThreads];
   const int tid = threadIdx.x;
-  const StackView st(ws, R, T);
+  const std::conditional_t<Ar2, StackView2, StackView> st(ws, R, T);
   for (long r = blockIdx.x; r < R; r += gridDim.x) {
     const In* __restrict__ row = y + r * ld;
     const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
@@ -298,7 +416,9 @@ __global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* 
         pool.seek(st, r, n, t);
         if constexpr (Base) Gl = G[pool.length()];
       }
-      const double c = dc_deconv_calcium(pool.val, G[t - pool.start]);
+      double c;
+      if constexpr (Ar2) c = dc_ar2_calc(dc_ar2_model(g1, g2, G_all, ldG), pool.val, pool.below, (int32_t)(t - pool.start));
+      else c = dc_deconv_calcium(pool.val, G[t - pool.start]);
       if constexpr (Base) {
         const double d = dc_base_resid((double)row[t], b, c);
         q = q + d * d;
@@ -323,7 +443,8 @@ __global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* 
 
 // ---- the launches: the arguments have been checked -----------------------------------------------------------------------------------
 // What every launch of a call shares.  One decay g and one table G for all traces (gs == nullptr, ldG == 0), or the decays gs and
-// the table rows G + r * ldG; base == nullptr: no baseline, the kernels of the entry points that have none.
+// the table rows G + r * ldG; base == nullptr: no baseline, the kernels of the entry points that have none.  ldH != 0: the AR(2)
+// model, g and g2 its coefficients and G its table of three rows of stride ldH (gs == nullptr, ldG == 0).
 struct Args {
   const char* who;
   const void* y;
@@ -338,6 +459,8 @@ struct Args {
   void* ws;
   int* pools;
   dc_stream_t stream;
+  double g2 = 0.0;
+  long ldH = 0;
 };
 
 // a flag of the call as a template argument of its kernel: launch(std::true_type()) or launch(std::false_type())
@@ -347,23 +470,31 @@ void with_flag(bool flag, F launch) {
   else launch(std::false_type());
 }
 
-// In, Each and Base of the forward and sweep kernels from the call: launch(In(), each, base), the last two as with_flag gives them
+// In, Each, Base and Ar2 of the forward and sweep kernels from the call: launch(In(), each, base, ar2), the last three as with_flag
+// gives them; the AR(2) model has no table per trace
 template <class F>
 void with_kernel_of(const Args& a, F launch) {
-  with_flag(a.ldG != 0, [&](auto each) {
-    with_flag(a.base != nullptr, [&](auto base) {
-      if (a.is_f64) launch(double(), each, base);
-      else launch(float(), each, base);
-    });
+  with_flag(a.base != nullptr, [&](auto base) {
+    auto typed = [&](auto each, auto ar2) {
+      if (a.is_f64) launch(double(), each, base, ar2);
+      else launch(float(), each, base, ar2);
+    };
+    if (a.ldH != 0) typed(std::false_type(), std::true_type());
+    else with_flag(a.ldG != 0, [&](auto each) { typed(each, std::false_type()); });
   });
 }
 
 int launch_forward(const Args& a) {
   const unsigned groups = (unsigned)(((long)a.R + kLanes - 1) / kLanes);                    // <= 2^25: no cap
-  with_kernel_of(a, [&](auto in, auto each, auto base) {
+  with_kernel_of(a, [&](auto in, auto each, auto base, auto ar2) {
     using In = decltype(in);
-    hipLaunchKernelGGL((deconv_forward_kernel<In, decltype(each)::value, decltype(base)::value>), dim3(groups), dim3(kLanes), 0, (hipStream_t)a.stream,
-                       (const In*)a.y, a.ld, a.R, a.T, a.g, a.gs, a.G, a.ldG, a.lam, a.smin, a.base, (double*)a.ws, a.pools);
+    if constexpr (decltype(ar2)::value) {
+      hipLaunchKernelGGL((deconv_ar2_forward_kernel<In, decltype(base)::value>), dim3(groups), dim3(kLanes), 0, (hipStream_t)a.stream, (const In*)a.y,
+                         a.ld, a.R, a.T, a.g, a.g2, a.G, a.ldH, a.lam, a.smin, a.base, (double*)a.ws, a.pools);
+    } else {
+      hipLaunchKernelGGL((deconv_forward_kernel<In, decltype(each)::value, decltype(base)::value>), dim3(groups), dim3(kLanes), 0,
+                         (hipStream_t)a.stream, (const In*)a.y, a.ld, a.R, a.T, a.g, a.gs, a.G, a.ldG, a.lam, a.smin, a.base, (double*)a.ws, a.pools);
+    }
   });
   DC_CHECK_LAUNCH(a.who);
   return DC_OK;
@@ -374,10 +505,15 @@ int launch_deconv(const Args& a, double* calcium, double* spikes) {
   const int rc = launch_forward(a);
   if (rc != DC_OK) return rc;
   const unsigned blocks = (unsigned)(((long)a.R * a.T + kFillThreads - 1) / kFillThreads);  // <= 2^23: no cap
-  with_flag(a.ldG != 0, [&](auto each) {
-    hipLaunchKernelGGL(deconv_fill_kernel<decltype(each)::value>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)a.stream, (const double*)a.ws,
-                       a.pools, a.R, a.T, a.g, a.gs, a.G, a.ldG, calcium, spikes);
-  });
+  if (a.ldH != 0) {
+    hipLaunchKernelGGL(deconv_ar2_fill_kernel, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)a.stream, (const double*)a.ws, a.pools, a.R, a.T,
+                       a.g, a.g2, a.G, a.ldH, calcium, spikes);
+  } else {
+    with_flag(a.ldG != 0, [&](auto each) {
+      hipLaunchKernelGGL(deconv_fill_kernel<decltype(each)::value>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)a.stream, (const double*)a.ws,
+                         a.pools, a.R, a.T, a.g, a.gs, a.G, a.ldG, calcium, spikes);
+    });
+  }
   DC_CHECK_LAUNCH(a.who);
   return DC_OK;
 }
@@ -385,10 +521,14 @@ int launch_deconv(const Args& a, double* calcium, double* spikes) {
 // the folds of the stacks in ws and what out.mode does with them
 int launch_sweep(const Args& a, const SweepOut& out) {
   const unsigned groups = (unsigned)(a.R < kSearchMaxGroups ? a.R : kSearchMaxGroups);
-  with_kernel_of(a, [&](auto in, auto each, auto base) {
+  DC_REQUIRE(a.ldH == 0 || a.base == nullptr, DC_EUNSUP, "%s: the AR(2) sweep takes no baseline", a.who);
+  with_kernel_of(a, [&](auto in, auto each, auto base, auto ar2) {
     using In = decltype(in);
-    hipLaunchKernelGGL((deconv_sweep_kernel<In, decltype(each)::value, decltype(base)::value>), dim3(groups), dim3(kSearchThreads), 0,
-                       (hipStream_t)a.stream, (const In*)a.y, a.ld, a.R, a.T, a.G, a.ldG, (const double*)a.ws, a.pools, out);
+    constexpr bool kAr2 = decltype(ar2)::value, kBase = decltype(base)::value;
+    if constexpr (!(kAr2 && kBase)) {                               // refused above
+      hipLaunchKernelGGL((deconv_sweep_kernel<In, decltype(each)::value, kBase, kAr2>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)a.stream,
+                         (const In*)a.y, a.ld, a.R, a.T, a.G, kAr2 ? a.ldH : a.ldG, a.g, a.g2, (const double*)a.ws, a.pools, out);
+    }
   });
   DC_CHECK_LAUNCH(a.who);
   return DC_OK;
@@ -781,5 +921,129 @@ extern "C" int dc_trace_deconv_ar1_constrained_base_host(const void* y, int is_f
     const int r = h.r;
     dc_base_search_host(h.y, T, h.g, h.G, which, sigma[r], fixed_other[r], base[r], rounds, h.pool, h.c, h.a, param + r, base + r, rss + r, status + r);
     return host_fit_found(which, param[r], fixed_other[r], base[r]);
+  });
+}
+
+// ---- a rise time in the deconvolution: AR(2) (csrc/deconv_ar2_math.h) -----------------------------------------------------------------
+namespace {
+
+// the coefficients and the table's stride
+int check_ar2(const char* who, int R, long T, double g1, double g2, long ldH) {
+  DC_REQUIRE(dc_ar2_roots_ok(g1, g2), DC_EINVAL, "%s: g1 = %g, g2 = %g are not those of two real roots 0 < r < d < 1", who, g1, g2);
+  DC_REQUIRE(ldH >= T + 1, DC_EINVAL, "%s: ldH = %ld is below T + 1 = %ld", who, ldH, T + 1);
+  return dc_trace_check_limits(who, R, T);
+}
+
+// the table of a host entry point holds the coefficients; T >= 1
+int check_ar2_host_table(const char* who, double g1, const double* H, long ldH) {
+  DC_REQUIRE(H[0] == 1.0 && H[1] == g1 && H[ldH] == 0.0 && H[2 * ldH] == 0.0, DC_EINVAL,
+             "%s: the table does not begin with h = (1, g1), HH[0] = HP[0] = 0", who);
+  return DC_OK;
+}
+
+// The rows of an AR(2) host entry point; R, T >= 1.  fit(r, row, pool, c), a generic lambda, gets trace r with its row as the type
+// it has, does what the entry point does before the outputs and returns what they are computed at.
+template <class F>
+int host_rows_ar2(const void* y, int is_f64, long ld, int R, long T, const DcAr2& m, double* calcium, double* spikes, int* pools, F fit) {
+  std::vector<DcPool2> pool((size_t)T);
+  for (int r = 0; r < R; ++r) {
+    double* c = calcium + (long)r * T;
+    auto one = [&](auto row) {
+      const HostFit at = fit(r, row, pool, c);
+      const int32_t n = dc_ar2_forward_host(row, T, m, at.lam, at.smin, at.b, pool);
+      pools[r] = n;
+      dc_ar2_calcium_host(pool, n, m, c);
+      dc_ar2_spikes_host(pool, n, m, T, c, spikes + (long)r * T);
+    };
+    if (is_f64) one((const double*)y + (long)r * ld);
+    else one((const float*)y + (long)r * ld);
+  }
+  return DC_OK;
+}
+
+}  // namespace
+
+extern "C" long dc_trace_deconv_ar2_ws_bytes(int R, long T) {
+  if (R <= 0 || T <= 0 || T > DC_TRACE_DECONV_MAX_FRAMES || (long)R * T > DC_TRACE_DECONV_MAX_SAMPLES) return 0;
+  return 40L * R * T;
+}
+
+extern "C" int dc_trace_deconv_ar2(const void* y, int is_f64, long ld, int R, long T, double g1, double g2, const double* H, long ldH,
+                                   const double* lam, const double* smin, const double* base, void* ws, double* calcium, double* spikes,
+                                   int* pools, dc_stream_t stream) {
+  const char* who = "dc_trace_deconv_ar2";
+  DC_REQUIRE(H && lam && smin && ws && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  rc = check_ar2(who, R, T, g1, g2, ldH);
+  if (rc != DC_OK) return rc;                                        // lam, smin, base: THE CALLER PROMISES lam, smin >= 0 and a finite base
+  DC_REQUIRE(dc_aligned(7, H, lam, smin, base, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL,
+             "%s: misaligned buffer", who);
+  if (R == 0 || T == 0) return DC_OK;
+  return launch_deconv({who, y, is_f64, ld, R, T, g1, nullptr, H, 0, lam, smin, base, ws, pools, stream, g2, ldH}, calcium, spikes);
+}
+
+extern "C" int dc_trace_deconv_ar2_host(const void* y, int is_f64, long ld, int R, long T, double g1, double g2, const double* H, long ldH,
+                                        const double* lam, const double* smin, const double* base, double* calcium, double* spikes,
+                                        int* pools) {
+  const char* who = "dc_trace_deconv_ar2_host";
+  DC_REQUIRE(H && lam && smin && calcium && spikes && pools, DC_EINVAL, "%s: null pointer", who);
+  DC_REQUIRE(dc_aligned(7, H, lam, smin, base, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL,
+             "%s: misaligned buffer", who);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  rc = check_ar2(who, R, T, g1, g2, ldH);
+  if (rc != DC_OK) return rc;
+  if (R == 0 || T == 0) return DC_OK;
+  rc = check_ar2_host_table(who, g1, H, ldH);
+  if (rc != DC_OK) return rc;
+  rc = check_host_ranges(who, R, lam, smin, nullptr, nullptr, base);
+  if (rc != DC_OK) return rc;
+  return host_rows_ar2(y, is_f64, ld, R, T, dc_ar2_model(g1, g2, H, ldH), calcium, spikes, pools,
+                       [&](int r, auto, std::vector<DcPool2>&, double*) { return HostFit{lam[r], smin[r], base ? base[r] : 0.0}; });
+}
+
+extern "C" int dc_trace_deconv_ar2_constrained(const void* y, int is_f64, long ld, int R, long T, double g1, double g2, const double* H, long ldH,
+                                               int which, const double* sigma, const double* fixed_other, int rounds, void* ws, void* state,
+                                               double* calcium, double* spikes, int* pools, double* param, double* rss, int* status,
+                                               dc_stream_t stream) {
+  const char* who = "dc_trace_deconv_ar2_constrained";
+  DC_REQUIRE(H && sigma && fixed_other && ws && state && calcium && spikes && pools && param && rss && status, DC_EINVAL, "%s: null pointer", who);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  rc = check_search(who, which, rounds);
+  if (rc != DC_OK) return rc;
+  rc = check_ar2(who, R, T, g1, g2, ldH);
+  if (rc != DC_OK) return rc;                                        // sigma, fixed_other: THE CALLER PROMISES 0 <= sigma[r] < 2^500, finite, and fixed_other[r] >= 0
+  DC_REQUIRE(dc_aligned(7, H, sigma, fixed_other, ws, state, calcium, spikes, param, rss) && dc_aligned(3, pools, status) &&
+                 dc_trace_aligned(y, is_f64),
+             DC_EINVAL, "%s: misaligned buffer", who);
+  if (R == 0 || T == 0) return DC_OK;
+  return launch_constrained({who, y, is_f64, ld, R, T, g1, nullptr, H, 0, nullptr, nullptr, nullptr, ws, pools, stream, g2, ldH}, which, sigma,
+                            fixed_other, rounds, {0, (double*)state, param, nullptr, rss, status, nullptr}, calcium, spikes);
+}
+
+extern "C" int dc_trace_deconv_ar2_constrained_host(const void* y, int is_f64, long ld, int R, long T, double g1, double g2, const double* H,
+                                                    long ldH, int which, const double* sigma, const double* fixed_other, int rounds,
+                                                    double* calcium, double* spikes, int* pools, double* param, double* rss, int* status) {
+  const char* who = "dc_trace_deconv_ar2_constrained_host";
+  DC_REQUIRE(H && sigma && fixed_other && calcium && spikes && pools && param && rss && status, DC_EINVAL, "%s: null pointer", who);
+  DC_REQUIRE(dc_aligned(7, H, sigma, fixed_other, calcium, spikes, param, rss) && dc_aligned(3, pools, status) && dc_trace_aligned(y, is_f64),
+             DC_EINVAL, "%s: misaligned buffer", who);
+  int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
+  if (rc != DC_OK) return rc;
+  rc = check_search(who, which, rounds);
+  if (rc != DC_OK) return rc;
+  rc = check_ar2(who, R, T, g1, g2, ldH);
+  if (rc != DC_OK) return rc;
+  if (R == 0 || T == 0) return DC_OK;
+  rc = check_ar2_host_table(who, g1, H, ldH);
+  if (rc != DC_OK) return rc;
+  rc = check_host_ranges(who, R, nullptr, nullptr, sigma, fixed_other, nullptr);
+  if (rc != DC_OK) return rc;
+  const DcAr2 m = dc_ar2_model(g1, g2, H, ldH);
+  return host_rows_ar2(y, is_f64, ld, R, T, m, calcium, spikes, pools, [&](int r, auto row, std::vector<DcPool2>& pool, double* c) {
+    dc_ar2_search_host(row, T, m, which, sigma[r], fixed_other[r], rounds, pool, c, param + r, rss + r, status + r);
+    return host_fit_found(which, param[r], fixed_other[r], 0.0);
   });
 }

@@ -47,7 +47,16 @@ without the baseline: the fitted trace is c + baseline.
 With a fixed threshold the fit is only as good as the threshold: one that is too high misses events, whose fluorescence is then
 absorbed into the baseline.
 
-Not built: AR(2), optimising g by the residual, a time-varying baseline; for the search: both parameters at once, a warm start,
+A rise time: rise=r makes the model AR(2), c[t] = g1 c[t-1] + g2 c[t-2] + s[t] with the roots g (the decay) and r (the rise) per
+frame, g1 = g + r, g2 = -(g * r) (the header's "A rise time in the deconvolution"; csrc/deconv_ar2_math.h).  An indicator that
+takes several frames to peak is otherwise explained as a run of spikes.  Everything above works as it does without it, except
+baseline='fit' and a decay per trace; the greedy pass is feasible but, unlike AR(1), not promised to be optimal.
+
+    dec = TraceDeconvolver(dff_dev, ar1_gamma(1.0, 30.0), rise=ar1_gamma(0.1, 30.0), constrain='s_min')
+    c, s = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau=1.0, tau_rise=0.1, fps=30.0, k='noise')
+
+Not built: estimating the rise, fitting the baseline under AR(2), a pair of roots per trace, complex or equal roots, OASIS's
+corrective passes; optimising g by the residual, a time-varying baseline; for the search: both parameters at once, a warm start,
 the closed-form lam update of OASIS, a joint search over g.
 
 Importing this module needs neither torch nor the GPU; constructing a TraceDeconvolver does (there is no CPU fallback).
@@ -155,6 +164,57 @@ def ar1_table(g, T):
     return np.multiply.accumulate(G)           # a sequential left fold: G[l] = G[l-1] * g
 
 
+def _check_roots(g, rise):
+    """The roots of the AR(2) model, decay and rise per frame: scalars, 0 < rise < g < 1 -> (g, rise) as floats."""
+    if np.ndim(g) != 0:
+        raise ValueError('a decay per trace is not built for AR(2): with rise=, g must be a scalar')
+    g = _check_gamma(g)
+    try:
+        if np.ndim(rise) != 0:
+            raise TypeError
+        rise = float(rise)
+    except (TypeError, ValueError):
+        raise ValueError('rise must be a number in (0, g), not %r' % (rise,))
+    if not 0.0 < rise < g:                     # NaN fails both comparisons
+        raise ValueError('rise must be inside (0, g = %r), not %r' % (g, rise))
+    return g, rise
+
+
+def ar2_coefficients(g, rise):
+    """g1 = g + rise, g2 = -(g * rise): the coefficients of c[t] = g1 c[t-1] + g2 c[t-2] + s[t] whose roots are g and rise."""
+    g, rise = _check_roots(g, rise)
+    return g + rise, -(g * rise)
+
+
+def ar2_table(g, rise, T):
+    """float64 (3, T + 1), the rows h, HH and HP of the header: h[0] = 1, h[1] = g1, h[k] = g1 * h[k-1] + g2 * h[k-2]; HH[0] = HP[0] =
+    0, HH[l+1] = HH[l] + h[l] * h[l], HP[l+1] = HP[l] + h[l] * h[l-1] (the term of l = 0 is +0.0).  The table IS the definition."""
+    g1, g2 = ar2_coefficients(g, rise)
+    if isinstance(T, (bool, np.bool_)) or not isinstance(T, (int, np.integer)) or T < 0:
+        raise ValueError('T must be a non-negative integer, not %r' % (T,))
+    T = int(T)
+    h = [1.0, g1]
+    for k in range(2, T + 1):                  # plain floats: one rounding per operation, in this order
+        h.append(g1 * h[k - 1] + g2 * h[k - 2])
+    H = np.zeros((3, T + 1), np.float64)
+    H[0] = h[:T + 1]
+    if T:
+        prod = np.zeros(T, np.float64)
+        H[1, 1:] = np.add.accumulate(H[0, :T] * H[0, :T])              # a sequential left fold, like ar1_table's
+        prod[1:] = H[0, 1:T] * H[0, :T - 1]
+        H[2, 1:] = np.add.accumulate(prod)
+    return H
+
+
+def ar2_peak(g, rise):
+    """The frame at which the response h to one spike peaks: the first k with h[k+1] <= h[k]."""
+    g1, g2 = ar2_coefficients(g, rise)
+    a, b, k = 1.0, g1, 0
+    while b > a:
+        a, b, k = b, g1 * b + g2 * a, k + 1
+    return k
+
+
 def trace_noise(y):
     """Per row of an (R, T) matrix: d = diff(float64(y)), sigma = 1.4826 * median(|d - median(d)|) / sqrt(2), the robust noise of
     the trace from its first difference.  0.0 for T < 3.  float64[R]."""
@@ -217,7 +277,8 @@ class TraceDeconvolver(_MatrixStage):
     kernels run at most once; result() only copies."""
     _noun = 'deconvolution'
 
-    def __init__(self, traces, g, s_min=0.0, lam=0.0, constrain=None, sigma=None, rounds=24, device=None, baseline=0.0, baseline_rounds=8):
+    def __init__(self, traces, g, s_min=0.0, lam=0.0, constrain=None, sigma=None, rounds=24, device=None, baseline=0.0, baseline_rounds=8,
+                 rise=None):
         """traces: (R, T) float32 or float64, numpy (checked for non-finite values) or a tensor already on the device (read in
         place, never written; THE CALLER PROMISES FINITE VALUES).  g in (0, 1): a scalar -- one decay and one table for all traces
         -- or an array of one value per trace (e.g. pick_gamma's g_each): the tables are then built on the device, one row per
@@ -228,9 +289,16 @@ class TraceDeconvolver(_MatrixStage):
         THAT RANGE).  baseline: one constant per trace that leaves the data inside the forward pass -- a scalar, one value per
         trace (finite), a float64 tensor on the device (read in place; THE CALLER PROMISES FINITE VALUES), or 'fit': estimated
         per trace on the device from 0, by baseline_rounds steps in [1, 64] at the given s_min and lam, or, with constrain=,
-        by one step in every round of the search (baseline_rounds is then not used).  A given baseline cannot go with constrain=."""
+        by one step in every round of the search (baseline_rounds is then not used).  A given baseline cannot go with constrain=.
+        rise: None, or the second root of the AR(2) model, a scalar with 0 < rise < g < 1 (g is then a scalar too, the decay):
+        everything else works as without it, but baseline='fit' and a decay per trace are not built for AR(2)."""
         # ---- everything that can be wrong with the arguments is a ValueError before the library or the GPU is touched ----
         R, T, f64 = _check_traces(traces)
+        self.rise = None
+        if rise is not None:
+            g, self.rise = _check_roots(g, rise)
+            if isinstance(baseline, str) and baseline == 'fit':
+                raise ValueError("baseline='fit' is not built for AR(2) (rise=): give the baseline or leave it out")
         self._each = np.ndim(g) != 0
         if self._each:
             self.g = _per_trace_gamma(g, R)
@@ -255,7 +323,10 @@ class TraceDeconvolver(_MatrixStage):
         self.baseline = _check_baseline(baseline, baseline_rounds, R, constrain is not None)
         self._fit = isinstance(self.baseline, str)                     # 'fit'; otherwise None or the values given
         self.baseline_rounds = int(baseline_rounds) if self._fit else None
-        table = None if self._each else ar1_table(self.g, T)
+        if self.rise is not None:
+            table = ar2_table(self.g, self.rise, T)
+        else:
+            table = None if self._each else ar1_table(self.g, T)
         self.n_traces, self.n_frames = R, T
 
         self._open(device, like=traces)
@@ -286,7 +357,8 @@ class TraceDeconvolver(_MatrixStage):
         if self._out is not None:
             return self._out
         R, T, L = self.n_traces, self.n_frames, self.L
-        ws = self._empty(L.dc_trace_deconv_ws_bytes(R, T) // 8, 'float64')     # it goes back to the allocator (stream-ordered)
+        ws_bytes = L.dc_trace_deconv_ws_bytes if self.rise is None else L.dc_trace_deconv_ar2_ws_bytes
+        ws = self._empty(ws_bytes(R, T) // 8, 'float64')                       # it goes back to the allocator (stream-ordered)
         c, s, n = self._empty((R, T), 'float64'), self._empty((R, T), 'float64'), self._empty(R, 'int32')
         out = dict(calcium=c, spikes=s, pools=n)
         y, f64 = self._y.data_ptr(), int(self._f64)
@@ -311,10 +383,19 @@ class TraceDeconvolver(_MatrixStage):
                 state = self._empty(state_bytes(R) // 8, 'float64')
                 out.update(param=self._empty(R, 'float64'), rss=self._empty(R, 'float64'), status=self._empty(R, 'int32'))
                 other = self._lam if self.constrain == 's_min' else self._smin
-                head = traces + (CONSTRAIN[self.constrain], self._sigma.data_ptr(), other.data_ptr(), self.rounds, ws.data_ptr(),
-                                 state.data_ptr()) + results + (out['param'].data_ptr(),)
+                # what every search takes after its model: the same for AR(1) and AR(2)
+                sought = (CONSTRAIN[self.constrain], self._sigma.data_ptr(), other.data_ptr(), self.rounds, ws.data_ptr(),
+                          state.data_ptr()) + results + (out['param'].data_ptr(),)
+                head = traces + sought
                 found = (out['rss'].data_ptr(), out['status'].data_ptr())
-            if search and self._fit:                               # the threshold and the baseline, jointly
+            if self.rise is not None:                              # AR(2): one pair of roots, one table of three rows
+                g1, g2 = ar2_coefficients(self.g, self.rise)
+                model = (y, f64, self._ld, R, T, g1, g2, G.data_ptr(), T + 1)
+                if search:
+                    L.dc_trace_deconv_ar2_constrained(*model, *sought, *found, stream)
+                else:
+                    L.dc_trace_deconv_ar2(*model, lam, smin, None if self.baseline is None else base, ws.data_ptr(), *results, stream)
+            elif search and self._fit:                             # the threshold and the baseline, jointly
                 L.dc_trace_deconv_ar1_constrained_base(*head, base, *found, stream)
             elif search:
                 L.dc_trace_deconv_ar1_constrained(*head, *found, stream)
@@ -354,7 +435,7 @@ class TraceDeconvolver(_MatrixStage):
 
 
 def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0, details=False, lags=5, g_min=0.05, g_max=0.998, baseline=0.0,
-                             **dff_kw):
+                             tau_rise=None, **dff_kw):
     """-> (calcium, spikes), float64 (R, T): the dF/F traces of `rois` over a dataset file (dff_traces_device(dspath, rois, window,
     **dff_kw)) deconvolved with s_min = k * sigma_hat per trace and the penalty lam.  tau: a number -- the decay time in seconds,
     g = ar1_gamma(tau, fps) --, 'auto' -- the decay is estimated per trace from the dF/F (deep_calcium_amd.dynamics: TraceDynamics
@@ -367,10 +448,19 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
     baseline: TraceDeconvolver's -- a scalar, or 'fit': one constant per trace estimated on the device; info['baseline'] is
     float64[R], the values used.  Recommended: k='noise' with baseline='fit' -- dF/F over a low percentile sits about one sigma
     above zero when the cell is quiet, which the search alone pays for with spurious events.  With a numeric k the fit is only as
-    good as the threshold (one that is too high lets missed events lift the baseline)."""
+    good as the threshold (one that is too high lets missed events lift the baseline).  tau_rise: the rise time in seconds of an
+    AR(2) model, rise = ar1_gamma(tau_rise, fps) (TraceDeconvolver(rise=)); it needs a numeric tau above it, and baseline='fit' is
+    not built for it; info then also has rise=."""
     mode = tau if isinstance(tau, str) else None
     if mode is not None and mode not in ('auto', 'each'):
         raise ValueError("tau must be a number of seconds, 'auto' or 'each', not %r" % (tau,))
+    rise = None
+    if tau_rise is not None:
+        if mode is not None:
+            raise ValueError('tau_rise needs a number of seconds for tau: estimating the decay (tau=%r) is not built for AR(2)' % (tau,))
+        if isinstance(baseline, str) and baseline == 'fit':
+            raise ValueError("baseline='fit' is not built for AR(2) (tau_rise=)")
+        rise = _check_roots(ar1_gamma(tau, fps), ar1_gamma(tau_rise, fps))[1]
     if mode is None:
         g = ar1_gamma(tau, fps)
     else:
@@ -402,12 +492,14 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
     dff = dff_traces_device(dspath, rois, window, **dff_kw)
     if mode is None:
         if search:
-            dec = TraceDeconvolver(dff, g, lam=lam, constrain='s_min', device=dff_kw.get('device'), baseline=baseline)
+            dec = TraceDeconvolver(dff, g, lam=lam, constrain='s_min', device=dff_kw.get('device'), baseline=baseline, rise=rise)
             sigma = dec.sigma_device.cpu().numpy()
         else:
             sigma = trace_noise(dff)
-            dec = TraceDeconvolver(dff, g, s_min=k * sigma, lam=lam, device=dff_kw.get('device'), baseline=baseline)
+            dec = TraceDeconvolver(dff, g, s_min=k * sigma, lam=lam, device=dff_kw.get('device'), baseline=baseline, rise=rise)
         info = dict(g=g, g_raw=None, status=None, sigma=sigma, pooled=None)
+        if rise is not None:
+            info['rise'] = rise
     else:
         from .dynamics import TraceDynamics
         dyn = TraceDynamics(dff, lags=lags, device=dff_kw.get('device'))

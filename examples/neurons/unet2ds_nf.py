@@ -7,7 +7,7 @@
     python examples/neurons/unet2ds_nf.py evaluate neurofinder.00.00 --model unet2ds_model.hdf5
     python examples/neurons/unet2ds_nf.py train all_train [-m model.hdf5] [-c checkpoints_dir]
     python examples/neurons/unet2ds_nf.py predict all_test --model unet2ds_model.hdf5
-    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve auto|each|TAU [--fps F] [--spike-k K | --spike-constrain s_min|lam] [--spike-baseline fit|VALUE]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
+    python examples/neurons/unet2ds_nf.py traces neurofinder.00.00 --model unet2ds_model.hdf5 [--kind mean|zscore|sum] [--register [S] [--blocks ByxBx [--max-dev D]] [--coarse C] [--subpixel]] [--bidi [P]] [--dff WINDOW [--percentile Q] [--neuropil INNER,OUTER,WEIGHT] [--deconvolve auto|each|TAU [--fps F] [--spike-rise TAU_RISE] [--spike-k K | --spike-constrain s_min|lam] [--spike-baseline fit|VALUE]]] [--refine THR [--halo N]] [--split [GAP] [--min-area N]] [--bin-frames B] [--detrend L] [--merge [THR] [--merge-dist D]] [--weighted [FLOOR] [--overlap keep|exclude|demix]]
 
 `--model` takes the reference's own files: the released Keras `unet2ds_model.hdf5`
 (unet_2d_summary.py:28), any Keras ModelCheckpoint file, or a checkpoint written by this build.  With the released
@@ -37,6 +37,7 @@ from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, wr
                               footprint_weights, exclude_overlap, weighted_traces_device, TraceDeconvolver, ar1_gamma, trace_noise,
                               TraceDynamics, pick_gamma, ar1_tau)
 from deep_calcium_amd.weighted import shared_pixels            # noqa: E402
+from deep_calcium_amd.deconv import ar2_coefficients, ar2_peak   # noqa: E402
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
 from deep_calcium_amd.nf_datasets import nf_load_hdf5, default_dirs      # noqa: E402
 
@@ -157,7 +158,7 @@ def _n_frames(dspath):
 def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None, blocks=None, max_dev=3, subpixel=False, dff=None,
            percentile=8, neuropil=None, refine=None, halo=2, coarse=None, split=None, min_area=8, bidi=None,
            bin_frames=None, detrend=None, merge=None, merge_dist=2, drop_artefacts=None, weighted=None, overlap='keep', deconvolve=None,
-           fps=None, spike_k=3.0, spike_constrain=None, spike_baseline=None):
+           fps=None, spike_k=3.0, spike_constrain=None, spike_baseline=None, spike_rise=None):
     """Mask -> traces: predict each dataset's neurons (with TTA), take the 8-connected regions of the rounded mask as ROIs and
     write `<checkpoints_dir>/<name>_traces.hdf5` with one trace per region over `series/raw` (no reference counterpart: its spikes
     model starts from such a file).  register=S: the frames of `series/raw` are first registered on the GPU (rigid, whole pixels,
@@ -213,7 +214,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     deconvolution, on the GPU (TraceDeconvolver(baseline='fit')): dF/F over a low percentile sits about one sigma_hat above zero
     when the cell is quiet, which costs spurious events; recommended together with spike_constrain, since with a spike_k that is
     too high the missed events lift the fitted baseline.  spike_baseline=VALUE (not with spike_constrain): that constant is taken
-    off every trace."""
+    off every trace.  spike_rise=TAU_RISE (with deconvolve=TAU, not auto or each, and not with spike_baseline='fit'): the indicator's
+    rise time in seconds; the model is then AR(2) with the roots exp(-1 / (TAU F)) and exp(-1 / (TAU_RISE F))
+    (TraceDeconvolver(rise=)), which keeps an event whose fluorescence takes several frames to peak from being reported as a run
+    of spikes."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -249,6 +253,16 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     if deconvolve is not None and not spike_k >= 0:
         raise ValueError('--spike-k is the smallest spike in units of the trace noise, K >= 0, not %r' % (spike_k,))
     g = None if deconvolve is None or estimated else ar1_gamma(deconvolve, fps)
+    rise = None
+    if spike_rise is not None:
+        if g is None:
+            raise ValueError('--spike-rise needs --deconvolve TAU: estimating the decay (auto, each) is not built for AR(2)')
+        if spike_baseline == 'fit':
+            raise ValueError('--spike-baseline fit is not built for AR(2) (--spike-rise)')
+        rise = ar1_gamma(spike_rise, fps)
+        if not rise < g:
+            raise ValueError('--spike-rise must be shorter than the decay time: TAU_RISE = %r against TAU = %r' % (spike_rise, deconvolve))
+        base_kw = dict(base_kw, rise=rise)
     if estimated and fps is not None:
         ar1_gamma(1.0, fps)
     if bin_frames is not None and refine is None and split is None:
@@ -427,6 +441,10 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
                         'events per ROI min / median / max = %d / %g / %d' % (name, g, deconvolve, fps, 0.0 if spike_constrain == 'lam' else spike_k,
                                                                               float(np.median(sigma)), int(events.min()), float(np.median(events)),
                                                                               int(events.max())))
+            if rise is not None:
+                g1, g2 = ar2_coefficients(g, rise)
+                logger.info('%s: AR(2) (--spike-rise %g s): d = %.6f, r = %.6f, g1 = %.6f, g2 = %.6f; the response to one spike peaks at frame %d'
+                            % (name, spike_rise, g, rise, g1, g2, ar2_peak(g, rise)))
         if extra is not None and spike_constrain is not None:
             found, st = dec.result('param'), dec.result('status')
             ratio = found[sigma > 0] / sigma[sigma > 0] if (sigma > 0).any() else np.zeros(1)
@@ -493,6 +511,8 @@ if __name__ == '__main__':
     sp_trc.add_argument('--fps', help='with --deconvolve: the frame rate of the recording in frames per second', default=None, type=float, metavar='F')
     sp_trc.add_argument('--spike-k', help='with --deconvolve: the smallest spike allowed, in units of every trace\'s noise (default 3)', default=3.0,
                         type=float, metavar='K', dest='spike_k')
+    sp_trc.add_argument('--spike-rise', help='with --deconvolve TAU: the rise time of the indicator in seconds; the model is then AR(2), with the '
+                        'roots exp(-1 / (TAU F)) and exp(-1 / (TAU_RISE F))', default=None, type=float, metavar='TAU_RISE', dest='spike_rise')
     sp_trc.add_argument('--spike-constrain', help='with --deconvolve, instead of --spike-k: search s_min (for events) or lam (for a denoised calcium) '
                         'per trace until the residual equals the trace noise', default=None, choices=('s_min', 'lam'), dest='spike_constrain')
     sp_trc.add_argument('--spike-baseline', help='with --deconvolve: fit one constant per trace inside the deconvolution (fit; recommended with '
@@ -531,6 +551,11 @@ if __name__ == '__main__':
         ap.error('--deconvolve needs --dff: the deconvolution has no baseline term')
     if args['which'] == 'traces' and args['deconvolve'] is not None and not isinstance(args['deconvolve'], str) and args['fps'] is None:
         ap.error('--deconvolve needs --fps')
+    if args['which'] == 'traces' and args['spike_rise'] is not None:
+        if args['deconvolve'] is None or isinstance(args['deconvolve'], str):
+            ap.error('--spike-rise needs --deconvolve TAU: estimating the decay (auto, each) is not built for AR(2)')
+        if args['spike_baseline'] == 'fit':
+            ap.error('--spike-baseline fit is not built for AR(2) (--spike-rise)')
     if args['which'] == 'traces' and args['spike_constrain'] is not None:
         if any(a == '--spike-k' or a.startswith('--spike-k=') for a in sys.argv[1:]):
             ap.error('--spike-constrain searches the threshold: not together with --spike-k')
