@@ -235,7 +235,7 @@ class _TwoSlotStage(object):
 
 class _FrameReader(object):
     """A reader that is fed the frames of a recording in order.  A subclass's __init__ calls _declare() (host only), makes its own
-    checks, calls _open() (the device) and allocates its state; it defines _chunk() and result().
+    checks, calls _open() (the device), allocates its state and ends with _constructed(); it defines _chunk() and result().
 
     _stage_tag names the reader's pinned staging slots (cached by name: two readers alive at once never share one); _noun is what
     the reader is called where a tensor lies on another device."""
@@ -255,7 +255,7 @@ class _FrameReader(object):
             self._known = _check_known_shifts(shifts, fine_shifts, self.n_frames, self.shape) + (_check_bidi(bidi, self.shape),)
         self._unsigned = int(self.dtype == np.dtype(np.uint16))
         self.fed = 0
-        self._stage = self._shifted = None
+        self._stage = self._shifted = self._ready = None
 
     def _open(self, device, name):
         """The device: torch, the library, the normalised device, and the corrections _declare() checked.  -> torch."""
@@ -268,6 +268,14 @@ class _FrameReader(object):
 
     def _stream(self):
         return self._torch.cuda.current_stream(self.device)
+
+    def _constructed(self):
+        """The last call of a constructor, on the stream it ran on: an event behind everything it enqueued there (the fills of
+        torch.zeros / torch.full, a kernel).  feed() waits for it on its own stream, so a reader may be fed on another stream
+        than the one it was made on.  The owner of a _LeadingExtractor calls it again once its own state is made."""
+        with self._torch.cuda.device(self.device):
+            self._ready = self._torch.cuda.Event()
+            self._ready.record(self._stream())
 
     def _check_frames(self, frames):
         """The argument of a feed(): type, shape and dtype against the declaration -> whether it lies on the device."""
@@ -308,6 +316,7 @@ class _FrameReader(object):
             raise ValueError('%d frames after %d fed: the recording was declared to have %d' % (t, self.fed, self.n_frames))
         with self._torch.cuda.device(self.device):
             main = self._stream()
+            main.wait_event(self._ready)                # the constructor's fills and launches, on whichever stream it ran
             st = main.cuda_stream
             out, needed = self._begin_feed(t)
 

@@ -175,6 +175,7 @@ class RoiFootprints(object):
             self._pss = torch.zeros((self.n_rois, 2), dtype=torch.int64, device=dev)
             self._rmom = torch.empty((3, self.n_rois), dtype=torch.int64, device=dev)
         self._corr = None
+        ext._constructed()               # again: the fills above belong to what its feed() waits for
 
     @property
     def fed(self):

@@ -160,6 +160,7 @@ class FrameQuality(_FrameReader):
                                         self._tsums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
             # rows [0, fed) are written, each by the call that reads its frame: never cleared here
             self._moments = torch.empty((self.n_frames, 3), dtype=torch.int64, device=dev)
+        self._constructed()
 
     def _chunk(self, fp, tc, t0, st):
         (H, W), (y0, y1, x0, x1) = self.shape, self.rect
@@ -221,6 +222,7 @@ class FrameFilter(_FrameReader):
 
         torch = self._open(device, 'FrameFilter')
         self._kept_dev = torch.from_numpy(self._kept).to(self.device)      # the kept frames' indices in the recording, ascending
+        self._constructed()
 
     def feed(self, frames):
         """The next frames of the recording, any t >= 1: what SeriesSummarizer.feed takes.  -> the kept ones among them: a

@@ -318,7 +318,6 @@ class MotionCorrector(_FrameReader):
             with torch.cuda.device(dev):
                 self.L.dc_motion_bin(self._tmpl.data_ptr(), self._unsigned, 1, H, W, c, self._tmpl_c.data_ptr(),
                                      self._stream().cuda_stream)
-                self._stream().synchronize()         # feed() may run on another stream
         if self.blocks is not None:
             (By, Bx), nb = self.blocks, 2 * self.max_dev + 1
             self._bshifts = torch.zeros((n_frames, By, Bx, 2), dtype=torch.int32, device=dev)
@@ -327,6 +326,7 @@ class MotionCorrector(_FrameReader):
             self._fine = torch.zeros((n_frames, 2) if self.blocks is None else (n_frames,) + self.blocks + (2,), dtype=torch.int32, device=dev)
         if self.bidi:                      # one chunk of frames whose odd lines have been moved: what everything below reads
             self._bidi_scratch = torch.empty((self.chunk_frames, H, W), dtype=torch.int16, device=dev)
+        self._constructed()                # feed() may run on another stream: it waits for the fills and the binned template
 
     def _register(self, fp, tc, t0, out, st):
         """The launches of one piece of at most chunk_frames frames at fp, frames [t0, t0 + tc); out: where the corrected frames
@@ -584,6 +584,7 @@ class BidiEstimator(_FrameReader):
             raise ValueError('shape must be (H, W) with H * W <= 2**28 for the scan-phase search, not %r' % (self.shape,))
         self._tables = []                  # one (t, 2P+1) int64 tensor per piece, in order
         self._open(device, 'BidiEstimator')
+        self._constructed()
 
     def feed(self, frames):
         """The next frames, any t >= 1: a (t, H, W) numpy array or memmap of the recording's dtype (staged through two pinned
@@ -598,6 +599,7 @@ class BidiEstimator(_FrameReader):
         P = self.max_offset
         with torch.cuda.device(self.device):
             main = self._stream()
+            main.wait_event(self._ready)
             st = main.cuda_stream
 
             def piece(fp, tc):

@@ -132,6 +132,7 @@ class RoiPairCorr(object):
         self._g = torch.zeros((G,), dtype=torch.int64, device=dev)
         self._pooled = torch.zeros((G, 2), dtype=torch.int64, device=dev) if self._seg is not None else None      # 16-byte {lo, hi} words
         self._corr = None
+        ext._constructed()               # again: the fills above belong to what its feed() waits for
 
     @property
     def fed(self):

@@ -154,6 +154,7 @@ class SeriesSummarizer(_FrameReader):
             self._pcov = torch.zeros((4, n, 2), dtype=torch.int64, device=dev) if self._xy else None
             self._sum_total = torch.zeros(n, dtype=torch.int64, device=dev)
             self._vmax_total = torch.full((n,), -2 ** 31, dtype=torch.int32, device=dev)
+        self._constructed()
 
     def _chunk(self, fp, tc, t0, st):
         H, W = self.shape
@@ -290,6 +291,7 @@ class TemporalBinner(_FrameReader):
         torch = self._open(device, 'TemporalBinner')
         # the open bin's sum: read only once a call has left frames in it, so never cleared here
         self._carry = torch.empty(self.shape[0] * self.shape[1], dtype=torch.int32, device=self.device)
+        self._constructed()
 
     def feed(self, frames):
         """The next frames of the recording, any t >= 1: what SeriesSummarizer.feed takes (numpy or memmap chunks of the

@@ -117,6 +117,7 @@ class RoiTraceExtractor(_FrameReader):
         self._rows = len(row_roi)
         # every chunk writes its own columns of every row, so the state is never cleared
         self.sums = torch.empty((self.n_rois, self.n_frames), dtype=torch.int64, device=dev)
+        self._constructed()
 
     def _launch(self, fp, tc, t0, st):
         """The sums of one chunk (weighted.WeightedTraceExtractor: the weighted entry point instead)."""

@@ -134,6 +134,7 @@ class WeightedTraceExtractor(RoiTraceExtractor):
         self.areas = wsums.astype(np.int32)               # W_r stands where the area stood (finalize, TraceBaseline, TracePairCorr)
         self._areas = self._torch.from_numpy(self.areas).to(self.device)
         self._row_wgt = self._torch.from_numpy(row_wgt.view(np.int16)).to(self.device)
+        self._constructed()
 
     def _launch(self, fp, tc, t0, st):
         H, W = self.shape
