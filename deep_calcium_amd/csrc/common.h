@@ -27,6 +27,11 @@ const DcConfig& dc_config();
     }                                      \
   } while (0)
 
+// The frames of one call (include/dcunet.h, DC_FRAMES_PER_CALL_MAX), after the sign check of tc: below it 2 * f and f + gridDim fit an int.
+#define DC_REQUIRE_FRAMES(who, tc)                                                                                                    \
+  DC_REQUIRE((long)(tc) <= DC_FRAMES_PER_CALL_MAX, DC_EUNSUP, "%s: tc = %d: the frames of one call are limited to 2^30 = %ld", who, tc, \
+             (long)DC_FRAMES_PER_CALL_MAX)
+
 // Check the launch that just happened (asynchronous: catches configuration errors only).
 #define DC_CHECK_LAUNCH(name)                                               \
   do {                                                                      \

@@ -252,6 +252,7 @@ extern "C" int dc_roi_pixel_accumulate(const void* frames, int is_unsigned, int 
   DC_REQUIRE(frames && row_off && row_pix && sums && mom, DC_EINVAL, "dc_roi_pixel_accumulate: null pointer");
   DC_REQUIRE(S >= 0 && R >= 0 && N >= 0 && tc >= 0 && t0 >= 0, DC_EINVAL,
              "dc_roi_pixel_accumulate: negative count (S %d, R %d, N %d, tc %d, t0 %ld)", S, R, N, tc, t0);
+  DC_REQUIRE_FRAMES("dc_roi_pixel_accumulate", tc);
   DC_REQUIRE(row_roi || S == R, DC_EINVAL, "dc_roi_pixel_accumulate: without row_roi every CSR row is an ROI, but S = %d and R = %d", S, R);
   DC_REQUIRE(ld >= t0 + tc, DC_EINVAL, "dc_roi_pixel_accumulate: ld = %ld is below t0 + tc = %ld", ld, t0 + tc);
   DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "dc_roi_pixel_accumulate: image %d x %d out of range", H, W);

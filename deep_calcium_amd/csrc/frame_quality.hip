@@ -152,6 +152,7 @@ extern "C" int dc_frame_moments(const void* frames, int is_unsigned, int tc, con
                                 long* moments, dc_stream_t stream) {
   DC_REQUIRE(frames && moments, DC_EINVAL, "dc_frame_moments: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_frame_moments: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE_FRAMES("dc_frame_moments", tc);
   DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_frame_moments: image %d x %d: H * W is limited to 2^30", H, W);
   const int64_t n = dc_frame_rect_pixels(H, W, y0, y1, x0, x1);
   DC_REQUIRE(n > 0, DC_EINVAL, "dc_frame_moments: the rectangle [%d, %d) x [%d, %d) is empty or leaves the %d x %d frame", y0, y1, x0, x1, H, W);
@@ -177,6 +178,7 @@ extern "C" int dc_frame_moments(const void* frames, int is_unsigned, int tc, con
 extern "C" int dc_frame_quality(const long* moments, int tc, long n, long ta, long tb, float* mean, float* corr, dc_stream_t stream) {
   DC_REQUIRE(moments && mean, DC_EINVAL, "dc_frame_quality: null pointer");
   DC_REQUIRE(tc >= 0, DC_EINVAL, "dc_frame_quality: negative count (tc %d)", tc);
+  DC_REQUIRE_FRAMES("dc_frame_quality", tc);
   DC_REQUIRE(n >= 1, DC_EINVAL, "dc_frame_quality: n = %ld pixels", n);
   DC_REQUIRE(n <= DC_FRAME_MAX_PIXELS, DC_EUNSUP, "dc_frame_quality: n = %ld pixels: limited to 2^28 = %ld", n, (long)DC_FRAME_MAX_PIXELS);
   DC_REQUIRE((((uintptr_t)moments) & 7) == 0 && ((((uintptr_t)mean) | ((uintptr_t)corr)) & 3) == 0, DC_EINVAL,
@@ -191,6 +193,7 @@ extern "C" int dc_frame_quality(const long* moments, int tc, long n, long ta, lo
 
 extern "C" int dc_frame_gather(const void* frames, int tc, const int* idx, int k, int H, int W, void* out, dc_stream_t stream) {
   DC_REQUIRE(tc >= 0 && k >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_frame_gather: negative or zero size (tc %d, k %d, H %d, W %d)", tc, k, H, W);
+  DC_REQUIRE_FRAMES("dc_frame_gather", tc);
   DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_frame_gather: image %d x %d: H * W is limited to 2^30", H, W);
   if (k == 0) return DC_OK;
   DC_REQUIRE(frames && idx && out, DC_EINVAL, "dc_frame_gather: null pointer");

@@ -384,7 +384,7 @@ __global__ __launch_bounds__(kThreads) void motion_apply_kernel(const uint16_t* 
 __global__ __launch_bounds__(kThreads) void motion_refine_kernel(const int64_t* __restrict__ scores, const int* __restrict__ shifts, int tc,
                                                                 int S, int* __restrict__ fine) {
   const long n = (2 * S + 1) * (2 * S + 1);
-  for (int f = blockIdx.x * kThreads + threadIdx.x; f < tc; f += gridDim.x * kThreads) {
+  for (long f = (long)blockIdx.x * kThreads + threadIdx.x; f < tc; f += (long)gridDim.x * kThreads) {
     const int dy = shifts[2 * f], dx = shifts[2 * f + 1];
     const DcSubShift q = dc_motion_refine_entry(scores + f * n, S, dy, dx);
     fine[2 * f] = dc_motion_fine(dy, q.qy);
@@ -902,6 +902,7 @@ extern "C" int dc_motion_ssd(const void* frames, int is_unsigned, int tc, const 
                              dc_stream_t stream) {
   DC_REQUIRE(frames && tmpl && scores, DC_EINVAL, "dc_motion_ssd: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_ssd: negative or zero size (tc %d, S %d, H %d, W %d)", tc, S, H, W);
+  DC_REQUIRE_FRAMES("dc_motion_ssd", tc);
   DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, "dc_motion_ssd: S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);
   DC_REQUIRE_IMAGE("dc_motion_ssd", H, W);
   DC_REQUIRE(H > 2 * S && W > 2 * S, DC_EINVAL, "dc_motion_ssd: image %d x %d has no interior at S = %d (H > 2S and W > 2S)", H, W, S);
@@ -913,6 +914,7 @@ extern "C" int dc_motion_ssd(const void* frames, int is_unsigned, int tc, const 
 extern "C" int dc_motion_pick(const long* scores, int tc, int S, int* shifts, long* best, dc_stream_t stream) {
   DC_REQUIRE(scores && shifts, DC_EINVAL, "dc_motion_pick: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0, DC_EINVAL, "dc_motion_pick: negative size (tc %d, S %d)", tc, S);
+  DC_REQUIRE_FRAMES("dc_motion_pick", tc);
   DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, "dc_motion_pick: S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);
   DC_REQUIRE((((uintptr_t)scores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)shifts) & 3) == 0, DC_EINVAL, "dc_motion_pick: misaligned buffer");
   return launch_pick("dc_motion_pick", scores, nullptr, 0, tc, S, S, shifts, best, nullptr, (hipStream_t)stream);
@@ -921,6 +923,7 @@ extern "C" int dc_motion_pick(const long* scores, int tc, int S, int* shifts, lo
 extern "C" int dc_motion_apply(const void* frames, int tc, const int* shifts, int H, int W, int fill, void* out, dc_stream_t stream) {
   DC_REQUIRE(frames && shifts && out, DC_EINVAL, "dc_motion_apply: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_apply: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE_FRAMES("dc_motion_apply", tc);
   DC_REQUIRE_IMAGE("dc_motion_apply", H, W);
   DC_REQUIRE_MOVE("dc_motion_apply", frames, shifts, out, tc, H, W, fill);
   return launch_apply<false>("dc_motion_apply", frames, 0u, tc, shifts, H, W, fill, out, (hipStream_t)stream);
@@ -931,6 +934,7 @@ extern "C" int dc_motion_block_ssd(const void* frames, int is_unsigned, int tc, 
   DC_REQUIRE(frames && tmpl && rigid && bscores, DC_EINVAL, "dc_motion_block_ssd: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL,
              "dc_motion_block_ssd: negative or zero size (tc %d, S %d, D %d, H %d, W %d, blocks %d x %d)", tc, S, D, H, W, By, Bx);
+  DC_REQUIRE_FRAMES("dc_motion_block_ssd", tc);
   DC_REQUIRE_GRID("dc_motion_block_ssd", S, D, By, Bx);
   DC_REQUIRE_IMAGE("dc_motion_block_ssd", H, W);
   DC_REQUIRE(dc_block_axis_ok(H, By, S + D) && dc_block_axis_ok(W, Bx, S + D), DC_EINVAL,
@@ -948,6 +952,7 @@ extern "C" int dc_motion_block_pick(const long* bscores, const int* rigid, int t
   DC_REQUIRE(bscores && rigid && block_shifts, DC_EINVAL, "dc_motion_block_pick: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && By > 0 && Bx > 0, DC_EINVAL,
              "dc_motion_block_pick: negative or zero size (tc %d, S %d, D %d, blocks %d x %d)", tc, S, D, By, Bx);
+  DC_REQUIRE_FRAMES("dc_motion_block_pick", tc);
   DC_REQUIRE_GRID("dc_motion_block_pick", S, D, By, Bx);
   DC_REQUIRE((((uintptr_t)bscores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)rigid | (uintptr_t)block_shifts) & 3) == 0, DC_EINVAL,
              "dc_motion_block_pick: misaligned buffer");
@@ -964,6 +969,7 @@ extern "C" int dc_motion_warp(const void* frames, int tc, const int* block_shift
   DC_REQUIRE(frames && block_shifts && out, DC_EINVAL, "dc_motion_warp: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL, "dc_motion_warp: negative or zero size (tc %d, H %d, W %d, blocks %d x %d)",
              tc, H, W, By, Bx);
+  DC_REQUIRE_FRAMES("dc_motion_warp", tc);
   DC_REQUIRE_WARP("dc_motion_warp", frames, block_shifts, out, tc, By, Bx, H, W, fill);
   return launch_warp<false>("dc_motion_warp", frames, 0u, tc, block_shifts, By, Bx, H, W, fill, out, (hipStream_t)stream);
 }
@@ -971,6 +977,7 @@ extern "C" int dc_motion_warp(const void* frames, int tc, const int* block_shift
 extern "C" int dc_motion_refine(const long* scores, const int* shifts, int tc, int S, int* fine, dc_stream_t stream) {
   DC_REQUIRE(scores && shifts && fine, DC_EINVAL, "dc_motion_refine: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0, DC_EINVAL, "dc_motion_refine: negative size (tc %d, S %d)", tc, S);
+  DC_REQUIRE_FRAMES("dc_motion_refine", tc);
   DC_REQUIRE(S <= DC_MOTION_MAX_SHIFT, DC_EUNSUP, "dc_motion_refine: S = %d: the search radius is limited to %d", S, DC_MOTION_MAX_SHIFT);
   DC_REQUIRE((((uintptr_t)scores) & 7) == 0 && (((uintptr_t)shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL, "dc_motion_refine: misaligned buffer");
   if (tc == 0) return DC_OK;
@@ -985,6 +992,7 @@ extern "C" int dc_motion_block_refine(const long* bscores, const int* rigid, con
   DC_REQUIRE(bscores && rigid && block_shifts && fine, DC_EINVAL, "dc_motion_block_refine: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && By > 0 && Bx > 0, DC_EINVAL,
              "dc_motion_block_refine: negative or zero size (tc %d, S %d, D %d, blocks %d x %d)", tc, S, D, By, Bx);
+  DC_REQUIRE_FRAMES("dc_motion_block_refine", tc);
   DC_REQUIRE_GRID("dc_motion_block_refine", S, D, By, Bx);
   DC_REQUIRE((((uintptr_t)bscores) & 7) == 0 && (((uintptr_t)rigid | (uintptr_t)block_shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL,
              "dc_motion_block_refine: misaligned buffer");
@@ -1000,6 +1008,7 @@ extern "C" int dc_motion_apply_sub(const void* frames, int is_unsigned, int tc, 
                                    dc_stream_t stream) {
   DC_REQUIRE(frames && fine && out, DC_EINVAL, "dc_motion_apply_sub: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_apply_sub: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE_FRAMES("dc_motion_apply_sub", tc);
   DC_REQUIRE_IMAGE("dc_motion_apply_sub", H, W);
   DC_REQUIRE_MOVE("dc_motion_apply_sub", frames, fine, out, tc, H, W, fill);
   return launch_apply<true>("dc_motion_apply_sub", frames, is_unsigned ? 0u : 0x8000u, tc, fine, H, W, fill, out, (hipStream_t)stream);
@@ -1010,6 +1019,7 @@ extern "C" int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, c
   DC_REQUIRE(frames && fine_block_shifts && out, DC_EINVAL, "dc_motion_warp_sub: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0 && By > 0 && Bx > 0, DC_EINVAL,
              "dc_motion_warp_sub: negative or zero size (tc %d, H %d, W %d, blocks %d x %d)", tc, H, W, By, Bx);
+  DC_REQUIRE_FRAMES("dc_motion_warp_sub", tc);
   DC_REQUIRE_WARP("dc_motion_warp_sub", frames, fine_block_shifts, out, tc, By, Bx, H, W, fill);
   return launch_warp<true>("dc_motion_warp_sub", frames, is_unsigned ? 0u : 0x8000u, tc, fine_block_shifts, By, Bx, H, W, fill, out,
                            (hipStream_t)stream);
@@ -1018,6 +1028,7 @@ extern "C" int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, c
 extern "C" int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H, int W, int c, void* out, dc_stream_t stream) {
   DC_REQUIRE(frames && out, DC_EINVAL, "dc_motion_bin: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_bin: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE_FRAMES("dc_motion_bin", tc);
   const int lg = dc_motion_bin_log2(c);
   DC_REQUIRE(lg > 0, DC_EUNSUP, "dc_motion_bin: c = %d: the binning factor is limited to 2, 4 and 8", c);
   DC_REQUIRE_IMAGE("dc_motion_bin", H, W);
@@ -1037,6 +1048,7 @@ extern "C" int dc_motion_ssd_around(const void* frames, int is_unsigned, int tc,
   DC_REQUIRE(frames && tmpl && rows && wscores, DC_EINVAL, "dc_motion_ssd_around: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_motion_ssd_around: negative or zero size (tc %d, S %d, D %d, H %d, W %d)",
              tc, S, D, H, W);
+  DC_REQUIRE_FRAMES("dc_motion_ssd_around", tc);
   DC_REQUIRE_WINDOW("dc_motion_ssd_around", S, D);
   DC_REQUIRE_IMAGE("dc_motion_ssd_around", H, W);
   DC_REQUIRE(H > 2 * S && W > 2 * S, DC_EINVAL, "dc_motion_ssd_around: image %d x %d has no interior at S = %d (H > 2S and W > 2S)", H, W, S);
@@ -1050,6 +1062,7 @@ extern "C" int dc_motion_pick_around(const long* wscores, const int* rows, int m
                                      dc_stream_t stream) {
   DC_REQUIRE(wscores && rows && shifts, DC_EINVAL, "dc_motion_pick_around: null pointer");
   DC_REQUIRE(tc >= 0 && S >= 0 && D >= 0, DC_EINVAL, "dc_motion_pick_around: negative size (tc %d, S %d, D %d)", tc, S, D);
+  DC_REQUIRE_FRAMES("dc_motion_pick_around", tc);
   DC_REQUIRE_WINDOW("dc_motion_pick_around", S, D);
   DC_REQUIRE((((uintptr_t)wscores | (uintptr_t)best) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)shifts | (uintptr_t)fine) & 3) == 0, DC_EINVAL,
              "dc_motion_pick_around: misaligned buffer");
@@ -1074,6 +1087,7 @@ int launch_bidi_scores(const void* frames, int is_unsigned, int tc, int H, int W
 extern "C" int dc_bidi_scores(const void* frames, int is_unsigned, int tc, int H, int W, int P, long* scores, dc_stream_t stream) {
   DC_REQUIRE(frames && scores, DC_EINVAL, "dc_bidi_scores: null pointer");
   DC_REQUIRE(tc >= 0 && P >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_bidi_scores: negative or zero size (tc %d, P %d, H %d, W %d)", tc, P, H, W);
+  DC_REQUIRE_FRAMES("dc_bidi_scores", tc);
   DC_REQUIRE(P <= DC_BIDI_MAX_OFFSET, DC_EUNSUP, "dc_bidi_scores: P = %d: the offset radius is limited to %d", P, DC_BIDI_MAX_OFFSET);
   DC_REQUIRE((long)H * W <= (1L << 28), DC_EUNSUP, "dc_bidi_scores: image %d x %d: H * W is limited to 2^28", H, W);
   DC_REQUIRE(H >= 3 && W > 2 * P, DC_EINVAL, "dc_bidi_scores: image %d x %d has no odd line between two even ones, or no interior at P = %d (H >= 3 and W > 2P)",
@@ -1094,6 +1108,7 @@ extern "C" int dc_bidi_scores(const void* frames, int is_unsigned, int tc, int H
 extern "C" int dc_bidi_apply(const void* frames, int tc, int p, int H, int W, int fill, void* out, dc_stream_t stream) {
   DC_REQUIRE(frames && out, DC_EINVAL, "dc_bidi_apply: null pointer");
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_bidi_apply: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE_FRAMES("dc_bidi_apply", tc);
   DC_REQUIRE_IMAGE("dc_bidi_apply", H, W);
   DC_REQUIRE_MOVE("dc_bidi_apply", frames, nullptr, out, tc, H, W, fill);
   if (tc == 0) return DC_OK;

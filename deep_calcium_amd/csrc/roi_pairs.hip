@@ -221,6 +221,7 @@ extern "C" int dc_roi_pair_accumulate(const void* frames, int is_unsigned, int t
   DC_REQUIRE(frames && roi_off && roi_pix && goff && tiles && a && g, DC_EINVAL, "dc_roi_pair_accumulate: null pointer");
   DC_REQUIRE(tc >= 0 && ntiles >= 0 && R >= 0 && P >= 0 && G >= 0, DC_EINVAL,
              "dc_roi_pair_accumulate: negative count (tc %d, ntiles %ld, R %d, P %d, G %ld)", tc, ntiles, R, P, G);
+  DC_REQUIRE_FRAMES("dc_roi_pair_accumulate", tc);
   DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "dc_roi_pair_accumulate: image %d x %d out of range", H, W);
   DC_REQUIRE((((uintptr_t)frames) & 1) == 0 && (((uintptr_t)roi_off | (uintptr_t)roi_pix | (uintptr_t)tiles) & 3) == 0 &&
              (((uintptr_t)goff | (uintptr_t)a | (uintptr_t)g) & 7) == 0, DC_EINVAL, "dc_roi_pair_accumulate: misaligned buffer");

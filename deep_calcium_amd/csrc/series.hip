@@ -393,6 +393,7 @@ int series_check(const char* fn, const void* frames, int tc, long t0, int H, int
   DC_REQUIRE(frames, DC_EINVAL, "%s: null pointer", fn);
   DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "%s: image %d x %d out of range", fn, H, W);
   DC_REQUIRE(tc > 0 && t0 >= 0, DC_EINVAL, "%s: chunk of %d frames at frame %ld", fn, tc, t0);
+  DC_REQUIRE_FRAMES(fn, tc);
   DC_REQUIRE((((uintptr_t)frames) & 1) == 0, DC_EINVAL, "%s: frames must be 2-byte aligned", fn);
   return DC_OK;
 }
@@ -507,6 +508,7 @@ extern "C" int dc_series_bin_time(const void* frames, int is_unsigned, int tc, i
   DC_REQUIRE(b <= DC_SERIES_MAX_BIN_FRAMES, DC_EUNSUP, "dc_series_bin_time: b = %d: a bin is limited to %d frames", b, DC_SERIES_MAX_BIN_FRAMES);
   DC_REQUIRE(phase >= 0 && phase < b, DC_EINVAL, "dc_series_bin_time: phase = %d outside [0, %d)", phase, b);
   DC_REQUIRE(tc >= 0 && H > 0 && W > 0, DC_EINVAL, "dc_series_bin_time: negative or zero size (tc %d, H %d, W %d)", tc, H, W);
+  DC_REQUIRE_FRAMES("dc_series_bin_time", tc);
   DC_REQUIRE((long)H * W <= (1L << 30), DC_EUNSUP, "dc_series_bin_time: image %d x %d: H * W is limited to 2^30", H, W);
   if (tc == 0) return DC_OK;
   const long seen = (long)phase + tc, n_out = seen / b;

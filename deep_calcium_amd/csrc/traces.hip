@@ -174,6 +174,7 @@ static int roi_accumulate(const char* who, bool weighted, const void* frames, in
                           dc_stream_t stream) {
   DC_REQUIRE(frames && row_off && row_pix && sums && (row_wgt || !weighted), DC_EINVAL, "%s: null pointer", who);
   DC_REQUIRE(S >= 0 && R >= 0 && tc >= 0 && t0 >= 0, DC_EINVAL, "%s: negative count (S %d, R %d, tc %d, t0 %ld)", who, S, R, tc, t0);
+  DC_REQUIRE_FRAMES(who, tc);
   DC_REQUIRE(row_roi || S == R, DC_EINVAL, "%s: without row_roi every CSR row is an ROI, but S = %d and R = %d", who, S, R);
   DC_REQUIRE(ld >= t0 + tc, DC_EINVAL, "%s: ld = %ld is below t0 + tc = %ld", who, ld, t0 + tc);
   DC_REQUIRE(H > 0 && W > 0 && (long)H * W <= (1L << 30), DC_EINVAL, "%s: image %d x %d out of range", who, H, W);

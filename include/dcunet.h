@@ -36,9 +36,15 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 130
+#define DC_ABI_VERSION 131
 int dc_version(void);
 const char* dc_last_error(void);
+
+/* The frames of ONE call: every device entry point that takes `int tc` refuses tc > DC_FRAMES_PER_CALL_MAX = 2^30 with
+ * DC_EUNSUP (-3) before it launches anything (a longer recording arrives in chunks, as every reader of the package feeds it).
+ * Below the limit the kernels' per-frame table indices 2 * f + 1 and their frame loops' f + gridDim.y (at most 65535) fit an
+ * int; the contract no longer relies on the caller for that.  The limits on t0 + tc, T * H * W and H * W stay as they are. */
+#define DC_FRAMES_PER_CALL_MAX 1073741824L
 
 /* ---- weight re-layout for the implicit-GEMM kernels -------------------------
  * dst[tap][k/4][n][k%4] = src[(flip ? taps-1-tap : tap)*s_tap + k*s_k + n*s_n].
@@ -508,12 +514,12 @@ int dc_host_label8(const uint8_t* mask, int H, int W, int* labels, int* n, void*
  *   sum, sumsq (int64), vmax (int32): exact sum x, sum x*x and the true maximum.
  * mean16 / max16: both given or both NULL (the float16 chain is the expensive part of the pass). */
 int dc_series_accumulate(const void* frames, int is_unsigned, int tc, long t0, long n_total, uint16_t* mean16,
-                         int16_t* max16, long* sum, long* sumsq, int* vmax, int H, int W, dc_stream_t stream);
+                         int16_t* max16, long* sum, long* sumsq, int* vmax, int H, int W, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 /* the exact cross sums of the local correlation image (no counterpart in datasets/nf.py:121-130 or
  * unet_2d_summary.py:227-241: a series_summary_func of the user's): xy = int64[4][H*W], xy[j][p] = sum_t x_p * x_q with q the
  * right (j = 0), down (1), down-right (2), down-left (3) neighbour of p; a neighbour outside the image contributes 0. */
 int dc_series_accumulate_xy(const void* frames, int is_unsigned, int tc, long t0, long* xy, int H, int W,
-                            dc_stream_t stream);
+                            dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 /* state -> float32 images (each output nullable; the user-side summaries next to datasets/nf.py:121-130 /
  * unet_2d_summary.py:227-241): mean = sum / T; std = sqrt(T sum x^2 - (sum x)^2) / T (population); corr (needs xy) = the
  * mean over the pixel's EXISTING 8 neighbours of the Pearson correlation, a pair with a zero-variance pixel counting 0,
@@ -543,7 +549,7 @@ int dc_image_standardize(const float* in, float* out, float* ws, int H, int W, d
  * buffer, out overlapping frames or carry (or carry overlapping frames).  DC_EUNSUP (-3): b > DC_SERIES_MAX_BIN_FRAMES, H * W > 2^30. */
 #define DC_SERIES_MAX_BIN_FRAMES 64
 int dc_series_bin_time(const void* frames, int is_unsigned, int tc, int H, int W, int b, int phase, int* carry, void* out,
-                       dc_stream_t stream);
+                       dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- ROI traces: a recording (T,H,W) of 16-bit frames + a set of ROIs -> one fluorescence trace per ROI -------------------
  * What the reference's spikes model reads from its dataset files: `traces`, a (no. ROIs, no. frames) matrix
@@ -572,7 +578,7 @@ int dc_series_bin_time(const void* frames, int is_unsigned, int tc, int H, int W
  * dc_roi_trace_finalize, which is not told the image size, T alone. */
 #define DC_ROI_TRACE_MAX_VOLUME 70368744177664L
 int dc_roi_trace_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
-                            const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);
+                            const int* row_roi, int S, int R, long* sums, long ld, int H, int W, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, long T, float* mean, float* zscore,
                           dc_stream_t stream);
 
@@ -591,7 +597,7 @@ int dc_roi_trace_finalize(const long* sums, long ld, const int* areas, int R, lo
  * PROMISES 1 <= W_r <= 2^31 - 1 and T * W_r <= 2^46 (the volume limit above, with W for H * W). */
 int dc_roi_wtrace_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
                              const unsigned short* row_wgt, const int* row_roi, int S, int R, long* sums, long ld, int H, int W,
-                             dc_stream_t stream);
+                             dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- ROI footprint maps: the correlation of every pixel of an ROI's support with the ROI's own trace ---------------------------
  * The one decision of the chain that never looks at the recording is which pixels belong to a neuron (the ROIs are the regions
@@ -627,7 +633,7 @@ int dc_roi_wtrace_accumulate(const void* frames, int is_unsigned, int tc, long t
 #define DC_ROI_PIXEL_MAX_FRAMES 2147483647L
 int dc_roi_pixel_accumulate(const void* frames, int is_unsigned, int tc, long t0, const int* row_off, const int* row_pix,
                             const int* row_roi, int S, int R, const long* sums, long ld, long* mom, int N, int H, int W,
-                            dc_stream_t stream);
+                            dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_roi_trace_moments(const long* sums, long ld, int R, long T, long* rmom, dc_stream_t stream);
 int dc_roi_pixel_corr(const long* mom, int N, const int* row_off, const int* row_roi, int S, int R, const int* inside,
                       const long* rmom, long T, float* corr, dc_stream_t stream);
@@ -670,7 +676,7 @@ int dc_roi_pixel_corr(const long* mom, int N, const int* row_off, const int* row
 #define DC_ROI_PAIR_MAX_AREA 1024
 #define DC_ROI_PAIR_MAX_STATE 134217728L
 int dc_roi_pair_accumulate(const void* frames, int is_unsigned, int tc, const int* roi_off, const int* roi_pix, const long* goff,
-                           const int* tiles, long ntiles, int R, long* a, long* g, int P, long G, int H, int W, dc_stream_t stream);
+                           const int* tiles, long ntiles, int R, long* a, long* g, int P, long G, int H, int W, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_roi_pair_corr(const long* a, const long* g, const int* roi_off, const long* goff, int R, int P, long G, long T, float* corr,
                      dc_stream_t stream);
 
@@ -789,9 +795,9 @@ int dc_trace_pair_corr(const long* num, long P, float* corr, dc_stream_t stream)
  * nothing is read on the host. */
 #define DC_FRAME_MAX_PIXELS 268435456L
 int dc_frame_moments(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int y0, int y1, int x0, int x1,
-                     long* moments, dc_stream_t stream);
-int dc_frame_quality(const long* moments, int tc, long n, long ta, long tb, float* mean, float* corr, dc_stream_t stream);
-int dc_frame_gather(const void* frames, int tc, const int* idx, int k, int H, int W, void* out, dc_stream_t stream);
+                     long* moments, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
+int dc_frame_quality(const long* moments, int tc, long n, long ta, long tb, float* mean, float* corr, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
+int dc_frame_gather(const void* frames, int tc, const int* idx, int k, int H, int W, void* out, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- dF/F traces: neuropil correction, rolling-percentile baseline, (F - F0) / F0 -----------------------------------------------
  * The step between ROI traces and spikes that the z-score above cannot replace: a recording bleaches and drifts, and every ROI
@@ -1127,9 +1133,9 @@ int dc_trace_ar1_estimate_host(const void* y, int is_f64, long ld, int R, long T
  *     an all-fill frame.  out must not overlap frames (DC_EINVAL). */
 #define DC_MOTION_MAX_SHIFT 16
 int dc_motion_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, long* scores,
-                  dc_stream_t stream);
-int dc_motion_pick(const long* scores, int tc, int S, int* shifts, long* best, dc_stream_t stream);
-int dc_motion_apply(const void* frames, int tc, const int* shifts, int H, int W, int fill, void* out, dc_stream_t stream);
+                  dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
+int dc_motion_pick(const long* scores, int tc, int S, int* shifts, long* best, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
+int dc_motion_apply(const void* frames, int tc, const int* shifts, int H, int W, int fill, void* out, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- piecewise-rigid motion correction: one whole-pixel shift per block of the frame, blended into a shift field ----------------
  * A two-photon frame is scanned line by line while the tissue moves, so its top is displaced differently from its bottom.  The
@@ -1162,11 +1168,11 @@ int dc_motion_apply(const void* frames, int tc, const int* shifts, int H, int W,
 #define DC_MOTION_MAX_DEV 8
 #define DC_MOTION_MAX_BLOCKS 32
 int dc_motion_block_ssd(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, int By, int Bx,
-                        const int* rigid, long* bscores, dc_stream_t stream);
+                        const int* rigid, long* bscores, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_motion_block_pick(const long* bscores, const int* rigid, int tc, int By, int Bx, int S, int D, int* block_shifts, long* best,
-                         dc_stream_t stream);
+                         dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_motion_warp(const void* frames, int tc, const int* block_shifts, int By, int Bx, int H, int W, int fill, void* out,
-                   dc_stream_t stream);
+                   dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- sub-pixel motion correction: the picks refined to 1/16 pixel, the frames interpolated bilinearly ---------------------------
  * FINE SHIFTS are int32 in units of 1 / DC_MOTION_SUB of a pixel, with the sign convention above: a fine shift (sy, sx) =
@@ -1198,13 +1204,13 @@ int dc_motion_warp(const void* frames, int tc, const int* block_shifts, int By, 
  *     that the whole-pixel field rounds away, which is the point of it.
  * Sizes, limits, alignment and the overlap rule are those of the whole-pixel counterparts (DC_EINVAL / DC_EUNSUP alike). */
 #define DC_MOTION_SUB 16
-int dc_motion_refine(const long* scores, const int* shifts, int tc, int S, int* fine, dc_stream_t stream);
+int dc_motion_refine(const long* scores, const int* shifts, int tc, int S, int* fine, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_motion_block_refine(const long* bscores, const int* rigid, const int* block_shifts, int tc, int By, int Bx, int S, int D, int* fine,
-                           dc_stream_t stream);
+                           dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_motion_apply_sub(const void* frames, int is_unsigned, int tc, const int* fine, int H, int W, int fill, void* out,
-                        dc_stream_t stream);
+                        dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, const int* fine_block_shifts, int By, int Bx, int H, int W, int fill,
-                       void* out, dc_stream_t stream);
+                       void* out, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- wide search: shifts beyond DC_MOTION_MAX_SHIFT by a two-level, coarse-to-fine search -------------------------------------
  * The exhaustive search costs (2S+1)^2 passes over the interior, so its radius is capped at 16.  The wide search finds a coarse
@@ -1229,11 +1235,11 @@ int dc_motion_warp_sub(const void* frames, int is_unsigned, int tc, const int* f
  *     q = 0 on an axis where the residual lies on the window's border (such a pick is not refined) or where the denominator is 0.
  * S > 128, D > 8 or H * W > 2^30: DC_EUNSUP (-3); S < D or no interior: DC_EINVAL.  tc == 0 launches nothing. */
 #define DC_MOTION_MAX_WIDE_SHIFT 128
-int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H, int W, int c, void* out, dc_stream_t stream);
+int dc_motion_bin(const void* frames, int is_unsigned, int tc, int H, int W, int c, void* out, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_motion_ssd_around(const void* frames, int is_unsigned, int tc, const void* tmpl, int H, int W, int S, int D, const int* rows,
-                         int mult, long* wscores, dc_stream_t stream);
+                         int mult, long* wscores, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 int dc_motion_pick_around(const long* wscores, const int* rows, int mult, int tc, int S, int D, int* shifts, long* best, int* fine,
-                          dc_stream_t stream);
+                          dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- bidirectional scan-phase correction: the odd lines of a resonant-scanned recording moved against the even ones ------------
  * A resonant scanner draws even lines left to right and odd lines right to left; a phase error between the two sweeps displaces
@@ -1255,8 +1261,8 @@ int dc_motion_pick_around(const long* wscores, const int* rows, int mult, int tc
  *     passed by value and any int32 is legal; |p| >= W gives all-fill odd rows; p = 0 is a copy.  out must not overlap frames
  *     (DC_EINVAL); H * W > 2^30: DC_EUNSUP. */
 #define DC_BIDI_MAX_OFFSET 16
-int dc_bidi_scores(const void* frames, int is_unsigned, int tc, int H, int W, int P, long* scores, dc_stream_t stream);
-int dc_bidi_apply(const void* frames, int tc, int p, int H, int W, int fill, void* out, dc_stream_t stream);
+int dc_bidi_scores(const void* frames, int is_unsigned, int tc, int H, int W, int P, long* scores, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
+int dc_bidi_apply(const void* frames, int tc, int p, int H, int W, int fill, void* out, dc_stream_t stream);   /* tc <= DC_FRAMES_PER_CALL_MAX */
 
 /* ---- UNet1D spike inference: traces in, spike probabilities out ------------------------------------------------------------
  * The reference's second model family, UNet1DSegmentation: the network unet1d (unet_1d_segmentation.py:49-148) as its predict()

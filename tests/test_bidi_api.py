@@ -299,3 +299,9 @@ def test_summing_over_frames_is_what_recovers_the_noisy_recording():
             single_misses += sum(bref.pick(row.tolist()) != -b for row in sc)
             picks += len(sc)
     assert picks == 480 and single_misses >= 1                              # per-frame picks alone would not pass
+
+
+def test_frames_of_one_call_are_limited(dclib):
+    """DC_FRAMES_PER_CALL_MAX: tc = 2^30 + 1 is refused with (-3) and the limit's message before any launch, tc = 2^30 is not."""
+    import _wideindex
+    _wideindex.check_frame_limit(dclib, 'test_bidi_api')

@@ -324,3 +324,9 @@ def test_pair_math_under_the_host_sanitizers(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'pair_math_check: ok' in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+
+
+def test_frames_of_one_call_are_limited(dclib):
+    """DC_FRAMES_PER_CALL_MAX: tc = 2^30 + 1 is refused with (-3) and the limit's message before any launch, tc = 2^30 is not."""
+    import _wideindex
+    _wideindex.check_frame_limit(dclib, 'test_roi_pairs_api')

@@ -270,3 +270,9 @@ def test_the_gpu_scene_meets_its_conditions_on_the_reference():
         new, origin, gaps = _split_binned(f, r, 4)
         print('%s at b = 4: gap %.3f' % (kind, gaps[0]))
         assert len(new) == 1 and not gaps[0] > 0.02, (kind, gaps[0])
+
+
+def test_frames_of_one_call_are_limited(dclib):
+    """DC_FRAMES_PER_CALL_MAX: tc = 2^30 + 1 is refused with (-3) and the limit's message before any launch, tc = 2^30 is not."""
+    import _wideindex
+    _wideindex.check_frame_limit(dclib, 'test_tbin_api')
