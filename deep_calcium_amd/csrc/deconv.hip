@@ -8,10 +8,12 @@
 // same depth touch one line.  The noise-constrained search (csrc/deconv_search_math.h) and the fit of a baseline
 // (csrc/deconv_base_math.h) run that forward pass once or twice a round, with the searched parameter and the baseline in the device
 // arrays the pass reads anyway, and between two passes one launch of the sweep kernel, which folds the residual of the stacks and
-// moves every trace's bracket or baseline: nothing is read back.  The AR(2) model (csrc/deconv_ar2_math.h, "A rise time in the
-// deconvolution") runs through the same walk over the tiles, the same sweep and the same search; its pools carry two data moments
-// and lie in five planes.  Nothing here may be contracted or reassociated: the pragma of deconv_math.h and the per-file flag in
-// _build.py.
+// moves every trace's bracket or baseline: nothing is read back.  There are two models, DcAr1 (csrc/deconv_math.h) and DcAr2
+// (csrc/deconv_ar2_math.h, "A rise time in the deconvolution": pools that carry two data moments and lie in five planes), and one
+// interface to them: the pool type, its planes, mu, fresh, push, calc and spike.  The stack view, the forward kernel, the fill, the
+// sweep and the host drivers below are each written once against it; a kernel is instantiated per model source (Ar1From<Each>,
+// Ar2From), and the launches pick the instantiation from what Args names.  Nothing here may be contracted or reassociated: the
+// pragma of deconv_math.h and the per-file flag in _build.py.
 #pragma clang fp contract(off)
 #include <type_traits>
 #include <vector>
@@ -54,81 +56,44 @@ struct StackIndex {
   }
 };
 
-// the AR(1) stacks: three planes, v, w and (t0, l)
+// The stacks of a model: Model::kPlanes planes of doubles, the fields of its pool in the order of Model::words -- v and w for AR(1);
+// v, u, A and B for AR(2), where v could be had again from A, u and l and is kept, a load for a division --, then (t0, l).
+template <class Model>
 struct StackView : StackIndex {
-  double* v;
-  double* w;
-  __device__ __forceinline__ StackView(const double* ws, int R_, long T)
-      : StackIndex(ws, 2, R_, T), v(const_cast<double*>(ws)), w(v + (long)R_ * T) {}
-  // what a pool's calcium is computed from, for the cursor of the sweep
-  __device__ __forceinline__ void value(long word, double& val, double& below) const {
-    val = v[word];
-    below = 0.0;
+  using Pool = typename Model::Pool;
+  double* d[Model::kPlanes];
+  __device__ __forceinline__ StackView(const double* ws, int R_, long T) : StackIndex(ws, Model::kPlanes, R_, T) {
+    for (int j = 0; j < Model::kPlanes; ++j) d[j] = const_cast<double*>(ws) + j * ((long)R_ * T);
   }
-  __device__ __forceinline__ DcPool load(int32_t i, long r) const {
-    DcPool p;
-    p.v = v[at(i, r)];
-    p.w = w[at(i, r)];
-    const int2 x = tl[at(i, r)];
+  __device__ __forceinline__ Pool load(int32_t i, long r) const {
+    Pool p;
+    const long word = at(i, r);                                      // once, before the visitor: formed inside it, 8 - 12 VGPRs more in the forward kernels
+    Model::words(p, [&](int j, double& x) { x = d[j][word]; });
+    const int2 x = tl[word];
     p.t0 = x.x;
     p.l = x.y;
     return p;
   }
-  __device__ __forceinline__ void store(int32_t i, long r, const DcPool& p) const {
-    v[at(i, r)] = p.v;
-    w[at(i, r)] = p.w;
-    tl[at(i, r)] = make_int2(p.t0, p.l);
+  __device__ __forceinline__ void store(int32_t i, long r, const Pool& p) const {
+    const long word = at(i, r);
+    Model::words(p, [&](int j, const double& x) { d[j][word] = x; });
+    tl[word] = make_int2(p.t0, p.l);
   }
-};
-
-// the AR(2) stacks: five planes, v, u, A, B and (t0, l).  v could be had again from A, u and l; it is kept, a load for a division
-struct StackView2 : StackIndex {
-  double *v, *u, *A, *B;
-  __device__ __forceinline__ StackView2(const double* ws, int R_, long T)
-      : StackIndex(ws, 4, R_, T), v(const_cast<double*>(ws)), u(v + (long)R_ * T), A(u + (long)R_ * T), B(A + (long)R_ * T) {}
-  __device__ __forceinline__ void value(long word, double& val, double& below) const {
-    val = v[word];
-    below = u[word];
-  }
-  __device__ __forceinline__ DcPool2 load(int32_t i, long r) const {
-    DcPool2 p;
-    p.v = v[at(i, r)];
-    p.u = u[at(i, r)];
-    p.A = A[at(i, r)];
-    p.B = B[at(i, r)];
-    const int2 x = tl[at(i, r)];
-    p.t0 = x.x;
-    p.l = x.y;
-    return p;
-  }
-  // a pool without its moments: what its calcium takes (v, u, t0, l); A and B are +0.0 and not read
-  __device__ __forceinline__ DcPool2 load_fit(int32_t i, long r) const {
-    DcPool2 p;
-    p.v = v[at(i, r)];
-    p.u = u[at(i, r)];
-    p.A = 0.0;
-    p.B = 0.0;
-    const int2 x = tl[at(i, r)];
-    p.t0 = x.x;
-    p.l = x.y;
-    return p;
-  }
-  __device__ __forceinline__ void store(int32_t i, long r, const DcPool2& p) const {
-    v[at(i, r)] = p.v;
-    u[at(i, r)] = p.u;
-    A[at(i, r)] = p.A;
-    B[at(i, r)] = p.B;
-    tl[at(i, r)] = make_int2(p.t0, p.l);
+  // what a pool's calcium is computed from (Model::calc): the fields that are not used are not loaded
+  __device__ __forceinline__ void value(int32_t i, long r, double& val, double& below) const {
+    const Pool p = load(i, r);
+    val = p.v;
+    below = Model::below(p);
   }
 };
 
 // the stack of one trace, as dc_deconv_push and dc_ar2_push take it
-template <class View, class Pool>
+template <class Model>
 struct DeviceStack {
-  View s;
+  StackView<Model> s;
   long r;
-  __device__ __forceinline__ Pool load(int32_t i) const { return s.load(i, r); }
-  __device__ __forceinline__ void store(int32_t i, const Pool& p) { s.store(i, r, p); }
+  __device__ __forceinline__ typename Model::Pool load(int32_t i) const { return s.load(i, r); }
+  __device__ __forceinline__ void store(int32_t i, const typename Model::Pool& p) { s.store(i, r, p); }
 };
 
 // The walk of a workgroup of one wave over its 64 traces: a tile of 64 traces x 64 frames at a time is staged through `tile`
@@ -154,28 +119,58 @@ __device__ __forceinline__ void walk_tiles(In* tile, const In* __restrict__ y, l
   }
 }
 
-// One workgroup of one wave per 64 traces (walk_tiles).
-// Each = false: one decay g and one table G for all traces (dc_trace_deconv_ar1).  Each = true: trace r has the decay gs[r] and
-// the table row G + r * ldG (dc_trace_deconv_ar1_each); the arithmetic of a trace is the same, only where its g and G come from.
+// Where a kernel's model comes from: what the call gave, as the launches pass it on.  of(r): the model of trace r for the forward
+// pass and the fill; a lane without a trace (mine = false) reads nothing.  of_table(r): the same for the sweep, whose entry points
+// are given the table alone.
+// AR(1): one decay g and one table G for all traces (Each = false; gs == nullptr, ldG == 0), or trace r has the decay gs[r] and the
+// table row G + r * ldG (Each = true); the arithmetic of a trace is the same, only where its g and G come from.
+struct Ar1Args {
+  double g;
+  const double *gs, *G;
+  long ldG;
+};
+template <bool Each>
+struct Ar1From : Ar1Args {
+  using Model = DcAr1;
+  __device__ __forceinline__ DcAr1 of(long r, bool mine = true) const {
+    return {Each ? (mine ? gs[r] : 0.5) : g, Each && mine ? G + r * ldG : G};
+  }
+  __device__ __forceinline__ DcAr1 of_table(long r) const {
+    const double* row = Each ? G + r * ldG : G;
+    return {row[1], row};                                            // T >= 1: the table has the entry
+  }
+};
+// AR(2): one pair of coefficients and one table H of three rows of stride ldH for all traces
+struct Ar2Args {
+  double g1, g2;
+  const double* H;
+  long ldH;
+};
+struct Ar2From : Ar2Args {
+  using Model = DcAr2;
+  __device__ __forceinline__ DcAr2 of(long, bool = true) const { return dc_ar2_model(g1, g2, H, ldH); }
+  __device__ __forceinline__ DcAr2 of_table(long r) const { return of(r); }
+};
+
+// The forward pass: one workgroup of one wave per 64 traces (walk_tiles), one lane per trace, the model from `from`.
 // Base = true: the baseline base[r] leaves every frame of trace r before the penalty's shift (csrc/deconv_base_math.h).
-template <typename In, bool Each, bool Base>
-__global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g_all,
-                                                               const double* __restrict__ gs, const double* __restrict__ G_all, long ldG,
+template <typename In, class From, bool Base>
+__global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __restrict__ y, long ld, int R, long T, const From from,
                                                                const double* __restrict__ lam, const double* __restrict__ smin,
                                                                const double* __restrict__ base, double* ws, int* __restrict__ pools) {
+  using Model = typename From::Model;
   __shared__ In tile[kLanes * kPitch];
   const long r = (long)blockIdx.x * kLanes + threadIdx.x;
   const bool mine = r < R;
-  DeviceStack<StackView, DcPool> st = {StackView(ws, R, T), r};
+  DeviceStack<Model> st = {StackView<Model>(ws, R, T), r};
   const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
-  const double g = Each ? (mine ? gs[r] : 0.5) : g_all;
-  const double* __restrict__ G = Each && mine ? G_all + r * ldG : G_all;
+  const Model m = from.of(r, mine);
   const double b = Base && mine ? base[r] : 0.0;
-  DcPool top = dc_deconv_new(0.0, 0);
+  typename Model::Pool top = Model::fresh();
   int32_t n = 0;
   walk_tiles(tile, y, ld, R, T, [&](long t, double y_t) {
-    const double x = (Base ? dc_base_data(y_t, b) : y_t) - dc_deconv_mu(la, g, t, T);
-    dc_deconv_push(top, n, st, x, t, G, sm);
+    const double x = (Base ? dc_base_data(y_t, b) : y_t) - m.mu(la, t, T);
+    m.push(top, n, st, x, t, sm);
   });
   if (mine) {
     st.store(n - 1, top);                                            // T >= 1: n >= 1.  The fill kernel reads the workspace only
@@ -183,77 +178,25 @@ __global__ __launch_bounds__(kLanes) void deconv_forward_kernel(const In* __rest
   }
 }
 
-// The AR(2) forward pass (csrc/deconv_ar2_math.h): the same walk, one lane per trace; one pair of coefficients and one table H of
-// three rows for all traces.
-template <typename In, bool Base>
-__global__ __launch_bounds__(kLanes) void deconv_ar2_forward_kernel(const In* __restrict__ y, long ld, int R, long T, double g1, double g2,
-                                                                   const double* __restrict__ H, long ldH, const double* __restrict__ lam,
-                                                                   const double* __restrict__ smin, const double* __restrict__ base, double* ws,
-                                                                   int* __restrict__ pools) {
-  __shared__ In tile[kLanes * kPitch];
-  const long r = (long)blockIdx.x * kLanes + threadIdx.x;
-  const bool mine = r < R;
-  DeviceStack<StackView2, DcPool2> st = {StackView2(ws, R, T), r};
-  const DcAr2 m = dc_ar2_model(g1, g2, H, ldH);
-  const double la = mine ? lam[r] : 0.0, sm = mine ? smin[r] : 0.0;
-  const double b = Base && mine ? base[r] : 0.0;
-  DcPool2 top = dc_ar2_new(0.0, 0);
-  int32_t n = 0;
-  walk_tiles(tile, y, ld, R, T, [&](long t, double y_t) {
-    const double x = (Base ? dc_base_data(y_t, b) : y_t) - dc_ar2_mu(la, g1, g2, t, T);
-    dc_ar2_push(top, n, st, x, t, m, sm);
-  });
-  if (mine) {
-    st.store(n - 1, top);                                            // T >= 1: n >= 1
-    pools[r] = n;
-  }
-}
-
-// One thread per sample (r, t): pool_of over the trace's n pools.  Every output element is written, each by one product or one
-// multiply-subtract.
-template <bool Each>
+// One thread per sample (r, t): pool_of over the trace's n pools.  Every output element is written: the calcium by Model::calc, the
+// spike, at the first frame of a pool above another, by Model::spike from that pool.
+template <class From>
 __global__ __launch_bounds__(kFillThreads) void deconv_fill_kernel(const double* __restrict__ ws, const int* __restrict__ pools, int R, long T,
-                                                                  double g_all, const double* __restrict__ gs, const double* __restrict__ G_all,
-                                                                  long ldG, double* __restrict__ calcium, double* __restrict__ spikes) {
+                                                                  const From from, double* __restrict__ calcium, double* __restrict__ spikes) {
+  using Model = typename From::Model;
   const long idx = (long)blockIdx.x * kFillThreads + threadIdx.x;
   if (idx >= (long)R * T) return;
   const long r = idx / T;
   const int32_t t = (int32_t)(idx - r * T);
-  const double g = Each ? gs[r] : g_all;
-  const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
-  const StackView st(ws, R, T);
+  const Model m = from.of(r);
+  const StackView<Model> st(ws, R, T);
   const int32_t lo = st.pool_of(r, 0, pools[r] - 1, t);
   const int32_t k = t - st.tl[st.at(lo, r)].x;
-  const double c = dc_deconv_calcium(st.v[st.at(lo, r)], G[k]);
+  double val, below;
+  st.value(lo, r, val, below);
+  const double c = m.calc(val, below, k);
   double s = 0.0;
-  if (k == 0 && lo > 0) {
-    const long below = st.at(lo - 1, r);
-    s = dc_deconv_spike(c, g, dc_deconv_calcium(st.v[below], G[st.tl[below].y - 1]));
-  }
-  calcium[idx] = c;
-  spikes[idx] = s;
-}
-
-// The AR(2) fill: one thread per sample, as above; the spike of a pool's first frame takes the last two values of the pool below.
-__global__ __launch_bounds__(kFillThreads) void deconv_ar2_fill_kernel(const double* __restrict__ ws, const int* __restrict__ pools, int R, long T,
-                                                                      double g1, double g2, const double* __restrict__ H, long ldH,
-                                                                      double* __restrict__ calcium, double* __restrict__ spikes) {
-  const long idx = (long)blockIdx.x * kFillThreads + threadIdx.x;
-  if (idx >= (long)R * T) return;
-  const long r = idx / T;
-  const int32_t t = (int32_t)(idx - r * T);
-  const DcAr2 m = dc_ar2_model(g1, g2, H, ldH);
-  const StackView2 st(ws, R, T);
-  const int32_t lo = st.pool_of(r, 0, pools[r] - 1, t);
-  const long own = st.at(lo, r);
-  const int32_t k = t - st.tl[own].x;
-  const double c = dc_ar2_calc(m, st.v[own], st.u[own], k);
-  double s = 0.0;
-  if (k == 0 && lo > 0) {
-    double last, sec;
-    dc_ar2_tail(m, st.load_fit(lo - 1, r), last, sec);
-    s = dc_ar2_spike(m, c, last, sec);
-  }
+  if (k == 0 && lo > 0) s = m.spike(c, st.load(lo - 1, r));
   calcium[idx] = c;
   spikes[idx] = s;
 }
@@ -319,9 +262,9 @@ struct SweepOut {
   double* sums;
 };
 
-// The pool that holds the frame a thread of the sweep stands at: pool `at` of the trace, frames [start, end), of value val, above
-// the calcium `below` (AR(2); +0.0 and unused for AR(1)).  A thread's frames ascend, so it seeks from its previous pool upwards,
-// and only when a frame t >= end has left that pool.
+// The pool that holds the frame a thread of the sweep stands at: pool `at` of the trace, frames [start, end), and the two words
+// Model::calc takes, its value and what lies below it.  A thread's frames ascend, so it seeks from its previous pool upwards, and
+// only when a frame t >= end has left that pool.
 struct PoolCursor {
   int32_t at = 0, start = 0, end = 0;        // no pool yet: frame 0 seeks
   double val = 0.0, below = 0.0;
@@ -332,7 +275,7 @@ struct PoolCursor {
     const int2 own = st.tl[st.at(at, r)];
     start = own.x;
     end = own.x + own.y;
-    st.value(st.at(at, r), val, below);
+    st.value(at, r, val, below);
   }
 };
 
@@ -390,22 +333,24 @@ __device__ __forceinline__ void base_tail(const SweepOut& o, long r, long R, lon
 // base[r] off the data and folds RSS, S and A of deconv_base_math.h into red[3 * 256].  The tree through LDS is dc_dyn_fold_tree of
 // trace_dyn_math.h.  Its results red[0], red[256] and red[512] are thread 0's own words, and its last barrier frees the others for
 // the next trace; it also lies between every thread's read of base[r] and thread 0's write.  Every word has one writer; frames
-// t >= T of a row and rows r >= R are never read.  Ar2: the stacks are those of the AR(2) pass, G_all is its table of three rows
-// of stride ldG and g1, g2 its coefficients (Each and Base are then false): the plain search's residual, nothing else differs.
-template <typename In, bool Each, bool Base, bool Ar2>
-__global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* __restrict__ y, long ld, int R, long T,
-                                                                      const double* __restrict__ G_all, long ldG, double g1, double g2,
+// t >= T of a row and rows r >= R are never read.  The model comes from the table (From::of_table), the calcium of a frame from
+// Model::calc.  The sweep with a baseline exists for AR(1) only: dc_base_gain is the arithmetic of one decay.
+template <class Model, bool Base>
+constexpr bool kSweepExists = !Base || std::is_same<Model, DcAr1>::value;
+
+template <typename In, class From, bool Base>
+__global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* __restrict__ y, long ld, int R, long T, const From from,
                                                                       const double* __restrict__ ws, const int* __restrict__ pools,
                                                                       const SweepOut out) {
-  static_assert(!Ar2 || (!Each && !Base), "the AR(2) sweep has one table and no baseline");
+  using Model = typename From::Model;
+  static_assert(kSweepExists<Model, Base>, "the sweep with a baseline is AR(1) arithmetic");
   const int folds = Base ? 3 : 1;
   __shared__ double red[folds * kSearchThreads];
   const int tid = threadIdx.x;
-  const std::conditional_t<Ar2, StackView2, StackView> st(ws, R, T);
+  const StackView<Model> st(ws, R, T);
   for (long r = blockIdx.x; r < R; r += gridDim.x) {
     const In* __restrict__ row = y + r * ld;
-    const double* __restrict__ G = Each ? G_all + r * ldG : G_all;
-    const double g = Base ? G[1] : 0.0;                              // T >= 1: the table has the entry
+    const Model m = from.of_table(r);
     const double b = Base ? out.base[r] : 0.0;
     const int32_t n = pools[r];
     PoolCursor pool;
@@ -414,16 +359,14 @@ __global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* 
     for (long t = tid; t < T; t += kSearchThreads) {
       if (t >= pool.end) {
         pool.seek(st, r, n, t);
-        if constexpr (Base) Gl = G[pool.length()];
+        if constexpr (Base) Gl = m.G[pool.length()];
       }
-      double c;
-      if constexpr (Ar2) c = dc_ar2_calc(dc_ar2_model(g1, g2, G_all, ldG), pool.val, pool.below, (int32_t)(t - pool.start));
-      else c = dc_deconv_calcium(pool.val, G[t - pool.start]);
+      const double c = m.calc(pool.val, pool.below, (int32_t)(t - pool.start));
       if constexpr (Base) {
         const double d = dc_base_resid((double)row[t], b, c);
         q = q + d * d;
         s = s + d;
-        a = a + dc_base_gain_at(pool.val, t, pool.start, g, Gl);
+        a = a + dc_base_gain_at(pool.val, t, pool.start, m.g, Gl);
       } else {
         q = q + dc_search_term((double)row[t], c);
       }
@@ -442,9 +385,9 @@ __global__ __launch_bounds__(kSearchThreads) void deconv_sweep_kernel(const In* 
 }
 
 // ---- the launches: the arguments have been checked -----------------------------------------------------------------------------------
-// What every launch of a call shares.  One decay g and one table G for all traces (gs == nullptr, ldG == 0), or the decays gs and
-// the table rows G + r * ldG; base == nullptr: no baseline, the kernels of the entry points that have none.  ldH != 0: the AR(2)
-// model, g and g2 its coefficients and G its table of three rows of stride ldH (gs == nullptr, ldG == 0).
+// What every launch of a call shares: the model it named and that model's description (the other one is empty); base == nullptr: no
+// baseline, the kernels of the entry points that have none.
+enum ModelKind { kAr1, kAr2 };
 struct Args {
   const char* who;
   const void* y;
@@ -452,15 +395,13 @@ struct Args {
   long ld;
   int R;
   long T;
-  double g;
-  const double *gs, *G;
-  long ldG;
+  ModelKind model;
+  Ar1Args ar1;
+  Ar2Args ar2;
   const double *lam, *smin, *base;
   void* ws;
   int* pools;
   dc_stream_t stream;
-  double g2 = 0.0;
-  long ldH = 0;
 };
 
 // a flag of the call as a template argument of its kernel: launch(std::true_type()) or launch(std::false_type())
@@ -470,31 +411,30 @@ void with_flag(bool flag, F launch) {
   else launch(std::false_type());
 }
 
-// In, Each, Base and Ar2 of the forward and sweep kernels from the call: launch(In(), each, base, ar2), the last three as with_flag
-// gives them; the AR(2) model has no table per trace
+// where the kernels of the call take their model from: launch(from), an Ar1From<Each> or an Ar2From
+template <class F>
+void with_model_of(const Args& a, F launch) {
+  if (a.model == kAr2) launch(Ar2From{a.ar2});
+  else with_flag(a.ar1.ldG != 0, [&](auto each) { launch(Ar1From<decltype(each)::value>{a.ar1}); });
+}
+
+// In, the model and Base of the forward and sweep kernels from the call: launch(In(), from, base), base as with_flag gives it
 template <class F>
 void with_kernel_of(const Args& a, F launch) {
-  with_flag(a.base != nullptr, [&](auto base) {
-    auto typed = [&](auto each, auto ar2) {
-      if (a.is_f64) launch(double(), each, base, ar2);
-      else launch(float(), each, base, ar2);
-    };
-    if (a.ldH != 0) typed(std::false_type(), std::true_type());
-    else with_flag(a.ldG != 0, [&](auto each) { typed(each, std::false_type()); });
+  with_model_of(a, [&](auto from) {
+    with_flag(a.base != nullptr, [&](auto base) {
+      if (a.is_f64) launch(double(), from, base);
+      else launch(float(), from, base);
+    });
   });
 }
 
 int launch_forward(const Args& a) {
   const unsigned groups = (unsigned)(((long)a.R + kLanes - 1) / kLanes);                    // <= 2^25: no cap
-  with_kernel_of(a, [&](auto in, auto each, auto base, auto ar2) {
+  with_kernel_of(a, [&](auto in, auto from, auto base) {
     using In = decltype(in);
-    if constexpr (decltype(ar2)::value) {
-      hipLaunchKernelGGL((deconv_ar2_forward_kernel<In, decltype(base)::value>), dim3(groups), dim3(kLanes), 0, (hipStream_t)a.stream, (const In*)a.y,
-                         a.ld, a.R, a.T, a.g, a.g2, a.G, a.ldH, a.lam, a.smin, a.base, (double*)a.ws, a.pools);
-    } else {
-      hipLaunchKernelGGL((deconv_forward_kernel<In, decltype(each)::value, decltype(base)::value>), dim3(groups), dim3(kLanes), 0,
-                         (hipStream_t)a.stream, (const In*)a.y, a.ld, a.R, a.T, a.g, a.gs, a.G, a.ldG, a.lam, a.smin, a.base, (double*)a.ws, a.pools);
-    }
+    hipLaunchKernelGGL((deconv_forward_kernel<In, decltype(from), decltype(base)::value>), dim3(groups), dim3(kLanes), 0, (hipStream_t)a.stream,
+                       (const In*)a.y, a.ld, a.R, a.T, from, a.lam, a.smin, a.base, (double*)a.ws, a.pools);
   });
   DC_CHECK_LAUNCH(a.who);
   return DC_OK;
@@ -505,15 +445,10 @@ int launch_deconv(const Args& a, double* calcium, double* spikes) {
   const int rc = launch_forward(a);
   if (rc != DC_OK) return rc;
   const unsigned blocks = (unsigned)(((long)a.R * a.T + kFillThreads - 1) / kFillThreads);  // <= 2^23: no cap
-  if (a.ldH != 0) {
-    hipLaunchKernelGGL(deconv_ar2_fill_kernel, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)a.stream, (const double*)a.ws, a.pools, a.R, a.T,
-                       a.g, a.g2, a.G, a.ldH, calcium, spikes);
-  } else {
-    with_flag(a.ldG != 0, [&](auto each) {
-      hipLaunchKernelGGL(deconv_fill_kernel<decltype(each)::value>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)a.stream, (const double*)a.ws,
-                         a.pools, a.R, a.T, a.g, a.gs, a.G, a.ldG, calcium, spikes);
-    });
-  }
+  with_model_of(a, [&](auto from) {
+    hipLaunchKernelGGL(deconv_fill_kernel<decltype(from)>, dim3(blocks), dim3(kFillThreads), 0, (hipStream_t)a.stream, (const double*)a.ws, a.pools,
+                       a.R, a.T, from, calcium, spikes);
+  });
   DC_CHECK_LAUNCH(a.who);
   return DC_OK;
 }
@@ -521,13 +456,14 @@ int launch_deconv(const Args& a, double* calcium, double* spikes) {
 // the folds of the stacks in ws and what out.mode does with them
 int launch_sweep(const Args& a, const SweepOut& out) {
   const unsigned groups = (unsigned)(a.R < kSearchMaxGroups ? a.R : kSearchMaxGroups);
-  DC_REQUIRE(a.ldH == 0 || a.base == nullptr, DC_EUNSUP, "%s: the AR(2) sweep takes no baseline", a.who);
-  with_kernel_of(a, [&](auto in, auto each, auto base, auto ar2) {
+  DC_REQUIRE(a.model == kAr1 || a.base == nullptr, DC_EUNSUP, "%s: the AR(2) sweep takes no baseline", a.who);
+  with_kernel_of(a, [&](auto in, auto from, auto base) {
     using In = decltype(in);
-    constexpr bool kAr2 = decltype(ar2)::value, kBase = decltype(base)::value;
-    if constexpr (!(kAr2 && kBase)) {                               // refused above
-      hipLaunchKernelGGL((deconv_sweep_kernel<In, decltype(each)::value, kBase, kAr2>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)a.stream,
-                         (const In*)a.y, a.ld, a.R, a.T, a.G, kAr2 ? a.ldH : a.ldG, a.g, a.g2, (const double*)a.ws, a.pools, out);
+    using From = decltype(from);
+    constexpr bool kBase = decltype(base)::value;
+    if constexpr (kSweepExists<typename From::Model, kBase>) {      // else: refused above
+      hipLaunchKernelGGL((deconv_sweep_kernel<In, From, kBase>), dim3(groups), dim3(kSearchThreads), 0, (hipStream_t)a.stream, (const In*)a.y, a.ld,
+                         a.R, a.T, from, (const double*)a.ws, a.pools, out);
     }
   });
   DC_CHECK_LAUNCH(a.who);
@@ -619,23 +555,36 @@ int check_host_table(const char* who, int R, long T, const double* G) {
   return check_limits(who, R, T, G[1]);
 }
 
-// the decay and the table of trace r on the host: one table for all (ldG == 0) or row r; -> DC_OK where the row holds a decay
-int host_table(const char* who, const double* G, long ldG, int r, long T, const double** row, double* g) {
-  *row = G + (long)r * ldG;
-  DC_REQUIRE((*row)[0] == 1.0, DC_EINVAL, "%s: trace %d: G[0] = %g is not 1", who, r, (*row)[0]);
-  *g = (*row)[1];
-  DC_REQUIRE(*g > 0.0 && *g < 1.0, DC_EINVAL, "%s: trace %d: g = %g is outside (0, 1)", who, r, *g);
-  return DC_OK;
-}
+// the AR(1) model of trace r on the host: one table for all (ldG == 0) or row r; -> DC_OK where the row holds a decay
+struct HostAr1 {
+  const char* who;
+  const double* G;
+  long ldG;
+  int operator()(int r, DcAr1& m) const {
+    m.G = G + (long)r * ldG;
+    DC_REQUIRE(m.G[0] == 1.0, DC_EINVAL, "%s: trace %d: G[0] = %g is not 1", who, r, m.G[0]);
+    m.g = m.G[1];
+    DC_REQUIRE(m.g > 0.0 && m.g < 1.0, DC_EINVAL, "%s: trace %d: g = %g is outside (0, 1)", who, r, m.g);
+    return DC_OK;
+  }
+};
 
-// one trace of a host entry point: its row, decay and table, and the scratch of the header functions (T pools, T doubles twice)
-template <typename Row>
+// the AR(2) model of every trace: checked before the rows
+struct HostAr2 {
+  DcAr2 m;
+  int operator()(int, DcAr2& out) const {
+    out = m;
+    return DC_OK;
+  }
+};
+
+// one trace of a host entry point: its row and model, and the scratch of the header functions (T pools, T doubles twice)
+template <class Model, typename Row>
 struct HostTrace {
   int r;
   Row y;                                     // const float* or const double*
-  double g;
-  const double* G;
-  std::vector<DcPool>& pool;
+  Model m;
+  std::vector<typename Model::Pool>& pool;
   double* c;
   double* a;
 };
@@ -651,34 +600,25 @@ HostFit host_fit_found(int which, double p, double other, double b) {
   return {other, p, b};
 }
 
-// calcium, spikes and the pool count of one trace at `at`
-template <typename Row>
-void host_row(const HostTrace<Row>& h, long T, const HostFit& at, double* calcium, double* spikes, int* pools) {
-  const int32_t n = dc_base_forward_host(h.y, T, h.g, h.G, at.lam, at.smin, at.b, h.pool);
-  *pools = n;
-  dc_deconv_calcium_host(h.pool, n, h.G, calcium);
-  for (long t = 0; t < T; ++t) spikes[t] = 0.0;
-  for (int32_t i = 1; i < n; ++i) {
-    const int32_t t0 = h.pool[(size_t)i].t0;
-    spikes[t0] = dc_deconv_spike(calcium[t0], h.g, calcium[t0 - 1]);
-  }
-}
-
-// The rows of a host entry point; R, T >= 1.  fit(h), a generic lambda, gets trace h.r with its row as the type it has, does what
-// the entry point does before the outputs and returns what they are computed at.
-template <class F>
-int host_rows(const char* who, const void* y, int is_f64, long ld, int R, long T, const double* G, long ldG, double* calcium, double* spikes,
-              int* pools, F fit) {
-  std::vector<DcPool> pool((size_t)T);
+// The rows of a host entry point; R, T >= 1.  model_of(r, m) gives trace r its model or refuses it.  fit(h), a generic lambda, gets
+// trace h.r with its row as the type it has, does what the entry point does before the outputs and returns what they -- calcium,
+// spikes and the pool count -- are computed at.
+template <class Model, class Of, class F>
+int host_rows(const void* y, int is_f64, long ld, int R, long T, Of model_of, double* calcium, double* spikes, int* pools, F fit) {
+  std::vector<typename Model::Pool> pool((size_t)T);
   std::vector<double> scratch(2 * (size_t)T);
   for (int r = 0; r < R; ++r) {
-    const double* row_G;
-    double g;
-    const int rc = host_table(who, G, ldG, r, T, &row_G, &g);
+    Model m;
+    const int rc = model_of(r, m);
     if (rc != DC_OK) return rc;
+    double *c = calcium + (long)r * T, *s = spikes + (long)r * T;
     auto one = [&](auto row) {
-      const HostTrace<decltype(row)> h = {r, row, g, row_G, pool, scratch.data(), scratch.data() + T};
-      host_row(h, T, fit(h), calcium + (long)r * T, spikes + (long)r * T, pools + r);
+      const HostTrace<Model, decltype(row)> h = {r, row, m, pool, scratch.data(), scratch.data() + T};
+      const HostFit at = fit(h);
+      const int32_t n = dc_forward_host(row, T, m, at.lam, at.smin, at.b, pool);
+      pools[r] = n;
+      dc_calcium_host(pool, n, m, c);
+      dc_spikes_host(pool, n, m, T, c, s);
     };
     if (is_f64) one((const double*)y + (long)r * ld);
     else one((const float*)y + (long)r * ld);
@@ -703,7 +643,7 @@ extern "C" int dc_trace_deconv_ar1(const void* y, int is_f64, long ld, int R, lo
   if (rc != DC_OK) return rc;
   DC_REQUIRE(dc_aligned(7, G, lam, smin, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_deconv({who, y, is_f64, ld, R, T, g, nullptr, G, 0, lam, smin, nullptr, ws, pools, stream}, calcium, spikes);
+  return launch_deconv({who, y, is_f64, ld, R, T, kAr1, {g, nullptr, G, 0}, {}, lam, smin, nullptr, ws, pools, stream}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int R, long T, const double* g, const double* G, long ldG,
@@ -717,7 +657,7 @@ extern "C" int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int 
   if (rc != DC_OK) return rc;
   DC_REQUIRE(dc_aligned(7, g, G, lam, smin, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_deconv({who, y, is_f64, ld, R, T, 0.0, g, G, ldG, lam, smin, nullptr, ws, pools, stream}, calcium, spikes);
+  return launch_deconv({who, y, is_f64, ld, R, T, kAr1, {0.0, g, G, ldG}, {}, lam, smin, nullptr, ws, pools, stream}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int R, long T, const double* G, const double* lam,
@@ -732,7 +672,7 @@ extern "C" int dc_trace_deconv_ar1_host(const void* y, int is_f64, long ld, int 
   if (rc != DC_OK) return rc;
   rc = check_host_ranges(who, R, lam, smin, nullptr, nullptr, nullptr);
   if (rc != DC_OK) return rc;
-  return host_rows(who, y, is_f64, ld, R, T, G, 0, calcium, spikes, pools, [&](const auto& h) { return HostFit{lam[h.r], smin[h.r], 0.0}; });
+  return host_rows<DcAr1>(y, is_f64, ld, R, T, HostAr1{who, G, 0}, calcium, spikes, pools, [&](const auto& h) { return HostFit{lam[h.r], smin[h.r], 0.0}; });
 }
 
 // ---- the noise-constrained search --------------------------------------------------------------------------------------------------
@@ -754,7 +694,7 @@ extern "C" int dc_trace_deconv_ar1_constrained(const void* y, int is_f64, long l
                  dc_trace_aligned(y, is_f64),
              DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_constrained({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, nullptr, nullptr, nullptr, ws, pools, stream}, which, sigma, fixed_other,
+  return launch_constrained({who, y, is_f64, ld, R, T, kAr1, {g, gs, G, gs ? ldG : 0}, {}, nullptr, nullptr, nullptr, ws, pools, stream}, which, sigma, fixed_other,
                             rounds, {0, (double*)state, param, nullptr, rss, status, nullptr}, calcium, spikes);
 }
 
@@ -773,7 +713,7 @@ extern "C" int dc_trace_deconv_search_step(const void* y, int is_f64, long ld, i
   DC_REQUIRE(dc_aligned(7, G, ws, state, param, rss) && dc_aligned(3, pools, status) && dc_trace_aligned(y, is_f64), DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
   // the sweep only reads ws and pools
-  return launch_sweep({who, y, is_f64, ld, R, T, 0.0, nullptr, G, ldG, nullptr, nullptr, nullptr, const_cast<void*>(ws), const_cast<int*>(pools), stream},
+  return launch_sweep({who, y, is_f64, ld, R, T, kAr1, {0.0, nullptr, G, ldG}, {}, nullptr, nullptr, nullptr, const_cast<void*>(ws), const_cast<int*>(pools), stream},
                       {last ? DC_BASE_PASS_LAST : DC_BASE_PASS_B, (double*)state, param, nullptr, rss, status, nullptr});
 }
 
@@ -793,9 +733,9 @@ extern "C" int dc_trace_deconv_ar1_constrained_host(const void* y, int is_f64, l
   if (rc != DC_OK) return rc;
   rc = check_host_ranges(who, R, nullptr, nullptr, sigma, fixed_other, nullptr);
   if (rc != DC_OK) return rc;
-  return host_rows(who, y, is_f64, ld, R, T, G, 0, calcium, spikes, pools, [&](const auto& h) {
+  return host_rows<DcAr1>(y, is_f64, ld, R, T, HostAr1{who, G, 0}, calcium, spikes, pools, [&](const auto& h) {
     const int r = h.r;
-    dc_search_host(h.y, T, h.g, h.G, which, sigma[r], fixed_other[r], rounds, h.pool, h.c, param + r, rss + r, status + r);
+    dc_search_host(h.y, T, h.m, which, sigma[r], fixed_other[r], rounds, h.pool, h.c, param + r, rss + r, status + r);
     return host_fit_found(which, param[r], fixed_other[r], 0.0);
   });
 }
@@ -815,7 +755,7 @@ extern "C" int dc_trace_deconv_ar1_base(const void* y, int is_f64, long ld, int 
   DC_REQUIRE(dc_aligned(7, gs, G, lam, smin, base, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL,
              "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_deconv({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, lam, smin, base, ws, pools, stream}, calcium, spikes);
+  return launch_deconv({who, y, is_f64, ld, R, T, kAr1, {g, gs, G, gs ? ldG : 0}, {}, lam, smin, base, ws, pools, stream}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_fit_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
@@ -831,7 +771,7 @@ extern "C" int dc_trace_deconv_ar1_fit_base(const void* y, int is_f64, long ld, 
   DC_REQUIRE(dc_aligned(7, gs, G, lam, smin, ws, calcium, spikes, base) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL,
              "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_fit_base({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, lam, smin, base, ws, pools, stream}, rounds, base, calcium, spikes);
+  return launch_fit_base({who, y, is_f64, ld, R, T, kAr1, {g, gs, G, gs ? ldG : 0}, {}, lam, smin, base, ws, pools, stream}, rounds, base, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar1_constrained_base(const void* y, int is_f64, long ld, int R, long T, double g, const double* gs, const double* G,
@@ -851,7 +791,7 @@ extern "C" int dc_trace_deconv_ar1_constrained_base(const void* y, int is_f64, l
                  dc_trace_aligned(y, is_f64),
              DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_constrained({who, y, is_f64, ld, R, T, g, gs, G, gs ? ldG : 0, nullptr, nullptr, base, ws, pools, stream}, which, sigma, fixed_other,
+  return launch_constrained({who, y, is_f64, ld, R, T, kAr1, {g, gs, G, gs ? ldG : 0}, {}, nullptr, nullptr, base, ws, pools, stream}, which, sigma, fixed_other,
                             rounds, {0, (double*)state, param, base, rss, status, nullptr}, calcium, spikes);
 }
 
@@ -872,7 +812,7 @@ extern "C" int dc_trace_deconv_base_step(const void* y, int is_f64, long ld, int
              "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
   // the sweep only reads ws and pools
-  return launch_sweep({who, y, is_f64, ld, R, T, 0.0, nullptr, G, ldG, nullptr, nullptr, base, const_cast<void*>(ws), const_cast<int*>(pools), stream},
+  return launch_sweep({who, y, is_f64, ld, R, T, kAr1, {0.0, nullptr, G, ldG}, {}, nullptr, nullptr, base, const_cast<void*>(ws), const_cast<int*>(pools), stream},
                       {mode, (double*)state, param, base, rss, status, sums});
 }
 
@@ -892,9 +832,9 @@ extern "C" int dc_trace_deconv_ar1_fit_base_host(const void* y, int is_f64, long
   if (rc != DC_OK) return rc;
   rc = check_host_ranges(who, R, lam, smin, nullptr, nullptr, base);
   if (rc != DC_OK) return rc;
-  return host_rows(who, y, is_f64, ld, R, T, G, ldG, calcium, spikes, pools, [&](const auto& h) {
+  return host_rows<DcAr1>(y, is_f64, ld, R, T, HostAr1{who, G, ldG}, calcium, spikes, pools, [&](const auto& h) {
     const int r = h.r;
-    base[r] = dc_base_fit_host(h.y, T, h.g, h.G, lam[r], smin[r], base[r], rounds, h.pool, h.c, h.a);
+    base[r] = dc_base_fit_host(h.y, T, h.m.g, h.m.G, lam[r], smin[r], base[r], rounds, h.pool, h.c, h.a);
     return HostFit{lam[r], smin[r], base[r]};
   });
 }
@@ -917,9 +857,9 @@ extern "C" int dc_trace_deconv_ar1_constrained_base_host(const void* y, int is_f
   if (rc != DC_OK) return rc;
   rc = check_host_ranges(who, R, nullptr, nullptr, sigma, fixed_other, base);
   if (rc != DC_OK) return rc;
-  return host_rows(who, y, is_f64, ld, R, T, G, ldG, calcium, spikes, pools, [&](const auto& h) {
+  return host_rows<DcAr1>(y, is_f64, ld, R, T, HostAr1{who, G, ldG}, calcium, spikes, pools, [&](const auto& h) {
     const int r = h.r;
-    dc_base_search_host(h.y, T, h.g, h.G, which, sigma[r], fixed_other[r], base[r], rounds, h.pool, h.c, h.a, param + r, base + r, rss + r, status + r);
+    dc_base_search_host(h.y, T, h.m.g, h.m.G, which, sigma[r], fixed_other[r], base[r], rounds, h.pool, h.c, h.a, param + r, base + r, rss + r, status + r);
     return host_fit_found(which, param[r], fixed_other[r], base[r]);
   });
 }
@@ -938,26 +878,6 @@ int check_ar2(const char* who, int R, long T, double g1, double g2, long ldH) {
 int check_ar2_host_table(const char* who, double g1, const double* H, long ldH) {
   DC_REQUIRE(H[0] == 1.0 && H[1] == g1 && H[ldH] == 0.0 && H[2 * ldH] == 0.0, DC_EINVAL,
              "%s: the table does not begin with h = (1, g1), HH[0] = HP[0] = 0", who);
-  return DC_OK;
-}
-
-// The rows of an AR(2) host entry point; R, T >= 1.  fit(r, row, pool, c), a generic lambda, gets trace r with its row as the type
-// it has, does what the entry point does before the outputs and returns what they are computed at.
-template <class F>
-int host_rows_ar2(const void* y, int is_f64, long ld, int R, long T, const DcAr2& m, double* calcium, double* spikes, int* pools, F fit) {
-  std::vector<DcPool2> pool((size_t)T);
-  for (int r = 0; r < R; ++r) {
-    double* c = calcium + (long)r * T;
-    auto one = [&](auto row) {
-      const HostFit at = fit(r, row, pool, c);
-      const int32_t n = dc_ar2_forward_host(row, T, m, at.lam, at.smin, at.b, pool);
-      pools[r] = n;
-      dc_ar2_calcium_host(pool, n, m, c);
-      dc_ar2_spikes_host(pool, n, m, T, c, spikes + (long)r * T);
-    };
-    if (is_f64) one((const double*)y + (long)r * ld);
-    else one((const float*)y + (long)r * ld);
-  }
   return DC_OK;
 }
 
@@ -980,7 +900,7 @@ extern "C" int dc_trace_deconv_ar2(const void* y, int is_f64, long ld, int R, lo
   DC_REQUIRE(dc_aligned(7, H, lam, smin, base, ws, calcium, spikes) && dc_aligned(3, pools) && dc_trace_aligned(y, is_f64), DC_EINVAL,
              "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_deconv({who, y, is_f64, ld, R, T, g1, nullptr, H, 0, lam, smin, base, ws, pools, stream, g2, ldH}, calcium, spikes);
+  return launch_deconv({who, y, is_f64, ld, R, T, kAr2, {}, {g1, g2, H, ldH}, lam, smin, base, ws, pools, stream}, calcium, spikes);
 }
 
 extern "C" int dc_trace_deconv_ar2_host(const void* y, int is_f64, long ld, int R, long T, double g1, double g2, const double* H, long ldH,
@@ -999,8 +919,8 @@ extern "C" int dc_trace_deconv_ar2_host(const void* y, int is_f64, long ld, int 
   if (rc != DC_OK) return rc;
   rc = check_host_ranges(who, R, lam, smin, nullptr, nullptr, base);
   if (rc != DC_OK) return rc;
-  return host_rows_ar2(y, is_f64, ld, R, T, dc_ar2_model(g1, g2, H, ldH), calcium, spikes, pools,
-                       [&](int r, auto, std::vector<DcPool2>&, double*) { return HostFit{lam[r], smin[r], base ? base[r] : 0.0}; });
+  return host_rows<DcAr2>(y, is_f64, ld, R, T, HostAr2{dc_ar2_model(g1, g2, H, ldH)}, calcium, spikes, pools,
+                          [&](const auto& h) { return HostFit{lam[h.r], smin[h.r], base ? base[h.r] : 0.0}; });
 }
 
 extern "C" int dc_trace_deconv_ar2_constrained(const void* y, int is_f64, long ld, int R, long T, double g1, double g2, const double* H, long ldH,
@@ -1019,7 +939,7 @@ extern "C" int dc_trace_deconv_ar2_constrained(const void* y, int is_f64, long l
                  dc_trace_aligned(y, is_f64),
              DC_EINVAL, "%s: misaligned buffer", who);
   if (R == 0 || T == 0) return DC_OK;
-  return launch_constrained({who, y, is_f64, ld, R, T, g1, nullptr, H, 0, nullptr, nullptr, nullptr, ws, pools, stream, g2, ldH}, which, sigma,
+  return launch_constrained({who, y, is_f64, ld, R, T, kAr2, {}, {g1, g2, H, ldH}, nullptr, nullptr, nullptr, ws, pools, stream}, which, sigma,
                             fixed_other, rounds, {0, (double*)state, param, nullptr, rss, status, nullptr}, calcium, spikes);
 }
 
@@ -1041,9 +961,9 @@ extern "C" int dc_trace_deconv_ar2_constrained_host(const void* y, int is_f64, l
   if (rc != DC_OK) return rc;
   rc = check_host_ranges(who, R, nullptr, nullptr, sigma, fixed_other, nullptr);
   if (rc != DC_OK) return rc;
-  const DcAr2 m = dc_ar2_model(g1, g2, H, ldH);
-  return host_rows_ar2(y, is_f64, ld, R, T, m, calcium, spikes, pools, [&](int r, auto row, std::vector<DcPool2>& pool, double* c) {
-    dc_ar2_search_host(row, T, m, which, sigma[r], fixed_other[r], rounds, pool, c, param + r, rss + r, status + r);
+  return host_rows<DcAr2>(y, is_f64, ld, R, T, HostAr2{dc_ar2_model(g1, g2, H, ldH)}, calcium, spikes, pools, [&](const auto& h) {
+    const int r = h.r;
+    dc_search_host(h.y, T, h.m, which, sigma[r], fixed_other[r], rounds, h.pool, h.c, param + r, rss + r, status + r);
     return host_fit_found(which, param[r], fixed_other[r], 0.0);
   });
 }

@@ -6,17 +6,42 @@
 // for the device kernels, for the host entry points dc_trace_deconv_ar2_host and dc_trace_deconv_ar2_constrained_host and into a
 // stand-alone host program (tests/native/deconv_ar2_check.cpp, run under the address / undefined-behaviour sanitizers).  The
 // result is defined bit for bit: IEEE double operations in the order written here, the parentheses included.  No fused
-// multiply-add and no reassociation anywhere: the pragma below, and -ffp-contract=off for deconv.hip in _build.py.  The search is
-// the one of deconv_search_math.h, unchanged; only the residual it steps on is formed here.
+// multiply-add and no reassociation anywhere: the pragma below, and -ffp-contract=off for deconv.hip in _build.py.  There is no
+// host tail here: the forward pass, the outputs and the search of one trace are the templates of deconv_math.h and
+// deconv_search_math.h, which take this model as they take DcAr1.
 #pragma once
 #pragma clang fp contract(off)
 #include "deconv_search_math.h"
 
+// A pool: `l` consecutive frames from t0 on.  v is the fitted calcium at t0 and u the calcium at t0 - 1 (the last value of the
+// pool below, +0.0 for the lowest pool); A = sum_k h[k] x[t0+k] and B = sum_k h[k-1] x[t0+k] (k >= 1) are the data moments.
+struct DcPool2 {
+  double v, u, A, B;
+  int32_t t0, l;
+};
+
 // The model: the two coefficients and the three tables of T + 1 doubles each.  h[0] = 1, h[1] = g1, h[k] = g1 h[k-1] + g2 h[k-2]:
-// the response to one spike.  HH[l] = sum_{k<l} h[k] h[k] and HP[l] = sum_{1<=k<l} h[k] h[k-1], by running sums from +0.0.
+// the response to one spike.  HH[l] = sum_{k<l} h[k] h[k] and HP[l] = sum_{1<=k<l} h[k] h[k-1], by running sums from +0.0.  Its
+// members are those of DcAr1 (deconv_math.h), the names under which csrc/deconv.hip and the host drivers reach the functions below.
 struct DcAr2 {
+  typedef DcPool2 Pool;
+  static const int kPlanes = 4;
   double g1, g2;
   const double *h, *HH, *HP;
+  template <class P, class F>
+  DC_DECONV_HD static void words(P& p, F f) {
+    f(0, p.v);
+    f(1, p.u);
+    f(2, p.A);
+    f(3, p.B);
+  }
+  DC_DECONV_HD static double below(const DcPool2& p) { return p.u; }
+  DC_DECONV_HD double mu(double lam, long t, long T) const;
+  DC_DECONV_HD static DcPool2 fresh();
+  template <class Stack>
+  DC_DECONV_HD void push(DcPool2& top, int32_t& n, Stack& st, double x, long t, double smin) const;
+  DC_DECONV_HD double calc(double val, double below, int32_t k) const;
+  DC_DECONV_HD double spike(double c, const DcPool2& under) const;
 };
 
 // the rows of a (3, ldH) table as the entry points take it
@@ -32,13 +57,6 @@ DC_DECONV_HD DcAr2 dc_ar2_model(double g1, double g2, const double* H, long ldH)
 
 // two real roots inside (0, 1), not equal; a NaN fails
 DC_DECONV_HD bool dc_ar2_roots_ok(double g1, double g2) { return g2 < 0.0 && g1 > 0.0 && g1 + g2 < 1.0 && g1 * g1 + 4.0 * g2 > 0.0; }
-
-// A pool: `l` consecutive frames from t0 on.  v is the fitted calcium at t0 and u the calcium at t0 - 1 (the last value of the
-// pool below, +0.0 for the lowest pool); A = sum_k h[k] x[t0+k] and B = sum_k h[k-1] x[t0+k] (k >= 1) are the data moments.
-struct DcPool2 {
-  double v, u, A, B;
-  int32_t t0, l;
-};
 
 // what is subtracted from frame t of a trace of T frames: the L1 penalty lam on the spikes, written as a shift of the data
 DC_DECONV_HD double dc_ar2_mu(double lam, double g1, double g2, long t, long T) {
@@ -149,63 +167,14 @@ DC_DECONV_HD void dc_ar2_push(DcPool2& top, int32_t& n, Stack& st, double x, lon
   n = k + 1;
 }
 
-// ---- the host restatement: the host entry points and the stand-alone check -----------------------------------------------------------
-// (host functions: no attribute)
-struct DcHostStack2 {
-  std::vector<DcPool2>* pools;
-  DcPool2 load(int32_t i) const { return (*pools)[(size_t)i]; }
-  void store(int32_t i, const DcPool2& p) { (*pools)[(size_t)i] = p; }
-};
-
-// the forward pass of one trace of T >= 1 frames, the baseline b taken off every frame (b = +0.0: none, the same bits), into
-// pool[0 .. n), which needs T entries; -> n
-template <typename In>
-inline int32_t dc_ar2_forward_host(const In* y, long T, const DcAr2& m, double lam, double smin, double b, std::vector<DcPool2>& pool) {
-  DcHostStack2 st = {&pool};
-  DcPool2 top = dc_ar2_new(0.0, 0);
-  int32_t n = 0;
-  for (long t = 0; t < T; ++t) dc_ar2_push(top, n, st, dc_base_data((double)y[t], b) - dc_ar2_mu(lam, m.g1, m.g2, t, T), t, m, smin);
-  st.store(n - 1, top);
-  return n;
-}
-
-// the calcium of the stack pool[0 .. n) of a trace, frame by frame: c takes one double per frame
-inline void dc_ar2_calcium_host(const std::vector<DcPool2>& pool, int32_t n, const DcAr2& m, double* c) {
-  for (int32_t i = 0; i < n; ++i) {
-    const DcPool2& p = pool[(size_t)i];
-    for (int32_t k = 0; k < p.l; ++k) c[p.t0 + k] = dc_ar2_calc(m, p.v, p.u, k);
-  }
-}
-
-// the spikes of a trace of T frames whose calcium is c
-inline void dc_ar2_spikes_host(const std::vector<DcPool2>& pool, int32_t n, const DcAr2& m, long T, const double* c, double* s) {
-  for (long t = 0; t < T; ++t) s[t] = 0.0;
-  for (int32_t i = 1; i < n; ++i) {
-    double last, sec;
-    dc_ar2_tail(m, pool[(size_t)i - 1], last, sec);
-    const int32_t t0 = pool[(size_t)i].t0;
-    s[t0] = dc_ar2_spike(m, c[t0], last, sec);
-  }
-}
-
-// RSS of the stack pool[0 .. n): c is T doubles of scratch
-template <typename In>
-inline double dc_ar2_rss_host(const In* y, long T, const DcAr2& m, const std::vector<DcPool2>& pool, int32_t n, double* c) {
-  dc_ar2_calcium_host(pool, n, m, c);
-  return dc_dyn_fold_host([&](long t) { return dc_search_term((double)y[t], c[t]); }, T);
-}
-
-// The search of one trace, dc_search_host with this forward pass and this residual: round 0 and `rounds` more.
-template <typename In>
-inline void dc_ar2_search_host(const In* y, long T, const DcAr2& m, int which, double sigma, double other, int rounds, std::vector<DcPool2>& pool,
-                               double* c, double* param, double* rss, int32_t* status) {
-  DcSearch s = dc_search_begin(sigma, T);
-  double p = 0.0;
-  for (int round = 0; round <= rounds; ++round) {
-    const int32_t n = which == DC_SEARCH_LAM ? dc_ar2_forward_host(y, T, m, p, other, 0.0, pool) : dc_ar2_forward_host(y, T, m, other, p, 0.0, pool);
-    p = dc_search_step(s, p, dc_ar2_rss_host(y, T, m, pool, n, c));
-  }
-  *param = s.lo;
-  *rss = s.rss_lo;
-  *status = dc_search_status(s);
+// ---- the members of the model: the functions above under the names of DcAr1 ---------------------------------------------------------
+DC_DECONV_HD double DcAr2::mu(double lam, long t, long T) const { return dc_ar2_mu(lam, g1, g2, t, T); }
+DC_DECONV_HD DcPool2 DcAr2::fresh() { return dc_ar2_new(0.0, 0); }
+template <class Stack>
+DC_DECONV_HD void DcAr2::push(DcPool2& top, int32_t& n, Stack& st, double x, long t, double smin) const { dc_ar2_push(top, n, st, x, t, *this, smin); }
+DC_DECONV_HD double DcAr2::calc(double val, double below, int32_t k) const { return dc_ar2_calc(*this, val, below, k); }
+DC_DECONV_HD double DcAr2::spike(double c, const DcPool2& under) const {
+  double last, sec;
+  dc_ar2_tail(*this, under, last, sec);
+  return dc_ar2_spike(*this, c, last, sec);
 }

@@ -78,7 +78,7 @@ struct DcBaseSums {
 template <typename In>
 inline DcBaseSums dc_base_sums_host(const In* y, long T, const double* G, double b, const std::vector<DcPool>& pool, int32_t n, double* c, double* a) {
   const double g = G[1];
-  dc_deconv_calcium_host(pool, n, G, c);
+  dc_calcium_host(pool, n, DcAr1{g, G}, c);
   for (int32_t i = 0; i < n; ++i) {
     const DcPool& p = pool[(size_t)i];
     for (int32_t k = 0; k < p.l; ++k) a[p.t0 + k] = dc_base_gain_at(p.v, p.t0 + k, p.t0, g, G[p.l]);

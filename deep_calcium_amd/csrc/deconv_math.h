@@ -1,5 +1,6 @@
 // The arithmetic of the AR(1) deconvolution (include/dcunet.h, "Spikes by deconvolution"; csrc/deconv.hip): the push / merge step
-// of the pool stack, the two output formulas and, in a host-only tail, the forward pass of one trace.  Plain C++ like
+// of the pool stack, the two output formulas, the model DcAr1 that names them for the code written once over AR(1) and AR(2) and,
+// in a host-only tail, the forward pass and the outputs of one trace under either model.  Plain C++ like
 // footprint_math.h, so the same inline functions compile for the device kernels, for the host entry point dc_trace_deconv_ar1_host
 // and into a stand-alone host program (tests/native/deconv_math_check.cpp, run under the address / undefined-behaviour sanitizers).
 // The result is defined bit for bit:
@@ -93,25 +94,57 @@ DC_DECONV_HD double dc_deconv_calcium(double v, double Gk) {
 // the spike at the first frame of a pool that has a pool below it: c is its own calcium there, cprev the calcium one frame earlier
 DC_DECONV_HD double dc_deconv_spike(double c, double g, double cprev) { return c - g * cprev; }
 
-// ---- the host restatement: dc_trace_deconv_ar1_host, the search of deconv_search_math.h and the stand-alone checks -----------------
+// The model as the kernels, the stack views and the host drivers of csrc/deconv.hip take it -- DcAr2 of deconv_ar2_math.h gives the
+// same members --: the pool type, the planes of doubles its stacks take, and the arithmetic above under one set of names.
+struct DcAr1 {
+  typedef DcPool Pool;
+  static const int kPlanes = 2;
+  double g;                                  // the decay
+  const double* G;                           // G[k] = g^k, k = 0 .. T
+  // the doubles of a pool, in the order of its planes: f(plane, field)
+  template <class P, class F>
+  DC_DECONV_HD static void words(P& p, F f) {
+    f(0, p.v);
+    f(1, p.w);
+  }
+  DC_DECONV_HD double mu(double lam, long t, long T) const { return dc_deconv_mu(lam, g, t, T); }
+  DC_DECONV_HD static DcPool fresh() { return dc_deconv_new(0.0, 0); }
+  template <class Stack>
+  DC_DECONV_HD void push(DcPool& top, int32_t& n, Stack& st, double x, long t, double smin) const { dc_deconv_push(top, n, st, x, t, G, smin); }
+  // what calc takes beside a pool's value: nothing lies below an AR(1) pool
+  DC_DECONV_HD static double below(const DcPool&) { return 0.0; }
+  // calcium of frame t0 + k of a pool of value val
+  DC_DECONV_HD double calc(double val, double, int32_t k) const { return dc_deconv_calcium(val, G[k]); }
+  // the spike at the first frame of a pool whose calcium there is c, above the pool `under`
+  DC_DECONV_HD double spike(double c, const DcPool& under) const { return dc_deconv_spike(c, g, dc_deconv_calcium(under.v, G[under.l - 1])); }
+};
+
+// ---- the host restatement, over the model: the host entry points, the search of deconv_search_math.h and the stand-alone checks ----
 // (host functions: no attribute)
 #include <vector>
 
+template <class Pool>
 struct DcHostStack {
-  std::vector<DcPool>* pools;
-  DcPool load(int32_t i) const { return (*pools)[(size_t)i]; }
-  void store(int32_t i, const DcPool& p) { (*pools)[(size_t)i] = p; }
+  std::vector<Pool>* pools;
+  Pool load(int32_t i) const { return (*pools)[(size_t)i]; }
+  void store(int32_t i, const Pool& p) { (*pools)[(size_t)i] = p; }
 };
 
 // the forward pass of one trace of T >= 1 frames, the baseline b taken off every frame, into pool[0 .. n), which needs T entries; -> n
-template <typename In>
-inline int32_t dc_base_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, double b, std::vector<DcPool>& pool) {
-  DcHostStack st = {&pool};
-  DcPool top = dc_deconv_new(0.0, 0);
+template <class Model, typename In>
+inline int32_t dc_forward_host(const In* y, long T, const Model& m, double lam, double smin, double b, std::vector<typename Model::Pool>& pool) {
+  DcHostStack<typename Model::Pool> st = {&pool};
+  typename Model::Pool top = Model::fresh();
   int32_t n = 0;
-  for (long t = 0; t < T; ++t) dc_deconv_push(top, n, st, dc_base_data((double)y[t], b) - dc_deconv_mu(lam, g, t, T), t, G, smin);
+  for (long t = 0; t < T; ++t) m.push(top, n, st, dc_base_data((double)y[t], b) - m.mu(lam, t, T), t, smin);
   st.store(n - 1, top);
   return n;
+}
+
+// the AR(1) pass by its decay and table
+template <typename In>
+inline int32_t dc_base_forward_host(const In* y, long T, double g, const double* G, double lam, double smin, double b, std::vector<DcPool>& pool) {
+  return dc_forward_host(y, T, DcAr1{g, G}, lam, smin, b, pool);
 }
 
 // Without a baseline: b = +0.0 gives the same bits, because x - (+0.0) == x for every double x under round-to-nearest, -0.0 and the
@@ -122,9 +155,20 @@ inline int32_t dc_deconv_forward_host(const In* y, long T, double g, const doubl
 }
 
 // the calcium of the stack pool[0 .. n) of a trace, frame by frame: c takes one double per frame
-inline void dc_deconv_calcium_host(const std::vector<DcPool>& pool, int32_t n, const double* G, double* c) {
+template <class Model>
+inline void dc_calcium_host(const std::vector<typename Model::Pool>& pool, int32_t n, const Model& m, double* c) {
   for (int32_t i = 0; i < n; ++i) {
-    const DcPool& p = pool[(size_t)i];
-    for (int32_t k = 0; k < p.l; ++k) c[p.t0 + k] = dc_deconv_calcium(p.v, G[k]);
+    const typename Model::Pool& p = pool[(size_t)i];
+    for (int32_t k = 0; k < p.l; ++k) c[p.t0 + k] = m.calc(p.v, Model::below(p), k);
+  }
+}
+
+// the spikes of a trace of T frames whose calcium is c: one at the first frame of every pool but the lowest
+template <class Model>
+inline void dc_spikes_host(const std::vector<typename Model::Pool>& pool, int32_t n, const Model& m, long T, const double* c, double* s) {
+  for (long t = 0; t < T; ++t) s[t] = 0.0;
+  for (int32_t i = 1; i < n; ++i) {
+    const int32_t t0 = pool[(size_t)i].t0;
+    s[t0] = m.spike(c[t0], pool[(size_t)i - 1]);
   }
 }

@@ -2,8 +2,9 @@
 // residual term, the step that moves one trace's bracket, and the host restatement of the whole search.  Plain C++ like
 // deconv_math.h, which it builds on: the same inline functions compile for the device kernels of csrc/deconv.hip, for the host entry
 // point dc_trace_deconv_ar1_constrained_host and into a stand-alone host program (tests/native/deconv_search_check.cpp, run under
-// the address / undefined-behaviour sanitizers).  The host forward pass is deconv_math.h's, the fold of the residual the one of
-// trace_dyn_math.h.  Defined bit for bit: no fused multiply-add and no reassociation (the pragma below, and -ffp-contract=off for
+// the address / undefined-behaviour sanitizers).  There is one search: the step never sees the model, and the host loop is a
+// template over it (DcAr1 here, DcAr2 of deconv_ar2_math.h), as the sweep kernel is.  The host forward pass is deconv_math.h's,
+// the fold of the residual the one of trace_dyn_math.h.  Defined bit for bit: no fused multiply-add and no reassociation (the pragma below, and -ffp-contract=off for
 // deconv.hip in _build.py).
 #pragma once
 #pragma clang fp contract(off)
@@ -70,24 +71,24 @@ DC_DECONV_HD double dc_search_step(DcSearch& s, double p, double r) {
 // 0: bracketed; 1: p* = 0, the residual reaches the noise unconstrained; 2: never bracketed, the constraint is still slack at p*
 DC_DECONV_HD int32_t dc_search_status(const DcSearch& s) { return s.phase == DC_SEARCH_DONE ? 1 : s.phase == DC_SEARCH_EXPAND ? 2 : 0; }
 
-// ---- the host restatement: dc_trace_deconv_ar1_constrained_host and the stand-alone check ------------------------------------------
+// ---- the host restatement, over the model (DcAr1, DcAr2): the *_constrained_host entry points and the stand-alone checks ----------
 // (host functions: no attribute)
 // RSS of the stack pool[0 .. n): c is T doubles of scratch
-template <typename In>
-inline double dc_search_rss_host(const In* y, long T, const double* G, const std::vector<DcPool>& pool, int32_t n, double* c) {
-  dc_deconv_calcium_host(pool, n, G, c);
+template <class Model, typename In>
+inline double dc_rss_host(const In* y, long T, const Model& m, const std::vector<typename Model::Pool>& pool, int32_t n, double* c) {
+  dc_calcium_host(pool, n, m, c);
   return dc_dyn_fold_host([&](long t) { return dc_search_term((double)y[t], c[t]); }, T);
 }
 
 // The search of one trace: round 0 and `rounds` more.  -> p*, RSS(p*) and the status; pool needs T entries, c T doubles.
-template <typename In>
-inline void dc_search_host(const In* y, long T, double g, const double* G, int which, double sigma, double other, int rounds,
-                           std::vector<DcPool>& pool, double* c, double* param, double* rss, int32_t* status) {
+template <class Model, typename In>
+inline void dc_search_host(const In* y, long T, const Model& m, int which, double sigma, double other, int rounds,
+                           std::vector<typename Model::Pool>& pool, double* c, double* param, double* rss, int32_t* status) {
   DcSearch s = dc_search_begin(sigma, T);
   double p = 0.0;
   for (int round = 0; round <= rounds; ++round) {
-    const int32_t n = which == DC_SEARCH_LAM ? dc_deconv_forward_host(y, T, g, G, p, other, pool) : dc_deconv_forward_host(y, T, g, G, other, p, pool);
-    p = dc_search_step(s, p, dc_search_rss_host(y, T, G, pool, n, c));
+    const int32_t n = which == DC_SEARCH_LAM ? dc_forward_host(y, T, m, p, other, 0.0, pool) : dc_forward_host(y, T, m, other, p, 0.0, pool);
+    p = dc_search_step(s, p, dc_rss_host(y, T, m, pool, n, c));
   }
   *param = s.lo;
   *rss = s.rss_lo;

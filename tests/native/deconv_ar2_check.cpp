@@ -72,16 +72,16 @@ static void structural(double d, double r, long T) {
   std::vector<DcPool2> pool((size_t)T);
   std::vector<double> y((size_t)T), c((size_t)T), s((size_t)T);
   for (long t = 0; t < T; ++t) y[(size_t)t] = (double)t + 1.0;
-  int32_t n = dc_ar2_forward_host(y.data(), T, m, 0.0, 0.0, 0.0, pool);
+  int32_t n = dc_forward_host(y.data(), T, m, 0.0, 0.0, 0.0, pool);
   CHECK(n == T, "roots %g, %g: the ramp of %ld frames kept %d pools", d, r, T, n);
-  dc_ar2_calcium_host(pool, n, m, c.data());
-  dc_ar2_spikes_host(pool, n, m, T, c.data(), s.data());
+  dc_calcium_host(pool, n, m, c.data());
+  dc_spikes_host(pool, n, m, T, c.data(), s.data());
   for (long t = 0; t < T; ++t) CHECK(c[(size_t)t] == y[(size_t)t] && (t == 0 ? is_plus_zero(s[0]) : s[(size_t)t] > 0.0), "the ramp, frame %ld", t);
   for (long t = 0; t < T; ++t) y[(size_t)t] = -(double)t;
-  n = dc_ar2_forward_host(y.data(), T, m, 0.0, 0.0, 0.0, pool);
+  n = dc_forward_host(y.data(), T, m, 0.0, 0.0, 0.0, pool);
   CHECK(n == 1 && pool[0].t0 == 0 && pool[0].l == T, "roots %g, %g: -t of %ld frames ends as %d pools", d, r, T, n);
-  dc_ar2_calcium_host(pool, n, m, c.data());
-  dc_ar2_spikes_host(pool, n, m, T, c.data(), s.data());
+  dc_calcium_host(pool, n, m, c.data());
+  dc_spikes_host(pool, n, m, T, c.data(), s.data());
   for (long t = 0; t < T; ++t) CHECK(is_plus_zero(c[(size_t)t]) && is_plus_zero(s[(size_t)t]), "-t, frame %ld: %g, %g", t, c[(size_t)t], s[(size_t)t]);
 }
 
@@ -92,15 +92,15 @@ static void run_trace(const std::vector<In>& y, double d, double r, double lam, 
   const DcAr2 m = tab.model();
   std::vector<DcPool2> pool((size_t)T);
   std::vector<double> c((size_t)T), s((size_t)T), x((size_t)T);
-  const int32_t n = dc_ar2_forward_host(y.data(), T, m, lam, smin, b, pool);
+  const int32_t n = dc_forward_host(y.data(), T, m, lam, smin, b, pool);
   CHECK(n >= 1 && n <= T, "%s: %d pools of %ld frames", what, n, T);
   double top = 0.0;
   for (long t = 0; t < T; ++t) {
     x[(size_t)t] = dc_base_data((double)y[(size_t)t], b) - dc_ar2_mu(lam, m.g1, m.g2, t, T);
     top = fmax(top, fabs((double)y[(size_t)t]));
   }
-  dc_ar2_calcium_host(pool, n, m, c.data());
-  dc_ar2_spikes_host(pool, n, m, T, c.data(), s.data());
+  dc_calcium_host(pool, n, m, c.data());
+  dc_spikes_host(pool, n, m, T, c.data(), s.data());
   int32_t next = 0;
   for (int32_t i = 0; i < n; ++i) {
     const DcPool2& p = pool[(size_t)i];
@@ -134,11 +134,11 @@ static void run_search(const std::vector<In>& y, double d, double r, int which, 
   std::vector<double> c((size_t)T);
   double param = -1.0, rss = -1.0;
   int32_t status = -1;
-  dc_ar2_search_host(y.data(), T, m, which, sigma, other, rounds, pool, c.data(), &param, &rss, &status);
+  dc_search_host(y.data(), T, m, which, sigma, other, rounds, pool, c.data(), &param, &rss, &status);
   const double target = dc_search_target(sigma, T);
   auto at = [&](double p) {
-    const int32_t n = which == DC_SEARCH_LAM ? dc_ar2_forward_host(y.data(), T, m, p, other, 0.0, pool) : dc_ar2_forward_host(y.data(), T, m, other, p, 0.0, pool);
-    return dc_ar2_rss_host(y.data(), T, m, pool, n, c.data());
+    const int32_t n = which == DC_SEARCH_LAM ? dc_forward_host(y.data(), T, m, p, other, 0.0, pool) : dc_forward_host(y.data(), T, m, other, p, 0.0, pool);
+    return dc_rss_host(y.data(), T, m, pool, n, c.data());
   };
   const double r0 = at(0.0);
   CHECK(status >= 0 && status <= 2 && param >= 0.0 && at(param) == rss, "%s: status %d, p* = %g, RSS reported as %g", what, status, param, rss);

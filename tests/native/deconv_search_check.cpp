@@ -72,12 +72,12 @@ static void run_trace(const std::vector<In>& y, double g, int which, double sigm
   std::vector<double> c((size_t)T);
   double param = -1.0, rss = -1.0;
   int32_t status = -1;
-  dc_search_host(y.data(), T, g, G.data(), which, sigma, other, rounds, pool, c.data(), &param, &rss, &status);
+  dc_search_host(y.data(), T, DcAr1{g, G.data()}, which, sigma, other, rounds, pool, c.data(), &param, &rss, &status);
   const double target = dc_search_target(sigma, T);
   auto residual = [&](double p) {
     const int32_t n = which == DC_SEARCH_LAM ? dc_deconv_forward_host(y.data(), T, g, G.data(), p, other, pool)
                                              : dc_deconv_forward_host(y.data(), T, g, G.data(), other, p, pool);
-    return dc_search_rss_host(y.data(), T, G.data(), pool, n, c.data());
+    return dc_rss_host(y.data(), T, DcAr1{g, G.data()}, pool, n, c.data());
   };
   const double r0 = residual(0.0), again = residual(param);
   CHECK(status >= 0 && status <= 2 && param >= 0.0 && again == rss, "%s: status %d, p* = %g, RSS %g reported as %g", what, status, param, again, rss);
