@@ -34,7 +34,8 @@ _EXPORTS = {
     'weighted': ('WeightedTraceExtractor', 'weighted_traces_device', 'footprint_weights', 'exclude_overlap', 'roi_gram', 'demix_traces'),
     'dff': ('TraceBaseline', 'neuropil_rois', 'dff_traces_device'),
     'deconv': ('TraceDeconvolver', 'deconvolve_traces_device', 'ar1_gamma', 'ar1_table', 'ar2_table', 'trace_noise'),
-    'dynamics': ('TraceDynamics', 'estimate_ar1_device', 'ar1_tau', 'pick_gamma'),
+    'dynamics': ('TraceDynamics', 'estimate_ar1_device', 'ar1_tau', 'pick_gamma', 'TraceDynamicsAR2', 'estimate_ar2_device', 'ar2_roots',
+                 'pick_roots'),
     'motion': ('MotionCorrector', 'make_template', 'estimate_shifts_device', 'valid_rectangle', 'fine_to_pixels', 'BidiEstimator',
                'pick_bidi', 'estimate_bidi_device'),
     'spikes': ('UNet1DSegmentation', 'predict_spikes_device'),

@@ -9,6 +9,8 @@
 //   for the autocovariance a tile of 256 frames plus `lags` halo is staged into LDS as centred doubles: the lags + 1 shifted
 //     reads of a thread are consecutive 8-byte words (lane l reads word l + shift: 32 lanes cover the 64 banks once), and every
 //     thread keeps its lags + 1 lane sums in registers.
+// The AR(2) coefficients ("Trace dynamics: AR(2) coefficients") are an epilogue on the xc and the noise that launch wrote: one lane
+// per trace, a 2 x 2 least squares over lags rows.
 // No floating-point atomics; every output word is written by one thread.  Nothing here may be contracted or reassociated: the
 // pragma of trace_dyn_math.h and the per-file flag in _build.py.
 #pragma clang fp contract(off)
@@ -202,6 +204,19 @@ __global__ __launch_bounds__(kTabLanes) void ar1_tables_kernel(const double* __r
   }
 }
 
+// The per-trace epilogue of the AR(2) estimate: one lane per trace, which reads its lags + 1 covariances and its noise and writes
+// its two coefficients.  Beyond the capped grid a lane walks traces r, r + lanes, ...
+__global__ __launch_bounds__(kTabLanes) void trace_ar2_solve_kernel(const double* __restrict__ xc, int R, long T, int lags,
+                                                                    const double* __restrict__ sn, double* __restrict__ g12_raw) {
+  const long step = (long)gridDim.x * kTabLanes;
+  for (long r = (long)blockIdx.x * kTabLanes + threadIdx.x; r < R; r += step) {
+    double g1, g2;
+    dc_dyn_ar2_solve(xc + r * (lags + 1), lags, sn[r], T, &g1, &g2);
+    g12_raw[2 * r] = g1;
+    g12_raw[2 * r + 1] = g2;
+  }
+}
+
 // one matrix of traces: what every entry point that takes one refuses, in this order
 int check_traces(const char* who, const void* y, int is_f64, long ld, int R, long T) {
   const int rc = dc_trace_check_counts(who, y, is_f64, ld, R, T);
@@ -215,6 +230,15 @@ int check_estimate(const char* who, int lags, const double* sn, const double* si
   DC_REQUIRE(dc_aligned(7, sn, sigma, xc, g_raw), DC_EINVAL, "%s: misaligned buffer", who);
   DC_REQUIRE(lags >= 1 && lags <= DC_TRACE_DYN_MAX_LAGS, DC_EINVAL, "%s: lags = %d is outside [1, %d]", who, lags, DC_TRACE_DYN_MAX_LAGS);
   return DC_OK;
+}
+
+// what both entry points of the AR(2) solve refuse, in this order: they take no matrix of traces, only its counts
+int check_solve(const char* who, const double* xc, int R, long T, int lags, const double* sn, const double* g12_raw) {
+  DC_REQUIRE(xc && sn && g12_raw, DC_EINVAL, "%s: null pointer", who);
+  DC_REQUIRE(dc_aligned(7, xc, sn, g12_raw), DC_EINVAL, "%s: misaligned buffer", who);
+  DC_REQUIRE(lags >= 2 && lags <= DC_TRACE_DYN_MAX_LAGS, DC_EINVAL, "%s: lags = %d is outside [2, %d]", who, lags, DC_TRACE_DYN_MAX_LAGS);
+  DC_REQUIRE(R >= 0 && T >= 0, DC_EINVAL, "%s: negative count (R %d, T %ld)", who, R, T);
+  return dc_trace_check_limits(who, R, T);
 }
 
 unsigned groups_for(int R) { return (unsigned)(R < kGridCap ? R : kGridCap); }
@@ -293,5 +317,25 @@ extern "C" int dc_trace_ar1_estimate_host(const void* y, int is_f64, long ld, in
     if (sigma) sigma[r] = noise;
     g_raw[r] = dc_dyn_decay(cov, lags, sn ? sn[r] : noise, T);
   }
+  return DC_OK;
+}
+
+extern "C" int dc_trace_ar2_solve(const double* xc, int R, long T, int lags, const double* sn, double* g12_raw, dc_stream_t stream) {
+  const char* who = "dc_trace_ar2_solve";
+  const int rc = check_solve(who, xc, R, T, lags, sn, g12_raw);
+  if (rc != DC_OK) return rc;
+  if (R == 0) return DC_OK;
+  const long want = ((long)R + kTabLanes - 1) / kTabLanes;
+  const unsigned groups = (unsigned)(want < kGridCap ? want : kGridCap);
+  hipLaunchKernelGGL(trace_ar2_solve_kernel, dim3(groups), dim3(kTabLanes), 0, (hipStream_t)stream, xc, R, T, lags, sn, g12_raw);
+  DC_CHECK_LAUNCH(who);
+  return DC_OK;
+}
+
+extern "C" int dc_trace_ar2_solve_host(const double* xc, int R, long T, int lags, const double* sn, double* g12_raw) {
+  const char* who = "dc_trace_ar2_solve_host";
+  const int rc = check_solve(who, xc, R, T, lags, sn, g12_raw);
+  if (rc != DC_OK) return rc;
+  for (long r = 0; r < R; ++r) dc_dyn_ar2_solve(xc + r * (lags + 1), lags, sn[r], T, g12_raw + 2 * r, g12_raw + 2 * r + 1);
   return DC_OK;
 }

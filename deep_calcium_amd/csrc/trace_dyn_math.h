@@ -1,5 +1,6 @@
 // The arithmetic of the trace dynamics (include/dcunet.h, "Trace dynamics: noise and AR(1) decay"; csrc/trace_dyn.hip): the robust
-// noise of a trace from its first difference, the fixed-order fold, the autocovariance and the least-squares decay.  Plain C++
+// noise of a trace from its first difference, the fixed-order fold, the autocovariance, the least-squares decay and the
+// least-squares AR(2) coefficients ("Trace dynamics: AR(2) coefficients"; tests/native/trace_dyn_ar2_check.cpp).  Plain C++
 // like deconv_math.h, so the same inline functions compile for the device kernels, for the host entry point
 // dc_trace_ar1_estimate_host and into a stand-alone host program (tests/native/trace_dyn_math_check.cpp, run under the address /
 // undefined-behaviour sanitizers).  The results are defined bit for bit: the noise by VALUE (medians: any selection algorithm gives
@@ -59,6 +60,33 @@ DC_DYN_HD double dc_dyn_decay(const double* xc, int lags, double sn, long T) {
   if (T < (long)lags + 2 || den == 0.0) return NAN;
   const double q = num / den;
   return isfinite(q) ? q : NAN;
+}
+
+// (g1_raw, g2_raw) from xc[0 .. lags], lags >= 2: least squares of y_i = xc[i+1] on the two columns a and b of
+// toeplitz(xc[0 .. lags-1], xc[0 .. 1]) - sn^2 I, rows i = 0 .. lags-1; the five sums are left folds from +0.0 over ascending i,
+// the 2 x 2 system is solved by its determinant.  No roots are taken here.  Both NaN where the estimate is undefined:
+// T < lags + 2, a determinant that is not positive (NaN included), a quotient that is not finite.
+DC_DYN_HD void dc_dyn_ar2_solve(const double* xc, int lags, double sn, long T, double* g1_raw, double* g2_raw) {
+  const double c0 = xc[0] - sn * sn;
+  double Saa = 0.0, Sab = 0.0, Sbb = 0.0, Say = 0.0, Sby = 0.0;
+  for (int i = 0; i < lags; ++i) {
+    const double a = i == 0 ? c0 : xc[i];
+    const double b = i == 0 ? xc[1] : i == 1 ? c0 : xc[i - 1];
+    const double y = xc[i + 1];
+    Saa = Saa + a * a;
+    Sab = Sab + a * b;
+    Sbb = Sbb + b * b;
+    Say = Say + a * y;
+    Sby = Sby + b * y;
+  }
+  const double det = Saa * Sbb - Sab * Sab;
+  *g1_raw = *g2_raw = NAN;
+  if (T < (long)lags + 2 || !(det > 0.0)) return;
+  const double g1 = (Say * Sbb - Sby * Sab) / det;
+  const double g2 = (Saa * Sby - Sab * Say) / det;
+  if (!isfinite(g1) || !isfinite(g2)) return;
+  *g1_raw = g1;
+  *g2_raw = g2;
 }
 
 // ---- the host restatement: dc_trace_ar1_estimate_host and the stand-alone check ---------------------------------------------------

@@ -54,8 +54,11 @@ baseline='fit' and a decay per trace; the greedy pass is feasible but, unlike AR
 
     dec = TraceDeconvolver(dff_dev, ar1_gamma(1.0, 30.0), rise=ar1_gamma(0.1, 30.0), constrain='s_min')
     c, s = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau=1.0, tau_rise=0.1, fps=30.0, k='noise')
+    c, s = deconvolve_traces_device('dataset.hdf5', rois, window=1801, tau='auto', tau_rise='auto', k='noise')   # both roots estimated
 
-Not built: estimating the rise, fitting the baseline under AR(2), a pair of roots per trace, complex or equal roots, OASIS's
+(deep_calcium_amd.dynamics: TraceDynamicsAR2 and pick_roots estimate the pair of roots from the traces and pool it.)
+
+Not built: fitting the baseline under AR(2), a pair of roots per trace, complex or equal roots, OASIS's
 corrective passes; optimising g by the residual, a time-varying baseline; for the search: both parameters at once, a warm start,
 the closed-form lam update of OASIS, a joint search over g.
 
@@ -435,7 +438,7 @@ class TraceDeconvolver(_MatrixStage):
 
 
 def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0, details=False, lags=5, g_min=0.05, g_max=0.998, baseline=0.0,
-                             tau_rise=None, **dff_kw):
+                             tau_rise=None, rise_lags=10, **dff_kw):
     """-> (calcium, spikes), float64 (R, T): the dF/F traces of `rois` over a dataset file (dff_traces_device(dspath, rois, window,
     **dff_kw)) deconvolved with s_min = k * sigma_hat per trace and the penalty lam.  tau: a number -- the decay time in seconds,
     g = ar1_gamma(tau, fps) --, 'auto' -- the decay is estimated per trace from the dF/F (deep_calcium_amd.dynamics: TraceDynamics
@@ -450,12 +453,30 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
     above zero when the cell is quiet, which the search alone pays for with spurious events.  With a numeric k the fit is only as
     good as the threshold (one that is too high lets missed events lift the baseline).  tau_rise: the rise time in seconds of an
     AR(2) model, rise = ar1_gamma(tau_rise, fps) (TraceDeconvolver(rise=)); it needs a numeric tau above it, and baseline='fit' is
-    not built for it; info then also has rise=."""
+    not built for it; info then also has rise=.  tau='auto' with tau_rise='auto': both roots are estimated from the dF/F
+    (deep_calcium_amd.dynamics: TraceDynamicsAR2 with `rise_lags`, then pick_roots with d_max = g_max) and the pooled pair serves
+    all traces; info then has g= and rise= the pooled roots, pooled=(g, rise), g12_raw=, root_status= what pick_roots gave, and
+    g_raw= the AR(1) estimates at these lags (status= is None).  With no trace of two usable roots it is a ValueError: give tau
+    and tau_rise."""
     mode = tau if isinstance(tau, str) else None
     if mode is not None and mode not in ('auto', 'each'):
         raise ValueError("tau must be a number of seconds, 'auto' or 'each', not %r" % (tau,))
-    rise = None
-    if tau_rise is not None:
+    rise, rise_auto = None, False
+    if isinstance(tau_rise, str):                                    # both roots estimated: the decay and the rise, pooled
+        if tau_rise != 'auto':
+            raise ValueError("tau_rise must be a number of seconds or 'auto', not %r" % (tau_rise,))
+        if mode != 'auto':
+            raise ValueError("tau_rise='auto' estimates both roots, pooled over the traces: it needs tau='auto', not tau=%r (a given "
+                             'decay beside an estimated rise, and roots per trace, are not built)' % (tau,))
+        if isinstance(baseline, str) and baseline == 'fit':
+            raise ValueError("baseline='fit' is not built for AR(2) (tau_rise=)")
+        from .dynamics import _check_lags
+        try:
+            _check_lags(rise_lags, 2)
+        except ValueError as e:
+            raise ValueError('rise_%s' % e)
+        rise_auto = True
+    elif tau_rise is not None:
         if mode is not None:
             raise ValueError('tau_rise needs a number of seconds for tau: estimating the decay (tau=%r) is not built for AR(2)' % (tau,))
         if isinstance(baseline, str) and baseline == 'fit':
@@ -500,6 +521,18 @@ def deconvolve_traces_device(dspath, rois, window, tau, fps=None, k=3.0, lam=0.0
         info = dict(g=g, g_raw=None, status=None, sigma=sigma, pooled=None)
         if rise is not None:
             info['rise'] = rise
+    elif rise_auto:
+        from .dynamics import TraceDynamicsAR2, pick_roots
+        dyn = TraceDynamicsAR2(dff, lags=rise_lags, device=dff_kw.get('device'))
+        sigma, g12_raw = dyn.result('noise'), dyn.result('g12_raw')
+        _, root_status, (g, rise) = pick_roots(g12_raw, d_max=g_max)
+        if search:
+            dec = TraceDeconvolver(dyn.traces_device, g, lam=lam, constrain='s_min', sigma=dyn.result_device('noise'), device=dyn.device,
+                                   baseline=baseline, rise=rise)
+        else:
+            dec = TraceDeconvolver(dyn.traces_device, g, s_min=k * sigma, lam=lam, device=dyn.device, baseline=baseline, rise=rise)
+        info = dict(g=g, rise=rise, g_raw=dyn.result('g_raw'), status=None, sigma=sigma, pooled=(g, rise), g12_raw=g12_raw,
+                    root_status=root_status)
     else:
         from .dynamics import TraceDynamics
         dyn = TraceDynamics(dff, lags=lags, device=dff_kw.get('device'))

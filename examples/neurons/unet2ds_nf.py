@@ -35,7 +35,7 @@ from deep_calcium_amd import (UNet2DSummary, parallel, extract_traces_device, wr
                               estimate_shifts_device, estimate_bidi_device, summarize_series_device, valid_rectangle, dff_traces_device, roi_footprints_device, refine_rois,
                               split_rois_device, detrend_plan, merge_rois_device, make_template, frame_quality_device, flag_frames,
                               footprint_weights, exclude_overlap, weighted_traces_device, TraceDeconvolver, ar1_gamma, trace_noise,
-                              TraceDynamics, pick_gamma, ar1_tau)
+                              TraceDynamics, pick_gamma, ar1_tau, TraceDynamicsAR2, pick_roots)
 from deep_calcium_amd.weighted import shared_pixels            # noqa: E402
 from deep_calcium_amd.deconv import ar2_coefficients, ar2_peak   # noqa: E402
 from deep_calcium_amd.nf_metrics import nf_submit                # noqa: E402
@@ -135,6 +135,16 @@ def _deconvolve_arg(text):
         raise argparse.ArgumentTypeError('expected auto, each or the decay time TAU in seconds, not %r' % text)
 
 
+def _rise_arg(text):
+    """'auto' | a rise time in seconds."""
+    if text == 'auto':
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected auto or the rise time TAU_RISE in seconds, not %r' % text)
+
+
 def _baseline_arg(text):
     """'fit' | a constant."""
     if text == 'fit':
@@ -217,7 +227,9 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
     off every trace.  spike_rise=TAU_RISE (with deconvolve=TAU, not auto or each, and not with spike_baseline='fit'): the indicator's
     rise time in seconds; the model is then AR(2) with the roots exp(-1 / (TAU F)) and exp(-1 / (TAU_RISE F))
     (TraceDeconvolver(rise=)), which keeps an event whose fluorescence takes several frames to peak from being reported as a run
-    of spikes."""
+    of spikes.  spike_rise='auto' (with deconvolve='auto'): both roots are estimated from the dF/F (deep_calcium_amd.TraceDynamicsAR2,
+    pick_roots: the coefficients per trace, the medians of decay and rise over the traces that give two real roots in (0, 1)) and
+    the pooled pair serves all traces."""
     logger = logging.getLogger('traces')
     if blocks is not None and register is None:
         raise ValueError('--blocks needs --register')
@@ -254,7 +266,14 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         raise ValueError('--spike-k is the smallest spike in units of the trace noise, K >= 0, not %r' % (spike_k,))
     g = None if deconvolve is None or estimated else ar1_gamma(deconvolve, fps)
     rise = None
-    if spike_rise is not None:
+    if isinstance(spike_rise, str):
+        if spike_rise != 'auto':
+            raise ValueError('--spike-rise takes auto or the rise time TAU_RISE in seconds, not %r' % (spike_rise,))
+        if deconvolve != 'auto':
+            raise ValueError('--spike-rise auto estimates both roots, pooled over the traces: it needs --deconvolve auto')
+        if spike_baseline == 'fit':
+            raise ValueError('--spike-baseline fit is not built for AR(2) (--spike-rise)')
+    elif spike_rise is not None:
         if g is None:
             raise ValueError('--spike-rise needs --deconvolve TAU: estimating the decay (auto, each) is not built for AR(2)')
         if spike_baseline == 'fit':
@@ -411,7 +430,27 @@ def traces(dataset_name, model_path, checkpoints_dir, kind='mean', register=None
         else:
             tr = extract_traces_device(dspath, mask, kind=kind, **moves(dspath))
         extra = None
-        if estimated:
+        if spike_rise == 'auto':
+            dyn = TraceDynamicsAR2(tr)
+            sigma = dyn.result('noise')
+            _, status, (g_pool, r_pool) = pick_roots(dyn.result('g12_raw'))
+            if spike_constrain is not None:
+                dec = TraceDeconvolver(dyn.traces_device, g_pool, rise=r_pool, constrain=spike_constrain, sigma=dyn.result_device('noise'), **base_kw)
+            else:
+                dec = TraceDeconvolver(dyn.traces_device, g_pool, rise=r_pool, s_min=spike_k * sigma, **base_kw)
+            extra = dict(calcium=dec.result('calcium'), deconvolved=dec.result('spikes'))
+            events = (extra['deconvolved'] > 0).sum(1)
+            g1, g2 = ar2_coefficients(g_pool, r_pool)
+            logger.info('%s: decay and rise estimated from the traces (--deconvolve auto --spike-rise auto, %d lags): pooled d = %.6f, r = %.6f%s, '
+                        'g1 = %.6f, g2 = %.6f; the response to one spike peaks at frame %d; status fine / complex / no rise / too slow / '
+                        'undefined = %d / %d / %d / %d / %d; s_min = %g sigma_hat, median sigma_hat %.4g: events per ROI min / median / max = '
+                        '%d / %g / %d' % (
+                            name, dyn.lags, g_pool, r_pool,
+                            '' if fps is None else ' (tau %.4g s, tau_rise %.4g s at %g frames/s)' % (ar1_tau(g_pool, fps), ar1_tau(r_pool, fps), fps),
+                            g1, g2, ar2_peak(g_pool, r_pool), int((status == 0).sum()), int((status == 1).sum()), int((status == 2).sum()),
+                            int((status == 3).sum()), int((status == 4).sum()), 0.0 if spike_constrain == 'lam' else spike_k,
+                            float(np.median(sigma)), int(events.min()), float(np.median(events)), int(events.max())))
+        elif estimated:
             dyn = TraceDynamics(tr)
             sigma = dyn.result('noise')
             g_each, status, g_pool = pick_gamma(dyn.result('g_raw'))
@@ -512,7 +551,8 @@ if __name__ == '__main__':
     sp_trc.add_argument('--spike-k', help='with --deconvolve: the smallest spike allowed, in units of every trace\'s noise (default 3)', default=3.0,
                         type=float, metavar='K', dest='spike_k')
     sp_trc.add_argument('--spike-rise', help='with --deconvolve TAU: the rise time of the indicator in seconds; the model is then AR(2), with the '
-                        'roots exp(-1 / (TAU F)) and exp(-1 / (TAU_RISE F))', default=None, type=float, metavar='TAU_RISE', dest='spike_rise')
+                        'roots exp(-1 / (TAU F)) and exp(-1 / (TAU_RISE F)); auto (with --deconvolve auto): both roots are estimated from the '
+                        'traces and the pooled pair serves all', default=None, type=_rise_arg, metavar='auto|TAU_RISE', dest='spike_rise')
     sp_trc.add_argument('--spike-constrain', help='with --deconvolve, instead of --spike-k: search s_min (for events) or lam (for a denoised calcium) '
                         'per trace until the residual equals the trace noise', default=None, choices=('s_min', 'lam'), dest='spike_constrain')
     sp_trc.add_argument('--spike-baseline', help='with --deconvolve: fit one constant per trace inside the deconvolution (fit; recommended with '
@@ -551,7 +591,12 @@ if __name__ == '__main__':
         ap.error('--deconvolve needs --dff: the deconvolution has no baseline term')
     if args['which'] == 'traces' and args['deconvolve'] is not None and not isinstance(args['deconvolve'], str) and args['fps'] is None:
         ap.error('--deconvolve needs --fps')
-    if args['which'] == 'traces' and args['spike_rise'] is not None:
+    if args['which'] == 'traces' and args['spike_rise'] == 'auto':
+        if args['deconvolve'] != 'auto':
+            ap.error('--spike-rise auto estimates both roots, pooled over the traces: it needs --deconvolve auto')
+        if args['spike_baseline'] == 'fit':
+            ap.error('--spike-baseline fit is not built for AR(2) (--spike-rise)')
+    elif args['which'] == 'traces' and args['spike_rise'] is not None:
         if args['deconvolve'] is None or isinstance(args['deconvolve'], str):
             ap.error('--spike-rise needs --deconvolve TAU: estimating the decay (auto, each) is not built for AR(2)')
         if args['spike_baseline'] == 'fit':

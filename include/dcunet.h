@@ -36,7 +36,7 @@ typedef void* dc_stream_t;
 
 /* ABI revision: dc_version() of the loaded library must EQUAL the DC_ABI_VERSION of the header the caller was built /
  * bound against (argument lists change between revisions; the Python binding refuses a mismatch). */
-#define DC_ABI_VERSION 131
+#define DC_ABI_VERSION 132
 int dc_version(void);
 const char* dc_last_error(void);
 
@@ -1042,9 +1042,9 @@ int dc_trace_deconv_ar1_constrained_base_host(const void* y, int is_f64, long ld
  *   dc_trace_deconv_ar2_host, dc_trace_deconv_ar2_constrained_host: the same arithmetic (the same header) compiled for the host,
  *     over HOST pointers, one trace after the other on the calling thread.  What is read is checked (-1), the first entries of the
  *     table included.
- * Not built: estimating r, or (g1, g2), from the autocovariance; fitting the baseline under AR(2) (A of "A baseline in the
- * deconvolution" has no AR(2) form yet); a pair of roots per trace; complex or equal roots; OASIS's corrective passes towards the
- * exact optimum. */
+ * (g1, g2) from the traces themselves: "Trace dynamics: AR(2) coefficients" below.
+ * Not built: fitting the baseline under AR(2) (A of "A baseline in the deconvolution" has no AR(2) form yet); a pair of roots per
+ * trace; complex or equal roots; OASIS's corrective passes towards the exact optimum. */
 long dc_trace_deconv_ar2_ws_bytes(int R, long T);
 int dc_trace_deconv_ar2(const void* y, int is_f64, long ld, int R, long T, double g1, double g2, const double* H, long ldH, const double* lam,
                         const double* smin, const double* base, void* ws, double* calcium, double* spikes, int* pools, dc_stream_t stream);
@@ -1093,8 +1093,8 @@ int dc_trace_deconv_ar2_constrained_host(const void* y, int is_f64, long ld, int
  *     call.  The speed baseline, and the bit-for-bit check of the library against the oracle on a machine without a GPU.
  * Limits as for the deconvolution: T > 2^24 or R * T > 2^31: DC_EUNSUP (-3).  A null or misaligned pointer (8 bytes; 4 for
  * float32 y), ld < T, a negative count, lags outside [1, 16]: -1.  R == 0 or T == 0: 0, nothing launched (dc_ar1_tables: R == 0).
- * Not built: AR(2); refining g by the deconvolution residual; noise from the power spectrum; per-segment estimates; weights on
- * the lags. */
+ * Not built: refining g by the deconvolution residual; noise from the power spectrum; per-segment estimates; weights on
+ * the lags.  AR(2): the next section. */
 #define DC_TRACE_DYN_LANES 256
 #define DC_TRACE_DYN_MAX_LAGS 16
 #define DC_TRACE_DYN_MAX_GROUPS 8192
@@ -1107,6 +1107,31 @@ int dc_trace_deconv_ar1_each(const void* y, int is_f64, long ld, int R, long T, 
                              dc_stream_t stream);
 int dc_trace_ar1_estimate_host(const void* y, int is_f64, long ld, int R, long T, int lags, const double* sn, double* sigma, double* xc,
                                double* g_raw);
+
+/* ---- Trace dynamics: AR(2) coefficients ----------------------------------------------------------------------------------------
+ * The two parameters of "A rise time in the deconvolution" from the traces themselves: CaImAn's estimate_time_constant(p = 2), a
+ * least squares in two unknowns on the autocovariance, the noise removed on the diagonal.  The O(R T) work -- the two medians and
+ * the lags + 1 folds -- is dc_trace_ar1_estimate above, unchanged; this is the per-trace epilogue on what it wrote.  THESE
+ * DEFINITIONS ARE THE SPECIFICATION (csrc/trace_dyn_math.h, dc_dyn_ar2_solve: IEEE doubles, no fused multiply-add, this order).
+ *   with c0 = xc_0 - sn * sn, rows i = 0 .. lags - 1:  a_i = (i == 0 ? c0 : xc_i),  b_i = (i == 0 ? xc_1 : i == 1 ? c0 : xc_(i-1)),
+ *     y_i = xc_(i+1) -- toeplitz(xc[0 .. lags-1], xc[0 .. 1]) - sn^2 I, regressed on xc[1 .. lags];
+ *   five left folds from +0.0 over ascending i: Saa += a_i * a_i, Sab += a_i * b_i, Sbb += b_i * b_i, Say += a_i * y_i,
+ *     Sby += b_i * y_i;
+ *   det = Saa * Sbb - Sab * Sab,  g1_raw = (Say * Sbb - Sby * Sab) / det,  g2_raw = (Saa * Sby - Sab * Say) / det.
+ *   Both are NaN (undefined) when T < lags + 2, when !(det > 0.0) or when either quotient is not finite.  Nothing is clamped and
+ *   no roots are taken: the roots d, r = (g1 +- sqrt(g1 * g1 + 4 g2)) / 2, which of them are usable and their pooling over the
+ *   traces are the caller's (deep_calcium_amd.ar2_roots, pick_roots).
+ *   dc_trace_ar2_solve: xc = double (R, lags + 1) dense, exactly as dc_trace_ar1_estimate writes it; sn = double[R], the sigma the
+ *     same launch wrote or the caller's own; g12_raw = double (R, 2) dense.  All DEVICE memory; T is the length of the traces xc
+ *     came from (it only decides whether the estimate is defined).  One lane per trace, 64 to a workgroup, at most
+ *     DC_TRACE_DYN_MAX_GROUPS workgroups: beyond, a lane walks several traces.  Every output word is written by one thread.
+ *   dc_trace_ar2_solve_host: the same function compiled for the host, over HOST pointers.
+ * lags in [2, DC_TRACE_DYN_MAX_LAGS].  A null or misaligned pointer (8 bytes), lags outside [2, 16], a negative count: -1; the
+ * limits of the deconvolution (T > 2^24, R * T > 2^31): -3.  R == 0: 0, nothing launched.
+ * Not built: roots per trace in the deconvolution (one pooled pair serves all traces); complex or equal roots; per-segment
+ * estimates; weights on the lags; fitting the baseline under AR(2). */
+int dc_trace_ar2_solve(const double* xc, int R, long T, int lags, const double* sn, double* g12_raw, dc_stream_t stream);
+int dc_trace_ar2_solve_host(const double* xc, int R, long T, int lags, const double* sn, double* g12_raw);
 
 /* ---- rigid motion correction: register the frames of a recording to a template ------------------------------------------------
  * Every stage above assumes registered frames (Neurofinder's are; the recordings of the reference's other example,
